@@ -49,7 +49,8 @@ N > 1 (one rank per GPU): every chain also hands its markets' compact records (n
 its OWN all-gather on its OWN stream and communicator and rebuilds the learner-side arrays there (parallel.py); the timed
 region contains all of it.
 
-Prints ONE JSON line on rank 0; see the fields `roofline` and `cpu_baseline` in DESIGN.md.
+Prints ONE JSON line on rank 0; see the fields `roofline` and `cpu_baseline` in DESIGN.md.  `--dump-outputs DIR` also writes what the timed path
+computed in its last step (dump_outputs; the inputs are seeded, so two builds can be compared output for output).
 """
 import argparse
 import datetime
@@ -72,13 +73,15 @@ PG_TIMEOUT = datetime.timedelta(seconds=240)      # a collective that never comp
 ACTION_SEED = 2024          # bench_seed
 SEED_BASE = 1000            # market i is seeded SeedSequence(1000 + i)
 CONFIGS = {"c3": (4096, 4), "c4": (2048, 8)}
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: the whole dump stays under this
+DUMP_SAMPLE_SEED = 12345    # --dump-outputs: the market sample of an output larger than DUMP_MAX_BYTES
 
 
 def parse():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
-    p.add_argument("--steps", type=int, default=1000)
-    p.add_argument("--warmup", type=int, default=64)
+    p.add_argument("--steps", type=int, default=None, help="timed steps (--learner dp: timed iterations); default 1000 (8)")
+    p.add_argument("--warmup", type=int, default=None, help="untimed steps before them (--learner dp: iterations); default 64 (2)")
     p.add_argument("--config", choices=sorted(CONFIGS), default="c3", help="c3: 4096 markets x 4 agents per GPU (BASELINE configs[2]); "
                    "c4: 2048 x 8 per GPU (the per-GPU share of BASELINE configs[3], 16384 x 8 over 8 GPUs)")
     p.add_argument("--markets", type=int, default=None, help="markets per GPU (overrides --config)")
@@ -108,7 +111,17 @@ def parse():
                         "itself data-parallel over the same shards, the all-gather can be skipped entirely'); here a step = one iteration (a 64-step rollout + its update)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU work budget of the cpu_baseline sample")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the timed path computed in its LAST step (the arrays its caller receives) as DIR/<name>.npy, finite float32 / float64 (a None is a 0.0 with <name>_present.npy = 0), "
+                        f"at most {DUMP_MAX_BYTES >> 20} MB in all (beyond that a fixed, seeded sample of the markets; DIR/market_sample.npy names them); rank 0 only")
+    args = p.parse_args()
+    if args.steps is None:
+        args.steps = 8 if args.learner == "dp" else 1000
+    if args.warmup is None:
+        args.warmup = 2 if args.learner == "dp" else 64
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def cpu_model():
@@ -259,7 +272,9 @@ def learner_dp(args, dist, world, rank, device, backend):
     cfg = {"num_of_agents": A, "init_cash": 1000000, "max_step": 4096, "is_render": False, "auto_reset": True}
     env = CDAVecEnv(cfg, n_markets=N, device=str(device), with_info=False)
     allreduce = make_grad_allreduce(dist) if world > 1 else None
-    _, hist = ppo.train_fused(env, iters=W + K, horizon=T, seed=0, log=lambda s: None, chains=args.groups or 4, allreduce=allreduce, world=world, first_market=rank * N)
+    policy, hist = ppo.train_fused(env, iters=W + K, horizon=T, seed=0, log=lambda s: None, chains=args.groups or 4, allreduce=allreduce, world=world, first_market=rank * N)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"theta": policy.theta})             # the policy's parameters after the last iteration
     dt = torch.tensor([sum(h["rollout_s"] + h["update_s"] for h in hist[W:])], dtype=torch.float64, device=device)
     if world > 1:
         dist.all_reduce(dt, op=dist.ReduceOp.MAX)
@@ -300,7 +315,7 @@ def learner_shape(args):
     N, A = CONFIGS[args.config]
     N = args.markets if args.markets is not None else N
     A = args.agents if args.agents is not None else A
-    return N, A, (args.steps if args.steps != 1000 else 8), (args.warmup if args.warmup != 64 else 2), 64
+    return N, A, args.steps, args.warmup, 64
 
 
 def learner_line(world, N, A, T, K, W, elapsed, backend, flags, losses):
@@ -315,6 +330,49 @@ def learner_line(world, N, A, T, K, W, elapsed, backend, flags, losses):
                                       "no observation / reward hand-back"),
                        "flagged_markets": flags},
             "loss_last_iteration": losses}
+
+
+def dump_outputs(dirname, arrays, dec=(), nullable=()):
+    """--dump-outputs: {name: tensor, all with the same rows (markets) on axis 0} -> dirname/<name>.npy.  float32 stays float32, every other element type becomes float64
+    (exact for the integers and flags); the dec28 arrays named in `dec` (uint8 [..., 16]) become the float64 nearest to their exact value.  Every value written is
+    finite: the arrays named in `nullable` encode None as NaN (include/cda.h), so they are written with 0.0 in its place next to <name>_present.npy (1.0 = a value,
+    0.0 = None); a non-finite value anywhere else is an error.  When the whole would exceed DUMP_MAX_BYTES, every array keeps the same fixed, seeded sample
+    of the markets (ascending), written as market_sample.npy."""
+    import numpy as np
+    import torch
+    from gym_continuousdoubleauction_amd import _capi as K
+    ns = {int(a.shape[0]) for a in arrays.values()}
+    assert len(ns) == 1, {k: tuple(a.shape) for k, a in arrays.items()}
+    n = ns.pop()
+
+    def row_bytes(name, a):
+        elems = int(np.prod(a.shape[1:], dtype=np.int64)) // (16 if name in dec else 1)
+        return elems * (4 if a.dtype == torch.float32 else 8) * (2 if name in nullable else 1)
+    per_market = sum(row_bytes(k, a) for k, a in arrays.items())
+    budget = DUMP_MAX_BYTES - 128 * (len(arrays) + len(nullable) + 1)  # (the .npy headers)
+    rows = None
+    if per_market * n > budget:
+        m = max(1, budget // (per_market + 8))                           # (+ the sample's own index)
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, m, replace=False))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        if rows is not None:
+            a = a.index_select(0, torch.as_tensor(rows, device=a.device))
+        x = a.detach().cpu().numpy()
+        if name in dec:
+            raw = np.ascontiguousarray(x).view(K.DEC_DTYPE)[..., 0]
+            x = np.array([float(K.dec_to_decimal(d)) for d in raw.reshape(-1)], np.float64).reshape(raw.shape)
+        elif x.dtype != np.float32:
+            x = x.astype(np.float64)
+        if name in nullable:
+            present = ~np.isnan(x)
+            np.save(os.path.join(dirname, f"{name}_present.npy"), present.astype(np.float64))
+            x = np.where(present, x, 0.0).astype(x.dtype)
+        if not np.isfinite(x).all():
+            raise ValueError(f"--dump-outputs: {name} holds {int((~np.isfinite(x)).sum())} non-finite values")
+        np.save(os.path.join(dirname, f"{name}.npy"), x)
+    if rows is not None:
+        np.save(os.path.join(dirname, "market_sample.npy"), rows.astype(np.float64))
 
 
 def group_ranges(n, groups):
@@ -544,6 +602,7 @@ def main():
     torch.cuda.set_device(device)
 
     from gym_continuousdoubleauction_amd import CDAVecEnv
+    from gym_continuousdoubleauction_amd import _capi
     from gym_continuousdoubleauction_amd.parallel import ShardedVecEnv, handback_stride
 
     if args.learner == "dp":
@@ -583,6 +642,18 @@ def main():
                 self.sh.step(*step_acts[i], pipelined=True)
             else:
                 self.env.step(*step_acts[i], pipelined=not self.ordered)
+
+        def outputs(self):
+            """({name: tensor}, names of the dec28 ones, names of the NaN-for-None ones): what the caller of this leg holds after its last step - the buffers every step rewrites in place"""
+            e = self.env
+            if args.fused:
+                return {"obs": e.obs, "episode_return": e._rr_return, "terminated": e._term, "truncated": e._trunc, "steps_taken": e._rr_steps}, (), ()
+            if self.sh is not None:                                 # the hand-back: the learner-side arrays of every rank's markets
+                return dict(zip(("obs", "reward", "terminated", "truncated"), self.sh.full)), (), ()
+            out = {"obs": e.obs, "reward": e.reward, "terminated": e._term, "truncated": e._trunc}
+            out.update((f"info_{k}", v) for k, v in e.info.items())
+            return (out, {f"info_{name}" for name, ct, _, _ in _capi.INFO_FIELDS if ct is _capi.Dec},
+                    {f"info_{name}" for name in ("best_bid", "best_ask", "spread") if name in e.info})         # NaN encodes None (include/cda.h cda_info_ptrs)
 
         def close(self):
             (self.sh or self.env).close()
@@ -690,6 +761,8 @@ def main():
         if use_dist:
             dist.barrier(); dist.destroy_process_group()
         sys.exit(0 if ok else 4)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *head.outputs())
     head.close()
 
     extras = {}

@@ -228,3 +228,27 @@ def test_native_transport_probe_runs_in_a_sacrificial_child():
         assert not ok and "did not finish" in note and "torch.distributed carries the records" in note, note
     finally:
         os.environ.update(env_keep)
+
+
+def test_bench_dump_outputs_is_the_same_from_run_to_run(tmp_path):
+    """--dump-outputs: the headline leg's last-step outputs (obs, reward, flags, every info tensor) as finite float32 / float64 .npy files under 64 MB; two runs
+    with the same arguments write the same arrays, and so does a run that steps the batch as one launch instead of two group chains (markets never interact)."""
+    import numpy as np
+    runs = {"a": [], "b": [], "one_launch": ["--groups", "1"]}
+    for name, extra in runs.items():
+        out = subprocess.check_output([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "30", "--warmup", "6", "--markets", "512", "--no-cpu-baseline",
+                                       "--no-extra-legs", "--dump-outputs", str(tmp_path / name)] + extra, cwd=ROOT, stderr=subprocess.DEVNULL, text=True, timeout=600)
+        d = json.loads([ln for ln in out.splitlines() if ln.startswith("{")][0])
+        assert d["steps"] == 30 and d["ms_per_step"] > 0 and d["config"]["flagged_markets"] == 0
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert {"obs.npy", "reward.npy", "terminated.npy", "truncated.npy", "info_nav.npy", "info_reward_terms.npy"} <= set(files)
+    assert sum((tmp_path / "a" / f).stat().st_size for f in files) <= 64 << 20
+    obs = np.load(tmp_path / "a" / "obs.npy")
+    assert obs.dtype == np.float32 and obs.shape[0] == 512 and np.load(tmp_path / "a" / "reward.npy").shape == (512, 4)
+    assert np.abs(obs).sum() > 0 and all(np.isfinite(np.load(tmp_path / "a" / f)).all() for f in files)
+    assert {"info_best_bid_present.npy", "info_best_ask_present.npy", "info_spread_present.npy"} <= set(files)      # (None, NaN in the env's tensors, as a mask)
+    for other in ("b", "one_launch"):
+        assert sorted(p.name for p in (tmp_path / other).iterdir()) == files
+        for f in files:
+            x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / other / f)
+            assert x.dtype in (np.float32, np.float64) and x.dtype == y.dtype and np.array_equal(x.view(np.uint8), y.view(np.uint8)), (other, f)

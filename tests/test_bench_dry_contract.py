@@ -71,3 +71,58 @@ def test_c4_shape_and_no_gather_flag():
     d = run(2, "--config", "c4", "--steps", "300", "--warmup", "10", "--no-gather")
     assert d["config"]["markets_per_gpu"] == 2048 and d["config"]["agents"] == 8 and d["config"]["collective"] == "none" and d["config"]["groups"] == 4
     assert d["timed_repeats"]["n"] == 1 and "configs[3]" in d["config"]["workload"]
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_dump_outputs_writes_float_arrays_and_a_fixed_sample_under_the_cap(tmp_path):
+    """--dump-outputs (no GPU: the writer on host tensors): float32 stays float32, integers / flags become exact float64, a dec28 array becomes the float64 of
+    its exact value; above the cap every array keeps the same seeded sample of the markets, named by market_sample.npy, and the whole stays under the cap."""
+    import decimal
+    import numpy as np
+    import torch
+    from gym_continuousdoubleauction_amd import _capi as K
+    bench = _bench_module()
+    N, A = 1000, 4
+    vals = [decimal.Decimal("1000000.123456789"), decimal.Decimal("-12.5"), decimal.Decimal("79228162514264337593543950335"), decimal.Decimal("0.000001")]
+    nav = np.zeros((N, A, 16), np.uint8)
+    for i in range(N):
+        for a in range(A):
+            nav[i, a] = np.frombuffer(bytes(K.decimal_to_dec(vals[(i + a) % 4])), np.uint8)
+    g = torch.Generator().manual_seed(0)
+    arrays = {"obs": torch.randn(N, 168, generator=g), "reward": torch.randn(N, A, dtype=torch.float64, generator=g),
+              "terminated": (torch.arange(N) % 3 == 0).to(torch.uint8), "info_nav": torch.from_numpy(nav),
+              "info_lob_actions": torch.randint(-5, 9, (N, A, 4), dtype=torch.int32, generator=g),
+              "info_best_bid": torch.where(torch.arange(N) % 7 == 0, float("nan"), torch.arange(N, dtype=torch.float64))}
+    bench.dump_outputs(str(tmp_path / "all"), arrays, {"info_nav"}, {"info_best_bid"})
+    got = {n: np.load(tmp_path / "all" / f"{n}.npy") for n in arrays}
+    assert not (tmp_path / "all" / "market_sample.npy").exists()
+    assert got["obs"].dtype == np.float32 and np.array_equal(got["obs"], arrays["obs"].numpy())
+    assert got["reward"].dtype == np.float64 and np.array_equal(got["reward"], arrays["reward"].numpy())
+    assert got["terminated"].dtype == np.float64 and np.array_equal(got["terminated"], arrays["terminated"].numpy())
+    assert got["info_lob_actions"].dtype == np.float64 and np.array_equal(got["info_lob_actions"], arrays["info_lob_actions"].numpy())
+    assert got["info_nav"].shape == (N, A) and all(got["info_nav"][i, a] == float(vals[(i + a) % 4]) for i in range(4) for a in range(A))
+    # NaN encodes None in the nullable fields: written as 0.0 next to a presence mask, so that every value on disk is finite
+    present = np.load(tmp_path / "all" / "info_best_bid_present.npy")
+    assert present.dtype == np.float64 and np.array_equal(present, (np.arange(N) % 7 != 0).astype(np.float64))
+    assert np.array_equal(got["info_best_bid"], np.where(np.arange(N) % 7 == 0, 0.0, np.arange(N)))
+    for f in (tmp_path / "all").iterdir():
+        assert np.isfinite(np.load(f)).all(), f.name
+    with pytest.raises(ValueError, match="non-finite"):
+        bench.dump_outputs(str(tmp_path / "bad"), {"reward": torch.tensor([1.0, float("inf")], dtype=torch.float64)})
+    bench.DUMP_MAX_BYTES = 256 << 10
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), arrays, {"info_nav"}, {"info_best_bid"})
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= bench.DUMP_MAX_BYTES
+    rows = np.load(tmp_path / "s1" / "market_sample.npy")
+    assert rows.dtype == np.float64 and 0 < len(rows) < N and np.all(np.diff(rows) > 0)
+    for n in list(arrays) + ["info_best_bid_present", "market_sample"]:
+        assert np.array_equal(np.load(tmp_path / "s1" / f"{n}.npy"), np.load(tmp_path / "s2" / f"{n}.npy")), n
+    for n in list(arrays) + ["info_best_bid_present"]:
+        assert np.array_equal(np.load(tmp_path / "s1" / f"{n}.npy"), (got[n] if n in got else present)[rows.astype(np.int64)]), n
