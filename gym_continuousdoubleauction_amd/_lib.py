@@ -31,6 +31,7 @@ MLP_SYMBOLS = [
     "cda_mlp_wgrad", "cda_mlp_adam", "cda_ppo_loss32", "cda_gae_records", "cda_ppo_loss_records", "cda_mlp_forward_backward", "cda_mlp_rollout_chain", "cda_mlp_selftest_mfma",
     "cda_mlp_reduce", "cda_mlp_apply", "cda_gae_records_bootstrap", "cda_mlp_values", "cda_mlp_values_counted", "cda_episode_returns", "cda_mlp_league_step", "cda_mlp_league_rollout_chain",
     "cda_gae_records_league", "cda_league_assign", "cda_mlp_wgrad_jobs",
+    "cda_mlp_policy_act", "cda_mlp_league_act", "cda_mlp_eval_chain", "cda_mlp_league_eval_chain",
 ]
 # the same entry points compiled for other history depths carry the suffix _h<H> (include/cda_mlp.h CDA_MLP_HIST_VARIANTS, csrc/cda_mlp_variant.h)
 MLP_HIST_VARIANTS = (1, 2, 3, 6, 7, 8)
@@ -125,6 +126,7 @@ def lib():
     L.cda_mlp_pack.argtypes = [vp, vp, vp]
     L.cda_mlp_permutation.argtypes = [u64, i64, vp, vp]
     L.cda_mlp_policy_step.argtypes = [vp, vp, vp, i32, i32, i32, u64, vp, i64] + [vp] * 8 + [vp]
+    L.cda_mlp_policy_act.argtypes = [vp, vp, vp, i32, i32, i32] + [vp] * 8 + [vp]
     L.cda_mlp_forward.argtypes = [vp, vp, vp, i64, i64, vp, vp]
     L.cda_mlp_prep_rows.argtypes = [vp, vp, i64, vp, vp, vp]
     L.cda_mlp_forward_train.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp]
@@ -140,6 +142,9 @@ def lib():
     L.cda_episode_returns.argtypes = [vp, vp, vp, i32, i64, i32, vp, vp, vp, vp, vp]
     L.cda_mlp_league_step.argtypes = [C.POINTER(League), vp, i32, i32, i32, u64, vp, i64] + [vp] * 8 + [i64, vp, vp, i64, vp]
     L.cda_mlp_league_rollout_chain.argtypes = [vp, C.POINTER(League), i32, i32, i32, u64, vp, C.POINTER(RolloutBufs), i32, vp]
+    L.cda_mlp_league_act.argtypes = L.cda_mlp_league_step.argtypes
+    L.cda_mlp_eval_chain.argtypes = [vp, vp, vp, i32, i32, i32, C.POINTER(RolloutBufs), i32, vp]
+    L.cda_mlp_league_eval_chain.argtypes = L.cda_mlp_league_rollout_chain.argtypes
     L.cda_league_assign.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp, vp, vp]
     L.cda_step_range_capture.argtypes = [vp, i32, i32] + [vp] * 6 + [vp] * 4 + [C.POINTER(K.InfoPtrs), vp, i32, vp, vp, vp]
     L.cda_policy_step_supported.argtypes = [vp]

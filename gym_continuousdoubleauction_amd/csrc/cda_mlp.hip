@@ -155,7 +155,12 @@ __device__ __forceinline__ void store_lds_pair(__bf16* act, int ld, int row_base
 }
 
 // ---- forward ---------------------------------------------------------------------------------------------------------------
-enum { MODE_TRAIN = 0, MODE_OUT = 1, MODE_SAMPLE = 2, MODE_VALUE = 3, MODE_LEAGUE = 4 };
+// MODE_GREEDY / MODE_LEAGUE_GREEDY: MODE_SAMPLE / MODE_LEAGUE with the MODE of each slot's distribution instead of a sample (cda_mlp_dev.inc mode_action; evaluation) -
+// the league's random-module slots draw exactly as MODE_LEAGUE draws them
+enum { MODE_TRAIN = 0, MODE_OUT = 1, MODE_SAMPLE = 2, MODE_VALUE = 3, MODE_LEAGUE = 4, MODE_GREEDY = 5, MODE_LEAGUE_GREEDY = 6 };
+constexpr bool mode_acts(int m) { return m == MODE_SAMPLE || m == MODE_LEAGUE || m == MODE_GREEDY || m == MODE_LEAGUE_GREEDY; }   // the policy epilogue: actions per (row, agent)
+constexpr bool mode_league(int m) { return m == MODE_LEAGUE || m == MODE_LEAGUE_GREEDY; }
+constexpr bool mode_greedy(int m) { return m == MODE_GREEDY || m == MODE_LEAGUE_GREEDY; }
 struct FwdArgs {
     const __bf16* x_rm;          // MODE_TRAIN: [n_rows][176] bf16
     const float* obs;            // otherwise: f32 [*][168]
@@ -190,6 +195,7 @@ struct FwdArgs {
 template <int MT, int MODE>
 __global__ __launch_bounds__(256) void k_mlp_fwd(FwdArgs A) {
     constexpr int M = 32 * MT, PF = MT == 1 ? 16 : (MT == 2 ? 3 : CDA_MLP_PF4);
+    constexpr bool ACTS = mode_acts(MODE), LEAGUE = mode_league(MODE), GREEDY = mode_greedy(MODE), SHARED = ACTS && !LEAGUE;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __bf16* xs = reinterpret_cast<__bf16*>(smem);                               // [M][XS_LD]
     __bf16* act = xs + M * XS_LD;                                               // [M][ACT_LD]
@@ -201,11 +207,11 @@ __global__ __launch_bounds__(256) void k_mlp_fwd(FwdArgs A) {
     // A league launch (MODE_LEAGUE; the bootstrap values of its trainable nets: MODE_VALUE with n_train > 0): blockIdx.y names the (net, half) job
     // and the net's parameters are its row of the banks.  Uniform per workgroup: scalar registers.
     int net = 0, job_half = 0;
-    if (MODE == MODE_LEAGUE) { const int y = (int)blockIdx.y; net = y < 2 * A.n_train ? y >> 1 : A.n_train + (y - 2 * A.n_train); job_half = y < 2 * A.n_train ? (y & 1) : 0; }
+    if (LEAGUE) { const int y = (int)blockIdx.y; net = y < 2 * A.n_train ? y >> 1 : A.n_train + (y - 2 * A.n_train); job_half = y < 2 * A.n_train ? (y & 1) : 0; }
     if (MODE == MODE_VALUE && A.n_train > 0) net = (int)blockIdx.y;
     const float* theta = A.theta + (size_t)net * CDA_MLP_PARAMS;
     const __bf16* wb = A.wb + (size_t)net * CDA_MLP_WB_ELEMS;
-    if (MODE == MODE_LEAGUE && net >= A.n_train) {
+    if (LEAGUE && net >= A.n_train) {
         // a frozen snapshot (champion) is only needed where one of the tile's (market, slot) pairs is played by it: whole workgroups leave otherwise
         int mine = 0;
         for (int s = (int)threadIdx.x; s < M * A.agents; s += 256) {
@@ -230,8 +236,8 @@ __global__ __launch_bounds__(256) void k_mlp_fwd(FwdArgs A) {
     WRing<2, KX / 16, PF, true> R1; WRing<2, HID / 16, PF, true> R2; WRing<1, HID / 16, PF> RO;
     // The two halves are independent networks: a rollout launch gives each its own workgroup (half the serial chain, half the weight bytes
     // through one CU's L1); the update's launches run both in one workgroup (the observation tile is staged once).
-    const int half_begin = MODE == MODE_LEAGUE ? job_half : (A.split_halves == 1 ? (int)blockIdx.y : (A.split_halves == 2 ? 1 : 0));
-    const int half_end = (MODE == MODE_LEAGUE || A.split_halves) ? half_begin + 1 : 2;
+    const int half_begin = LEAGUE ? job_half : (A.split_halves == 1 ? (int)blockIdx.y : (A.split_halves == 2 ? 1 : 0));
+    const int half_end = (LEAGUE || A.split_halves) ? half_begin + 1 : 2;
     float* const value_out = A.value ? A.value + (size_t)net * A.value_stride : nullptr;
     R1.prime(W1b + (size_t)(256 * half_begin + 64 * w) * KX, KX, lane);         // (layer 1's weights fly while the observation tile is staged)
     if (MODE == MODE_TRAIN) load_x_bf16<M>(A.x_rm, row0, rows_end, xs); else load_x_f32<M>(A.obs, row0, rows_end, xs);
@@ -303,26 +309,26 @@ __global__ __launch_bounds__(256) void k_mlp_fwd(FwdArgs A) {
         for (int r = 0; r < 16; r++) {
             const int row = 32 * w + rowmap(r, h);
             const float o = acc3[0][0][r] + bo;
-            if (MODE == MODE_SAMPLE || MODE == MODE_LEAGUE) { if (half_begin == 0) outs[row * OUTS_LD + j] = o; else if (j == N_LOGITS && row0 + row < rows_end) value_out[row0 + row] = o; }
+            if (ACTS) { if (half_begin == 0) outs[row * OUTS_LD + j] = o; else if (j == N_LOGITS && row0 + row < rows_end) value_out[row0 + row] = o; }
             else if (MODE == MODE_VALUE) { if (j == N_LOGITS && row0 + row < rows_end) value_out[row0 + row] = o; }
             else if (own_col && (MODE == MODE_TRAIN || row0 + row < rows_end)) A.out[(row0 + row) * NOUT + j] = o;
         }
     }
     MLP_MARK(18);
-    if ((MODE == MODE_SAMPLE || MODE == MODE_LEAGUE) && half_begin == 0) {
+    if (ACTS && half_begin == 0) {
         __syncthreads();
         // one thread per (row, agent) sample: three categorical heads by inverse CDF, two Gaussian heads by Box-Muller, the action's
         // log-probability, and the env's five action words (size_mean = tanh, size_sigma = sigmoid: the Box bounds of
         // action_helper.py:126-138)
         const int ag = A.agents;
-        const unsigned long long key = rollout_key(A.seed, A.counter[0], A.draw);
+        const unsigned long long key = GREEDY ? 0ull : rollout_key(A.seed, A.counter[0], A.draw);      // (greedy: no draws - the counter may be NULL)
         const float ls0 = theta[CDA_MLP_OFF_LS], ls1 = theta[CDA_MLP_OFF_LS + 1];
         for (int s = (int)threadIdx.x; s < M * ag; s += 256) {
             const int row = s / ag, a = s - row * ag;
             const long long grow = row0 + row;
             if (grow >= rows_end) continue;
             const long long i = grow * ag + a;
-            if (MODE == MODE_LEAGUE) {
+            if (LEAGUE) {
                 // the slot's module: this net -> sampled below; the uniform random module (RandomRLModule's law, train/model/model_handler.py:38-53;
                 // the counter-based stream of include/cda_random_agents.h keyed (random_seed + rollout counter, market, step, slot)) -> drawn by net 0's
                 // workgroup; any other net -> that net's workgroup writes the slot
@@ -345,9 +351,10 @@ __global__ __launch_bounds__(256) void k_mlp_fwd(FwdArgs A) {
             float l[N_LOGITS];
             #pragma unroll
             for (int q = 0; q < N_LOGITS; q++) l[q] = outs[row * OUTS_LD + q];
-            if (MODE == MODE_SAMPLE && a == 0 && !A.split_halves) A.value[grow] = outs[row * OUTS_LD + N_LOGITS];
+            if (SHARED && a == 0 && !A.split_halves) A.value[grow] = outs[row * OUTS_LD + N_LOGITS];
             // (log-std = the free vector + the row's outputs 25, 26: the state-dependent head's offsets, zero in a network built without it - include/cda_mlp.h sd_log_std)
-            const SampledAction sa = sample_action(l, key, i, ls0 + outs[row * OUTS_LD + N_LOGITS + 1], ls1 + outs[row * OUTS_LD + N_LOGITS + 2]);         // (cda_mlp_dev.inc: the arithmetic k_policy_step shares)
+            const float lsa = ls0 + outs[row * OUTS_LD + N_LOGITS + 1], lsb = ls1 + outs[row * OUTS_LD + N_LOGITS + 2];
+            const SampledAction sa = GREEDY ? mode_action(l, lsa, lsb) : sample_action(l, key, i, lsa, lsb);         // (cda_mlp_dev.inc: the arithmetic k_policy_step shares)
             const int c = sa.cat, p = sa.price, o = sa.off;
             const float x0 = sa.x0, x1 = sa.x1, lp = sa.logp;
             A.env_cat[i] = c; A.env_price[i] = p; A.env_off[i] = o;
@@ -361,7 +368,7 @@ __global__ __launch_bounds__(256) void k_mlp_fwd(FwdArgs A) {
                 *reinterpret_cast<float2*>(A.rec + 8 * i + 4) = make_float2(x1, lp);
             }
         }
-        if (A.dist && (MODE == MODE_SAMPLE || net < A.n_train)) {
+        if (A.dist && (SHARED || net < A.n_train)) {
             // the rollout policy's distribution of every row, for the update's KL term: 22 normalised log-probabilities | 2 means | 2 log-stds | 2 zeros (a thread per row)
             float* dist = A.dist + (size_t)net * A.dist_stride;
             for (int row = (int)threadIdx.x; row < M; row += 256) {
@@ -1804,7 +1811,7 @@ int rollout_mt() {
     if (!mt) { const char* e = getenv("CDA_MLP_ROLLOUT_MT"); mt = e ? atoi(e) : 1; if (mt != 1 && mt != 2 && mt != 4) mt = 1; }
     return mt;
 }
-size_t fwd_lds(int mt, int mode) { const size_t M = 32 * (size_t)mt; return M * XS_LD * 2 + M * ACT_LD * 2 + ((mode == MODE_SAMPLE || mode == MODE_LEAGUE) ? M * OUTS_LD * 4 : 0); }
+size_t fwd_lds(int mt, int mode) { const size_t M = 32 * (size_t)mt; return M * XS_LD * 2 + M * ACT_LD * 2 + (mode_acts(mode) ? M * OUTS_LD * 4 : 0); }
 size_t bwd_lds(int mt) { const size_t M = 32 * (size_t)mt; return M * DO_LD * 2 + M * ACT_LD * 2 + M * OUTS_LD * 4; }
 
 // more than 64 KB of dynamic LDS needs the function attribute raised, once per (kernel, device): remembered here (a launch path, not a setup path)
@@ -1881,6 +1888,21 @@ extern "C" int cda_mlp_policy_step(const void* wb, const float* theta, const flo
     A.a_cont = a_cont; A.logp = logp; A.value = value;
     A.split_halves = 1;
     return launch_fwd<MODE_SAMPLE>(A, rollout_mt(), (hipStream_t)stream);
+}
+
+// cda_mlp_policy_step's launch with the mode action of every (market, agent) pair: no seed, no counter, no draw
+extern "C" int cda_mlp_policy_act(const void* wb, const float* theta, const float* obs, int32_t first_market, int32_t n_markets, int32_t num_agents,
+                                  int32_t* env_category, float* env_size_mean, float* env_size_sigma, int32_t* env_price, int32_t* env_price_offset,
+                                  float* a_cont, float* logp, float* value, void* stream) {
+    if (!wb || !theta || !obs || !env_category || !env_size_mean || !env_size_sigma || !env_price || !env_price_offset || !a_cont || !logp || !value ||
+        first_market < 0 || n_markets < 1 || num_agents < 1 || num_agents > CDA_MAX_AGENTS) return CDA_ERR_INVALID;
+    FwdArgs A; memset(&A, 0, sizeof A);
+    A.obs = obs; A.first_row = first_market; A.n_rows = n_markets; A.wb = (const __bf16*)wb; A.theta = theta;
+    A.agents = num_agents;
+    A.env_cat = env_category; A.env_mean = env_size_mean; A.env_sigma = env_size_sigma; A.env_price = env_price; A.env_off = env_price_offset;
+    A.a_cont = a_cont; A.logp = logp; A.value = value;
+    A.split_halves = 1;
+    return launch_fwd<MODE_GREEDY>(A, rollout_mt(), (hipStream_t)stream);
 }
 
 extern "C" int cda_mlp_forward(const void* wb, const float* theta, const float* obs, int64_t first_row, int64_t n_rows, float* out, void* stream) {
@@ -2107,10 +2129,11 @@ extern "C" int cda_ppo_loss_records(const float* outputs, const float* log_std, 
     return hipGetLastError() == hipSuccess ? CDA_OK : CDA_ERR_HIP;
 }
 
-extern "C" int cda_mlp_league_step(const cda_league* L, const float* obs, int32_t first_market, int32_t n_markets, int32_t num_agents,
-                                   uint64_t seed, const int64_t* counter_dev, int64_t draw,
-                                   int32_t* env_category, float* env_size_mean, float* env_size_sigma, int32_t* env_price, int32_t* env_price_offset,
-                                   float* a_cont, float* logp, float* value, int64_t value_stride, float* rec, float* dist, int64_t dist_stride, void* stream) {
+template <int MODE>
+static int league_step(const cda_league* L, const float* obs, int32_t first_market, int32_t n_markets, int32_t num_agents,
+                       uint64_t seed, const int64_t* counter_dev, int64_t draw,
+                       int32_t* env_category, float* env_size_mean, float* env_size_sigma, int32_t* env_price, int32_t* env_price_offset,
+                       float* a_cont, float* logp, float* value, int64_t value_stride, float* rec, float* dist, int64_t dist_stride, void* stream) {
     if (!L || !L->wb_bank || !L->theta_bank || !L->slot_net || L->n_trainable < 1 || L->n_nets < L->n_trainable || L->n_nets > CDA_LEAGUE_MAX_NETS ||
         !obs || !counter_dev || !env_category || !env_size_mean || !env_size_sigma || !env_price || !env_price_offset || !a_cont || !logp || !value ||
         first_market < 0 || n_markets < 1 || num_agents < 1 || num_agents > CDA_MAX_AGENTS) return CDA_ERR_INVALID;
@@ -2121,7 +2144,22 @@ extern "C" int cda_mlp_league_step(const cda_league* L, const float* obs, int32_
     A.a_cont = a_cont; A.logp = logp; A.value = value; A.rec = rec; A.dist = dist;
     A.n_train = L->n_trainable; A.slot_net = L->slot_net; A.value_stride = value_stride; A.dist_stride = dist_stride; A.random_seed = L->random_seed;
     A.split_halves = 1;
-    return launch_fwd<MODE_LEAGUE>(A, rollout_mt(), (hipStream_t)stream, (unsigned)(L->n_trainable + L->n_nets));     // 2 jobs per trainable net, 1 per frozen one
+    return launch_fwd<MODE>(A, rollout_mt(), (hipStream_t)stream, (unsigned)(L->n_trainable + L->n_nets));     // 2 jobs per trainable net, 1 per frozen one
+}
+extern "C" int cda_mlp_league_step(const cda_league* L, const float* obs, int32_t first_market, int32_t n_markets, int32_t num_agents,
+                                   uint64_t seed, const int64_t* counter_dev, int64_t draw,
+                                   int32_t* env_category, float* env_size_mean, float* env_size_sigma, int32_t* env_price, int32_t* env_price_offset,
+                                   float* a_cont, float* logp, float* value, int64_t value_stride, float* rec, float* dist, int64_t dist_stride, void* stream) {
+    return league_step<MODE_LEAGUE>(L, obs, first_market, n_markets, num_agents, seed, counter_dev, draw, env_category, env_size_mean, env_size_sigma, env_price,
+                                    env_price_offset, a_cont, logp, value, value_stride, rec, dist, dist_stride, stream);
+}
+// ... with the mode action on every network slot; the random-module slots draw as there (seed / counter / draw key them)
+extern "C" int cda_mlp_league_act(const cda_league* L, const float* obs, int32_t first_market, int32_t n_markets, int32_t num_agents,
+                                  uint64_t seed, const int64_t* counter_dev, int64_t draw,
+                                  int32_t* env_category, float* env_size_mean, float* env_size_sigma, int32_t* env_price, int32_t* env_price_offset,
+                                  float* a_cont, float* logp, float* value, int64_t value_stride, float* rec, float* dist, int64_t dist_stride, void* stream) {
+    return league_step<MODE_LEAGUE_GREEDY>(L, obs, first_market, n_markets, num_agents, seed, counter_dev, draw, env_category, env_size_mean, env_size_sigma, env_price,
+                                           env_price_offset, a_cont, logp, value, value_stride, rec, dist, dist_stride, stream);
 }
 
 // The reference's agent-to-module mapping (train/callbk/league_based_self_play_callback.py:1286-1344) for every (market, pool slot) at once: slot s >= n_trainable
@@ -2167,9 +2205,10 @@ extern "C" int cda_league_assign(const uint32_t* episode_crc, int32_t n_markets,
 
 #ifndef CDA_MLP_TIMING          /* (the tools build holds the network kernels only, not the env) */
 // One chain's rollout: the loop of {policy step, env step} launches; L != NULL: the league's policy step (banks of nets, per-slot modules)
+// greedy: the mode actions (MODE_GREEDY / MODE_LEAGUE_GREEDY) - always the two launches (k_policy_step samples); a shared policy's greedy chain needs no counter
 static int rollout_chain(cda_env* env, const cda_league* L, const void* wb, const float* theta, int32_t first_market, int32_t n_markets, int32_t n_steps,
-                         uint64_t seed, const int64_t* counter_dev, const cda_rollout_bufs* B, int32_t copy_first_obs, void* stream) {
-    if (!env || !counter_dev || !B || n_steps < 1 || first_market < 0 || n_markets < 1) return CDA_ERR_INVALID;
+                         uint64_t seed, const int64_t* counter_dev, const cda_rollout_bufs* B, int32_t copy_first_obs, void* stream, bool greedy = false) {
+    if (!env || (!counter_dev && (L || !greedy)) || !B || n_steps < 1 || first_market < 0 || n_markets < 1) return CDA_ERR_INVALID;
     if (L ? (!L->wb_bank || !L->theta_bank || !L->slot_net || L->n_trainable < 1 || L->n_nets < L->n_trainable || L->n_nets > CDA_LEAGUE_MAX_NETS) : (!wb || !theta)) return CDA_ERR_INVALID;
     if (!B->obs || !B->category || !B->size_mean || !B->size_sigma || !B->price || !B->price_offset || !B->a_cont || !B->logp || !B->value || !B->reward ||
         !B->terminated || !B->truncated) return CDA_ERR_INVALID;
@@ -2192,7 +2231,7 @@ static int rollout_chain(cda_env* env, const cda_league* L, const void* wb, cons
         const char* ev = getenv("CDA_POLICY_STEP");              // read per call: an A / B run toggles it between two rollouts of one process
         const int want = ev ? atoi(ev) : 1;
         // (the env's history depth is this build's: checked above.  CDA_POLICY_STEP=2: wherever supported, also where the batched policy kernel is the faster one)
-        one_launch = want != 0 && !L && !B->info_steps && (want == 2 ? cda_policy_step_supported(env) : cda_policy_step_advised(env));
+        one_launch = !greedy && want != 0 && !L && !B->info_steps && (want == 2 ? cda_policy_step_supported(env) : cda_policy_step_advised(env));
     }
     for (int32_t t = 0; t < n_steps; t++) {
         const size_t o = (size_t)t * NA;
@@ -2221,8 +2260,9 @@ static int rollout_chain(cda_env* env, const cda_league* L, const void* wb, cons
         if (L) {
             P.n_train = n_train; P.slot_net = L->slot_net; P.random_seed = L->random_seed;
             P.value_stride = (long long)(n_steps + 1) * N; P.dist_stride = (long long)n_steps * N * CDA_MLP_DIST_LD;
-            rc = launch_fwd<MODE_LEAGUE>(P, rollout_mt(), st, (unsigned)(L->n_trainable + L->n_nets));
-        } else rc = launch_fwd<MODE_SAMPLE>(P, rollout_mt(), st);
+            rc = greedy ? launch_fwd<MODE_LEAGUE_GREEDY>(P, rollout_mt(), st, (unsigned)(L->n_trainable + L->n_nets))
+                        : launch_fwd<MODE_LEAGUE>(P, rollout_mt(), st, (unsigned)(L->n_trainable + L->n_nets));
+        } else rc = greedy ? launch_fwd<MODE_GREEDY>(P, rollout_mt(), st) : launch_fwd<MODE_SAMPLE>(P, rollout_mt(), st);
         if (rc) return rc;
         rc = cda_step_range_capture(env, first_market, n_markets, B->category + o, B->size_mean + o, B->size_sigma + o, B->price + o, B->price_offset + o, NULL,
                                     B->obs + (size_t)(t + 1) * N * OBS, B->reward + o, B->terminated + (size_t)t * N, B->truncated + (size_t)t * N,
@@ -2253,6 +2293,15 @@ extern "C" int cda_mlp_league_rollout_chain(cda_env* env, const cda_league* L, i
                                             uint64_t seed, const int64_t* counter_dev, const cda_rollout_bufs* B, int32_t copy_first_obs, void* stream) {
     if (!L) return CDA_ERR_INVALID;
     return rollout_chain(env, L, NULL, NULL, first_market, n_markets, n_steps, seed, counter_dev, B, copy_first_obs, stream);
+}
+extern "C" int cda_mlp_eval_chain(cda_env* env, const void* wb, const float* theta, int32_t first_market, int32_t n_markets, int32_t n_steps,
+                                  const cda_rollout_bufs* B, int32_t copy_first_obs, void* stream) {
+    return rollout_chain(env, NULL, wb, theta, first_market, n_markets, n_steps, 0, NULL, B, copy_first_obs, stream, true);
+}
+extern "C" int cda_mlp_league_eval_chain(cda_env* env, const cda_league* L, int32_t first_market, int32_t n_markets, int32_t n_steps,
+                                         uint64_t seed, const int64_t* counter_dev, const cda_rollout_bufs* B, int32_t copy_first_obs, void* stream) {
+    if (!L) return CDA_ERR_INVALID;
+    return rollout_chain(env, L, NULL, NULL, first_market, n_markets, n_steps, seed, counter_dev, B, copy_first_obs, stream, true);
 }
 #endif
 

@@ -143,6 +143,35 @@ __device__ __forceinline__ SampledAction sample_action(const float (&l)[N_LOGITS
     s.size_sigma = 1.0f / (1.0f + __expf(-s.x1));
     return s;
 }
+// The MODE of the same distribution (RLlib's to_deterministic(), explore=False): each categorical head takes its largest logit (strict > from index 0: the lowest
+// index wins a tie, torch.argmax), the Gaussian heads their means.  logp = the mode's log-probability - sample_action's formula with n0 = n1 = 0; the env words
+// are sample_action's expressions of the means.  No randomness.
+template <int N>
+__device__ __forceinline__ int mode_head(const float* l, float& logp) {
+    float mx = l[0];
+    int a = 0;
+    #pragma unroll
+    for (int j = 1; j < N; j++) if (l[j] > mx) { mx = l[j]; a = j; }
+    float s = 0.0f;
+    #pragma unroll
+    for (int j = 0; j < N; j++) s += __expf(l[j] - mx);
+    logp -= __logf(s);                                 // l[a] - max - log(sum): l[a] IS the max (a dynamic l[a] keeps every compare mask of the scan live: SGPR spills)
+    return a;
+}
+__device__ __forceinline__ SampledAction mode_action(const float (&l)[N_LOGITS], float ls0, float ls1) {
+    const float HALF_LOG_2PI = 0.918938533204672742f;
+    SampledAction s;
+    float lp = 0.0f;
+    s.cat = mode_head<N_CAT>(l, lp);
+    s.price = mode_head<N_PRICE>(l + N_CAT, lp);
+    s.off = mode_head<N_OFF>(l + N_CAT + N_PRICE, lp);
+    s.x0 = l[22]; s.x1 = l[23];
+    lp += -ls0 - HALF_LOG_2PI - ls1 - HALF_LOG_2PI;
+    s.logp = lp;
+    s.size_mean = __builtin_fmaf(-2.0f, __builtin_amdgcn_rcpf(__expf(2.0f * s.x0) + 1.0f), 1.0f);
+    s.size_sigma = 1.0f / (1.0f + __expf(-s.x1));
+    return s;
+}
 __device__ __forceinline__ unsigned long long rollout_key(unsigned long long seed, long long counter, long long draw) {
     return mix64(seed + (unsigned long long)counter * 0xd1342543de82ef95ull + (unsigned long long)draw * 0x2545f4914f6cdd1dull);
 }

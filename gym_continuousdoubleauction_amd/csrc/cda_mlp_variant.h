@@ -15,6 +15,7 @@
 #define cda_mlp_wgrad_jobs CDA_MLP_SFX(cda_mlp_wgrad_jobs)
 #define cda_mlp_pack CDA_MLP_SFX(cda_mlp_pack)
 #define cda_mlp_policy_step CDA_MLP_SFX(cda_mlp_policy_step)
+#define cda_mlp_policy_act CDA_MLP_SFX(cda_mlp_policy_act)
 #define cda_mlp_forward CDA_MLP_SFX(cda_mlp_forward)
 #define cda_mlp_permutation CDA_MLP_SFX(cda_mlp_permutation)
 #define cda_mlp_prep_rows CDA_MLP_SFX(cda_mlp_prep_rows)
@@ -35,6 +36,9 @@
 #define cda_mlp_forward_backward CDA_MLP_SFX(cda_mlp_forward_backward)
 #define cda_mlp_league_step CDA_MLP_SFX(cda_mlp_league_step)
 #define cda_mlp_league_rollout_chain CDA_MLP_SFX(cda_mlp_league_rollout_chain)
+#define cda_mlp_league_act CDA_MLP_SFX(cda_mlp_league_act)
+#define cda_mlp_eval_chain CDA_MLP_SFX(cda_mlp_eval_chain)
+#define cda_mlp_league_eval_chain CDA_MLP_SFX(cda_mlp_league_eval_chain)
 #define cda_gae_records_league CDA_MLP_SFX(cda_gae_records_league)
 #define cda_league_assign CDA_MLP_SFX(cda_league_assign)
 #define cda_mlp_selftest_mfma CDA_MLP_SFX(cda_mlp_selftest_mfma)

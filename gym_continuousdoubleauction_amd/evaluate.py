@@ -1,0 +1,187 @@
+"""Evaluate a trained policy: play it (greedy by default) against chosen opponents and read per-module episode results off the device.
+
+Placement (`slot_modules`): slots 0 .. trained_slots - 1 of every market play the policy (module 0); every other slot of market m plays opponent
+opponents[m % P] (module 1 + m % P).  Without opponents the policy plays every slot through the shared-policy chain (self-play).  With opponents the
+markets run on a PolicyBank: row 0 is the policy, the frozen rows behind it the network opponents, LEAGUE_RANDOM marks the uniform random module.
+
+The loop resets every market from `seed`, switches the env's episode metrics on BEFORE the chains are built (a toggle after graph capture would not reach
+the captured kernels), runs episodes * max_step steps, and reads the episodes that ENDED in that window with module_of = the placement
+(episode_metrics.summarise; check_nav_conservation strict).  Episodes still running at the end of the horizon are not counted: `episodes` and each module's
+`agent_episodes` say how many completed.  mode="greedy" plays the mode of every network slot's distribution (RLlib's explore=False: mlp.FusedPolicy.act,
+the greedy chains); mode="sample" runs the same loop on the sampling kernels.
+
+CLI: python -m gym_continuousdoubleauction_amd.evaluate --policy P [--opponent random|FILE ...] --markets --agents --max-step --episodes --trained-slots
+     [--sample] --seed --out JSON
+"""
+import argparse
+import json
+import time
+
+import numpy as np
+import torch
+
+from . import _capi as K
+from .episode_metrics import REWARD_TERMS, check_nav_conservation, summarise
+
+RANDOM = "random"
+
+
+def slot_modules(n_markets, num_agents, trained_slots, n_opponents):
+    """the documented placement: int32 [N, A] module per (market, slot) - 0 = the policy, 1 + p = opponent p.  n_opponents = 0: the policy everywhere."""
+    N, A, k, P = int(n_markets), int(num_agents), int(trained_slots), int(n_opponents)
+    if not 1 <= k <= A:
+        raise ValueError(f"trained_slots must be in 1 .. {A} (got {trained_slots})")
+    m = np.zeros((N, A), dtype=np.int32)
+    if P > 0:
+        m[:, k:] = (1 + np.arange(N) % P)[:, None]
+    return m
+
+
+def _as_policy(x, device):
+    from .mlp import FusedPolicy, load_policy
+    if isinstance(x, FusedPolicy):
+        return x
+    return load_policy(x, device)
+
+
+def _describe(x):
+    from .mlp import FusedPolicy
+    if isinstance(x, str):
+        return x
+    return "FusedPolicy" if isinstance(x, FusedPolicy) else str(x)
+
+
+def _horizon(total, cap=128):
+    """the rollout length: the largest divisor of the step count up to `cap` (the chains' buffers are [T, N, ...])"""
+    for h in range(min(cap, total), 0, -1):
+        if total % h == 0:
+            return h
+    return 1
+
+
+def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="greedy", seed=0, groups=None, keep=None):
+    """Play `policy` (a FusedPolicy or a policy file) on `env` (a CDAVecEnv with auto_reset) for episodes * max_step steps; return per-module results.
+    opponents: None = self-play; else a list of "random", FusedPolicy objects or policy files, placed by slot_modules.  trained_slots: the policy's slots per
+    market when there are opponents (default 1).  groups: rollout chains (default 4).  keep (a dict, optional): receives the RolloutChains object, the
+    placement, the collected metric tables (agent table, env row) and host copies of every step's env actions (`actions`: category, size_mean, size_sigma,
+    price, price_offset as [steps, N, A]) - what a replay needs."""
+    from .mlp import LEAGUE_RANDOM, PolicyBank, RolloutChains
+    if mode not in ("greedy", "sample"):
+        raise ValueError(f"mode must be 'greedy' or 'sample' (got {mode!r})")
+    if not bool(env.config.get("auto_reset", False)):
+        raise ValueError("evaluate needs an auto_reset env")
+    dev, N, A = env.device, env.n_markets, env.num_agents
+    pol = _as_policy(policy, dev)
+    opp = None if opponents is None else list(opponents)
+    if opp is not None and len(opp) == 0:
+        raise ValueError("opponents: None (self-play) or a non-empty list")
+    nets = []                                                           # (opponent index, FusedPolicy) of the network opponents
+    for p, o in enumerate(opp or []):
+        if isinstance(o, str) and o == RANDOM:
+            continue
+        op = _as_policy(o, dev)
+        if op.L.hist != pol.L.hist:
+            raise ValueError(f"opponent {p} is laid out for n_hist = {op.L.hist}, the policy for {pol.L.hist}")
+        nets.append((p, op))
+    k = (A if opp is None else 1) if trained_slots is None else int(trained_slots)
+    modules = slot_modules(N, A, k, 0 if opp is None else len(opp))
+    names = ["policy"] + [f"opponent_{p}" for p in range(len(opp or []))]
+
+    total = int(episodes) * int(env.max_step)
+    if total < 1:
+        raise ValueError("episodes * max_step must be at least 1")
+    T = _horizon(total)
+    prev_metrics = bool(getattr(env, "episode_metrics_on", False))
+    env.enable_episode_metrics(True)                                    # before the chains are captured
+    try:
+        if opp is None:
+            driver = pol
+        else:
+            bank = PolicyBank(dev, N, A, n_trainable=1, max_frozen=max(1, len(nets)), random_seed=seed, n_hist=pol.L.hist)
+            bank.theta[0].copy_(pol.theta)
+            bank.wb[0].copy_(pol.wb)
+            row_of = {}
+            for p, op in nets:
+                row = bank.n_trainable + bank.n_frozen
+                bank.n_frozen += 1
+                bank.theta[row].copy_(op.theta)
+                bank.wb[row].copy_(op.wb)
+                row_of[p] = row
+            bank._refresh()
+            slot_net = np.zeros((N, A), dtype=np.int32)
+            for p in range(len(opp)):
+                slot_net[modules == 1 + p] = row_of.get(p, LEAGUE_RANDOM)
+            bank.set_slots(torch.from_numpy(slot_net))
+            driver = bank
+        seeds = (np.uint64(int(seed) & (2 ** 63 - 1)) * np.uint64(N) + np.arange(N, dtype=np.uint64))
+        env.reset(seed=seeds)
+        env.collect_episode_metrics(clear=True)                          # nothing that ended before the reset counts
+        chains = RolloutChains(env, driver, T, groups=4 if groups is None else int(groups), seed=seed, greedy=mode == "greedy")
+        acts = [] if keep is not None else None
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        for _ in range(total // T):
+            buf = chains.run()
+            if acts is not None:
+                acts.append({key: buf[key].cpu() for key in ("category", "size_mean", "size_sigma", "price", "price_offset")})
+        torch.cuda.synchronize(dev)
+        wall = time.perf_counter() - t0
+        module_of = torch.from_numpy(modules).to(dev).contiguous()
+        table, env_row = env.collect_episode_metrics(module_of=module_of, n_modules=len(names), clear=True)
+    finally:
+        env.enable_episode_metrics(prev_metrics)
+    table_h, env_h = table.cpu().numpy(), env_row.cpu().numpy()
+    summary = summarise(table_h, env_h, module_names=names)
+    check_nav_conservation(0, summary, strict=True)
+    mods = {}
+    for i, name in enumerate(names):
+        r = table_h[i]
+        s = summary["modules"].get(name, {"agent_episodes": 0.0})
+        mods[name] = {"agent_episodes": s["agent_episodes"], "episode_return_mean": s.get("episode_return_mean"), "episode_return_std": s.get("episode_return_std"),
+                      "episode_nav_mean": s.get("episode_nav_mean"), "trades": float(r[K.EM_TRADES]), "rejections": float(r[K.EM_REJECTIONS]),
+                      "maker_fill_ratio_mean": s.get("maker_fill_ratio_mean"),
+                      "reward_term_sums": {t: float(r[K.EM_TERM_SUM + j]) for j, t in enumerate(REWARD_TERMS)},
+                      "slots": int((modules == i).sum())}
+    result = {"mode": mode, "episodes": summary["episodes"], "nav_conservation_violations": summary["nav_conservation_violations"], "modules": mods,
+              "config": {"markets": N, "agents": A, "max_step": int(env.max_step), "episodes": int(episodes), "steps": total, "horizon": T, "seed": int(seed),
+                         "trained_slots": k, "opponents": None if opp is None else [_describe(o) for o in opp], "n_hist": pol.L.hist},
+              "agent_steps_per_s": N * A * total / wall if wall > 0 else None,
+              "summary": summary}
+    if keep is not None:
+        keep["chains"], keep["modules"], keep["tables"] = chains, modules, (table_h, env_h)
+        keep["actions"] = {key: torch.cat([a[key] for a in acts]) for key in acts[0]}
+    return result
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser(description="evaluate a saved policy (greedy by default) against opponents on the HIP env")
+    p.add_argument("--policy", required=True, help="a policy file (ppo --save, league_train --save-dir)")
+    p.add_argument("--opponent", action="append", default=None, help="'random' or a policy file; repeat for several (market m plays opponent m mod P); none = self-play")
+    p.add_argument("--markets", type=int, default=1024)
+    p.add_argument("--agents", type=int, default=4)
+    p.add_argument("--max-step", type=int, default=256)
+    p.add_argument("--episodes", type=int, default=1)
+    p.add_argument("--trained-slots", type=int, default=None, help="slots per market the policy plays when there are opponents (default 1)")
+    p.add_argument("--sample", action="store_true", help="sample actions (the training kernels) instead of the greedy mode")
+    p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--out", default=None, help="also write the JSON result to this file")
+    args = p.parse_args(argv)
+    from .mlp import layout_of_params, read_policy
+    from .vec_env import CDAVecEnv
+    n_hist = layout_of_params(read_policy(args.policy).numel()).hist
+    env = CDAVecEnv({"num_of_agents": args.agents, "init_cash": 1000000, "max_step": args.max_step, "is_render": False, "auto_reset": True, "n_hist": n_hist},
+                    n_markets=args.markets, device="cuda:0", with_info=False)
+    try:
+        res = evaluate(env, args.policy, opponents=args.opponent, trained_slots=args.trained_slots, episodes=args.episodes,
+                       mode="sample" if args.sample else "greedy", seed=args.seed)
+    finally:
+        env.close()
+    res.pop("summary")
+    print(json.dumps(res))
+    if args.out:
+        with open(args.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+
+
+if __name__ == "__main__":
+    main()

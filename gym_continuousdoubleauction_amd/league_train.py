@@ -301,6 +301,30 @@ def train_league_fused(env, iters=4, horizon=None, num_trainable=2, lr=5e-5, epo
     return bank, league, history
 
 
+def save_league(directory, bank, league):
+    """write every trainable policy (policy_<p>.pt, bank row p) and every champion snapshot held in the bank (champion_<id>.pt) as policy files
+    (mlp.save_policy's format) and a league.json naming them: module id, bank row, file, and for champions the promotion iteration / return / source.
+    Returns the league.json dict."""
+    import os
+    from .mlp import policy_record
+    os.makedirs(directory, exist_ok=True)
+    promoted = {c["id"]: c for c in league.history}
+    out = {"format": "cda-league", "version": 1, "trainable": [], "champions": []}
+    for p in range(bank.n_trainable):
+        fname = f"policy_{p}.pt"
+        torch.save(policy_record(bank.theta[p]), os.path.join(directory, fname))
+        out["trainable"].append({"module": f"policy_{p}", "row": p, "file": fname})
+    for cid, row in sorted(league.net_of.items(), key=lambda kv: kv[1]):
+        fname = "champion_" + "".join(ch if ch.isalnum() or ch in "-_" else "_" for ch in str(cid)) + ".pt"
+        torch.save(policy_record(bank.theta[row]), os.path.join(directory, fname))
+        c = promoted.get(cid, {})
+        out["champions"].append({"module": str(cid), "row": int(row), "file": fname, "promoted_iteration": c.get("iteration"),
+                                 "return": None if c.get("return") is None else float(c["return"]), "source": None if c.get("source") is None else str(c["source"])})
+    with open(os.path.join(directory, "league.json"), "w") as fh:
+        json.dump(out, fh, indent=1)
+    return out
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description="League self-play (PPO vs random opponents and champion snapshots) on one MI355X.")
     p.add_argument("--markets", type=int, default=1024)
@@ -315,6 +339,7 @@ def main(argv=None):
     p.add_argument("--fcnet-hiddens", type=int, nargs=2, default=(256, 256), metavar=("H1", "H2"), help="hidden widths of the trainable policies (config/train_config.json:49), <= 256 each")
     p.add_argument("--log-std-head", action="store_true", help="the trainable policies carry the state-dependent log-std head (RLlib's default module for Box actions)")
     p.add_argument("--out", default=None, help="write a JSON summary to this file")
+    p.add_argument("--save-dir", default=None, help="--fused: write the trainable policies, the champion snapshots and league.json here (save_league)")
     args = p.parse_args(argv)
     from .vec_env import CDAVecEnv
     from . import ppo
@@ -326,7 +351,7 @@ def main(argv=None):
         return
     env = CDAVecEnv(dict(cfg, auto_reset=True), n_markets=args.markets, device="cuda:0", with_info=False)
     k = args.trainable or 2
-    _, league, hist = train_league_fused(env, iters=args.iters, horizon=args.horizon, num_trainable=k, chains=args.chains,
+    bank, league, hist = train_league_fused(env, iters=args.iters, horizon=args.horizon, num_trainable=k, chains=args.chains,
                                          objective=ppo.RLLIB_DEFAULTS if args.objective == "rllib" else None, state_dependent_log_std=args.log_std_head, hidden=tuple(args.fcnet_hiddens))
     flags = env.flags()
     _, bad = env.nav_conservation()
@@ -343,6 +368,9 @@ def main(argv=None):
                "rollout_agent_steps_per_s": sum(h["agent_steps"] for h in tail) / sum(h["rollout_s"] for h in tail),
                "champions": league.history, "flagged_markets": int((flags != 0).sum().item()), "nav_conservation_violations": int(bad.sum().item()),
                "invariant_violations": int((env.check_invariants() != 0).sum().item())}
+    if args.save_dir:
+        save_league(args.save_dir, bank, league)
+        summary["saved"] = args.save_dir
     print(json.dumps(summary))
     if args.out:
         with open(args.out, "w") as fh:

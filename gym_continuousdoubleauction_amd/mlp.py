@@ -328,9 +328,32 @@ class FusedPolicy:
                     "logp": e((N, A), torch.float32), "value": e((N,), torch.float32)}
         _check(self.L.fn("cda_mlp_policy_step")(self.wb.data_ptr(), self.theta.data_ptr(), obs.data_ptr(), int(first_market), int(n_markets), A,
                                           int(seed) & (2 ** 64 - 1), counter.data_ptr(), int(draw),
-                                          *[outs[k].data_ptr() for k in ("category", "size_mean", "size_sigma", "price", "price_offset", "a_cont", "logp", "value")],
+                                          *[outs[k].data_ptr() for k in _ACT_KEYS],
                                           _stream(dev)), "cda_mlp_policy_step")
         return outs
+
+    def act(self, obs, num_agents, first_market=0, n_markets=None, outs=None):
+        """policy_step with the MODE of the distribution instead of a sample (RLlib's explore=False): argmax of each categorical head, the Gaussian means,
+        the mode's log-probability (include/cda_mlp.h cda_mlp_policy_act).  Deterministic; returns the same dict as policy_step."""
+        obs = obs.contiguous()
+        assert obs.dtype == torch.float32 and obs.shape[-1] == self.L.OBS
+        N = obs.shape[0]
+        n_markets = N - first_market if n_markets is None else n_markets
+        A, dev = int(num_agents), self.device
+        outs = _act_outputs(N, A, dev) if outs is None else outs
+        _check(self.L.fn("cda_mlp_policy_act")(self.wb.data_ptr(), self.theta.data_ptr(), obs.data_ptr(), int(first_market), int(n_markets), A,
+                                               *[outs[k].data_ptr() for k in _ACT_KEYS], _stream(dev)), "cda_mlp_policy_act")
+        return outs
+
+
+_ACT_KEYS = ("category", "size_mean", "size_sigma", "price", "price_offset", "a_cont", "logp", "value")
+
+
+def _act_outputs(N, A, dev):
+    e = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)         # noqa: E731
+    return {"category": e((N, A), torch.int32), "size_mean": e((N, A), torch.float32), "size_sigma": e((N, A), torch.float32),
+            "price": e((N, A), torch.int32), "price_offset": e((N, A), torch.int32), "a_cont": e((N, A, 2), torch.float32),
+            "logp": e((N, A), torch.float32), "value": e((N,), torch.float32)}
 
 
 LEAGUE_RANDOM, LEAGUE_MAX_NETS = -1, 16
@@ -398,6 +421,22 @@ class PolicyBank:
             raise ValueError("slot_net names a bank row that does not exist")
         self.slot_net.copy_(t.to(self.device), non_blocking=True)
 
+    def act(self, obs, seed, counter, draw, first_market=0, n_markets=None, outs=None, greedy=True):
+        """one league launch over the markets [first_market, first_market + n_markets): greedy (cda_mlp_league_act) = the mode action on every network slot,
+        else the sampled step (cda_mlp_league_step); random-module slots draw from (random_seed, counter, draw) either way.  Returns policy_step's dict with
+        value [n_trainable, N]."""
+        obs = obs.contiguous()
+        assert obs.dtype == torch.float32 and obs.shape[-1] == self.L.OBS
+        N, A = self.slot_net.shape
+        n_markets = N - first_market if n_markets is None else n_markets
+        if outs is None:
+            outs = _act_outputs(N, A, self.device)
+            outs["value"] = torch.zeros((self.n_trainable, N), dtype=torch.float32, device=self.device)
+        name = "cda_mlp_league_act" if greedy else "cda_mlp_league_step"
+        _check(self.L.fn(name)(C.byref(self._struct), obs.data_ptr(), int(first_market), int(n_markets), A, int(seed) & (2 ** 64 - 1), counter.data_ptr(), int(draw),
+                               *[outs[k].data_ptr() for k in _ACT_KEYS], N, None, None, 0, _stream(self.device)), name)
+        return outs
+
 
 class RolloutChains:
     """Whole rollouts of a CDAVecEnv (auto_reset on) under a FusedPolicy as G independent chains: chain g = the markets of group g, on
@@ -412,12 +451,15 @@ class RolloutChains:
     capture_ends: episode-end capture (include/cda.h cda_step_range_capture): the last observation of every episode that ends inside the rollout is kept
         (fin_obs / fin_index) - gae() then bootstraps time-limit truncations with V(that observation), as RLlib does.
     info_markets = S > 0: the LAST S markets are a chain of their own that also writes the info tensors of every step into [T, S, ...] buffers
-        (`info`: what BatchedEpisodeRecorder.record_rollout reads; the reference records one episode in N, train/episode_record.py:197)."""
+        (`info`: what BatchedEpisodeRecorder.record_rollout reads; the reference records one episode in N, train/episode_record.py:197).
+    greedy: the evaluation chains (cda_mlp_eval_chain / cda_mlp_league_eval_chain): every network slot plays the MODE of its distribution (FusedPolicy.act),
+        each step is two launches (mode-action network kernel, env step); random-module slots of a bank still draw."""
 
-    def __init__(self, env, policy, horizon, groups=4, seed=0, use_graphs=True, with_dist=False, capture_ends=False, info_markets=0):
+    def __init__(self, env, policy, horizon, groups=4, seed=0, use_graphs=True, with_dist=False, capture_ends=False, info_markets=0, greedy=False):
         from ._lib import RolloutBufs
         from . import _capi as K
         self.env, self.policy, self.T = env, policy, int(horizon)
+        self.greedy = bool(greedy)
         self.bank = policy if isinstance(policy, PolicyBank) else None
         N, A, dev, T = env.n_markets, env.num_agents, env.device, int(horizon)
         self.L = L = policy.L
@@ -512,8 +554,11 @@ class RolloutChains:
         ctr = self._counters[g:].data_ptr()
         with torch.cuda.device(self.device):
             if self.bank is not None:
-                _check(self.L.fn("cda_mlp_league_rollout_chain")(self.env._h, C.byref(self.bank.struct()), first, cnt, self.T, self.seed, ctr,
-                                                                 C.byref(self._cbufs[g]), int(copy_first_obs), st), "cda_mlp_league_rollout_chain")
+                name = "cda_mlp_league_eval_chain" if self.greedy else "cda_mlp_league_rollout_chain"
+                _check(self.L.fn(name)(self.env._h, C.byref(self.bank.struct()), first, cnt, self.T, self.seed, ctr, C.byref(self._cbufs[g]), int(copy_first_obs), st), name)
+            elif self.greedy:
+                _check(self.L.fn("cda_mlp_eval_chain")(self.env._h, self.policy.wb.data_ptr(), self.policy.theta.data_ptr(), first, cnt, self.T,
+                                                       C.byref(self._cbufs[g]), int(copy_first_obs), st), "cda_mlp_eval_chain")
             else:
                 _check(self.L.fn("cda_mlp_rollout_chain")(self.env._h, self.policy.wb.data_ptr(), self.policy.theta.data_ptr(), first, cnt, self.T, self.seed,
                                                           ctr, C.byref(self._cbufs[g]), int(copy_first_obs), st), "cda_mlp_rollout_chain")
@@ -807,3 +852,61 @@ class FusedUpdate:
                 self.minibatch_step(s, rows, acts, logp_old, adv, ret, clip, vf_coef, ent_coef, lr, betas, eps, max_norm, records=records,
                                     obs_rows=obs_rows if fused else None)
         return {"pg_loss": self.out6[0], "v_loss": self.out6[1], "entropy": self.out6[2], "kl": self.out6[6]}
+
+
+# ---- policy files ------------------------------------------------------------------------------------------------------------------
+POLICY_FORMAT, POLICY_VERSION = "cda-mlp-policy", 1
+
+
+def policy_record(policy, row=None):
+    """the dict a policy file holds: {"format", "version", "theta" (f32, CPU), "n_hist", "hidden", "state_dependent_log_std"}.  policy: a FusedPolicy, a PolicyBank
+    with its `row`, or a parameter vector (CPU or device tensor)"""
+    if isinstance(policy, PolicyBank):
+        if row is None:
+            raise ValueError("a PolicyBank needs the bank row to save (row=...)")
+        theta = policy.theta[int(row)]
+    elif isinstance(policy, FusedPolicy):
+        if row is not None:
+            raise ValueError("row= names a row of a PolicyBank")
+        theta = policy.theta
+    else:
+        theta = policy
+    theta = theta.detach().to("cpu", torch.float32).contiguous().clone()
+    L = layout_of_params(theta.numel())
+    return {"format": POLICY_FORMAT, "version": POLICY_VERSION, "theta": theta, "n_hist": L.hist, "hidden": list(hidden_widths(theta)),
+            "state_dependent_log_std": has_log_std_head(theta)}
+
+
+def save_policy(path, policy, row=None):
+    """write a policy file (one torch.save dict, policy_record): a FusedPolicy, or row `row` of a PolicyBank (a trainable net or a champion snapshot)"""
+    torch.save(policy_record(policy, row), path)
+
+
+def check_policy_record(rec):
+    """validate a policy file's dict: format tag, version, and the metadata against the parameter vector it carries; returns the vector (f32, CPU)"""
+    if not isinstance(rec, dict) or rec.get("format") != POLICY_FORMAT:
+        raise ValueError(f"not a policy file (format tag {rec.get('format') if isinstance(rec, dict) else type(rec).__name__!r}, want {POLICY_FORMAT!r})")
+    if rec.get("version") != POLICY_VERSION:
+        raise ValueError(f"policy file version {rec.get('version')!r} is not supported (this build reads version {POLICY_VERSION})")
+    theta = rec.get("theta")
+    if not isinstance(theta, torch.Tensor) or theta.dtype != torch.float32 or theta.dim() != 1:
+        raise ValueError("a policy file's theta must be a 1-d float32 tensor")
+    L = layout_of_params(theta.numel())                                 # (ValueError: no compiled depth has this many parameters)
+    if int(rec.get("n_hist", -1)) != L.hist:
+        raise ValueError(f"policy file says n_hist = {rec.get('n_hist')!r}, its parameter vector is laid out for {L.hist}")
+    if list(rec.get("hidden", ())) != list(hidden_widths(theta)):
+        raise ValueError(f"policy file says hidden = {rec.get('hidden')!r}, its parameter vector has {list(hidden_widths(theta))}")
+    if bool(rec.get("state_dependent_log_std")) != has_log_std_head(theta) or not isinstance(rec.get("state_dependent_log_std"), bool):
+        raise ValueError(f"policy file says state_dependent_log_std = {rec.get('state_dependent_log_std')!r}, its parameter vector says {has_log_std_head(theta)}")
+    return theta
+
+
+def read_policy(path):
+    """a policy file's parameter vector (f32, CPU), validated (check_policy_record); no device needed"""
+    return check_policy_record(torch.load(path, map_location="cpu", weights_only=True))
+
+
+def load_policy(path, device):
+    """a policy file -> a FusedPolicy on `device` (theta bit-equal to the saved vector, wb re-packed from it)"""
+    theta = read_policy(path)
+    return FusedPolicy(device, theta=theta, state_dependent_log_std=has_log_std_head(theta))

@@ -715,6 +715,7 @@ def main(argv=None):
     p.add_argument("--log-std-head", action="store_true", help="fused loop: the state-dependent log-std head (RLlib's default module for Box actions) instead of a free log_std vector")
     p.add_argument("--objective", choices=("ppo", "rllib"), default="ppo", help="fused loop: PPO_DEFAULTS, or RLLIB_DEFAULTS = the objective the reference's RLlib run optimises "
                                                                               "(clip 0.3, lambda 1, vf coeff 1, entropy 0, vf clip 10, adaptive KL penalty, no gradient clipping, truncation bootstrap)")
+    p.add_argument("--save", default=None, metavar="PATH", help="fused loop: write the trained policy to this file (mlp.save_policy; evaluate.py reads it)")
     args = p.parse_args(argv)
     from .vec_env import CDAVecEnv
     p_groups = max(1, min(args.groups, args.markets))
@@ -725,10 +726,12 @@ def main(argv=None):
         # the fused kernels step whole 32-row tiles and are compiled per history depth: other shapes run the PyTorch statement of the same loop
         print(json.dumps({"note": f"fused loop needs horizon * markets % 32 == 0 and n_hist in {HIST_VARIANTS} (got {args.horizon} x {args.markets}, n_hist {env.n_hist}): running the legacy loop"}))
         args.legacy = True
+    if args.save and args.legacy:
+        raise SystemExit("--save needs the fused loop (the legacy loop's network is a PyTorch module)")
     if args.legacy:
         _, hist = train(env, iters=args.iters, horizon=args.horizon, amp=not args.fp32_update, shared_obs=not args.per_sample_forward, use_graph=not args.no_graphs)
     else:
-        _, hist = train_fused(env, iters=args.iters, horizon=args.horizon, use_graph=not args.no_graphs, chains=args.chains,
+        trained, hist = train_fused(env, iters=args.iters, horizon=args.horizon, use_graph=not args.no_graphs, chains=args.chains,
                               objective=RLLIB_DEFAULTS if args.objective == "rllib" else None, state_dependent_log_std=args.log_std_head, hidden=tuple(args.fcnet_hiddens))
     flags = env.flags()
     _, bad = env.nav_conservation()
@@ -754,6 +757,10 @@ def main(argv=None):
                "rollout_agent_steps_per_s": sum(h["agent_steps"] for h in tail) / sum(h["rollout_s"] for h in tail),
                "unit": "agent-steps/s", "flagged_markets": int((flags != 0).sum().item()), "nav_conservation_violations": int(bad.sum().item()),
                "invariant_violations": int((env.check_invariants() != 0).sum().item())}
+    if args.save:
+        from .mlp import save_policy
+        save_policy(args.save, trained)
+        summary["saved"] = args.save
     print(json.dumps(summary))
     if args.out:
         with open(args.out, "w") as fh:

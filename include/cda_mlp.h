@@ -95,6 +95,12 @@ int cda_mlp_policy_step(const void* wb, const float* theta, const float* obs, in
                         uint64_t seed, const int64_t* counter_dev, int64_t draw,
                         int32_t* env_category, float* env_size_mean, float* env_size_sigma, int32_t* env_price, int32_t* env_price_offset,
                         float* a_cont, float* logp, float* value, void* stream);
+/* The same launch with the MODE of every slot's distribution instead of a sample (evaluation; RLlib's explore=False / to_deterministic()): each categorical head
+ * its largest logit (the lowest index wins a tie: argmax), a_cont = the two Gaussian means, size_mean = tanh / size_sigma = sigmoid of the means (the sampled path's
+ * expressions), logp = the mode's log-probability (the sampled formula with zero normal draws), value as there.  Deterministic: no seed, counter or draw. */
+int cda_mlp_policy_act(const void* wb, const float* theta, const float* obs, int32_t first_market, int32_t n_markets, int32_t num_agents,
+                       int32_t* env_category, float* env_size_mean, float* env_size_sigma, int32_t* env_price, int32_t* env_price_offset,
+                       float* a_cont, float* logp, float* value, void* stream);
 /* The network outputs alone for rows [first_row, first_row + n_rows) of obs f32[*,168] -> out f32[*,32] (same row indexing). */
 int cda_mlp_forward(const void* wb, const float* theta, const float* obs, int64_t first_row, int64_t n_rows, float* out, void* stream);
 
@@ -285,9 +291,22 @@ int cda_mlp_league_step(const cda_league* league, const float* obs, int32_t firs
                         uint64_t seed, const int64_t* counter_dev, int64_t draw,
                         int32_t* env_category, float* env_size_mean, float* env_size_sigma, int32_t* env_price, int32_t* env_price_offset,
                         float* a_cont, float* logp, float* value, int64_t value_stride, float* rec, float* dist, int64_t dist_stride, void* stream);
+/* cda_mlp_league_step with the mode action (cda_mlp_policy_act's rule) on every slot a network plays, trainable or frozen; slots of the random module draw
+ * exactly as cda_mlp_league_step draws them (seed is unused, counter_dev / draw key the random module's stream). */
+int cda_mlp_league_act(const cda_league* league, const float* obs, int32_t first_market, int32_t n_markets, int32_t num_agents,
+                       uint64_t seed, const int64_t* counter_dev, int64_t draw,
+                       int32_t* env_category, float* env_size_mean, float* env_size_sigma, int32_t* env_price, int32_t* env_price_offset,
+                       float* a_cont, float* logp, float* value, int64_t value_stride, float* rec, float* dist, int64_t dist_stride, void* stream);
 /* cda_mlp_rollout_chain for a league: bufs as there except value f32 [n_trainable][T+1][N] and dist f32 [n_trainable][T][N][CDA_MLP_DIST_LD]. */
 int cda_mlp_league_rollout_chain(cda_env* env, const cda_league* league, int32_t first_market, int32_t n_markets, int32_t n_steps,
                                  uint64_t seed, const int64_t* counter_dev, const cda_rollout_bufs* bufs, int32_t copy_first_obs, void* stream);
+/* Greedy (evaluation) forms of the two chains: every step is the mode-action launch (cda_mlp_policy_act / cda_mlp_league_act) followed by the env step with auto
+ * reset (and the episode-metric tallies when they are on) - always TWO launches: the one-launch step (cda_policy_step_range) samples.  Buffers as the sampled chains';
+ * the shared policy's chain takes no seed or counter (bufs->counter_bump is still honoured). */
+int cda_mlp_eval_chain(cda_env* env, const void* wb, const float* theta, int32_t first_market, int32_t n_markets, int32_t n_steps,
+                       const cda_rollout_bufs* bufs, int32_t copy_first_obs, void* stream);
+int cda_mlp_league_eval_chain(cda_env* env, const cda_league* league, int32_t first_market, int32_t n_markets, int32_t n_steps,
+                              uint64_t seed, const int64_t* counter_dev, const cda_rollout_bufs* bufs, int32_t copy_first_obs, void* stream);
 /* cda_gae_records for a league: value f32 [n_trainable][T+1][N]; slot p < n_trainable gets advantage / return from net p's values, the other slots' records are left
  * alone; stats2k f64 [n_trainable][2]: per net, the sums its update normalises the advantages with. */
 int cda_gae_records_league(const double* reward, const float* value, const uint8_t* terminated, const uint8_t* truncated, int32_t n_steps, int64_t n_markets,
