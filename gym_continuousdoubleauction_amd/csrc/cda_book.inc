@@ -585,6 +585,7 @@ __device__ __forceinline__ void settle_fill(Lds& L, int tr, int counter, int32_t
             TF_COUNT(20);
         }
         CDA_WSYNC();
+        TF_WAVE(tr, counter);
         TF_RESYNC();
     } else if (lane == tr) {                             // init_is_counter_cash_transfer (cash_processor.py:55-62)
         Acc& a = L.acc[lane];
@@ -595,6 +596,7 @@ __device__ __forceinline__ void settle_fill(Lds& L, int tr, int counter, int32_t
     if (__ballot((f & 0xffu) != 0)) flags |= CDA_FLAG_DEC_DOMAIN;
     if (__ballot((f >> 8) != 0)) flags |= CDA_FLAG_INT_OVERFLOW;
     TF_END(19);
+    TF_WAVE_END();
 }
 
 // matching loops of OrderBook.process_order_list / process_market_order / process_limit_order

@@ -541,56 +541,58 @@ __device__ __forceinline__ int ndigits_u32(uint32_t n) {     // len(str(n)), n >
     d = n >= 1000000u ? 7 : d; d = n >= 10000000u ? 8 : d; d = n >= 100000000u ? 9 : d; d = n >= 1000000000u ? 10 : d;
     return d;
 }
-// Inexact quotients (a VWAP after almost every fill) are rounded DIRECTLY to 28 digits: the coefficient is scaled so that
-// floor(c * 10^s / n) has 26..28 digits (s from the bit length of c and the digit count of n), the long division is
-// continued digit by digit from the 32-bit remainder until there are 28, and the final remainder against n/2 decides
-// half-even - the correctly rounded quotient, which is what Decimal.__truediv__ followed by _fix produces.  A zero
-// remainder anywhere means the quotient is exact at that scale; that case (ideal exponent, trailing zeros) is left to
-// d_div_general.
-__device__ __noinline__ D d_div_inexact_leaf(D a, uint32_t n) { // a LEAF (no calls: no return-address spill to scratch)
+// The VWAP division of a fill, as ONE leaf (no calls: no return-address spill to scratch) for a divisor n < 2^30 - a position
+// size, in practice far below that.  It returns Decimal.__truediv__'s result whatever the operands (the general routine above
+// stays as the cold fallback for larger divisors):
+//   * c / n exact (zero included): c / n at the ideal exponent a.exp;
+//   * otherwise the quotient correctly rounded (half-even) to 28 digits - what the 29- or 30-digit coefficient of
+//     _pydecimal.py:1362-1376 followed by _fix produces.  The scale s is fixed UP FRONT so that q = floor(c * 10^s / n) has
+//     exactly 28 digits: with dc = len(str(c)) and ln = len(str(n)), c * 10^(27 + ln - dc) / n has 27 or 28 digits, and one
+//     compare of c * 10^s0 against n * 10^27 (< 2^120) decides which - no digit-by-digit loop;
+//   * the rare quotient that is exact at scale s but not at the ideal exponent (n = 2^i 5^j, say) loses its trailing zeros
+//     down to the ideal exponent, as __truediv__ strips them.
+// One f64 reciprocal of n serves both long divisions.
+__device__ __noinline__ D d_div_pos_leaf(D a, uint32_t n) {
     DEC_COUNT(6);
+    if (n - 1u >= (1u << 30) - 1u) return d_make(0, 0, 0, D_NOT_HANDLED, 0);
+    const double rn = 1.0 / (double)n;
     const u128 c = d_c128(a);
-    const int ln = ndigits_u32(n);
-    if (c != 0 && ln <= 9) {
-        const int dn_hi = ((bits128(c) * 1233) >> 12) + 1;        // len(str(c)) or one more
-        int s = 27 + ln - dn_hi;
-        s = s < 0 ? 0 : s;                                        // c * 10^s < 10^(27 + ln) <= 10^36 < 2^120
-        W4 x = w4_from128(c);
-        w_mul_pow10(x, s);
-        const double rn = 1.0 / (double)n;
-        uint32_t r = n < (1u << 30) ? w_div_small(x, n, rn) : w_div_u32(x, n);
-        #pragma unroll 1
-        while (r != 0 && !(x.w[2] > 0x033b2e3cu || (x.w[2] == 0x033b2e3cu && (x.w[1] > 0x9fd0803cu || (x.w[1] == 0x9fd0803cu && x.w[0] >= 0xe8000000u))))) {
-            const uint64_t r10 = (uint64_t)r * 10u;               // next quotient digit from the remainder (x < 10^27 so far)
-            uint32_t dg = (uint32_t)((double)r10 * rn);
-            int64_t rr = (int64_t)(r10 - (uint64_t)dg * n);
-            if (rr < 0) { dg -= 1; rr += n; }
-            if (rr >= (int64_t)n) { dg += 1; rr -= n; }
-            r = (uint32_t)rr;
-            uint64_t cy = dg;                                     // x = x * 10 + dg
-            #pragma unroll
-            for (int i = 0; i < 4; i++) { cy += (uint64_t)x.w[i] * 10u; x.w[i] = (uint32_t)cy; cy >>= 32; }
-            s += 1;
-        }
+    WN<3> q; q.w[0] = a.w0; q.w[1] = a.w1; q.w[2] = a.w2;
+    int s = 0;
+    if (w_div_small(q, n, rn) != 0) {                           // inexact at the ideal exponent (c != 0)
+        const int t = (bits128(c) * 1233) >> 12;                // len(str(c)) is t or t + 1, t <= 28
+        const lds_u32p pt = lds_pow10(t);
+        const u128 pw_t = ((u128)pt[2] << 64) | ((u128)pt[1] << 32) | (u128)pt[0];
+        const int s0 = 27 + ndigits_u32(n) - (t + (c >= pw_t ? 1 : 0));  // 0 .. 36
+        const lds_u32p ps = lds_pow10(s0);
+        const u128 pw_s = ((u128)ps[3] << 96) | ((u128)ps[2] << 64) | ((u128)ps[1] << 32) | (u128)ps[0];
+        const u128 x0 = c * pw_s;                               // < 10^(27 + ln) <= 10^37: exact in 128 bits
+        const u128 n27 = (u128)n * (((u128)0x033b2e3cULL << 64) | 0x9fd0803ce8000000ULL);    // n * 10^27
+        const bool d28 = x0 >= n27;
+        s = s0 + (d28 ? 0 : 1);
+        W4 x = w4_from128(d28 ? x0 : x0 * 10u);                 // < n * 10^28 < 2^124
+        const uint32_t r = w_div_small(x, n, rn);               // 10^27 <= x < 10^28: three limbs
+        q.w[0] = x.w[0]; q.w[1] = x.w[1]; q.w[2] = x.w[2];
         if (r != 0) {
-            const uint64_t twice = (uint64_t)r * 2u;
-            if (twice > n || (twice == n && (x.w[0] & 1u))) {
-                w_inc(x);
-                if (x.w[0] == 0x10000000u && x.w[1] == 0x3e250261u && x.w[2] == 0x204fce5eu) {    // reached 10^28
-                    x.w[0] = 0xe8000000u; x.w[1] = 0x9fd0803cu; x.w[2] = 0x033b2e3cu; s -= 1;     // 10^27
-                }
-            }
-            return d_make(x.w[0], x.w[1], x.w[2], a.exp - s, a.sign);
+            const uint32_t twice = r * 2u;                      // r < 2^30
+            const bool up = twice > n || (twice == n && (q.w[0] & 1u) != 0);
+            const uint64_t s0w = (uint64_t)q.w[0] + (up ? 1u : 0u);
+            const uint64_t s1w = (uint64_t)q.w[1] + (s0w >> 32);
+            uint32_t w0 = (uint32_t)s0w, w1 = (uint32_t)s1w, w2 = q.w[2] + (uint32_t)(s1w >> 32);
+            const bool ten28 = w0 == 0x10000000u && w1 == 0x3e250261u && w2 == 0x204fce5eu;          // 10^28 -> 10^27, one exponent up
+            w0 = ten28 ? 0xe8000000u : w0; w1 = ten28 ? 0x9fd0803cu : w1; w2 = ten28 ? 0x033b2e3cu : w2;
+            return d_make(w0, w1, w2, a.exp - s + (ten28 ? 1 : 0), a.sign);
         }
+        // exact at scale s only: strip trailing zeros towards the ideal exponent (c % n != 0 keeps at least one power of ten)
+        #pragma unroll 1
+        while (s >= 4) { WN<3> u = q; if (w_divc<10000u>(u) != 0) break; q = u; s -= 4; }
+        #pragma unroll 1
+        while (s >= 1) { WN<3> u = q; if (w_divc<10u>(u) != 0) break; q = u; s -= 1; }
     }
-    return d_make(0, 0, 0, D_NOT_HANDLED, 0);
+    return d_make(q.w[0], q.w[1], q.w[2], a.exp - s, a.sign);
 }
 __device__ __forceinline__ D d_div_u32(D a, uint32_t n) {
-    if (a.w2 == 0) {        // a short dividend - a position built at ONE price, the usual case early in an episode: mostly an exact
-        WN<2> x; x.w[0] = a.w0; x.w[1] = a.w1;          // quotient, which the inexact leaf would only hand on to the general routine
-        if (w_div_u32(x, n) == 0) return d_make(x.w[0], x.w[1], 0, a.exp, a.sign);     // coefficient / n at the ideal exponent (also 0 / n)
-    }
-    D r = d_div_inexact_leaf(a, n);
+    D r = d_div_pos_leaf(a, n);
     if (r.exp == D_NOT_HANDLED) r = d_div_general(a, n);
     return r;
 }

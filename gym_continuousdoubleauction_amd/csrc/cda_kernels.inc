@@ -453,7 +453,7 @@ __device__ __forceinline__ void step_loaded(const Params& P, const StepArgs& S, 
     store_levels(mp, L, lane);
     PH_MARK(ph, 9);
 #ifdef CDA_PHASE_TIMING
-    if (ph && lane == 0) for (int i = 0; i < 24; i++) ph[10 + i] = m.tacc[i];
+    if (ph && lane == 0) for (int i = 0; i < 30; i++) ph[10 + i] = m.tacc[i];
 #endif
 }
 
@@ -498,7 +498,7 @@ __attribute__((noinline, cold)) __device__ int slow_step(const StepKernArgs* ker
     const uint8_t present = *(S.present ? S.present + ab : reinterpret_cast<const uint8_t*>(S.category + ab));
     Mkt m;
 #ifdef CDA_PHASE_TIMING
-    for (int i = 0; i < 24; i++) m.tacc[i] = 0;
+    for (int i = 0; i < 30; i++) m.tacc[i] = 0;
 #endif
     load_market<true>(mp, P, L, m, lane);
 #ifdef CDA_DEBUG_SKIP
@@ -554,7 +554,7 @@ __global__ __launch_bounds__(64 * CDA_WPB, CDA_MIN_WAVES) CDA_VGPR_CAP_ATTR void
     Mkt m;
     unsigned long long* ph = nullptr;
 #ifdef CDA_PHASE_TIMING
-    for (int i = 0; i < 24; i++) m.tacc[i] = 0;
+    for (int i = 0; i < 30; i++) m.tacc[i] = 0;
     ph = S.phase_cycles ? S.phase_cycles + (size_t)mi * 40 : nullptr;
 #endif
     PH_MARK(ph, 0);
@@ -677,7 +677,7 @@ __device__ __forceinline__ int run_random_part(uint8_t* arena, const Params& P, 
     Mkt m;
     const int A = P.cfg.num_agents, H = P.cfg.n_hist, tick = P.cfg.tick_size;
 #ifdef CDA_PHASE_TIMING
-    for (int i = 0; i < 24; i++) m.tacc[i] = 0;
+    for (int i = 0; i < 30; i++) m.tacc[i] = 0;
 #endif
     {
         const MarketPrefetch q = load_market_issue<true>(mp, P, lane);

@@ -127,7 +127,8 @@ struct Mkt {
 #endif
     int32_t fills;               // fills settled in the current step (issue priority of this wave grows with it)
 #ifdef CDA_PHASE_TIMING
-    unsigned long long tacc[24];    // debug: cycles in approval / find / match+settle / insert+remove / escrow+cancel, fills, ...; 14..20: inside a fill
+    unsigned long long tacc[30];    // debug: cycles in approval / find / match+settle / insert+remove / escrow+cancel, fills, ...; 14..23: inside a fill
+                                    // (stamps of the lanes that take part), 24..29: per fill, wave-uniform (see TF_WAVE)
 #endif
 };
 #ifdef CDA_PHASE_TIMING
@@ -136,10 +137,22 @@ struct Mkt {
 #define TACC_COUNT(m, i, n) do { (m).tacc[i] += (n); } while (0)
 #define CDA_TF_PARAM , unsigned long long* tf
 #define CDA_TF_ARG(m) , (m).tacc
-#define TF_BEGIN() unsigned long long _fb = __builtin_readcyclecounter()
-#define TF_END(i) do { unsigned long long _fe = __builtin_readcyclecounter(); tf[i] += _fe - _fb; _fb = _fe; } while (0)
+#define TF_BEGIN() unsigned long long _fb = __builtin_readcyclecounter(); const unsigned long long _fw = _fb; uint32_t _fs[4] = {0u, 0u, 0u, 0u}
+// stamps 14..18, 22, 23 also add to the lane's own stage total: 0 prep, 1 stage 1, 2 stage 2 (select + add), 3 stage 3
+__device__ __forceinline__ int tf_stage(int i) { return i == 14 ? 0 : (i == 15 ? 1 : (i == 16 || i == 17 ? 2 : (i == 18 || i == 22 || i == 23 ? 3 : -1))); }
+#define TF_END(i) do { unsigned long long _fe = __builtin_readcyclecounter(); tf[i] += _fe - _fb; \
+                       if (tf_stage(i) >= 0) _fs[tf_stage(i) & 3] += (uint32_t)(_fe - _fb); _fb = _fe; } while (0)
 #define TF_COUNT(i) do { tf[i] += 1; } while (0)
 #define TF_RESYNC() do { _fb = __builtin_readcyclecounter(); } while (0)
+// Per fill, on every lane (wave-uniform): what the WAVE waited for in each stage - the longer of the two owner lanes (an
+// account's owner lane is lane == account), whichever parties the lanes serve - in tacc[25..28], the whole fill in tacc[24],
+// fills that settle two parties in tacc[29].  The per-lane stamps above only accumulate on lanes that own a party.
+#define TF_WAVE(tr, counter) do { \
+        _Pragma("unroll") for (int _k = 0; _k < 4; _k++) { \
+            const uint32_t _a = (uint32_t)__builtin_amdgcn_readlane((int)_fs[_k], (tr)), _b = (uint32_t)__builtin_amdgcn_readlane((int)_fs[_k], (counter)); \
+            tf[25 + _k] += _a > _b ? _a : _b; } \
+        tf[29] += 1; } while (0)
+#define TF_WAVE_END() do { tf[24] += __builtin_readcyclecounter() - _fw; } while (0)
 #else
 #define CDA_TF_PARAM
 #define CDA_TF_ARG(m)
@@ -147,6 +160,8 @@ struct Mkt {
 #define TF_END(i) do {} while (0)
 #define TF_COUNT(i) do {} while (0)
 #define TF_RESYNC() do {} while (0)
+#define TF_WAVE(tr, counter) do {} while (0)
+#define TF_WAVE_END() do {} while (0)
 #define TACC_BEGIN() do {} while (0)
 #define TACC_END(m, i) do {} while (0)
 #define TACC_COUNT(m, i, n) do {} while (0)

@@ -94,7 +94,7 @@ __global__ __launch_bounds__(64 * PS_WPB, 1) void PS_NAME(k_policy_step)(PolicyS
     const unsigned long long* zig_ki = zig_wi + 256;
     Mkt m;
 #ifdef CDA_PHASE_TIMING
-    for (int i = 0; i < 24; i++) m.tacc[i] = 0;
+    for (int i = 0; i < 30; i++) m.tacc[i] = 0;
 #endif
     load_market_finish<true, false>(mp, P, L, m, mq, lane);
 #ifdef CDA_DEBUG_SKIP

@@ -12,11 +12,19 @@ import numpy as np
 import torch
 
 so = os.path.join(ROOT, "gpurun_out", "libcda_hip_timing.so")
-os.makedirs(os.path.dirname(so), exist_ok=True)
 COUNTERS = "--counters" in sys.argv      # atomics in every out-of-line decimal routine: call counts, but the cycle stamps are then meaningless
+PREBUILT = sys.argv[sys.argv.index("--lib") + 1] if "--lib" in sys.argv else None     # a -DCDA_PHASE_TIMING library built beforehand (e.g. of another tree)
+if PREBUILT:
+    so = os.path.abspath(PREBUILT)
+os.makedirs(os.path.dirname(so), exist_ok=True)
 import __graft_entry__ as G   # the product's own flags + the timing macro
-subprocess.check_call(["hipcc"] + G.HIPCC_FLAGS + ["-DCDA_PHASE_TIMING"] + (["-DCDA_DEC_COUNTERS"] if COUNTERS else []) + ["-o", so, os.path.join(ROOT, "gym_continuousdoubleauction_amd", "csrc", "cda_hip.hip"), os.path.join(ROOT, "gym_continuousdoubleauction_amd", "csrc", "cda_ppo.hip"),
-                       os.path.join(ROOT, "gym_continuousdoubleauction_amd", "csrc", "cda_mlp.hip")])      # (the whole library: _lib binds every symbol of both headers)
+if "--build-only" in sys.argv or not PREBUILT:
+    subprocess.check_call(["hipcc"] + G.HIPCC_FLAGS + ["-DCDA_PHASE_TIMING"] + (["-DCDA_DEC_COUNTERS"] if COUNTERS else []) + ["-o", so, os.path.join(ROOT, "gym_continuousdoubleauction_amd", "csrc", "cda_hip.hip"), os.path.join(ROOT, "gym_continuousdoubleauction_amd", "csrc", "cda_ppo.hip"),
+                           os.path.join(ROOT, "gym_continuousdoubleauction_amd", "csrc", "cda_mlp.hip")]
+                          + ["-Wl," + os.path.join(ROOT, "gym_continuousdoubleauction_amd", "build_tmp", f"cda_mlp_h{h}.o") for h in G.MLP_HIST_VARIANTS])
+    # (the whole library: _lib binds every symbol of both headers, the network's extra history depths too - their objects as build() left them)
+if "--build-only" in sys.argv:
+    sys.exit(0)
 from gym_continuousdoubleauction_amd import _lib
 _lib.LIB_PATH = so
 from gym_continuousdoubleauction_amd import CDAVecEnv
@@ -31,7 +39,8 @@ L.cda_debug_set_phase_buffer(C.c_void_p(buf.data_ptr()))
 g = torch.Generator(device="cuda:0"); g.manual_seed(1)
 names = ["load", "snapshot_pre", "decode+rng", "shuffle", "orders", "mtm", "snapshot_post+obs", "reward/info", "store"]
 acc = np.zeros(9); span = 0.0
-tot_all = []; worst = None; sub = np.zeros(24); sub_worst = None; sub_slow = np.zeros(24); ph_slow = np.zeros(9)
+tot_all = []; worst = None; sub = np.zeros(30); sub_worst = None; sub_slow = np.zeros(30); ph_slow = np.zeros(9)
+slow_fill_rows = []   # per step: the slowest wave's [fills, per-fill wave stamps 24..29]
 T, W = 300, 200
 calls = (C.c_ulonglong * 8)()
 if COUNTERS:
@@ -50,13 +59,14 @@ for t in range(W + T):
         d = b[:, 1:10] - b[:, 0:9]
         acc += d.mean(axis=0)
         span += (b[:, 9].max() - b[:, 0].min())
-        sub += b[:, 10:34].mean(axis=0)
+        sub += b[:, 10:40].mean(axis=0)
         tw = d.sum(axis=1)
         tot_all.append(tw)
         i = int(tw.argmax())
-        sub_slow += b[i, 10:34]; ph_slow += d[i]
+        sub_slow += b[i, 10:40]; ph_slow += d[i]
+        slow_fill_rows.append(b[i, 10:40].copy())
         if worst is None or tw[i] > worst[0]:
-            worst = (tw[i], d[i].copy(), t, i); sub_worst = b[i, 10:34].copy()
+            worst = (tw[i], d[i].copy(), t, i); sub_worst = b[i, 10:40].copy()
 acc /= T
 tot = acc.sum()
 print(f"mean cycles per wave per step: {tot:.0f}; kernel span (first start -> last end) {span / T:.0f} cycles")
@@ -72,13 +82,26 @@ print("slowest wave seen: %.0f cycles at step %d market %d; phases:" % (worst[0]
 subn = ["approval", "find_own", "match+settle", "insert/remove(after match)", "cancel/escrow/other", "fills",
         "book_remove/in-place", "release transfer", "escrow transfer", "x9", "n_modify", "n_escrow", "lane-0 fills in mode 0", "x13",
         "fill:prep(mode,tv)", "fill:stage1 mul", "fill:stage2 select", "fill:stage2 add", "fill:stage3 (modes 1, 2)", "fill:tail(sync,ballots)", "fills with lane 0 involved", "lane-0 fills in mode 3/4", "fill:stage3 (covered)", "fill:stage3 (neutral)"]
-print("orders phase breakdown, mean per wave per step:", {n: round(v / T, 1) for n, v in zip(subn, sub)})
-print("orders phase breakdown, slowest wave:", dict(zip(subn, sub_worst.astype(int).tolist())))
+# the old printout (its fill:* stamps accumulate on lane 0 only, i.e. only in fills that lane 0's account takes part in)
+print("orders phase breakdown, mean per wave per step:", {n: round(v / T, 1) for n, v in zip(subn, sub[:24])})
+print("orders phase breakdown, slowest wave:", dict(zip(subn, sub_worst[:24].astype(int).tolist())))
 print("the slowest wave of each step, averaged over the steps - phases:", dict(zip(names, (ph_slow / T).astype(int).tolist())))
-print("  its orders phase:", {n: round(v / T, 1) for n, v in zip(subn, sub_slow)})
+print("  its orders phase:", {n: round(v / T, 1) for n, v in zip(subn, sub_slow[:24])})
+
+# every fill counted (tacc[24..29], wave-uniform: each stage is the longer of the two owner lanes - what the wave waits for)
+fn = ["fill (whole settle_fill)", "prep", "stage 1 (mul)", "stage 2 (select + add)", "stage 3 (VWAP division / covered)"]
+def per_fill(row_sum):
+    f = max(row_sum[5], 1e-9)
+    return {n: round(row_sum[c] / f, 1) for n, c in zip(fn, (24, 25, 26, 27, 28))}
+print()
+print("per-fill cycles, every fill counted")
+print("  mean wave:    fills per wave-step %.2f (two-party %.2f);" % (sub[5] / T, sub[29] / T), per_fill(sub))
+sr = np.array(slow_fill_rows)
+print("  slowest wave of each step: fills %.2f (two-party %.2f), match+settle %.0f cycles;" % (sr[:, 5].mean(), sr[:, 29].mean(), sr[:, 2].mean()), per_fill(sr.sum(axis=0)))
+print("  slowest wave per step: mean %.0f cycles" % per_step_max.mean())
 
 if not COUNTERS:
     sys.exit(0)
 torch.cuda.synchronize(); L.cda_debug_dec_calls(calls, 0)
-cn = ["d_fix_mid", "d_fix_wide", "d_round_mid", "d_add_wide", "d_add_mid", "d_div_general", "d_div_u32", "d_to_double_slow"]
+cn = ["d_fix_mid", "d_fix_wide", "d_round_mid", "d_add_wide", "d_add_mid", "d_div_general", "d_div_pos_leaf", "d_to_double_slow"]
 print("out-of-line decimal calls per market-step (lanes counted individually):", {n: round(calls[i] / (T * N), 2) for i, n in enumerate(cn)})
