@@ -130,6 +130,19 @@ ENV_DEFAULTS = {
 }
 
 
+class SnapshotHeader(C.Structure):
+    """cda_snapshot_header (include/cda.h): the first 256 bytes of a snapshot blob"""
+    _fields_ = [("magic", C.c_uint32), ("version", C.c_uint32), ("header_bytes", C.c_int32), ("n_markets", C.c_int32), ("total_bytes", C.c_int64),
+                ("book_capacity", C.c_int32), ("record_stride", C.c_int32), ("n_hist", C.c_int32), ("num_agents", C.c_int32),
+                ("spill_cap", C.c_int32), ("episode_metrics_on", C.c_int32), ("nav_tolerance", C.c_double),
+                ("first_market", C.c_int32), ("em_agent_fields", C.c_int32), ("em_env_fields", C.c_int32), ("section_meta_bytes", C.c_int32),
+                ("cfg", Config), ("reserved", C.c_uint8 * 88)]
+
+
+SNAP_MAGIC = 0x53414443          # "CDAS"
+SNAP_VERSION = 1
+
+
 def make_config(config=None):
     """Env-config dict (reference keys, continuousDoubleAuction_env.py:27-55) -> Config struct.
 

@@ -22,6 +22,7 @@ SYMBOLS = [
     "cda_get_book", "cda_book_spill", "cda_book_spill_wanted", "cda_num_agents", "cda_handback_stride", "cda_set_handback", "cda_set_handback_geometry", "cda_handback_unpack", "cda_ppo_loss", "cda_policy_sample", "cda_gae", "cda_store_slots", "cda_step_groups_handback", "cda_handback_groups",
     "cda_step_range_capture", "cda_policy_step_supported", "cda_policy_step_advised", "cda_policy_step_range",
     "cda_episode_metrics_enable", "cda_episode_metrics_collect",
+    "cda_snapshot_table_bytes", "cda_snapshot_offsets", "cda_snapshot_pack", "cda_snapshot_check_header", "cda_snapshot_restore",
 ]
 
 
@@ -118,6 +119,12 @@ def lib():
     L.cda_obs_dim.argtypes = [vp]
     L.cda_state_bytes_per_market.argtypes = [vp]
     L.cda_state_bytes_per_market.restype = i64
+    L.cda_snapshot_table_bytes.argtypes = [i32]
+    L.cda_snapshot_table_bytes.restype = i64
+    L.cda_snapshot_offsets.argtypes = [vp, i32, i32, vp, vp]
+    L.cda_snapshot_pack.argtypes = [vp, i32, i32, vp, vp, i64, vp]
+    L.cda_snapshot_check_header.argtypes = [vp, C.POINTER(K.SnapshotHeader), i64]
+    L.cda_snapshot_restore.argtypes = [vp, i32, vp, i64, i32, i32, vp, vp]
     f32 = C.c_float
     L.cda_mlp_tile_rows.argtypes = []
     L.cda_mlp_tile_rows.restype = i32

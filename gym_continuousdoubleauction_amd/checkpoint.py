@@ -1,0 +1,190 @@
+"""Resumable training runs: checkpoint directories and the learner-state records the fused loops save and restore.
+
+The run surface of the reference (config/train_config.json "run": chkpt_freq, chkpt_keep, is_restore, restore_path, num_iters_is_delta): a checkpoint
+is a directory `iter_<n>` (n = iterations completed, 1-based) under the run's checkpoint directory, written as `iter_<n>.tmp` and renamed when complete;
+the newest `keep` are kept.  A restore takes the newest one (or a named one); the iteration count is then the TARGET, unless iters_is_delta.
+
+A checkpoint holds everything the next iteration reads, so that a resumed run continues the same markets, RNG streams and episodes bit for bit:
+    env.snap        the env's snapshot file (snapshot.save_snapshot: every market, spilled books included)
+    state.pt        {"format", "version", "kind", "iteration", "run_id", "args"} + the learner: per trained net theta / adam_m / adam_v / adam_step,
+                    the rollout chains' seed and counters, the update's shuffle seed and epoch count, the KL coefficient, the running episode returns
+    league/         (league checkpoints) save_league's policy files of every bank row and its league.json
+Everything here is host code; only the env snapshot needs the device."""
+import os
+import re
+import shutil
+import uuid
+
+import torch
+
+CHECKPOINT_FORMAT = "cda-train-checkpoint"
+CHECKPOINT_VERSION = 1
+STATE_FILE = "state.pt"
+ENV_FILE = "env.snap"
+_NAME = re.compile(r"^iter_(\d+)$")
+
+
+def checkpoint_name(n_done):
+    return f"iter_{int(n_done)}"
+
+
+def is_checkpoint(path):
+    return os.path.isdir(path) and _NAME.match(os.path.basename(os.path.normpath(path))) is not None and os.path.isfile(os.path.join(path, STATE_FILE))
+
+
+def list_checkpoints(checkpoint_dir):
+    """[(n, path)] of the complete checkpoints under checkpoint_dir, oldest first (staging `.tmp` directories and anything else are skipped)"""
+    if checkpoint_dir is None or not os.path.isdir(checkpoint_dir):
+        return []
+    out = []
+    for name in os.listdir(checkpoint_dir):
+        m = _NAME.match(name)
+        path = os.path.join(checkpoint_dir, name)
+        if m and is_checkpoint(path):
+            out.append((int(m.group(1)), path))
+    return sorted(out)
+
+
+def newest_checkpoint(checkpoint_dir):
+    cks = list_checkpoints(checkpoint_dir)
+    return cks[-1][1] if cks else None
+
+
+def resolve_restore(checkpoint_dir, restore):
+    """restore=True: the newest checkpoint under checkpoint_dir (FileNotFoundError if there is none); a path: that checkpoint (ValueError if it is not one)"""
+    if restore is True:
+        path = newest_checkpoint(checkpoint_dir)
+        if path is None:
+            raise FileNotFoundError(f"restore=True but {checkpoint_dir!r} holds no checkpoint")
+        return path
+    path = os.fspath(restore)
+    if not is_checkpoint(path):
+        raise ValueError(f"{path!r} is not a checkpoint (an iter_<n> directory holding {STATE_FILE})")
+    return path
+
+
+def iteration_range(done, iters, iters_is_delta=False):
+    """the iterations a run still runs (0-based global numbers): `iters` is the target count, or - iters_is_delta - the number of further iterations"""
+    done = int(done)
+    target = done + int(iters) if iters_is_delta else int(iters)
+    return range(done, max(done, target))
+
+
+def prune(checkpoint_dir, keep):
+    """remove all but the newest `keep` checkpoints (keep <= 0 keeps all)"""
+    if keep is None or int(keep) <= 0:
+        return
+    for _, path in list_checkpoints(checkpoint_dir)[:-int(keep)]:
+        shutil.rmtree(path, ignore_errors=True)
+
+
+def save_checkpoint(checkpoint_dir, n_done, state, env_snapshot=None, keep=3, extra_dirs=None):
+    """write iter_<n_done> (staged as iter_<n_done>.tmp, renamed when complete), then prune to `keep`; returns its path.  extra_dirs {name: directory}:
+    directories written beforehand (the league's policy files) that are moved into the checkpoint as <name>/"""
+    from .snapshot import save_snapshot
+    os.makedirs(checkpoint_dir, exist_ok=True)
+    final = os.path.join(checkpoint_dir, checkpoint_name(n_done))
+    tmp = final + ".tmp"
+    shutil.rmtree(tmp, ignore_errors=True)
+    os.makedirs(tmp)
+    for name, src in (extra_dirs or {}).items():
+        shutil.move(src, os.path.join(tmp, name))
+    rec = dict(state, format=CHECKPOINT_FORMAT, version=CHECKPOINT_VERSION, iteration=int(n_done))
+    torch.save(rec, os.path.join(tmp, STATE_FILE))
+    if env_snapshot is not None:
+        save_snapshot(os.path.join(tmp, ENV_FILE), env_snapshot)
+    if os.path.exists(final):
+        shutil.rmtree(final)
+    os.rename(tmp, final)
+    prune(checkpoint_dir, keep)
+    return final
+
+
+def check_state_record(rec):
+    if not isinstance(rec, dict) or rec.get("format") != CHECKPOINT_FORMAT:
+        raise ValueError(f"not a training checkpoint (format tag {rec.get('format') if isinstance(rec, dict) else type(rec).__name__!r}, want {CHECKPOINT_FORMAT!r})")
+    if rec.get("version") != CHECKPOINT_VERSION:
+        raise ValueError(f"checkpoint version {rec.get('version')!r} is not supported (this build reads version {CHECKPOINT_VERSION})")
+    for k in ("kind", "iteration", "args", "run_id"):
+        if k not in rec:
+            raise ValueError(f"checkpoint record lacks {k!r}")
+    return rec
+
+
+def load_checkpoint(path):
+    """(state dict, env Snapshot on the CPU or None) of a checkpoint directory; validated, no device needed"""
+    from .snapshot import load_snapshot
+    rec = check_state_record(torch.load(os.path.join(path, STATE_FILE), map_location="cpu", weights_only=True))
+    env_path = os.path.join(path, ENV_FILE)
+    return rec, (load_snapshot(env_path) if os.path.exists(env_path) else None)
+
+
+def check_args(saved, now):
+    """a resumed run must be the same run: every field of the saved loop arguments must equal the new one (ValueError naming the first that differs)"""
+    for k in sorted(set(saved) | set(now)):
+        if saved.get(k) != now.get(k):
+            raise ValueError(f"checkpoint was written by a run with {k} = {saved.get(k)!r}, this run has {k} = {now.get(k)!r}")
+
+
+def new_run_id():
+    return uuid.uuid4().hex
+
+
+# ---- learner-state records -------------------------------------------------------------------------------------------------------
+def net_record(policy):
+    """a FusedPolicy's trained state: theta and its Adam moments and step (CPU tensors)"""
+    return {k: getattr(policy, k).detach().cpu().clone() for k in ("theta", "adam_m", "adam_v", "adam_step")}
+
+
+def load_net_record(policy, rec):
+    for k in ("theta", "adam_m", "adam_v", "adam_step"):
+        dst, src = getattr(policy, k), rec[k]
+        if tuple(dst.shape) != tuple(src.shape) or dst.dtype != src.dtype:
+            raise ValueError(f"checkpoint {k} has shape {tuple(src.shape)} / {src.dtype}, the policy has {tuple(dst.shape)} / {dst.dtype}")
+        dst.copy_(src)
+    policy.pack()
+
+
+def rollout_record(roll):
+    return {"seed": int(roll.seed), "counters": roll._counters.detach().cpu().clone()}
+
+
+def load_rollout_record(roll, rec):
+    if int(rec["seed"]) != int(roll.seed):
+        raise ValueError(f"checkpoint rollout seed {rec['seed']} != {roll.seed}")
+    if tuple(rec["counters"].shape) != tuple(roll._counters.shape):
+        raise ValueError(f"checkpoint has {rec['counters'].numel()} rollout chains, this run has {roll._counters.numel()}")
+    roll._counters.copy_(rec["counters"])
+
+
+def update_record(upd):
+    return {"shuffle_seed": int(upd.shuffle_seed), "epochs_done": int(upd._epochs_done)}
+
+
+def load_update_record(upd, rec):
+    upd.shuffle_seed, upd._epochs_done = int(rec["shuffle_seed"]), int(rec["epochs_done"])
+
+
+def returns_record(returns):
+    """mlp.EpisodeReturns: the running return of every episode in progress (what history's episode_return of a later iteration adds to)"""
+    return {"running": returns.running.detach().cpu().clone()}
+
+
+def load_returns_record(returns, rec):
+    if tuple(rec["running"].shape) != tuple(returns.running.shape):
+        raise ValueError(f"checkpoint episode returns have shape {tuple(rec['running'].shape)}, this run has {tuple(returns.running.shape)}")
+    returns.running.copy_(rec["running"])
+
+
+def check_resumable(checkpoint_dir, chkpt_freq, restore, world=1, allreduce=None, recorder=None):
+    """the refusals shared by both fused loops; returns whether the run is resumable (checkpoints written or a restore asked for)"""
+    if int(chkpt_freq) < 0:
+        raise ValueError("chkpt_freq must be >= 0")
+    if int(chkpt_freq) > 0 and checkpoint_dir is None:
+        raise ValueError("chkpt_freq > 0 needs a checkpoint_dir")
+    resumable = checkpoint_dir is not None or bool(restore)
+    if resumable and (world > 1 or allreduce is not None):
+        raise ValueError("checkpoint / restore: data-parallel runs (world > 1) are not supported")
+    if resumable and recorder is not None:
+        raise ValueError("checkpoint / restore: an episode recorder's files cannot be resumed; run without a recorder")
+    return resumable

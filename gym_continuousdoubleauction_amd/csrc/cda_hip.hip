@@ -13,6 +13,7 @@
 //                      k_place_order   Trader.place_order     agent/trader.py:49-106   (test hook, 1 market)
 //                      k_mark_to_mkt   Exchg_Helper.mark_to_mkt                         (test hook, 1 market)
 //                      k_raw_snapshot  agg_LOB_raw            exchg/state_helper.py:159-160
+//   cda_snapshot.inc k_snap_offsets, k_snap_pack, k_snap_check, k_snap_restore and the cda_snapshot_* entry points (included at the end)
 //   here             k_init_arena, k_random_actions, k_nav_conservation, k_check_invariants, k_flags, k_book_peak, k_handback_unpack,
 //                    self-tests, and the host side: arena, capacity dispatch, every extern "C" entry point
 //   (the measuring probes - operation micro-benchmark, clock probe, PMC calibration - live in tools/csrc/cda_tools.hip, a
@@ -626,6 +627,7 @@ struct cda_env {
     int64_t hb_row_stride, hb_rows_total;   // cda_set_handback_geometry: rows between two ranks' first markets / global row count (0, 0 = equal shards of N)
     int32_t spill_wanted;    // orders per side the spill ring was asked to hold (automatic: num_agents * max_step rounded up); P.lay.spill_cap is what it got
     double* em_partials;     // cda_episode_metrics_collect: the blocks' partial sums (EM_BLOCKS rows)
+    uint32_t* snap_flag;     // cda_snapshot_restore: the check pass's verdict (allocated at the first restore)
 };
 static inline int32_t handback_stride_of(int32_t num_agents) { return (CDA_SNAPSHOT_DIM * 4 + num_agents * 8 + 3 + 7) & ~7; }
 
@@ -758,6 +760,7 @@ int cda_destroy(cda_env* e) {
     (void)hipSetDevice(e->device);
     (void)hipFree(e->arena);
     if (e->em_partials) (void)hipFree(e->em_partials);
+    if (e->snap_flag) (void)hipFree(e->snap_flag);
     free(e);
     return CDA_OK;
 }
@@ -1462,3 +1465,6 @@ int32_t cda_obs_dim(const cda_env* e) { return e ? e->P.cfg.n_hist * CDA_SNAPSHO
 int64_t cda_state_bytes_per_market(const cda_env* e) { return e ? (int64_t)e->P.lay.stride : 0; }
 
 }  // extern "C"
+
+// device snapshot / restore of a market range (cda_snapshot_*): kernels and entry points
+#include "cda_snapshot.inc"

@@ -21,6 +21,8 @@ Two loops:
 import argparse
 import copy
 import json
+import os
+import shutil
 import time
 
 import torch
@@ -169,7 +171,8 @@ class League:
 def train_league_fused(env, iters=4, horizon=None, num_trainable=2, lr=5e-5, epochs=4, seed=0, original_opponent_weight=1.0, champion_weight=3.0,
                        std_dev_multiplier=0.1, max_champions=8, min_iterations_between_champions=2, chains=4, minibatch=262144, objective=None, use_graph=True,
                        recorder=None, info_markets=0, run_id="league", log=print, keep=None, allreduce=None, world=1, first_market=0, episode_metrics=True,
-                       strict_nav_check=True, state_dependent_log_std=False, hidden=(256, 256)):
+                       strict_nav_check=True, state_dependent_log_std=False, hidden=(256, 256),
+                       checkpoint_dir=None, chkpt_freq=0, chkpt_keep=3, restore=None, iters_is_delta=False):
     """League self-play on the fused kernels (include/cda_mlp.h `cda_league`): the reference's training topology - `num_trainable` SEPARATELY trained policies
     (policy_p plays slot p), every other slot drawn per episode from the pool of uniform random modules and frozen champions by the reference's mapping rule
     (computed on the device, league.LeagueSlotMapper.assign_device) - at the speed of the fused loop: ONE policy launch per step serves every module of every
@@ -182,7 +185,13 @@ def train_league_fused(env, iters=4, horizon=None, num_trainable=2, lr=5e-5, epo
     allreduce / world / first_market: the data-parallel learner of ppo.train_fused for the league - every rank rolls out and back-propagates its own shard of
     markets (global indices [first_market, first_market + N): env seeds, sampling keys and EPISODE IDS follow them, so the opponents a market meets do not depend
     on the GPU count), the ranks sum each policy's gradient (one all-reduce of 0.9 MB per policy and minibatch step) and advantage sums, and the per-module returns
-    behind the promotion rule - so every rank promotes the same champions in lockstep."""
+    behind the promotion rule - so every rank promotes the same champions in lockstep.
+    checkpoint_dir / chkpt_freq / chkpt_keep / restore / iters_is_delta (all off by default): a resumable run, as in ppo.train_fused (checkpoint.py).  A league
+    checkpoint is taken only at an EPISODE BOUNDARY ((it + 1) % per_episode == 0, where no opponent window is open): chkpt_freq must be a multiple of
+    max_step / horizon (ValueError otherwise), and the final save is skipped when the run does not end on a boundary.  It holds the env snapshot, every
+    trainable net (theta + Adam), every bank row as save_league's policy files (league/ in the checkpoint) plus the bank's packed weights, the League and mapper
+    state (champions and their rows, promotion history, champion id counter, pool), the rollout counters, the updates' shuffle state, the KL coefficients and
+    the running episode returns: the mapping, episode ids and promotions continue exactly.  Single-process runs only; no recorder."""
     import numpy as np
     from . import ppo
     from .mlp import EpisodeReturns, FusedUpdate, PolicyBank, RolloutChains
@@ -194,12 +203,37 @@ def train_league_fused(env, iters=4, horizon=None, num_trainable=2, lr=5e-5, epo
     if int(env.max_step) % T:
         raise ValueError("the horizon must divide the episode length (max_step)")
     per_episode = int(env.max_step) // T
+    from . import checkpoint as CK
+    resumable = CK.check_resumable(checkpoint_dir, chkpt_freq, restore, world=world, allreduce=allreduce, recorder=recorder)
+    if resumable and int(chkpt_freq) % per_episode:
+        raise ValueError(f"league checkpoints are taken at episode boundaries only: chkpt_freq ({chkpt_freq}) must be a multiple of max_step / horizon = {per_episode}")
     bank = PolicyBank(dev, N, A, k, max_frozen=max_champions, seed=seed, random_seed=seed + 12345 + 104729 * int(first_market), n_hist=env.n_hist, state_dependent_log_std=state_dependent_log_std, hidden=hidden)
     mapper = LeagueSlotMapper(A, k, A - k, original_opponent_weight, champion_weight)
     league = League(mapper, bank, std_dev_multiplier, max_champions, min_iterations_between_champions)
-    env.reset(seed=seed + int(first_market))
-    if episode_metrics:
-        env.enable_episode_metrics(True)
+    ck_state = None
+    if resumable:
+        from .mlp import has_log_std_head, hidden_widths
+        run_args = {"markets": int(N), "agents": int(A), "horizon": int(T), "max_step": int(env.max_step), "chains": int(chains), "trainable": int(k),
+                    "objective": {kk: float(v) for kk, v in obj.items()}, "hidden": [int(h) for h in hidden_widths(bank.policies[0].theta)],
+                    "state_dependent_log_std": bool(has_log_std_head(bank.policies[0].theta)), "epochs": int(epochs), "lr": float(lr), "minibatch": int(minibatch),
+                    "seed": int(seed), "episode_metrics": bool(episode_metrics), "max_champions": int(max_champions), "std_dev_multiplier": float(std_dev_multiplier),
+                    "min_iterations_between_champions": int(min_iterations_between_champions), "original_opponent_weight": float(original_opponent_weight),
+                    "champion_weight": float(champion_weight), "run_id": str(run_id)}
+        if restore:
+            ck_path = CK.resolve_restore(checkpoint_dir, restore)
+            ck_state, ck_snap = CK.load_checkpoint(ck_path)
+            if ck_state["kind"] != "league":
+                raise ValueError(f"{ck_path} is a {ck_state['kind']!r} checkpoint, not a league_train.train_league_fused one")
+            CK.check_args(ck_state["args"], run_args)
+    if ck_state is not None:
+        if episode_metrics:                                     # (before the restore: the snapshot carries the metrics setting and the running tallies)
+            env.enable_episode_metrics(True)
+        env.restore(ck_snap)
+        _load_league_state(os.path.join(ck_path, "league"), ck_state, bank, league)
+    else:
+        env.reset(seed=seed + int(first_market))
+        if episode_metrics:
+            env.enable_episode_metrics(True)
     module_of, module_names = torch.zeros((N, A), dtype=torch.int32, device=dev), list(mapper.available_modules)
     use_kl = obj["kl_coef"] > 0.0
     roll = RolloutChains(env, bank, T, groups=chains, seed=seed + 7919 * int(first_market), use_graphs=use_graph, with_dist=use_kl,
@@ -209,7 +243,6 @@ def train_league_fused(env, iters=4, horizon=None, num_trainable=2, lr=5e-5, epo
     dp = allreduce is not None and world > 1
     upds = [FusedUpdate(bank.policies[p], R, rows_mb, 1, allreduce=allreduce if dp else None, world=world if dp else 1) for p in range(k)]
     # the trainable policies' updates are independent of each other: on their own streams one's kernel tails fill with the other's launches (CDA_LEAGUE_UPDATE_STREAMS=0: one stream)
-    import os
     update_streams = list(roll.streams[:k]) if (k > 1 and len(roll.streams) >= 2 and not dp and os.environ.get("CDA_LEAGUE_UPDATE_STREAMS", "1") != "0") else []
     # (data parallel: one stream - the ranks must issue their collectives in ONE order)
     returns = EpisodeReturns(N, A, dev, per_slot=True)
@@ -226,7 +259,29 @@ def train_league_fused(env, iters=4, horizon=None, num_trainable=2, lr=5e-5, epo
         recorder.episode_namer = lambda m, e: f"{run_id}-episode{e}-market{m}"
         recorder.init_cash = int(env.config.get("init_cash", 1000000))
     history = []
-    for it in range(iters):
+    its = range(int(iters))
+    if resumable:
+        its = CK.iteration_range(ck_state["iteration"] if ck_state is not None else 0, iters, iters_is_delta)
+        if ck_state is not None:
+            CK.load_rollout_record(roll, ck_state["rollout"])
+            for p in range(k):
+                CK.load_update_record(upds[p], ck_state["updates"][p])
+            CK.load_returns_record(returns, ck_state["returns"])
+            kl_coefs = [float(x) for x in ck_state["kl_coefs"]]
+            next_crcs = mapper.episode_crcs(episode_ids(int(ck_state["iteration"]) // per_episode))
+
+    def save(n_done):
+        tmp = os.path.join(checkpoint_dir, CK.checkpoint_name(n_done) + ".league")
+        shutil.rmtree(tmp, ignore_errors=True)
+        save_league(tmp, bank, league)                          # the bank rows as policy files
+        state = {"kind": "league", "run_id": run_id, "args": run_args, "nets": [CK.net_record(pol) for pol in bank.policies],
+                 "wb": bank.wb.detach().cpu().clone(), "n_frozen": int(bank.n_frozen), "league": _league_record(league),
+                 "rollout": CK.rollout_record(roll), "updates": [CK.update_record(u) for u in upds], "returns": CK.returns_record(returns),
+                 "kl_coefs": [float(x) for x in kl_coefs]}
+        path = CK.save_checkpoint(checkpoint_dir, n_done, state, env.snapshot(), keep=chkpt_keep, extra_dirs={"league": tmp})
+        return path
+    saved_at = None
+    for it in its:
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
         if it % per_episode == 0:                                            # a new episode everywhere: new opponents (one launch; the crcs were computed while the GPU worked)
@@ -296,16 +351,55 @@ def train_league_fused(env, iters=4, horizon=None, num_trainable=2, lr=5e-5, epo
         log(json.dumps(stats_h))
         if em is not None:
             EM.check_nav_conservation(it, summ, strict=strict_nav_check, log=log)
+        if checkpoint_dir is not None and chkpt_freq > 0 and (it + 1) % int(chkpt_freq) == 0:      # (a multiple of per_episode: an episode boundary)
+            save(it + 1)
+            saved_at = it + 1
+    if checkpoint_dir is not None and len(its) > 0 and saved_at != its[-1] + 1 and (its[-1] + 1) % per_episode == 0:
+        save(its[-1] + 1)                                       # the final save, when the run ends on an episode boundary
     if keep is not None:
         keep.update(buffers=roll.buf, rollout=roll, updates=upds, slot_pool=slot_pool, returns=returns)
     return bank, league, history
+
+
+def _league_record(league):
+    """League + mapper host state: champions and their bank rows, promotion history, champion id counter, the pool in its order"""
+    m = league.mapper
+    return {"net_of": {str(c): int(r) for c, r in league.net_of.items()}, "history": [dict(c, **{"return": float(c["return"]), "iteration": int(c["iteration"])})
+                                                                                      for c in league.history],
+            "available_modules": [str(x) for x in m.available_modules], "champion_id_counter": int(m.champion_id_counter)}
+
+
+def _load_league_state(league_dir, state, bank, league):
+    """a league checkpoint back into fresh bank / League objects: trainable nets (theta + Adam), champion rows from save_league's policy files, the bank's
+    packed weights, the League and mapper state"""
+    from . import checkpoint as CK
+    from .mlp import read_policy
+    for pol, rec in zip(bank.policies, state["nets"]):
+        CK.load_net_record(pol, rec)
+    with open(os.path.join(league_dir, "league.json")) as fh:
+        lj = json.load(fh)
+    for entry in lj["trainable"] + lj["champions"]:
+        theta = read_policy(os.path.join(league_dir, entry["file"]))
+        row = int(entry["row"])
+        if theta.numel() != bank.theta.shape[1]:
+            raise ValueError(f"{entry['file']}: {theta.numel()} parameters, the bank rows hold {bank.theta.shape[1]}")
+        bank.theta[row].copy_(theta)
+    if tuple(state["wb"].shape) != tuple(bank.wb.shape):
+        raise ValueError(f"checkpoint bank weights have shape {tuple(state['wb'].shape)}, this bank {tuple(bank.wb.shape)}")
+    bank.wb.copy_(state["wb"])
+    bank.n_frozen = int(state["n_frozen"])
+    bank._refresh()
+    lr = state["league"]
+    league.net_of = {str(c): int(r) for c, r in lr["net_of"].items()}
+    league.history = [dict(c) for c in lr["history"]]
+    league.mapper.available_modules = list(lr["available_modules"])
+    league.mapper.champion_id_counter = int(lr["champion_id_counter"])
 
 
 def save_league(directory, bank, league):
     """write every trainable policy (policy_<p>.pt, bank row p) and every champion snapshot held in the bank (champion_<id>.pt) as policy files
     (mlp.save_policy's format) and a league.json naming them: module id, bank row, file, and for champions the promotion iteration / return / source.
     Returns the league.json dict."""
-    import os
     from .mlp import policy_record
     os.makedirs(directory, exist_ok=True)
     promoted = {c["id"]: c for c in league.history}
@@ -340,7 +434,14 @@ def main(argv=None):
     p.add_argument("--log-std-head", action="store_true", help="the trainable policies carry the state-dependent log-std head (RLlib's default module for Box actions)")
     p.add_argument("--out", default=None, help="write a JSON summary to this file")
     p.add_argument("--save-dir", default=None, help="--fused: write the trainable policies, the champion snapshots and league.json here (save_league)")
+    p.add_argument("--checkpoint-dir", default=None, help="--fused: save resumable checkpoints (env markets, bank, league, learner state) as <dir>/iter_<n>")
+    p.add_argument("--chkpt-freq", type=int, default=0, help="--fused: checkpoint every N iterations, a multiple of episode / horizon (0: only a final one on an episode boundary)")
+    p.add_argument("--chkpt-keep", type=int, default=3, help="--fused: keep the newest N checkpoints")
+    p.add_argument("--restore", nargs="?", const=True, default=None, metavar="PATH", help="--fused: resume from the newest checkpoint under --checkpoint-dir, or from PATH")
+    p.add_argument("--iters-is-delta", action="store_true", help="with --restore: --iters counts further iterations instead of being the target")
     args = p.parse_args(argv)
+    if not args.fused and (args.checkpoint_dir or args.restore):
+        raise SystemExit("--checkpoint-dir / --restore need --fused")
     from .vec_env import CDAVecEnv
     from . import ppo
     cfg = {"num_of_agents": args.agents, "init_cash": 1000000, "max_step": args.episode, "is_render": False}
@@ -352,7 +453,9 @@ def main(argv=None):
     env = CDAVecEnv(dict(cfg, auto_reset=True), n_markets=args.markets, device="cuda:0", with_info=False)
     k = args.trainable or 2
     bank, league, hist = train_league_fused(env, iters=args.iters, horizon=args.horizon, num_trainable=k, chains=args.chains,
-                                         objective=ppo.RLLIB_DEFAULTS if args.objective == "rllib" else None, state_dependent_log_std=args.log_std_head, hidden=tuple(args.fcnet_hiddens))
+                                         objective=ppo.RLLIB_DEFAULTS if args.objective == "rllib" else None, state_dependent_log_std=args.log_std_head, hidden=tuple(args.fcnet_hiddens),
+                                         checkpoint_dir=args.checkpoint_dir, chkpt_freq=args.chkpt_freq, chkpt_keep=args.chkpt_keep, restore=args.restore,
+                                         iters_is_delta=args.iters_is_delta)
     flags = env.flags()
     _, bad = env.nav_conservation()
     tail = hist[2:] if len(hist) >= 4 else (hist[1:] or hist)          # (two warm-up iterations: graph capture, first replays)

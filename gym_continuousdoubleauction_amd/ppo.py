@@ -506,7 +506,8 @@ def adapt_kl_coef(kl_coef, sampled_kl, kl_target):
 
 def train_fused(env, iters=4, horizon=64, lr=5e-5, epochs=4, reward_scale=None, seed=0, log=print, use_graph=True, chains=4, minibatch=262144,
                 gamma=None, lam=None, clip=None, vf_coef=None, ent_coef=None, policy=None, keep=None, sub_batches=None, objective=None, recorder=None, info_markets=0,
-                allreduce=None, world=1, first_market=0, episode_metrics=True, strict_nav_check=True, state_dependent_log_std=False, hidden=(256, 256)):
+                allreduce=None, world=1, first_market=0, episode_metrics=True, strict_nav_check=True, state_dependent_log_std=False, hidden=(256, 256),
+                checkpoint_dir=None, chkpt_freq=0, chkpt_keep=3, restore=None, iters_is_delta=False):
     """The PPO loop on the hand-written network kernels (mlp.py, include/cda_mlp.h): rollouts as `chains` independent per-chain launch
     sequences (policy forward + sampling -> env step -> auto reset, one HIP graph per chain, no cross-stream edge inside the horizon), the
     sample records completed by one GAE launch, the update as {gather + forward + loss + back-propagation, weight gradients, reduce, clip + Adam}
@@ -526,7 +527,12 @@ def train_fused(env, iters=4, horizon=64, lr=5e-5, epochs=4, reward_scale=None, 
     brings its own.  hidden: `fcnet_hiddens` of a fresh policy, <= 256 each (mlp.init_theta).
     Needs a HIP CDAVecEnv with auto_reset and 168-float observations.  Returns (FusedPolicy, history); `keep` (a dict) receives the last
     rollout's buffers and the RolloutChains object.  history[i]: losses, `mean_reward` (of the rollout's slice of the episodes - it depends on WHICH part of
-    the episodes the slice covers) and `episode_return` (mean return of the episodes that were COMPLETED during the iteration, None if none was)."""
+    the episodes the slice covers) and `episode_return` (mean return of the episodes that were COMPLETED during the iteration, None if none was).
+    checkpoint_dir / chkpt_freq / chkpt_keep / restore / iters_is_delta (all off by default): a resumable run (checkpoint.py).  Every chkpt_freq iterations and at
+    the end the env's markets and the learner's state are saved as checkpoint_dir/iter_<n> (n = iterations done), the newest chkpt_keep kept.  restore=True resumes
+    from the newest checkpoint under checkpoint_dir, a path from that one: the env is restored instead of reset, and `iters` is the TARGET iteration count
+    (iters_is_delta: that many more).  The resumed rollouts are bit-identical to the uninterrupted run's.  history entries carry the global iteration number.
+    Single-process runs only (world == 1), without a recorder; chkpt_freq > 0 needs a checkpoint_dir (ValueError otherwise)."""
     from .mlp import EpisodeReturns, FusedPolicy, FusedUpdate, RolloutChains
     obj = dict(PPO_DEFAULTS)
     obj.update(objective or {})
@@ -537,9 +543,31 @@ def train_fused(env, iters=4, horizon=64, lr=5e-5, epochs=4, reward_scale=None, 
     N, A, T = env.n_markets, env.num_agents, int(horizon)
     if policy is None:
         policy = FusedPolicy(dev, seed=seed, n_hist=env.n_hist, state_dependent_log_std=state_dependent_log_std, hidden=hidden)
-    env.reset(seed=seed + int(first_market))
-    if episode_metrics:
-        env.enable_episode_metrics(True)
+    from . import checkpoint as CK
+    resumable = CK.check_resumable(checkpoint_dir, chkpt_freq, restore, world=world, allreduce=allreduce, recorder=recorder)
+    ck_state = None
+    if resumable:
+        from .mlp import has_log_std_head, hidden_widths
+        run_args = {"markets": int(N), "agents": int(A), "horizon": int(T), "chains": int(chains), "objective": {k: float(v) for k, v in obj.items()},
+                    "hidden": [int(h) for h in hidden_widths(policy.theta)], "state_dependent_log_std": bool(has_log_std_head(policy.theta)),
+                    "epochs": int(epochs), "lr": float(lr), "minibatch": int(minibatch), "seed": int(seed), "episode_metrics": bool(episode_metrics)}
+        run_id = CK.new_run_id()
+        if restore:
+            ck_path = CK.resolve_restore(checkpoint_dir, restore)
+            ck_state, ck_snap = CK.load_checkpoint(ck_path)
+            if ck_state["kind"] != "ppo":
+                raise ValueError(f"{ck_path} is a {ck_state['kind']!r} checkpoint, not a ppo.train_fused one")
+            CK.check_args(ck_state["args"], run_args)
+            run_id = ck_state["run_id"]
+    if ck_state is not None:
+        if episode_metrics:                                     # (before the restore: the snapshot carries the metrics setting and the running tallies)
+            env.enable_episode_metrics(True)
+        env.restore(ck_snap)
+        CK.load_net_record(policy, ck_state["nets"][0])
+    else:
+        env.reset(seed=seed + int(first_market))
+        if episode_metrics:
+            env.enable_episode_metrics(True)
     use_kl = obj["kl_coef"] > 0.0
     roll = RolloutChains(env, policy, T, groups=chains, seed=seed + 7919 * int(first_market), use_graphs=use_graph, with_dist=use_kl,
                          capture_ends=bool(obj["bootstrap_truncation"]), info_markets=info_markets if recorder is not None else 0)
@@ -551,7 +579,21 @@ def train_fused(env, iters=4, horizon=64, lr=5e-5, epochs=4, reward_scale=None, 
     returns = EpisodeReturns(N, A, dev)
     kl_coef = float(obj["kl_coef"])
     history = []
-    for it in range(iters):
+    its = range(int(iters))
+    if resumable:
+        its = CK.iteration_range(ck_state["iteration"] if ck_state is not None else 0, iters, iters_is_delta)
+        if ck_state is not None:
+            CK.load_rollout_record(roll, ck_state["rollout"])
+            CK.load_update_record(upd, ck_state["update"])
+            CK.load_returns_record(returns, ck_state["returns"])
+            kl_coef = float(ck_state["kl_coef"])
+
+    def save(n_done):
+        state = {"kind": "ppo", "run_id": run_id, "args": run_args, "nets": [CK.net_record(policy)], "rollout": CK.rollout_record(roll),
+                 "update": CK.update_record(upd), "returns": CK.returns_record(returns), "kl_coef": float(kl_coef)}
+        return CK.save_checkpoint(checkpoint_dir, n_done, state, env.snapshot(), keep=chkpt_keep)
+    saved_at = None
+    for it in its:
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
         buf = roll.run()
@@ -586,6 +628,11 @@ def train_fused(env, iters=4, horizon=64, lr=5e-5, epochs=4, reward_scale=None, 
         log(json.dumps(stats))
         if em is not None:
             EM.check_nav_conservation(it, summ, strict=strict_nav_check, log=log)
+        if checkpoint_dir is not None and chkpt_freq > 0 and (it + 1) % int(chkpt_freq) == 0:
+            save(it + 1)
+            saved_at = it + 1
+    if checkpoint_dir is not None and len(its) > 0 and saved_at != its[-1] + 1:
+        save(its[-1] + 1)                                       # the final save
     if keep is not None:
         keep.update(buffers=roll.buf, rollout=roll, update=upd)
     return policy, history
@@ -716,6 +763,11 @@ def main(argv=None):
     p.add_argument("--objective", choices=("ppo", "rllib"), default="ppo", help="fused loop: PPO_DEFAULTS, or RLLIB_DEFAULTS = the objective the reference's RLlib run optimises "
                                                                               "(clip 0.3, lambda 1, vf coeff 1, entropy 0, vf clip 10, adaptive KL penalty, no gradient clipping, truncation bootstrap)")
     p.add_argument("--save", default=None, metavar="PATH", help="fused loop: write the trained policy to this file (mlp.save_policy; evaluate.py reads it)")
+    p.add_argument("--checkpoint-dir", default=None, help="fused loop: save resumable checkpoints (env markets + learner state) as <dir>/iter_<n> (checkpoint.py)")
+    p.add_argument("--chkpt-freq", type=int, default=0, help="fused loop: checkpoint every N iterations (0: only the final one, when --checkpoint-dir is given)")
+    p.add_argument("--chkpt-keep", type=int, default=3, help="fused loop: keep the newest N checkpoints")
+    p.add_argument("--restore", nargs="?", const=True, default=None, metavar="PATH", help="fused loop: resume from the newest checkpoint under --checkpoint-dir, or from PATH")
+    p.add_argument("--iters-is-delta", action="store_true", help="with --restore: --iters counts further iterations instead of being the target")
     args = p.parse_args(argv)
     from .vec_env import CDAVecEnv
     p_groups = max(1, min(args.groups, args.markets))
@@ -726,13 +778,17 @@ def main(argv=None):
         # the fused kernels step whole 32-row tiles and are compiled per history depth: other shapes run the PyTorch statement of the same loop
         print(json.dumps({"note": f"fused loop needs horizon * markets % 32 == 0 and n_hist in {HIST_VARIANTS} (got {args.horizon} x {args.markets}, n_hist {env.n_hist}): running the legacy loop"}))
         args.legacy = True
+    if args.legacy and (args.checkpoint_dir or args.restore):
+        raise SystemExit("--checkpoint-dir / --restore need the fused loop")
     if args.save and args.legacy:
         raise SystemExit("--save needs the fused loop (the legacy loop's network is a PyTorch module)")
     if args.legacy:
         _, hist = train(env, iters=args.iters, horizon=args.horizon, amp=not args.fp32_update, shared_obs=not args.per_sample_forward, use_graph=not args.no_graphs)
     else:
         trained, hist = train_fused(env, iters=args.iters, horizon=args.horizon, use_graph=not args.no_graphs, chains=args.chains,
-                              objective=RLLIB_DEFAULTS if args.objective == "rllib" else None, state_dependent_log_std=args.log_std_head, hidden=tuple(args.fcnet_hiddens))
+                              objective=RLLIB_DEFAULTS if args.objective == "rllib" else None, state_dependent_log_std=args.log_std_head, hidden=tuple(args.fcnet_hiddens),
+                              checkpoint_dir=args.checkpoint_dir, chkpt_freq=args.chkpt_freq, chkpt_keep=args.chkpt_keep, restore=args.restore,
+                              iters_is_delta=args.iters_is_delta)
     flags = env.flags()
     _, bad = env.nav_conservation()
     tail = hist[2:] if len(hist) >= 4 else (hist[1:] or hist)

@@ -440,6 +440,7 @@ class CDAVecEnv:
         included (include/cda.h cda_episode_metrics_enable; train/callbk/league_based_self_play_callback.py:541-755)."""
         check(lib().cda_episode_metrics_enable(self._h, 1 if on else 0, float(nav_tolerance)), "cda_episode_metrics_enable")
         self.episode_metrics_on = bool(on)
+        self.episode_metrics_tolerance = float(nav_tolerance)
 
     def collect_episode_metrics(self, module_of=None, n_modules=1, clear=True, out=None):
         """The episodes that ended since the last collection, reduced on the device (two launches, a fixed order): (f64 [n_modules, EM_AGENT_FIELDS] per-module
@@ -454,6 +455,51 @@ class CDAVecEnv:
             check(lib().cda_episode_metrics_collect(self._h, module_of.data_ptr() if module_of is not None else None, int(n_modules), out[0].data_ptr(), out[1].data_ptr(),
                                                     1 if clear else 0, self._stream()), "cda_episode_metrics_collect")
         return out
+
+    # ------------------------------------------------------------------ snapshots, forks and resumable runs
+    def snapshot(self, first=0, n=None):
+        """A compact device image of markets [first, first + n) (include/cda.h cda_snapshot_*): their records, done bytes, episode-metric rows and the
+        live windows of their HBM rings.  Returns a snapshot.Snapshot (uint8 device tensor + parsed header).  Ordered after every group's last step."""
+        from .snapshot import Snapshot, parse_header
+        n = self.n_markets - int(first) if n is None else int(n)
+        if not (0 <= int(first) and n >= 1 and int(first) + n <= self.n_markets):
+            raise ValueError(f"snapshot range [{first}, {int(first) + n}) is outside the env's {self.n_markets} markets")
+        self.join()
+        with torch.cuda.device(self.device):
+            off = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+            check(lib().cda_snapshot_offsets(self._h, int(first), n, off.data_ptr(), self._stream()), "cda_snapshot_offsets")
+            total = int(off[n].item())                  # the one 8-byte read
+            blob = torch.empty(total, dtype=torch.uint8, device=self.device)
+            check(lib().cda_snapshot_pack(self._h, int(first), n, off.data_ptr(), blob.data_ptr(), total, self._stream()), "cda_snapshot_pack")
+            header = parse_header(blob[:256].cpu())
+        return Snapshot(blob, header)
+
+    def restore(self, snap, first=0, src_first=0, n=None):
+        """Markets [src_first, src_first + n) of `snap` -> markets [first, first + n) of this env (a Snapshot from this env or another with the same
+        numeric config, tile, history depth, agents and episode-metrics setting; book_spill may differ).  The arena is written in place and the restored
+        markets' observation rows of `obs` are re-emitted.  A mismatch raises ValueError naming the field; a blob the device check refuses raises
+        CDAError - in both cases before any byte of the env is written."""
+        from .snapshot import mismatch
+        n = len(snap) - int(src_first) if n is None else int(n)
+        if not (0 <= int(src_first) and n >= 1 and int(src_first) + n <= len(snap)):
+            raise ValueError(f"source range [{src_first}, {int(src_first) + n}) is outside the snapshot's {len(snap)} markets")
+        if not (0 <= int(first) and int(first) + n <= self.n_markets):
+            raise ValueError(f"target range [{first}, {int(first) + n}) is outside the env's {self.n_markets} markets")
+        why = mismatch(snap.header, self)
+        if why is not None:
+            raise ValueError(f"cannot restore this snapshot: {why}")
+        blob = snap.blob
+        if blob.device != self.device or blob.data_ptr() % 256 != 0:
+            blob = blob.to(self.device).clone()
+        self.host_epoch += 1
+        self.join()
+        with torch.cuda.device(self.device):
+            check(lib().cda_snapshot_restore(self._h, int(first), blob.data_ptr(), int(snap.nbytes), int(src_first), n, self.obs.data_ptr(), self._stream()),
+                  "cda_snapshot_restore")
+        blob.record_stream(torch.cuda.current_stream(self.device))     # (the allocator keeps it until the restore has run on this stream; nothing is held beyond)
+        if self.groups > 1:
+            self.fork()                                 # the group streams see the restored markets
+        return self.obs
 
     def state_bytes_per_market(self):
         return int(lib().cda_state_bytes_per_market(self._h))

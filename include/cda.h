@@ -499,6 +499,50 @@ int cda_gae(const float* rew, const float* val, const float* last_val, const flo
 #define CDA_SLOT_ITEMS_MAX 12
 int cda_store_slots(int32_t n_items, const void* const* src, void* const* dst_base, const int64_t* bytes, int64_t* slot_dev, int32_t bump, void* stream);
 
+/* ---- device snapshot / restore of a market range --------------------------------------------------------------------------------
+ * A compact, position-independent image of markets [first, first + n) of an env, built on the device (csrc/cda_snapshot.inc): per market the
+ * whole record (header words with the PCG64 state, accounts, history frames, the book tile, the running episode tallies), its done_buf byte,
+ * its rows of the episode-metric accumulators and, for a side whose book continues in the HBM ring, the ring's count and base and ONLY the live
+ * window of orders.  The blob holds no address.  Layout: cda_snapshot_header (256 B), int64 offsets[n + 1] (byte offset of every market's
+ * section from the blob's start; offsets[n] = total bytes) zero padded to a multiple of 256 B, then the sections, each 256-B aligned.
+ *
+ *   cda_snapshot_offsets  sizes every market's section from its header and status words and scans them into offsets_dev i64[n + 1] (device)
+ *                         on `stream`; offsets_dev[n] (one 8-byte read) is the blob size the caller allocates.
+ *   cda_snapshot_pack     writes the blob (device, 256-B aligned, blob_bytes >= offsets_dev[n]) on `stream`; the env must not be stepped
+ *                         between the two calls (stream order).
+ *   cda_snapshot_restore  markets [src_first, src_first + n) of a blob -> markets [first_market, first_market + n) of `env` (this env or any other
+ *                         with the same numeric config, tile, history depth, agent count and episode-metrics setting; its n_markets and
+ *                         book_spill may differ: a ring window is rebased into the target's ring, at the saved base when the capacities are
+ *                         equal).  SYNCHRONOUS in its checks: the header is read back and every section is vetted on the device before any
+ *                         byte of the env is written; a blob that does not fit (config, tile, depth, agents, metrics, a live window larger than
+ *                         the target's ring, a corrupt header or table) returns CDA_ERR_INVALID and leaves the env as it was.  Then, on
+ *                         `stream`, the arena is written in place (captured graphs keep their addresses) and, if obs_out (f32 [N, n_hist*42],
+ *                         device) is not NULL, the restored markets' observation rows are re-emitted from their history frames.
+ *   cda_snapshot_check_header   the host half of those checks, for a header already on the host (CDA_OK / CDA_ERR_INVALID).
+ *   cda_snapshot_table_bytes    bytes of header + offset table for n markets: where the first section starts. */
+#define CDA_SNAP_MAGIC   0x53414443u    /* "CDAS" */
+#define CDA_SNAP_VERSION 1u
+typedef struct cda_snapshot_header {
+    uint32_t magic, version;
+    int32_t  header_bytes;          /* = cda_snapshot_table_bytes(n_markets) */
+    int32_t  n_markets;             /* markets in the blob */
+    int64_t  total_bytes;
+    int32_t  book_capacity, record_stride, n_hist, num_agents;
+    int32_t  spill_cap;             /* ring of the env the blob was taken from */
+    int32_t  episode_metrics_on;
+    double   nav_tolerance;
+    int32_t  first_market;          /* of the env the blob was taken from */
+    int32_t  em_agent_fields, em_env_fields, section_meta_bytes;
+    cda_config cfg;                 /* the full config of the env the blob was taken from */
+    uint8_t  reserved[88];
+} cda_snapshot_header;
+int64_t cda_snapshot_table_bytes(int32_t n_markets);
+int cda_snapshot_offsets(cda_env* env, int32_t first_market, int32_t n_markets, int64_t* offsets_dev, void* stream);
+int cda_snapshot_pack(cda_env* env, int32_t first_market, int32_t n_markets, const int64_t* offsets_dev, void* blob_dev, int64_t blob_bytes, void* stream);
+int cda_snapshot_check_header(const cda_env* env, const cda_snapshot_header* header_host, int64_t blob_bytes);
+int cda_snapshot_restore(cda_env* env, int32_t first_market, const void* blob_dev, int64_t blob_bytes, int32_t src_first, int32_t n_markets,
+                         float* obs_out, void* stream);
+
 const char* cda_strerror(int status);
 int32_t cda_num_markets(const cda_env* env);
 int32_t cda_num_agents(const cda_env* env);
