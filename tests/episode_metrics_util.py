@@ -120,3 +120,37 @@ def assert_tables_equal(dev_agent, dev_env, ref_agent, ref_env, what=""):
     scale = np.maximum(np.abs(ref_agent), 1e-300)
     assert (np.abs(da - ref_agent) <= 1e-12 * scale + 1e-9 * (np.abs(ref_agent) < 1e-6)).all(), (what, np.abs(da - ref_agent).max(0))
     assert np.allclose(de, ref_env, rtol=1e-12, atol=0), (what, de, ref_env)
+
+
+def abs_sums(em, module_of=None, n_modules=1):
+    """before em.table(): per module and field the sum of |x| over the (market, agent) rows the table adds, the number of those rows, and the same for the env
+    row's per-market sums - what the summation-order bound of assert_tables_within_order_bound scales with"""
+    N, A = em.N, em.A
+    mod = np.zeros((N, A), np.int64) if module_of is None else np.asarray(module_of).reshape(N, A)
+    S, n = np.zeros((n_modules, K.EM_AGENT_FIELDS)), np.zeros(n_modules, np.int64)
+    for m in range(n_modules):
+        rows = em.F[(mod == m) & (em.F[..., K.EM_EPISODES] > 0)]
+        S[m], n[m] = np.abs(rows).sum(0), len(rows)
+    return S, n, np.abs(em.M).sum(0), N
+
+
+def assert_tables_within_order_bound(dev_agent, dev_env, ref_agent, ref_env, sums, what=""):
+    """integer / decimal-derived fields bit for bit (as assert_tables_equal); every f64 sum of n terms within 2 n eps sum|x| of the host's: the device adds
+    thousands of (market, agent) rows in another order (blocks, groups, lanes) than numpy, and either order is within (n - 1) eps sum|x| of the exact sum"""
+    S, n, S_env, n_env = sums
+    da, de = np.asarray(dev_agent), np.asarray(dev_env)
+    assert da.shape == ref_agent.shape, (da.shape, ref_agent.shape)
+    for f in EXACT_AGENT:
+        assert np.array_equal(da[:, f], ref_agent[:, f]), (what, "agent field", f, da[:, f], ref_agent[:, f])
+    for f in EXACT_ENV:
+        assert de[f] == ref_env[f], (what, "env field", f, de[f], ref_env[f])
+    eps = np.finfo(np.float64).eps
+    bound = 2 * n[:, None] * eps * S
+    err = np.abs(da - ref_agent)
+    assert (err <= bound).all(), (what, np.argwhere(err > bound), err.max(0))
+    bound_env = 2 * n_env * eps * S_env
+    assert (np.abs(de - ref_env) <= bound_env).all(), (what, de, ref_env)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.where(bound > 0, err / np.where(bound > 0, bound, 1), 0.0)
+        ratio_env = np.where(bound_env > 0, np.abs(de - ref_env) / np.where(bound_env > 0, bound_env, 1), 0.0)
+    return float(max(ratio.max(), ratio_env.max()))

@@ -270,3 +270,85 @@ def test_metrics_off_touch_nothing_and_the_step_is_unchanged():
         for x, y in zip(a, b):
             assert np.array_equal(x.view(np.uint8), y.view(np.uint8))
     assert outs[0][1] == outs[1][1]
+
+
+@pytest.mark.parametrize("N,A,max_step,T,cash,modules", [(8448, 2, 3, 7, 1000000, False),      # > 8192 markets: k_em_partial's per-market loop runs twice
+                                                         (2304, 4, 10, 20, 1500, True)])        # fills and a bankruptcy; 32 modules, ids outside [0, 32) skipped
+def test_collect_at_scale_equals_the_oracle_replay(N, A, max_step, T, cash, modules):
+    """cda_episode_metrics_collect where k_em_partial's loops run more than once: (market, agent) pairs > 256 blocks x 8 groups = 2048, markets > 256 x 32 = 8192,
+    n_modules = CDA_EM_MAX_MODULES with ids -1 and >= n_modules in module_of - against the CPU oracle's replay of every market"""
+    from gym_continuousdoubleauction_amd import CDAVecEnv, _capi as K
+    from episode_metrics_util import OracleEpisodeMetrics, abs_sums, assert_tables_within_order_bound
+    seed = 7300 + N
+    cfg = _cfg(A, max_step, cash)
+    env = CDAVecEnv(cfg, n_markets=N, with_info=False)
+    env.reset(seed=seed)
+    env.enable_episode_metrics(True)
+    rng = np.random.default_rng(N)
+    steps = [_actions(rng, N, A, aggressive=cash < 100000) for _ in range(T)]
+    for acts in steps:
+        env.step(*acts)
+    n_mod, module_of = 1, None
+    if modules:
+        n_mod = K.EM_MAX_MODULES                                                # (32: every module accumulator of k_em_partial in use)
+        module_of = rng.integers(-1, n_mod + 3, (N, A)).astype(np.int32)       # -1 and n_mod .. n_mod + 2: played by nobody the table counts
+        module_of[0, 0], module_of[1, 0], module_of[2, 0] = -1, n_mod, n_mod + 2
+    dev = [t.cpu().numpy() for t in env.collect_episode_metrics(module_of=None if module_of is None else torch.from_numpy(module_of).to(env.device), n_modules=n_mod)]
+    ora, em = _oracle(cfg, N, seed), OracleEpisodeMetrics(N, A, cash)
+    _replay(ora, em, steps)
+    sums = abs_sums(em, module_of, n_mod)
+    bankrupt = em.F[..., K.EM_BANKRUPT].sum()
+    ref = em.table(module_of, n_mod)
+    assert ref[1][K.EM_ENV_EPISODES] == N * (T // max_step)
+    if modules:
+        assert (ref[0][:, K.EM_EPISODES] > 0).all() and bankrupt > 0 and ref[0][:, K.EM_TRADES].sum() > 1000
+        skipped = (module_of < 0) | (module_of >= n_mod)
+        assert 0 < skipped.sum() and ref[0][:, K.EM_EPISODES].sum() == (T // max_step) * (~skipped).sum()
+    worst = assert_tables_within_order_bound(dev[0], dev[1], *ref, sums, what=f"{N} x {A}")
+    print(f"\n[episode metrics at scale] {N} x {A}: worst f64 sum error / (2 n eps sum|x|) = {worst:.3g}")
+    assert not em.violating and (env.flags() == 0).all()
+    env.close(); ora.close()
+
+
+def _returns_reference(reward, done, running):
+    """k_episode_returns restated in float64 on the host, forwards in time per (market, agent): (running, per-slot sum of completed returns, their number)"""
+    run, s, c = running.copy(), np.zeros_like(running), np.zeros_like(running)
+    for t in range(reward.shape[0]):
+        run = run + reward[t]
+        d = done[t][:, None] & np.ones(run.shape, bool)
+        s = np.where(d, s + run, s)
+        c = np.where(d, c + 1.0, c)
+        run = np.where(d, 0.0, run)
+    return run, s, c
+
+
+@pytest.mark.parametrize("T", [13, 64])
+def test_episode_returns_equal_the_float64_recursion(T):
+    """mlp.EpisodeReturns (k_episode_returns: eight steps' operands per request, a ragged last group at T = 13) over two consecutive rollouts of 4096 x 4: episodes
+    ending at t = 0, at t = T - 1 and in the middle of an 8-step group; running and per-slot figures bit for bit (the same additions in the same time order), the
+    per-slot totals within the order bound of their atomic sum over markets"""
+    from gym_continuousdoubleauction_amd import mlp
+    N, A = 4096, 4
+    er = mlp.EpisodeReturns(N, A, "cuda:0", per_slot=True)
+    rng = np.random.default_rng(T)
+    running = np.zeros((N, A))
+    for rnd in range(2):
+        reward = rng.standard_normal((T, N, A)) * np.exp(rng.uniform(-8, 8, (T, N, A)))      # magnitudes over many binades: any reordering shows
+        term = rng.random((T, N)) < 0.04
+        trunc = rng.random((T, N)) < 0.02
+        term[0, 0:64] = True; trunc[T - 1, 64:128] = True; term[min(11, T - 1), 128:192] = True; term[3, 192:256] = True
+        term[:, 256:320] = False; trunc[:, 256:320] = False                          # markets whose episode spans both rollouts
+        done = term | trunc
+        buf = {"reward": torch.from_numpy(reward).to("cuda:0"), "terminated": torch.from_numpy(term.astype(np.uint8)).to("cuda:0"),
+               "truncated": torch.from_numpy(trunc.astype(np.uint8)).to("cuda:0")}
+        acc = er.update(buf, T).cpu().numpy()
+        running, s, c = _returns_reference(reward, done, running)
+        assert np.array_equal(er.running.cpu().numpy().view(np.uint64), running.view(np.uint64)), rnd
+        ps = er.per_slot.cpu().numpy()
+        assert np.array_equal(ps[..., 0].view(np.uint64), s.view(np.uint64)) and np.array_equal(ps[..., 1], c), rnd
+        assert np.array_equal(acc[1], c.sum(0)) and (acc[1] > 0).all()
+        want = s.sum(0)
+        bound = 2 * N * np.finfo(np.float64).eps * np.abs(s).sum(0)
+        assert (np.abs(acc[0] - want) <= bound).all(), (rnd, acc[0], want)
+        print(f"\n[episode returns] T {T} rollout {rnd}: worst done_sum error / (2 n eps sum|x|) = {float((np.abs(acc[0] - want) / bound).max()):.3g}")
+    assert (np.abs(running[256:320]) > 0).all()

@@ -11,18 +11,13 @@ import numpy as np
 import pytest
 import torch
 
+from update_check_util import _obs, check_gradient
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 HERE = os.path.dirname(os.path.abspath(__file__))
 ACTION_KEYS = ("category", "size_mean", "size_sigma", "price", "price_offset")
-
-
-def _obs(n, seed=5):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(n, 168, generator=g) * 1.5
-    x[:, ::7] = 0.0
-    return x
 
 
 def _bank(N, A, k, frozen, seed=3, scale=2.0):
@@ -292,46 +287,6 @@ def test_gae_bootstraps_truncations_with_the_value_of_the_captured_observation(l
     env.close()
 
 
-def _torch_objective(m, x, acts, lp_old, adv, ret, dist_old, ls_old, clip, vf_coef, ent_coef, kl_coef, vf_clip, agents_per_row):
-    """the loss the fused kernel differentiates, stated with torch ops (RLlib's PPO torch learner: surrogate, clamped value error, entropy, KL(old || new))"""
-    logp, ent, v = m.evaluate(x, acts, agents_per_row=agents_per_row)
-    ratio = (logp - lp_old).exp()
-    pg = -torch.min(ratio * adv, ratio.clamp(1 - clip, 1 + clip) * adv).mean()
-    sq = (v - ret).pow(2)
-    vl = (sq.clamp(max=vf_clip) if vf_clip > 0 else sq).mean()
-    o, _ = m.trunk(x)
-    o = o.float()
-    kl = torch.zeros(x.shape[0])
-    for lo, hi in ((0, 9), (9, 19), (19, 22)):
-        ls_new = torch.log_softmax(o[:, lo:hi], -1)
-        kl = kl + (dist_old[:, lo:hi].exp() * (dist_old[:, lo:hi] - ls_new)).sum(-1)
-    mu_o, mu_n = dist_old[:, 22:24], o[:, 22:24]
-    ls_new, ls_old = m.trunk_ls(x)[2], dist_old[:, 24:26]               # per row: the free vector (+ the state-dependent head's offsets); the rollout's ride in the row
-    kl = kl + ((ls_new - ls_old) + (torch.exp(2 * ls_old) + (mu_o - mu_n) ** 2) / (2 * torch.exp(2 * ls_new)) - 0.5).sum(-1)
-    return pg + vf_coef * vl - ent_coef * ent.mean() + kl_coef * kl.mean(), pg, vl, kl.mean()
-
-
-def _grad_vector(m):
-    from gym_continuousdoubleauction_amd import mlp
-    gm = torch.zeros(mlp.PARAMS, dtype=torch.float64)
-    H = 256
-    gm[mlp.OFF_W1:mlp.OFF_B1] = m.l1.weight.grad.double().reshape(-1); gm[mlp.OFF_B1:mlp.OFF_W2] = m.l1.bias.grad.double()
-    w2g = m.l2.weight.grad.double()
-    gm[mlp.OFF_W2:mlp.OFF_B2] = torch.stack([w2g[:H, :H], w2g[H:, H:]]).reshape(-1); gm[mlp.OFF_B2:mlp.OFF_WO] = m.l2.bias.grad.double()
-    wog = m.out.weight.grad.double(); blk = torch.zeros(32, H, dtype=torch.float64); blk[:24] = wog[:24, :H]; blk[24] = wog[24, H:]
-    sd = m.state_dependent_log_std
-    if sd:
-        blk[25:27] = wog[25:27, :H]
-    gm[mlp.OFF_WO:mlp.OFF_BO] = blk.reshape(-1)
-    bog = m.out.bias.grad.double().clone(); bog[27 if sd else 25:] = 0
-    gm[mlp.OFF_BO:mlp.OFF_LS] = bog; gm[mlp.OFF_LS:] = 0.0 if m.log_std.grad is None else m.log_std.grad.double()
-    return gm
-
-
-BLOCKS = lambda mlp: ((mlp.OFF_W1, mlp.OFF_B1, "W1"), (mlp.OFF_B1, mlp.OFF_W2, "b1"), (mlp.OFF_W2, mlp.OFF_B2, "W2"), (mlp.OFF_B2, mlp.OFF_WO, "b2"),   # noqa: E731
-                      (mlp.OFF_WO, mlp.OFF_BO, "Wo"), (mlp.OFF_BO, mlp.OFF_LS, "bo"), (mlp.OFF_LS, mlp.PARAMS, "log_std"))
-
-
 @pytest.mark.parametrize("A,slot,kl_coef,vf_clip", [(8, 1, 0.0, 0.0),       # a league update: only slot 1's samples of 8 feed the gradient
                                                     (4, None, 0.2, 0.7),     # one shared policy with RLlib's KL penalty and value clamp
                                                     (8, 0, 0.3, 0.5)])       # both
@@ -350,133 +305,6 @@ def test_state_dependent_log_std_head_gradient_equals_float32_autograd(A, slot, 
     every row back through columns 25, 26, rows 25, 26 of Wo / bo get their gradient, the free vector none - against float64 autograd on the kernel's own outputs and
     float32 autograd through ppo.ActorCritic(state_dependent_log_std=True)."""
     check_gradient(A, slot, kl_coef, vf_clip, sd=True)
-
-
-def _loss_gradient_on_outputs(out, log_std, sel, dist_old, ls_old, clip, vf_coef, ent_coef, kl_coef, vf_clip, sd=False):
-    """d loss / d outputs and d loss / d log_std by float64 autograd, starting from the kernel's OWN float32 outputs [R, 32] (so the clip / clamp decisions are taken
-    on the same numbers): sel [R, agents, 8] the rows' sample records, dist_old [R, 24] - all in minibatch order"""
-    R, agents = sel.shape[0], sel.shape[1]
-    o = out.double().clone().requires_grad_()
-    ls_free = log_std.double().clone().requires_grad_()
-    ls_row = ls_free + o[:, 25:27]                                  # [R, 2]: the free vector + the head's offsets (the kernel adds them whether or not the head trains)
-    if not sd:
-        ls_row = ls_free + o[:, 25:27].detach()
-    O = o.repeat_interleave(agents, 0)
-    ls = ls_row.repeat_interleave(agents, 0)
-    flat = sel.reshape(R * agents, 8)
-    acts = [flat[:, c].contiguous().view(torch.int32).long() for c in range(3)]
-    a_cont, lp_old, adv, ret = flat[:, 3:5].double(), flat[:, 5].double(), flat[:, 6].double(), flat[:, 7].double()
-    logp = ent = 0.0
-    for (lo, hi), a in zip(((0, 9), (9, 19), (19, 22)), acts):
-        l = torch.log_softmax(O[:, lo:hi], -1)
-        logp = logp + l.gather(1, a.view(-1, 1)).squeeze(1)
-        ent = ent - (l.exp() * l).sum(-1)
-    z = (a_cont - O[:, 22:24]) * torch.exp(-ls)
-    logp = logp + (-0.5 * z * z - ls - 0.5 * math.log(2 * math.pi)).sum(-1)
-    ent = ent + (0.5 + 0.5 * math.log(2 * math.pi) + ls).sum(-1)
-    ratio = (logp - lp_old).exp()
-    pg = -torch.min(ratio * adv, ratio.clamp(1 - clip, 1 + clip) * adv).mean()
-    sq = (O[:, 24] - ret).pow(2)
-    vl = (sq.clamp(max=vf_clip) if vf_clip > 0 else sq).mean()
-    loss = pg + vf_coef * vl - ent_coef * ent.mean()
-    if kl_coef:
-        d = dist_old.double()
-        lo_ = d[:, 24:26]                                           # the log-stds every row was sampled with
-        kl = 0.0
-        for lo, hi in ((0, 9), (9, 19), (19, 22)):
-            kl = kl + (d[:, lo:hi].exp() * (d[:, lo:hi] - torch.log_softmax(o[:, lo:hi], -1))).sum(-1)
-        kl = kl + ((ls_row - lo_) + (torch.exp(2 * lo_) + (d[:, 22:24] - o[:, 22:24]) ** 2) / (2 * torch.exp(2 * ls_row)) - 0.5).sum(-1)
-        loss = loss + kl_coef * kl.mean()
-    loss.backward()
-    return o.grad, (torch.zeros(2, dtype=torch.float64) if sd else ls_free.grad)
-
-
-def check_gradient(A, slot, kl_coef, vf_clip, R=512, seed=6, chunks=4, check_clip_share=True, soak=False, sd=False):
-    """(also driven over random shapes by tools/gradient_soak.py, soak=True: there the TIGHT check is the loss gradient on the kernel's own outputs; the whole
-    gradient against float32 autograd is held to wider bands - a sample whose ratio / value error sits within bfloat16 noise of a clip / clamp boundary takes the
-    other branch in float32, a discrete change of that sample's whole contribution, and random shapes with few samples per minibatch meet that)"""
-    from gym_continuousdoubleauction_amd import mlp
-    g = torch.Generator().manual_seed(seed)
-    th = mlp.init_theta(generator=torch.Generator().manual_seed(13), state_dependent_log_std=sd)
-    p = mlp.FusedPolicy(DEV, theta=th)
-    assert p.state_dependent_log_std == sd
-    th_old = th.clone(); th_old[:mlp.OFF_LS] += 0.02 * torch.randn(mlp.OFF_LS, generator=g); th_old[mlp.OFF_LS:] = torch.tensor([-0.4, -0.65])
-    x = _obs(R, seed=17) * 0.5
-    rec = torch.zeros(R, A, 8)
-    rec[..., 0] = torch.randint(0, 9, (R, A), generator=g).int().view(torch.float32)
-    rec[..., 1] = torch.randint(0, 10, (R, A), generator=g).int().view(torch.float32)
-    rec[..., 2] = torch.randint(0, 3, (R, A), generator=g).int().view(torch.float32)
-    rec[..., 3:5] = torch.randn(R, A, 2, generator=g)
-    rec[..., 5] = torch.randn(R, A, generator=g) * 0.1 - 7.0
-    rec[..., 6] = torch.randn(R, A, generator=g)
-    rec[..., 7] = torch.randn(R, A, generator=g)
-    old_out = mlp.reference_outputs(th_old, x, emulate_bf16=False, dtype=torch.float32)
-    ls_old = th_old[mlp.OFF_LS:].clone()
-    dist_old = torch.cat([torch.log_softmax(old_out[:, :9], -1), torch.log_softmax(old_out[:, 9:19], -1), torch.log_softmax(old_out[:, 19:22], -1), old_out[:, 22:24],
-                          ls_old + old_out[:, 25:27], torch.zeros(R, 2)], dim=1).contiguous()           # a rollout's row: ... | the log-stds it was sampled with | 2 zeros
-    agents = 1 if slot is not None else A
-    upd = mlp.FusedUpdate(p, R, R, agents, chunks=chunks)
-    upd.perm.copy_(torch.randperm(R, generator=g))
-    recd, xd, dd, lsd = rec.to(DEV), x.to(DEV), dist_old.to(DEV), ls_old.to(DEV)
-    upd.set_extra(rec_stride=8 * A if slot is not None else 0, kl_coef=kl_coef, vf_clip=vf_clip, dist_old=dd, log_std_old=lsd)
-    theta0 = p.theta.clone()
-    base = recd.data_ptr() + (32 * slot if slot is not None else 0)
-    upd.minibatch_step(0, R, None, None, None, None, 0.3, 1.0, 0.01, 0.0, (0.9, 0.999), 1e-8, math.inf, records=(base, None, 0), obs_rows=xd, debug_outputs=True)
-    torch.cuda.synchronize()
-    assert torch.equal(p.theta, theta0)                          # lr = 0
-    grad, out6 = upd.grad.cpu().double(), upd.out6.cpu()
-    perm = upd.perm.cpu()
-    m = mlp.actor_critic_from_theta(p.theta).float()
-    sel = rec[:, slot:slot + 1] if slot is not None else rec     # [R, agents, 8]
-    acts = (sel[..., 0].contiguous().view(torch.int32).long().reshape(-1), sel[..., 1].contiguous().view(torch.int32).long().reshape(-1),
-            sel[..., 2].contiguous().view(torch.int32).long().reshape(-1), sel[..., 3:5].reshape(-1, 2))
-    loss, pg, vl, kl = _torch_objective(m, x, acts, sel[..., 5].reshape(-1), sel[..., 6].reshape(-1), sel[..., 7].reshape(-1), dist_old, ls_old,
-                                        0.3, 1.0, 0.01, kl_coef, vf_clip, agents)
-    loss.backward()
-    gm = _grad_vector(m)
-    # (1) tight: the loss gradient the kernel fed its backward pass, against float64 autograd on the kernel's own outputs (same decisions at the clip / clamp
-    #     boundaries): every shape-dependent piece - record stride, agents per row, the KL rows, the clamp - is in this step
-    pm = perm[:R]
-    g_out, g_ls = _loss_gradient_on_outputs(upd.out[:R].cpu(), p.theta[mlp.OFF_LS:].cpu(), sel[pm], dist_old[pm], ls_old, 0.3, 1.0, 0.01, kl_coef, vf_clip, sd=sd)
-    d_out = upd.d_out[:R].cpu().double()
-    scale = float(g_out.abs().max())
-    NC = 27 if sd else 25                                        # the columns that carry a gradient: 24 policy outputs, the value, (the head's two log-std offsets)
-    row_err = (d_out[:, :NC] - g_out[:, :NC]).abs().max(1).values
-    if sd:
-        assert float(d_out[:, 25:27].abs().max()) > 1e-3 * scale and float(upd.out[:R, 25:27].abs().max()) > 0.05
-    off = int((row_err > 1e-4 * scale).sum())
-    # (a sample EXACTLY on a clip / clamp boundary - within float32 rounding of it - may take the other branch in float64: at most one row per 20 000 samples)
-    assert off <= (R * agents) // 20000, ("d loss / d outputs", off, float(row_err.max()), scale)
-    assert float(d_out[:, NC:].abs().max()) == 0.0
-    assert float((grad[mlp.OFF_LS:] - g_ls).abs().max()) <= 1e-4 * float(g_ls.abs().max()) + 1e-9, ("d loss / d log_std", grad[mlp.OFF_LS:], g_ls)
-    # (2) the network's backward pass alone: the kernel's loss gradient pushed through the float32 PyTorch network by autograd - no decision is taken in this
-    #     comparison, what is left is bfloat16 operands against float32
-    m2 = mlp.actor_critic_from_theta(p.theta).float()
-    o2 = m2.trunk_packed(x[pm])
-    torch.autograd.backward([o2], [torch.cat([d_out[:, :NC], torch.zeros(R, 32 - NC, dtype=torch.float64)], 1).float()])
-    m2.log_std.grad = torch.zeros(2)
-    g2 = _grad_vector(m2)
-    for lo, hi, name in BLOCKS(mlp)[:-1]:
-        a, b = grad[lo:hi], g2[lo:hi]
-        assert (a - b).norm() <= 3e-2 * b.norm() + 1e-9, ("backward pass alone", name, float((a - b).norm() / b.norm()))
-    # (3) the whole gradient against float32 autograd through the PyTorch network
-    cos = float((grad * gm).sum() / (grad.norm() * gm.norm()))
-    assert cos > (0.9 if soak else 0.999), cos                   # bfloat16 operands against float32: direction within 1e-3, every block's magnitude within 3 %
-    # (with the state-dependent head every row's log-stds are bfloat16-operand products too - they scale the Gaussian heads' whole gradient: 4 %, measured 3.1 % on W1)
-    for lo, hi, name in BLOCKS(mlp):
-        a, b = grad[lo:hi], gm[lo:hi]
-        assert (a - b).norm() <= (0.5 if soak else (4e-2 if sd else 3e-2)) * b.norm() + 1e-9, (name, float((a - b).norm() / b.norm()))
-    assert abs(float(out6[3]) - float(loss.detach())) <= 2e-2 * abs(float(loss.detach())) + 1e-3
-    assert abs(float(out6[1]) - float(vl.detach())) <= 2e-2 * float(vl.detach()) + 1e-4
-    if kl_coef:
-        assert float(kl.detach()) > 1e-4 and abs(float(out6[6]) - float(kl.detach())) <= 3e-2 * float(kl.detach()) + 1e-5, (float(out6[6]), float(kl.detach()))
-    else:
-        assert float(out6[6]) == 0.0
-    if vf_clip and check_clip_share:                               # the clamp is active on a real share of the samples
-        frac = float(((m.evaluate(x, acts, agents_per_row=agents)[2] - sel[..., 7].reshape(-1)).pow(2) > vf_clip).float().mean())
-        assert 0.2 < frac < 0.95, frac
-    del perm
-    return cos
 
 
 def test_fused_league_training_runs_the_reference_topology():

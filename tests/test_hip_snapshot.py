@@ -233,3 +233,53 @@ def test_bad_ranges_are_refused():
     with pytest.raises(ValueError):
         env.snapshot(3, 2)
     env.close()
+
+
+@pytest.mark.parametrize("n", [4096, 2500])
+def test_checkpoint_size_snapshot_equals_its_ranges_and_restores_every_market(n):
+    """A checkpoint's snapshot of a whole env of 4096 / 2500 markets: k_snap_offsets' threads then size 4 / 3 markets each.  Deep books (HBM ring in use) grown
+    in markets on both sides of the chunk boundaries: the offset table and every section equal those of the snapshots of ranges of at most 1024 markets (one
+    market per thread), and a fresh env restored from it holds every market's state and book and steps on bit for bit."""
+    cfg = {"num_of_agents": 4, "init_cash": 10 ** 12, "max_step": 4096, "is_render": False, "book_capacity": 256, "book_spill": 1024, "auto_reset": True}
+    env = CDAVecEnv(cfg, n_markets=n, device="cuda:0", with_info=False)
+    env.reset(seed=n)
+    env.run_random(12, action_seed=3)
+    deep = [0, 2, 3, 4, 1022, 1023, 1024, n - 1]                        # (chunks of 4 / 3 markets: 2 | 3, 3 | 4, 1022 | 1023, 1023 | 1024 are boundaries)
+    for m in deep:                                                       # _grow_deep_books' orders, in these markets only
+        for k in range(1100):
+            env.place_order(m, k % 4, K.T_LIMIT, K.S_BID, 1 + k % 3, 20000 - k - 3 * m)
+        for k in range(1100 // 3):
+            env.place_order(m, (k + 1) % 4, K.T_LIMIT, K.S_ASK, 2, 30000 + k)
+    torch.cuda.synchronize()
+    snap = env.snapshot()
+    assert len(snap) == n
+    raw = snap.blob.cpu().numpy()
+    off = raw[256:256 + 8 * (n + 1)].view(np.int64)
+    assert off[n] == snap.nbytes and (np.diff(off) > 0).all()
+    stride = env.state_bytes_per_market()
+    for m in deep:                                                       # the ring holds a live window in every deep market, none in the others
+        meta = raw[off[m] + stride: off[m] + stride + 32].view(np.int32)
+        # (the 366 asks above every bid always rest: the ask ring holds > 100; the random agents' asks absorb a market-dependent share of the bids)
+        assert meta[3] > 100 and meta[2] >= 0, (m, meta.tolist(), len(env.get_book(m, 0)), len(env.get_book(m, 1)), env.book_capacity, env.book_spill)
+    sizes = np.diff(off)
+    assert len(set(sizes[np.setdiff1d(np.arange(n), deep)].tolist())) == 1 and (sizes[deep] > sizes[5]).all()
+    for f in range(0, n, 1024):
+        k = min(1024, n - f)
+        part = env.snapshot(f, k)
+        r = part.blob.cpu().numpy()
+        o = r[256:256 + 8 * (k + 1)].view(np.int64)
+        assert np.array_equal(np.diff(o), sizes[f:f + k]), f
+        assert np.array_equal(r[o[0]:o[k]], raw[off[f]:off[f + k]]), f                 # the sections, byte for byte
+    fresh = CDAVecEnv(cfg, n_markets=n, device="cuda:0", with_info=False)
+    fresh.reset(seed=1)
+    fresh.restore(snap)
+    for m in range(n):
+        assert bytes(fresh.get_state(m)) == bytes(env.get_state(m)), m
+        (b1, a1), (b2, a2) = fresh.get_book(m), env.get_book(m)
+        assert np.array_equal(b1, b2) and np.array_equal(a1, a2), m
+    assert torch.equal(fresh.snapshot().blob, snap.blob)
+    rng = np.random.default_rng(n)
+    acts = [_actions(rng, n, 4, env.device) for _ in range(10)]
+    _same_runs(_run(env, acts), _run(fresh, acts))
+    assert torch.equal(fresh.snapshot().blob, env.snapshot().blob)
+    env.close(); fresh.close()

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Soak of the fused update's gradient (k_mlp_fb + k_mlp_wgrad + k_grad_reduce: bf16 MFMA operands, f32 accumulation) against float32 autograd through the PyTorch
 statement of the network and of the objective, over random shapes: rows per minibatch (whole and ragged 64-row tiles), agents per row, a league's record stride
-selecting one slot, KL penalty, value-error clamp, weight-gradient chunk counts.  tests/test_hip_league.py check_gradient(soak=True) in three stages:
+selecting one slot, KL penalty, value-error clamp, weight-gradient chunk counts.  tests/update_check_util.py check_gradient(soak=True) in three stages:
 (1) TIGHT (1e-4 of the largest entry): the loss gradient the kernel feeds its backward pass against float64 autograd on the kernel's own outputs - where every
 shape-dependent piece lives; (2) the backward pass alone: that loss gradient pushed through the float32 PyTorch network by autograd, every parameter block within 3 %
 (bfloat16 operands against float32, no decision taken inside the comparison); (3) the whole gradient against float32 autograd of the whole objective, in WIDE bands
@@ -27,7 +27,7 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--log-std-head", action="store_true", help="every shape with the state-dependent log-std head (sd_log_std: columns 25, 26 carry the rows' log-std gradients)")
     a = ap.parse_args()
-    from test_hip_league import check_gradient
+    from update_check_util import check_gradient
     rng = np.random.default_rng(a.seed)
     t0, worst, failed = time.time(), 1.0, 0
     print(f"fused update gradient against float32 autograd, {a.configs} random shapes (seed {a.seed}):")
@@ -41,7 +41,7 @@ def main():
         seed = int(rng.integers(1, 1 << 30))
         what = f"  {i:3d}: {R:4d} rows x {A:2d} agents, slot {slot}, kl_coef {kl}, vf_clip {vf_clip}, {chunks} chunk(s), seed {seed}{', log-std head' if a.log_std_head else ''}"
         try:
-            cos = check_gradient(A, slot, kl, vf_clip, R=R, seed=seed, chunks=chunks, check_clip_share=False, soak=True, sd=a.log_std_head)
+            cos, _ = check_gradient(A, slot, kl, vf_clip, R=R, seed=seed, chunks=chunks, check_clip_share=False, soak=True, sd=a.log_std_head)
         except AssertionError as ex:
             print(f"{what}: FAILED {ex}", flush=True)
             failed += 1
