@@ -44,6 +44,17 @@ class Config(C.Structure):
     ]
 
 
+class MarketParams(C.Structure):
+    """cda_market_params (include/cda.h): the fields one market of an env may set for itself"""
+    _fields_ = [
+        ("max_step", C.c_int32), ("tick_size", C.c_int32), ("init_cash", C.c_int64),
+        ("initial_price_min", C.c_int32), ("initial_price_max", C.c_int32),
+        ("min_size", C.c_int32), ("mkt_max_size", C.c_int32), ("limit_size_multiple", C.c_int32), ("reserved", C.c_int32),
+        ("order_penalty", C.c_double), ("trade_penalty", C.c_double), ("drawdown_penalty", C.c_double),
+        ("passive_bonus", C.c_double), ("loss_multiplier", C.c_double),
+    ]
+
+
 class Dec(C.Structure):
     _fields_ = [("w", C.c_uint32 * 3), ("exp", C.c_int16), ("sign", C.c_uint8), ("pad", C.c_uint8)]
 

@@ -23,6 +23,7 @@ SYMBOLS = [
     "cda_step_range_capture", "cda_policy_step_supported", "cda_policy_step_advised", "cda_policy_step_range",
     "cda_episode_metrics_enable", "cda_episode_metrics_collect",
     "cda_snapshot_table_bytes", "cda_snapshot_offsets", "cda_snapshot_pack", "cda_snapshot_check_header", "cda_snapshot_restore",
+    "cda_market_params_from_config", "cda_check_market_params", "cda_set_market_params", "cda_get_market_params",
 ]
 
 
@@ -125,6 +126,10 @@ def lib():
     L.cda_snapshot_pack.argtypes = [vp, i32, i32, vp, vp, i64, vp]
     L.cda_snapshot_check_header.argtypes = [vp, C.POINTER(K.SnapshotHeader), i64]
     L.cda_snapshot_restore.argtypes = [vp, i32, vp, i64, i32, i32, vp, vp]
+    L.cda_market_params_from_config.argtypes = [C.POINTER(K.Config), C.POINTER(K.MarketParams)]
+    L.cda_check_market_params.argtypes = [C.POINTER(K.Config), i32, C.POINTER(K.MarketParams)]
+    L.cda_set_market_params.argtypes = [vp, i32, i32, C.POINTER(K.MarketParams)]
+    L.cda_get_market_params.argtypes = [vp, i32, i32, C.POINTER(K.MarketParams)]
     f32 = C.c_float
     L.cda_mlp_tile_rows.argtypes = []
     L.cda_mlp_tile_rows.restype = i32

@@ -7,6 +7,7 @@ Two modes:
   * `run_random_batched(...)`  N markets through `CDAVecEnv` with the same uniform action law sampled on the GPU.
 
     python -m gym_continuousdoubleauction_amd.cda_rand --agents 4 --steps 1000 --seed 123 [--markets 4096]
+    python -m gym_continuousdoubleauction_amd.cda_rand --markets 4096 --steps 256 --market-configs sweep.json     (`sweep`: one launch, many configs)
 """
 import argparse
 import sys
@@ -86,6 +87,41 @@ def run_random_batched(n_markets, num_agents=None, max_step=None, init_cash=None
     return steps, rate
 
 
+def sweep(configs, markets_per_config, steps, seed=0, base=None, device="cuda:0", env_out=None):
+    """The tuning use case in one launch: the override dicts `configs` (per-market keys, market_params.PER_MARKET_KEYS) laid out over ONE env of
+    len(configs) * markets_per_config markets (market m runs configs[m % len(configs)]), reset with `seed`, one cda_run_random launch of `steps`
+    steps.  `base`: the env config the overrides apply to (default: 4 agents, init_cash 1e6, max_step = steps; a config's max_step may not exceed
+    the env's).  Returns one dict per config: the markets that ran it, per agent the mean and std (population) of the episode return, and the mean
+    and std of the steps taken.  env_out: a list that receives the env (left open) instead of closing it."""
+    import numpy as np
+    import torch
+    from .vec_env import CDAVecEnv
+    from .market_params import round_robin
+    k, per = len(configs), int(markets_per_config)
+    if k < 1 or per < 1:
+        raise ValueError("sweep needs at least one config and one market per config")
+    cfg = {"num_of_agents": DEFAULT_AGENTS, "init_cash": DEFAULT_CASH, "max_step": int(steps), "is_render": False}
+    cfg.update(base or {})
+    env = CDAVecEnv(cfg, n_markets=k * per, device=device, with_info=False, market_configs=round_robin(list(configs), k * per))
+    try:
+        env.reset(seed=seed)
+        _, ret, _, _, taken = env.run_random(int(steps), action_seed=seed)
+        ret = ret.cpu().numpy().astype(np.float64)
+        taken = taken.cpu().numpy().astype(np.float64)
+        torch.cuda.synchronize(env.device)
+    finally:
+        if env_out is None:
+            env.close()
+        else:
+            env_out.append(env)
+    out = []
+    for c in range(k):
+        r, t = ret[c::k], taken[c::k]
+        out.append({"config": dict(configs[c]), "markets": int(len(r)), "return_mean": r.mean(axis=0).tolist(), "return_std": r.std(axis=0).tolist(),
+                    "steps_mean": float(t.mean()), "steps_std": float(t.std())})
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Random-agent CDA simulation on one MI355X.")
     ap.add_argument("--agents", type=int, default=DEFAULT_AGENTS)
@@ -94,7 +130,17 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--markets", type=int, default=1, help="> 1 runs the batched env")
     ap.add_argument("--per-step-launch", action="store_true", help="batched env: one launch per step instead of one per episode")
+    ap.add_argument("--market-configs", default=None, metavar="FILE.json", help="a sweep: a JSON list of per-market override dicts, market m runs entry m %% len(list); "
+                                                                              "prints one JSON line per entry (cda_rand.sweep over --markets markets)")
     args = ap.parse_args(argv)
+    if args.market_configs:
+        import json
+        from .market_params import load_market_configs
+        configs = load_market_configs(args.market_configs)
+        for row in sweep(configs, max(1, args.markets // len(configs)), args.steps, seed=args.seed or 0,
+                         base={"num_of_agents": args.agents, "init_cash": args.init_cash}):
+            print(json.dumps(row))
+        return 0
     if args.markets > 1:
         steps, rate = run_random_batched(args.markets, args.agents, args.steps, args.init_cash, seed=args.seed or 0,
                                          fused=not args.per_step_launch)

@@ -263,7 +263,7 @@ __attribute__((noinline, cold)) __device__ bool episode_summarise(uint8_t* arena
     __builtin_amdgcn_sched_barrier(0);
     D total = d_zero();
     for (int a = 0; a < A; a++) total = d_add(total, ld_dec(acc[a].nav));
-    D err = d_sub(total, d_mul_int(d_from_i64(P.cfg.init_cash), (uint32_t)A));
+    D err = d_sub(total, d_mul_int(d_from_i64(mrow(P, mi).init_cash), (uint32_t)A));
     err.sign = 0;
     uint32_t ferr = 0;
     const double e = d_to_double(err, &ferr);
@@ -343,7 +343,7 @@ __global__ void k_nav_conservation(const uint8_t* arena, Params P, double tol, d
     const Acc* acc = reinterpret_cast<const Acc*>(arena + (size_t)i * (size_t)P.lay.stride + (size_t)P.lay.acc_off);
     D total = d_zero();
     for (int a = 0; a < P.cfg.num_agents; a++) total = d_add(total, ld_dec(acc[a].nav));
-    D err = d_sub(total, d_mul_int(d_from_i64(P.cfg.init_cash), (uint32_t)P.cfg.num_agents));
+    D err = d_sub(total, d_mul_int(d_from_i64(mrow_lane(P, i).init_cash), (uint32_t)P.cfg.num_agents));
     err.sign = 0;
     uint32_t ferr = 0;
     const double e = d_to_double(err, &ferr);
@@ -522,7 +522,7 @@ __global__ void k_init_arena(uint8_t* arena, Params P) {
     for (int k = 0; k < P.lay.stride / 4; k++) w[k] = 0;
     Acc* acc = (Acc*)(rec + P.lay.acc_off);
     uint32_t f = 0;
-    const D cash = d_from_i64(P.cfg.init_cash);
+    const D cash = d_from_i64(mrow_lane(P, i).init_cash);
     for (int a = 0; a < P.cfg.num_agents; a++) { st_dec(acc[a].cash, cash, f); st_dec(acc[a].nav, cash, f); st_dec(acc[a].prev_nav, cash, f); st_dec(acc[a].max_nav, cash, f); }
 }
 // the random agents' actions of steps [step0, step0 + n_steps) for n_markets markets: one thread per (step, market, agent)
@@ -627,6 +627,8 @@ struct cda_env {
     int64_t hb_row_stride, hb_rows_total;   // cda_set_handback_geometry: rows between two ranks' first markets / global row count (0, 0 = equal shards of N)
     int32_t spill_wanted;    // orders per side the spill ring was asked to hold (automatic: num_agents * max_step rounded up); P.lay.spill_cap is what it got
     double* em_partials;     // cda_episode_metrics_collect: the blocks' partial sums (EM_BLOCKS rows)
+    MktRow* rows;            // the per-market parameter table (device): MktRow[n_markets + CDA_ROW_PAD]; P.rows points at it
+    cda_market_params* rows_host;   // what cda_set_market_params last wrote for each market (the config's row until then)
     uint32_t* snap_flag;     // cda_snapshot_restore: the check pass's verdict (allocated at the first restore)
 };
 static inline int32_t handback_stride_of(int32_t num_agents) { return (CDA_SNAPSHOT_DIM * 4 + num_agents * 8 + 3 + 7) & ~7; }
@@ -680,6 +682,57 @@ static int cfg_ok(const cda_config* c) {
     if (c->book_capacity != 0 && c->book_capacity != 256 && c->book_capacity != 512) return CDA_ERR_INVALID;
     if (c->init_cash > (1LL << 62) || c->init_cash < -(1LL << 62)) return CDA_ERR_INVALID;
     if (c->auto_reset != 0 && c->auto_reset != 1) return CDA_ERR_INVALID;
+    return CDA_OK;
+}
+
+// ---- per-market parameters ---------------------------------------------------------------------------------------------------------------------
+static void row_into_config(cda_config* c, const cda_market_params* r) {
+    c->max_step = r->max_step; c->tick_size = r->tick_size; c->init_cash = r->init_cash;
+    c->initial_price_min = r->initial_price_min; c->initial_price_max = r->initial_price_max;
+    c->min_size = r->min_size; c->mkt_max_size = r->mkt_max_size; c->limit_size_multiple = r->limit_size_multiple;
+    c->order_penalty = r->order_penalty; c->trade_penalty = r->trade_penalty; c->drawdown_penalty = r->drawdown_penalty;
+    c->passive_bonus = r->passive_bonus; c->loss_multiplier = r->loss_multiplier;
+}
+// a row is valid when the env's config with the row merged in passes cfg_ok (one set of domain rules) and its horizon is within the env's:
+// the automatic spill ring was sized from the env's max_step
+static int row_ok(const cda_config* env_cfg, const cda_market_params* r) {
+    if (r->reserved != 0) return CDA_ERR_INVALID;
+    cda_config c = *env_cfg;
+    row_into_config(&c, r);
+    const int rc = cfg_ok(&c);
+    if (rc) return rc;
+    if (r->max_step > env_cfg->max_step) return CDA_ERR_INVALID;
+    return CDA_OK;
+}
+// the device form of a row (the size scales with exactly the expressions cda_create has always used)
+static MktRow device_row(const cda_market_params* r) {
+    MktRow d;
+    memset(&d, 0, sizeof d);
+    d.max_step = r->max_step; d.tick_size = r->tick_size; d.price_min = r->initial_price_min; d.price_max = r->initial_price_max; d.min_size = r->min_size;
+    d.mkt_mul = (float)((double)(r->mkt_max_size - r->min_size) / 2.0);
+    d.lim_mul = (float)((double)((int64_t)r->mkt_max_size * (int64_t)r->limit_size_multiple - (int64_t)r->min_size) / 2.0);
+    d.init_cash = r->init_cash;
+    d.order_penalty = r->order_penalty; d.trade_penalty = r->trade_penalty; d.drawdown_penalty = r->drawdown_penalty;
+    d.passive_bonus = r->passive_bonus; d.loss_multiplier = r->loss_multiplier;
+    return d;
+}
+
+int cda_market_params_from_config(const cda_config* c, cda_market_params* r) {
+    if (!c || !r) return CDA_ERR_INVALID;
+    memset(r, 0, sizeof *r);
+    r->max_step = c->max_step; r->tick_size = c->tick_size; r->init_cash = c->init_cash;
+    r->initial_price_min = c->initial_price_min; r->initial_price_max = c->initial_price_max;
+    r->min_size = c->min_size; r->mkt_max_size = c->mkt_max_size; r->limit_size_multiple = c->limit_size_multiple;
+    r->order_penalty = c->order_penalty; r->trade_penalty = c->trade_penalty; r->drawdown_penalty = c->drawdown_penalty;
+    r->passive_bonus = c->passive_bonus; r->loss_multiplier = c->loss_multiplier;
+    return CDA_OK;
+}
+
+int cda_check_market_params(const cda_config* env_cfg, int32_t n, const cda_market_params* rows_host) {
+    if (!env_cfg || n < 0 || (n > 0 && !rows_host)) return CDA_ERR_INVALID;
+    int rc = cfg_ok(env_cfg);
+    if (rc) return rc;
+    for (int32_t i = 0; i < n; i++) if ((rc = row_ok(env_cfg, rows_host + i))) return rc;
     return CDA_OK;
 }
 
@@ -745,11 +798,32 @@ int cda_create(const cda_config* cfg, int32_t n_markets, int32_t device, cda_env
     if (he != hipSuccess) { free(e); return he == hipErrorOutOfMemory ? CDA_ERR_NOMEM : hip_fail(he, "hipMalloc"); }
     e->done_buf = e->arena + records;
     P.ep_tol = 1e-6;
+    // the per-market parameter table, every row the config's (also the CDA_ROW_PAD rows behind the last market)
+    {
+        const size_t nrows = (size_t)n_markets + CDA_ROW_PAD;
+        e->rows_host = (cda_market_params*)malloc(sizeof(cda_market_params) * (size_t)n_markets);
+        MktRow* staged = (MktRow*)malloc(sizeof(MktRow) * nrows);
+        he = (e->rows_host && staged) ? hipMalloc((void**)&e->rows, sizeof(MktRow) * nrows) : hipErrorOutOfMemory;
+        if (he == hipSuccess) {
+            cda_market_params r0;
+            cda_market_params_from_config(cfg, &r0);
+            const MktRow d0 = device_row(&r0);
+            for (size_t i = 0; i < nrows; i++) staged[i] = d0;
+            for (int32_t i = 0; i < n_markets; i++) e->rows_host[i] = r0;
+            he = hipMemcpy(e->rows, staged, sizeof(MktRow) * nrows, hipMemcpyHostToDevice);
+        }
+        free(staged);
+        if (he != hipSuccess) {
+            (void)hipFree(e->arena); if (e->rows) (void)hipFree(e->rows); free(e->rows_host); free(e);
+            return he == hipErrorOutOfMemory ? CDA_ERR_NOMEM : hip_fail(he, "market parameter table");
+        }
+        P.rows = e->rows;
+    }
     hipLaunchKernelGGL(k_init_arena, dim3((unsigned)((n_markets + 255) / 256)), dim3(256), 0, 0, e->arena, P);
     he = hipMemsetAsync(e->arena + em_agent_off(P), 0, spill_arena_off(P) - em_agent_off(P), 0);          // the episode-metric accumulators
     if (he == hipSuccess) he = hipMalloc((void**)&e->em_partials, (size_t)EM_BLOCKS * (CDA_EM_MAX_MODULES * CDA_EM_AGENT_FIELDS + CDA_EM_ENV_FIELDS) * sizeof(double));
     if (he == hipSuccess) he = hipDeviceSynchronize();
-    if (he != hipSuccess) { (void)hipFree(e->arena); if (e->em_partials) (void)hipFree(e->em_partials); free(e); return hip_fail(he, "k_init_arena"); }
+    if (he != hipSuccess) { (void)hipFree(e->arena); (void)hipFree(e->rows); free(e->rows_host); if (e->em_partials) (void)hipFree(e->em_partials); free(e); return hip_fail(he, "k_init_arena"); }
     if (cda_policy_step_supported(e)) (void)grant_policy_step_lds(e);          // (a refusal resurfaces as CDA_ERR_HIP at the first cda_policy_step_range)
     *out = e;
     return CDA_OK;
@@ -761,7 +835,39 @@ int cda_destroy(cda_env* e) {
     (void)hipFree(e->arena);
     if (e->em_partials) (void)hipFree(e->em_partials);
     if (e->snap_flag) (void)hipFree(e->snap_flag);
+    if (e->rows) (void)hipFree(e->rows);
+    free(e->rows_host);
     free(e);
+    return CDA_OK;
+}
+
+int cda_set_market_params(cda_env* e, int32_t first_market, int32_t n_markets, const cda_market_params* rows_host) {
+    if (!e || !rows_host || n_markets < 1 || first_market < 0 || (int64_t)first_market + (int64_t)n_markets > (int64_t)e->P.n_markets) return CDA_ERR_INVALID;
+    const int64_t cap = e->cap, ring = e->P.lay.spill_cap;
+    for (int32_t i = 0; i < n_markets; i++) {
+        const cda_market_params* r = rows_host + i;
+        const int rc = row_ok(&e->P.cfg, r);
+        if (rc) return rc;
+        // cda_create cut the ring so that the largest decodable size times the orders of a side stays in int32: a row must keep to that ring
+        const int64_t scale = (int64_t)r->mkt_max_size * (int64_t)r->limit_size_multiple + (int64_t)r->min_size;
+        if (ring > 0 && scale * (cap + ring) > 0x7fffffffLL) return CDA_ERR_INVALID;
+    }
+    MktRow* staged = (MktRow*)malloc(sizeof(MktRow) * (size_t)n_markets);
+    if (!staged) return CDA_ERR_NOMEM;
+    for (int32_t i = 0; i < n_markets; i++) staged[i] = device_row(rows_host + i);
+    hipError_t he = hipSetDevice(e->device);
+    // a launch in flight on any stream reads the rows it started with: the table is rewritten once the device is idle
+    if (he == hipSuccess) he = hipDeviceSynchronize();
+    if (he == hipSuccess) he = hipMemcpy(e->rows + first_market, staged, sizeof(MktRow) * (size_t)n_markets, hipMemcpyHostToDevice);
+    free(staged);
+    if (he != hipSuccess) return hip_fail(he, "cda_set_market_params");
+    memcpy(e->rows_host + first_market, rows_host, sizeof(cda_market_params) * (size_t)n_markets);
+    return CDA_OK;
+}
+
+int cda_get_market_params(const cda_env* e, int32_t first_market, int32_t n_markets, cda_market_params* rows_host_out) {
+    if (!e || !rows_host_out || n_markets < 1 || first_market < 0 || (int64_t)first_market + (int64_t)n_markets > (int64_t)e->P.n_markets) return CDA_ERR_INVALID;
+    memcpy(rows_host_out, e->rows_host + first_market, sizeof(cda_market_params) * (size_t)n_markets);
     return CDA_OK;
 }
 

@@ -79,8 +79,8 @@ __device__ __forceinline__ Lds& wave_lds(const Params& P, int wave, int extra = 
     return *reinterpret_cast<Lds*>(cda_smem + DEC_TABLE_BYTES + extra + (size_t)wave * (size_t)lds_bytes_per_wave(P.cfg.num_agents, P.cfg.n_hist));
 }
 
-__device__ __forceinline__ bool episode_over(const Mkt& m, const Params& P) {      // after step_loaded: t_step already counts the step
-    return __popc(m.done_mask) == P.cfg.num_agents || m.t_step >= P.cfg.max_step;
+__device__ __forceinline__ bool episode_over(const Mkt& m, const Params& P, int mi) {      // after step_loaded: t_step already counts the step
+    return __popc(m.done_mask) == P.cfg.num_agents || m.t_step >= mrow(P, mi).max_step;
 }
 // handback / keep_step_outputs: see cda_set_handback (include/cda.h).  keep_step_outputs = the auto-reset pass: the record keeps the
 // finished step's reward and flags and only receives the new episode's first frame.
@@ -98,7 +98,7 @@ __device__ __forceinline__ void reset_market(uint8_t* arena, const Params& P, Ld
     // NOT over is discarded like one the reference's callback never sees end; the conservation flag survives the device-side auto reset
     uint32_t keep_flags = keep_step_outputs ? (m.flags & CDA_FLAG_NAV_CONSERVATION) : 0u;
     if (m.status & ST_EP_ON) {
-        if (!(m.status & ST_EP_SUMMARISED) && episode_over(m, P)) {
+        if (!(m.status & ST_EP_SUMMARISED) && episode_over(m, P, mi)) {
             if constexpr (SUMMARISE) { if (episode_summarise(arena, Pk, mi, nullptr)) keep_flags |= CDA_FLAG_NAV_CONSERVATION; }
         } else if (!(m.status & ST_EP_SUMMARISED) && lane < P.cfg.num_agents) ep_clear(ep_stats(mp, P) + lane);      // (a summarised episode's tallies are clear already)
     }
@@ -106,12 +106,13 @@ __device__ __forceinline__ void reset_market(uint8_t* arena, const Params& P, Ld
     m.t_step = 0; m.lob_time = 0; m.next_oid = 0; m.has_trade = 0; m.last_trade_price = 0; m.done_mask = 0; m.flags = keep_flags;
     m.peak_orders = 0;
     m.status &= ST_EP_ON;                                 // (an empty book has no tail; its spill ring is simply forgotten)
-    m.last_price = rng_integers(m, P.cfg.initial_price_min, P.cfg.initial_price_max);
+    ConstRow& R = mrow(P, mi);
+    m.last_price = rng_integers(m, R.price_min, R.price_max);
     int A = P.cfg.num_agents;
     if (lane < A) {                                     // Account.reset_acc (account/account.py:55-82)
         Acc& a = L.acc[lane];
         uint32_t f = 0;
-        D cash = d_from_i64(P.cfg.init_cash), z = d_zero();
+        D cash = d_from_i64(R.init_cash), z = d_zero();
         st_dec(a.cash, cash, f); st_dec(a.hold, z, f); st_dec(a.posval, z, f); st_dec(a.vwap, z, f);
         st_dec(a.nav, cash, f); st_dec(a.prev_nav, cash, f); st_dec(a.max_nav, cash, f);
         a.net_position = 0; a.num_trades = 0; a.num_trades_step = 0; a.num_passive_fills_step = 0;
@@ -120,7 +121,7 @@ __device__ __forceinline__ void reset_market(uint8_t* arena, const Params& P, Ld
     aggregate_levels<false>(L, m, lane);
     int H = P.cfg.n_hist;
     if (lane < CDA_SNAPSHOT_DIM) {
-        float v = snapshot_value(L, m, P.cfg.tick_size, lane);
+        float v = snapshot_value(L, m, R.tick_size, lane);
         for (int h = 0; h < H; h++) {
             mp.hist[h * CDA_SNAPSHOT_DIM + lane] = v;
             if (obs_out) obs_out[(size_t)mi * (size_t)(H * CDA_SNAPSHOT_DIM) + (size_t)(h * CDA_SNAPSHOT_DIM + lane)] = v;
@@ -175,9 +176,9 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_reset(uint8_t* arena, Params P
 
 // phases 1-5: everything of a step that changes the market.  Returns the mask of agents that passed.
 template <bool TAILS>
-__device__ __forceinline__ uint32_t step_market(Lds& L, Mkt& m, const Params& P, const unsigned long long* zig_wi, const unsigned long long* zig_ki,
+__device__ __forceinline__ uint32_t step_market(Lds& L, Mkt& m, const Params& P, int mi, const unsigned long long* zig_wi, const unsigned long long* zig_ki,
                                                 const LaneAction& in, unsigned long long* ph, int lane) {
-    const int A = P.cfg.num_agents, tick = P.cfg.tick_size;
+    const int A = P.cfg.num_agents, tick = mrow(P, mi).tick_size;
     // 1. pre-step snapshot (continuousDoubleAuction_env.py:274): prices of ALL orders resolve against it.  It equals the
     //    post-step aggregation of the previous step, which travels in the header; recomputed only when a test hook,
     //    set_state or reset touched the book in between.
@@ -232,14 +233,14 @@ __device__ __forceinline__ uint32_t step_market(Lds& L, Mkt& m, const Params& P,
                 int type = cat == 0 ? T_MARKET : ((cat - 1) & 3);
                 // (both factors read as SCALARS first: `cond ? P.a : P.b` on a per-lane condition makes the compiler select the kernarg ADDRESS
                 //  per lane and fetch it with a vector load - a global round trip in the middle of the decode phase)
-                const float mul_mkt = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(P.mkt_mul)));
-                const float mul_lim = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(P.lim_mul)));
+                const float mul_mkt = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(mrow(P, mi).mkt_mul)));
+                const float mul_lim = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(mrow(P, mi).lim_mul)));
                 float locf = (type == T_MARKET ? mul_mkt : mul_lim) * mean;          // float32 product (numpy NEP 50)
                 double prod = (double)sigma * z;
                 double sample = (double)locf + prod;                                   // built with -ffp-contract=off
                 double rs = rint(fabs(sample));
                 if (rs > 1.0e9) { rs = 1.0e9; ovf = true; }
-                int32_t size = (int32_t)rs + P.cfg.min_size;
+                int32_t size = (int32_t)rs + mrow(P, mi).min_size;
                 int32_t pr = -1;
                 if (type != T_MARKET) {                                                // _set_price (action_helper.py:341-397)
                     int32_t p = L.lvl_px[side == S_BID ? 0 : 1][level];
@@ -297,7 +298,7 @@ __device__ __forceinline__ uint32_t step_market(Lds& L, Mkt& m, const Params& P,
 // while its helper lane (a + 16) converts max_nav - nav, in the same instruction stream.
 // WITH_MAX_NAV (info outputs): a third lane (a + 32) converts max_nav itself through the same call site, so the info
 // tensor float(max_nav) costs no conversion of its own.
-__device__ __forceinline__ StepReward step_reward(Lds& L, const Params& P, uint32_t& ferr, int lane, bool with_max_nav = false) {
+__device__ __forceinline__ StepReward step_reward(Lds& L, const Params& P, int mi, uint32_t& ferr, int lane, bool with_max_nav = false) {
     const int A = P.cfg.num_agents;
     StepReward o; o.r = o.t0 = o.t1 = o.t2 = o.t3 = o.t4 = o.drawdown = o.max_nav = 0.0; o.bankrupt = false;
     double conv = 0.0;
@@ -316,13 +317,14 @@ __device__ __forceinline__ StepReward step_reward(Lds& L, const Params& P, uint3
     if (lane < A) {
         const Acc& a = L.acc[lane];
         double nav_change = conv;
-        double nav_term = nav_change * (nav_change < 0 ? P.cfg.loss_multiplier : 1.0);
+        ConstRow& R = mrow(P, mi);
+        double nav_term = nav_change * (nav_change < 0 ? R.loss_multiplier : 1.0);
         o.drawdown = conv_helper;
         o.t0 = nav_term;
-        o.t1 = -(P.cfg.order_penalty * (double)a.order_step_placed);
-        o.t2 = -(P.cfg.trade_penalty * (double)a.num_trades_step);
-        o.t3 = -(P.cfg.drawdown_penalty * o.drawdown);
-        o.t4 = P.cfg.passive_bonus * (double)a.num_passive_fills_step;
+        o.t1 = -(R.order_penalty * (double)a.order_step_placed);
+        o.t2 = -(R.trade_penalty * (double)a.num_trades_step);
+        o.t3 = -(R.drawdown_penalty * o.drawdown);
+        o.t4 = R.passive_bonus * (double)a.num_passive_fills_step;
         double r = 0.0; r += o.t0; r += o.t1; r += o.t2; r += o.t3; r += o.t4;   // left to right (reward_helper.py:92-94)
         o.r = r;
         o.bankrupt = d_sgn(ld_dec(a.nav)) <= 0;
@@ -343,11 +345,11 @@ template <bool INFO, bool TAILS, int TALLY>
 __device__ __forceinline__ void step_loaded(const Params& P, const StepArgs& S, const MarketPtrs& mp, Lds& L, Mkt& m, LaneAction in, uint8_t present,
                                             const unsigned long long* zig_wi, const unsigned long long* zig_ki, int mi, int lane, unsigned long long* ph) {
     const bool has_info = INFO && S.has_info != 0;   // <true> keeps the run-time test (its code is the one-kernel build's), <false> folds it away
-    const int A = P.cfg.num_agents, H = P.cfg.n_hist, tick = P.cfg.tick_size;
+    const int A = P.cfg.num_agents, H = P.cfg.n_hist, tick = mrow(P, mi).tick_size;
     in.pres = lane < A && (!S.present || present != 0);
     in.ord = S.present ? (int)present : 1;
     uint32_t pass_mask = 0;
-    if (!CDA_DBG_HAS(S, 1)) pass_mask = step_market<TAILS>(L, m, P, zig_wi, zig_ki, in, ph, lane);
+    if (!CDA_DBG_HAS(S, 1)) pass_mask = step_market<TAILS>(L, m, P, mi, zig_wi, zig_ki, in, ph, lane);
     else if (!CDA_DBG_HAS(S, 2)) mark_to_mkt(L, m, A, lane);
     // 6. prep_next_state (state_helper.py:80-92): new frame, history ring, stacked observation.  The frame is COMPUTED here and
     //    written behind the last decimal routine of phase 7: every out-of-line function starts with s_waitcnt vmcnt(0) - it would
@@ -361,7 +363,7 @@ __device__ __forceinline__ void step_loaded(const Params& P, const StepArgs& S, 
     // 7. set_step_outputs (exchg_helper.py:93-124)
     uint32_t ferr = 0;
     StepReward rw; rw.r = rw.t0 = rw.t1 = rw.t2 = rw.t3 = rw.t4 = rw.drawdown = rw.max_nav = 0.0; rw.bankrupt = false;
-    if (!CDA_DBG_HAS(S, 8)) rw = step_reward(L, P, ferr, lane, has_info);
+    if (!CDA_DBG_HAS(S, 8)) rw = step_reward(L, P, mi, ferr, lane, has_info);
     if (has_info) {                                                          // Info_Helper.set_info (info_helper.py:30-116)
         // the four float(Decimal) fields of an account are converted by four lanes (a, a+16, a+32, a+48) through ONE call site
         const cda_info_ptrs& I = S.info;
@@ -431,7 +433,7 @@ __device__ __forceinline__ void step_loaded(const Params& P, const StepArgs& S, 
             if (I.spread) I.spread[mi] = (m.nb && m.na) ? ba - bb : __longlong_as_double(0x7ff8000000000000LL);
         }
         // Done_Helper.set_all_done (done_helper.py:20-54)
-        const bool term = __popc(m.done_mask) == A, trunc = m.t_step + 1 >= P.cfg.max_step;
+        const bool term = __popc(m.done_mask) == A, trunc = m.t_step + 1 >= mrow(P, mi).max_step;
         S.terminated_out[mi] = (uint8_t)term;
         S.truncated_out[mi] = (uint8_t)trunc;
         if (S.done_out) S.done_out[mi] = (uint8_t)(term || trunc);
@@ -442,7 +444,7 @@ __device__ __forceinline__ void step_loaded(const Params& P, const StepArgs& S, 
         if (lane < A) reinterpret_cast<double*>(rec + CDA_SNAPSHOT_DIM * 4)[lane] = rw.r;
         if (lane == 0) {
             uint8_t* fl = rec + CDA_SNAPSHOT_DIM * 4 + A * 8;
-            fl[0] = (uint8_t)(__popc(m.done_mask) == A); fl[1] = (uint8_t)(m.t_step + 1 >= P.cfg.max_step); fl[2] = 0;
+            fl[0] = (uint8_t)(__popc(m.done_mask) == A); fl[1] = (uint8_t)(m.t_step + 1 >= mrow(P, mi).max_step); fl[2] = 0;
         }
     }
     m.t_step += 1;
@@ -505,7 +507,7 @@ __attribute__((noinline, cold)) __device__ int slow_step(const StepKernArgs* ker
     m.dbg = S.dbg_skip;
 #endif
     step_loaded<INFO, true, 2>(P, S, mp, L, m, in, present, zig_wi, zig_ki, mi, lane, nullptr);
-    if constexpr (!INFO) { if (S.done_out && episode_over(m, P)) return (m.status & ST_EP_ON) ? 2 : 1; }
+    if constexpr (!INFO) { if (S.done_out && episode_over(m, P, mi)) return (m.status & ST_EP_ON) ? 2 : 1; }
     return 0;
 }
 // what the info-less step kernels do with a market whose episode has just ended: the callback's episode end, then the reset.  Out of line and thin - ONE cold call
@@ -580,7 +582,7 @@ __global__ __launch_bounds__(64 * CDA_WPB, CDA_MIN_WAVES) CDA_VGPR_CAP_ATTR void
     // (only in the info-less instance - the one a learner's rollout runs: in k_step<true> the extra call site cost 13-19 more spilled SGPRs and
     // 1.5 % of the headline, so an env that asks for info tensors AND auto reset keeps the k_reset launch behind the step)
     if constexpr (!INFO) {
-        if (__builtin_expect(S.done_out != nullptr && episode_over(m, P), 0)) {
+        if (__builtin_expect(S.done_out != nullptr && episode_over(m, P, mi), 0)) {
             if constexpr (TALLY) episode_end_after_step((const StepKernArgs*)__builtin_amdgcn_kernarg_segment_ptr(), mi, wave, true);
             else reset_after_step((const StepKernArgs*)__builtin_amdgcn_kernarg_segment_ptr(), mi, wave);      // (the metrics are off: the instance of every measured number)
         }
@@ -675,7 +677,7 @@ __device__ __forceinline__ int run_random_part(uint8_t* arena, const Params& P, 
     const unsigned long long* zig_ki = zig_wi + 256;
     MarketPtrs mp = market_ptrs(arena, P, mi);
     Mkt m;
-    const int A = P.cfg.num_agents, H = P.cfg.n_hist, tick = P.cfg.tick_size;
+    const int A = P.cfg.num_agents, H = P.cfg.n_hist, tick = mrow(P, mi).tick_size;
 #ifdef CDA_PHASE_TIMING
     for (int i = 0; i < 30; i++) m.tacc[i] = 0;
 #endif
@@ -692,7 +694,7 @@ __device__ __forceinline__ int run_random_part(uint8_t* arena, const Params& P, 
         LaneAction in;
         in.pres = lane < A; in.ord = 1; in.cat = 0; in.level = 0; in.off = 0; in.mean = 0.0f; in.sigma = 0.0f;
         if (in.pres) cda_random_action(R.seed, R.market_base + (uint64_t)mi, (uint32_t)m.t_step, (uint32_t)lane, &in.cat, &in.mean, &in.sigma, &in.level, &in.off);
-        const uint32_t pass_mask = step_market<TAILS>(L, m, P, zig_wi, zig_ki, in, nullptr, lane);
+        const uint32_t pass_mask = step_market<TAILS>(L, m, P, mi, zig_wi, zig_ki, in, nullptr, lane);
         aggregate_levels<TAILS>(L, m, lane);
         // Nobody reads the observation while the episode runs: the ring keeps the RAW frame (the 2 x 2 x 10 level
         // aggregation and last_price, 41 integers) and the normalisation (f64 divisions, square roots, log, log1p) is
@@ -701,7 +703,7 @@ __device__ __forceinline__ int run_random_part(uint8_t* arena, const Params& P, 
         else if (lane == 4 * CDA_K_ROWS) hist_raw[m.hist_head * CDA_SNAPSHOT_DIM + lane] = m.last_price;
         m.hist_head = m.hist_head + 1 >= H ? 0 : m.hist_head + 1;
         uint32_t ferr = 0;
-        const StepReward rw = step_reward(L, P, ferr, lane);
+        const StepReward rw = step_reward(L, P, mi, ferr, lane);
         if (lane < A) {
             ret += rw.r;
             if constexpr (TALLY != 0) {
@@ -711,7 +713,7 @@ __device__ __forceinline__ int run_random_part(uint8_t* arena, const Params& P, 
         }
         if (__ballot(ferr != 0)) m.flags |= CDA_FLAG_DEC_DOMAIN;
         m.done_mask |= (uint32_t)__ballot(rw.bankrupt);
-        term = __popc(m.done_mask) == A; trunc = m.t_step + 1 >= P.cfg.max_step;
+        term = __popc(m.done_mask) == A; trunc = m.t_step + 1 >= mrow(P, mi).max_step;
         m.t_step += 1;
         m.status |= ST_LEVELS_VALID;
         steps += 1; part_steps += 1;

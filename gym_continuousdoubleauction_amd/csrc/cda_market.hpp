@@ -105,13 +105,35 @@ __host__ __device__ constexpr Layout record_layout(int num_agents, int n_hist, i
     return l;
 }
 
+// One market's parameters (include/cda.h cda_market_params) as the kernels read them: a row per market in a device table that
+// every env has (cda_create fills each row from the config; cda_set_market_params rewrites rows).  A kernel reads the row of its
+// own market only - wave-uniform, so every field is a scalar load (see mrow) - in place of the config's field.
+struct MktRow {                  // 128 B (a power of two: the row's address is a shift and an add)
+    int32_t max_step, tick_size, price_min, price_max, min_size;
+    float mkt_mul, lim_mul;      // the decode's size scales, computed on the host (cda_create's expressions, per row)
+    int32_t pad0;
+    int64_t init_cash;
+    double order_penalty, trade_penalty, drawdown_penalty, passive_bonus, loss_multiplier;
+    int32_t pad1[12];
+};
+static_assert(sizeof(MktRow) == 128, "MktRow layout");
+
 struct Params {
-    cda_config cfg;
+    cda_config cfg;              // the env's config: its shape fields (agents, history, tile, ring, auto reset) hold for every market; the
+                                 // per-market fields are the DEFAULT row (and max_step the largest a row may take) - kernels read rows
     Layout lay;
     int32_t n_markets;
-    float mkt_mul, lim_mul;
+    float mkt_mul, lim_mul;      // (the default row's; host side only)
     double ep_tol;               // episode metrics: the callback's nav_tolerance (1e-6)
+    const MktRow* rows;          // MktRow[n_markets + CDA_ROW_PAD] (device)
 };
+constexpr int CDA_ROW_PAD = 64;  // rows behind the last market (copies of the default row): a workgroup's surplus waves index up to 15 beyond it
+// The row of market `mi` for a wave-uniform mi, through the constant address space: the table is written only between launches, so every
+// field is an s_load into SGPRs, issued where the compiler wants it - nothing in VGPRs, nothing held across the step that it cannot reload.
+typedef const __attribute__((address_space(4))) MktRow ConstRow;
+__device__ __forceinline__ ConstRow& mrow(const Params& P, int mi) { return ((ConstRow*)P.rows)[__builtin_amdgcn_readfirstlane(mi)]; }
+// ... and for a kernel with one market per THREAD (k_init_arena, k_nav_conservation)
+__device__ __forceinline__ const MktRow& mrow_lane(const Params& P, int mi) { return P.rows[mi]; }
 
 // ---- uniform (per-wave) market scalars kept in registers -----------------------------------
 struct Mkt {

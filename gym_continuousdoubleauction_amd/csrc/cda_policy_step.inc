@@ -110,7 +110,7 @@ __global__ __launch_bounds__(64 * PS_WPB, 1) void PS_NAME(k_policy_step)(PolicyS
         return;
     }
     step_loaded<false, false, TALLY ? 1 : 0>(P, S, mp, L, m, in, 1, zig_wi, zig_ki, mi, lane, ph);
-    if (__builtin_expect(S.done_out != nullptr && episode_over(m, P), 0)) {
+    if (__builtin_expect(S.done_out != nullptr && episode_over(m, P, mi), 0)) {
         if constexpr (TALLY) episode_end_after_step((const StepKernArgs*)__builtin_amdgcn_kernarg_segment_ptr(), mi, wave, true);
         else reset_after_step((const StepKernArgs*)__builtin_amdgcn_kernarg_segment_ptr(), mi, wave);
     }

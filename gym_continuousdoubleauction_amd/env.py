@@ -547,11 +547,12 @@ class CDAVecMultiAgentEnv(_DictSurface):
     With config["auto_reset"] a finished market restarts in place (see include/cda.h); otherwise reset(mask=...).
     """
 
-    def __init__(self, config=None, num_envs=1, device="cuda:0", with_info=True, groups=1):
+    def __init__(self, config=None, num_envs=1, device="cuda:0", with_info=True, groups=1, market_configs=None):
         super().__init__()
         self.config = dict(config or {})
         self.num_envs = int(num_envs)
-        self._vec = CDAVecEnv(self.config, n_markets=self.num_envs, device=device, with_info=with_info, groups=groups)
+        # market_configs: one override dict of per-market keys per sub-env (CDAVecEnv); the spaces are the same for every sub-env
+        self._vec = CDAVecEnv(self.config, n_markets=self.num_envs, device=device, with_info=with_info, groups=groups, market_configs=market_configs)
         self._init_surface(self._vec)
         self._seeded = False
         N, A = self.num_envs, self.num_of_agents

@@ -158,12 +158,13 @@ class BatchedEpisodeRecorder:
                 self._mk_t[j] += 1
                 if done[j]:
                     if getattr(self, "init_cash", None) is not None:
+                        cash = self.init_cash if np.ndim(self.init_cash) == 0 else self.init_cash[int(self.markets[j])]     # (per-market init_cash: a row per env market)
                         nav = np.ascontiguousarray(info["nav"][t][j]).view(K.DEC_DTYPE).reshape(A)
                         with decimal.localcontext() as ctx:
                             ctx.prec = 28
                             total = sum((K.dec_to_decimal(nav[a]) for a in range(A)), decimal.Decimal(0))
                         self.nav_checked += 1
-                        if abs(total - decimal.Decimal(A) * decimal.Decimal(int(self.init_cash))) > decimal.Decimal(str(getattr(self, "nav_tolerance", 1e-6))):
+                        if abs(total - decimal.Decimal(A) * decimal.Decimal(int(cash))) > decimal.Decimal(str(getattr(self, "nav_tolerance", 1e-6))):
                             self.nav_violations += 1
                     self._finish_market(j, complete=True)
                     self._mk_ordinal[j] += 1

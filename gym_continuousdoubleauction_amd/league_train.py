@@ -257,7 +257,7 @@ def train_league_fused(env, iters=4, horizon=None, num_trainable=2, lr=5e-5, epo
     if recorder is not None:
         names = lambda: np.array(mapper.available_modules, dtype=object)             # noqa: E731
         recorder.episode_namer = lambda m, e: f"{run_id}-episode{e}-market{m}"
-        recorder.init_cash = int(env.config.get("init_cash", 1000000))
+        recorder.init_cash = env.market_rows(0, N)["init_cash"].astype("int64") if getattr(env, "per_market", False) else int(env.config.get("init_cash", 1000000))
     history = []
     its = range(int(iters))
     if resumable:
@@ -439,18 +439,22 @@ def main(argv=None):
     p.add_argument("--chkpt-keep", type=int, default=3, help="--fused: keep the newest N checkpoints")
     p.add_argument("--restore", nargs="?", const=True, default=None, metavar="PATH", help="--fused: resume from the newest checkpoint under --checkpoint-dir, or from PATH")
     p.add_argument("--iters-is-delta", action="store_true", help="with --restore: --iters counts further iterations instead of being the target")
+    p.add_argument("--market-configs", default=None, metavar="FILE.json", help="per-market parameters: a JSON list of override dicts, market m runs entry m %% len(list) "
+                                                                             "(market_params.PER_MARKET_KEYS; a max_step there may not exceed --episode)")
     args = p.parse_args(argv)
     if not args.fused and (args.checkpoint_dir or args.restore):
         raise SystemExit("--checkpoint-dir / --restore need --fused")
     from .vec_env import CDAVecEnv
+    from .market_params import load_market_configs, round_robin
     from . import ppo
     cfg = {"num_of_agents": args.agents, "init_cash": 1000000, "max_step": args.episode, "is_render": False}
+    mcfg = round_robin(load_market_configs(args.market_configs), args.markets) if args.market_configs else None
     if not args.fused:
-        env = CDAVecEnv(cfg, n_markets=args.markets, device="cuda:0", with_info=False)
+        env = CDAVecEnv(cfg, n_markets=args.markets, device="cuda:0", with_info=False, market_configs=mcfg)
         train_league(env, iters=args.iters, num_trainable=args.trainable or 1)
         env.close()
         return
-    env = CDAVecEnv(dict(cfg, auto_reset=True), n_markets=args.markets, device="cuda:0", with_info=False)
+    env = CDAVecEnv(dict(cfg, auto_reset=True), n_markets=args.markets, device="cuda:0", with_info=False, market_configs=mcfg)
     k = args.trainable or 2
     bank, league, hist = train_league_fused(env, iters=args.iters, horizon=args.horizon, num_trainable=k, chains=args.chains,
                                          objective=ppo.RLLIB_DEFAULTS if args.objective == "rllib" else None, state_dependent_log_std=args.log_std_head, hidden=tuple(args.fcnet_hiddens),

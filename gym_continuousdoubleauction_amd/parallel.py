@@ -234,7 +234,9 @@ class ShardedVecEnv:
     side (default: the HIP kernel behind cda_handback_unpack; the CPU tests inject a restatement)."""
 
     def __init__(self, config, n_markets_total, device=None, env_factory=None, dist=None, groups=1, handback=False, unpack=None, transport="auto",
-                 force_collective=False):
+                 force_collective=False, market_configs=None):
+        if market_configs is not None:
+            raise ValueError("ShardedVecEnv does not take per-market parameters (market_configs) yet: build a CDAVecEnv per device with market_configs instead")
         import torch.distributed as tdist
         self.dist = dist or tdist
         self.rank = self.dist.get_rank() if self.dist.is_initialized() else 0

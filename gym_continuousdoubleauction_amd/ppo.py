@@ -768,11 +768,15 @@ def main(argv=None):
     p.add_argument("--chkpt-keep", type=int, default=3, help="fused loop: keep the newest N checkpoints")
     p.add_argument("--restore", nargs="?", const=True, default=None, metavar="PATH", help="fused loop: resume from the newest checkpoint under --checkpoint-dir, or from PATH")
     p.add_argument("--iters-is-delta", action="store_true", help="with --restore: --iters counts further iterations instead of being the target")
+    p.add_argument("--market-configs", default=None, metavar="FILE.json", help="per-market parameters: a JSON list of override dicts, market m runs entry m %% len(list) "
+                                                                             "(market_params.PER_MARKET_KEYS; a max_step there may not exceed --max-step)")
     args = p.parse_args(argv)
     from .vec_env import CDAVecEnv
+    from .market_params import load_market_configs, round_robin
     p_groups = max(1, min(args.groups, args.markets))
     env = CDAVecEnv({"num_of_agents": args.agents, "init_cash": 1000000, "max_step": args.max_step, "is_render": False, "auto_reset": True, "n_hist": args.n_hist},
-                    n_markets=args.markets, device="cuda:0", with_info=False, groups=p_groups)
+                    n_markets=args.markets, device="cuda:0", with_info=False, groups=p_groups,
+                    market_configs=round_robin(load_market_configs(args.market_configs), args.markets) if args.market_configs else None)
     from .mlp import HIST_VARIANTS
     if not args.legacy and ((args.horizon * args.markets) % 32 or env.n_hist not in HIST_VARIANTS):
         # the fused kernels step whole 32-row tiles and are compiled per history depth: other shapes run the PyTorch statement of the same loop

@@ -44,9 +44,10 @@ def parse_header(raw):
 class Snapshot:
     """A snapshot blob (uint8 tensor, device or CPU) and its parsed header.  len(snap) = markets it holds."""
 
-    def __init__(self, blob, header):
+    def __init__(self, blob, header, market_params=None):
         self.blob = blob
         self.header = header
+        self.market_params = market_params      # the rows of its markets (numpy, market_params.ROW_DTYPE), or None: the markets ran the env's config
 
     def __len__(self):
         return int(self.header["n_markets"])
@@ -56,7 +57,7 @@ class Snapshot:
         return int(self.header["total_bytes"])
 
     def to(self, device):
-        return Snapshot(self.blob.to(device), self.header)
+        return Snapshot(self.blob.to(device), self.header, self.market_params)
 
 
 def mismatch(header, env):
@@ -76,8 +77,14 @@ def mismatch(header, env):
 
 
 def snapshot_record(snap):
-    """the dict a snapshot file holds: {"format", "version", "header", "blob" (uint8, CPU)}"""
-    return {"format": SNAPSHOT_FORMAT, "version": SNAPSHOT_FILE_VERSION, "header": dict(snap.header), "blob": snap.blob.detach().to("cpu").contiguous().clone()}
+    """the dict a snapshot file holds: {"format", "version", "header", "blob" (uint8, CPU)} and, for markets with rows of their own, "market_params"
+    (uint8 [n, row bytes]: their cda_market_params rows)"""
+    rec = {"format": SNAPSHOT_FORMAT, "version": SNAPSHOT_FILE_VERSION, "header": dict(snap.header), "blob": snap.blob.detach().to("cpu").contiguous().clone()}
+    if snap.market_params is not None:
+        import numpy as np
+        rows = np.ascontiguousarray(snap.market_params)
+        rec["market_params"] = torch.from_numpy(rows.view(np.uint8).reshape(len(rows), rows.dtype.itemsize).copy())
+    return rec
 
 
 def check_snapshot_record(rec):
@@ -94,7 +101,13 @@ def check_snapshot_record(rec):
         raise ValueError(f"snapshot blob holds {blob.numel()} bytes, its header says {header['total_bytes']} (truncated or padded)")
     if rec.get("header") != header:
         raise ValueError("a snapshot file's header record does not match the blob's own header")
-    return Snapshot(blob, header)
+    rows = rec.get("market_params")
+    if rows is not None:
+        from .market_params import ROW_DTYPE
+        if not isinstance(rows, torch.Tensor) or rows.dtype != torch.uint8 or tuple(rows.shape) != (header["n_markets"], ROW_DTYPE.itemsize):
+            raise ValueError(f"a snapshot file's market_params must be uint8 [{header['n_markets']}, {ROW_DTYPE.itemsize}]")
+        rows = rows.contiguous().numpy().copy().view(ROW_DTYPE).reshape(-1)
+    return Snapshot(blob, header, market_params=rows)
 
 
 def save_snapshot(path, snap):

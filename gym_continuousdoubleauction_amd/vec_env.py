@@ -23,9 +23,19 @@ class CDAVecEnv:
     """Batched env.  Tensors: actions [N,A]; obs f32[N, n_hist*42]; reward f64[N,A];
     terminated/truncated bool[N] (the reference's "__all__" flags); info = dict of SoA tensors."""
 
-    def __init__(self, config=None, n_markets=1, device="cuda:0", with_info=True, out_buffers=1, groups=1, handback=False, group_streams=None):
+    def __init__(self, config=None, n_markets=1, device="cuda:0", with_info=True, out_buffers=1, groups=1, handback=False, group_streams=None,
+                 market_configs=None):
+        """market_configs: None (every market runs `config`) or a list of n_markets override dicts, one per market, holding only per-market keys
+        (market_params.PER_MARKET_KEYS); missing keys come from `config`.  A row is validated before the device is touched."""
         self.cfg_struct, self.config = K.make_config(config)
         self.n_markets = int(n_markets)
+        rows = None
+        if market_configs is not None:
+            from .market_params import rows_of
+            if len(market_configs) != self.n_markets:
+                raise ValueError(f"market_configs holds {len(market_configs)} configs for {self.n_markets} markets")
+            rows = rows_of(self.config, list(market_configs))
+        self.per_market = False             # whether rows were ever written (a snapshot then carries its markets' rows)
         self.host_epoch = 0                 # bumped by every host-side call that changes the markets (reset / step / run_random / place_order / set_state): consumers that keep
                                             # their own copy of the observations across calls (mlp.RolloutChains) compare it to know when theirs is stale
         self.num_agents = self.cfg_struct.num_agents
@@ -42,6 +52,8 @@ class CDAVecEnv:
         h = C.c_void_p()
         check(lib().cda_create(C.byref(self.cfg_struct), self.n_markets, self.device_index, C.byref(h)), "cda_create")
         self._h = h
+        if rows is not None:
+            self._write_rows(0, rows)
         self.book_capacity = int(lib().cda_book_capacity(h))     # LDS book tile: 256 or 512 resting orders per market (config['book_capacity'])
         self.book_spill = int(lib().cda_book_spill(h))           # HBM spill ring behind it: orders per side (config['book_spill']; 0 = none)
         self.book_spill_wanted = int(lib().cda_book_spill_wanted(h))   # ... and what an unbounded-inside-an-episode book needs
@@ -231,6 +243,76 @@ class CDAVecEnv:
         if self.groups > 1:
             self._need_fork = True          # the group streams must see this reset (issued on the caller's stream)
         return self.obs
+
+    # ------------------------------------------------------------------ per-market parameters (include/cda.h cda_market_params)
+    def _write_rows(self, first, rows):
+        if hasattr(self, "groups"):
+            self.join()                     # (in the constructor nothing has been launched yet)
+        with torch.cuda.device(self.device):
+            check(lib().cda_set_market_params(self._h, int(first), len(rows), rows), "cda_set_market_params")
+        self.per_market = True
+
+    def market_rows(self, first=0, n=None):
+        """the rows of markets [first, first + n) as a numpy array of market_params.ROW_DTYPE"""
+        from .market_params import rows_to_numpy
+        n = self.n_markets - int(first) if n is None else int(n)
+        rows = (K.MarketParams * n)()
+        check(lib().cda_get_market_params(self._h, int(first), n, rows), "cda_get_market_params")
+        return rows_to_numpy(rows)
+
+    def set_market_rows(self, first, rows_np):
+        """write numpy rows (market_params.ROW_DTYPE) to markets [first, first + len(rows_np)), validated first; no reset"""
+        from .market_params import rows_from_numpy, validate_rows
+        rows = rows_from_numpy(rows_np)
+        validate_rows(self.config, rows)
+        self._write_rows(first, rows)
+
+    def set_market_configs(self, configs, markets=None, seeds=None):
+        """Give markets `markets` (default: all, in order) the override dicts `configs` (one per market; missing keys from the env's config) and
+        reset exactly those markets: seeds=None keeps their RNG streams (reset(seed=None)), an int s seeds market i with s + i, a sequence seeds
+        the listed markets one by one.  Every row is validated before anything is written; the other markets are untouched."""
+        from .market_params import rows_of
+        idx = np.arange(self.n_markets) if markets is None else np.asarray(markets, dtype=np.int64).reshape(-1)
+        if len(configs) != len(idx):
+            raise ValueError(f"{len(configs)} configs for {len(idx)} markets")
+        if len(idx) == 0:
+            return self.obs
+        if idx.min() < 0 or idx.max() >= self.n_markets or len(np.unique(idx)) != len(idx):
+            raise ValueError("markets must be distinct indices in [0, n_markets)")
+        rows = rows_of(self.config, list(configs))
+        seed_arr = None
+        if seeds is not None:
+            seed_arr = np.zeros(self.n_markets, dtype=np.uint64)
+            if isinstance(seeds, (int, np.integer)):
+                seed_arr[idx] = np.uint64(int(seeds)) + idx.astype(np.uint64)
+            else:
+                sv = np.asarray(seeds, dtype=np.uint64).reshape(-1)
+                if len(sv) != len(idx):
+                    raise ValueError(f"{len(sv)} seeds for {len(idx)} markets")
+                seed_arr[idx] = sv
+        order = np.argsort(idx, kind="stable")
+        start = 0
+        while start < len(order):                          # one table write per run of consecutive markets
+            end = start + 1
+            while end < len(order) and idx[order[end]] == idx[order[end - 1]] + 1:
+                end += 1
+            run = (K.MarketParams * (end - start))(*[rows[int(j)] for j in order[start:end]])
+            self._write_rows(int(idx[order[start]]), run)
+            start = end
+        mask = np.zeros(self.n_markets, dtype=np.uint8)
+        mask[idx] = 1
+        return self.reset(seed=seed_arr, mask=mask)
+
+    def market_config(self, i):
+        """market i's effective config dict (the env's config with its row merged in)"""
+        from .market_params import row_dict
+        if not 0 <= int(i) < self.n_markets:
+            raise IndexError(f"market {i} outside [0, {self.n_markets})")
+        row = K.MarketParams()
+        check(lib().cda_get_market_params(self._h, int(i), 1, C.byref(row)), "cda_get_market_params")
+        out = dict(self.config)
+        out.update(row_dict(row))
+        return out
 
     # ------------------------------------------------------------------ market groups (groups > 1)
     def fork(self):
@@ -472,7 +554,7 @@ class CDAVecEnv:
             blob = torch.empty(total, dtype=torch.uint8, device=self.device)
             check(lib().cda_snapshot_pack(self._h, int(first), n, off.data_ptr(), blob.data_ptr(), total, self._stream()), "cda_snapshot_pack")
             header = parse_header(blob[:256].cpu())
-        return Snapshot(blob, header)
+        return Snapshot(blob, header, market_params=self.market_rows(int(first), n) if self.per_market else None)
 
     def restore(self, snap, first=0, src_first=0, n=None):
         """Markets [src_first, src_first + n) of `snap` -> markets [first, first + n) of this env (a Snapshot from this env or another with the same
@@ -488,6 +570,15 @@ class CDAVecEnv:
         why = mismatch(snap.header, self)
         if why is not None:
             raise ValueError(f"cannot restore this snapshot: {why}")
+        # the restored markets' rows: the snapshot's (validated against this env first), else - for an env with rows of its own - the env's config
+        rows = None
+        if snap.market_params is not None:
+            from .market_params import rows_from_numpy, validate_rows
+            rows = rows_from_numpy(snap.market_params[int(src_first):int(src_first) + n])
+            validate_rows(self.config, rows)
+        elif self.per_market:
+            from .market_params import rows_of
+            rows = rows_of(self.config, [{}] * n)
         blob = snap.blob
         if blob.device != self.device or blob.data_ptr() % 256 != 0:
             blob = blob.to(self.device).clone()
@@ -497,6 +588,8 @@ class CDAVecEnv:
             check(lib().cda_snapshot_restore(self._h, int(first), blob.data_ptr(), int(snap.nbytes), int(src_first), n, self.obs.data_ptr(), self._stream()),
                   "cda_snapshot_restore")
         blob.record_stream(torch.cuda.current_stream(self.device))     # (the allocator keeps it until the restore has run on this stream; nothing is held beyond)
+        if rows is not None:
+            self._write_rows(int(first), rows)          # (after the device's checks passed: a refused blob leaves the rows too as they were)
         if self.groups > 1:
             self.fork()                                 # the group streams see the restored markets
         return self.obs

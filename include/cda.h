@@ -543,6 +543,35 @@ int cda_snapshot_check_header(const cda_env* env, const cda_snapshot_header* hea
 int cda_snapshot_restore(cda_env* env, int32_t first_market, const void* blob_dev, int64_t blob_bytes, int32_t src_first, int32_t n_markets,
                          float* obs_out, void* stream);
 
+/* ---- per-market parameters: many configurations in one env ----------------------------------------------------------------------------
+ * Every market reads the fields below from a row of its own (a device table every env has; cda_create fills each row from the config).  The
+ * config's other fields - num_agents, n_hist, book_capacity, book_spill, auto_reset - set shapes, memory and kernel choice and hold for the
+ * whole env.
+ *   cda_market_params_from_config   the row a config implies (host only).
+ *   cda_check_market_params         validates rows against an env config without a device: a row is valid when the config with the row merged
+ *                                   in passes cda_create's checks and row.max_step <= config.max_step (the automatic spill ring is sized from
+ *                                   the config's horizon); CDA_ERR_UNSUPPORTED for a tick outside 1 .. CDA_TICK_MAX, CDA_ERR_INVALID otherwise.
+ *   cda_set_market_params           rows_host[i] -> market first_market + i.  Every row is validated first (the checks above, and a size scale
+ *                                   that fits the env's spill ring); one bad row returns the error and changes nothing.  Synchronous: it waits
+ *                                   for the device to be idle, then writes the table.
+ *   cda_get_market_params           the rows last written (the config's row for a market never set).
+ * Contract: a kernel uses the row that is in the table when it runs.  The markets are NOT reset: a changed init_cash, price range or horizon
+ * acts on a running episode from its next step on (sum(NAV) is then checked against the new init_cash) - resetting the changed markets is the
+ * caller's business (the Python env does it).  A snapshot blob carries no rows: restoring one keeps the target markets' rows. */
+typedef struct cda_market_params {
+    int32_t max_step;
+    int32_t tick_size;
+    int64_t init_cash;
+    int32_t initial_price_min, initial_price_max;
+    int32_t min_size, mkt_max_size, limit_size_multiple;
+    int32_t reserved;               /* 0 */
+    double  order_penalty, trade_penalty, drawdown_penalty, passive_bonus, loss_multiplier;
+} cda_market_params;
+int cda_market_params_from_config(const cda_config* cfg, cda_market_params* out_host);
+int cda_check_market_params(const cda_config* env_cfg, int32_t n, const cda_market_params* rows_host);
+int cda_set_market_params(cda_env* env, int32_t first_market, int32_t n_markets, const cda_market_params* rows_host);
+int cda_get_market_params(const cda_env* env, int32_t first_market, int32_t n_markets, cda_market_params* rows_host_out);
+
 const char* cda_strerror(int status);
 int32_t cda_num_markets(const cda_env* env);
 int32_t cda_num_agents(const cda_env* env);

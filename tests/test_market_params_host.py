@@ -1,0 +1,143 @@
+"""CPU: per-market environment parameters on the host (no GPU): a row is validated before anything reaches the device, the ctypes row matches C,
+--market-configs files are parsed and laid out round robin, and a snapshot file carries its markets' rows."""
+import ctypes as C
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+HEADER = os.path.join(ROOT, "include", "cda.h")
+
+BASE = {"num_of_agents": 4, "n_hist": 4, "max_step": 256, "is_render": False}
+
+
+@pytest.fixture(scope="module")
+def lib():
+    import __graft_entry__ as g
+    g.build_hip()
+    from gym_continuousdoubleauction_amd._lib import lib as L
+    return L()
+
+
+def _base():
+    from gym_continuousdoubleauction_amd import _capi as K
+    return K.make_config(BASE)[1]
+
+
+@pytest.mark.parametrize("bad", [
+    {"tick_size": 0}, {"tick_size": 65537},
+    {"initial_price_min": 50, "initial_price_max": 10},
+    {"max_step": 257},
+    {"mkt_max_size": 300000, "limit_size_multiple": 10},
+    {"num_of_agents": 5}, {"n_hist": 3},
+    {"min_size": -1}, {"init_cash": 2 ** 63 - 1},
+])
+def test_a_bad_row_is_refused_on_the_host(lib, bad):
+    from gym_continuousdoubleauction_amd.market_params import rows_of
+    with pytest.raises(ValueError):
+        rows_of(_base(), [{}, bad])
+
+
+def test_the_library_check_is_the_envs_own(lib):
+    from gym_continuousdoubleauction_amd import _capi as K
+    cfg, _ = K.make_config(BASE)
+    r = K.MarketParams()
+    assert lib.cda_market_params_from_config(C.byref(cfg), C.byref(r)) == 0
+    assert (r.max_step, r.tick_size, r.init_cash, r.loss_multiplier) == (256, 1, 1000000, 1.5)
+    assert lib.cda_check_market_params(C.byref(cfg), 1, C.byref(r)) == 0
+    for field, value, rc in (("tick_size", 0, K.ERR_UNSUPPORTED), ("tick_size", 65537, K.ERR_UNSUPPORTED), ("max_step", 257, K.ERR_INVALID), ("max_step", 0, K.ERR_INVALID),
+                             ("initial_price_max", 1 << 24, K.ERR_INVALID), ("limit_size_multiple", 0, K.ERR_INVALID), ("reserved", 1, K.ERR_INVALID)):
+        b = K.MarketParams.from_buffer_copy(r)
+        setattr(b, field, value)
+        assert lib.cda_check_market_params(C.byref(cfg), 1, C.byref(b)) == rc, field
+    rows = (K.MarketParams * 3)(r, r, r)
+    rows[2].max_step = 300
+    assert lib.cda_check_market_params(C.byref(cfg), 2, rows) == 0          # (only the first two are checked)
+    assert lib.cda_check_market_params(C.byref(cfg), 3, rows) == K.ERR_INVALID
+
+
+def test_rows_keep_the_overrides_and_take_the_rest_from_the_config(lib):
+    from gym_continuousdoubleauction_amd.market_params import row_dict, rows_of, rows_to_numpy, rows_from_numpy
+    rows = rows_of(_base(), [{"tick_size": 5, "init_cash": 400}, {}, {"trade_penalty": 0.5, "max_step": 40, "num_of_agents": 4}])
+    d = [row_dict(r) for r in rows]
+    assert d[0]["tick_size"] == 5 and d[0]["init_cash"] == 400 and d[0]["max_step"] == 256
+    assert d[1] == row_dict(rows_of(_base(), [{}])[0])
+    assert d[2]["trade_penalty"] == 0.5 and d[2]["max_step"] == 40 and d[2]["order_penalty"] == 0.1
+    back = rows_from_numpy(rows_to_numpy(rows))
+    assert [row_dict(r) for r in back] == d
+    with pytest.raises(KeyError):
+        rows_of(_base(), [{"no_such_key": 1}])
+
+
+def test_ctypes_row_layout_matches_c(tmp_path):
+    from gym_continuousdoubleauction_amd import _capi as K
+    fields = [n for n, _ in K.MarketParams._fields_]
+    src = tmp_path / "mp.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "%s"\nint main(){printf("%%zu", sizeof(cda_market_params));%s printf("\\n");return 0;}\n'
+                   % (HEADER, "".join(' printf(" %%zu", offsetof(cda_market_params, %s));' % f for f in fields)))
+    exe = tmp_path / "mp"
+    subprocess.check_call(["gcc", "-o", str(exe), str(src)])
+    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
+    assert got == [C.sizeof(K.MarketParams)] + [getattr(K.MarketParams, f).offset for f in fields]
+
+
+def test_market_configs_file_and_round_robin(tmp_path):
+    from gym_continuousdoubleauction_amd.market_params import load_market_configs, round_robin
+    p = tmp_path / "m.json"
+    p.write_text(json.dumps([{"tick_size": 2}, {"init_cash": 3000}, {}]))
+    cfgs = load_market_configs(str(p))
+    rr = round_robin(cfgs, 8)
+    assert rr == [cfgs[m % 3] for m in range(8)] and rr[4] == {"init_cash": 3000}
+    for bad in ("{}", "[]", "[1, 2]"):
+        p.write_text(bad)
+        with pytest.raises(ValueError):
+            load_market_configs(str(p))
+
+
+def test_the_clis_take_market_configs():
+    from gym_continuousdoubleauction_amd import cda_rand, league_train, ppo
+    import inspect
+    for mod in (cda_rand, ppo, league_train):
+        assert "--market-configs" in inspect.getsource(mod.main), mod.__name__
+    assert "market_configs" in inspect.signature(__import__("gym_continuousdoubleauction_amd.vec_env", fromlist=["CDAVecEnv"]).CDAVecEnv.__init__).parameters
+    from gym_continuousdoubleauction_amd.env import CDAVecMultiAgentEnv
+    assert "market_configs" in inspect.signature(CDAVecMultiAgentEnv.__init__).parameters
+
+
+def test_the_sharded_env_refuses_rows():
+    from gym_continuousdoubleauction_amd.parallel import ShardedVecEnv
+    with pytest.raises(ValueError, match="per-market"):
+        ShardedVecEnv(BASE, 8, market_configs=[{}] * 8)
+
+
+def test_a_snapshot_file_round_trips_with_rows(tmp_path, lib):
+    from gym_continuousdoubleauction_amd import _capi as K
+    from gym_continuousdoubleauction_amd.market_params import ROW_DTYPE, rows_of, rows_to_numpy
+    from gym_continuousdoubleauction_amd.snapshot import HEADER_BYTES, Snapshot, load_snapshot, parse_header, save_snapshot, table_bytes
+    n = 3
+    h = K.SnapshotHeader()
+    h.magic, h.version, h.n_markets, h.header_bytes = K.SNAP_MAGIC, K.SNAP_VERSION, n, table_bytes(n)
+    h.total_bytes = h.header_bytes + 256 * n
+    blob = torch.zeros(h.total_bytes, dtype=torch.uint8)
+    blob[:HEADER_BYTES] = torch.frombuffer(bytearray(bytes(h)), dtype=torch.uint8)
+    rows = rows_to_numpy(rows_of(_base(), [{"tick_size": 3}, {"init_cash": 400}, {"max_step": 17, "passive_bonus": 0.25}]))
+    snap = Snapshot(blob, parse_header(blob[:HEADER_BYTES]), market_params=rows)
+    save_snapshot(tmp_path / "s.snap", snap)
+    back = load_snapshot(tmp_path / "s.snap")
+    assert back.market_params.dtype == ROW_DTYPE and back.market_params.tobytes() == rows.tobytes()
+    assert torch.equal(back.blob, blob)
+    plain = Snapshot(blob, parse_header(blob[:HEADER_BYTES]))
+    save_snapshot(tmp_path / "p.snap", plain)
+    assert "market_params" not in torch.load(tmp_path / "p.snap", weights_only=True) and load_snapshot(tmp_path / "p.snap").market_params is None
+    rec = torch.load(tmp_path / "s.snap", weights_only=True)
+    rec["market_params"] = rec["market_params"][:2]
+    torch.save(rec, tmp_path / "t.snap")
+    with pytest.raises(ValueError):
+        load_snapshot(tmp_path / "t.snap")
+    assert np.array_equal(back.market_params["max_step"], [256, 256, 17])
