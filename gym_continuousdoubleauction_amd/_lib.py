@@ -37,6 +37,15 @@ MLP_SYMBOLS = [
 ]
 # the same entry points compiled for other history depths carry the suffix _h<H> (include/cda_mlp.h CDA_MLP_HIST_VARIANTS, csrc/cda_mlp_variant.h)
 MLP_HIST_VARIANTS = (1, 2, 3, 6, 7, 8)
+# ... and compiled for the other hidden activations (RLlib's fcnet_activation; tanh is the unsuffixed default), at every depth including 4, carry the suffix _<act>
+# behind the depth's: <name>[_h<H>]_<act> (include/cda_mlp.h CDA_MLP_ACT_VARIANTS)
+MLP_ACT_VARIANTS = ("relu", "elu", "linear")
+
+
+def mlp_variant_suffixes():
+    """the suffixes of every compiled variant of the network entry points besides the unsuffixed (n_hist 4, tanh) ones: _h<H>, _<act>, _h<H>_<act>"""
+    hs = [""] + [f"_h{h}" for h in MLP_HIST_VARIANTS]
+    return [f"_h{h}" for h in MLP_HIST_VARIANTS] + [h + "_" + a for h in hs for a in MLP_ACT_VARIANTS]
 
 
 class RolloutBufs(C.Structure):
@@ -174,9 +183,9 @@ def lib():
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("cda_strerror", "cda_group_range"):
             fn.restype = C.c_int
-    for h in MLP_HIST_VARIANTS:                              # same signatures, other observation width
+    for sfx in mlp_variant_suffixes():                       # same signatures, other observation width / activation
         for name in MLP_SYMBOLS:
-            base, var = getattr(L, name), getattr(L, f"{name}_h{h}")
+            base, var = getattr(L, name), getattr(L, name + sfx)
             var.argtypes, var.restype = base.argtypes, base.restype
     _lib = L
     return L

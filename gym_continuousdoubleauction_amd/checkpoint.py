@@ -126,6 +126,15 @@ def check_args(saved, now):
             raise ValueError(f"checkpoint was written by a run with {k} = {saved.get(k)!r}, this run has {k} = {now.get(k)!r}")
 
 
+def with_activation(args, activation):
+    """the loop arguments of a run whose network has hidden activation `activation`: the "activation" key is added only when it is not tanh, so a tanh run's
+    arguments are exactly what they were before the key existed (check_args compares the union of the keys: a tanh checkpoint written before then still
+    resumes, and one of either kind refuses a run of the other)"""
+    from .mlp import check_activation
+    act = check_activation(activation)
+    return dict(args, activation=act) if act != "tanh" else dict(args)
+
+
 def new_run_id():
     return uuid.uuid4().hex
 

@@ -27,7 +27,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <type_traits>
-#include "cda_mlp_variant.h"        // CDA_MLP_HIST != 4: every entry point of cda_mlp.h gets the suffix _h<H> (one object file per history depth)
+#include "cda_mlp_variant.h"        // CDA_MLP_HIST != 4 / CDA_MLP_ACT != 0: every entry point of cda_mlp.h gets the suffix [_h<H>][_<act>] (one object file per depth and activation)
 #include "../../include/cda_mlp.h"
 #include "../../include/cda_random_agents.h"
 
@@ -227,8 +227,8 @@ __global__ __launch_bounds__(256) void k_mlp_fwd(FwdArgs A) {
     for (int hf = 0; hf < 2; hf++)
         #pragma unroll
         for (int jt = 0; jt < 2; jt++) {
-            b1s[hf][jt] = theta[CDA_MLP_OFF_B1 + 256 * hf + 64 * w + 2 * j + jt] * TWO_LOG2E;
-            b2s[hf][jt] = theta[CDA_MLP_OFF_B2 + 256 * hf + 64 * w + 2 * j + jt] * TWO_LOG2E;
+            b1s[hf][jt] = theta[CDA_MLP_OFF_B1 + 256 * hf + 64 * w + 2 * j + jt] * Act::BIAS_SCALE;
+            b2s[hf][jt] = theta[CDA_MLP_OFF_B2 + 256 * hf + 64 * w + 2 * j + jt] * Act::BIAS_SCALE;
         }
     const float bo = theta[CDA_MLP_OFF_BO + j];
     const __bf16* W1b = wb + CDA_MLP_WB_W1; const __bf16* W2b = wb + CDA_MLP_WB_W2; const __bf16* Wob = wb + CDA_MLP_WB_WO;
@@ -259,7 +259,7 @@ __global__ __launch_bounds__(256) void k_mlp_fwd(FwdArgs A) {
             for (int it = 0; it < MT; it++) {
                 float v0[16], v1[16];
                 #pragma unroll
-                for (int r = 0; r < 16; r++) { v0[r] = tanh_biased(acc[it][0][r], bias0); v1[r] = tanh_biased(acc[it][1][r], bias1); }
+                for (int r = 0; r < 16; r++) { v0[r] = Act::apply(acc[it][0][r], bias0); v1[r] = Act::apply(acc[it][1][r], bias1); }
                 if (MODE == MODE_TRAIN) {                                       // (buffers are padded to whole workgroup tiles: no tail predicate)
                     store_packed(A.h1p, row0 / 32 + it, 16, (f0 >> 5), lane, v0);
                     store_packed(A.h1p, row0 / 32 + it, 16, (f0 >> 5) + 1, lane, v1);
@@ -284,7 +284,7 @@ __global__ __launch_bounds__(256) void k_mlp_fwd(FwdArgs A) {
             for (int it = 0; it < MT; it++) {
                 float v0[16], v1[16];
                 #pragma unroll
-                for (int r = 0; r < 16; r++) { v0[r] = tanh_biased(acc[it][0][r], bias0); v1[r] = tanh_biased(acc[it][1][r], bias1); }
+                for (int r = 0; r < 16; r++) { v0[r] = Act::apply(acc[it][0][r], bias0); v1[r] = Act::apply(acc[it][1][r], bias1); }
                 if (MODE == MODE_TRAIN) {
                     store_packed(A.h2p, row0 / 32 + it, 16, (f0 >> 5), lane, v0);
                     store_packed(A.h2p, row0 / 32 + it, 16, (f0 >> 5) + 1, lane, v1);
@@ -406,8 +406,8 @@ __global__ __launch_bounds__(512) void k_mlp_fwd8(FwdArgs A) {
     __bf16* act = xs + M * XS_LD + half * (M * ACT_LD);                         // this half's [M][ACT_LD]
     const long long row0 = (long long)blockIdx.x * M, rows_end = A.n_rows;
     const int f0 = 256 * half + 64 * w;
-    const float b1_0 = A.theta[CDA_MLP_OFF_B1 + f0 + 2 * j] * TWO_LOG2E, b1_1 = A.theta[CDA_MLP_OFF_B1 + f0 + 2 * j + 1] * TWO_LOG2E;
-    const float b2_0 = A.theta[CDA_MLP_OFF_B2 + f0 + 2 * j] * TWO_LOG2E, b2_1 = A.theta[CDA_MLP_OFF_B2 + f0 + 2 * j + 1] * TWO_LOG2E;
+    const float b1_0 = A.theta[CDA_MLP_OFF_B1 + f0 + 2 * j] * Act::BIAS_SCALE, b1_1 = A.theta[CDA_MLP_OFF_B1 + f0 + 2 * j + 1] * Act::BIAS_SCALE;
+    const float b2_0 = A.theta[CDA_MLP_OFF_B2 + f0 + 2 * j] * Act::BIAS_SCALE, b2_1 = A.theta[CDA_MLP_OFF_B2 + f0 + 2 * j + 1] * Act::BIAS_SCALE;
     const float bo = A.theta[CDA_MLP_OFF_BO + j];
     MLP_MARK8(0);
     load_x_bf16<M, 512>(A.x_rm, row0, rows_end, xs);
@@ -430,7 +430,7 @@ __global__ __launch_bounds__(512) void k_mlp_fwd8(FwdArgs A) {
     for (int it = 0; it < MT; it++) {                                           // E1
         float v0[16], v1[16];
         #pragma unroll
-        for (int r = 0; r < 16; r++) { v0[r] = tanh_biased(acc[it][0][r], b1_0); v1[r] = tanh_biased(acc[it][1][r], b1_1); }
+        for (int r = 0; r < 16; r++) { v0[r] = Act::apply(acc[it][0][r], b1_0); v1[r] = Act::apply(acc[it][1][r], b1_1); }
         store_packed(A.h1p, row0 / 32 + it, 16, (f0 >> 5), lane, v0);
         store_packed(A.h1p, row0 / 32 + it, 16, (f0 >> 5) + 1, lane, v1);
         store_lds_pair(act, ACT_LD, 32 * it, 64 * w, lane, v0, v1);
@@ -450,7 +450,7 @@ __global__ __launch_bounds__(512) void k_mlp_fwd8(FwdArgs A) {
     for (int it = 0; it < MT; it++) {                                           // E2
         float v0[16], v1[16];
         #pragma unroll
-        for (int r = 0; r < 16; r++) { v0[r] = tanh_biased(acc[it][0][r], b2_0); v1[r] = tanh_biased(acc[it][1][r], b2_1); }
+        for (int r = 0; r < 16; r++) { v0[r] = Act::apply(acc[it][0][r], b2_0); v1[r] = Act::apply(acc[it][1][r], b2_1); }
         store_packed(A.h2p, row0 / 32 + it, 16, (f0 >> 5), lane, v0);
         store_packed(A.h2p, row0 / 32 + it, 16, (f0 >> 5) + 1, lane, v1);
         store_lds_pair(act, ACT_LD, 32 * it, 64 * w, lane, v0, v1);
@@ -592,7 +592,7 @@ __global__ __launch_bounds__(256) void k_mlp_bwd(BwdArgs A) {
                 #pragma unroll
                 for (int r = 0; r < 16; r++) {
                     const float h0 = (float)hp[it][0][r >> 3][r & 7], h1 = (float)hp[it][1][r >> 3][r & 7];
-                    v0[r] = (float)(__bf16)(acc[it][0][r] * (1.0f - h0 * h0)); v1[r] = (float)(__bf16)(acc[it][1][r] * (1.0f - h1 * h1));
+                    v0[r] = (float)(__bf16)(acc[it][0][r] * Act::grad_from_out(h0)); v1[r] = (float)(__bf16)(acc[it][1][r] * Act::grad_from_out(h1));
                     colsum0 += v0[r]; colsum1 += v1[r];
                 }
                 store_packed(A.dz2p, row0 / 32 + it, 16, ft0, lane, v0); store_packed(A.dz2p, row0 / 32 + it, 16, ft0 + 1, lane, v1);
@@ -622,7 +622,7 @@ __global__ __launch_bounds__(256) void k_mlp_bwd(BwdArgs A) {
                 #pragma unroll
                 for (int r = 0; r < 16; r++) {
                     const float h0 = (float)hp[it][0][r >> 3][r & 7], h1 = (float)hp[it][1][r >> 3][r & 7];
-                    v0[r] = (float)(__bf16)(acc[it][0][r] * (1.0f - h0 * h0)); v1[r] = (float)(__bf16)(acc[it][1][r] * (1.0f - h1 * h1));
+                    v0[r] = (float)(__bf16)(acc[it][0][r] * Act::grad_from_out(h0)); v1[r] = (float)(__bf16)(acc[it][1][r] * Act::grad_from_out(h1));
                     colsum0 += v0[r]; colsum1 += v1[r];
                 }
                 store_packed(A.dz1p, row0 / 32 + it, 16, ft0, lane, v0); store_packed(A.dz1p, row0 / 32 + it, 16, ft0 + 1, lane, v1);
@@ -691,7 +691,7 @@ __global__ __launch_bounds__(512) void k_mlp_bwd8(BwdArgs A) {
             #pragma unroll
             for (int r = 0; r < 16; r++) {
                 const float h0 = (float)hp[it][0][r >> 3][r & 7], h1 = (float)hp[it][1][r >> 3][r & 7];
-                v0[r] = (float)(__bf16)(acc[it][0][r] * (1.0f - h0 * h0)); v1[r] = (float)(__bf16)(acc[it][1][r] * (1.0f - h1 * h1));
+                v0[r] = (float)(__bf16)(acc[it][0][r] * Act::grad_from_out(h0)); v1[r] = (float)(__bf16)(acc[it][1][r] * Act::grad_from_out(h1));
                 colsum0 += v0[r]; colsum1 += v1[r];
             }
             store_packed(A.dz2p, row0 / 32 + it, 16, ft0, lane, v0); store_packed(A.dz2p, row0 / 32 + it, 16, ft0 + 1, lane, v1);
@@ -718,7 +718,7 @@ __global__ __launch_bounds__(512) void k_mlp_bwd8(BwdArgs A) {
             #pragma unroll
             for (int r = 0; r < 16; r++) {
                 const float h0 = (float)hp[it][0][r >> 3][r & 7], h1 = (float)hp[it][1][r >> 3][r & 7];
-                v0[r] = (float)(__bf16)(acc[it][0][r] * (1.0f - h0 * h0)); v1[r] = (float)(__bf16)(acc[it][1][r] * (1.0f - h1 * h1));
+                v0[r] = (float)(__bf16)(acc[it][0][r] * Act::grad_from_out(h0)); v1[r] = (float)(__bf16)(acc[it][1][r] * Act::grad_from_out(h1));
                 colsum0 += v0[r]; colsum1 += v1[r];
             }
             store_packed(A.dz1p, row0 / 32 + it, 16, ft0, lane, v0); store_packed(A.dz1p, row0 / 32 + it, 16, ft0 + 1, lane, v1);
@@ -806,8 +806,8 @@ __global__ __launch_bounds__(256, 2) void k_mlp_fb(FbArgs A) {     // (two workg
     float* recs = lps + M * LPS_LD;                                             // [M][agents][8]: the tile's sample records
     const long long row0 = (long long)tile_id * M, rows_end = A.n_rows;
     const int f0 = 256 * half + 64 * w, ft0 = f0 >> 5;
-    const float b1_0 = A.theta[CDA_MLP_OFF_B1 + f0 + 2 * j] * TWO_LOG2E, b1_1 = A.theta[CDA_MLP_OFF_B1 + f0 + 2 * j + 1] * TWO_LOG2E;
-    const float b2_0 = A.theta[CDA_MLP_OFF_B2 + f0 + 2 * j] * TWO_LOG2E, b2_1 = A.theta[CDA_MLP_OFF_B2 + f0 + 2 * j + 1] * TWO_LOG2E;
+    const float b1_0 = A.theta[CDA_MLP_OFF_B1 + f0 + 2 * j] * Act::BIAS_SCALE, b1_1 = A.theta[CDA_MLP_OFF_B1 + f0 + 2 * j + 1] * Act::BIAS_SCALE;
+    const float b2_0 = A.theta[CDA_MLP_OFF_B2 + f0 + 2 * j] * Act::BIAS_SCALE, b2_1 = A.theta[CDA_MLP_OFF_B2 + f0 + 2 * j + 1] * Act::BIAS_SCALE;
     const float bo = A.theta[CDA_MLP_OFF_BO + j];
     float* bs = A.bias_slab + (size_t)tile_id * CDA_MLP_BSLAB;
     const __bf16* W1b = A.wb + CDA_MLP_WB_W1; const __bf16* W2b = A.wb + CDA_MLP_WB_W2; const __bf16* Wob = A.wb + CDA_MLP_WB_WO;
@@ -867,7 +867,7 @@ __global__ __launch_bounds__(256, 2) void k_mlp_fb(FbArgs A) {     // (two workg
     for (int it = 0; it < MT; it++) {                                           // E1
         float v0[16], v1[16];
         #pragma unroll
-        for (int r = 0; r < 16; r++) { v0[r] = tanh_biased(acc[it][0][r], b1_0); v1[r] = tanh_biased(acc[it][1][r], b1_1); }
+        for (int r = 0; r < 16; r++) { v0[r] = Act::apply(acc[it][0][r], b1_0); v1[r] = Act::apply(acc[it][1][r], b1_1); }
 #ifdef CDA_MLP_TIMING
         if (A.exper & 1) { keep_packed(v0, k1[it][0]); keep_packed(v1, k1[it][1]); } else
 #endif
@@ -892,7 +892,7 @@ __global__ __launch_bounds__(256, 2) void k_mlp_fb(FbArgs A) {     // (two workg
     for (int it = 0; it < MT; it++) {                                           // E2
         float v0[16], v1[16];
         #pragma unroll
-        for (int r = 0; r < 16; r++) { v0[r] = tanh_biased(acc[it][0][r], b2_0); v1[r] = tanh_biased(acc[it][1][r], b2_1); }
+        for (int r = 0; r < 16; r++) { v0[r] = Act::apply(acc[it][0][r], b2_0); v1[r] = Act::apply(acc[it][1][r], b2_1); }
         store_packed_keep(A.h2p, row0 / 32 + it, 16, ft0, lane, v0, k2[it][0]);
         store_packed_keep(A.h2p, row0 / 32 + it, 16, ft0 + 1, lane, v1, k2[it][1]);
         store_lds_pair(act, ACT_LD, 32 * it, 64 * w, lane, v0, v1);
@@ -1144,7 +1144,7 @@ __global__ __launch_bounds__(256, 2) void k_mlp_fb(FbArgs A) {     // (two workg
             #pragma unroll
             for (int r = 0; r < 16; r++) {
                 const float h0 = (float)k2[it][0][r >> 3][r & 7], h1 = (float)k2[it][1][r >> 3][r & 7];
-                v0[r] = (float)(__bf16)(acc[it][0][r] * (1.0f - h0 * h0)); v1[r] = (float)(__bf16)(acc[it][1][r] * (1.0f - h1 * h1));
+                v0[r] = (float)(__bf16)(acc[it][0][r] * Act::grad_from_out(h0)); v1[r] = (float)(__bf16)(acc[it][1][r] * Act::grad_from_out(h1));
                 colsum0 += v0[r]; colsum1 += v1[r];
             }
 #ifdef CDA_MLP_TIMING
@@ -1196,7 +1196,7 @@ __global__ __launch_bounds__(256, 2) void k_mlp_fb(FbArgs A) {     // (two workg
             #pragma unroll
             for (int r = 0; r < 16; r++) {
                 const float h0 = (float)k1[it][0][r >> 3][r & 7], h1 = (float)k1[it][1][r >> 3][r & 7];
-                v0[r] = (float)(__bf16)(acc[it][0][r] * (1.0f - h0 * h0)); v1[r] = (float)(__bf16)(acc[it][1][r] * (1.0f - h1 * h1));
+                v0[r] = (float)(__bf16)(acc[it][0][r] * Act::grad_from_out(h0)); v1[r] = (float)(__bf16)(acc[it][1][r] * Act::grad_from_out(h1));
                 colsum0 += v0[r]; colsum1 += v1[r];
             }
             store_packed(A.dz1p, row0 / 32 + it, 16, ft0, lane, v0); store_packed(A.dz1p, row0 / 32 + it, 16, ft0 + 1, lane, v1);
@@ -2231,7 +2231,8 @@ static int rollout_chain(cda_env* env, const cda_league* L, const void* wb, cons
         const char* ev = getenv("CDA_POLICY_STEP");              // read per call: an A / B run toggles it between two rollouts of one process
         const int want = ev ? atoi(ev) : 1;
         // (the env's history depth is this build's: checked above.  CDA_POLICY_STEP=2: wherever supported, also where the batched policy kernel is the faster one)
-        one_launch = !greedy && want != 0 && !L && !B->info_steps && (want == 2 ? cda_policy_step_supported(env) : cda_policy_step_advised(env));
+        // (k_policy_step is compiled with the tanh network only: an object of another activation (CDA_MLP_ACT) always takes the two launches)
+        one_launch = CDA_MLP_ACT == 0 && !greedy && want != 0 && !L && !B->info_steps && (want == 2 ? cda_policy_step_supported(env) : cda_policy_step_advised(env));
     }
     for (int32_t t = 0; t < n_steps; t++) {
         const size_t o = (size_t)t * NA;

@@ -48,6 +48,43 @@ __device__ __forceinline__ float tanh_biased(float a, float bias_scaled) {
     const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(a, TWO_LOG2E, bias_scaled));
     return __builtin_fmaf(-2.0f, __builtin_amdgcn_rcpf(e + 1.0f), 1.0f);
 }
+// ---- the hidden layers' activation: RLlib's fcnet_activation, one per object file (CDA_MLP_ACT: 0 tanh, the default and the reference's; 1 relu; 2 elu, alpha = 1;
+// 3 linear).  BIAS_SCALE is folded into the bias where it is loaded; apply(acc, bias_scaled) = act(acc + bias); grad_from_out(h) = act'(z) from the STORED
+// output h = act(z) - the backward never sees z.  Every act(0) = 0 (the dead units of a narrow network stay dead).  SiLU / swish has no such derivative (h does not
+// determine z), hence no trait.
+#ifndef CDA_MLP_ACT
+#define CDA_MLP_ACT 0
+#endif
+template <int ACT> struct ActT;
+template <> struct ActT<0> {
+    static constexpr float BIAS_SCALE = TWO_LOG2E;
+    static __device__ __forceinline__ float apply(float a, float bias_scaled) { return tanh_biased(a, bias_scaled); }
+    static __device__ __forceinline__ float grad_from_out(float h) { return 1.0f - h * h; }
+};
+template <> struct ActT<1> {
+    static constexpr float BIAS_SCALE = 1.0f;
+    static __device__ __forceinline__ float apply(float a, float b) { return fmaxf(a + b, 0.0f); }
+    static __device__ __forceinline__ float grad_from_out(float h) { return h > 0.0f ? 1.0f : 0.0f; }          // (torch: relu'(0) = 0)
+};
+template <> struct ActT<2> {
+    static constexpr float BIAS_SCALE = 1.0f;
+    static __device__ __forceinline__ float apply(float a, float b) {
+        // z < 0: e^z - 1.  2^(z log2 e) - 1 cancels as z -> 0- (all relative accuracy is gone by |z| ~ 1e-7), so -1/4 < z < 0 takes the Taylor series of
+        // expm1 to z^5 (truncation < z^6 / 720: relative 1.4e-6 at -1/4) and only z <= -1/4 (|e^z - 1| >= 0.22) the exponential
+        const float z = a + b;
+        const float p = z * __builtin_fmaf(z, __builtin_fmaf(z, __builtin_fmaf(z, __builtin_fmaf(z, 1.0f / 120.0f, 1.0f / 24.0f), 1.0f / 6.0f), 0.5f), 1.0f);
+        const float e = __builtin_amdgcn_exp2f(z * 1.442695040888963407f) - 1.0f;
+        return z > 0.0f ? z : (z > -0.25f ? p : e);
+    }
+    static __device__ __forceinline__ float grad_from_out(float h) { return h > 0.0f ? 1.0f : h + 1.0f; }     // (e^z = h + 1: exact for alpha = 1)
+};
+template <> struct ActT<3> {
+    static constexpr float BIAS_SCALE = 1.0f;
+    static __device__ __forceinline__ float apply(float a, float b) { return a + b; }
+    // (h - h) + 1 = 1 for every finite h.  A bare constant leaves the update kernel's stored-h registers dead, and k_mlp_fb's allocation then spills 81 SGPRs
+    static __device__ __forceinline__ float grad_from_out(float h) { return (h - h) + 1.0f; }
+};
+typedef ActT<CDA_MLP_ACT> Act;
 __device__ __forceinline__ f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ f32x16 zero16() { f32x16 z; for (int r = 0; r < 16; r++) z[r] = 0.0f; return z; }
 
@@ -224,7 +261,7 @@ __device__ __forceinline__ void forward16(const __bf16* __restrict__ wb, const f
     const int q = lane & 31, h = lane >> 5;
     const int half = w >> 3, grp = (w >> 1) & 3, jt = w & 1;
     const int f = 256 * half + 64 * grp + 2 * q + jt;                            // this lane's feature (of 512) in both hidden layers
-    const float b1 = theta[CDA_MLP_OFF_B1 + f] * TWO_LOG2E, b2 = theta[CDA_MLP_OFF_B2 + f] * TWO_LOG2E, bo = theta[CDA_MLP_OFF_BO + q];
+    const float b1 = theta[CDA_MLP_OFF_B1 + f] * Act::BIAS_SCALE, b2 = theta[CDA_MLP_OFF_B2 + f] * Act::BIAS_SCALE, bo = theta[CDA_MLP_OFF_BO + q];
     const bool heads = (w & 7) == 0;                                             // waves 0 and 8: the policy / value output tile of their half
     WRing<1, HID / 16, PF, false> R2, RO;
     f32x16 acc = zero16();
@@ -233,7 +270,7 @@ __device__ __forceinline__ void forward16(const __bf16* __restrict__ wb, const f
     {
         __bf16* dst = T.h1 + (half * F16_ROWS) * ACT_LD + 64 * grp + 2 * q + jt;
         #pragma unroll
-        for (int r = 0; r < 8; r++) dst[rowmap(r, h) * ACT_LD] = (__bf16)tanh_biased(acc[r], b1);
+        for (int r = 0; r < 8; r++) dst[rowmap(r, h) * ACT_LD] = (__bf16)Act::apply(acc[r], b1);
     }
     __syncthreads();
     acc = zero16();
@@ -242,7 +279,7 @@ __device__ __forceinline__ void forward16(const __bf16* __restrict__ wb, const f
     {
         __bf16* dst = T.h2 + (half * F16_ROWS) * ACT_LD + 64 * grp + 2 * q + jt;
         #pragma unroll
-        for (int r = 0; r < 8; r++) dst[rowmap(r, h) * ACT_LD] = (__bf16)tanh_biased(acc[r], b2);
+        for (int r = 0; r < 8; r++) dst[rowmap(r, h) * ACT_LD] = (__bf16)Act::apply(acc[r], b2);
     }
     __syncthreads();
     if (heads) {

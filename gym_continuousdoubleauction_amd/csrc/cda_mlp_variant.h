@@ -1,16 +1,35 @@
-/* cda_mlp_variant.h - one object file of csrc/cda_mlp.hip per history depth.
+/* cda_mlp_variant.h - one object file of csrc/cda_mlp.hip per history depth and hidden activation.
  *
  * The network kernels are compiled for ONE observation width (CDA_MLP_HIST frames of 42 floats: layer 1's k-steps, W1's operand layout, the LDS tiles, the dW1 slab
- * are compile-time shapes).  The default build (CDA_MLP_HIST = 4, the reference's n_hist) defines the entry points of include/cda_mlp.h under their own names; a
- * build with -DCDA_MLP_HIST=<H> renames every one of them to <name>_h<H> BEFORE the header is read, so declarations and definitions agree and the objects link into
- * one library (__graft_entry__.build_hip compiles CDA_MLP_HIST_VARIANTS).  Entry points that do not depend on the width (GAE, episode returns, league assignment)
- * are renamed too: a few duplicate kilobytes instead of a second source file.  Generated list: keep in step with include/cda_mlp.h (tests/test_capi_load.py checks it). */
+ * are compile-time shapes) and ONE hidden activation (CDA_MLP_ACT: 0 tanh, 1 relu, 2 elu, 3 linear - csrc/cda_mlp_dev.inc ActT).  The default build (CDA_MLP_HIST = 4,
+ * the reference's n_hist; tanh) defines the entry points of include/cda_mlp.h under their own names; a build with -DCDA_MLP_HIST=<H> and / or -DCDA_MLP_ACT=<a>
+ * renames every one of them to <name>[_h<H>][_<act>] (cda_mlp_forward_relu, cda_mlp_forward_h6_elu) BEFORE the header is read, so declarations and definitions
+ * agree and the objects link into one library (__graft_entry__.build_hip compiles CDA_MLP_HIST_VARIANTS x CDA_MLP_ACT_VARIANTS).  Entry points that depend on
+ * neither (GAE, episode returns, league assignment) are renamed too: a few duplicate kilobytes instead of a second source file.  Generated list: keep in step with
+ * include/cda_mlp.h (tests/test_capi_load.py checks it). */
 #ifndef CDA_MLP_VARIANT_H
 #define CDA_MLP_VARIANT_H
-#if defined(CDA_MLP_HIST) && CDA_MLP_HIST != 4
+#if defined(CDA_MLP_ACT) && CDA_MLP_ACT == 1
+#define CDA_MLP_ACT_NAME relu
+#elif defined(CDA_MLP_ACT) && CDA_MLP_ACT == 2
+#define CDA_MLP_ACT_NAME elu
+#elif defined(CDA_MLP_ACT) && CDA_MLP_ACT == 3
+#define CDA_MLP_ACT_NAME linear
+#elif defined(CDA_MLP_ACT) && CDA_MLP_ACT != 0
+#error "CDA_MLP_ACT: 0 tanh, 1 relu, 2 elu, 3 linear"
+#endif
 #define CDA_MLP_SFX2(n, h) n##_h##h
 #define CDA_MLP_SFX1(n, h) CDA_MLP_SFX2(n, h)
+#define CDA_MLP_ASFX2(n, a) n##_##a
+#define CDA_MLP_ASFX1(n, a) CDA_MLP_ASFX2(n, a)
+#if defined(CDA_MLP_HIST) && CDA_MLP_HIST != 4 && defined(CDA_MLP_ACT_NAME)
+#define CDA_MLP_SFX(n) CDA_MLP_ASFX1(CDA_MLP_SFX1(n, CDA_MLP_HIST), CDA_MLP_ACT_NAME)
+#elif defined(CDA_MLP_HIST) && CDA_MLP_HIST != 4
 #define CDA_MLP_SFX(n) CDA_MLP_SFX1(n, CDA_MLP_HIST)
+#elif defined(CDA_MLP_ACT_NAME)
+#define CDA_MLP_SFX(n) CDA_MLP_ASFX1(n, CDA_MLP_ACT_NAME)
+#endif
+#ifdef CDA_MLP_SFX
 #define cda_mlp_tile_rows CDA_MLP_SFX(cda_mlp_tile_rows)
 #define cda_mlp_wgrad_jobs CDA_MLP_SFX(cda_mlp_wgrad_jobs)
 #define cda_mlp_pack CDA_MLP_SFX(cda_mlp_pack)

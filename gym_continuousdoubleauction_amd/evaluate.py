@@ -64,8 +64,10 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
     opponents: None = self-play; else a list of "random", FusedPolicy objects or policy files, placed by slot_modules.  trained_slots: the policy's slots per
     market when there are opponents (default 1).  groups: rollout chains (default 4).  keep (a dict, optional): receives the RolloutChains object, the
     placement, the collected metric tables (agent table, env row) and host copies of every step's env actions (`actions`: category, size_mean, size_sigma,
-    price, price_offset as [steps, N, A]) - what a replay needs."""
-    from .mlp import LEAGUE_RANDOM, PolicyBank, RolloutChains
+    price, price_offset as [steps, N, A]) - what a replay needs.
+    Every network opponent must have the policy's hidden activation (the bank's rows are launched by one activation's kernels): ValueError otherwise, raised
+    before the opponent is loaded and before anything runs."""
+    from .mlp import LEAGUE_RANDOM, FusedPolicy, PolicyBank, RolloutChains, read_policy
     if mode not in ("greedy", "sample"):
         raise ValueError(f"mode must be 'greedy' or 'sample' (got {mode!r})")
     if not bool(env.config.get("auto_reset", False)):
@@ -79,6 +81,9 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
     for p, o in enumerate(opp or []):
         if isinstance(o, str) and o == RANDOM:
             continue
+        act = o.activation if isinstance(o, FusedPolicy) else read_policy(o, with_activation=True)[1]
+        if act != pol.activation:
+            raise ValueError(f"opponent {p} is a {act} network, the policy a {pol.activation} one: a bank holds networks of one activation")
         op = _as_policy(o, dev)
         if op.L.hist != pol.L.hist:
             raise ValueError(f"opponent {p} is laid out for n_hist = {op.L.hist}, the policy for {pol.L.hist}")
@@ -97,7 +102,8 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
         if opp is None:
             driver = pol
         else:
-            bank = PolicyBank(dev, N, A, n_trainable=1, max_frozen=max(1, len(nets)), random_seed=seed, n_hist=pol.L.hist)
+            bank = PolicyBank(dev, N, A, n_trainable=1, max_frozen=max(1, len(nets)), random_seed=seed, n_hist=pol.L.hist,
+                              activation=pol.activation)
             bank.theta[0].copy_(pol.theta)
             bank.wb[0].copy_(pol.wb)
             row_of = {}
@@ -144,7 +150,8 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
                       "slots": int((modules == i).sum())}
     result = {"mode": mode, "episodes": summary["episodes"], "nav_conservation_violations": summary["nav_conservation_violations"], "modules": mods,
               "config": {"markets": N, "agents": A, "max_step": int(env.max_step), "episodes": int(episodes), "steps": total, "horizon": T, "seed": int(seed),
-                         "trained_slots": k, "opponents": None if opp is None else [_describe(o) for o in opp], "n_hist": pol.L.hist},
+                         "trained_slots": k, "opponents": None if opp is None else [_describe(o) for o in opp], "n_hist": pol.L.hist,
+                         "activation": pol.activation},
               "agent_steps_per_s": N * A * total / wall if wall > 0 else None,
               "summary": summary}
     if keep is not None:
@@ -168,7 +175,7 @@ def main(argv=None):
     args = p.parse_args(argv)
     from .mlp import layout_of_params, read_policy
     from .vec_env import CDAVecEnv
-    n_hist = layout_of_params(read_policy(args.policy).numel()).hist
+    n_hist = layout_of_params(read_policy(args.policy).numel()).hist             # (the hidden activation comes with the file: load_policy)
     env = CDAVecEnv({"num_of_agents": args.agents, "init_cash": 1000000, "max_step": args.max_step, "is_render": False, "auto_reset": True, "n_hist": n_hist},
                     n_markets=args.markets, device="cuda:0", with_info=False)
     try:

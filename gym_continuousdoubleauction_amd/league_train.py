@@ -172,7 +172,7 @@ def train_league_fused(env, iters=4, horizon=None, num_trainable=2, lr=5e-5, epo
                        std_dev_multiplier=0.1, max_champions=8, min_iterations_between_champions=2, chains=4, minibatch=262144, objective=None, use_graph=True,
                        recorder=None, info_markets=0, run_id="league", log=print, keep=None, allreduce=None, world=1, first_market=0, episode_metrics=True,
                        strict_nav_check=True, state_dependent_log_std=False, hidden=(256, 256),
-                       checkpoint_dir=None, chkpt_freq=0, chkpt_keep=3, restore=None, iters_is_delta=False):
+                       checkpoint_dir=None, chkpt_freq=0, chkpt_keep=3, restore=None, iters_is_delta=False, activation="tanh"):
     """League self-play on the fused kernels (include/cda_mlp.h `cda_league`): the reference's training topology - `num_trainable` SEPARATELY trained policies
     (policy_p plays slot p), every other slot drawn per episode from the pool of uniform random modules and frozen champions by the reference's mapping rule
     (computed on the device, league.LeagueSlotMapper.assign_device) - at the speed of the fused loop: ONE policy launch per step serves every module of every
@@ -191,7 +191,8 @@ def train_league_fused(env, iters=4, horizon=None, num_trainable=2, lr=5e-5, epo
     max_step / horizon (ValueError otherwise), and the final save is skipped when the run does not end on a boundary.  It holds the env snapshot, every
     trainable net (theta + Adam), every bank row as save_league's policy files (league/ in the checkpoint) plus the bank's packed weights, the League and mapper
     state (champions and their rows, promotion history, champion id counter, pool), the rollout counters, the updates' shuffle state, the KL coefficients and
-    the running episode returns: the mapping, episode ids and promotions continue exactly.  Single-process runs only; no recorder."""
+    the running episode returns: the mapping, episode ids and promotions continue exactly.  Single-process runs only; no recorder.
+    activation: `fcnet_activation` of the whole bank (mlp.PolicyBank: trainable policies and their champion snapshots share it)."""
     import numpy as np
     from . import ppo
     from .mlp import EpisodeReturns, FusedUpdate, PolicyBank, RolloutChains
@@ -207,7 +208,8 @@ def train_league_fused(env, iters=4, horizon=None, num_trainable=2, lr=5e-5, epo
     resumable = CK.check_resumable(checkpoint_dir, chkpt_freq, restore, world=world, allreduce=allreduce, recorder=recorder)
     if resumable and int(chkpt_freq) % per_episode:
         raise ValueError(f"league checkpoints are taken at episode boundaries only: chkpt_freq ({chkpt_freq}) must be a multiple of max_step / horizon = {per_episode}")
-    bank = PolicyBank(dev, N, A, k, max_frozen=max_champions, seed=seed, random_seed=seed + 12345 + 104729 * int(first_market), n_hist=env.n_hist, state_dependent_log_std=state_dependent_log_std, hidden=hidden)
+    bank = PolicyBank(dev, N, A, k, max_frozen=max_champions, seed=seed, random_seed=seed + 12345 + 104729 * int(first_market), n_hist=env.n_hist, state_dependent_log_std=state_dependent_log_std, hidden=hidden,
+                      activation=activation)
     mapper = LeagueSlotMapper(A, k, A - k, original_opponent_weight, champion_weight)
     league = League(mapper, bank, std_dev_multiplier, max_champions, min_iterations_between_champions)
     ck_state = None
@@ -219,6 +221,7 @@ def train_league_fused(env, iters=4, horizon=None, num_trainable=2, lr=5e-5, epo
                     "seed": int(seed), "episode_metrics": bool(episode_metrics), "max_champions": int(max_champions), "std_dev_multiplier": float(std_dev_multiplier),
                     "min_iterations_between_champions": int(min_iterations_between_champions), "original_opponent_weight": float(original_opponent_weight),
                     "champion_weight": float(champion_weight), "run_id": str(run_id)}
+        run_args = CK.with_activation(run_args, bank.activation)
         if restore:
             ck_path = CK.resolve_restore(checkpoint_dir, restore)
             ck_state, ck_snap = CK.load_checkpoint(ck_path)
@@ -379,8 +382,10 @@ def _load_league_state(league_dir, state, bank, league):
     with open(os.path.join(league_dir, "league.json")) as fh:
         lj = json.load(fh)
     for entry in lj["trainable"] + lj["champions"]:
-        theta = read_policy(os.path.join(league_dir, entry["file"]))
+        theta, act = read_policy(os.path.join(league_dir, entry["file"]), with_activation=True)
         row = int(entry["row"])
+        if act != bank.activation:
+            raise ValueError(f"{entry['file']}: a {act} network, the bank's are {bank.activation}")
         if theta.numel() != bank.theta.shape[1]:
             raise ValueError(f"{entry['file']}: {theta.numel()} parameters, the bank rows hold {bank.theta.shape[1]}")
         bank.theta[row].copy_(theta)
@@ -401,16 +406,17 @@ def save_league(directory, bank, league):
     (mlp.save_policy's format) and a league.json naming them: module id, bank row, file, and for champions the promotion iteration / return / source.
     Returns the league.json dict."""
     from .mlp import policy_record
+    act = getattr(bank, "activation", "tanh")                   # (the bank's one activation: every file carries it, tanh files no key)
     os.makedirs(directory, exist_ok=True)
     promoted = {c["id"]: c for c in league.history}
     out = {"format": "cda-league", "version": 1, "trainable": [], "champions": []}
     for p in range(bank.n_trainable):
         fname = f"policy_{p}.pt"
-        torch.save(policy_record(bank.theta[p]), os.path.join(directory, fname))
+        torch.save(policy_record(bank.theta[p], activation=act), os.path.join(directory, fname))
         out["trainable"].append({"module": f"policy_{p}", "row": p, "file": fname})
     for cid, row in sorted(league.net_of.items(), key=lambda kv: kv[1]):
         fname = "champion_" + "".join(ch if ch.isalnum() or ch in "-_" else "_" for ch in str(cid)) + ".pt"
-        torch.save(policy_record(bank.theta[row]), os.path.join(directory, fname))
+        torch.save(policy_record(bank.theta[row], activation=act), os.path.join(directory, fname))
         c = promoted.get(cid, {})
         out["champions"].append({"module": str(cid), "row": int(row), "file": fname, "promoted_iteration": c.get("iteration"),
                                  "return": None if c.get("return") is None else float(c["return"]), "source": None if c.get("source") is None else str(c["source"])})
@@ -431,6 +437,8 @@ def main(argv=None):
     p.add_argument("--chains", type=int, default=4)
     p.add_argument("--objective", choices=("ppo", "rllib"), default="ppo")
     p.add_argument("--fcnet-hiddens", type=int, nargs=2, default=(256, 256), metavar=("H1", "H2"), help="hidden widths of the trainable policies (config/train_config.json:49), <= 256 each")
+    p.add_argument("--fcnet-activation", choices=("tanh", "relu", "elu", "linear"), default="tanh",
+                   help="--fused: the hidden activation of every policy in the bank (config/train_config.json:50)")
     p.add_argument("--log-std-head", action="store_true", help="the trainable policies carry the state-dependent log-std head (RLlib's default module for Box actions)")
     p.add_argument("--out", default=None, help="write a JSON summary to this file")
     p.add_argument("--save-dir", default=None, help="--fused: write the trainable policies, the champion snapshots and league.json here (save_league)")
@@ -459,7 +467,7 @@ def main(argv=None):
     bank, league, hist = train_league_fused(env, iters=args.iters, horizon=args.horizon, num_trainable=k, chains=args.chains,
                                          objective=ppo.RLLIB_DEFAULTS if args.objective == "rllib" else None, state_dependent_log_std=args.log_std_head, hidden=tuple(args.fcnet_hiddens),
                                          checkpoint_dir=args.checkpoint_dir, chkpt_freq=args.chkpt_freq, chkpt_keep=args.chkpt_keep, restore=args.restore,
-                                         iters_is_delta=args.iters_is_delta)
+                                         iters_is_delta=args.iters_is_delta, activation=args.fcnet_activation)
     flags = env.flags()
     _, bad = env.nav_conservation()
     tail = hist[2:] if len(hist) >= 4 else (hist[1:] or hist)          # (two warm-up iterations: graph capture, first replays)
@@ -469,7 +477,7 @@ def main(argv=None):
                                       f"{args.episode} steps, horizon {args.horizon or args.episode}, {args.iters} iterations; hand-written bf16 MFMA network kernels, one policy launch per step "
                                       "for every module, 4 epochs per policy per iteration",
                           "markets": args.markets, "agents": args.agents, "trainable": k, "episode": args.episode, "horizon": args.horizon or args.episode, "chains": args.chains,
-                          "objective": args.objective},
+                          "objective": args.objective, "activation": args.fcnet_activation},
                "iterations": hist, "timed_iterations": len(tail),
                "value": sum(h["agent_steps"] for h in tail) / sum(h["rollout_s"] + h["update_s"] for h in tail), "unit": "agent-steps/s",
                "rollout_agent_steps_per_s": sum(h["agent_steps"] for h in tail) / sum(h["rollout_s"] for h in tail),

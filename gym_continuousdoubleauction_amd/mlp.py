@@ -24,6 +24,20 @@ POLICY_ROWS = list(range(N_LOGITS)) + list(LS_ROWS)
 #: history depths the network kernels are compiled for (include/cda_mlp.h CDA_MLP_HIST + CDA_MLP_HIST_VARIANTS): 4 = the reference's n_hist, the unsuffixed entry points
 HIST_VARIANTS = (1, 2, 3, 4, 6, 7, 8)          # (5: the update kernel's gather of 210-float rows spills 14 registers at that width - not built; 9 .. 16: the 128-row forward tile
 #:  no longer fits the LDS - both run the PyTorch loops)
+#: hidden activations (RLlib's fcnet_activation, its torch get_activation_fn) the kernels are compiled for (include/cda_mlp.h CDA_MLP_ACT_VARIANTS): tanh = the
+#: reference's and the unsuffixed entry points, the others <name>[_h<H>]_<act>.  The backward takes act'(z) from the stored bf16 output h = act(z)
+#: (csrc/cda_mlp_dev.inc ActT), so an activation whose derivative h does not determine - SiLU / swish, GELU - is refused.
+ACTIVATIONS = ("tanh", "relu", "elu", "linear")
+
+
+def check_activation(activation):
+    """the canonical name of a hidden activation: one of ACTIVATIONS; None is "linear" (RLlib's get_activation_fn(None)); anything else raises ValueError"""
+    if activation is None:
+        return "linear"
+    if not isinstance(activation, str) or activation not in ACTIVATIONS:
+        raise ValueError(f"fcnet_activation must be one of {ACTIVATIONS} (or None = linear), got {activation!r}; swish / silu and the like are not supported: "
+                         f"the fused backward recovers the derivative from the stored activation h = act(z), and SiLU's derivative is not a function of h")
+    return activation
 
 
 def _lib():
@@ -33,10 +47,11 @@ def _lib():
 
 class Layout:
     """The constants of include/cda_mlp.h at one history depth (observation = n_hist frames of 42 floats) and the entry points compiled for it
-    (`fn("cda_mlp_policy_step")` -> the library's cda_mlp_policy_step[_h<H>])."""
+    and hidden activation (`fn("cda_mlp_policy_step")` -> the library's cda_mlp_policy_step[_h<H>][_<act>])."""
 
-    def __init__(self, n_hist):
+    def __init__(self, n_hist, activation="tanh"):
         h = int(n_hist)
+        self.activation = act = check_activation(activation)
         if h not in HIST_VARIANTS:
             raise ValueError(f"the network kernels are compiled for n_hist in {HIST_VARIANTS} (got {n_hist}); other depths run the PyTorch loops (ppo.train)")
         self.hist, self.OBS = h, 42 * h
@@ -52,7 +67,7 @@ class Layout:
         self.PARAMS = self.OFF_LS + 2
         self.WB_ELEMS = FEAT * self.KX + 2 * HID * HID + 2 * NOUT * HID + 2 * HID * HID + 2 * HID * NOUT
         self.SLAB = FEAT * 32 * self.XT + 2 * HID * HID + NOUT * FEAT
-        self.suffix = "" if h == 4 else f"_h{h}"
+        self.suffix = ("" if h == 4 else f"_h{h}") + ("" if act == "tanh" else f"_{act}")
 
     def fn(self, name):
         return getattr(_lib(), name + self.suffix)
@@ -61,14 +76,15 @@ class Layout:
 _LAYOUTS = {}
 
 
-def layout(n_hist=4):
-    if n_hist not in _LAYOUTS:
-        _LAYOUTS[n_hist] = Layout(n_hist)
-    return _LAYOUTS[n_hist]
+def layout(n_hist=4, activation="tanh"):
+    key = (n_hist, check_activation(activation))
+    if key not in _LAYOUTS:
+        _LAYOUTS[key] = Layout(*key)
+    return _LAYOUTS[key]
 
 
 def layout_of_params(n_params):
-    """the layout whose parameter vector has `n_params` entries"""
+    """the (tanh) layout whose parameter vector has `n_params` entries (the count does not depend on the activation: layout(L.hist, activation) for another)"""
     for h in HIST_VARIANTS:
         if layout(h).PARAMS == int(n_params):
             return layout(h)
@@ -98,7 +114,7 @@ def init_theta(obs_dim=OBS, generator=None, state_dependent_log_std=False, hidde
     (train/policy/policy_handler.py:69-76) - are initialised like every other output row instead of zero (`has_log_std_head(theta)` tells the two apart).
     hidden = (h1, h2), each 1 .. 256: the reference's `fcnet_hiddens` (config/train_config.json:49; 256 x 256 there).  The kernels are compiled for 256-wide layers; a
     NARROWER network is the same parameter vector with the units beyond h1 / h2 of both halves dead - incoming and outgoing weights and biases exactly zero.  A dead
-    unit outputs tanh(0) = 0 exactly, so every gradient that touches it is an exact zero and Adam never moves it (tests/test_hip_mlp.py): the narrow network trains
+    unit outputs act(0) = 0 exactly (every activation of ACTIVATIONS), so every gradient that touches it is an exact zero and Adam never moves it (tests/test_hip_mlp.py): the narrow network trains
     inside the wide kernels at the wide kernels' cost.  `hidden_widths(theta)` reads the widths back."""
     if obs_dim % 42:
         raise ValueError("an observation is n_hist frames of 42 floats")
@@ -172,12 +188,12 @@ def theta_from_actor_critic(model):
     return th
 
 
-def actor_critic_from_theta(theta, dtype=torch.float32):
+def actor_critic_from_theta(theta, dtype=torch.float32, activation="tanh"):
     from .ppo import ActorCritic
     th = theta.detach().float().cpu()
     L = layout_of_params(th.numel())
     sd = has_log_std_head(th)
-    m = ActorCritic(L.OBS, state_dependent_log_std=sd).to(dtype)
+    m = ActorCritic(L.OBS, state_dependent_log_std=sd, activation=activation).to(dtype)
     H = HID
     with torch.no_grad():
         m.l1.weight.copy_(th[L.OFF_W1:L.OFF_B1].view(FEAT, L.OBS)); m.l1.bias.copy_(th[L.OFF_B1:L.OFF_W2])
@@ -196,9 +212,28 @@ def _r(t):
     return t.to(torch.bfloat16).to(t.dtype)
 
 
-def reference_outputs(theta, x, emulate_bf16=True, dtype=torch.float64, keep=False):
+def act_fn(activation):
+    """the hidden activation as a torch function (RLlib's get_activation_fn for the torch framework: nn.ELU() has alpha = 1)"""
+    a = check_activation(activation)
+    return {"tanh": torch.tanh, "relu": torch.relu, "elu": torch.nn.functional.elu, "linear": lambda z: z}[a]
+
+
+def act_grad_from_out(activation, h):
+    """act'(z) as a function of the output h = act(z), as the kernels' backward takes it (csrc/cda_mlp_dev.inc ActT::grad_from_out)"""
+    a = check_activation(activation)
+    if a == "tanh":
+        return 1 - h * h
+    if a == "relu":
+        return (h > 0).to(h.dtype)
+    if a == "elu":
+        return torch.where(h > 0, torch.ones_like(h), h + 1)
+    return torch.ones_like(h)
+
+
+def reference_outputs(theta, x, emulate_bf16=True, dtype=torch.float64, keep=False, activation="tanh"):
     """The network in plain PyTorch on the CPU: out [n, 32].  emulate_bf16: operands (inputs, weights, activations between layers) rounded
-    to bfloat16 as the kernels do, products and sums in `dtype`.  keep: also return (xb, h1, h2) as the kernels store them."""
+    to bfloat16 as the kernels do, products and sums in `dtype`.  keep: also return (xb, h1, h2) as the kernels store them.  activation: of both hidden layers."""
+    act = act_fn(activation)
     th = theta.detach().cpu().to(dtype)
     x = x.detach().cpu().to(dtype)
     L = layout_of_params(th.numel())
@@ -207,17 +242,17 @@ def reference_outputs(theta, x, emulate_bf16=True, dtype=torch.float64, keep=Fal
     W2, b2 = rd(th[L.OFF_W2:L.OFF_B2].view(2, HID, HID)), th[L.OFF_B2:L.OFF_WO]
     Wo, bo = rd(th[L.OFF_WO:L.OFF_BO].view(NOUT, HID)), th[L.OFF_BO:L.OFF_LS]
     xb = rd(x)
-    h1 = rd(torch.tanh(xb @ W1.t() + b1))
-    h2 = torch.cat([rd(torch.tanh(h1[:, :HID] @ W2[0].t() + b2[:HID])), rd(torch.tanh(h1[:, HID:] @ W2[1].t() + b2[HID:]))], dim=1)
+    h1 = rd(act(xb @ W1.t() + b1))
+    h2 = torch.cat([rd(act(h1[:, :HID] @ W2[0].t() + b2[:HID])), rd(act(h1[:, HID:] @ W2[1].t() + b2[HID:]))], dim=1)
     out = torch.zeros(x.shape[0], NOUT, dtype=dtype)
     out[:, POLICY_ROWS] = h2[:, :HID] @ Wo[POLICY_ROWS].t() + bo[POLICY_ROWS]          # (rows 25, 26: the log-std head's offsets; zero rows without the head)
     out[:, N_LOGITS] = h2[:, HID:] @ Wo[N_LOGITS] + bo[N_LOGITS]
     return (out, xb, h1, h2) if keep else out
 
 
-def reference_gradients(theta, xb, h1, h2, d_out, dtype=torch.float64):
+def reference_gradients(theta, xb, h1, h2, d_out, dtype=torch.float64, activation="tanh"):
     """The back-propagation the kernels perform, in plain PyTorch: gradient of theta (dense vector, log_std entries zero) for given
-    d_out [n, 32], with the kernels' roundings (d_out, dz2, dz1 rounded to bfloat16 where they become operands)."""
+    d_out [n, 32], with the kernels' roundings (d_out, dz2, dz1 rounded to bfloat16 where they become operands); act' from the stored h1 / h2."""
     th = theta.detach().cpu().to(dtype)
     L = layout_of_params(th.numel())
     OFF_W1, OFF_B1, OFF_W2, OFF_B2, OFF_WO, OFF_BO, OFF_LS, PARAMS = L.OFF_W1, L.OFF_B1, L.OFF_W2, L.OFF_B2, L.OFF_WO, L.OFF_BO, L.OFF_LS, L.PARAMS      # (this depth's, not the module's)
@@ -225,9 +260,9 @@ def reference_gradients(theta, xb, h1, h2, d_out, dtype=torch.float64):
     d_out = d_out.detach().cpu().to(dtype)
     dob = _r(d_out)
     dh2 = torch.cat([dob[:, POLICY_ROWS] @ Wo[POLICY_ROWS], dob[:, N_LOGITS:N_LOGITS + 1] @ Wo[N_LOGITS:N_LOGITS + 1]], dim=1)
-    dz2 = _r(dh2 * (1 - h2 * h2))
+    dz2 = _r(dh2 * act_grad_from_out(activation, h2))
     dh1 = torch.cat([dz2[:, :HID] @ W2[0], dz2[:, HID:] @ W2[1]], dim=1)
-    dz1 = _r(dh1 * (1 - h1 * h1))
+    dz1 = _r(dh1 * act_grad_from_out(activation, h1))
     g = torch.zeros(PARAMS, dtype=dtype)
     g[OFF_W1:OFF_B1] = (dz1.t() @ xb).reshape(-1); g[OFF_B1:OFF_W2] = dz1.sum(0)
     g[OFF_W2:OFF_B2] = torch.stack([dz2[:, :HID].t() @ h1[:, :HID], dz2[:, HID:].t() @ h1[:, HID:]]).reshape(-1); g[OFF_B2:OFF_WO] = dz2.sum(0)
@@ -261,18 +296,20 @@ class FusedPolicy:
     """theta (f32 master copy), Adam state and the bf16 operand blob on one HIP device.  storage = (theta row, wb row): views into a PolicyBank's
     banks instead of tensors of its own (the league's kernels address a net as a row of the banks)."""
 
-    def __init__(self, device, theta=None, seed=0, storage=None, n_hist=None, state_dependent_log_std=None, hidden=(HID, HID)):
+    def __init__(self, device, theta=None, seed=0, storage=None, n_hist=None, state_dependent_log_std=None, hidden=(HID, HID), activation="tanh"):
         """n_hist: the history depth of the observations (default: the depth `theta` was laid out for, else the reference's 4).
         state_dependent_log_std: RLlib's default head for Box actions - the policy network emits two log-std offsets per row (output rows 25, 26) on top of the free
         log_std vector, and the update trains them (FusedUpdate reads this attribute); default: what `theta` carries (has_log_std_head), False for a fresh network.
-        hidden: the widths of a FRESH network's two hidden layers, <= 256 each (init_theta: the reference's `fcnet_hiddens`)."""
+        hidden: the widths of a FRESH network's two hidden layers, <= 256 each (init_theta: the reference's `fcnet_hiddens`).
+        activation: of both hidden layers of both halves (the reference's `fcnet_activation`: ACTIVATIONS); every kernel this policy launches is that activation's."""
+        self.activation = check_activation(activation)
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("FusedPolicy needs a HIP device; the PyTorch statement of the network is ppo.ActorCritic")
         if theta is None:
             g = torch.Generator().manual_seed(int(seed))
             theta = init_theta(42 * int(n_hist or 4), generator=g, state_dependent_log_std=bool(state_dependent_log_std), hidden=hidden)
-        self.L = L = layout_of_params(theta.numel())
+        self.L = L = layout(layout_of_params(theta.numel()).hist, self.activation)
         self.state_dependent_log_std = has_log_std_head(theta) if state_dependent_log_std is None else bool(state_dependent_log_std)
         if n_hist is not None and int(n_hist) != L.hist:
             raise ValueError(f"theta is laid out for n_hist = {L.hist}, not {n_hist}")
@@ -290,10 +327,10 @@ class FusedPolicy:
 
     @classmethod
     def from_actor_critic(cls, model, device):
-        return cls(device, theta=theta_from_actor_critic(model))
+        return cls(device, theta=theta_from_actor_critic(model), activation=getattr(model, "activation", "tanh"))
 
     def to_actor_critic(self, dtype=torch.float32):
-        return actor_critic_from_theta(self.theta, dtype)
+        return actor_critic_from_theta(self.theta, dtype, activation=self.activation)
 
     @property
     def log_std(self):
@@ -365,10 +402,13 @@ class PolicyBank:
     rollout with no copy), the rows behind them frozen snapshots (champions: league_based_self_play_callback.py:938-1170).  slot_net i32 [N, A] names
     the row that plays each (market, slot), LEAGUE_RANDOM = the uniform random module."""
 
-    def __init__(self, device, n_markets, num_agents, n_trainable, max_frozen=8, seed=0, random_seed=0, n_hist=4, state_dependent_log_std=False, hidden=(HID, HID)):
+    def __init__(self, device, n_markets, num_agents, n_trainable, max_frozen=8, seed=0, random_seed=0, n_hist=4, state_dependent_log_std=False, hidden=(HID, HID),
+                 activation="tanh"):
+        """activation: ONE hidden activation for the whole bank - trainable rows and the champions snapshotted from them (a bank row is launched by one object's kernels)"""
         from ._lib import League
         self.device = torch.device(device)
-        self.L = L = layout(n_hist)
+        self.activation = check_activation(activation)
+        self.L = L = layout(n_hist, self.activation)
         PARAMS, WB_ELEMS = L.PARAMS, L.WB_ELEMS
         self.n_trainable, self.max_frozen, self.n_frozen = int(n_trainable), int(max_frozen), 0
         if not 1 <= self.n_trainable <= num_agents or self.n_trainable + self.max_frozen > LEAGUE_MAX_NETS:
@@ -376,7 +416,8 @@ class PolicyBank:
         n_max = self.n_trainable + self.max_frozen
         self.theta = torch.zeros((n_max, PARAMS), dtype=torch.float32, device=self.device)
         self.wb = torch.zeros((n_max, WB_ELEMS), dtype=torch.bfloat16, device=self.device)
-        self.policies = [FusedPolicy(self.device, seed=seed + 7919 * p, storage=(self.theta[p], self.wb[p]), n_hist=L.hist, state_dependent_log_std=state_dependent_log_std, hidden=hidden)
+        self.policies = [FusedPolicy(self.device, seed=seed + 7919 * p, storage=(self.theta[p], self.wb[p]), n_hist=L.hist, state_dependent_log_std=state_dependent_log_std, hidden=hidden,
+                                     activation=self.activation)
                          for p in range(self.n_trainable)]
         self.slot_net = torch.full((int(n_markets), int(num_agents)), LEAGUE_RANDOM, dtype=torch.int32, device=self.device)
         self.slot_net[:, :self.n_trainable] = torch.arange(self.n_trainable, dtype=torch.int32, device=self.device)
@@ -858,9 +899,13 @@ class FusedUpdate:
 POLICY_FORMAT, POLICY_VERSION = "cda-mlp-policy", 1
 
 
-def policy_record(policy, row=None):
-    """the dict a policy file holds: {"format", "version", "theta" (f32, CPU), "n_hist", "hidden", "state_dependent_log_std"}.  policy: a FusedPolicy, a PolicyBank
-    with its `row`, or a parameter vector (CPU or device tensor)"""
+def policy_record(policy, row=None, activation=None):
+    """the dict a policy file holds: {"format", "version", "theta" (f32, CPU), "n_hist", "hidden", "state_dependent_log_std"} and, for a network whose hidden activation
+    is not tanh, "activation" (a file without the key is a tanh network: files of tanh networks are the same as before the key existed).  policy: a FusedPolicy, a
+    PolicyBank with its `row`, or a parameter vector (CPU or device tensor; `activation` then names its activation, default tanh)"""
+    act = check_activation(activation if activation is not None else getattr(policy, "activation", "tanh"))
+    if activation is not None and isinstance(policy, (FusedPolicy, PolicyBank)) and act != policy.activation:
+        raise ValueError(f"activation={activation!r}, but the policy's is {policy.activation!r}")
     if isinstance(policy, PolicyBank):
         if row is None:
             raise ValueError("a PolicyBank needs the bank row to save (row=...)")
@@ -873,8 +918,21 @@ def policy_record(policy, row=None):
         theta = policy
     theta = theta.detach().to("cpu", torch.float32).contiguous().clone()
     L = layout_of_params(theta.numel())
-    return {"format": POLICY_FORMAT, "version": POLICY_VERSION, "theta": theta, "n_hist": L.hist, "hidden": list(hidden_widths(theta)),
-            "state_dependent_log_std": has_log_std_head(theta)}
+    rec = {"format": POLICY_FORMAT, "version": POLICY_VERSION, "theta": theta, "n_hist": L.hist, "hidden": list(hidden_widths(theta)),
+           "state_dependent_log_std": has_log_std_head(theta)}
+    if act != "tanh":
+        rec["activation"] = act
+    return rec
+
+
+def record_activation(rec):
+    """the hidden activation a policy file's dict names: "tanh" where the key is missing; an unknown name raises ValueError"""
+    if "activation" not in rec:
+        return "tanh"
+    a = rec["activation"]
+    if not isinstance(a, str):
+        raise ValueError(f"policy file says activation = {a!r}: one of {ACTIVATIONS} (a tanh network's file carries no key)")
+    return check_activation(a)
 
 
 def save_policy(path, policy, row=None):
@@ -898,15 +956,19 @@ def check_policy_record(rec):
         raise ValueError(f"policy file says hidden = {rec.get('hidden')!r}, its parameter vector has {list(hidden_widths(theta))}")
     if bool(rec.get("state_dependent_log_std")) != has_log_std_head(theta) or not isinstance(rec.get("state_dependent_log_std"), bool):
         raise ValueError(f"policy file says state_dependent_log_std = {rec.get('state_dependent_log_std')!r}, its parameter vector says {has_log_std_head(theta)}")
+    record_activation(rec)
     return theta
 
 
-def read_policy(path):
-    """a policy file's parameter vector (f32, CPU), validated (check_policy_record); no device needed"""
-    return check_policy_record(torch.load(path, map_location="cpu", weights_only=True))
+def read_policy(path, with_activation=False):
+    """a policy file's parameter vector (f32, CPU), validated (check_policy_record); no device needed.  with_activation: (theta, the hidden activation), "tanh" for a
+    file without the key"""
+    rec = torch.load(path, map_location="cpu", weights_only=True)
+    theta = check_policy_record(rec)
+    return (theta, record_activation(rec)) if with_activation else theta
 
 
 def load_policy(path, device):
-    """a policy file -> a FusedPolicy on `device` (theta bit-equal to the saved vector, wb re-packed from it)"""
-    theta = read_policy(path)
-    return FusedPolicy(device, theta=theta, state_dependent_log_std=has_log_std_head(theta))
+    """a policy file -> a FusedPolicy on `device` (theta bit-equal to the saved vector, wb re-packed from it; the file's hidden activation)"""
+    theta, act = read_policy(path, with_activation=True)
+    return FusedPolicy(device, theta=theta, state_dependent_log_std=has_log_std_head(theta), activation=act)

@@ -46,6 +46,9 @@ extern "C" {
 #define CDA_MLP_HIST 4
 #endif
 #define CDA_MLP_HIST_VARIANTS "1 2 3 6 7 8"
+/* Hidden activations (RLlib's fcnet_activation) the entry points are compiled for besides tanh, the default and the unsuffixed names: every depth above and 4 again
+ * under <name>[_h<H>]_<act> (cda_mlp_forward_relu, cda_mlp_forward_backward_h6_elu, ...: same signatures; csrc/cda_mlp_variant.h).  Python: mlp.layout(n_hist, activation). */
+#define CDA_MLP_ACT_VARIANTS "relu elu linear"
 #define CDA_MLP_OBS       (42 * CDA_MLP_HIST)                       /* 168 */
 #define CDA_MLP_KX        ((CDA_MLP_OBS + 15) / 16 * 16)             /* 176: the observation padded to MFMA k-steps of 16 */
 #define CDA_MLP_XTILES    ((CDA_MLP_KX + 31) / 32)                   /* 6: ... and to feature tiles of 32 in the packed layout */
