@@ -42,10 +42,17 @@ MLP_HIST_VARIANTS = (1, 2, 3, 6, 7, 8)
 MLP_ACT_VARIANTS = ("relu", "elu", "linear")
 
 
+# ... and every (depth, activation) pair, the unsuffixed one included, once more as the shared-trunk network (RLlib's vf_share_layers): <name>[_h<H>][_<act>]_vfs
+# (include/cda_mlp.h CDA_MLP_VFS_VARIANTS)
+MLP_VFS_SUFFIX = "_vfs"
+
+
 def mlp_variant_suffixes():
-    """the suffixes of every compiled variant of the network entry points besides the unsuffixed (n_hist 4, tanh) ones: _h<H>, _<act>, _h<H>_<act>"""
+    """the suffixes of every compiled variant of the network entry points besides the unsuffixed (n_hist 4, tanh) ones: _h<H>, _<act>, _h<H>_<act>, and each of
+    those and the empty one followed by _vfs"""
     hs = [""] + [f"_h{h}" for h in MLP_HIST_VARIANTS]
-    return [f"_h{h}" for h in MLP_HIST_VARIANTS] + [h + "_" + a for h in hs for a in MLP_ACT_VARIANTS]
+    base = [f"_h{h}" for h in MLP_HIST_VARIANTS] + [h + "_" + a for h in hs for a in MLP_ACT_VARIANTS]
+    return base + [b + MLP_VFS_SUFFIX for b in [""] + base]
 
 
 class RolloutBufs(C.Structure):

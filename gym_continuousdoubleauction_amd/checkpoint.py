@@ -135,6 +135,12 @@ def with_activation(args, activation):
     return dict(args, activation=act) if act != "tanh" else dict(args)
 
 
+def with_vf_share_layers(args, vf_share_layers):
+    """the loop arguments of a run with a shared-trunk network (RLlib's vf_share_layers): the "vf_share_layers" key is added only when it is True, so the arguments of a
+    run with separate networks are exactly what they were before the key existed, and a checkpoint of either kind refuses a run of the other (check_args)"""
+    return dict(args, vf_share_layers=True) if vf_share_layers else dict(args)
+
+
 def new_run_id():
     return uuid.uuid4().hex
 

@@ -207,7 +207,11 @@ __global__ __launch_bounds__(256) void k_mlp_fwd(FwdArgs A) {
     // A league launch (MODE_LEAGUE; the bootstrap values of its trainable nets: MODE_VALUE with n_train > 0): blockIdx.y names the (net, half) job
     // and the net's parameters are its row of the banks.  Uniform per workgroup: scalar registers.
     int net = 0, job_half = 0;
+#if CDA_MLP_VFS
+    if (LEAGUE) net = (int)blockIdx.y;                                          // (a shared trunk: one job per net, trainable or frozen - the trunk owns every column)
+#else
     if (LEAGUE) { const int y = (int)blockIdx.y; net = y < 2 * A.n_train ? y >> 1 : A.n_train + (y - 2 * A.n_train); job_half = y < 2 * A.n_train ? (y & 1) : 0; }
+#endif
     if (MODE == MODE_VALUE && A.n_train > 0) net = (int)blockIdx.y;
     const float* theta = A.theta + (size_t)net * CDA_MLP_PARAMS;
     const __bf16* wb = A.wb + (size_t)net * CDA_MLP_WB_ELEMS;
@@ -236,8 +240,15 @@ __global__ __launch_bounds__(256) void k_mlp_fwd(FwdArgs A) {
     WRing<2, KX / 16, PF, true> R1; WRing<2, HID / 16, PF, true> R2; WRing<1, HID / 16, PF> RO;
     // The two halves are independent networks: a rollout launch gives each its own workgroup (half the serial chain, half the weight bytes
     // through one CU's L1); the update's launches run both in one workgroup (the observation tile is staged once).
+#if CDA_MLP_VFS
+    // a shared trunk: the value column is the trunk's (Wo row 24 is packed into half 0) - every launch but the training forward (which keeps the dead half's h
+    // images defined for the 4-wave backward) runs half 0 alone: the rollout's and the bootstrap value's one workgroup per row tile, MODE_OUT
+    (void)job_half;
+    const int half_begin = 0, half_end = MODE == MODE_TRAIN ? 2 : 1;
+#else
     const int half_begin = LEAGUE ? job_half : (A.split_halves == 1 ? (int)blockIdx.y : (A.split_halves == 2 ? 1 : 0));
     const int half_end = (LEAGUE || A.split_halves) ? half_begin + 1 : 2;
+#endif
     float* const value_out = A.value ? A.value + (size_t)net * A.value_stride : nullptr;
     R1.prime(W1b + (size_t)(256 * half_begin + 64 * w) * KX, KX, lane);         // (layer 1's weights fly while the observation tile is staged)
     if (MODE == MODE_TRAIN) load_x_bf16<M>(A.x_rm, row0, rows_end, xs); else load_x_f32<M>(A.obs, row0, rows_end, xs);
@@ -303,13 +314,24 @@ __global__ __launch_bounds__(256) void k_mlp_fwd(FwdArgs A) {
     }
     // outputs: column j of rows rowmap(r, h) of row tile w.  A workgroup that ran one half only owns that half's columns (policy: 0 .. 23 and the
     // zero padding; value: 24)
+#if CDA_MLP_VFS
+    const bool own_col = true;                                                  // (the trunk's workgroup owns every column, the value's 24 included)
+#else
     const bool own_col = !A.split_halves || (half_begin == 0 ? j != N_LOGITS : j == N_LOGITS);
+#endif
     if (w < MT) {
         #pragma unroll
         for (int r = 0; r < 16; r++) {
             const int row = 32 * w + rowmap(r, h);
             const float o = acc3[0][0][r] + bo;
+#if CDA_MLP_VFS
+            if (ACTS) {
+                outs[row * OUTS_LD + j] = o;
+                if (j == N_LOGITS && value_out && (!LEAGUE || net < A.n_train) && row0 + row < rows_end) value_out[row0 + row] = o;
+            }
+#else
             if (ACTS) { if (half_begin == 0) outs[row * OUTS_LD + j] = o; else if (j == N_LOGITS && row0 + row < rows_end) value_out[row0 + row] = o; }
+#endif
             else if (MODE == MODE_VALUE) { if (j == N_LOGITS && row0 + row < rows_end) value_out[row0 + row] = o; }
             else if (own_col && (MODE == MODE_TRAIN || row0 + row < rows_end)) A.out[(row0 + row) * NOUT + j] = o;
         }
@@ -462,7 +484,11 @@ __global__ __launch_bounds__(512) void k_mlp_fwd8(FwdArgs A) {
     f32x16 acc3[1][1]; acc3[0][0] = zero16();                                   // MH: wave w of the half owns row tile w (waves >= MT multiply a tile nobody reads)
     layer_mma(act + (w < MT ? 32 * w : 0) * ACT_LD, ACT_LD, RO, lane, acc3);
     MLP_MARK8(11);
+#if CDA_MLP_VFS
+    const bool own_col = half == 0;                                             // a shared trunk: half 0 owns every column (Wo row 24 reads it); half 1 is dead
+#else
     const bool own_col = half == 0 ? j != N_LOGITS : j == N_LOGITS;             // policy: columns 0 .. 23 and the zero padding; value: column 24
+#endif
     if (w < MT && own_col) {
         #pragma unroll
         for (int r = 0; r < 16; r++) A.out[(row0 + 32 * w + rowmap(r, h)) * NOUT + j] = acc3[0][0][r] + bo;
@@ -798,7 +824,12 @@ __global__ __launch_bounds__(256, 2) void k_mlp_fb(FbArgs A) {     // (two workg
     // Workgroup -> (tile, half), XCD-aware: workgroup ids go round the eight XCDs, so ids 8 apart share an L2.  The two halves of a tile gather
     // the same rows and records: id = 16 g + 8 half + k is tile 8 g + k - its sibling is dispatched 8 ids later, on the same XCD, and finds them
     // in that L2 (half, tile as the grid's y, x: siblings a thousand ids apart, every row fetched twice - 132 MB instead of 82 per launch).
+#if CDA_MLP_VFS
+    // A shared trunk: ONE workgroup per tile (the value half is dead: no sibling to meet in L2) - consecutive ids are consecutive tiles, dealt round the XCDs
+    const int wg = (int)blockIdx.x, half = 0, tile_id = wg;
+#else
     const int wg = (int)blockIdx.x, half = (wg >> 3) & 1, tile_id = 8 * (wg >> 4) + (wg & 7);
+#endif
     const int w = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     if ((long long)tile_id * M >= A.n_rows) return;                             // (the last group of eight may be short; whole workgroups leave)
     __bf16* act = reinterpret_cast<__bf16*>(smem + FB_XS_BYTES);                // [M][ACT_LD]: h1, h2, then dz2
@@ -845,7 +876,7 @@ __global__ __launch_bounds__(256, 2) void k_mlp_fb(FbArgs A) {     // (two workg
     }
     __syncthreads();                                                            // the observation tile is in LDS
     MLP_MARKH(1);
-    if (half == 1) {                                                            // value half: the packed image of x for the weight gradients
+    if (half == (CDA_MLP_VFS ? 0 : 1)) {                                        // value half (shared trunk: the one workgroup): the packed image of x for the weight gradients
         #pragma unroll
         for (int u = 0; u < MT * XT * 2 / 4; u++) {                             // 24 pieces (row tile, feature tile, k-step), 6 per wave
             const int pc = w + 4 * u, it = pc / (XT * 2), rem = pc - it * (XT * 2), ft = rem >> 1, ks = rem & 1;
@@ -901,7 +932,11 @@ __global__ __launch_bounds__(256, 2) void k_mlp_fb(FbArgs A) {     // (two workg
     MLP_MARKH(8);
     __syncthreads();
     MLP_MARKH(9);
+#if CDA_MLP_VFS
+    const bool own_col = true;                                                  // shared trunk: every column, the value's 24 included
+#else
     const bool own_col = half == 0 ? j != N_LOGITS : j == N_LOGITS;             // policy: columns 0 .. 23 and the zero padding; value: column 24
+#endif
     {   // MH: wave w owns row tile w (waves >= MT multiply a tile nobody reads); the outputs go to LDS (the observation tile is dead)
         f32x16 acc3[1][1]; acc3[0][0] = zero16();
         layer_mma(act + (w < MT ? 32 * w : 0) * ACT_LD, ACT_LD, RO, lane, acc3);
@@ -973,6 +1008,10 @@ __global__ __launch_bounds__(256, 2) void k_mlp_fb(FbArgs A) {     // (two workg
         // the row's two log-stds: the free vector + outputs 25, 26 (the state-dependent head's offsets; zero in a network without the head) - read before the
         // tile's columns 24 .. 31 are overwritten with their gradients below (same wave, program order)
         const float lo0 = orow[N_LOGITS + 1], lo1 = orow[N_LOGITS + 2];
+#if CDA_MLP_VFS
+        const float val = orow[N_LOGITS];                                       // the trunk's value column: its loss runs on the same quad (below)
+        float vl = 0.0f, dval = 0.0f;
+#endif
         const float ls0 = A.theta[CDA_MLP_OFF_LS] + lo0, ls1 = A.theta[CDA_MLP_OFF_LS + 1] + lo1;
         const float is0 = __expf(-ls0), is1 = __expf(-ls1);
         const float HALF_LOG_2PI = 0.918938533204672742f;
@@ -999,6 +1038,12 @@ __global__ __launch_bounds__(256, 2) void k_mlp_fb(FbArgs A) {     // (two workg
                 gz0 = g * z0 * is0; gz1 = g * z1 * is1;
                 dls0 += g * (z0 * z0 - 1.0f) - es;
                 dls1 += g * (z1 * z1 - 1.0f) - es;
+#if CDA_MLP_VFS
+                const float dv = val - w1.w, sqe = dv * dv;                     // the value loss of this agent (the value workgroup's rule, see below)
+                const bool clamped = A.vf_clip > 0.0f && sqe > A.vf_clip;
+                vl += clamped ? A.vf_clip : sqe;
+                dval += clamped ? 0.0f : 2.0f * A.vf_coef * dv * invB;
+#endif
             }
             // agent Q of this group, broadcast: its three actions as slot numbers of THIS lane (head ranges are disjoint: at most one of the
             // three can name a slot; an absent agent adds g = 0)
@@ -1048,14 +1093,23 @@ __global__ __launch_bounds__(256, 2) void k_mlp_fb(FbArgs A) {     // (two workg
             if (sq == 1) e0 = D1;
             dls0 = dls1 = 0.0f;
         }
+#if CDA_MLP_VFS
+        { const float D = quad_sum(dval); if (sq == 0) e0 = D; }                // column 24: d loss / d value of the row (its agents summed over the quad)
+#endif
         if (A.out && live) {
             #pragma unroll
             for (int k = 0; k < 6; k++) A.out[(row0 + row) * NOUT + i0 + k] = l[k];
             if (sq != 0) A.out[(row0 + row) * NOUT + N_LOGITS + 2 * sq] = sq == 1 ? lo1 : 0.0f;
+#if CDA_MLP_VFS
+            else A.out[(row0 + row) * NOUT + N_LOGITS] = val;
+#endif
             A.out[(row0 + row) * NOUT + N_LOGITS + 2 * sq + 1] = sq == 0 ? lo0 : 0.0f;
         }
         if (!live) {
             pg = en = dls0 = dls1 = klsum = e0 = e1 = 0.0f;
+#if CDA_MLP_VFS
+            vl = 0.0f;
+#endif
             #pragma unroll
             for (int k = 0; k < 6; k++) d[k] = 0.0f;
         }
@@ -1072,7 +1126,11 @@ __global__ __launch_bounds__(256, 2) void k_mlp_fb(FbArgs A) {     // (two workg
         if (A.d_out && live) {
             #pragma unroll
             for (int k = 0; k < 6; k++) A.d_out[(row0 + row) * NOUT + i0 + k] = d[k];
+#if CDA_MLP_VFS
+            A.d_out[(row0 + row) * NOUT + N_LOGITS + 2 * sq] = e0;
+#else
             if (sq != 0) A.d_out[(row0 + row) * NOUT + N_LOGITS + 2 * sq] = e0;
+#endif
             A.d_out[(row0 + row) * NOUT + N_LOGITS + 2 * sq + 1] = e1;
         }
         float v4[5] = {pg, en, dls0, dls1, klsum};
@@ -1088,6 +1146,11 @@ __global__ __launch_bounds__(256, 2) void k_mlp_fb(FbArgs A) {     // (two workg
             atomicAdd(&slot[0], (double)v4[0]); atomicAdd(&slot[2], (double)v4[1]); atomicAdd(&slot[3], (double)v4[2]); atomicAdd(&slot[4], (double)v4[3]);
             if (A.dist_old) atomicAdd(&slot[5], (double)v4[4]);
         }
+#if CDA_MLP_VFS
+        #pragma unroll
+        for (int o = 32; o > 0; o >>= 1) vl += __shfl_down(vl, o, 64);
+        if (lane == 0) atomicAdd(&slot[1], (double)vl);
+#endif
     } else if (w == 0) {                                                        // the value loss: a lane per row
         const int row = lane;
         const bool live = row0 + row < rows_end;
@@ -1271,7 +1334,9 @@ __device__ __forceinline__ void wgrad_store(float* __restrict__ dst, int ld, int
             }
         }
 }
-constexpr int WG_TJ = XT <= 2 ? 1 : (XT <= 4 ? 2 : 3), WG_XG = (XT + 2 * WG_TJ - 1) / (2 * WG_TJ), WG_JOBS = 3 + 2 * WG_XG;     // x tiles per wave, groups per half, jobs (n_hist 4: 3, 1, 5)
+constexpr int WG_TJ = XT <= 2 ? 1 : (XT <= 4 ? 2 : 3), WG_XG = (XT + 2 * WG_TJ - 1) / (2 * WG_TJ);     // x tiles per wave, groups per half (n_hist 4: 3, 1)
+// network halves with weight gradients: a shared trunk's value half is dead (no dW2 block 1, no value panels of dW1; dWo reads the trunk's h2 only)
+constexpr int WG_HALVES = CDA_MLP_VFS ? 1 : 2, WG_JOBS = WG_HALVES * (1 + WG_XG) + 1;                  // jobs (n_hist 4: 5; shared trunk 3)
 struct WgradArgs { const bf16x8* x_pk; const bf16x8* h1p; const bf16x8* h2p; const bf16x8* dz1p; const bf16x8* dz2p; const bf16x8* doutp;
                    long long n_rt; int n_chunks; float* slab; int first_job; };
 __global__ __launch_bounds__(256) void k_mlp_wgrad(WgradArgs A) {
@@ -1279,7 +1344,7 @@ __global__ __launch_bounds__(256) void k_mlp_wgrad(WgradArgs A) {
     const int job = (int)blockIdx.y + A.first_job, chunk = (int)blockIdx.x;
     const long long rt0 = A.n_rt * chunk / A.n_chunks, rt1 = A.n_rt * (chunk + 1) / A.n_chunks;
     float* slab = A.slab + (size_t)chunk * CDA_MLP_SLAB;
-    if (job < 2) {
+    if (job < WG_HALVES) {
         f32x16 acc[4][4];
         #pragma unroll
         for (int a = 0; a < 4; a++)
@@ -1287,9 +1352,9 @@ __global__ __launch_bounds__(256) void k_mlp_wgrad(WgradArgs A) {
             for (int b = 0; b < 4; b++) acc[a][b] = zero16();
         wgrad_wave<4, 4>(A.dz2p, 16, 8 * job + 4 * wi, A.h1p, 16, 8 * job + 4 * wj, rt0, rt1, lane, acc);
         wgrad_store<4, 4, true, true>(slab + CDA_MLP_SLAB_W2 + (size_t)job * HID * HID, HID, 4 * wi, 4 * wj, lane, acc);
-    } else if (job < 2 + 2 * WG_XG) {
+    } else if (job < WG_HALVES + WG_HALVES * WG_XG) {
         // dW1: per network half, the x panel's XT tiles in WG_XG groups of 2 WG_TJ (a wave: 128 features x WG_TJ tiles; n_hist 4: one group, 128 x 96 per wave)
-        const int b = (job - 2) / WG_XG, xg = (job - 2) - b * WG_XG, x0 = 2 * WG_TJ * xg + WG_TJ * wj;
+        const int b = (job - WG_HALVES) / WG_XG, xg = (job - WG_HALVES) - b * WG_XG, x0 = 2 * WG_TJ * xg + WG_TJ * wj;
         f32x16 acc[4][WG_TJ];
         #pragma unroll
         for (int a = 0; a < 4; a++)
@@ -1298,11 +1363,12 @@ __global__ __launch_bounds__(256) void k_mlp_wgrad(WgradArgs A) {
         wgrad_wave<4, WG_TJ>(A.dz1p, 16, 8 * b + 4 * wi, A.x_pk, XT, x0, rt0, rt1, lane, acc);
         wgrad_store<4, WG_TJ, true, false>(slab + CDA_MLP_SLAB_W1 + (size_t)(256 * b) * (32 * XT), 32 * XT, 4 * wi, x0, lane, acc, XT);
     } else {
-        f32x16 acc[1][4];
+        constexpr int TJ = 2 * WG_HALVES;                                        // h2 tiles per wave: 4 of 16 (shared trunk: 2 of the trunk's 8)
+        f32x16 acc[1][TJ];
         #pragma unroll
-        for (int c = 0; c < 4; c++) acc[0][c] = zero16();
-        wgrad_wave<1, 4>(A.doutp, 1, 0, A.h2p, 16, 4 * w, rt0, rt1, lane, acc);
-        wgrad_store<1, 4, false, true>(slab + CDA_MLP_SLAB_WO, CDA_MLP_FEAT, 0, 4 * w, lane, acc);
+        for (int c = 0; c < TJ; c++) acc[0][c] = zero16();
+        wgrad_wave<1, TJ>(A.doutp, 1, 0, A.h2p, 16, TJ * w, rt0, rt1, lane, acc);
+        wgrad_store<1, TJ, false, true>(slab + CDA_MLP_SLAB_WO, CDA_MLP_FEAT, 0, TJ * w, lane, acc);
     }
 }
 
@@ -1318,9 +1384,18 @@ __device__ __forceinline__ int param_of_dense(int d) {
     if (d < CDA_MLP_SLAB_WO) return CDA_MLP_OFF_W2 + (d - CDA_MLP_SLAB_W2);
     const int q = d - CDA_MLP_SLAB_WO, o = q / CDA_MLP_FEAT, c = q - o * CDA_MLP_FEAT;
     if (o < N_LOGITS || o == N_LOGITS + 1 || o == N_LOGITS + 2) return c < HID ? CDA_MLP_OFF_WO + o * HID + c : -1;     // (25, 26: the log-std head's rows - zero gradient unless it trains)
+#if CDA_MLP_VFS
+    if (o == N_LOGITS) return c < HID ? CDA_MLP_OFF_WO + N_LOGITS * HID + c : -1;                   // (a shared trunk: the value head reads half 0)
+#else
     if (o == N_LOGITS) return c >= HID ? CDA_MLP_OFF_WO + N_LOGITS * HID + (c - HID) : -1;
+#endif
     return -1;
 }
+#if CDA_MLP_VFS
+// a shared trunk's value half (W1 rows 256 .. 511, W2 block 1 in the dense slab; b1 / b2 256 .. 511 in the bias slab): nobody writes its partial sums, its gradient is 0
+__device__ __forceinline__ bool dead_dense(int d) { return (d >= 256 * 32 * XT && d < CDA_MLP_SLAB_W2) || (d >= CDA_MLP_SLAB_W2 + HID * HID && d < CDA_MLP_SLAB_WO); }
+__device__ __forceinline__ bool dead_bias(int e) { return e < 2 * CDA_MLP_FEAT && (e & (CDA_MLP_FEAT - 1)) >= HID; }
+#endif
 struct LossFinish { double* sums5; long long samples; float vf_coef, ent_coef, kl_coef; float* out6; };      // out6: f32[8] (CDA_LOSS_OUT_*)
 __global__ __launch_bounds__(256) void k_grad_reduce(const float* __restrict__ slab, int n_chunks, const float* __restrict__ bslab, int n_tiles,
                                                      LossFinish LF, float* __restrict__ grad, double* __restrict__ norm2, float* __restrict__ step) {
@@ -1331,6 +1406,9 @@ __global__ __launch_bounds__(256) void k_grad_reduce(const float* __restrict__ s
         const float4* src = reinterpret_cast<const float4*>(slab + d);
         float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0, s2 = s0, s3 = s0;
         int c = 0;
+#if CDA_MLP_VFS
+        if (dead_dense(d)) n_chunks = 0;                                          // (no partial sums to read: the sum is 0; a group of four never straddles the bounds)
+#endif
         for (; c + 8 <= n_chunks; c += 8) {
             float4 v[8];
             #pragma unroll
@@ -1360,6 +1438,9 @@ __global__ __launch_bounds__(256) void k_grad_reduce(const float* __restrict__ s
         // handful of threads was latency bound: 60 us)
         const int e = ((int)blockIdx.x - RED_DENSE_BLOCKS) * 16 + ((int)threadIdx.x & 15), part = (int)threadIdx.x >> 4;
         float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, s3 = 0.0f;
+#if CDA_MLP_VFS
+        if (dead_bias(e)) n_tiles = 0;
+#endif
         if (e < CDA_MLP_BSLAB) {
             const float* src = bslab + e;
             int t = part;
@@ -1432,7 +1513,7 @@ __device__ __forceinline__ void pack_one(int p, float v, __bf16* __restrict__ wb
     } else if (p >= CDA_MLP_OFF_WO && p < CDA_MLP_OFF_BO) {                      // Wo[o][i] -> Wop (one tile of 32 outputs per half) and WoTp (rows = features, k = outputs)
         const int q = p - CDA_MLP_OFF_WO, o = q / HID, i = q - o * HID;
         if (o <= N_LOGITS + 2) {                                                 // (25, 26: the log-std head's rows of the policy half)
-            const int hf = o == N_LOGITS ? 1 : 0;
+            const int hf = o == N_LOGITS && !CDA_MLP_VFS ? 1 : 0;                 // (shared trunk: the value head reads half 0; half 1 of Wop / WoTp stays zero)
             wb[CDA_MLP_WB_WO + (size_t)hf * NOUT * HID + op_index(HID / 16, 0, i, o)] = b;
             wb[CDA_MLP_WB_WOT + ((size_t)hf * 4 + (i >> 6)) * 64 * NOUT + op_index(NOUT / 16, i & 1, o, (i & 63) >> 1)] = b;
         }
@@ -1830,7 +1911,7 @@ int allow_lds(K kern, size_t bytes) {
 template <int MODE>
 int launch_fwd(const FwdArgs& A, int mt, hipStream_t st, unsigned grid_y = 0) {
     const size_t lds = fwd_lds(mt, MODE);
-    const dim3 grid((unsigned)((A.n_rows + 32 * mt - 1) / (32 * mt)), grid_y ? grid_y : (A.split_halves == 1 ? 2u : 1u));
+    const dim3 grid((unsigned)((A.n_rows + 32 * mt - 1) / (32 * mt)), grid_y ? grid_y : (A.split_halves == 1 && !CDA_MLP_VFS ? 2u : 1u));     // (shared trunk: one workgroup per tile)
     int rc = CDA_OK;
     if (mt == 4) { rc = allow_lds(k_mlp_fwd<4, MODE>, lds); if (!rc) hipLaunchKernelGGL((k_mlp_fwd<4, MODE>), grid, dim3(256), lds, st, A); }
     else if (mt == 2) { rc = allow_lds(k_mlp_fwd<2, MODE>, lds); if (!rc) hipLaunchKernelGGL((k_mlp_fwd<2, MODE>), grid, dim3(256), lds, st, A); }
@@ -2005,7 +2086,7 @@ extern "C" int cda_mlp_forward_backward(const void* wb, const float* theta, cons
     if (clear && hipMemsetAsync(sums5, 0, (size_t)CDA_MLP_LOSS_SLOTS * 8 * sizeof(double), st) != hipSuccess) return CDA_ERR_HIP;
     int rc = allow_lds(k_mlp_fb, lds); if (rc) return rc;
     const long long tiles = (n_rows + 63) / 64;
-    hipLaunchKernelGGL(k_mlp_fb, dim3((unsigned)(16 * ((tiles + 7) / 8))), dim3(256), lds, st, A);
+    hipLaunchKernelGGL(k_mlp_fb, dim3((unsigned)(CDA_MLP_VFS ? tiles : 16 * ((tiles + 7) / 8))), dim3(256), lds, st, A);     // (shared trunk: one workgroup per tile)
     if (finish) hipLaunchKernelGGL(k_ppo_finish_slots, dim3(1), dim3(64), 0, st, (const double*)sums5, A.norm_rows * agents_per_row, vf_coef, ent_coef, A.kl_coef, out6);
     return hipGetLastError() == hipSuccess ? CDA_OK : CDA_ERR_HIP;
 }
@@ -2144,7 +2225,7 @@ static int league_step(const cda_league* L, const float* obs, int32_t first_mark
     A.a_cont = a_cont; A.logp = logp; A.value = value; A.rec = rec; A.dist = dist;
     A.n_train = L->n_trainable; A.slot_net = L->slot_net; A.value_stride = value_stride; A.dist_stride = dist_stride; A.random_seed = L->random_seed;
     A.split_halves = 1;
-    return launch_fwd<MODE>(A, rollout_mt(), (hipStream_t)stream, (unsigned)(L->n_trainable + L->n_nets));     // 2 jobs per trainable net, 1 per frozen one
+    return launch_fwd<MODE>(A, rollout_mt(), (hipStream_t)stream, (unsigned)((CDA_MLP_VFS ? 0 : L->n_trainable) + L->n_nets));     // 2 jobs per trainable net, 1 per frozen one (shared trunk: 1 per net)
 }
 extern "C" int cda_mlp_league_step(const cda_league* L, const float* obs, int32_t first_market, int32_t n_markets, int32_t num_agents,
                                    uint64_t seed, const int64_t* counter_dev, int64_t draw,
@@ -2232,7 +2313,8 @@ static int rollout_chain(cda_env* env, const cda_league* L, const void* wb, cons
         const int want = ev ? atoi(ev) : 1;
         // (the env's history depth is this build's: checked above.  CDA_POLICY_STEP=2: wherever supported, also where the batched policy kernel is the faster one)
         // (k_policy_step is compiled with the tanh network only: an object of another activation (CDA_MLP_ACT) always takes the two launches)
-        one_launch = CDA_MLP_ACT == 0 && !greedy && want != 0 && !L && !B->info_steps && (want == 2 ? cda_policy_step_supported(env) : cda_policy_step_advised(env));
+        // (... and a separate value network: a shared-trunk object (CDA_MLP_VFS) takes the two launches as well)
+        one_launch = CDA_MLP_ACT == 0 && !CDA_MLP_VFS && !greedy && want != 0 && !L && !B->info_steps && (want == 2 ? cda_policy_step_supported(env) : cda_policy_step_advised(env));
     }
     for (int32_t t = 0; t < n_steps; t++) {
         const size_t o = (size_t)t * NA;
@@ -2261,8 +2343,9 @@ static int rollout_chain(cda_env* env, const cda_league* L, const void* wb, cons
         if (L) {
             P.n_train = n_train; P.slot_net = L->slot_net; P.random_seed = L->random_seed;
             P.value_stride = (long long)(n_steps + 1) * N; P.dist_stride = (long long)n_steps * N * CDA_MLP_DIST_LD;
-            rc = greedy ? launch_fwd<MODE_LEAGUE_GREEDY>(P, rollout_mt(), st, (unsigned)(L->n_trainable + L->n_nets))
-                        : launch_fwd<MODE_LEAGUE>(P, rollout_mt(), st, (unsigned)(L->n_trainable + L->n_nets));
+            const unsigned jobs = (unsigned)((CDA_MLP_VFS ? 0 : L->n_trainable) + L->n_nets);     // (shared trunk: one job per net)
+            rc = greedy ? launch_fwd<MODE_LEAGUE_GREEDY>(P, rollout_mt(), st, jobs)
+                        : launch_fwd<MODE_LEAGUE>(P, rollout_mt(), st, jobs);
         } else rc = greedy ? launch_fwd<MODE_GREEDY>(P, rollout_mt(), st) : launch_fwd<MODE_SAMPLE>(P, rollout_mt(), st);
         if (rc) return rc;
         rc = cda_step_range_capture(env, first_market, n_markets, B->category + o, B->size_mean + o, B->size_sigma + o, B->price + o, B->price_offset + o, NULL,

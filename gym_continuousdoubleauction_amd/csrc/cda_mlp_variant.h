@@ -6,7 +6,9 @@
  * renames every one of them to <name>[_h<H>][_<act>] (cda_mlp_forward_relu, cda_mlp_forward_h6_elu) BEFORE the header is read, so declarations and definitions
  * agree and the objects link into one library (__graft_entry__.build_hip compiles CDA_MLP_HIST_VARIANTS x CDA_MLP_ACT_VARIANTS).  Entry points that depend on
  * neither (GAE, episode returns, league assignment) are renamed too: a few duplicate kilobytes instead of a second source file.  Generated list: keep in step with
- * include/cda_mlp.h (tests/test_capi_load.py checks it). */
+ * include/cda_mlp.h (tests/test_capi_load.py checks it).
+ * -DCDA_MLP_VFS=1 builds the shared-trunk network (RLlib's vf_share_layers: the value head reads the policy half, the value half is dead) and appends _vfs behind
+ * the other suffixes: <name>[_h<H>][_<act>]_vfs (cda_mlp_forward_vfs, cda_mlp_forward_backward_h6_elu_vfs). */
 #ifndef CDA_MLP_VARIANT_H
 #define CDA_MLP_VARIANT_H
 #if defined(CDA_MLP_ACT) && CDA_MLP_ACT == 1
@@ -23,11 +25,23 @@
 #define CDA_MLP_ASFX2(n, a) n##_##a
 #define CDA_MLP_ASFX1(n, a) CDA_MLP_ASFX2(n, a)
 #if defined(CDA_MLP_HIST) && CDA_MLP_HIST != 4 && defined(CDA_MLP_ACT_NAME)
-#define CDA_MLP_SFX(n) CDA_MLP_ASFX1(CDA_MLP_SFX1(n, CDA_MLP_HIST), CDA_MLP_ACT_NAME)
+#define CDA_MLP_BSFX(n) CDA_MLP_ASFX1(CDA_MLP_SFX1(n, CDA_MLP_HIST), CDA_MLP_ACT_NAME)
 #elif defined(CDA_MLP_HIST) && CDA_MLP_HIST != 4
-#define CDA_MLP_SFX(n) CDA_MLP_SFX1(n, CDA_MLP_HIST)
+#define CDA_MLP_BSFX(n) CDA_MLP_SFX1(n, CDA_MLP_HIST)
 #elif defined(CDA_MLP_ACT_NAME)
-#define CDA_MLP_SFX(n) CDA_MLP_ASFX1(n, CDA_MLP_ACT_NAME)
+#define CDA_MLP_BSFX(n) CDA_MLP_ASFX1(n, CDA_MLP_ACT_NAME)
+#endif
+#ifndef CDA_MLP_VFS
+#define CDA_MLP_VFS 0
+#endif
+#define CDA_MLP_VSFX2(n) n##_vfs
+#define CDA_MLP_VSFX1(n) CDA_MLP_VSFX2(n)
+#if CDA_MLP_VFS && defined(CDA_MLP_BSFX)
+#define CDA_MLP_SFX(n) CDA_MLP_VSFX1(CDA_MLP_BSFX(n))
+#elif CDA_MLP_VFS
+#define CDA_MLP_SFX(n) CDA_MLP_VSFX1(n)
+#elif defined(CDA_MLP_BSFX)
+#define CDA_MLP_SFX(n) CDA_MLP_BSFX(n)
 #endif
 #ifdef CDA_MLP_SFX
 #define cda_mlp_tile_rows CDA_MLP_SFX(cda_mlp_tile_rows)

@@ -65,8 +65,8 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
     market when there are opponents (default 1).  groups: rollout chains (default 4).  keep (a dict, optional): receives the RolloutChains object, the
     placement, the collected metric tables (agent table, env row) and host copies of every step's env actions (`actions`: category, size_mean, size_sigma,
     price, price_offset as [steps, N, A]) - what a replay needs.
-    Every network opponent must have the policy's hidden activation (the bank's rows are launched by one activation's kernels): ValueError otherwise, raised
-    before the opponent is loaded and before anything runs."""
+    Every network opponent must have the policy's hidden activation and vf_share_layers setting (the bank's rows are launched by one object's kernels): ValueError
+    otherwise, raised before the opponent is loaded and before anything runs."""
     from .mlp import LEAGUE_RANDOM, FusedPolicy, PolicyBank, RolloutChains, read_policy
     if mode not in ("greedy", "sample"):
         raise ValueError(f"mode must be 'greedy' or 'sample' (got {mode!r})")
@@ -81,9 +81,11 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
     for p, o in enumerate(opp or []):
         if isinstance(o, str) and o == RANDOM:
             continue
-        act = o.activation if isinstance(o, FusedPolicy) else read_policy(o, with_activation=True)[1]
+        act, vfs = (o.activation, o.vf_share_layers) if isinstance(o, FusedPolicy) else read_policy(o, with_activation=True, with_vf_share_layers=True)[1:]
         if act != pol.activation:
             raise ValueError(f"opponent {p} is a {act} network, the policy a {pol.activation} one: a bank holds networks of one activation")
+        if vfs != pol.vf_share_layers:
+            raise ValueError(f"opponent {p} has vf_share_layers = {vfs}, the policy {pol.vf_share_layers}: a bank holds networks of one setting")
         op = _as_policy(o, dev)
         if op.L.hist != pol.L.hist:
             raise ValueError(f"opponent {p} is laid out for n_hist = {op.L.hist}, the policy for {pol.L.hist}")
@@ -103,7 +105,7 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
             driver = pol
         else:
             bank = PolicyBank(dev, N, A, n_trainable=1, max_frozen=max(1, len(nets)), random_seed=seed, n_hist=pol.L.hist,
-                              activation=pol.activation)
+                              activation=pol.activation, vf_share_layers=pol.vf_share_layers)
             bank.theta[0].copy_(pol.theta)
             bank.wb[0].copy_(pol.wb)
             row_of = {}

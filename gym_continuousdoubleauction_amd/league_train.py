@@ -172,7 +172,7 @@ def train_league_fused(env, iters=4, horizon=None, num_trainable=2, lr=5e-5, epo
                        std_dev_multiplier=0.1, max_champions=8, min_iterations_between_champions=2, chains=4, minibatch=262144, objective=None, use_graph=True,
                        recorder=None, info_markets=0, run_id="league", log=print, keep=None, allreduce=None, world=1, first_market=0, episode_metrics=True,
                        strict_nav_check=True, state_dependent_log_std=False, hidden=(256, 256),
-                       checkpoint_dir=None, chkpt_freq=0, chkpt_keep=3, restore=None, iters_is_delta=False, activation="tanh"):
+                       checkpoint_dir=None, chkpt_freq=0, chkpt_keep=3, restore=None, iters_is_delta=False, activation="tanh", vf_share_layers=False):
     """League self-play on the fused kernels (include/cda_mlp.h `cda_league`): the reference's training topology - `num_trainable` SEPARATELY trained policies
     (policy_p plays slot p), every other slot drawn per episode from the pool of uniform random modules and frozen champions by the reference's mapping rule
     (computed on the device, league.LeagueSlotMapper.assign_device) - at the speed of the fused loop: ONE policy launch per step serves every module of every
@@ -192,7 +192,8 @@ def train_league_fused(env, iters=4, horizon=None, num_trainable=2, lr=5e-5, epo
     trainable net (theta + Adam), every bank row as save_league's policy files (league/ in the checkpoint) plus the bank's packed weights, the League and mapper
     state (champions and their rows, promotion history, champion id counter, pool), the rollout counters, the updates' shuffle state, the KL coefficients and
     the running episode returns: the mapping, episode ids and promotions continue exactly.  Single-process runs only; no recorder.
-    activation: `fcnet_activation` of the whole bank (mlp.PolicyBank: trainable policies and their champion snapshots share it)."""
+    activation: `fcnet_activation` of the whole bank (mlp.PolicyBank: trainable policies and their champion snapshots share it); vf_share_layers likewise (RLlib's
+    shared trunk for every net of the bank)."""
     import numpy as np
     from . import ppo
     from .mlp import EpisodeReturns, FusedUpdate, PolicyBank, RolloutChains
@@ -209,7 +210,7 @@ def train_league_fused(env, iters=4, horizon=None, num_trainable=2, lr=5e-5, epo
     if resumable and int(chkpt_freq) % per_episode:
         raise ValueError(f"league checkpoints are taken at episode boundaries only: chkpt_freq ({chkpt_freq}) must be a multiple of max_step / horizon = {per_episode}")
     bank = PolicyBank(dev, N, A, k, max_frozen=max_champions, seed=seed, random_seed=seed + 12345 + 104729 * int(first_market), n_hist=env.n_hist, state_dependent_log_std=state_dependent_log_std, hidden=hidden,
-                      activation=activation)
+                      activation=activation, vf_share_layers=vf_share_layers)
     mapper = LeagueSlotMapper(A, k, A - k, original_opponent_weight, champion_weight)
     league = League(mapper, bank, std_dev_multiplier, max_champions, min_iterations_between_champions)
     ck_state = None
@@ -221,7 +222,7 @@ def train_league_fused(env, iters=4, horizon=None, num_trainable=2, lr=5e-5, epo
                     "seed": int(seed), "episode_metrics": bool(episode_metrics), "max_champions": int(max_champions), "std_dev_multiplier": float(std_dev_multiplier),
                     "min_iterations_between_champions": int(min_iterations_between_champions), "original_opponent_weight": float(original_opponent_weight),
                     "champion_weight": float(champion_weight), "run_id": str(run_id)}
-        run_args = CK.with_activation(run_args, bank.activation)
+        run_args = CK.with_vf_share_layers(CK.with_activation(run_args, bank.activation), bank.vf_share_layers)
         if restore:
             ck_path = CK.resolve_restore(checkpoint_dir, restore)
             ck_state, ck_snap = CK.load_checkpoint(ck_path)
@@ -382,10 +383,12 @@ def _load_league_state(league_dir, state, bank, league):
     with open(os.path.join(league_dir, "league.json")) as fh:
         lj = json.load(fh)
     for entry in lj["trainable"] + lj["champions"]:
-        theta, act = read_policy(os.path.join(league_dir, entry["file"]), with_activation=True)
+        theta, act, vfs = read_policy(os.path.join(league_dir, entry["file"]), with_activation=True, with_vf_share_layers=True)
         row = int(entry["row"])
         if act != bank.activation:
             raise ValueError(f"{entry['file']}: a {act} network, the bank's are {bank.activation}")
+        if vfs != bank.vf_share_layers:
+            raise ValueError(f"{entry['file']}: vf_share_layers = {vfs}, the bank's networks have {bank.vf_share_layers}")
         if theta.numel() != bank.theta.shape[1]:
             raise ValueError(f"{entry['file']}: {theta.numel()} parameters, the bank rows hold {bank.theta.shape[1]}")
         bank.theta[row].copy_(theta)
@@ -407,16 +410,17 @@ def save_league(directory, bank, league):
     Returns the league.json dict."""
     from .mlp import policy_record
     act = getattr(bank, "activation", "tanh")                   # (the bank's one activation: every file carries it, tanh files no key)
+    vfs = bool(getattr(bank, "vf_share_layers", False))         # (likewise the bank's one vf_share_layers: only shared-trunk files carry the key)
     os.makedirs(directory, exist_ok=True)
     promoted = {c["id"]: c for c in league.history}
     out = {"format": "cda-league", "version": 1, "trainable": [], "champions": []}
     for p in range(bank.n_trainable):
         fname = f"policy_{p}.pt"
-        torch.save(policy_record(bank.theta[p], activation=act), os.path.join(directory, fname))
+        torch.save(policy_record(bank.theta[p], activation=act, vf_share_layers=vfs), os.path.join(directory, fname))
         out["trainable"].append({"module": f"policy_{p}", "row": p, "file": fname})
     for cid, row in sorted(league.net_of.items(), key=lambda kv: kv[1]):
         fname = "champion_" + "".join(ch if ch.isalnum() or ch in "-_" else "_" for ch in str(cid)) + ".pt"
-        torch.save(policy_record(bank.theta[row], activation=act), os.path.join(directory, fname))
+        torch.save(policy_record(bank.theta[row], activation=act, vf_share_layers=vfs), os.path.join(directory, fname))
         c = promoted.get(cid, {})
         out["champions"].append({"module": str(cid), "row": int(row), "file": fname, "promoted_iteration": c.get("iteration"),
                                  "return": None if c.get("return") is None else float(c["return"]), "source": None if c.get("source") is None else str(c["source"])})
@@ -439,6 +443,7 @@ def main(argv=None):
     p.add_argument("--fcnet-hiddens", type=int, nargs=2, default=(256, 256), metavar=("H1", "H2"), help="hidden widths of the trainable policies (config/train_config.json:49), <= 256 each")
     p.add_argument("--fcnet-activation", choices=("tanh", "relu", "elu", "linear"), default="tanh",
                    help="--fused: the hidden activation of every policy in the bank (config/train_config.json:50)")
+    p.add_argument("--vf-share-layers", action="store_true", help="--fused: one trunk for policy and value in every net of the bank (RLlib's vf_share_layers, config/train_config.json:51)")
     p.add_argument("--log-std-head", action="store_true", help="the trainable policies carry the state-dependent log-std head (RLlib's default module for Box actions)")
     p.add_argument("--out", default=None, help="write a JSON summary to this file")
     p.add_argument("--save-dir", default=None, help="--fused: write the trainable policies, the champion snapshots and league.json here (save_league)")
@@ -467,7 +472,7 @@ def main(argv=None):
     bank, league, hist = train_league_fused(env, iters=args.iters, horizon=args.horizon, num_trainable=k, chains=args.chains,
                                          objective=ppo.RLLIB_DEFAULTS if args.objective == "rllib" else None, state_dependent_log_std=args.log_std_head, hidden=tuple(args.fcnet_hiddens),
                                          checkpoint_dir=args.checkpoint_dir, chkpt_freq=args.chkpt_freq, chkpt_keep=args.chkpt_keep, restore=args.restore,
-                                         iters_is_delta=args.iters_is_delta, activation=args.fcnet_activation)
+                                         iters_is_delta=args.iters_is_delta, activation=args.fcnet_activation, vf_share_layers=args.vf_share_layers)
     flags = env.flags()
     _, bad = env.nav_conservation()
     tail = hist[2:] if len(hist) >= 4 else (hist[1:] or hist)          # (two warm-up iterations: graph capture, first replays)

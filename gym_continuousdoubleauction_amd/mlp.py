@@ -28,6 +28,9 @@ HIST_VARIANTS = (1, 2, 3, 4, 6, 7, 8)          # (5: the update kernel's gather 
 #: reference's and the unsuffixed entry points, the others <name>[_h<H>]_<act>.  The backward takes act'(z) from the stored bf16 output h = act(z)
 #: (csrc/cda_mlp_dev.inc ActT), so an activation whose derivative h does not determine - SiLU / swish, GELU - is refused.
 ACTIVATIONS = ("tanh", "relu", "elu", "linear")
+#: the shared-trunk network (RLlib's vf_share_layers = True) is compiled for every depth and activation above under <name>[_h<H>][_<act>]_vfs (include/cda_mlp.h
+#: CDA_MLP_VFS_VARIANTS): the same parameter vector with its value half (W1 / b1 rows 256..511, W2 block 1, b2 256..511) exact zeros, and output row 24 (the value
+#: head) reading the policy half - the trunk.
 
 
 def check_activation(activation):
@@ -47,11 +50,13 @@ def _lib():
 
 class Layout:
     """The constants of include/cda_mlp.h at one history depth (observation = n_hist frames of 42 floats) and the entry points compiled for it
-    and hidden activation (`fn("cda_mlp_policy_step")` -> the library's cda_mlp_policy_step[_h<H>][_<act>])."""
+    and hidden activation (`fn("cda_mlp_policy_step")` -> the library's cda_mlp_policy_step[_h<H>][_<act>]), and vf_share_layers: the shared-trunk objects
+    (cda_mlp_policy_step[_h<H>][_<act>]_vfs)."""
 
-    def __init__(self, n_hist, activation="tanh"):
+    def __init__(self, n_hist, activation="tanh", vf_share_layers=False):
         h = int(n_hist)
         self.activation = act = check_activation(activation)
+        self.vf_share_layers = vfs = bool(vf_share_layers)
         if h not in HIST_VARIANTS:
             raise ValueError(f"the network kernels are compiled for n_hist in {HIST_VARIANTS} (got {n_hist}); other depths run the PyTorch loops (ppo.train)")
         self.hist, self.OBS = h, 42 * h
@@ -67,7 +72,7 @@ class Layout:
         self.PARAMS = self.OFF_LS + 2
         self.WB_ELEMS = FEAT * self.KX + 2 * HID * HID + 2 * NOUT * HID + 2 * HID * HID + 2 * HID * NOUT
         self.SLAB = FEAT * 32 * self.XT + 2 * HID * HID + NOUT * FEAT
-        self.suffix = ("" if h == 4 else f"_h{h}") + ("" if act == "tanh" else f"_{act}")
+        self.suffix = ("" if h == 4 else f"_h{h}") + ("" if act == "tanh" else f"_{act}") + ("_vfs" if vfs else "")
 
     def fn(self, name):
         return getattr(_lib(), name + self.suffix)
@@ -76,8 +81,8 @@ class Layout:
 _LAYOUTS = {}
 
 
-def layout(n_hist=4, activation="tanh"):
-    key = (n_hist, check_activation(activation))
+def layout(n_hist=4, activation="tanh", vf_share_layers=False):
+    key = (n_hist, check_activation(activation), bool(vf_share_layers))
     if key not in _LAYOUTS:
         _LAYOUTS[key] = Layout(*key)
     return _LAYOUTS[key]
@@ -108,14 +113,27 @@ def _stream(dev):
     return torch.cuda.current_stream(dev).cuda_stream
 
 
-def init_theta(obs_dim=OBS, generator=None, state_dependent_log_std=False, hidden=(HID, HID)):
+def value_half(L):
+    """the index ranges (start, stop) of the value half in a parameter vector of layout L: W1 / b1 rows 256..511, W2 block 1, b2 256..511 - what a shared-trunk
+    network (vf_share_layers) holds at exact zeros (Wo row 24, the value head, then reads the policy half)"""
+    return ((L.OFF_W1 + HID * L.OBS, L.OFF_B1), (L.OFF_B1 + HID, L.OFF_W2), (L.OFF_W2 + HID * HID, L.OFF_B2), (L.OFF_B2 + HID, L.OFF_WO))
+
+
+def value_half_is_zero(theta):
+    """is every entry of theta's value half an exact zero (what a shared-trunk network must hold)?"""
+    L = layout_of_params(theta.numel())
+    return all(not bool((theta[a:b] != 0).any()) for a, b in value_half(L))
+
+
+def init_theta(obs_dim=OBS, generator=None, state_dependent_log_std=False, hidden=(HID, HID), vf_share_layers=False):
     """A fresh parameter vector with nn.Linear's default initialisation per block (uniform +-1/sqrt(fan_in)), log_std = -0.5; obs_dim = 42 n_hist.
     state_dependent_log_std: rows 25, 26 of the output layer - the log-std head's offsets on top of the free vector, RLlib's default module for Box actions
     (train/policy/policy_handler.py:69-76) - are initialised like every other output row instead of zero (`has_log_std_head(theta)` tells the two apart).
     hidden = (h1, h2), each 1 .. 256: the reference's `fcnet_hiddens` (config/train_config.json:49; 256 x 256 there).  The kernels are compiled for 256-wide layers; a
     NARROWER network is the same parameter vector with the units beyond h1 / h2 of both halves dead - incoming and outgoing weights and biases exactly zero.  A dead
     unit outputs act(0) = 0 exactly (every activation of ACTIVATIONS), so every gradient that touches it is an exact zero and Adam never moves it (tests/test_hip_mlp.py): the narrow network trains
-    inside the wide kernels at the wide kernels' cost.  `hidden_widths(theta)` reads the widths back."""
+    inside the wide kernels at the wide kernels' cost.  `hidden_widths(theta)` reads the widths back.
+    vf_share_layers: RLlib's shared trunk - the value half is zeroed (value_half) and output row 24 / bias 24, drawn like today's value head, read the policy half."""
     if obs_dim % 42:
         raise ValueError("an observation is n_hist frames of 42 floats")
     L = layout(obs_dim // 42)
@@ -140,17 +158,21 @@ def init_theta(obs_dim=OBS, generator=None, state_dependent_log_std=False, hidde
         w1[:, h1:] = 0; b1[:, h1:] = 0
         w2[:, h2:, :] = 0; w2[:, :, h1:] = 0; b2[:, h2:] = 0
         wo_v[:, h2:] = 0
+    if vf_share_layers:
+        for a, b in value_half(L):
+            th[a:b] = 0
     return th
 
 
 def hidden_widths(theta):
-    """(h1, h2): the live units of the two hidden layers (the same in the policy and the value half) - a unit is dead when its bias and every weight into it are zero"""
+    """(h1, h2): the live units of the two hidden layers, read from the policy half (the value half has the same widths, or is all dead in a shared-trunk network) - a
+    unit is dead when its bias and every weight into it are zero"""
     L = layout_of_params(theta.numel())
     th = theta.detach().float().cpu()
     w1, b1 = th[L.OFF_W1:L.OFF_B1].view(2, HID, L.OBS), th[L.OFF_B1:L.OFF_W2].view(2, HID)
     w2, b2 = th[L.OFF_W2:L.OFF_B2].view(2, HID, HID), th[L.OFF_B2:L.OFF_WO].view(2, HID)
-    live1 = ((w1 != 0).any(-1) | (b1 != 0)).any(0)
-    live2 = ((w2 != 0).any(-1) | (b2 != 0)).any(0)
+    live1 = ((w1 != 0).any(-1) | (b1 != 0))[0]
+    live2 = ((w2 != 0).any(-1) | (b2 != 0))[0]
     last = lambda m: int(m.nonzero().max()) + 1 if bool(m.any()) else 0       # noqa: E731
     return last(live1), last(live2)
 
@@ -176,7 +198,8 @@ def theta_from_actor_critic(model):
         th[L.OFF_B2:L.OFF_WO] = model.l2.bias.detach().float().cpu()
         wo = model.out.weight.detach().float().cpu()
         blk = torch.zeros(NOUT, H)
-        blk[:N_LOGITS] = wo[:N_LOGITS, :H]; blk[N_LOGITS] = wo[N_LOGITS, H:]
+        vfs = bool(getattr(model, "vf_share_layers", False))
+        blk[:N_LOGITS] = wo[:N_LOGITS, :H]; blk[N_LOGITS] = wo[N_LOGITS, :H] if vfs else wo[N_LOGITS, H:]
         bo = model.out.bias.detach().float().cpu().clone()
         if getattr(model, "state_dependent_log_std", False):
             blk[list(LS_ROWS)] = wo[list(LS_ROWS), :H]; bo[N_LOGITS + 3:] = 0
@@ -188,19 +211,25 @@ def theta_from_actor_critic(model):
     return th
 
 
-def actor_critic_from_theta(theta, dtype=torch.float32, activation="tanh"):
+def actor_critic_from_theta(theta, dtype=torch.float32, activation="tanh", vf_share_layers=False):
     from .ppo import ActorCritic
     th = theta.detach().float().cpu()
     L = layout_of_params(th.numel())
     sd = has_log_std_head(th)
-    m = ActorCritic(L.OBS, state_dependent_log_std=sd, activation=activation).to(dtype)
+    if vf_share_layers and not value_half_is_zero(th):
+        raise ValueError("vf_share_layers: the parameter vector's value half must be exact zeros")
+    m = ActorCritic(L.OBS, state_dependent_log_std=sd, activation=activation, vf_share_layers=vf_share_layers).to(dtype)
     H = HID
     with torch.no_grad():
         m.l1.weight.copy_(th[L.OFF_W1:L.OFF_B1].view(FEAT, L.OBS)); m.l1.bias.copy_(th[L.OFF_B1:L.OFF_W2])
         w2 = th[L.OFF_W2:L.OFF_B2].view(2, H, H)
         m.l2.weight.zero_(); m.l2.weight[:H, :H] = w2[0]; m.l2.weight[H:, H:] = w2[1]; m.l2.bias.copy_(th[L.OFF_B2:L.OFF_WO])
         wo = th[L.OFF_WO:L.OFF_BO].view(NOUT, H)
-        m.out.weight.zero_(); m.out.weight[:N_LOGITS, :H] = wo[:N_LOGITS]; m.out.weight[N_LOGITS, H:] = wo[N_LOGITS]
+        m.out.weight.zero_(); m.out.weight[:N_LOGITS, :H] = wo[:N_LOGITS]
+        if vf_share_layers:
+            m.out.weight[N_LOGITS, :H] = wo[N_LOGITS]
+        else:
+            m.out.weight[N_LOGITS, H:] = wo[N_LOGITS]
         if sd:
             m.out.weight[list(LS_ROWS), :H] = wo[list(LS_ROWS)]
         m.out.bias.copy_(th[L.OFF_BO:L.OFF_LS]); m.log_std.copy_(th[L.OFF_LS:])
@@ -230,9 +259,10 @@ def act_grad_from_out(activation, h):
     return torch.ones_like(h)
 
 
-def reference_outputs(theta, x, emulate_bf16=True, dtype=torch.float64, keep=False, activation="tanh"):
+def reference_outputs(theta, x, emulate_bf16=True, dtype=torch.float64, keep=False, activation="tanh", vf_share_layers=False):
     """The network in plain PyTorch on the CPU: out [n, 32].  emulate_bf16: operands (inputs, weights, activations between layers) rounded
-    to bfloat16 as the kernels do, products and sums in `dtype`.  keep: also return (xb, h1, h2) as the kernels store them.  activation: of both hidden layers."""
+    to bfloat16 as the kernels do, products and sums in `dtype`.  keep: also return (xb, h1, h2) as the kernels store them.  activation: of both hidden layers.
+    vf_share_layers: the value column 24 reads the policy half (the trunk); the value half's entries of theta are not read."""
     act = act_fn(activation)
     th = theta.detach().cpu().to(dtype)
     x = x.detach().cpu().to(dtype)
@@ -246,20 +276,25 @@ def reference_outputs(theta, x, emulate_bf16=True, dtype=torch.float64, keep=Fal
     h2 = torch.cat([rd(act(h1[:, :HID] @ W2[0].t() + b2[:HID])), rd(act(h1[:, HID:] @ W2[1].t() + b2[HID:]))], dim=1)
     out = torch.zeros(x.shape[0], NOUT, dtype=dtype)
     out[:, POLICY_ROWS] = h2[:, :HID] @ Wo[POLICY_ROWS].t() + bo[POLICY_ROWS]          # (rows 25, 26: the log-std head's offsets; zero rows without the head)
-    out[:, N_LOGITS] = h2[:, HID:] @ Wo[N_LOGITS] + bo[N_LOGITS]
+    out[:, N_LOGITS] = (h2[:, :HID] if vf_share_layers else h2[:, HID:]) @ Wo[N_LOGITS] + bo[N_LOGITS]
     return (out, xb, h1, h2) if keep else out
 
 
-def reference_gradients(theta, xb, h1, h2, d_out, dtype=torch.float64, activation="tanh"):
+def reference_gradients(theta, xb, h1, h2, d_out, dtype=torch.float64, activation="tanh", vf_share_layers=False):
     """The back-propagation the kernels perform, in plain PyTorch: gradient of theta (dense vector, log_std entries zero) for given
-    d_out [n, 32], with the kernels' roundings (d_out, dz2, dz1 rounded to bfloat16 where they become operands); act' from the stored h1 / h2."""
+    d_out [n, 32], with the kernels' roundings (d_out, dz2, dz1 rounded to bfloat16 where they become operands); act' from the stored h1 / h2.
+    vf_share_layers: column 24 back-propagates into the trunk (the policy half); the value half's gradient is exact zeros, dz1 / dz2 of that half too."""
     th = theta.detach().cpu().to(dtype)
     L = layout_of_params(th.numel())
     OFF_W1, OFF_B1, OFF_W2, OFF_B2, OFF_WO, OFF_BO, OFF_LS, PARAMS = L.OFF_W1, L.OFF_B1, L.OFF_W2, L.OFF_B2, L.OFF_WO, L.OFF_BO, L.OFF_LS, L.PARAMS      # (this depth's, not the module's)
     W2 = _r(th[OFF_W2:OFF_B2].view(2, HID, HID)); Wo = _r(th[OFF_WO:OFF_BO].view(NOUT, HID))
     d_out = d_out.detach().cpu().to(dtype)
     dob = _r(d_out)
-    dh2 = torch.cat([dob[:, POLICY_ROWS] @ Wo[POLICY_ROWS], dob[:, N_LOGITS:N_LOGITS + 1] @ Wo[N_LOGITS:N_LOGITS + 1]], dim=1)
+    if vf_share_layers:
+        rows = POLICY_ROWS + [N_LOGITS]
+        dh2 = torch.cat([dob[:, rows] @ Wo[rows], torch.zeros(dob.shape[0], HID, dtype=dtype)], dim=1)
+    else:
+        dh2 = torch.cat([dob[:, POLICY_ROWS] @ Wo[POLICY_ROWS], dob[:, N_LOGITS:N_LOGITS + 1] @ Wo[N_LOGITS:N_LOGITS + 1]], dim=1)
     dz2 = _r(dh2 * act_grad_from_out(activation, h2))
     dh1 = torch.cat([dz2[:, :HID] @ W2[0], dz2[:, HID:] @ W2[1]], dim=1)
     dz1 = _r(dh1 * act_grad_from_out(activation, h1))
@@ -267,8 +302,11 @@ def reference_gradients(theta, xb, h1, h2, d_out, dtype=torch.float64, activatio
     g[OFF_W1:OFF_B1] = (dz1.t() @ xb).reshape(-1); g[OFF_B1:OFF_W2] = dz1.sum(0)
     g[OFF_W2:OFF_B2] = torch.stack([dz2[:, :HID].t() @ h1[:, :HID], dz2[:, HID:].t() @ h1[:, HID:]]).reshape(-1); g[OFF_B2:OFF_WO] = dz2.sum(0)
     gwo = torch.zeros(NOUT, HID, dtype=dtype)
-    gwo[POLICY_ROWS] = dob[:, POLICY_ROWS].t() @ h2[:, :HID]; gwo[N_LOGITS] = dob[:, N_LOGITS] @ h2[:, HID:]
+    gwo[POLICY_ROWS] = dob[:, POLICY_ROWS].t() @ h2[:, :HID]; gwo[N_LOGITS] = dob[:, N_LOGITS] @ (h2[:, :HID] if vf_share_layers else h2[:, HID:])
     g[OFF_WO:OFF_BO] = gwo.reshape(-1)
+    if vf_share_layers:
+        for a, b in value_half(L):
+            g[a:b] = 0
     gbo = torch.zeros(NOUT, dtype=dtype); gbo[:N_LOGITS + 3] = d_out[:, :N_LOGITS + 3].sum(0)
     g[OFF_BO:OFF_LS] = gbo
     return g, dz1, dz2
@@ -296,20 +334,25 @@ class FusedPolicy:
     """theta (f32 master copy), Adam state and the bf16 operand blob on one HIP device.  storage = (theta row, wb row): views into a PolicyBank's
     banks instead of tensors of its own (the league's kernels address a net as a row of the banks)."""
 
-    def __init__(self, device, theta=None, seed=0, storage=None, n_hist=None, state_dependent_log_std=None, hidden=(HID, HID), activation="tanh"):
+    def __init__(self, device, theta=None, seed=0, storage=None, n_hist=None, state_dependent_log_std=None, hidden=(HID, HID), activation="tanh", vf_share_layers=False):
         """n_hist: the history depth of the observations (default: the depth `theta` was laid out for, else the reference's 4).
         state_dependent_log_std: RLlib's default head for Box actions - the policy network emits two log-std offsets per row (output rows 25, 26) on top of the free
         log_std vector, and the update trains them (FusedUpdate reads this attribute); default: what `theta` carries (has_log_std_head), False for a fresh network.
         hidden: the widths of a FRESH network's two hidden layers, <= 256 each (init_theta: the reference's `fcnet_hiddens`).
-        activation: of both hidden layers of both halves (the reference's `fcnet_activation`: ACTIVATIONS); every kernel this policy launches is that activation's."""
+        activation: of both hidden layers of both halves (the reference's `fcnet_activation`: ACTIVATIONS); every kernel this policy launches is that activation's.
+        vf_share_layers: RLlib's shared trunk (the value head reads the policy half; the value half is exact zeros - a given `theta` must hold them); every kernel
+        this policy launches is the shared-trunk object's (Layout.suffix _vfs)."""
         self.activation = check_activation(activation)
+        self.vf_share_layers = bool(vf_share_layers)
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("FusedPolicy needs a HIP device; the PyTorch statement of the network is ppo.ActorCritic")
         if theta is None:
             g = torch.Generator().manual_seed(int(seed))
-            theta = init_theta(42 * int(n_hist or 4), generator=g, state_dependent_log_std=bool(state_dependent_log_std), hidden=hidden)
-        self.L = L = layout(layout_of_params(theta.numel()).hist, self.activation)
+            theta = init_theta(42 * int(n_hist or 4), generator=g, state_dependent_log_std=bool(state_dependent_log_std), hidden=hidden, vf_share_layers=self.vf_share_layers)
+        elif self.vf_share_layers and not value_half_is_zero(theta.detach().cpu()):
+            raise ValueError("vf_share_layers: the parameter vector's value half (W1 / b1 rows 256..511, W2 block 1, b2 256..511) must be exact zeros")
+        self.L = L = layout(layout_of_params(theta.numel()).hist, self.activation, self.vf_share_layers)
         self.state_dependent_log_std = has_log_std_head(theta) if state_dependent_log_std is None else bool(state_dependent_log_std)
         if n_hist is not None and int(n_hist) != L.hist:
             raise ValueError(f"theta is laid out for n_hist = {L.hist}, not {n_hist}")
@@ -327,10 +370,11 @@ class FusedPolicy:
 
     @classmethod
     def from_actor_critic(cls, model, device):
-        return cls(device, theta=theta_from_actor_critic(model), activation=getattr(model, "activation", "tanh"))
+        return cls(device, theta=theta_from_actor_critic(model), activation=getattr(model, "activation", "tanh"),
+                   vf_share_layers=getattr(model, "vf_share_layers", False))
 
     def to_actor_critic(self, dtype=torch.float32):
-        return actor_critic_from_theta(self.theta, dtype, activation=self.activation)
+        return actor_critic_from_theta(self.theta, dtype, activation=self.activation, vf_share_layers=self.vf_share_layers)
 
     @property
     def log_std(self):
@@ -403,12 +447,14 @@ class PolicyBank:
     the row that plays each (market, slot), LEAGUE_RANDOM = the uniform random module."""
 
     def __init__(self, device, n_markets, num_agents, n_trainable, max_frozen=8, seed=0, random_seed=0, n_hist=4, state_dependent_log_std=False, hidden=(HID, HID),
-                 activation="tanh"):
-        """activation: ONE hidden activation for the whole bank - trainable rows and the champions snapshotted from them (a bank row is launched by one object's kernels)"""
+                 activation="tanh", vf_share_layers=False):
+        """activation: ONE hidden activation for the whole bank - trainable rows and the champions snapshotted from them (a bank row is launched by one object's kernels);
+        vf_share_layers likewise: one setting for every row (a champion is a copy of a trainable row: it inherits it)"""
         from ._lib import League
         self.device = torch.device(device)
         self.activation = check_activation(activation)
-        self.L = L = layout(n_hist, self.activation)
+        self.vf_share_layers = bool(vf_share_layers)
+        self.L = L = layout(n_hist, self.activation, self.vf_share_layers)
         PARAMS, WB_ELEMS = L.PARAMS, L.WB_ELEMS
         self.n_trainable, self.max_frozen, self.n_frozen = int(n_trainable), int(max_frozen), 0
         if not 1 <= self.n_trainable <= num_agents or self.n_trainable + self.max_frozen > LEAGUE_MAX_NETS:
@@ -417,7 +463,7 @@ class PolicyBank:
         self.theta = torch.zeros((n_max, PARAMS), dtype=torch.float32, device=self.device)
         self.wb = torch.zeros((n_max, WB_ELEMS), dtype=torch.bfloat16, device=self.device)
         self.policies = [FusedPolicy(self.device, seed=seed + 7919 * p, storage=(self.theta[p], self.wb[p]), n_hist=L.hist, state_dependent_log_std=state_dependent_log_std, hidden=hidden,
-                                     activation=self.activation)
+                                     activation=self.activation, vf_share_layers=self.vf_share_layers)
                          for p in range(self.n_trainable)]
         self.slot_net = torch.full((int(n_markets), int(num_agents)), LEAGUE_RANDOM, dtype=torch.int32, device=self.device)
         self.slot_net[:, :self.n_trainable] = torch.arange(self.n_trainable, dtype=torch.int32, device=self.device)
@@ -899,13 +945,17 @@ class FusedUpdate:
 POLICY_FORMAT, POLICY_VERSION = "cda-mlp-policy", 1
 
 
-def policy_record(policy, row=None, activation=None):
+def policy_record(policy, row=None, activation=None, vf_share_layers=None):
     """the dict a policy file holds: {"format", "version", "theta" (f32, CPU), "n_hist", "hidden", "state_dependent_log_std"} and, for a network whose hidden activation
-    is not tanh, "activation" (a file without the key is a tanh network: files of tanh networks are the same as before the key existed).  policy: a FusedPolicy, a
-    PolicyBank with its `row`, or a parameter vector (CPU or device tensor; `activation` then names its activation, default tanh)"""
+    is not tanh, "activation" (a file without the key is a tanh network: files of tanh networks are the same as before the key existed); for a shared-trunk network
+    "vf_share_layers": True (likewise absent otherwise).  policy: a FusedPolicy, a PolicyBank with its `row`, or a parameter vector (CPU or device tensor; `activation` /
+    `vf_share_layers` then name its activation, default tanh, and whether it is a shared trunk, default False)"""
     act = check_activation(activation if activation is not None else getattr(policy, "activation", "tanh"))
     if activation is not None and isinstance(policy, (FusedPolicy, PolicyBank)) and act != policy.activation:
         raise ValueError(f"activation={activation!r}, but the policy's is {policy.activation!r}")
+    vfs = bool(vf_share_layers if vf_share_layers is not None else getattr(policy, "vf_share_layers", False))
+    if vf_share_layers is not None and isinstance(policy, (FusedPolicy, PolicyBank)) and vfs != policy.vf_share_layers:
+        raise ValueError(f"vf_share_layers={vf_share_layers!r}, but the policy's is {policy.vf_share_layers!r}")
     if isinstance(policy, PolicyBank):
         if row is None:
             raise ValueError("a PolicyBank needs the bank row to save (row=...)")
@@ -922,6 +972,10 @@ def policy_record(policy, row=None, activation=None):
            "state_dependent_log_std": has_log_std_head(theta)}
     if act != "tanh":
         rec["activation"] = act
+    if vfs:
+        if not value_half_is_zero(theta):
+            raise ValueError("vf_share_layers: the parameter vector's value half must be exact zeros")
+        rec["vf_share_layers"] = True
     return rec
 
 
@@ -933,6 +987,14 @@ def record_activation(rec):
     if not isinstance(a, str):
         raise ValueError(f"policy file says activation = {a!r}: one of {ACTIVATIONS} (a tanh network's file carries no key)")
     return check_activation(a)
+
+
+def record_vf_share_layers(rec):
+    """does a policy file's dict describe a shared-trunk network (RLlib's vf_share_layers)?  False where the key is missing; a non-bool value raises ValueError"""
+    v = rec.get("vf_share_layers", False)
+    if not isinstance(v, bool):
+        raise ValueError(f"policy file says vf_share_layers = {v!r}: a bool (a network with a separate value half carries no key)")
+    return v
 
 
 def save_policy(path, policy, row=None):
@@ -957,18 +1019,22 @@ def check_policy_record(rec):
     if bool(rec.get("state_dependent_log_std")) != has_log_std_head(theta) or not isinstance(rec.get("state_dependent_log_std"), bool):
         raise ValueError(f"policy file says state_dependent_log_std = {rec.get('state_dependent_log_std')!r}, its parameter vector says {has_log_std_head(theta)}")
     record_activation(rec)
+    if record_vf_share_layers(rec) and not value_half_is_zero(theta):
+        raise ValueError("policy file says vf_share_layers = True, but its parameter vector's value half (W1 / b1 rows 256..511, W2 block 1, b2 256..511) is not all zeros")
     return theta
 
 
-def read_policy(path, with_activation=False):
+def read_policy(path, with_activation=False, with_vf_share_layers=False):
     """a policy file's parameter vector (f32, CPU), validated (check_policy_record); no device needed.  with_activation: (theta, the hidden activation), "tanh" for a
-    file without the key"""
+    file without the key; with_vf_share_layers: ... and whether the network is a shared trunk, appended to the tuple"""
     rec = torch.load(path, map_location="cpu", weights_only=True)
     theta = check_policy_record(rec)
-    return (theta, record_activation(rec)) if with_activation else theta
+    if not (with_activation or with_vf_share_layers):
+        return theta
+    return (theta,) + ((record_activation(rec),) if with_activation else ()) + ((record_vf_share_layers(rec),) if with_vf_share_layers else ())
 
 
 def load_policy(path, device):
-    """a policy file -> a FusedPolicy on `device` (theta bit-equal to the saved vector, wb re-packed from it; the file's hidden activation)"""
-    theta, act = read_policy(path, with_activation=True)
-    return FusedPolicy(device, theta=theta, state_dependent_log_std=has_log_std_head(theta), activation=act)
+    """a policy file -> a FusedPolicy on `device` (theta bit-equal to the saved vector, wb re-packed from it; the file's hidden activation and vf_share_layers)"""
+    theta, act, vfs = read_policy(path, with_activation=True, with_vf_share_layers=True)
+    return FusedPolicy(device, theta=theta, state_dependent_log_std=has_log_std_head(theta), activation=act, vf_share_layers=vfs)

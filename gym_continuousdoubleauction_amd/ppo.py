@@ -75,13 +75,16 @@ class ActorCritic(nn.Module):
     backward pass take 12 ms of host time, tools/ppo_probe.py)."""
     N_OUT, N_PAD = CAT_N + PRICE_N + OFF_N + 2, 32
 
-    def __init__(self, obs_dim, hidden=256, state_dependent_log_std=False, activation="tanh"):
+    def __init__(self, obs_dim, hidden=256, state_dependent_log_std=False, activation="tanh", vf_share_layers=False):
         """state_dependent_log_std: RLlib's default module for Box actions (what the reference's PPO modules are, train/policy/policy_handler.py:69-76): rows 25, 26 of
         the output matrix read the policy half and are per-row log-std OFFSETS on top of the free `log_std` vector (which then stays where it is).
-        activation: of both hidden layers of both halves - the reference's `fcnet_activation` (mlp.ACTIVATIONS: tanh, relu, elu, linear; None = linear)."""
+        activation: of both hidden layers of both halves - the reference's `fcnet_activation` (mlp.ACTIVATIONS: tanh, relu, elu, linear; None = linear).
+        vf_share_layers: RLlib's shared trunk - ONE encoder (the first half), the value row 24 reads it like the pi heads, and vf_coef * value loss reaches the trunk.
+        The same block matrices: the value half (rows H.. of l1, block 1 of l2 and their biases) is masked to exact zeros and, with a zero gradient, stays so."""
         from .mlp import check_activation
         super().__init__()
         self.activation = check_activation(activation)
+        self.vf_share_layers = bool(vf_share_layers)
         self.hidden = hidden
         self.state_dependent_log_std = bool(state_dependent_log_std)
         H = hidden
@@ -89,9 +92,15 @@ class ActorCritic(nn.Module):
         self.l2 = _Linear(2 * H, 2 * H)
         self.out = _Linear(2 * H, self.N_PAD)
         m2 = torch.zeros(2 * H, 2 * H)
-        m2[:H, :H] = 1; m2[H:, H:] = 1
+        m2[:H, :H] = 1
+        if not self.vf_share_layers:
+            m2[H:, H:] = 1
         mo = torch.zeros(self.N_PAD, 2 * H)
-        mo[:self.N_OUT, :H] = 1; mo[self.N_OUT, H:] = 1
+        mo[:self.N_OUT, :H] = 1
+        if self.vf_share_layers:
+            mo[self.N_OUT, :H] = 1
+        else:
+            mo[self.N_OUT, H:] = 1
         if self.state_dependent_log_std:
             mo[self.N_OUT + 1:self.N_OUT + 3, :H] = 1
         self.register_buffer("mask2", m2)
@@ -102,6 +111,12 @@ class ActorCritic(nn.Module):
                 w.uniform_(-bound, bound); b.uniform_(-bound, bound)
             self.l2.weight.mul_(m2); self.out.weight.mul_(mo)
             self.out.bias[self.N_OUT + (3 if self.state_dependent_log_std else 1):] = 0
+        if self.vf_share_layers:
+            m1 = torch.zeros(2 * H, obs_dim)
+            m1[:H] = 1
+            self.register_buffer("mask1", m1)
+            with torch.no_grad():
+                self.l1.weight[H:] = 0; self.l1.bias[H:] = 0; self.l2.bias[H:] = 0
         self.log_std = nn.Parameter(torch.full((2,), -0.5), requires_grad=not self.state_dependent_log_std)
 
     def trunk(self, obs):
@@ -122,7 +137,10 @@ class ActorCritic(nn.Module):
         (what cda_ppo_loss / cda_policy_sample read in place, `out_stride` / `logits_stride` = 32)"""
         from .mlp import act_fn
         act = act_fn(self.activation)
-        h = act(self.l1(obs))
+        if self.vf_share_layers:                                   # (the dead value half: zero weights with a masked gradient; its biases' gradient is exactly zero)
+            h = act(_SplitKLinear.apply(obs, self.l1.weight, self.l1.bias, self.mask1))
+        else:
+            h = act(self.l1(obs))
         h = act(_SplitKLinear.apply(h, self.l2.weight, self.l2.bias, self.mask2))     # (off-block entries: zero at init, zero gradient)
         return _SplitKLinear.apply(h, self.out.weight, self.out.bias, self.mask_out)
 
@@ -512,7 +530,7 @@ def adapt_kl_coef(kl_coef, sampled_kl, kl_target):
 def train_fused(env, iters=4, horizon=64, lr=5e-5, epochs=4, reward_scale=None, seed=0, log=print, use_graph=True, chains=4, minibatch=262144,
                 gamma=None, lam=None, clip=None, vf_coef=None, ent_coef=None, policy=None, keep=None, sub_batches=None, objective=None, recorder=None, info_markets=0,
                 allreduce=None, world=1, first_market=0, episode_metrics=True, strict_nav_check=True, state_dependent_log_std=False, hidden=(256, 256),
-                checkpoint_dir=None, chkpt_freq=0, chkpt_keep=3, restore=None, iters_is_delta=False, activation="tanh"):
+                checkpoint_dir=None, chkpt_freq=0, chkpt_keep=3, restore=None, iters_is_delta=False, activation="tanh", vf_share_layers=False):
     """The PPO loop on the hand-written network kernels (mlp.py, include/cda_mlp.h): rollouts as `chains` independent per-chain launch
     sequences (policy forward + sampling -> env step -> auto reset, one HIP graph per chain, no cross-stream edge inside the horizon), the
     sample records completed by one GAE launch, the update as {gather + forward + loss + back-propagation, weight gradients, reduce, clip + Adam}
@@ -530,7 +548,8 @@ def train_fused(env, iters=4, horizon=64, lr=5e-5, epochs=4, reward_scale=None, 
     agent's passive share) and a violation raises NavConservationError like the reference's strict_nav_check run (train/train.py:1125-1164); strict_nav_check=False logs it.
     state_dependent_log_std: a fresh policy gets RLlib's default head for Box actions (two log-stds per row from the policy network: mlp.FusedPolicy); a given `policy`
     brings its own.  hidden: `fcnet_hiddens` of a fresh policy, <= 256 each (mlp.init_theta).  activation: `fcnet_activation` of a fresh policy (mlp.ACTIVATIONS;
-    a given `policy` brings its own); a network that is not tanh rolls out with two launches per step (k_policy_step is the tanh network's).
+    a given `policy` brings its own); a network that is not tanh rolls out with two launches per step (k_policy_step is the tanh network's).  vf_share_layers: RLlib's
+    shared trunk for a fresh policy (mlp.FusedPolicy; a given `policy` brings its own) - it too rolls out with two launches per step.
     Needs a HIP CDAVecEnv with auto_reset and 168-float observations.  Returns (FusedPolicy, history); `keep` (a dict) receives the last
     rollout's buffers and the RolloutChains object.  history[i]: losses, `mean_reward` (of the rollout's slice of the episodes - it depends on WHICH part of
     the episodes the slice covers) and `episode_return` (mean return of the episodes that were COMPLETED during the iteration, None if none was).
@@ -548,7 +567,8 @@ def train_fused(env, iters=4, horizon=64, lr=5e-5, epochs=4, reward_scale=None, 
     dev = env.obs.device
     N, A, T = env.n_markets, env.num_agents, int(horizon)
     if policy is None:
-        policy = FusedPolicy(dev, seed=seed, n_hist=env.n_hist, state_dependent_log_std=state_dependent_log_std, hidden=hidden, activation=activation)
+        policy = FusedPolicy(dev, seed=seed, n_hist=env.n_hist, state_dependent_log_std=state_dependent_log_std, hidden=hidden, activation=activation,
+                             vf_share_layers=vf_share_layers)
     from . import checkpoint as CK
     resumable = CK.check_resumable(checkpoint_dir, chkpt_freq, restore, world=world, allreduce=allreduce, recorder=recorder)
     ck_state = None
@@ -557,7 +577,7 @@ def train_fused(env, iters=4, horizon=64, lr=5e-5, epochs=4, reward_scale=None, 
         run_args = {"markets": int(N), "agents": int(A), "horizon": int(T), "chains": int(chains), "objective": {k: float(v) for k, v in obj.items()},
                     "hidden": [int(h) for h in hidden_widths(policy.theta)], "state_dependent_log_std": bool(has_log_std_head(policy.theta)),
                     "epochs": int(epochs), "lr": float(lr), "minibatch": int(minibatch), "seed": int(seed), "episode_metrics": bool(episode_metrics)}
-        run_args = CK.with_activation(run_args, policy.activation)
+        run_args = CK.with_vf_share_layers(CK.with_activation(run_args, policy.activation), getattr(policy, "vf_share_layers", False))
         run_id = CK.new_run_id()
         if restore:
             ck_path = CK.resolve_restore(checkpoint_dir, restore)
@@ -646,7 +666,7 @@ def train_fused(env, iters=4, horizon=64, lr=5e-5, epochs=4, reward_scale=None, 
 
 
 def train(env, iters=4, horizon=64, lr=5e-5, epochs=4, reward_scale=1e-3, seed=0, log=print, use_graph=True, rollout_hook=None, amp=None,
-          shared_obs=True, activation="tanh"):
+          shared_obs=True, activation="tanh", vf_share_layers=False):
     """On-device PPO over a CDAVecEnv-shaped env. Returns per-iteration stats (incl. agent-steps/s).
     rollout_hook(iteration, step, env_actions, obs, reward, terminated, truncated): called after every env step with the
     five [N,A] action tensors the policy produced and the step's output tensors (device tensors; clone what you keep).
@@ -654,13 +674,13 @@ def train(env, iters=4, horizon=64, lr=5e-5, epochs=4, reward_scale=1e-3, seed=0
     use_graph (HIP devices): the rollout step is replayed from a captured HIP graph - the whole step (policy, env step, buffer writes:
     _capture_rollout_step) on an auto_reset env without a rollout_hook, else the policy step alone (_capture_policy_step) - and from
     the second iteration on the update's minibatch steps are too (_GraphedUpdate).
-    activation: the hidden activation of the network (ActorCritic)."""
+    activation: the hidden activation of the network (ActorCritic); vf_share_layers: RLlib's shared trunk (ActorCritic)."""
     torch.manual_seed(seed)
     dev = env.obs.device
     amp = (dev.type == "cuda") if amp is None else bool(amp)
     N, A = env.n_markets, env.num_agents
     per_row = A if shared_obs else 1
-    model = ActorCritic(env.obs_dim, activation=activation).to(dev)
+    model = ActorCritic(env.obs_dim, activation=activation, vf_share_layers=vf_share_layers).to(dev)
     hip = dev.type == "cuda"
     opt = torch.optim.Adam(model.parameters(), lr=lr, fused=hip, capturable=hip and bool(use_graph))     # one kernel per step instead of one per tensor
     env.reset(seed=seed)
@@ -769,6 +789,8 @@ def main(argv=None):
     p.add_argument("--fcnet-hiddens", type=int, nargs=2, default=(256, 256), metavar=("H1", "H2"), help="fused loop: the two hidden widths (config/train_config.json:49), <= 256 each")
     p.add_argument("--fcnet-activation", choices=("tanh", "relu", "elu", "linear"), default="tanh",
                    help="the hidden activation of both networks (config/train_config.json:50; both loops; not tanh: the rollout takes two launches per step)")
+    p.add_argument("--vf-share-layers", action="store_true",
+                   help="one trunk for policy and value (RLlib's vf_share_layers, config/train_config.json:51; both loops; the rollout takes two launches per step)")
     p.add_argument("--log-std-head", action="store_true", help="fused loop: the state-dependent log-std head (RLlib's default module for Box actions) instead of a free log_std vector")
     p.add_argument("--objective", choices=("ppo", "rllib"), default="ppo", help="fused loop: PPO_DEFAULTS, or RLLIB_DEFAULTS = the objective the reference's RLlib run optimises "
                                                                               "(clip 0.3, lambda 1, vf coeff 1, entropy 0, vf clip 10, adaptive KL penalty, no gradient clipping, truncation bootstrap)")
@@ -798,12 +820,12 @@ def main(argv=None):
         raise SystemExit("--save needs the fused loop (the legacy loop's network is a PyTorch module)")
     if args.legacy:
         _, hist = train(env, iters=args.iters, horizon=args.horizon, amp=not args.fp32_update, shared_obs=not args.per_sample_forward, use_graph=not args.no_graphs,
-                        activation=args.fcnet_activation)
+                        activation=args.fcnet_activation, vf_share_layers=args.vf_share_layers)
     else:
         trained, hist = train_fused(env, iters=args.iters, horizon=args.horizon, use_graph=not args.no_graphs, chains=args.chains,
                               objective=RLLIB_DEFAULTS if args.objective == "rllib" else None, state_dependent_log_std=args.log_std_head, hidden=tuple(args.fcnet_hiddens),
                               checkpoint_dir=args.checkpoint_dir, chkpt_freq=args.chkpt_freq, chkpt_keep=args.chkpt_keep, restore=args.restore,
-                              iters_is_delta=args.iters_is_delta, activation=args.fcnet_activation)
+                              iters_is_delta=args.iters_is_delta, activation=args.fcnet_activation, vf_share_layers=args.vf_share_layers)
     flags = env.flags()
     _, bad = env.nav_conservation()
     tail = hist[2:] if len(hist) >= 4 else (hist[1:] or hist)

@@ -49,6 +49,12 @@ extern "C" {
 /* Hidden activations (RLlib's fcnet_activation) the entry points are compiled for besides tanh, the default and the unsuffixed names: every depth above and 4 again
  * under <name>[_h<H>]_<act> (cda_mlp_forward_relu, cda_mlp_forward_backward_h6_elu, ...: same signatures; csrc/cda_mlp_variant.h).  Python: mlp.layout(n_hist, activation). */
 #define CDA_MLP_ACT_VARIANTS "relu elu linear"
+/* The shared-trunk network (RLlib's vf_share_layers = True: ONE 168 -> 256 -> 256 encoder, the pi heads and the value head both read its last layer) is compiled
+ * for every depth and activation above, 4 and tanh included, under <name>[_h<H>][_<act>]_vfs (cda_mlp_forward_vfs, cda_mlp_wgrad_h6_elu_vfs, ...: same signatures,
+ * the same theta / wb / slab / Adam sizes).  In such a network W1 / b1 rows 256..511, W2 block 1 and b2 256..511 (the value half) are exact zeros and stay so (the
+ * gradient of every value-half entry is written as 0), and Wo row 24 reads the FIRST half: it is packed into half 0 of Wo / Wo^T, half 1 of both is zero.
+ * The kernels skip the dead half (the fused update, the rollout and evaluation forwards, the weight gradients).  Python: mlp.layout(n_hist, activation, vf_share_layers). */
+#define CDA_MLP_VFS_VARIANTS "vfs"
 #define CDA_MLP_OBS       (42 * CDA_MLP_HIST)                       /* 168 */
 #define CDA_MLP_KX        ((CDA_MLP_OBS + 15) / 16 * 16)             /* 176: the observation padded to MFMA k-steps of 16 */
 #define CDA_MLP_XTILES    ((CDA_MLP_KX + 31) / 32)                   /* 6: ... and to feature tiles of 32 in the packed layout */
