@@ -150,6 +150,7 @@ class SnapshotHeader(C.Structure):
                 ("cfg", Config), ("reserved", C.c_uint8 * 88)]
 
 
+TAPE_WORDS = 8                   # include/cda.h CDA_TAPE_WORDS: int32 words of a cda_tape_record
 SNAP_MAGIC = 0x53414443          # "CDAS"
 SNAP_VERSION = 1
 

@@ -604,7 +604,10 @@ __device__ __forceinline__ void settle_fill(Lds& L, int tr, int counter, int32_t
 // TAILS: the general build (a side may continue in the HBM tier, "The HBM tier of the book" above).  The hot kernels are
 // compiled with TAILS = false - exactly the tile-only code - and hand a market whose book may outgrow its tile during the step
 // to the general build BEFORE they touch it (cda_kernels.inc, market_is_cold).
-template <bool TAILS, bool LAZY_POSVAL>
+// TAPE: the tape-writing instances (include/cda.h cda_tape_enable) append one record per fill to the market's ring, here, where price,
+// quantity, both parties, the resting order's id and what is left of it are at hand - self-trades included: the reference appends its
+// transaction_record before _process_trades looks at the parties (orderbook.py:108-140).  One lane, two 16-byte vector stores.
+template <bool TAILS, bool LAZY_POSVAL, bool TAPE = false>
 __device__ __forceinline__ int32_t match(Lds& L, Mkt& m, int tr, int own_side, int32_t qty, int32_t limit, int lane) {
     int opp = own_side ^ 1;
     Book& bk = L.book;
@@ -615,6 +618,16 @@ __device__ __forceinline__ int32_t match(Lds& L, Mkt& m, int tr, int own_side, i
             int32_t p = bk.price[opp][h];
             if (limit >= 0) { if (own_side == S_BID ? !(limit >= p) : !(limit <= p)) break; }
             int32_t rq = bk.qty[opp][h], c = oo_owner(bk.oo[opp][h]), f;
+            if constexpr (TAPE) {
+                if (lane == 0) {
+                    uint4* rec = m.tape_ring + 2 * (size_t)(m.tape_pos & m.tape_mask);
+                    const int32_t fq = qty < rq ? qty : rq;
+                    rec[0] = make_uint4((uint32_t)m.lob_time, (uint32_t)p, (uint32_t)fq, (uint32_t)c);
+                    rec[1] = make_uint4((uint32_t)bk.oo[opp][h] >> 4, (uint32_t)(qty < rq ? rq - qty : -1), (uint32_t)tr,
+                                        ((uint32_t)m.t_step << 2) | ((uint32_t)own_side << 1) | (uint32_t)opp);
+                }
+                m.tape_pos += 1; m.tape_new += 1;
+            }
             if (qty < rq) { f = qty; bk.qty[opp][h] = rq - qty; qty = 0; CDA_WSYNC(); }    // all lanes store the same value
             else { f = rq; qty -= rq; h++; }
             m.has_trade = 1; m.last_trade_price = p;
@@ -697,7 +710,7 @@ __device__ __forceinline__ bool order_approved(Lds& L, const Mkt& m, int tr, int
 // __modify_limit_order / _cancel_limit_order (:189-252) and OrderBook.process_order / modify_order /
 // cancel_order (orderbook/orderbook.py:33-59, :196-266).  Structured so that the matching loop has ONE
 // call site: the type-specific part only decides what (if anything) is matched and what may rest.
-template <bool TAILS, bool LAZY_POSVAL>
+template <bool TAILS, bool LAZY_POSVAL, bool TAPE = false>
 __device__ __forceinline__ void place_order(Lds& L, Mkt& m, int tr, int type, int side, int32_t size, int32_t price, int lane) {
     if (side == S_NONE) return;
     TACC_BEGIN();
@@ -763,7 +776,7 @@ __device__ __forceinline__ void place_order(Lds& L, Mkt& m, int tr, int type, in
     if (m.next_oid >= (1 << 27)) m.flags |= CDA_FLAG_INT_OVERFLOW;
     TACC_END(m, 4);
     if (do_match) {
-        int32_t left = match<TAILS, LAZY_POSVAL>(L, m, tr, side, size, m_limit, lane);
+        int32_t left = match<TAILS, LAZY_POSVAL, TAPE>(L, m, tr, side, size, m_limit, lane);
         TACC_END(m, 2);
         if (left > 0 && can_rest) {
             const int nown = mkt_n(m, side);

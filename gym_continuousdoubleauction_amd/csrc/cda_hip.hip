@@ -630,7 +630,12 @@ struct cda_env {
     MktRow* rows;            // the per-market parameter table (device): MktRow[n_markets + CDA_ROW_PAD]; P.rows points at it
     cda_market_params* rows_host;   // what cda_set_market_params last wrote for each market (the config's row until then)
     uint32_t* snap_flag;     // cda_snapshot_restore: the check pass's verdict (allocated at the first restore)
+    TapeArgs tape;           // cda_tape_enable: the trade tape's rings and counters (ring == NULL: off - the launches are then the ones of an env without a tape)
 };
+// csrc/cda_tape.inc (included at the end): the tape's counters follow a reset / a restore queued on `stream`; no-ops while the tape is off
+static int tape_after_reset(cda_env* e, int32_t first, int32_t n, const uint8_t* mask, hipStream_t stream);
+static int tape_after_restore(cda_env* e, int32_t first, int32_t n, hipStream_t stream);
+static void tape_free(cda_env* e);
 static inline int32_t handback_stride_of(int32_t num_agents) { return (CDA_SNAPSHOT_DIM * 4 + num_agents * 8 + 3 + 7) & ~7; }
 
 static thread_local char g_err[256] = "";
@@ -835,6 +840,7 @@ int cda_destroy(cda_env* e) {
     (void)hipFree(e->arena);
     if (e->em_partials) (void)hipFree(e->em_partials);
     if (e->snap_flag) (void)hipFree(e->snap_flag);
+    tape_free(e);
     if (e->rows) (void)hipFree(e->rows);
     free(e->rows_host);
     free(e);
@@ -879,7 +885,7 @@ int cda_reset_range(cda_env* e, int32_t first_market, int32_t n_markets, const u
     LAUNCH_CAP(e, k_reset, grid_for(n_markets), dim3(64 * CDA_WPB), smem_for(e, CDA_WPB), (hipStream_t)stream, e->arena, e->P, seeds, mask, obs_out,
                        (int)first_market, (int)(first_market + n_markets), e->handback, handback_stride_of(e->P.cfg.num_agents), 0, FinCapture{NULL, NULL, NULL, 0});
     HIPCHK(hipGetLastError());
-    return CDA_OK;
+    return tape_after_reset(e, first_market, n_markets, mask, (hipStream_t)stream);
 }
 int cda_reset(cda_env* e, const uint64_t* seeds, const uint8_t* mask, float* obs_out, void* stream) {
     if (!e) return CDA_ERR_INVALID;
@@ -896,7 +902,14 @@ static int launch_step(cda_env* e, int32_t first, int32_t n, const StepArgs& S0,
                             else hipLaunchKernelGGL((cda::ns::k_step<true, false>), grid_for(n), dim3(64 * CDA_WPB), smem, stream, K); } \
         else { if (tally) hipLaunchKernelGGL((cda::ns::k_step<false, true>), grid_for(n), dim3(64 * CDA_WPB), smem, stream, K); \
                else hipLaunchKernelGGL((cda::ns::k_step<false, false>), grid_for(n), dim3(64 * CDA_WPB), smem, stream, K); } } while (0)
-    if (e->cap == 512) CDA_LAUNCH_STEP(cap512); else CDA_LAUNCH_STEP(cap256);
+    // the trade tape is on: the instances that write it (k_tstep: the tape's block behind k_step's arguments; the tallies by the market's ST_EP_ON bit)
+#define CDA_LAUNCH_TSTEP(ns) do { \
+        cda::ns::TStepKernArgs KT; KT.K.arena = e->arena; KT.K.P = e->P; KT.K.S = S0; KT.K.S.first_market = first; KT.K.S.end_market = first + n; KT.T = e->tape; \
+        if (KT.K.S.has_info) hipLaunchKernelGGL((cda::ns::k_tstep<true>), grid_for(n), dim3(64 * CDA_WPB), smem, stream, KT); \
+        else hipLaunchKernelGGL((cda::ns::k_tstep<false>), grid_for(n), dim3(64 * CDA_WPB), smem, stream, KT); } while (0)
+    if (e->tape.ring) { if (e->cap == 512) CDA_LAUNCH_TSTEP(cap512); else CDA_LAUNCH_TSTEP(cap256); }
+    else if (e->cap == 512) CDA_LAUNCH_STEP(cap512); else CDA_LAUNCH_STEP(cap256);
+#undef CDA_LAUNCH_TSTEP
 #undef CDA_LAUNCH_STEP
     HIPCHK(hipGetLastError());
     // auto_reset: in the info-less kernel a market whose episode ended resets itself as the kernel's last act (reset_after_step in
@@ -907,6 +920,7 @@ static int launch_step(cda_env* e, int32_t first, int32_t n, const StepArgs& S0,
                            (const uint64_t*)NULL, (const uint8_t*)e->done_buf, S0.obs_out, (int)first, (int)(first + n),
                            e->handback, handback_stride_of(e->P.cfg.num_agents), 1, FinCapture{S0.fin_obs, S0.fin_count, S0.fin_index_out, S0.fin_cap});
         HIPCHK(hipGetLastError());
+        return tape_after_reset(e, first, n, e->done_buf, stream);
     }
     return CDA_OK;
 }
@@ -1000,7 +1014,7 @@ static int grant_policy_step_lds(const cda_env* e) {
 int cda_policy_step_supported(const cda_env* e) {
     if (!e) return 0;
     const int lds = e->cap == 256 ? policy_step_lds(e) : 0;
-    return lds > 0 && lds <= 160 * 1024 && e->P.cfg.num_agents <= 8 && !e->handback;
+    return lds > 0 && lds <= 160 * 1024 && e->P.cfg.num_agents <= 8 && !e->handback && !e->tape.ring;      // (no k_policy_step instance writes the trade tape)
 }
 // ... and whether it pays: every workgroup of k_policy_step streams the whole network for its sixteen rows, so the one launch wins while all of the env's
 // workgroups are resident at once (N <= 16 x CUs: 4096 markets on an MI355X - policy in the loop 278 -> 301-308 M at 4096 x 4) and loses to the batched policy
@@ -1154,7 +1168,11 @@ int cda_run_random(cda_env* e, int32_t n_steps, uint64_t action_seed, uint64_t m
 #define CDA_LAUNCH_RUN(ns) do { cda::ns::RunKernArgs K; K.arena = e->arena; K.P = e->P; K.R = R; \
         if (e->P.lay.ep_on) hipLaunchKernelGGL(cda::ns::k_run_random<true>, grid_for(e->P.n_markets), dim3(64 * CDA_WPB), smem_for(e, CDA_WPB) + ZIG_LDS_BYTES, (hipStream_t)stream, K); \
         else hipLaunchKernelGGL(cda::ns::k_run_random<false>, grid_for(e->P.n_markets), dim3(64 * CDA_WPB), smem_for(e, CDA_WPB) + ZIG_LDS_BYTES, (hipStream_t)stream, K); } while (0)
-    if (e->cap == 512) CDA_LAUNCH_RUN(cap512); else CDA_LAUNCH_RUN(cap256);
+#define CDA_LAUNCH_TRUN(ns) do { cda::ns::TRunKernArgs KT; KT.K.arena = e->arena; KT.K.P = e->P; KT.K.R = R; KT.T = e->tape; \
+        hipLaunchKernelGGL(cda::ns::k_tape_run, grid_for(e->P.n_markets), dim3(64 * CDA_WPB), smem_for(e, CDA_WPB) + ZIG_LDS_BYTES, (hipStream_t)stream, KT); } while (0)
+    if (e->tape.ring) { if (e->cap == 512) CDA_LAUNCH_TRUN(cap512); else CDA_LAUNCH_TRUN(cap256); }
+    else if (e->cap == 512) CDA_LAUNCH_RUN(cap512); else CDA_LAUNCH_RUN(cap256);
+#undef CDA_LAUNCH_TRUN
 #undef CDA_LAUNCH_RUN
     HIPCHK(hipGetLastError());
     return CDA_OK;
@@ -1262,7 +1280,8 @@ int cda_place_order(cda_env* e, int32_t market, int32_t trader, int32_t type, in
     if (type < 0 || type > 3 || side < 0 || side > 1 || size < 1) return CDA_ERR_INVALID;
     if (type != 0 && price < 1) return CDA_ERR_INVALID;
     HIPCHK(hipSetDevice(e->device));
-    LAUNCH_CAP(e, k_place_order, dim3(1), dim3(64), smem_for(e, 1), 0, e->arena, e->P, market, trader, type, side, size, price);
+    if (e->tape.ring) LAUNCH_CAP(e, k_tape_place_order, dim3(1), dim3(64), smem_for(e, 1), 0, e->arena, e->P, market, trader, type, side, size, price, e->tape);
+    else LAUNCH_CAP(e, k_place_order, dim3(1), dim3(64), smem_for(e, 1), 0, e->arena, e->P, market, trader, type, side, size, price);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     return CDA_OK;
@@ -1574,3 +1593,5 @@ int64_t cda_state_bytes_per_market(const cda_env* e) { return e ? (int64_t)e->P.
 
 // device snapshot / restore of a market range (cda_snapshot_*): kernels and entry points
 #include "cda_snapshot.inc"
+// the trade tape (cda_tape_*): storage, the counters' upkeep around resets and restores, the read-out kernels and entry points
+#include "cda_tape.inc"

@@ -174,8 +174,29 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_reset(uint8_t* arena, Params P
 }
 
 
+// ---- trade tape: what a tape-writing instance does around the step ------------------------------------------------------------
+// tape_begin: where this market's next record goes (Mkt::tape_*); tape_finish: the records match() appended join the market's counters.  Only the
+// market's own wave touches its ring and its counters, between launches nobody does: no atomics.  `reset`: the launch resets the market behind this
+// step (the in-kernel auto reset) - the episode's count restarts and the episode number moves on; the ring is NOT cleared, the episode that just
+// ended stays readable until new fills overwrite it.
+__device__ __forceinline__ void tape_begin(const TapeArgs& T, int mi, Mkt& m) {
+    m.tape_ring = T.ring + (size_t)mi * (size_t)T.cap * 2;
+    m.tape_mask = T.cap - 1u;
+    // (a relaxed atomic load: a vector load that sees what this wave's earlier part of the launch wrote - k_tape_run hands over mid-episode)
+    m.tape_pos = (uint32_t)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(reinterpret_cast<const uint32_t*>(&T.meta[mi].n_total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    m.tape_new = 0;
+}
+__device__ __forceinline__ void tape_finish(const TapeArgs& T, int mi, const Mkt& m, bool reset, int lane) {
+    if (lane == 0) {
+        TapeMeta& h = T.meta[mi];
+        h.n_total += (int64_t)m.tape_new;
+        h.n_episode = reset ? 0 : h.n_episode + m.tape_new;
+        if (reset) { h.episode += 1; h.partial = 0; }
+    }
+}
+
 // phases 1-5: everything of a step that changes the market.  Returns the mask of agents that passed.
-template <bool TAILS>
+template <bool TAILS, bool TAPE = false>
 __device__ __forceinline__ uint32_t step_market(Lds& L, Mkt& m, const Params& P, int mi, const unsigned long long* zig_wi, const unsigned long long* zig_ki,
                                                 const LaneAction& in, unsigned long long* ph, int lane) {
     const int A = P.cfg.num_agents, tick = mrow(P, mi).tick_size;
@@ -284,7 +305,7 @@ __device__ __forceinline__ uint32_t step_market(Lds& L, Mkt& m, const Params& P,
         const int kk = (int)((perm >> (4 * i)) & 0xFull);                          // the shuffle's i-th pick from the arrival list
         const int tr = __ffsll((long long)__ballot(lane < CDA_MAX_AGENTS && ((act_mask >> (lane & 31)) & 1u) != 0 && arrival == kk)) - 1;
         int32_t tsp = L.act_tsp[tr], size = L.act_size[tr];
-        place_order<TAILS, true>(L, m, tr, tsp & 3, (tsp >> 2) & 3, size, (tsp >> 4) - 1, lane);     // mark_to_mkt below rewrites position_val
+        place_order<TAILS, true, TAPE>(L, m, tr, tsp & 3, (tsp >> 2) & 3, size, (tsp >> 4) - 1, lane);     // mark_to_mkt below rewrites position_val
     }
     PH_MARK(ph, 5);
     // 5. mark_to_mkt
@@ -341,7 +362,7 @@ struct StepKernArgs { uint8_t* arena; Params P; StepArgs S; };
 // TALLY (episode metrics, include/cda.h cda_episode_metrics_enable): 0 = this instance never tallies - the kernels an env launches while the metrics are off, i.e. every
 // measured number of bench.py: with the tally's code merely branched around, the hot kernels measured 1 % slower (+18 spilled scalars; profiles/r06/episode_metrics_cost.txt) -,
 // 1 = it always does (the instances launched while they are on), 2 = decided by the market's ST_EP_ON bit at run time (the out-of-line general build, one instance).
-template <bool INFO, bool TAILS, int TALLY>
+template <bool INFO, bool TAILS, int TALLY, bool TAPE = false>
 __device__ __forceinline__ void step_loaded(const Params& P, const StepArgs& S, const MarketPtrs& mp, Lds& L, Mkt& m, LaneAction in, uint8_t present,
                                             const unsigned long long* zig_wi, const unsigned long long* zig_ki, int mi, int lane, unsigned long long* ph) {
     const bool has_info = INFO && S.has_info != 0;   // <true> keeps the run-time test (its code is the one-kernel build's), <false> folds it away
@@ -349,7 +370,7 @@ __device__ __forceinline__ void step_loaded(const Params& P, const StepArgs& S, 
     in.pres = lane < A && (!S.present || present != 0);
     in.ord = S.present ? (int)present : 1;
     uint32_t pass_mask = 0;
-    if (!CDA_DBG_HAS(S, 1)) pass_mask = step_market<TAILS>(L, m, P, mi, zig_wi, zig_ki, in, ph, lane);
+    if (!CDA_DBG_HAS(S, 1)) pass_mask = step_market<TAILS, TAPE>(L, m, P, mi, zig_wi, zig_ki, in, ph, lane);
     else if (!CDA_DBG_HAS(S, 2)) mark_to_mkt(L, m, A, lane);
     // 6. prep_next_state (state_helper.py:80-92): new frame, history ring, stacked observation.  The frame is COMPUTED here and
     //    written behind the last decimal routine of phase 7: every out-of-line function starts with s_waitcnt vmcnt(0) - it would
@@ -510,6 +531,39 @@ __attribute__((noinline, cold)) __device__ int slow_step(const StepKernArgs* ker
     if constexpr (!INFO) { if (S.done_out && episode_over(m, P, mi)) return (m.status & ST_EP_ON) ? 2 : 1; }
     return 0;
 }
+// slow_step of the tape-writing kernels (k_tstep below): the same, with the market's tape opened and closed around the step (a routine of its own, not a shared body:
+// slow_step's code stays what it was)
+struct TStepKernArgs { StepKernArgs K; TapeArgs T; };    // K first: the cold paths read StepKernArgs where the kernel's arguments lie
+template <bool INFO>
+__attribute__((noinline, cold)) __device__ int slow_tstep(const TStepKernArgs* kernargs, int mi, int wave) {
+    const StepKernArgs& K = kernargs->K;
+    const Params& P = K.P;
+    const StepArgs& S = K.S;
+    const int lane = lane_id();
+    Lds& L = wave_lds(P, wave, ZIG_LDS_BYTES);
+    const unsigned long long* zig_wi = reinterpret_cast<const unsigned long long*>(cda_smem + DEC_TABLE_BYTES);
+    const unsigned long long* zig_ki = zig_wi + 256;
+    MarketPtrs mp = market_ptrs(K.arena, P, mi);
+    LaneAction in;
+    const size_t ab = (size_t)mi * (size_t)P.cfg.num_agents + (size_t)(lane < P.cfg.num_agents ? lane : 0);
+    in.cat = S.category[ab]; in.mean = S.size_mean[ab]; in.sigma = S.size_sigma[ab];
+    in.level = S.price[ab]; in.off = S.price_offset[ab]; in.pres = false; in.ord = 1;
+    const uint8_t present = *(S.present ? S.present + ab : reinterpret_cast<const uint8_t*>(S.category + ab));
+    Mkt m;
+#ifdef CDA_PHASE_TIMING
+    for (int i = 0; i < 30; i++) m.tacc[i] = 0;
+#endif
+    load_market<true>(mp, P, L, m, lane);
+#ifdef CDA_DEBUG_SKIP
+    m.dbg = S.dbg_skip;
+#endif
+    tape_begin(kernargs->T, mi, m);
+    step_loaded<INFO, true, 2, true>(P, S, mp, L, m, in, present, zig_wi, zig_ki, mi, lane, nullptr);
+    int over = 0;
+    if constexpr (!INFO) { if (S.done_out && episode_over(m, P, mi)) over = (m.status & ST_EP_ON) ? 2 : 1; }
+    tape_finish(kernargs->T, mi, m, over != 0, lane);
+    return over;
+}
 // what the info-less step kernels do with a market whose episode has just ended: the callback's episode end, then the reset.  Out of line and thin - ONE cold call
 // site in the kernel (every call site there costs the hot code spilled scalars), and the two routines it calls one after the other share its depth of scratch
 __attribute__((noinline, cold)) __device__ void episode_end_after_step(const StepKernArgs* kernargs, int mi, int wave, bool metrics) {
@@ -586,6 +640,55 @@ __global__ __launch_bounds__(64 * CDA_WPB, CDA_MIN_WAVES) CDA_VGPR_CAP_ATTR void
             if constexpr (TALLY) episode_end_after_step((const StepKernArgs*)__builtin_amdgcn_kernarg_segment_ptr(), mi, wave, true);
             else reset_after_step((const StepKernArgs*)__builtin_amdgcn_kernarg_segment_ptr(), mi, wave);      // (the metrics are off: the instance of every measured number)
         }
+    }
+}
+
+// k_step that also writes the trade tape (cda_tape_enable): what an env launches while its tape is on.  A kernel of its own name and arguments - the tape's block
+// lies behind k_step's -, so that with the tape off every launch runs the very instances it ran before the tape existed.  INFO as in k_step; the episode-metric tallies
+// are decided at run time by the market's ST_EP_ON bit (TALLY = 2, as in the general build): two instances per tile, not four.  Stages exactly as k_step does (see there).
+template <bool INFO>
+__global__ __launch_bounds__(64 * CDA_WPB, CDA_MIN_WAVES) CDA_VGPR_CAP_ATTR void k_tstep(TStepKernArgs KT) {
+    uint8_t* const arena = KT.K.arena;
+    const Params& P = KT.K.P;
+    const StepArgs& S = KT.K.S;
+    int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = lane_id();
+    int mi = S.first_market + (int)blockIdx.x * CDA_WPB + wave;
+    const bool live = mi < S.end_market;
+    const TablePrefetch tq = stage_tables_issue();
+    __builtin_amdgcn_sched_barrier(0);
+    const int mc = live ? mi : S.first_market;
+    MarketPtrs mp = market_ptrs(arena, P, mc);
+    const MarketPrefetch mq = load_market_issue<true>(mp, P, lane);
+    LaneAction in;
+    const size_t ab = (size_t)mc * (size_t)P.cfg.num_agents + (size_t)(lane < P.cfg.num_agents ? lane : 0);
+    in.cat = S.category[ab]; in.mean = S.size_mean[ab]; in.sigma = S.size_sigma[ab];
+    in.level = S.price[ab]; in.off = S.price_offset[ab]; in.pres = false; in.ord = 1;
+    const uint8_t present = *(S.present ? S.present + ab : reinterpret_cast<const uint8_t*>(S.category + ab));
+    stage_tables_commit(tq);
+    if (!live) return;
+    Lds& L = wave_lds(P, wave, ZIG_LDS_BYTES);
+    const unsigned long long* zig_wi = reinterpret_cast<const unsigned long long*>(cda_smem + DEC_TABLE_BYTES);
+    const unsigned long long* zig_ki = zig_wi + 256;
+    Mkt m;
+#ifdef CDA_PHASE_TIMING
+    for (int i = 0; i < 30; i++) m.tacc[i] = 0;
+#endif
+    load_market_finish<true, false>(mp, P, L, m, mq, lane);
+#ifdef CDA_DEBUG_SKIP
+    m.dbg = S.dbg_skip;
+#endif
+    if (__builtin_expect(market_is_cold(m, P), 0)) {
+        const int over = slow_tstep<INFO>((const TStepKernArgs*)__builtin_amdgcn_kernarg_segment_ptr(), mi, wave);
+        if constexpr (!INFO) { if (over) episode_end_after_step((const StepKernArgs*)__builtin_amdgcn_kernarg_segment_ptr(), mi, wave, over == 2); }
+        return;
+    }
+    tape_begin(KT.T, mi, m);
+    step_loaded<INFO, false, 2, true>(P, S, mp, L, m, in, present, zig_wi, zig_ki, mi, lane, nullptr);
+    bool over = false;
+    if constexpr (!INFO) over = S.done_out != nullptr && episode_over(m, P, mi);
+    tape_finish(KT.T, mi, m, over, lane);
+    if constexpr (!INFO) {
+        if (__builtin_expect(over, 0)) episode_end_after_step((const StepKernArgs*)__builtin_amdgcn_kernarg_segment_ptr(), mi, wave, (m.status & ST_EP_ON) != 0);
     }
 }
 
@@ -670,8 +773,12 @@ struct RunKernArgs { uint8_t* arena; Params P; RunArgs R; };
 // The episode loop of one market from iteration it0 on.  TAILS = false (the hot kernel) stops BEFORE a step its tile-only code
 // may not take (market_is_cold), writes the market back as it stands and returns that iteration; the general build then takes
 // over from the record (slow_run_random).  Returns -1 when the launch's work for this market is complete (outputs written).
-template <bool TAILS, int TALLY>
-__device__ __forceinline__ int run_random_part(uint8_t* arena, const Params& P, const RunArgs& R, int mi, int wave, int lane, int it0, double& ret, int& steps) {
+// TAPE (k_tape_run): the episode's fills go to the market's trade tape, *T (handed down explicitly: the general build is an out-of-line function and gets the
+// pointer from its caller, like its RunKernArgs)
+struct TRunKernArgs { RunKernArgs K; TapeArgs T; };
+template <bool TAILS, int TALLY, bool TAPE = false>
+__device__ __forceinline__ int run_random_part(uint8_t* arena, const Params& P, const RunArgs& R, int mi, int wave, int lane, int it0, double& ret, int& steps,
+                                               const TapeArgs* T = nullptr) {
     Lds& L = wave_lds(P, wave, ZIG_LDS_BYTES);
     const unsigned long long* zig_wi = reinterpret_cast<const unsigned long long*>(cda_smem + DEC_TABLE_BYTES);
     const unsigned long long* zig_ki = zig_wi + 256;
@@ -685,6 +792,7 @@ __device__ __forceinline__ int run_random_part(uint8_t* arena, const Params& P, 
         const MarketPrefetch q = load_market_issue<true>(mp, P, lane);
         load_market_finish<true, TAILS>(mp, P, L, m, q, lane);
     }
+    if constexpr (TAPE) tape_begin(*T, mi, m);
     float* hist = lds_hist(L, A);                           // the history ring stays in LDS for the whole episode
     int32_t* hist_raw = reinterpret_cast<int32_t*>(hist);
     int part_steps = 0, it = it0;
@@ -694,7 +802,7 @@ __device__ __forceinline__ int run_random_part(uint8_t* arena, const Params& P, 
         LaneAction in;
         in.pres = lane < A; in.ord = 1; in.cat = 0; in.level = 0; in.off = 0; in.mean = 0.0f; in.sigma = 0.0f;
         if (in.pres) cda_random_action(R.seed, R.market_base + (uint64_t)mi, (uint32_t)m.t_step, (uint32_t)lane, &in.cat, &in.mean, &in.sigma, &in.level, &in.off);
-        const uint32_t pass_mask = step_market<TAILS>(L, m, P, mi, zig_wi, zig_ki, in, nullptr, lane);
+        const uint32_t pass_mask = step_market<TAILS, TAPE>(L, m, P, mi, zig_wi, zig_ki, in, nullptr, lane);
         aggregate_levels<TAILS>(L, m, lane);
         // Nobody reads the observation while the episode runs: the ring keeps the RAW frame (the 2 x 2 x 10 level
         // aggregation and last_price, 41 integers) and the normalisation (f64 divisions, square roots, log, log1p) is
@@ -760,6 +868,7 @@ __device__ __forceinline__ int run_random_part(uint8_t* arena, const Params& P, 
     }
     const bool summarise = TALLY != 0 && (m.status & ST_EP_ON) && !handed && (term || trunc);    // the launch ended this market's episode: check and credit it here (a later reset must not)
     if (summarise) m.status |= ST_EP_SUMMARISED;
+    if constexpr (TAPE) tape_finish(*T, mi, m, false, lane);
     store_market<TAILS>(mp, P, L, m, lane);
     copy_words((uint32_t*)mp.hist, (const uint32_t*)hist, H * CDA_SNAPSHOT_DIM, lane);
     store_levels(mp, L, lane);
@@ -791,6 +900,31 @@ __global__ __launch_bounds__(64 * CDA_WPB, CDA_MIN_WAVES) CDA_VGPR_CAP_ATTR void
     }
 }
 
+// k_run_random with the trade tape (cda_tape_enable); the tallies by the market's ST_EP_ON bit, as in k_tstep
+__attribute__((noinline, cold)) __device__ int slow_tape_run(const TRunKernArgs* kernargs, int mi, int wave, int it0, int steps, double ret) {
+    const TRunKernArgs& KT = *kernargs;
+    return run_random_part<true, 2, true>(KT.K.arena, KT.K.P, KT.K.R, mi, wave, lane_id(), it0, ret, steps, &KT.T);
+}
+__global__ __launch_bounds__(64 * CDA_WPB, CDA_MIN_WAVES) CDA_VGPR_CAP_ATTR void k_tape_run(TRunKernArgs KT) {
+    int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = lane_id();
+    int mi = (int)blockIdx.x * CDA_WPB + wave;
+    zig_tables_init();
+    dec_tables_init();
+    if (mi >= KT.K.P.n_markets) return;
+    double ret = 0.0;
+    int steps = 0;
+    int it = run_random_part<false, 2, true>(KT.K.arena, KT.K.P, KT.K.R, mi, wave, lane, 0, ret, steps, &KT.T);
+    if (it >= 0) {
+        tail_fence();
+        it = slow_tape_run((const TRunKernArgs*)__builtin_amdgcn_kernarg_segment_ptr(), mi, wave, it, steps, ret);
+    }
+    if (__builtin_expect(it == -2, 0)) {
+        tail_fence();
+        const RunKernArgs* ka = (const RunKernArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+        episode_summarise(ka->arena, &ka->P, mi, &wave_lds(ka->P, wave, ZIG_LDS_BYTES).acc[0]);
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // test hooks and small kernels
 // ------------------------------------------------------------------------------------------
@@ -803,6 +937,19 @@ __global__ __launch_bounds__(64) void k_place_order(uint8_t* arena, Params P, in
     load_market(mp, P, lds1, m, lane);
     place_order<true, false>(lds1, m, tr, type, side, size, price, lane);
     m.status &= ~ST_LEVELS_VALID;                         // the cached aggregation no longer describes the book
+    store_market(mp, P, lds1, m, lane);
+}
+__global__ __launch_bounds__(64) void k_tape_place_order(uint8_t* arena, Params P, int mi, int tr, int type, int side, int size, int price, TapeArgs T) {
+    Lds& lds1 = wave_lds(P, 0);
+    int lane = lane_id();
+    dec_tables_init();
+    MarketPtrs mp = market_ptrs(arena, P, mi);
+    Mkt m;
+    load_market(mp, P, lds1, m, lane);
+    tape_begin(T, mi, m);
+    place_order<true, false, true>(lds1, m, tr, type, side, size, price, lane);
+    tape_finish(T, mi, m, false, lane);
+    m.status &= ~ST_LEVELS_VALID;
     store_market(mp, P, lds1, m, lane);
 }
 __global__ __launch_bounds__(64) void k_mark_to_mkt(uint8_t* arena, Params P, int mi) {

@@ -135,6 +135,17 @@ __device__ __forceinline__ ConstRow& mrow(const Params& P, int mi) { return ((Co
 // ... and for a kernel with one market per THREAD (k_init_arena, k_nav_conservation)
 __device__ __forceinline__ const MktRow& mrow_lane(const Params& P, int mi) { return P.rows[mi]; }
 
+// ---- trade tape (include/cda.h cda_tape_*): one record per fill, in a ring per market, outside the market record ----------------
+struct TapeMeta {                // 32 B per market
+    int64_t n_total;             // fills since the tape was enabled (the ring position is n_total % capacity)
+    int32_t n_episode;           // fills since the market's last reset = the reference's len(LOB.tape)
+    int32_t episode;             // resets since enable
+    int32_t partial;             // 1: the episode's head is missing (the market was restored from a snapshot); cleared by the next reset
+    int32_t pad[3];
+};
+static_assert(sizeof(TapeMeta) == 32, "TapeMeta layout");
+struct TapeArgs { uint4* ring; TapeMeta* meta; uint32_t cap; uint32_t pad; };      // ring: uint4[n_markets][cap][2]
+
 // ---- uniform (per-wave) market scalars kept in registers -----------------------------------
 struct Mkt {
     u128 rng_state, rng_inc;
@@ -148,6 +159,11 @@ struct Mkt {
     int32_t dbg;                 // debug: pieces of the order phase to leave out (tools/inst_count.sh); results are then wrong
 #endif
     int32_t fills;               // fills settled in the current step (issue priority of this wave grows with it)
+    // trade tape (TapeArgs below): set by tape_begin and touched by the tape-writing instances only (match<.., TAPE = true>) - in every other
+    // instance these four are dead and cost no register
+    uint4* tape_ring;            // this market's ring of CDA_TAPE_WORDS-word records
+    uint32_t tape_mask, tape_pos;        // capacity - 1; the next record's index (n_total, low word; the slot is tape_pos & tape_mask)
+    int32_t tape_new;            // records written since tape_begin (tape_finish adds them to the market's counters)
 #ifdef CDA_PHASE_TIMING
     unsigned long long tacc[30];    // debug: cycles in approval / find / match+settle / insert+remove / escrow+cancel, fills, ...; 14..23: inside a fill
                                     // (stamps of the lanes that take part), 24..29: per fill, wave-uniform (see TF_WAVE)

@@ -285,7 +285,7 @@ int cda_snapshot_restore(cda_env* e, int32_t first_market, const void* blob_dev,
     hipLaunchKernelGGL(k_snap_restore, dim3((unsigned)((n_markets + CDA_WPB - 1) / CDA_WPB)), dim3(64 * CDA_WPB), 0, st, e->arena, e->P, (int)first_market,
                        (const uint8_t*)blob_dev, (int)src_first, (int)n_markets, (int)(h.spill_cap == e->P.lay.spill_cap), obs_out);
     HIPCHK(hipGetLastError());
-    return CDA_OK;
+    return tape_after_restore(e, first_market, n_markets, st);      // (a blob carries no tape: the restored markets' records from here on are an episode's tail)
 }
 
 }  // extern "C"

@@ -427,6 +427,13 @@ class _DictSurface(_Base):
         return (observations, rewards, terminateds, truncateds, infos), lob_actions, pass_agents, bankrupt
 
 
+def _tape_of(vec, market):
+    from .tape import to_reference_records
+    if not vec.tape_enabled:
+        raise RuntimeError("the trade tape is off (it is opt-in): call enable_tape() before the episode whose fills you want to read")
+    return to_reference_records(vec.tape_episode(market))
+
+
 class CDAEnv(_DictSurface):
     def __init__(self, config=None, device="cuda:0"):
         super().__init__()
@@ -451,6 +458,19 @@ class CDAEnv(_DictSurface):
             self._hio = self._vec.bind_host_io()
         else:
             self._host = torch.empty(self._vec.packed.numel(), dtype=torch.uint8).pin_memory()
+
+    # -- the trade tape (OrderBook.tape, orderbook.py:108-140): off by default ---------------
+    def enable_tape(self, capacity=1024):
+        """Record every fill on the device from now on (CDAVecEnv.enable_tape); `capacity` bounds the records of one episode that `tape` can return."""
+        self._vec.enable_tape(capacity)
+
+    def disable_tape(self):
+        self._vec.disable_tape()
+
+    @property
+    def tape(self):
+        """The current episode's fills as the reference's env.LOB.tape holds them: a list of transaction_record dicts, newest last (tape.to_reference_records)."""
+        return _tape_of(self._vec, 0)
 
     # -- diagnostics some reference tests read --------------------------------------------
     @property
@@ -562,6 +582,17 @@ class CDAVecMultiAgentEnv(_DictSurface):
         self._info_lay = self._vec.info_layout
         self._host_io = _host_io_default() and int(groups) == 1 and bool(with_info)    # (see CDAEnv: kernel I/O on pinned host memory; single-launch envs)
         self._hio = None
+
+    def enable_tape(self, capacity=1024):
+        """Record every fill of every sub-env on the device from now on (CDAVecEnv.enable_tape; the tensor readers are on `self._vec`: drain_tape, tape_last)."""
+        self._vec.enable_tape(capacity)
+
+    def disable_tape(self):
+        self._vec.disable_tape()
+
+    def tape(self, i):
+        """Sub-env i's current episode as the reference's env.LOB.tape: transaction_record dicts, newest last."""
+        return _tape_of(self._vec, int(i))
 
     @property
     def vec(self):

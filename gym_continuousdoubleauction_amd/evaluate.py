@@ -59,14 +59,43 @@ def _horizon(total, cap=128):
     return 1
 
 
-def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="greedy", seed=0, groups=None, keep=None):
+def _tape_episodes(rows, offsets, before, after):
+    """The episode counter value (CDAVecEnv.tape_counts()["episode"]) of every record drained after a rollout chunk (nothing dropped); before / after: the
+    counters {episode, n_episode} read around the chunk.  A market whose counter did not move: that episode.  Otherwise its last n_episode rows are the current
+    episode's (exact: that is what the counter counts); if the counter moved by one, the rows before them are the episode that ended (exact as well); if it
+    moved by more (a chunk that spans several episodes) a new episode begins, going backwards, wherever the step index drops - exact unless an episode in
+    between had no fill at all."""
+    ep = np.zeros(len(rows), np.int32)
+    t = rows[:, 7] >> 2
+    for m in range(len(offsets) - 1):
+        a, b = int(offsets[m]), int(offsets[m + 1])
+        e0, e1 = int(before["episode"][m]), int(after["episode"][m])
+        if a == b:
+            continue
+        if e1 == e0:
+            ep[a:b] = e0
+            continue
+        k = min(int(after["n_episode"][m]), b - a)
+        ep[b - k:b] = e1
+        if b - k > a:
+            drops = np.diff(t[a:b - k]) < 0 if e1 > e0 + 1 else np.zeros(b - k - a - 1, bool)
+            ep[a:b - k] = (e1 - 1) - np.concatenate([np.cumsum(drops[::-1])[::-1], [0]])
+    return ep
+
+
+def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="greedy", seed=0, groups=None, keep=None, tape=None, tape_capacity=4096):
     """Play `policy` (a FusedPolicy or a policy file) on `env` (a CDAVecEnv with auto_reset) for episodes * max_step steps; return per-module results.
     opponents: None = self-play; else a list of "random", FusedPolicy objects or policy files, placed by slot_modules.  trained_slots: the policy's slots per
     market when there are opponents (default 1).  groups: rollout chains (default 4).  keep (a dict, optional): receives the RolloutChains object, the
     placement, the collected metric tables (agent table, env row) and host copies of every step's env actions (`actions`: category, size_mean, size_sigma,
     price, price_offset as [steps, N, A]) - what a replay needs.
     Every network opponent must have the policy's hidden activation and vf_share_layers setting (the bank's rows are launched by one object's kernels): ValueError
-    otherwise, raised before the opponent is loaded and before anything runs."""
+    otherwise, raised before the opponent is loaded and before anything runs.
+    tape (a path, optional): record every fill of the evaluated episodes on the device (CDAVecEnv.enable_tape, `tape_capacity` records per market, drained after every
+    rollout) and save them as an .npz (tape.save_tape): records i32 [K, 8] with, per record, `market`, `episode` (0 = the first evaluated) and the modules of both
+    parties (`init_module`, `counter_module`: indices into `module_names`, the keys of the result's "modules"), plus `dropped` per market (0 unless a market filled
+    more than tape_capacity times within one rollout: that raises RuntimeError instead of saving a tape with holes).  The env's tape must be OFF (ValueError
+    otherwise: enabling it here would wipe the caller's rings, counters and cursor, and stale every graph captured on the env); it is off again afterwards."""
     from .mlp import LEAGUE_RANDOM, FusedPolicy, PolicyBank, RolloutChains, read_policy
     if mode not in ("greedy", "sample"):
         raise ValueError(f"mode must be 'greedy' or 'sample' (got {mode!r})")
@@ -100,6 +129,12 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
     T = _horizon(total)
     prev_metrics = bool(getattr(env, "episode_metrics_on", False))
     env.enable_episode_metrics(True)                                    # before the chains are captured
+    if tape is not None and env.tape_enabled:
+        raise ValueError("evaluate(tape=...) needs an env whose trade tape is off: it enables a tape of its own for the evaluated episodes (disable_tape() first, or "
+                         "drain the running tape yourself with drain_tape(cursor=...))")
+    if tape is not None:
+        env.enable_tape(tape_capacity)                                  # (likewise: the chains' graphs hold the tape-writing step instances)
+    tape_parts, tape_dropped = [], np.zeros(N, np.int64)
     try:
         if opp is None:
             driver = pol
@@ -128,16 +163,36 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
         acts = [] if keep is not None else None
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
-        for _ in range(total // T):
+        for c in range(total // T):
+            before = {k: v.cpu().numpy() for k, v in env.tape_counts().items()} if tape is not None else None
+            if tape is not None and c == 0:
+                tape_ep0 = before["episode"].copy()                      # the first evaluated episode of every market
             buf = chains.run()
+            if tape is not None:
+                rows, off, dropped = (x.cpu().numpy() for x in env.drain_tape())
+                after = {k: v.cpu().numpy() for k, v in env.tape_counts().items()}
+                market = np.repeat(np.arange(N, dtype=np.int32), np.diff(off))
+                tape_parts.append((rows, market, _tape_episodes(rows, off, before, after) - tape_ep0[market]))
+                if int(dropped.sum()) > 0:                            # (rows are missing: neither the tape nor the ids derived from the counters could be trusted)
+                    raise RuntimeError(f"evaluate(tape=...): {int(dropped.sum())} fills were overwritten before they were drained - tape_capacity {tape_capacity} is "
+                                       f"too small for a rollout of {T} steps")
             if acts is not None:
                 acts.append({key: buf[key].cpu() for key in ("category", "size_mean", "size_sigma", "price", "price_offset")})
         torch.cuda.synchronize(dev)
         wall = time.perf_counter() - t0
         module_of = torch.from_numpy(modules).to(dev).contiguous()
         table, env_row = env.collect_episode_metrics(module_of=module_of, n_modules=len(names), clear=True)
+        if tape is not None:
+            from .tape import save_tape
+            rows = np.concatenate([p[0] for p in tape_parts]) if tape_parts else np.zeros((0, 8), np.int32)
+            market = np.concatenate([p[1] for p in tape_parts]) if tape_parts else np.zeros(0, np.int32)
+            save_tape(tape, rows, dropped=tape_dropped, market=market, episode=np.concatenate([p[2] for p in tape_parts]) if tape_parts else np.zeros(0, np.int32),
+                      init_module=modules[market, rows[:, 6]].astype(np.int32), counter_module=modules[market, rows[:, 3]].astype(np.int32),
+                      module_names=np.array(names), modules=modules.astype(np.int32))
     finally:
         env.enable_episode_metrics(prev_metrics)
+        if tape is not None:
+            env.disable_tape()
     table_h, env_h = table.cpu().numpy(), env_row.cpu().numpy()
     summary = summarise(table_h, env_h, module_names=names)
     check_nav_conservation(0, summary, strict=True)
@@ -174,6 +229,7 @@ def main(argv=None):
     p.add_argument("--sample", action="store_true", help="sample actions (the training kernels) instead of the greedy mode")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--out", default=None, help="also write the JSON result to this file")
+    p.add_argument("--tape", default=None, metavar="FILE.npz", help="record every fill of the evaluated episodes (the trade tape) and save the records with their market, episode and module ids")
     args = p.parse_args(argv)
     from .mlp import layout_of_params, read_policy
     from .vec_env import CDAVecEnv
@@ -182,7 +238,7 @@ def main(argv=None):
                     n_markets=args.markets, device="cuda:0", with_info=False)
     try:
         res = evaluate(env, args.policy, opponents=args.opponent, trained_slots=args.trained_slots, episodes=args.episodes,
-                       mode="sample" if args.sample else "greedy", seed=args.seed)
+                       mode="sample" if args.sample else "greedy", seed=args.seed, tape=args.tape)
     finally:
         env.close()
     res.pop("summary")

@@ -658,11 +658,16 @@ class RolloutChains:
                 self._enqueue(g, True)
             graphs.append(gr)
         self.graphs = graphs
+        # the graphs hold the step instances and arguments of the env's trade-tape setting as it is now (tape-writing kernels and the rings' addresses, or neither)
+        self._graph_tape_epoch = getattr(self.env, "tape_epoch", 0)
 
     def run(self):
         """one rollout of `horizon` steps; returns the buffer dict (views stay valid; the next run() overwrites them)"""
         dev = self.device
         cur = torch.cuda.current_stream(dev)
+        if self.graphs is not None and self._graph_tape_epoch != getattr(self.env, "tape_epoch", 0):
+            raise RuntimeError("the env's trade tape was enabled or disabled after this RolloutChains captured its graphs: they would replay the step kernels and "
+                               "tape buffers of the earlier setting - build a new RolloutChains")
         if not self._have_obs or self._env_epoch != getattr(self.env, "host_epoch", 0):
             # the very first rollout - and the first one after the markets were reset / stepped from the HOST (env.host_epoch) - starts from the env's own
             # observation tensor; every other rollout continues from its predecessor's last observation (the chains do not write env.obs)

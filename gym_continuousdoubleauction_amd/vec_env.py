@@ -38,6 +38,8 @@ class CDAVecEnv:
         self.per_market = False             # whether rows were ever written (a snapshot then carries its markets' rows)
         self.host_epoch = 0                 # bumped by every host-side call that changes the markets (reset / step / run_random / place_order / set_state): consumers that keep
                                             # their own copy of the observations across calls (mlp.RolloutChains) compare it to know when theirs is stale
+        self.tape_epoch = 0                 # bumped by enable_tape / disable_tape: graphs captured on this env's step launches hold the setting they were captured under
+        self._tape_cursor = None            # drain_tape's default cursor (i64 [N], device) while the tape is on
         self.num_agents = self.cfg_struct.num_agents
         self.n_hist = self.cfg_struct.n_hist
         self.obs_dim = self.n_hist * K.SNAPSHOT_DIM
@@ -537,6 +539,90 @@ class CDAVecEnv:
             check(lib().cda_episode_metrics_collect(self._h, module_of.data_ptr() if module_of is not None else None, int(n_modules), out[0].data_ptr(), out[1].data_ptr(),
                                                     1 if clear else 0, self._stream()), "cda_episode_metrics_collect")
         return out
+
+    # ------------------------------------------------------------------ the trade tape: every fill recorded on the device
+    @property
+    def tape_enabled(self):
+        return int(lib().cda_tape_capacity(self._h)) > 0
+
+    @property
+    def tape_capacity(self):
+        return int(lib().cda_tape_capacity(self._h))
+
+    def enable_tape(self, capacity=1024):
+        """From now on every fill of every market is appended to the market's ring of `capacity` records (a power of two) on the device - the reference's
+        OrderBook.tape (include/cda.h cda_tape_enable; tape.py for the record layout).  Off by default; counters and rings start empty, the default
+        drain cursor at 0.  Do not toggle it between the capture and the replay of a graph that holds this env's step launches (mlp.RolloutChains checks)."""
+        capacity = int(capacity)
+        if capacity < 1 or capacity & (capacity - 1):
+            raise ValueError(f"tape capacity must be a power of two, got {capacity}")
+        self.sync()
+        check(lib().cda_tape_enable(self._h, capacity), "cda_tape_enable")
+        self.tape_epoch += 1                                      # (captured graphs of this env's step launches are stale from here on)
+        self._tape_cursor = torch.zeros(self.n_markets, dtype=torch.int64, device=self.device)
+
+    def disable_tape(self):
+        self.sync()
+        check(lib().cda_tape_enable(self._h, 0), "cda_tape_enable")
+        self.tape_epoch += 1
+        self._tape_cursor = None
+
+    def _need_tape(self, what):
+        if not self.tape_enabled:
+            raise RuntimeError(f"{what} needs the trade tape: call enable_tape() first (it is off by default)")
+
+    def tape_counts(self):
+        """{'n_total' i64[N]: fills since enable_tape, 'n_episode' i32[N]: fills since the market's last reset (the reference's len(LOB.tape)), 'episode' i32[N]:
+        resets since enable_tape, 'partial' i32[N]: 1 = the episode's head is missing (the market was restored from a snapshot)}, device tensors."""
+        self._need_tape("tape_counts()")
+        self.join()
+        out = {"n_total": torch.empty(self.n_markets, dtype=torch.int64, device=self.device)}
+        for k in ("n_episode", "episode", "partial"):
+            out[k] = torch.empty(self.n_markets, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(lib().cda_tape_counts(self._h, out["n_total"].data_ptr(), out["n_episode"].data_ptr(), out["episode"].data_ptr(), out["partial"].data_ptr(),
+                                        self._stream()), "cda_tape_counts")
+        return out
+
+    def drain_tape(self, cursor=None):
+        """The streaming read: every market's records from its cursor on, oldest first, market after market -> (records i32 [K, 8] on the device, offsets i64 [N + 1]:
+        market i owns rows offsets[i] : offsets[i + 1], dropped i64 [N]: records the ring had overwritten before they were read).  `cursor`: an i64 [N] device
+        tensor of record numbers, advanced in place; None = the env's own, which starts at 0 with enable_tape."""
+        self._need_tape("drain_tape()")
+        cur = self._tape_cursor if cursor is None else cursor
+        assert cur.dtype == torch.int64 and cur.is_contiguous() and cur.numel() == self.n_markets and cur.device == self.device
+        self.join()
+        n = self.n_markets
+        with torch.cuda.device(self.device):
+            off = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+            dropped = torch.empty(n, dtype=torch.int64, device=self.device)
+            check(lib().cda_tape_offsets(self._h, 0, n, cur.data_ptr(), off.data_ptr(), dropped.data_ptr(), self._stream()), "cda_tape_offsets")
+            total = int(off[n].item())                  # the one 8-byte read
+            rec = torch.empty((total, K.TAPE_WORDS), dtype=torch.int32, device=self.device)
+            check(lib().cda_tape_pack(self._h, 0, n, cur.data_ptr(), off.data_ptr(), rec.data_ptr() if total else None, total, self._stream()), "cda_tape_pack")
+        return rec, off, dropped
+
+    def tape_last(self, k, first_market=0, n_markets=None):
+        """The last k records of each market's CURRENT episode, oldest first (what state_helper.py walks with tape_display_length) ->
+        (records i32 [n, k, 8], rows beyond the count zero; counts i32 [n]), device tensors."""
+        self._need_tape("tape_last()")
+        n = self.n_markets - int(first_market) if n_markets is None else int(n_markets)
+        if not (0 <= int(first_market) and n >= 1 and int(first_market) + n <= self.n_markets and int(k) >= 1):
+            raise ValueError(f"tape_last: range [{first_market}, {int(first_market) + n}) x {k} records is outside the env")
+        self.join()
+        with torch.cuda.device(self.device):
+            rec = torch.empty((n, int(k), K.TAPE_WORDS), dtype=torch.int32, device=self.device)
+            cnt = torch.empty(n, dtype=torch.int32, device=self.device)
+            check(lib().cda_tape_last(self._h, int(first_market), n, int(k), rec.data_ptr(), cnt.data_ptr(), self._stream()), "cda_tape_last")
+        return rec, cnt
+
+    def tape_episode(self, market=0):
+        """The current episode's records of one market, oldest first, as a host array i32 [n, 8] (at most the ring's capacity of them)."""
+        self._need_tape("tape_episode()")
+        n_ep = int(self.tape_counts()["n_episode"][int(market)].item())
+        k = max(1, min(n_ep, self.tape_capacity))
+        rec, cnt = self.tape_last(k, int(market), 1)
+        return rec[0, :int(cnt[0].item())].cpu().numpy()
 
     # ------------------------------------------------------------------ snapshots, forks and resumable runs
     def snapshot(self, first=0, n=None):

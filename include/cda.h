@@ -543,6 +543,49 @@ int cda_snapshot_check_header(const cda_env* env, const cda_snapshot_header* hea
 int cda_snapshot_restore(cda_env* env, int32_t first_market, const void* blob_dev, int64_t blob_bytes, int32_t src_first, int32_t n_markets,
                          float* obs_out, void* stream);
 
+/* ---- trade tape: every fill recorded on the device ------------------------------------------------------------------------------------
+ * The reference's order book keeps OrderBook.tape, one transaction_record per fill, appended in process_order_list (orderbook.py:108-140) -
+ * self-trades included - and read by everything that looks at executions rather than accounts (state_helper.py:148-156, tape_dump).
+ * cda_tape_enable(env, capacity): from now on the step launches of this env (cda_step*, cda_step_range*, cda_step_groups*, cda_run_random,
+ * cda_place_order; the general step that continues into the HBM tier of the book included) append one cda_tape_record per fill to a ring of
+ * `capacity` records per market, in memory of its own (capacity a power of two <= CDA_TAPE_CAP_MAX; 0 = off, and the memory is freed).  OFF by
+ * default; while it is off no launch runs a tape-writing instance (the instances an env without a tape launches carry no tape code).  While it is on cda_policy_step_supported answers 0
+ * (rollout chains take their two-launch path and record through the step kernel).  Synchronous (it waits for the device); do not toggle it
+ * between the capture and the replay of a graph that holds step launches.
+ * Per market: n_total (fills since enable; the ring slot of record j is j % capacity), n_episode (fills since the market's last reset = the
+ * reference's len(LOB.tape)), episode (resets since enable), partial.  A reset - cda_reset*, the device-side auto reset - zeroes n_episode, bumps
+ * episode and clears partial; it does NOT clear the ring: the episode that just ended stays readable until newer fills overwrite it.  Snapshots
+ * do not carry the tape: cda_snapshot_restore zeroes the restored markets' n_episode and sets partial = 1 (what follows is an episode's tail).
+ *   cda_tape_counts    n_total i64[N], n_episode i32[N], episode i32[N], partial i32[N] (device; each may be NULL).
+ *   cda_tape_offsets   the streaming read, first half: for market first + i everything from cursor_dev[i] (a record number; i64[n], device) to
+ *                      n_total that the ring still holds -> offsets_dev i64[n + 1] (exclusive scan of the counts; offsets[n] = records in all),
+ *                      dropped_dev i64[n] (may be NULL): records of [cursor, n_total) the ring had already overwritten.
+ *   cda_tape_pack      second half: the records, market by market, each market's oldest first, dense into records_out_dev
+ *                      [capacity_records][CDA_TAPE_WORDS] i32 (device, 16-B aligned, capacity_records >= offsets[n]); cursor_dev[i] := n_total.  The env
+ *                      must not be stepped between the two calls (stream order); a market whose run would not fit is left alone, cursor included.
+ *   cda_tape_last      the last k records of each market's CURRENT episode, oldest first -> records_out_dev [n][k][CDA_TAPE_WORDS] i32 (rows beyond
+ *                      the count are zero), counts_out_dev i32[n] (may be NULL): what state_helper.py walks with tape_display_length.
+ * CDA_ERR_UNSUPPORTED from the readers while the tape is off. */
+#define CDA_TAPE_WORDS   8
+#define CDA_TAPE_CAP_MAX (1 << 20)
+typedef struct cda_tape_record {       /* transaction_record of orderbook.py:108-140 */
+    int32_t time;                      /* 'time' = 'timestamp': LOB.time at the fill */
+    int32_t price;                     /* 'price', as the book holds it (ticks x tick_size) */
+    int32_t quantity;                  /* 'quantity' */
+    int32_t counter_id;                /* counter_party['ID']: the resting order's trader */
+    int32_t counter_order_id;          /* counter_party['order_id'] */
+    int32_t counter_left;              /* counter_party['new_book_quantity']; -1 where the reference stores None (the resting order was consumed) */
+    int32_t init_id;                   /* init_party['ID']: the incoming order's trader (== counter_id in a self-trade) */
+    int32_t sides_step;                /* bit 0: counter_party['side'] (0 bid, 1 ask); bit 1: init_party['side']; bits 2..: the env step index t of the episode */
+} cda_tape_record;
+int cda_tape_enable(cda_env* env, int64_t capacity_records);
+int64_t cda_tape_capacity(const cda_env* env);
+int cda_tape_counts(cda_env* env, int64_t* n_total_dev, int32_t* n_episode_dev, int32_t* episode_dev, int32_t* partial_dev, void* stream);
+int cda_tape_offsets(cda_env* env, int32_t first_market, int32_t n_markets, const int64_t* cursor_dev, int64_t* offsets_dev, int64_t* dropped_dev, void* stream);
+int cda_tape_pack(cda_env* env, int32_t first_market, int32_t n_markets, int64_t* cursor_dev, const int64_t* offsets_dev, void* records_out_dev,
+                  int64_t capacity_records, void* stream);
+int cda_tape_last(cda_env* env, int32_t first_market, int32_t n_markets, int32_t k, void* records_out_dev, int32_t* counts_out_dev, void* stream);
+
 /* ---- per-market parameters: many configurations in one env ----------------------------------------------------------------------------
  * Every market reads the fields below from a row of its own (a device table every env has; cda_create fills each row from the config).  The
  * config's other fields - num_agents, n_hist, book_capacity, book_spill, auto_reset - set shapes, memory and kernel choice and hold for the
