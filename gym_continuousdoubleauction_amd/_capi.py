@@ -151,6 +151,8 @@ class SnapshotHeader(C.Structure):
 
 
 TAPE_WORDS = 8                   # include/cda.h CDA_TAPE_WORDS: int32 words of a cda_tape_record
+TAPE_BAR_WORDS = 12              # int32 words of a cda_tape_bar
+TAPE_EPISODES = {"current": 0, "previous": 1}      # CDA_TAPE_CURRENT, CDA_TAPE_PREVIOUS
 SNAP_MAGIC = 0x53414443          # "CDAS"
 SNAP_VERSION = 1
 

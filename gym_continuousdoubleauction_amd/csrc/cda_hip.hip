@@ -1595,3 +1595,5 @@ int64_t cda_state_bytes_per_market(const cda_env* e) { return e ? (int64_t)e->P.
 #include "cda_snapshot.inc"
 // the trade tape (cda_tape_*): storage, the counters' upkeep around resets and restores, the read-out kernels and entry points
 #include "cda_tape.inc"
+// ... and the reductions over a remembered episode's records: price / volume bars, agent-to-agent flows
+#include "cda_tape_bars.inc"

@@ -177,8 +177,8 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_reset(uint8_t* arena, Params P
 // ---- trade tape: what a tape-writing instance does around the step ------------------------------------------------------------
 // tape_begin: where this market's next record goes (Mkt::tape_*); tape_finish: the records match() appended join the market's counters.  Only the
 // market's own wave touches its ring and its counters, between launches nobody does: no atomics.  `reset`: the launch resets the market behind this
-// step (the in-kernel auto reset) - the episode's count restarts and the episode number moves on; the ring is NOT cleared, the episode that just
-// ended stays readable until new fills overwrite it.
+// step (the in-kernel auto reset) - the episode's count restarts (and is remembered as n_prev) and the episode number moves on; the ring is NOT cleared,
+// the episode that just ended stays readable until new fills overwrite it.
 __device__ __forceinline__ void tape_begin(const TapeArgs& T, int mi, Mkt& m) {
     m.tape_ring = T.ring + (size_t)mi * (size_t)T.cap * 2;
     m.tape_mask = T.cap - 1u;
@@ -190,8 +190,9 @@ __device__ __forceinline__ void tape_finish(const TapeArgs& T, int mi, const Mkt
     if (lane == 0) {
         TapeMeta& h = T.meta[mi];
         h.n_total += (int64_t)m.tape_new;
-        h.n_episode = reset ? 0 : h.n_episode + m.tape_new;
-        if (reset) { h.episode += 1; h.partial = 0; }
+        const int32_t n_ep = h.n_episode + m.tape_new;
+        h.n_episode = reset ? 0 : n_ep;
+        if (reset) { h.n_prev = n_ep; h.prev_partial = h.partial; h.episode += 1; h.partial = 0; }     // (the last step's fills belong to the episode that ends)
     }
 }
 

@@ -141,7 +141,9 @@ struct TapeMeta {                // 32 B per market
     int32_t n_episode;           // fills since the market's last reset = the reference's len(LOB.tape)
     int32_t episode;             // resets since enable
     int32_t partial;             // 1: the episode's head is missing (the market was restored from a snapshot); cleared by the next reset
-    int32_t pad[3];
+    int32_t n_prev;              // fills of the episode that ended at the market's last reset: records [n_total - n_episode - n_prev, n_total - n_episode)
+    int32_t prev_partial;        // `partial` as it stood when that episode ended
+    int32_t pad[1];
 };
 static_assert(sizeof(TapeMeta) == 32, "TapeMeta layout");
 struct TapeArgs { uint4* ring; TapeMeta* meta; uint32_t cap; uint32_t pad; };      // ring: uint4[n_markets][cap][2]

@@ -7,8 +7,10 @@
 // k_place_order while its tape is on, and never otherwise.  Per market, TapeMeta (cda_market.hpp): n_total, n_episode, episode, partial.
 //
 //   reset (cda_reset*, the auto-reset pass behind a step with info tensors: k_tape_episode behind k_reset, same mask; the in-kernel auto reset:
-//   tape_finish)                    n_episode = 0, episode += 1, partial = 0.  The ring is NOT cleared: the episode that just ended stays readable.
-//   cda_snapshot_restore            n_episode = 0, partial = 1 (the blob carries no tape: what follows is an episode's tail).
+//   tape_finish)                    n_prev = n_episode, n_episode = 0, episode += 1, partial = 0.  The ring is NOT cleared: the episode that just ended
+//                                   stays readable, and n_prev says where it lies (tape_span below).
+//   cda_snapshot_restore            n_episode = 0, n_prev = 0, partial = 1 (the blob carries no tape: what follows is an episode's tail).
+// The reductions over an episode's records (price / volume bars, agent-to-agent flows) are in cda_tape_bars.inc.
 //
 // The readers below are one thread per market (counts), one workgroup (the offset scan) or one wave per market (the copies: a record is two 16-byte
 // words, lane l moves word l of the market's run - contiguous in the ring up to its wrap, contiguous in the output).
@@ -18,14 +20,15 @@ static_assert(sizeof(cda_tape_record) == CDA_TAPE_WORDS * 4 && sizeof(cda_tape_r
 __global__ __launch_bounds__(256) void k_tape_episode(TapeMeta* meta, const uint8_t* mask, int first, int end) {
     const int mi = first + (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (mi >= end || (mask && !mask[mi])) return;
+    meta[mi].n_prev = meta[mi].n_episode; meta[mi].prev_partial = meta[mi].partial;
     meta[mi].n_episode = 0; meta[mi].episode += 1; meta[mi].partial = 0;
 }
 __global__ __launch_bounds__(256) void k_tape_partial(TapeMeta* meta, int first, int end) {
     const int mi = first + (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (mi >= end) return;
-    meta[mi].n_episode = 0; meta[mi].partial = 1;
+    meta[mi].n_episode = 0; meta[mi].partial = 1; meta[mi].n_prev = 0; meta[mi].prev_partial = 0;
 }
-__global__ __launch_bounds__(256) void k_tape_counts(const TapeMeta* meta, int n, long long* n_total, int32_t* n_episode, int32_t* episode, int32_t* partial) {
+__global__ __launch_bounds__(256) void k_tape_counts(const TapeMeta* meta, int n, long long* n_total, int32_t* n_episode, int32_t* episode, int32_t* partial, int32_t* n_prev) {
     const int mi = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (mi >= n) return;
     const TapeMeta h = meta[mi];
@@ -33,6 +36,7 @@ __global__ __launch_bounds__(256) void k_tape_counts(const TapeMeta* meta, int n
     if (n_episode) n_episode[mi] = h.n_episode;
     if (episode) episode[mi] = h.episode;
     if (partial) partial[mi] = h.partial;
+    if (n_prev) n_prev[mi] = h.n_prev;
 }
 
 // what market mi still holds of [cursor, n_total): the ring keeps the last `cap` records
@@ -90,17 +94,32 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_tape_pack(TapeArgs T, int firs
     tape_copy(out + 2 * o, T.ring + (size_t)mi * (size_t)T.cap * 2, T.cap, r.start, r.count, lane);
     if (lane == 0) cursor[k] = r.start + r.count;
 }
-// the last k records of the CURRENT episode, oldest first; rows beyond the count are zero
-__global__ __launch_bounds__(64 * CDA_WPB) void k_tape_last(TapeArgs T, int first, int n, int kmax, uint4* out, int32_t* counts) {
+// One of the two episodes a market remembers, in record numbers: the current one is [n_total - n_episode, n_total), the previous one (the episode that ended at
+// the market's last reset) the n_prev records before it; `start` / `count`: what the ring still holds of it (the ring keeps [n_total - cap, n_total)), `lost`: the
+// records of its head that are already overwritten, `partial`: its head was never recorded (the market had been restored from a snapshot).
+struct TapeSpan { long long start, count, lost; int partial; };
+__device__ __forceinline__ TapeSpan tape_span(const TapeMeta& h, uint32_t cap, int which) {
+    long long hi = h.n_total - (which == CDA_TAPE_PREVIOUS ? (long long)h.n_episode : 0ll);
+    long long lo = hi - (long long)(which == CDA_TAPE_PREVIOUS ? h.n_prev : h.n_episode);
+    if (lo < 0) lo = 0;
+    if (hi < lo) hi = lo;
+    long long floor = h.n_total - (long long)cap;
+    if (floor < lo) floor = lo;
+    if (floor > hi) floor = hi;
+    TapeSpan s;
+    s.start = floor; s.count = hi - floor; s.lost = floor - lo; s.partial = which == CDA_TAPE_PREVIOUS ? h.prev_partial : h.partial;
+    return s;
+}
+// the last k records of the current (or the previous) episode, oldest first; rows beyond the count are zero
+__global__ __launch_bounds__(64 * CDA_WPB) void k_tape_last(TapeArgs T, int first, int n, int which, int kmax, uint4* out, int32_t* counts) {
     const int w = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = (int)(threadIdx.x & 63);
     if (w >= n) return;
     const int mi = first + w;
     const TapeMeta h = T.meta[mi];
-    long long cnt = h.n_episode;
-    if (cnt > (long long)kmax) cnt = kmax;
-    if (cnt > (long long)T.cap) cnt = (long long)T.cap;
+    const TapeSpan sp = tape_span(h, T.cap, which);
+    const long long cnt = sp.count > (long long)kmax ? (long long)kmax : sp.count;
     uint4* dst = out + 2 * (size_t)w * (size_t)kmax;
-    tape_copy(dst, T.ring + (size_t)mi * (size_t)T.cap * 2, T.cap, h.n_total - cnt, cnt, lane);
+    tape_copy(dst, T.ring + (size_t)mi * (size_t)T.cap * 2, T.cap, sp.start + sp.count - cnt, cnt, lane);
     for (long long i = 2 * cnt + lane; i < 2 * (long long)kmax; i += WAVE) dst[i] = make_uint4(0u, 0u, 0u, 0u);
     if (counts && lane == 0) counts[w] = (int32_t)cnt;
 }
@@ -145,14 +164,17 @@ int cda_tape_enable(cda_env* e, int64_t capacity_records) {
 }
 int64_t cda_tape_capacity(const cda_env* e) { return e && e->tape.ring ? (int64_t)e->tape.cap : 0; }
 
-int cda_tape_counts(cda_env* e, int64_t* n_total_dev, int32_t* n_episode_dev, int32_t* episode_dev, int32_t* partial_dev, void* stream) {
+int cda_tape_counts_ex(cda_env* e, int64_t* n_total_dev, int32_t* n_episode_dev, int32_t* episode_dev, int32_t* partial_dev, int32_t* n_previous_dev, void* stream) {
     if (!e) return CDA_ERR_INVALID;
     if (!e->tape.ring) return CDA_ERR_UNSUPPORTED;
     HIPCHK(hipSetDevice(e->device));
     hipLaunchKernelGGL(k_tape_counts, dim3((unsigned)((e->P.n_markets + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const TapeMeta*)e->tape.meta, (int)e->P.n_markets,
-                       (long long*)n_total_dev, n_episode_dev, episode_dev, partial_dev);
+                       (long long*)n_total_dev, n_episode_dev, episode_dev, partial_dev, n_previous_dev);
     HIPCHK(hipGetLastError());
     return CDA_OK;
+}
+int cda_tape_counts(cda_env* e, int64_t* n_total_dev, int32_t* n_episode_dev, int32_t* episode_dev, int32_t* partial_dev, void* stream) {
+    return cda_tape_counts_ex(e, n_total_dev, n_episode_dev, episode_dev, partial_dev, NULL, stream);
 }
 int cda_tape_offsets(cda_env* e, int32_t first_market, int32_t n_markets, const int64_t* cursor_dev, int64_t* offsets_dev, int64_t* dropped_dev, void* stream) {
     if (!e || !cursor_dev || !offsets_dev || !range_ok(e, first_market, n_markets)) return CDA_ERR_INVALID;
@@ -174,14 +196,17 @@ int cda_tape_pack(cda_env* e, int32_t first_market, int32_t n_markets, int64_t* 
     HIPCHK(hipGetLastError());
     return CDA_OK;
 }
-int cda_tape_last(cda_env* e, int32_t first_market, int32_t n_markets, int32_t k, void* records_out_dev, int32_t* counts_out_dev, void* stream) {
-    if (!e || !records_out_dev || k < 1 || !range_ok(e, first_market, n_markets) || ((uintptr_t)records_out_dev & 15) != 0) return CDA_ERR_INVALID;
+int cda_tape_last_of(cda_env* e, int32_t first_market, int32_t n_markets, int32_t which, int32_t k, void* records_out_dev, int32_t* counts_out_dev, void* stream) {
+    if (!e || !records_out_dev || k < 1 || (which != CDA_TAPE_CURRENT && which != CDA_TAPE_PREVIOUS) || !range_ok(e, first_market, n_markets) || ((uintptr_t)records_out_dev & 15) != 0) return CDA_ERR_INVALID;
     if (!e->tape.ring) return CDA_ERR_UNSUPPORTED;
     HIPCHK(hipSetDevice(e->device));
     hipLaunchKernelGGL(k_tape_last, dim3((unsigned)((n_markets + CDA_WPB - 1) / CDA_WPB)), dim3(64 * CDA_WPB), 0, (hipStream_t)stream, e->tape, (int)first_market, (int)n_markets,
-                       (int)k, (uint4*)records_out_dev, counts_out_dev);
+                       (int)which, (int)k, (uint4*)records_out_dev, counts_out_dev);
     HIPCHK(hipGetLastError());
     return CDA_OK;
+}
+int cda_tape_last(cda_env* e, int32_t first_market, int32_t n_markets, int32_t k, void* records_out_dev, int32_t* counts_out_dev, void* stream) {
+    return cda_tape_last_of(e, first_market, n_markets, CDA_TAPE_CURRENT, k, records_out_dev, counts_out_dev, stream);
 }
 
 }  // extern "C"

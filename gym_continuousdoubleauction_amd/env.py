@@ -472,6 +472,14 @@ class CDAEnv(_DictSurface):
         """The current episode's fills as the reference's env.LOB.tape holds them: a list of transaction_record dicts, newest last (tape.to_reference_records)."""
         return _tape_of(self._vec, 0)
 
+    def tape_bars(self, bar_steps, n_bars=None, episode="current"):
+        """Price / volume bars of this market's current (or previous) episode, reduced on the device (CDAVecEnv.tape_bars): a structured array of tape.BAR_DTYPE,
+        one element per bar of `bar_steps` env steps."""
+        from .tape import as_bars
+        if not self._vec.tape_enabled:
+            raise RuntimeError("the trade tape is off (it is opt-in): call enable_tape() before the episode whose fills you want to read")
+        return as_bars(self._vec.tape_bars(bar_steps, n_bars, episode, 0, 1)[0][0])
+
     # -- diagnostics some reference tests read --------------------------------------------
     @property
     def last_price(self):

@@ -1,5 +1,7 @@
 """The trade tape on the host: the record layout of include/cda.h cda_tape_record as a numpy dtype, the reference's transaction_record dicts
-built from it, and an .npz container.  No device code here: CDAVecEnv.enable_tape / drain_tape / tape_last produce the int32 [K, 8] rows."""
+built from it, an .npz container, and the two reductions of CDAVecEnv.tape_bars / tape_flows stated in plain numpy for tapes that are already on the host
+(bars_from_records, flows_from_records).  No device code here but flows_by_module (torch, on whatever device the flows are): CDAVecEnv.enable_tape / drain_tape /
+tape_last produce the int32 [K, 8] rows."""
 from decimal import Decimal
 
 import numpy as np
@@ -10,6 +12,11 @@ RECORD_DTYPE = np.dtype([("time", "<i4"), ("price", "<i4"), ("quantity", "<i4"),
                          ("counter_left", "<i4"), ("init_id", "<i4"), ("sides_step", "<i4")])
 assert RECORD_DTYPE.itemsize == 4 * TAPE_WORDS
 FIELDS = RECORD_DTYPE.names
+BAR_WORDS = 12
+# one bar = twelve int32 words (cda_tape_bar)
+BAR_DTYPE = np.dtype([("open", "<i4"), ("high", "<i4"), ("low", "<i4"), ("close", "<i4"), ("n_trades", "<i4"), ("n_self", "<i4"),
+                      ("volume", "<i8"), ("buy_volume", "<i8"), ("notional", "<i8")])
+assert BAR_DTYPE.itemsize == 4 * BAR_WORDS
 SIDES = ("bid", "ask")
 
 
@@ -86,3 +93,65 @@ def load_tape(path):
     """the arrays save_tape wrote, as a dict (records as int32 [K, 8]; as_records() gives the named view)"""
     with np.load(path, allow_pickle=False) as z:
         return {k: z[k] for k in z.files}
+
+
+def as_bars(bars):
+    """structured view (BAR_DTYPE) of int32 [..., 12] bars as CDAVecEnv.tape_bars returns them: bars['open'], bars['volume'], ... of shape [...]"""
+    if hasattr(bars, "detach"):
+        bars = bars.detach().cpu().numpy()
+    bars = np.asarray(bars)
+    if bars.dtype == BAR_DTYPE:
+        return bars
+    bars = np.ascontiguousarray(bars, dtype=np.int32)
+    if bars.ndim < 1 or bars.shape[-1] != BAR_WORDS:
+        raise ValueError(f"bars must have shape [..., {BAR_WORDS}], got {bars.shape}")
+    return bars.view(BAR_DTYPE).reshape(bars.shape[:-1])
+
+
+def bars_from_records(rows, bar_steps, n_bars):
+    """Price / volume bars of ONE market's episode (rows in tape order): bar b covers the fills of env steps [b * bar_steps, (b + 1) * bar_steps); open / close are
+    the first / last of them, a bar without fills is all zeros.  -> (BAR_DTYPE [n_bars], number of rows whose bar index was >= n_bars and that were left out).
+    What CDAVecEnv.tape_bars computes on the device."""
+    r = as_rows(rows).astype(np.int64)
+    bar_steps, n_bars = int(bar_steps), int(n_bars)
+    if bar_steps < 1 or n_bars < 1:
+        raise ValueError("bar_steps and n_bars must be >= 1")
+    b = (r[:, 7] >> 2) // bar_steps
+    keep = b < n_bars
+    out = np.zeros(n_bars, BAR_DTYPE)
+    r, b = r[keep], b[keep]
+    for k in np.unique(b):
+        x = r[b == k]
+        price, qty = x[:, 1], x[:, 2]
+        out[k] = (price[0], price.max(), price.min(), price[-1], len(x), int((x[:, 3] == x[:, 6]).sum()), qty.sum(), qty[((x[:, 7] >> 1) & 1) == 0].sum(),
+                  (price * qty).sum())
+    return out, int((~keep).sum())
+
+
+def flows_from_records(rows, num_agents):
+    """Who traded with whom: int64 [A, A, 3], [init_id, counter_id] = (quantity, notional = price x quantity, fills) over ONE market's rows; the diagonal holds
+    the self-trades.  What CDAVecEnv.tape_flows computes on the device."""
+    r = as_rows(rows).astype(np.int64)
+    a = int(num_agents)
+    out = np.zeros((a, a, 3), np.int64)
+    if len(r) and (r[:, [3, 6]].min() < 0 or r[:, [3, 6]].max() >= a):
+        raise ValueError(f"an agent id of the tape is outside 0 .. {a - 1}")
+    np.add.at(out, (r[:, 6], r[:, 3]), np.stack([r[:, 2], r[:, 1] * r[:, 2], np.ones(len(r), np.int64)], axis=1))
+    return out
+
+
+def flows_by_module(flows, slot_module, n_modules):
+    """Per-market flow matrices summed into one module x module table through a league's slot -> module map: flows i64 [N, A, A, 3] (CDAVecEnv.tape_flows),
+    slot_module integer [N, A] (the module that played slot a of market i, 0 .. n_modules - 1) -> i64 [n_modules, n_modules, 3], [initiator's module,
+    counterparty's module].  torch tensors, on the device the flows are on (one index_add_)."""
+    import torch
+    n, a = flows.shape[0], flows.shape[1]
+    if tuple(flows.shape) != (n, a, a, 3) or tuple(slot_module.shape) != (n, a):
+        raise ValueError(f"flows must be [N, A, A, 3] and slot_module [N, A], got {tuple(flows.shape)} and {tuple(slot_module.shape)}")
+    mod = slot_module.to(device=flows.device, dtype=torch.int64)
+    if mod.numel() and (int(mod.min()) < 0 or int(mod.max()) >= int(n_modules)):
+        raise ValueError(f"a module id is outside 0 .. {int(n_modules) - 1}")
+    cell = (mod[:, :, None] * int(n_modules) + mod[:, None, :]).reshape(-1)                  # [N * A * A]: initiator's module x counterparty's module
+    out = torch.zeros((int(n_modules) * int(n_modules), 3), dtype=torch.int64, device=flows.device)
+    out.index_add_(0, cell, flows.reshape(-1, 3).to(torch.int64))
+    return out.reshape(int(n_modules), int(n_modules), 3)

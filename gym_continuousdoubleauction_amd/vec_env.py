@@ -573,15 +573,16 @@ class CDAVecEnv:
 
     def tape_counts(self):
         """{'n_total' i64[N]: fills since enable_tape, 'n_episode' i32[N]: fills since the market's last reset (the reference's len(LOB.tape)), 'episode' i32[N]:
-        resets since enable_tape, 'partial' i32[N]: 1 = the episode's head is missing (the market was restored from a snapshot)}, device tensors."""
+        resets since enable_tape, 'partial' i32[N]: 1 = the episode's head is missing (the market was restored from a snapshot), 'n_previous' i32[N]: fills of the
+        episode that ended at the market's last reset - records [n_total - n_episode - n_previous, n_total - n_episode)}, device tensors."""
         self._need_tape("tape_counts()")
         self.join()
         out = {"n_total": torch.empty(self.n_markets, dtype=torch.int64, device=self.device)}
-        for k in ("n_episode", "episode", "partial"):
+        for k in ("n_episode", "episode", "partial", "n_previous"):
             out[k] = torch.empty(self.n_markets, dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):
-            check(lib().cda_tape_counts(self._h, out["n_total"].data_ptr(), out["n_episode"].data_ptr(), out["episode"].data_ptr(), out["partial"].data_ptr(),
-                                        self._stream()), "cda_tape_counts")
+            check(lib().cda_tape_counts_ex(self._h, out["n_total"].data_ptr(), out["n_episode"].data_ptr(), out["episode"].data_ptr(), out["partial"].data_ptr(),
+                                           out["n_previous"].data_ptr(), self._stream()), "cda_tape_counts_ex")
         return out
 
     def drain_tape(self, cursor=None):
@@ -602,19 +603,69 @@ class CDAVecEnv:
             check(lib().cda_tape_pack(self._h, 0, n, cur.data_ptr(), off.data_ptr(), rec.data_ptr() if total else None, total, self._stream()), "cda_tape_pack")
         return rec, off, dropped
 
-    def tape_last(self, k, first_market=0, n_markets=None):
+    def tape_last(self, k, first_market=0, n_markets=None, episode="current"):
         """The last k records of each market's CURRENT episode, oldest first (what state_helper.py walks with tape_display_length) ->
-        (records i32 [n, k, 8], rows beyond the count zero; counts i32 [n]), device tensors."""
+        (records i32 [n, k, 8], rows beyond the count zero; counts i32 [n]), device tensors.  episode="previous": of the episode that ended at the market's last reset."""
         self._need_tape("tape_last()")
         n = self.n_markets - int(first_market) if n_markets is None else int(n_markets)
         if not (0 <= int(first_market) and n >= 1 and int(first_market) + n <= self.n_markets and int(k) >= 1):
             raise ValueError(f"tape_last: range [{first_market}, {int(first_market) + n}) x {k} records is outside the env")
+        which = self._tape_which(episode)
         self.join()
         with torch.cuda.device(self.device):
             rec = torch.empty((n, int(k), K.TAPE_WORDS), dtype=torch.int32, device=self.device)
             cnt = torch.empty(n, dtype=torch.int32, device=self.device)
-            check(lib().cda_tape_last(self._h, int(first_market), n, int(k), rec.data_ptr(), cnt.data_ptr(), self._stream()), "cda_tape_last")
+            check(lib().cda_tape_last_of(self._h, int(first_market), n, which, int(k), rec.data_ptr(), cnt.data_ptr(), self._stream()), "cda_tape_last_of")
         return rec, cnt
+
+    @staticmethod
+    def _tape_which(episode):
+        if episode not in K.TAPE_EPISODES:
+            raise ValueError(f"episode must be 'current' or 'previous', got {episode!r}")
+        return K.TAPE_EPISODES[episode]
+
+    def _tape_range(self, what, first_market, n_markets):
+        n = self.n_markets - int(first_market) if n_markets is None else int(n_markets)
+        if not (0 <= int(first_market) and n >= 1 and int(first_market) + n <= self.n_markets):
+            raise ValueError(f"{what}: range [{first_market}, {int(first_market) + n}) is outside the env's {self.n_markets} markets")
+        return int(first_market), n
+
+    def tape_bars(self, bar_steps, n_bars=None, episode="current", first_market=0, n_markets=None):
+        """Price / volume bars of one remembered episode, reduced on the device in one launch (include/cda.h cda_tape_bars): bar b of a market covers the episode's
+        fills of env steps [b * bar_steps, (b + 1) * bar_steps) -> (bars i32 [n, n_bars, 12], info i32 [n, 4]), device tensors.  The twelve words of a bar are
+        tape.BAR_DTYPE (tape.as_bars() gives the named view: open, high, low, close, n_trades, n_self, volume, buy_volume, notional); a bar without fills is
+        all zeros.  info: records aggregated, records of the episode the ring had already overwritten, records beyond the last bar, partial flag.
+        episode: "current", or "previous" = the episode that ended at the market's last reset.  n_bars defaults to ceil(max_step / bar_steps), largest max_step."""
+        self._need_tape("tape_bars()")
+        first, n = self._tape_range("tape_bars", first_market, n_markets)
+        which = self._tape_which(episode)
+        if int(bar_steps) < 1:
+            raise ValueError(f"tape_bars: bar_steps must be >= 1, got {bar_steps}")
+        if n_bars is None:
+            top = int(self.market_rows()["max_step"].max()) if self.per_market else int(self.max_step)
+            n_bars = -(-top // int(bar_steps))
+        if int(n_bars) < 1:
+            raise ValueError(f"tape_bars: n_bars must be >= 1, got {n_bars}")
+        self.join()
+        with torch.cuda.device(self.device):
+            bars = torch.empty((n, int(n_bars), K.TAPE_BAR_WORDS), dtype=torch.int32, device=self.device)
+            info = torch.empty((n, 4), dtype=torch.int32, device=self.device)
+            check(lib().cda_tape_bars(self._h, first, n, which, int(bar_steps), int(n_bars), bars.data_ptr(), info.data_ptr(), self._stream()), "cda_tape_bars")
+        return bars, info
+
+    def tape_flows(self, episode="current", first_market=0, n_markets=None):
+        """Who trades with whom in one remembered episode (include/cda.h cda_tape_flows): (flows i64 [n, A, A, 3], info i32 [n, 4]), device tensors;
+        flows[i, init_id, counter_id] = (quantity, notional = price x quantity, fills), the diagonal holds the self-trades.  info as tape_bars (its third word is 0)."""
+        self._need_tape("tape_flows()")
+        first, n = self._tape_range("tape_flows", first_market, n_markets)
+        which = self._tape_which(episode)
+        self.join()
+        a = self.num_agents
+        with torch.cuda.device(self.device):
+            flows = torch.empty((n, a, a, 3), dtype=torch.int64, device=self.device)
+            info = torch.empty((n, 4), dtype=torch.int32, device=self.device)
+            check(lib().cda_tape_flows(self._h, first, n, which, flows.data_ptr(), info.data_ptr(), self._stream()), "cda_tape_flows")
+        return flows, info
 
     def tape_episode(self, market=0):
         """The current episode's records of one market, oldest first, as a host array i32 [n, 8] (at most the ring's capacity of them)."""

@@ -553,10 +553,14 @@ int cda_snapshot_restore(cda_env* env, int32_t first_market, const void* blob_de
  * (rollout chains take their two-launch path and record through the step kernel).  Synchronous (it waits for the device); do not toggle it
  * between the capture and the replay of a graph that holds step launches.
  * Per market: n_total (fills since enable; the ring slot of record j is j % capacity), n_episode (fills since the market's last reset = the
- * reference's len(LOB.tape)), episode (resets since enable), partial.  A reset - cda_reset*, the device-side auto reset - zeroes n_episode, bumps
- * episode and clears partial; it does NOT clear the ring: the episode that just ended stays readable until newer fills overwrite it.  Snapshots
- * do not carry the tape: cda_snapshot_restore zeroes the restored markets' n_episode and sets partial = 1 (what follows is an episode's tail).
+ * reference's len(LOB.tape)), episode (resets since enable), partial, n_previous.  A reset - cda_reset*, the device-side auto reset - remembers
+ * n_episode as n_previous (the fills of the step that ended the episode included), zeroes n_episode, bumps episode and clears partial; it does NOT
+ * clear the ring: the episode that just ended stays readable until newer fills overwrite it.  In record numbers the current episode is
+ * [n_total - n_episode, n_total) and the previous one [n_total - n_episode - n_previous, n_total - n_episode); the ring holds [n_total - capacity,
+ * n_total).  Snapshots do not carry the tape: cda_snapshot_restore zeroes the restored markets' n_episode and n_previous and sets partial = 1
+ * (what follows is an episode's tail).
  *   cda_tape_counts    n_total i64[N], n_episode i32[N], episode i32[N], partial i32[N] (device; each may be NULL).
+ *   cda_tape_counts_ex the same and n_previous i32[N] (may be NULL too).
  *   cda_tape_offsets   the streaming read, first half: for market first + i everything from cursor_dev[i] (a record number; i64[n], device) to
  *                      n_total that the ring still holds -> offsets_dev i64[n + 1] (exclusive scan of the counts; offsets[n] = records in all),
  *                      dropped_dev i64[n] (may be NULL): records of [cursor, n_total) the ring had already overwritten.
@@ -565,7 +569,20 @@ int cda_snapshot_restore(cda_env* env, int32_t first_market, const void* blob_de
  *                      must not be stepped between the two calls (stream order); a market whose run would not fit is left alone, cursor included.
  *   cda_tape_last      the last k records of each market's CURRENT episode, oldest first -> records_out_dev [n][k][CDA_TAPE_WORDS] i32 (rows beyond
  *                      the count are zero), counts_out_dev i32[n] (may be NULL): what state_helper.py walks with tape_display_length.
- * CDA_ERR_UNSUPPORTED from the readers while the tape is off. */
+ *   cda_tape_last_of   the same of the episode `which` names: CDA_TAPE_CURRENT or CDA_TAPE_PREVIOUS (the episode that ended at the market's last reset).
+ * Reductions over the records of one remembered episode, on the device, one launch each, a wave per market (no atomics on global memory: the result
+ * does not depend on scheduling).  Both take `which` as cda_tape_last_of does and fill info_out_dev i32 [n][4] (may be NULL): {records aggregated,
+ * records of that episode the ring had already overwritten, records whose bar index was >= n_bars (not aggregated; 0 for flows), 1 = the episode's
+ * head was never recorded (partial)}.
+ *   cda_tape_bars      price / volume bars: bar b of market first + i covers the episode's records whose step index (sides_step >> 2) lies in
+ *                      [b * bar_steps, (b + 1) * bar_steps) -> bars_out_dev [n][n_bars] cda_tape_bar (device, 16-B aligned).  open / close: the first /
+ *                      last such record in tape order; a bar without fills is all zeros (n_trades == 0).  Within an episode the step index never
+ *                      decreases, so a bar is one run of records; every row of the output is written exactly once.
+ *   cda_tape_flows     who trades with whom: flows_out_dev i64 [n][A][A][3] (A = num_agents), [init_id][counter_id] = {quantity, notional (price x
+ *                      quantity), fills}; the diagonal holds the self-trades.
+ * bar_steps < 1, n_bars < 1, a range outside the env or another `which`: CDA_ERR_INVALID.  CDA_ERR_UNSUPPORTED from the readers while the tape is off. */
+#define CDA_TAPE_CURRENT  0
+#define CDA_TAPE_PREVIOUS 1
 #define CDA_TAPE_WORDS   8
 #define CDA_TAPE_CAP_MAX (1 << 20)
 typedef struct cda_tape_record {       /* transaction_record of orderbook.py:108-140 */
@@ -585,6 +602,19 @@ int cda_tape_offsets(cda_env* env, int32_t first_market, int32_t n_markets, cons
 int cda_tape_pack(cda_env* env, int32_t first_market, int32_t n_markets, int64_t* cursor_dev, const int64_t* offsets_dev, void* records_out_dev,
                   int64_t capacity_records, void* stream);
 int cda_tape_last(cda_env* env, int32_t first_market, int32_t n_markets, int32_t k, void* records_out_dev, int32_t* counts_out_dev, void* stream);
+typedef struct cda_tape_bar {          /* 48 bytes = twelve int32 words */
+    int32_t open, high, low, close;    /* prices as the records hold them; all 0 where n_trades == 0 */
+    int32_t n_trades;                  /* fills in the bar */
+    int32_t n_self;                    /* ... of which counter_id == init_id */
+    int64_t volume;                    /* sum of quantity */
+    int64_t buy_volume;                /* ... over the fills whose initiator side is bid */
+    int64_t notional;                  /* sum of price x quantity */
+} cda_tape_bar;
+int cda_tape_counts_ex(cda_env* env, int64_t* n_total_dev, int32_t* n_episode_dev, int32_t* episode_dev, int32_t* partial_dev, int32_t* n_previous_dev, void* stream);
+int cda_tape_last_of(cda_env* env, int32_t first_market, int32_t n_markets, int32_t which, int32_t k, void* records_out_dev, int32_t* counts_out_dev, void* stream);
+int cda_tape_bars(cda_env* env, int32_t first_market, int32_t n_markets, int32_t which, int32_t bar_steps, int32_t n_bars, void* bars_out_dev,
+                  int32_t* info_out_dev, void* stream);
+int cda_tape_flows(cda_env* env, int32_t first_market, int32_t n_markets, int32_t which, int64_t* flows_out_dev, int32_t* info_out_dev, void* stream);
 
 /* ---- per-market parameters: many configurations in one env ----------------------------------------------------------------------------
  * Every market reads the fields below from a row of its own (a device table every env has; cda_create fills each row from the config).  The
