@@ -154,9 +154,12 @@ __device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
     z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
     return z ^ (z >> 31);
 }
-__device__ __forceinline__ float u01(unsigned long long w, int half) {               // (0, 1): 24 bits of one 32-bit half
+// k = the top 24 bits of one 32-bit half -> (k + 0.5) / 2^24 in float32, inside (0, 1): exact below 0.5; above, k + 0.5 is not representable and rounds to even
+// (u takes the even 24-bit values), and k = 2^24 - 1 would round to 1.0 - clamped to the largest float32 below 1.  At u == 1 an inverse CDF finds no class
+// (t = u * s reaches the running sum's last value) and falls through to the LAST one whatever its probability.
+__device__ __forceinline__ float u01(unsigned long long w, int half) {
     const unsigned int x = half ? (unsigned int)(w >> 32) : (unsigned int)w;
-    return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f);
+    return fminf(((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f), 0x1.fffffep-1f);
 }
 template <int N>
 __device__ __forceinline__ int sample_head(const float* l, float u, float& logp) {

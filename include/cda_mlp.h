@@ -99,7 +99,14 @@ int cda_mlp_pack(const float* theta, void* wb, void* stream);
  *   env_* [N,A]: category i32, size_mean f32 (tanh of the Gaussian sample), size_sigma f32 (sigmoid), price i32, price_offset i32 -
  *   what cda_step consumes; a_cont f32[N,A,2] the raw Gaussian samples; logp f32[N,A]; value f32[N].
  * Randomness: counter based (include/cda_random_agents.h's splitmix64), keyed (seed, *counter_dev, draw, global sample index); nothing
- * is bumped - the caller varies `draw` (the step index inside a rollout) and *counter_dev (once per rollout). */
+ * is bumped - the caller varies `draw` (the step index inside a rollout) and *counter_dev (once per rollout).
+ * Sampling law (restated on the host in tests/sampler_ref.py and held to it sample by sample, tests/test_hip_sampler.py):
+ *   key = mix(seed + counter * 0xd1342543de82ef95 + draw * 0x2545f4914f6cdd1d), mix = splitmix64's finaliser; sample i = market * agents + agent draws
+ *   w0 = mix(key + i), w1 = mix(w0), w2 = mix(w1).  A uniform is the top 24 bits k of a 32-bit half-word: category <- w0 low, price <- w0 high,
+ *   price_offset <- w1 low, Box-Muller radius <- w1 high, angle <- w2 low; u = (k + 1/2) / 2^24 in float32, strictly inside (0, 1): exact below 1/2; above,
+ *   k + 1/2 rounds to even (u takes the even 24-bit values) and the top value k = 2^24 - 1, which would round to 1.0, is clamped to 1 - 2^-24.  (At u = 1 an
+ *   inverse CDF finds no class and takes the last one whatever its probability.)  A categorical head takes the first class j with
+ *   u * sum_q e_q < sum_{q <= j} e_q, e_q = exp(l_q - max l); the Gaussians are n = sqrt(-2 ln u_r) (cos, sin)(2 pi u_a), a_cont = mean + exp(log_std) n. */
 int cda_mlp_policy_step(const void* wb, const float* theta, const float* obs, int32_t first_market, int32_t n_markets, int32_t num_agents,
                         uint64_t seed, const int64_t* counter_dev, int64_t draw,
                         int32_t* env_category, float* env_size_mean, float* env_size_sigma, int32_t* env_price, int32_t* env_price_offset,
