@@ -25,7 +25,7 @@ SYMBOLS = [
     "cda_snapshot_table_bytes", "cda_snapshot_offsets", "cda_snapshot_pack", "cda_snapshot_check_header", "cda_snapshot_restore",
     "cda_market_params_from_config", "cda_check_market_params", "cda_set_market_params", "cda_get_market_params",
     "cda_tape_enable", "cda_tape_capacity", "cda_tape_counts", "cda_tape_offsets", "cda_tape_pack", "cda_tape_last",
-    "cda_tape_counts_ex", "cda_tape_last_of", "cda_tape_bars", "cda_tape_flows",
+    "cda_tape_counts_ex", "cda_tape_last_of", "cda_tape_bars", "cda_tape_flows", "cda_tape_exec",
 ]
 
 
@@ -193,6 +193,7 @@ def lib():
     L.cda_tape_last_of.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp]
     L.cda_tape_bars.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp]
     L.cda_tape_flows.argtypes = [vp, i32, i32, i32, vp, vp, vp]
+    L.cda_tape_exec.argtypes = [vp, i32, i32, i32, vp, i32, vp, vp, vp, vp]
     L.cda_ppo_loss32.argtypes = [vp] * 10 + [i64, i32, i32, f32, f32, f32, vp, vp, vp, i64, i32, i32, vp]
     L.cda_gae_records.argtypes = [vp, vp, vp, vp, i32, i64, i32, f32, f32, f32, vp, vp, vp]
     L.cda_ppo_loss_records.argtypes = [vp, vp, vp, vp, i64, vp, i64, i32, i32, f32, f32, f32, vp, vp, vp, i64, i32, i32, vp]

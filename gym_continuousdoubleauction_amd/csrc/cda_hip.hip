@@ -1597,3 +1597,5 @@ int64_t cda_state_bytes_per_market(const cda_env* e) { return e ? (int64_t)e->P.
 #include "cda_tape.inc"
 // ... and the reductions over a remembered episode's records: price / volume bars, agent-to-agent flows
 #include "cda_tape_bars.inc"
+// ... and the execution report: per-agent inventory, turnover and mark-outs
+#include "cda_tape_exec.inc"

@@ -480,6 +480,19 @@ class CDAEnv(_DictSurface):
             raise RuntimeError("the trade tape is off (it is opt-in): call enable_tape() before the episode whose fills you want to read")
         return as_bars(self._vec.tape_bars(bar_steps, n_bars, episode, 0, 1)[0][0])
 
+    def tape_exec(self, horizons=(1, 5, 20), episode="current"):
+        """The execution report of this market's current (or previous) episode, reduced on the device (CDAVecEnv.tape_exec): a dict of numpy arrays - every
+        tape.STAT_FIELDS word as int64 [A], "markouts" int64 [A, H, 2, 4] (role 0 = maker, 1 = taker; words tape.MARKOUT_FIELDS), "horizons" and "info" (records
+        aggregated, records already overwritten, 0, partial flag).  tape.exec_summary turns one agent's row into the ratios."""
+        import numpy as np
+        from .tape import STAT_FIELDS, _horizons
+        if not self._vec.tape_enabled:
+            raise RuntimeError("the trade tape is off (it is opt-in): call enable_tape() before the episode whose fills you want to read")
+        stats, marks, info = (x.cpu().numpy() for x in self._vec.tape_exec(horizons, episode, 0, 1))
+        out = {f: stats[0, :, i].copy() for i, f in enumerate(STAT_FIELDS)}
+        out.update(markouts=marks[0], horizons=np.array(_horizons(horizons), np.int64), info=info[0])
+        return out
+
     # -- diagnostics some reference tests read --------------------------------------------
     @property
     def last_price(self):

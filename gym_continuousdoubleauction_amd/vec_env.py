@@ -667,6 +667,30 @@ class CDAVecEnv:
             check(lib().cda_tape_flows(self._h, first, n, which, flows.data_ptr(), info.data_ptr(), self._stream()), "cda_tape_flows")
         return flows, info
 
+    def tape_exec(self, horizons=(1, 5, 20), episode="current", first_market=0, n_markets=None):
+        """The execution report of one remembered episode, per market and agent, reduced on the device in one launch (include/cda.h cda_tape_exec; tape.py
+        exec_from_records is its specification, word for word): (stats i64 [n, A, 16], markouts i64 [n, A, H, 2, 4], info i32 [n, 4]), device tensors.
+        stats: tape.STAT_FIELDS - bought / sold quantity and notional, quantity and fills as maker (counter_id) and as taker (init_id), self-trades, the running
+        position's end, maximum and minimum, abs_pos_steps (the sum of |position| over the steps 0 .. S_last, S_last = the step of the last held record), first and
+        last step of the agent's fills.  markouts[.., h, role 0 = maker / 1 = taker] = (sum of sign x (mark(s + horizons[h]) - price) x quantity, quantity, fills -
+        over the fills whose s + horizons[h] <= S_last -, fills beyond that: open, counted and never marked); mark(t) = the last print at or before step t.
+        horizons: 1 .. 8 step counts >= 0.  info as tape_flows; when it reports overwritten records or a partial episode the position words are relative to the
+        first held record."""
+        from .tape import _horizons
+        self._need_tape("tape_exec()")
+        first, n = self._tape_range("tape_exec", first_market, n_markets)
+        which = self._tape_which(episode)
+        hz = _horizons(horizons)
+        self.join()
+        a = self.num_agents
+        with torch.cuda.device(self.device):
+            stats = torch.empty((n, a, K.TAPE_STAT_WORDS), dtype=torch.int64, device=self.device)
+            marks = torch.empty((n, a, len(hz), 2, 4), dtype=torch.int64, device=self.device)
+            info = torch.empty((n, 4), dtype=torch.int32, device=self.device)
+            check(lib().cda_tape_exec(self._h, first, n, which, (C.c_int32 * len(hz))(*hz), len(hz), stats.data_ptr(), marks.data_ptr(), info.data_ptr(),
+                                      self._stream()), "cda_tape_exec")
+        return stats, marks, info
+
     def tape_episode(self, market=0):
         """The current episode's records of one market, oldest first, as a host array i32 [n, 8] (at most the ring's capacity of them)."""
         self._need_tape("tape_episode()")

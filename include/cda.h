@@ -571,7 +571,7 @@ int cda_snapshot_restore(cda_env* env, int32_t first_market, const void* blob_de
  *                      the count are zero), counts_out_dev i32[n] (may be NULL): what state_helper.py walks with tape_display_length.
  *   cda_tape_last_of   the same of the episode `which` names: CDA_TAPE_CURRENT or CDA_TAPE_PREVIOUS (the episode that ended at the market's last reset).
  * Reductions over the records of one remembered episode, on the device, one launch each, a wave per market (no atomics on global memory: the result
- * does not depend on scheduling).  Both take `which` as cda_tape_last_of does and fill info_out_dev i32 [n][4] (may be NULL): {records aggregated,
+ * does not depend on scheduling).  All take `which` as cda_tape_last_of does and fill info_out_dev i32 [n][4] (may be NULL): {records aggregated,
  * records of that episode the ring had already overwritten, records whose bar index was >= n_bars (not aggregated; 0 for flows), 1 = the episode's
  * head was never recorded (partial)}.
  *   cda_tape_bars      price / volume bars: bar b of market first + i covers the episode's records whose step index (sides_step >> 2) lies in
@@ -580,7 +580,20 @@ int cda_snapshot_restore(cda_env* env, int32_t first_market, const void* blob_de
  *                      decreases, so a bar is one run of records; every row of the output is written exactly once.
  *   cda_tape_flows     who trades with whom: flows_out_dev i64 [n][A][A][3] (A = num_agents), [init_id][counter_id] = {quantity, notional (price x
  *                      quantity), fills}; the diagonal holds the self-trades.
- * bar_steps < 1, n_bars < 1, a range outside the env or another `which`: CDA_ERR_INVALID.  CDA_ERR_UNSUPPORTED from the readers while the tape is off. */
+ *   cda_tape_exec      the execution report, per agent: stats_out_dev i64 [n][A][CDA_TAPE_STAT_WORDS] and markouts_out_dev i64 [n][A][n_horizons][2][4]
+ *                      (device, 8-B aligned).  A party's side is 0 = bid (it bought, sign +1) or 1 = ask (it sold, sign -1); a self-trade (init_id ==
+ *                      counter_id) moves no position and is counted in self_qty / self_fills only; S_last = the step of the last held record.
+ *                      stats words, in order: buy_qty, sell_qty, buy_notional, sell_notional (price x quantity; both roles), maker_qty, maker_fills (the
+ *                      agent was counter_id), taker_qty, taker_fills (init_id), self_qty, self_fills, final_pos, max_long (largest running position,
+ *                      >= 0), max_short (most negative, <= 0), abs_pos_steps (sum over the steps 0 .. S_last of |position at the end of the step|),
+ *                      first_step, last_step of the agent's non-self fills (-1 without any).  The running position starts at 0 at the first held record.
+ *                      markouts[agent][horizon h][role: 0 maker, 1 taker] = {sum of sign x (mark(s + k_h) - price) x quantity, quantity, fills - over the
+ *                      agent's non-self fills in that role with s + k_h <= S_last -, fills with s + k_h > S_last (open: counted, never marked)};
+ *                      mark(t) = the price of the last held record whose step is <= t (the last print).  horizons_dev_or_host: n_horizons int32 >= 0,
+ *                      1 <= n_horizons <= CDA_TAPE_MAX_HORIZONS; a host array is read during the call, a device array costs a synchronising copy.
+ *                      info's third word is 0.
+ * bar_steps < 1, n_bars < 1, n_horizons outside 1 .. CDA_TAPE_MAX_HORIZONS, a negative horizon, a misaligned output, a range outside the env or another
+ * `which`: CDA_ERR_INVALID.  CDA_ERR_UNSUPPORTED from the readers while the tape is off. */
 #define CDA_TAPE_CURRENT  0
 #define CDA_TAPE_PREVIOUS 1
 #define CDA_TAPE_WORDS   8
@@ -615,6 +628,10 @@ int cda_tape_last_of(cda_env* env, int32_t first_market, int32_t n_markets, int3
 int cda_tape_bars(cda_env* env, int32_t first_market, int32_t n_markets, int32_t which, int32_t bar_steps, int32_t n_bars, void* bars_out_dev,
                   int32_t* info_out_dev, void* stream);
 int cda_tape_flows(cda_env* env, int32_t first_market, int32_t n_markets, int32_t which, int64_t* flows_out_dev, int32_t* info_out_dev, void* stream);
+#define CDA_TAPE_STAT_WORDS   16
+#define CDA_TAPE_MAX_HORIZONS 8
+int cda_tape_exec(cda_env* env, int32_t first_market, int32_t n_markets, int32_t which, const int32_t* horizons_dev_or_host, int32_t n_horizons,
+                  int64_t* stats_out_dev, int64_t* markouts_out_dev, int32_t* info_out_dev, void* stream);
 
 /* ---- per-market parameters: many configurations in one env ----------------------------------------------------------------------------
  * Every market reads the fields below from a row of its own (a device table every env has; cda_create fills each row from the config).  The
