@@ -26,6 +26,7 @@ SYMBOLS = [
     "cda_market_params_from_config", "cda_check_market_params", "cda_set_market_params", "cda_get_market_params",
     "cda_tape_enable", "cda_tape_capacity", "cda_tape_counts", "cda_tape_offsets", "cda_tape_pack", "cda_tape_last",
     "cda_tape_counts_ex", "cda_tape_last_of", "cda_tape_bars", "cda_tape_flows", "cda_tape_exec",
+    "cda_book_counts", "cda_book_levels", "cda_book_impact", "cda_book_agents", "cda_book_offsets", "cda_book_pack",
 ]
 
 
@@ -194,6 +195,12 @@ def lib():
     L.cda_tape_bars.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp]
     L.cda_tape_flows.argtypes = [vp, i32, i32, i32, vp, vp, vp]
     L.cda_tape_exec.argtypes = [vp, i32, i32, i32, vp, i32, vp, vp, vp, vp]
+    L.cda_book_counts.argtypes = [vp, i32, i32, vp, vp]
+    L.cda_book_levels.argtypes = [vp, i32, i32, i32, vp, vp]
+    L.cda_book_impact.argtypes = [vp, i32, i32, vp, i32, vp, vp]
+    L.cda_book_agents.argtypes = [vp, i32, i32, vp, vp]
+    L.cda_book_offsets.argtypes = [vp, i32, i32, vp, vp]
+    L.cda_book_pack.argtypes = [vp, i32, i32, vp, i64, vp, i64, vp]
     L.cda_ppo_loss32.argtypes = [vp] * 10 + [i64, i32, i32, f32, f32, f32, vp, vp, vp, i64, i32, i32, vp]
     L.cda_gae_records.argtypes = [vp, vp, vp, vp, i32, i64, i32, f32, f32, f32, vp, vp, vp]
     L.cda_ppo_loss_records.argtypes = [vp, vp, vp, vp, i64, vp, i64, i32, i32, f32, f32, f32, vp, vp, vp, i64, i32, i32, vp]

@@ -14,6 +14,8 @@
 //                      k_mark_to_mkt   Exchg_Helper.mark_to_mkt                         (test hook, 1 market)
 //                      k_raw_snapshot  agg_LOB_raw            exchg/state_helper.py:159-160
 //   cda_snapshot.inc k_snap_offsets, k_snap_pack, k_snap_check, k_snap_restore and the cda_snapshot_* entry points (included at the end)
+//   cda_book_report.inc  k_book_counts, k_book_levels, k_book_impact, k_book_agents, k_book_offsets, k_book_pack: read-only reductions over the
+//                    standing book (tile + spill ring), one wave per (market, side), and the cda_book_* entry points (included at the end)
 //   here             k_init_arena, k_random_actions, k_nav_conservation, k_check_invariants, k_flags, k_book_peak, k_handback_unpack,
 //                    self-tests, and the host side: arena, capacity dispatch, every extern "C" entry point
 //   (the measuring probes - operation micro-benchmark, clock probe, PMC calibration - live in tools/csrc/cda_tools.hip, a
@@ -1599,3 +1601,5 @@ int64_t cda_state_bytes_per_market(const cda_env* e) { return e ? (int64_t)e->P.
 #include "cda_tape_bars.inc"
 // ... and the execution report: per-agent inventory, turnover and mark-outs
 #include "cda_tape_exec.inc"
+// the book report (cda_book_counts .. cda_book_pack): depth ladder, market-order impact, every agent's resting orders, the Level-3 dump
+#include "cda_book_report.inc"

@@ -699,6 +699,58 @@ class CDAVecEnv:
         rec, cnt = self.tape_last(k, int(market), 1)
         return rec[0, :int(cnt[0].item())].cpu().numpy()
 
+    # ------------------------------------------------------------------ the book report: reductions over the standing book, on the device
+    def _book_call(self, name, first_market, n_markets, shape, dtype, *mid):
+        first, n = self._tape_range(name, first_market, n_markets)
+        self.join()
+        with torch.cuda.device(self.device):
+            out = torch.empty((n,) + shape, dtype=dtype, device=self.device)
+            check(getattr(lib(), "cda_" + name)(self._h, first, n, *mid, out.data_ptr(), self._stream()), "cda_" + name)
+        return out
+
+    def book_counts(self, first_market=0, n_markets=None):
+        """Resting orders and distinct price levels of every side, tile and HBM ring together (include/cda.h cda_book_counts): i32 [n, 2, 2] =
+        [market, side 0 bids / 1 asks, (orders, levels)], a device tensor.  Like every book_* reader: one launch on the caller's stream, ordered
+        after every group's last step, no host synchronisation; book.py states the result in numpy (book.counts_from_orders)."""
+        return self._book_call("book_counts", first_market, n_markets, (2, 2), torch.int32)
+
+    def book_levels(self, max_levels, first_market=0, n_markets=None):
+        """The Level-2 ladder of the WHOLE book, not only the observation's ten levels (cda_book_levels; book.levels_from_orders): i64 [n, 2, max_levels, 3]
+        = (price, volume, orders) per level, best first; rows past a side's level count are zero.  1 <= max_levels <= 4096.  book.summary() reads spread,
+        mid and imbalance off it."""
+        from .book import _max_levels
+        L = _max_levels(max_levels)
+        return self._book_call("book_levels", first_market, n_markets, (2, L, 3), torch.int64, L)
+
+    def book_impact(self, sizes, first_market=0, n_markets=None):
+        """What a market order of each of `sizes` (1 .. 16 integers >= 1) would pay right now (cda_book_impact; book.impact_from_orders): i64 [n, 2, K, 3] =
+        (filled, notional, last_price) for an order that consumes that side by price-time priority - side 0: the bids, hit by a sell; side 1: the asks, lifted
+        by a buy; own resting orders included.  filled = min(size, the side's quantity), notional = sum of price x quantity over what is consumed, last_price =
+        the price of the last order touched (0 on an empty side)."""
+        from .book import _sizes
+        q = _sizes(sizes)
+        return self._book_call("book_impact", first_market, n_markets, (2, len(q), 3), torch.int64, (C.c_int64 * len(q))(*q), len(q))
+
+    def book_agents(self, first_market=0, n_markets=None):
+        """Every agent's resting orders (cda_book_agents; book.agents_from_orders): i64 [n, 2, A, 6] = (orders, quantity, notional, best_price, worst_price,
+        ahead_qty) per side and agent; best / worst price = the prices of the agent's first / last own order in queue order, ahead_qty = the quantity resting
+        strictly before its first own order; zeros for an agent with nothing on that side.  Bid + ask notional of an agent is its cash_on_hold."""
+        return self._book_call("book_agents", first_market, n_markets, (2, self.num_agents, 6), torch.int64)
+
+    def book_orders(self, first_market=0, n_markets=None):
+        """The Level-3 dump of all markets in two launches (cda_book_offsets, cda_book_pack): (orders i32 [total, 5] - get_book()'s rows (price, qty, owner,
+        order_id, timestamp), queue order -, offsets i64 [2 n + 1]): side s of market first_market + i owns rows offsets[2 i + s] : offsets[2 i + s + 1].
+        Device tensors; the one host read is the 8-byte total.  book.split_orders() cuts them into per-market (bids, asks) pairs."""
+        first, n = self._tape_range("book_orders", first_market, n_markets)
+        self.join()
+        with torch.cuda.device(self.device):
+            off = torch.empty(2 * n + 1, dtype=torch.int64, device=self.device)
+            check(lib().cda_book_offsets(self._h, first, n, off.data_ptr(), self._stream()), "cda_book_offsets")
+            total = int(off[2 * n].item())              # the one 8-byte read
+            rows = torch.empty((total, 5), dtype=torch.int32, device=self.device)
+            check(lib().cda_book_pack(self._h, first, n, off.data_ptr(), total, rows.data_ptr() if total else None, total, self._stream()), "cda_book_pack")
+        return rows, off
+
     # ------------------------------------------------------------------ snapshots, forks and resumable runs
     def snapshot(self, first=0, n=None):
         """A compact device image of markets [first, first + n) (include/cda.h cda_snapshot_*): their records, done bytes, episode-metric rows and the

@@ -633,6 +633,42 @@ int cda_tape_flows(cda_env* env, int32_t first_market, int32_t n_markets, int32_
 int cda_tape_exec(cda_env* env, int32_t first_market, int32_t n_markets, int32_t which, const int32_t* horizons_dev_or_host, int32_t n_horizons,
                   int64_t* stats_out_dev, int64_t* markouts_out_dev, int32_t* info_out_dev, void* stream);
 
+/* ---- the book report: reductions over the STANDING book, on the device ------------------------------------------------------------------
+ * The resting orders of markets [first_market, first_market + n_markets), read where they lie - the record's tile and, behind it, the HBM spill
+ * ring - by one wave per (market, side), one launch each, on `stream`; no call synchronises the host and none writes the arena.  A side is walked
+ * in queue order: best price first, FIFO inside a level (the order of cda_get_book).  Side 0 = bids, 1 = asks.  All sums are 64-bit integers:
+ * the results are exact and do not depend on scheduling.  A = num_agents.
+ *   cda_book_counts    counts_out_dev i32 [n][2][2] = (resting orders, distinct price levels) per side.
+ *   cda_book_levels    the Level-2 ladder over the WHOLE side, ring included: levels_out_dev i64 [n][2][max_levels][3] = (price, volume, orders) per
+ *                      level, best first; rows past the side's level count are zero.  1 <= max_levels <= CDA_BOOK_MAX_LEVELS.
+ *   cda_book_impact    what a market order of sizes_host[k] units would pay now: impact_out_dev i64 [n][2][n_sizes][3] = (filled, notional,
+ *                      last_price) for an order that consumes this side by price-time priority - side 0: the bids, hit by a sell; side 1: the asks,
+ *                      lifted by a buy; the taker's own resting orders are part of the side, as they are for the matching loop.  filled =
+ *                      min(size, the side's quantity); notional = sum of price x quantity over what is consumed, the last order partially;
+ *                      last_price = the price of the last order touched, 0 on an empty side.  sizes_host: n_sizes int64 >= 1, read during the
+ *                      call, 1 <= n_sizes <= CDA_BOOK_MAX_SIZES (they travel in the kernel arguments).
+ *   cda_book_agents    agents_out_dev i64 [n][2][A][6] = (orders, quantity, notional = sum of price x quantity, best_price, worst_price, ahead_qty)
+ *                      per agent and side; best_price / worst_price = the prices of the agent's first / last own order in queue order, ahead_qty =
+ *                      the quantity resting strictly before the agent's first own order in queue order; all six are 0 for an agent with nothing on
+ *                      that side.  An agent's bid + ask notional is its cash_on_hold.
+ *   cda_book_offsets   the Level-3 dump of all markets in two launches, first half: offsets_dev i64 [2 n + 1], the exclusive scan of the sides'
+ *                      order counts (offsets[2 n] = orders in all).
+ *   cda_book_pack      second half: orders_out_dev i32 [capacity_orders][5], rows of (price, qty, owner, order_id, timestamp) - cda_order, the rows
+ *                      of cda_get_book; side s of market first + i lies at rows offsets[2 i + s] .. offsets[2 i + s + 1].  total_orders = the
+ *                      offsets[2 n] the caller read (its one 8-byte read); capacity_orders >= total_orders.  The env must not be stepped between
+ *                      the two calls (stream order); a side whose count no longer matches its offsets is left alone.
+ * NULL env or output, a range outside the env, max_levels or n_sizes outside their bounds, a size < 1, a misaligned output, capacity_orders <
+ * total_orders: CDA_ERR_INVALID, nothing is launched. */
+#define CDA_BOOK_MAX_LEVELS 4096
+#define CDA_BOOK_MAX_SIZES  16
+int cda_book_counts(cda_env* env, int32_t first_market, int32_t n_markets, int32_t* counts_out_dev, void* stream);
+int cda_book_levels(cda_env* env, int32_t first_market, int32_t n_markets, int32_t max_levels, int64_t* levels_out_dev, void* stream);
+int cda_book_impact(cda_env* env, int32_t first_market, int32_t n_markets, const int64_t* sizes_host, int32_t n_sizes, int64_t* impact_out_dev, void* stream);
+int cda_book_agents(cda_env* env, int32_t first_market, int32_t n_markets, int64_t* agents_out_dev, void* stream);
+int cda_book_offsets(cda_env* env, int32_t first_market, int32_t n_markets, int64_t* offsets_dev, void* stream);
+int cda_book_pack(cda_env* env, int32_t first_market, int32_t n_markets, const int64_t* offsets_dev, int64_t total_orders, void* orders_out_dev,
+                  int64_t capacity_orders, void* stream);
+
 /* ---- per-market parameters: many configurations in one env ----------------------------------------------------------------------------
  * Every market reads the fields below from a row of its own (a device table every env has; cda_create fills each row from the config).  The
  * config's other fields - num_agents, n_hist, book_capacity, book_spill, auto_reset - set shapes, memory and kernel choice and hold for the
