@@ -20,6 +20,8 @@ OK = 0
 ERR_INVALID, ERR_NO_DEVICE, ERR_HIP, ERR_UNSUPPORTED, ERR_NOMEM = -1, -2, -3, -4, -5
 
 FLAG_BOOK_OVERFLOW, FLAG_INT_OVERFLOW, FLAG_DEC_DOMAIN, FLAG_NAV_CONSERVATION = 1, 2, 4, 8
+# cda_check_invariants (include/cda.h CDA_INV_*): violation bits of one market
+INV_BIDS_SORTED, INV_ASKS_SORTED, INV_CROSSED, INV_QTY, INV_ESCROW, INV_NET_POSITION, INV_OWNER, INV_BOOK_COUNT = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20, 0x80, 0x100
 
 # episode metrics (include/cda.h CDA_EM_*): columns of the per-module table / of the per-env row cda_episode_metrics_collect returns
 EM_AGENT_FIELDS, EM_ENV_FIELDS, EM_MAX_MODULES = 32, 8, 32
