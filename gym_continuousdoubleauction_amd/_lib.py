@@ -27,6 +27,8 @@ SYMBOLS = [
     "cda_tape_enable", "cda_tape_capacity", "cda_tape_counts", "cda_tape_offsets", "cda_tape_pack", "cda_tape_last",
     "cda_tape_counts_ex", "cda_tape_last_of", "cda_tape_bars", "cda_tape_flows", "cda_tape_exec",
     "cda_book_counts", "cda_book_levels", "cda_book_impact", "cda_book_agents", "cda_book_offsets", "cda_book_pack",
+    "cda_scripted_attach", "cda_scripted_detach", "cda_scripted_epoch", "cda_scripted_attached", "cda_scripted_actions", "cda_scripted_decide_host",
+    "cda_scripted_profile_check_host",
 ]
 
 
@@ -201,6 +203,14 @@ def lib():
     L.cda_book_agents.argtypes = [vp, i32, i32, vp, vp]
     L.cda_book_offsets.argtypes = [vp, i32, i32, vp, vp]
     L.cda_book_pack.argtypes = [vp, i32, i32, vp, i64, vp, i64, vp]
+    L.cda_scripted_attach.argtypes = [vp, vp, vp, i32, u64, u64]
+    L.cda_scripted_detach.argtypes = [vp]
+    L.cda_scripted_epoch.argtypes = [vp]
+    L.cda_scripted_epoch.restype = i64
+    L.cda_scripted_attached.argtypes = [vp]
+    L.cda_scripted_actions.argtypes = [vp, i32, i32, vp, i64] + [vp] * 5 + [vp] * 3 + [vp]
+    L.cda_scripted_decide_host.argtypes = [vp, i32, vp, vp, i64, u64, u64, vp, vp, vp] + [vp] * 5
+    L.cda_scripted_profile_check_host.argtypes = [vp, i32]
     L.cda_ppo_loss32.argtypes = [vp] * 10 + [i64, i32, i32, f32, f32, f32, vp, vp, vp, i64, i32, i32, vp]
     L.cda_gae_records.argtypes = [vp, vp, vp, vp, i32, i64, i32, f32, f32, f32, vp, vp, vp]
     L.cda_ppo_loss_records.argtypes = [vp, vp, vp, vp, i64, vp, i64, i32, i32, f32, f32, f32, vp, vp, vp, i64, i32, i32, vp]

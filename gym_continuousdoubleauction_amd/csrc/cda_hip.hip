@@ -30,6 +30,7 @@
 
 #include "../../include/cda.h"
 #include "../../include/cda_random_agents.h"
+#include "../../include/cda_scripted_agents.h"
 #include "cda_dec.hpp"
 #include "cda_market.hpp"
 #include <type_traits>
@@ -618,6 +619,8 @@ __global__ void k_selftest_rng(uint64_t seed, int lo, int hi, int n_steps, int n
 // ==========================================================================================
 // host side: the C-ABI
 // ==========================================================================================
+// scripted opponents (include/cda_scripted_agents.h, csrc/cda_scripted.inc): what cda_scripted_attach keeps - caller-owned device memory, as slot_net is
+struct ScriptArgs { const int32_t* slot; const cda_script_profile* profiles; int32_t n_profiles; int32_t pad; uint64_t seed, market_base; int64_t epoch; };
 struct cda_env {
     Params P;
     int device;
@@ -633,6 +636,7 @@ struct cda_env {
     cda_market_params* rows_host;   // what cda_set_market_params last wrote for each market (the config's row until then)
     uint32_t* snap_flag;     // cda_snapshot_restore: the check pass's verdict (allocated at the first restore)
     TapeArgs tape;           // cda_tape_enable: the trade tape's rings and counters (ring == NULL: off - the launches are then the ones of an env without a tape)
+    ScriptArgs script;       // cda_scripted_attach: the caller's resident slot table and profiles (slot == NULL: nothing attached - cda_scripted_actions launches nothing)
 };
 // csrc/cda_tape.inc (included at the end): the tape's counters follow a reset / a restore queued on `stream`; no-ops while the tape is off
 static int tape_after_reset(cda_env* e, int32_t first, int32_t n, const uint8_t* mask, hipStream_t stream);
@@ -1016,7 +1020,7 @@ static int grant_policy_step_lds(const cda_env* e) {
 int cda_policy_step_supported(const cda_env* e) {
     if (!e) return 0;
     const int lds = e->cap == 256 ? policy_step_lds(e) : 0;
-    return lds > 0 && lds <= 160 * 1024 && e->P.cfg.num_agents <= 8 && !e->handback && !e->tape.ring;      // (no k_policy_step instance writes the trade tape)
+    return lds > 0 && lds <= 160 * 1024 && e->P.cfg.num_agents <= 8 && !e->handback && !e->tape.ring && !e->script.slot;      // (no k_policy_step instance writes the trade tape or asks a scripted law)
 }
 // ... and whether it pays: every workgroup of k_policy_step streams the whole network for its sixteen rows, so the one launch wins while all of the env's
 // workgroups are resident at once (N <= 16 x CUs: 4096 markets on an MI355X - policy in the loop 278 -> 301-308 M at 4096 x 4) and loses to the batched policy
@@ -1603,3 +1607,5 @@ int64_t cda_state_bytes_per_market(const cda_env* e) { return e ? (int64_t)e->P.
 #include "cda_tape_exec.inc"
 // the book report (cda_book_counts .. cda_book_pack): depth ladder, market-order impact, every agent's resting orders, the Level-3 dump
 #include "cda_book_report.inc"
+// scripted opponents (cda_scripted_*): one wave per market turns the market's state into the rule-based slots' actions
+#include "cda_scripted.inc"

@@ -11,9 +11,11 @@ the captured kernels), runs episodes * max_step steps, and reads the episodes th
 the greedy chains); mode="sample" runs the same loop on the sampling kernels.
 
 CLI: python -m gym_continuousdoubleauction_amd.evaluate --policy P [--opponent random|FILE ...] --markets --agents --max-step --episodes --trained-slots
+     (a scripted opponent: pass | maker | taker | imbalance | NAME:key=value,...)
      [--sample] --seed --out JSON [--tape FILE.npz [--exec-report K[,K...]]]
 """
 import argparse
+import dataclasses
 import json
 import time
 
@@ -48,6 +50,8 @@ def _describe(x):
     from .mlp import FusedPolicy
     if isinstance(x, str):
         return x
+    if dataclasses.is_dataclass(x):
+        return repr(x)
     return "FusedPolicy" if isinstance(x, FusedPolicy) else str(x)
 
 
@@ -114,7 +118,9 @@ def _execution_report(env, horizons, module_of, names, episode0, keep):
 def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="greedy", seed=0, groups=None, keep=None, tape=None, tape_capacity=4096,
              exec_horizons=None):
     """Play `policy` (a FusedPolicy or a policy file) on `env` (a CDAVecEnv with auto_reset) for episodes * max_step steps; return per-module results.
-    opponents: None = self-play; else a list of "random", FusedPolicy objects or policy files, placed by slot_modules.  trained_slots: the policy's slots per
+    opponents: None = self-play; else a list of "random", FusedPolicy objects, policy files or scripted opponents - "pass", "maker", "taker", "imbalance",
+    "NAME:key=value,..." or a scripted.Profile (rule-based agents on the device: their slots carry LEAGUE_RANDOM in slot_net and their profile in the env's slot_script,
+    attached for the evaluation and detached afterwards) -, placed by slot_modules.  trained_slots: the policy's slots per
     market when there are opponents (default 1).  groups: rollout chains (default 4).  keep (a dict, optional): receives the RolloutChains object, the
     placement, the collected metric tables (agent table, env row) and host copies of every step's env actions (`actions`: category, size_mean, size_sigma,
     price, price_offset as [steps, N, A]) - what a replay needs.
@@ -146,8 +152,12 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
     if opp is not None and len(opp) == 0:
         raise ValueError("opponents: None (self-play) or a non-empty list")
     nets = []                                                           # (opponent index, FusedPolicy) of the network opponents
+    from .scripted import is_scripted_spec, parse_profile
+    scripts = {p: parse_profile(o) for p, o in enumerate(opp or []) if is_scripted_spec(o)}      # opponent index -> Profile (a bad 'NAME:key=value' raises here)
+    if scripts and env.scripted:
+        raise ValueError("evaluate() with scripted opponents needs an env without scripts attached: it attaches its own for the evaluated episodes (clear_scripted() first)")
     for p, o in enumerate(opp or []):
-        if isinstance(o, str) and o == RANDOM:
+        if (isinstance(o, str) and o == RANDOM) or p in scripts:
             continue
         act, vfs = (o.activation, o.vf_share_layers) if isinstance(o, FusedPolicy) else read_policy(o, with_activation=True, with_vf_share_layers=True)[1:]
         if act != pol.activation:
@@ -195,6 +205,12 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
                 slot_net[modules == 1 + p] = row_of.get(p, LEAGUE_RANDOM)
             bank.set_slots(torch.from_numpy(slot_net))
             driver = bank
+            if scripts:                                                  # the scripted modules' slots: the random module in slot_net, their profile in slot_script
+                order = sorted(scripts)
+                slot_script = np.zeros((N, A), dtype=np.int32)
+                for j, p in enumerate(order):
+                    slot_script[modules == 1 + p] = 1 + j
+                env.set_scripted(slot_script, [scripts[p] for p in order], seed=seed)      # before the chains are captured
         seeds = (np.uint64(int(seed) & (2 ** 63 - 1)) * np.uint64(N) + np.arange(N, dtype=np.uint64))
         env.reset(seed=seeds)
         env.collect_episode_metrics(clear=True)                          # nothing that ended before the reset counts
@@ -235,6 +251,8 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
         env.enable_episode_metrics(prev_metrics)
         if tape is not None:
             env.disable_tape()
+        if scripts and env.scripted:
+            env.clear_scripted()
     table_h, env_h = table.cpu().numpy(), env_row.cpu().numpy()
     summary = summarise(table_h, env_h, module_names=names)
     check_nav_conservation(0, summary, strict=True)
@@ -266,7 +284,7 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
 def main(argv=None):
     p = argparse.ArgumentParser(description="evaluate a saved policy (greedy by default) against opponents on the HIP env")
     p.add_argument("--policy", required=True, help="a policy file (ppo --save, league_train --save-dir)")
-    p.add_argument("--opponent", action="append", default=None, help="'random' or a policy file; repeat for several (market m plays opponent m mod P); none = self-play")
+    p.add_argument("--opponent", action="append", default=None, help="'random', a scripted opponent ('pass', 'maker', 'taker', 'imbalance', 'NAME:key=value,...') or a policy file; repeat for several (market m plays opponent m mod P); none = self-play")
     p.add_argument("--markets", type=int, default=1024)
     p.add_argument("--agents", type=int, default=4)
     p.add_argument("--max-step", type=int, default=256)

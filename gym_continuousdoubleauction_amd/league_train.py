@@ -194,6 +194,8 @@ def train_league_fused(env, iters=4, horizon=None, num_trainable=2, lr=5e-5, epo
     the running episode returns: the mapping, episode ids and promotions continue exactly.  Single-process runs only; no recorder.
     activation: `fcnet_activation` of the whole bank (mlp.PolicyBank: trainable policies and their champion snapshots share it); vf_share_layers likewise (RLlib's
     shared trunk for every net of the bank)."""
+    if getattr(env, "scripted", False):        # (a scripted slot's sample record is no policy sample: it must not reach a loss)
+        raise ValueError("train_league_fused does not train on an env with scripted opponents attached (training against them is out of scope): clear_scripted() first")
     import numpy as np
     from . import ppo
     from .mlp import EpisodeReturns, FusedUpdate, PolicyBank, RolloutChains

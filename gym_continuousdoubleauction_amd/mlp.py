@@ -627,8 +627,17 @@ class RolloutChains:
         self._joins = [torch.cuda.Event() for _ in range(G)]
         self.graphs = None
         self._have_obs, self._env_epoch = False, 0
+        self._script_checked = None
         self.use_graphs = bool(use_graphs)
         self.join_mode = "events"
+        self._check_scripted_slots()                               # (raise before anything is captured; run() looks again when the env's scripts changed)
+
+    def _check_scripted_slots(self):
+        """league chains: a scripted opponent may sit in opponent slots only (once per script epoch of the env)"""
+        if self.bank is not None and getattr(self.env, "scripted", False) and self._script_checked != self.env.script_epoch:
+            if bool((self.env.scripted_slots()[:, :self.bank.n_trainable] != 0).any()):
+                raise ValueError(f"a scripted opponent sits in a trainable slot (< n_trainable = {self.bank.n_trainable}): scripted modules play opponent slots only")
+            self._script_checked = self.env.script_epoch
 
     @property
     def counter(self):
@@ -660,6 +669,8 @@ class RolloutChains:
         self.graphs = graphs
         # the graphs hold the step instances and arguments of the env's trade-tape setting as it is now (tape-writing kernels and the rings' addresses, or neither)
         self._graph_tape_epoch = getattr(self.env, "tape_epoch", 0)
+        # ... and the scripted launches (or none) of the env's scripted opponents as attached now (CDAVecEnv.set_scripted / clear_scripted)
+        self._graph_script_epoch = getattr(self.env, "script_epoch", 0)
 
     def run(self):
         """one rollout of `horizon` steps; returns the buffer dict (views stay valid; the next run() overwrites them)"""
@@ -668,6 +679,10 @@ class RolloutChains:
         if self.graphs is not None and self._graph_tape_epoch != getattr(self.env, "tape_epoch", 0):
             raise RuntimeError("the env's trade tape was enabled or disabled after this RolloutChains captured its graphs: they would replay the step kernels and "
                                "tape buffers of the earlier setting - build a new RolloutChains")
+        if self.graphs is not None and self._graph_script_epoch != getattr(self.env, "script_epoch", 0):
+            raise RuntimeError("the env's scripted opponents were attached or detached after this RolloutChains captured its graphs: they would replay the "
+                               "launches of the earlier setting - build a new RolloutChains")
+        self._check_scripted_slots()
         if not self._have_obs or self._env_epoch != getattr(self.env, "host_epoch", 0):
             # the very first rollout - and the first one after the markets were reset / stepped from the HOST (env.host_epoch) - starts from the env's own
             # observation tensor; every other rollout continues from its predecessor's last observation (the chains do not write env.obs)

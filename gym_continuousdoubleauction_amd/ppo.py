@@ -558,6 +558,8 @@ def train_fused(env, iters=4, horizon=64, lr=5e-5, epochs=4, reward_scale=None, 
     from the newest checkpoint under checkpoint_dir, a path from that one: the env is restored instead of reset, and `iters` is the TARGET iteration count
     (iters_is_delta: that many more).  The resumed rollouts are bit-identical to the uninterrupted run's.  history entries carry the global iteration number.
     Single-process runs only (world == 1), without a recorder; chkpt_freq > 0 needs a checkpoint_dir (ValueError otherwise)."""
+    if getattr(env, "scripted", False):        # (a scripted slot's sample record is no policy sample: it must not reach a loss)
+        raise ValueError("train_fused does not train on an env with scripted opponents attached (training against them is out of scope): clear_scripted() first")
     from .mlp import EpisodeReturns, FusedPolicy, FusedUpdate, RolloutChains
     obj = dict(PPO_DEFAULTS)
     obj.update(objective or {})

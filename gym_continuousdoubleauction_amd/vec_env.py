@@ -4,6 +4,7 @@ Host-side mirror of the reference env surface (continuousDoubleAuction_env.py:21
 `reset()` / `step()` over torch tensors that stay resident in HBM.  All compute happens in the HIP
 kernels behind the C-ABI (include/cda.h); PyTorch is only used for device memory and streams.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -17,6 +18,9 @@ _TORCH_OF = {C.c_int32: torch.int32, C.c_double: torch.float64, C.c_uint8: torch
 DEC_DTYPE = K.DEC_DTYPE
 
 ACTION_KEYS = ("category", "size_mean", "size_sigma", "price", "price_offset")
+
+# what set_scripted keeps: the two resident device tables (slot_script i32 [N, A], profiles u8 [n, 64]), the Profile objects, the draws' keys, and the slot table on the host
+AttachedScripts = collections.namedtuple("AttachedScripts", "slot_script profiles_dev profiles seed market_index_base slots_host")
 
 
 class CDAVecEnv:
@@ -40,6 +44,8 @@ class CDAVecEnv:
                                             # their own copy of the observations across calls (mlp.RolloutChains) compare it to know when theirs is stale
         self.tape_epoch = 0                 # bumped by enable_tape / disable_tape: graphs captured on this env's step launches hold the setting they were captured under
         self._tape_cursor = None            # drain_tape's default cursor (i64 [N], device) while the tape is on
+        self.script_epoch = 0               # bumped by set_scripted / clear_scripted: graphs captured on this env's rollout chains hold the scripted launches (or none) of then
+        self._script = None                 # set_scripted: an AttachedScripts (None while nothing is attached)
         self.num_agents = self.cfg_struct.num_agents
         self.n_hist = self.cfg_struct.n_hist
         self.obs_dim = self.n_hist * K.SNAPSHOT_DIM
@@ -624,7 +630,7 @@ class CDAVecEnv:
             raise ValueError(f"episode must be 'current' or 'previous', got {episode!r}")
         return K.TAPE_EPISODES[episode]
 
-    def _tape_range(self, what, first_market, n_markets):
+    def _market_range(self, what, first_market, n_markets):
         n = self.n_markets - int(first_market) if n_markets is None else int(n_markets)
         if not (0 <= int(first_market) and n >= 1 and int(first_market) + n <= self.n_markets):
             raise ValueError(f"{what}: range [{first_market}, {int(first_market) + n}) is outside the env's {self.n_markets} markets")
@@ -637,7 +643,7 @@ class CDAVecEnv:
         all zeros.  info: records aggregated, records of the episode the ring had already overwritten, records beyond the last bar, partial flag.
         episode: "current", or "previous" = the episode that ended at the market's last reset.  n_bars defaults to ceil(max_step / bar_steps), largest max_step."""
         self._need_tape("tape_bars()")
-        first, n = self._tape_range("tape_bars", first_market, n_markets)
+        first, n = self._market_range("tape_bars", first_market, n_markets)
         which = self._tape_which(episode)
         if int(bar_steps) < 1:
             raise ValueError(f"tape_bars: bar_steps must be >= 1, got {bar_steps}")
@@ -657,7 +663,7 @@ class CDAVecEnv:
         """Who trades with whom in one remembered episode (include/cda.h cda_tape_flows): (flows i64 [n, A, A, 3], info i32 [n, 4]), device tensors;
         flows[i, init_id, counter_id] = (quantity, notional = price x quantity, fills), the diagonal holds the self-trades.  info as tape_bars (its third word is 0)."""
         self._need_tape("tape_flows()")
-        first, n = self._tape_range("tape_flows", first_market, n_markets)
+        first, n = self._market_range("tape_flows", first_market, n_markets)
         which = self._tape_which(episode)
         self.join()
         a = self.num_agents
@@ -678,7 +684,7 @@ class CDAVecEnv:
         first held record."""
         from .tape import _horizons
         self._need_tape("tape_exec()")
-        first, n = self._tape_range("tape_exec", first_market, n_markets)
+        first, n = self._market_range("tape_exec", first_market, n_markets)
         which = self._tape_which(episode)
         hz = _horizons(horizons)
         self.join()
@@ -701,7 +707,7 @@ class CDAVecEnv:
 
     # ------------------------------------------------------------------ the book report: reductions over the standing book, on the device
     def _book_call(self, name, first_market, n_markets, shape, dtype, *mid):
-        first, n = self._tape_range(name, first_market, n_markets)
+        first, n = self._market_range(name, first_market, n_markets)
         self.join()
         with torch.cuda.device(self.device):
             out = torch.empty((n,) + shape, dtype=dtype, device=self.device)
@@ -741,7 +747,7 @@ class CDAVecEnv:
         """The Level-3 dump of all markets in two launches (cda_book_offsets, cda_book_pack): (orders i32 [total, 5] - get_book()'s rows (price, qty, owner,
         order_id, timestamp), queue order -, offsets i64 [2 n + 1]): side s of market first_market + i owns rows offsets[2 i + s] : offsets[2 i + s + 1].
         Device tensors; the one host read is the 8-byte total.  book.split_orders() cuts them into per-market (bids, asks) pairs."""
-        first, n = self._tape_range("book_orders", first_market, n_markets)
+        first, n = self._market_range("book_orders", first_market, n_markets)
         self.join()
         with torch.cuda.device(self.device):
             off = torch.empty(2 * n + 1, dtype=torch.int64, device=self.device)
@@ -750,6 +756,105 @@ class CDAVecEnv:
             rows = torch.empty((total, 5), dtype=torch.int32, device=self.device)
             check(lib().cda_book_pack(self._h, first, n, off.data_ptr(), total, rows.data_ptr() if total else None, total, self._stream()), "cda_book_pack")
         return rows, off
+
+    # ------------------------------------------------------------------ scripted opponents: rule-based agents on the device (scripted.py states the laws)
+    @property
+    def scripted(self):
+        return self._script is not None
+
+    def set_scripted(self, slot_script, profiles, seed=0, market_index_base=0):
+        """Attach scripted opponents (include/cda.h cda_scripted_attach): slot_script int [N, A], 0 = the slot is not scripted, 1 + k = it plays profiles[k];
+        profiles: 1 .. 16 scripted.Profile objects (or names / 'NAME:key=value' strings).  `seed` keys the taker's draws, market_index_base + market is the
+        market's index in them.  The two tables become resident tensors the env keeps; rollout chains and run_scripted() then play the laws.  While attached
+        the one-launch policy step is off (cda_policy_step_supported answers 0) and the fused trainers refuse the env."""
+        from .scripted import MAX_PROFILES, parse_profile, profiles_array
+        profs = [parse_profile(p) for p in profiles]
+        if not 1 <= len(profs) <= MAX_PROFILES:
+            raise ValueError(f"between 1 and {MAX_PROFILES} profiles, got {len(profs)}")
+        slots = np.ascontiguousarray(np.asarray(slot_script.detach().cpu().numpy() if hasattr(slot_script, "detach") else slot_script).astype(np.int64))
+        if slots.shape != (self.n_markets, self.num_agents):
+            raise ValueError(f"slot_script must have shape {(self.n_markets, self.num_agents)}, got {slots.shape}")
+        if slots.min() < 0 or slots.max() > len(profs):
+            raise ValueError(f"slot_script values must lie in 0 .. {len(profs)} (0 = not scripted, 1 + k = profile k)")
+        slot_t = torch.from_numpy(slots.astype(np.int32)).to(self.device)
+        prof_t = torch.from_numpy(profiles_array(profs).view(np.uint8).reshape(len(profs), 64).copy()).to(self.device)
+        self.sync()
+        with torch.cuda.device(self.device):
+            check(lib().cda_scripted_attach(self._h, slot_t.data_ptr(), prof_t.data_ptr(), len(profs), int(seed) & (2 ** 64 - 1), int(market_index_base) & (2 ** 64 - 1)),
+                  "cda_scripted_attach")
+        self._script = AttachedScripts(slot_t, prof_t, profs, int(seed) & (2 ** 64 - 1), int(market_index_base) & (2 ** 64 - 1), slots.astype(np.int32))
+        self.script_epoch += 1
+
+    def clear_scripted(self):
+        self.sync()
+        check(lib().cda_scripted_detach(self._h), "cda_scripted_detach")
+        self._script = None
+        self.script_epoch += 1
+
+    def scripted_slots(self):
+        """the attached slot table as a host array i32 [N, A] (zeros while nothing is attached)"""
+        return self._script.slots_host if self._script is not None else np.zeros((self.n_markets, self.num_agents), np.int32)
+
+    def scripted_profiles(self):
+        return list(self._script.profiles) if self._script is not None else []
+
+    def _action_buffers(self):
+        N, A, dev = self.n_markets, self.num_agents, self.device
+        return {"category": torch.zeros((N, A), dtype=torch.int32, device=dev), "size_mean": torch.zeros((N, A), dtype=torch.float32, device=dev),
+                "size_sigma": torch.zeros((N, A), dtype=torch.float32, device=dev), "price": torch.zeros((N, A), dtype=torch.int32, device=dev),
+                "price_offset": torch.ones((N, A), dtype=torch.int32, device=dev)}
+
+    def scripted_actions(self, draw=0, counter=0, out=None, first_market=0, n_markets=None):
+        """Every scripted slot's action of the markets' state NOW (include/cda.h cda_scripted_actions; scripted.actions_from_views is its specification): one
+        launch on the caller's stream, ordered after every group's last step, no host synchronisation.  out: a dict of the five [N, A] action tensors (ACTION_KEYS;
+        optionally 'a_cont' f32 [N, A, 2], 'logp' f32 [N, A], 'record' f32 [N, A, 8]) written in place where a slot is scripted and left alone elsewhere; None =
+        fresh tensors holding a pass everywhere else.  counter: an int, or an i64 [1] device tensor read on the device.  Nothing attached: nothing is written."""
+        first, n = self._market_range("scripted_actions", first_market, n_markets)
+        if out is None:
+            out = self._action_buffers()
+        dts = {"category": torch.int32, "size_mean": torch.float32, "size_sigma": torch.float32, "price": torch.int32, "price_offset": torch.int32,
+               "a_cont": torch.float32, "logp": torch.float32, "record": torch.float32}
+        per = {"a_cont": 2, "record": 8}
+        for k, t in out.items():
+            if k in dts:
+                assert t.dtype == dts[k] and t.is_contiguous() and t.device == self.device and t.numel() == self.n_markets * self.num_agents * per.get(k, 1), k
+        if isinstance(counter, torch.Tensor):
+            assert counter.dtype == torch.int64 and counter.device == self.device and counter.numel() >= 1
+            ctr = counter
+        elif int(counter) == 0:
+            ctr = None
+        else:
+            ctr = torch.tensor([int(counter)], dtype=torch.int64, device=self.device)
+        self.join()
+        opt = lambda k: out[k].data_ptr() if k in out else None     # noqa: E731
+        with torch.cuda.device(self.device):
+            check(lib().cda_scripted_actions(self._h, first, n, ctr.data_ptr() if ctr is not None else None, int(draw), *(out[k].data_ptr() for k in ACTION_KEYS),
+                                             opt("a_cont"), opt("logp"), opt("record"), self._stream()), "cda_scripted_actions")
+        if ctr is not None:
+            ctr.record_stream(torch.cuda.current_stream(self.device))
+        return out
+
+    def run_scripted(self, n_steps, others="pass", action_seed=0, draw0=None):
+        """Step the env n_steps times with every scripted slot playing its law: per step {the other slots' actions, cda_scripted_actions, step}, all on the
+        device, no host synchronisation inside the loop.  others: what the slots that are not scripted play - 'pass', or 'random' = the uniform random stream
+        (random_actions_device keyed action_seed and the draw number).  The taker's draw number of step k is draw0 + k; draw0 = None continues where the last
+        run_scripted stopped.  Returns step()'s tuple of the last step."""
+        if self._script is None:
+            raise RuntimeError("run_scripted() needs scripted opponents: call set_scripted() first")
+        if others not in ("pass", "random"):
+            raise ValueError(f"others must be 'pass' or 'random', got {others!r}")
+        d = int(getattr(self, "_script_draw", 0) if draw0 is None else draw0)
+        acts = self._action_buffers()
+        ret = None
+        for k in range(int(n_steps)):
+            if others == "random":
+                with torch.cuda.device(self.device):
+                    check(lib().cda_random_actions(int(action_seed) & (2 ** 64 - 1), self._script.market_index_base, d + k, 1, self.n_markets, self.num_agents,
+                                                   *(acts[key].data_ptr() for key in ACTION_KEYS), self._stream()), "cda_random_actions")
+            self.scripted_actions(draw=d + k, out=acts)
+            ret = self.step(acts)
+        self._script_draw = d + int(n_steps)
+        return ret
 
     # ------------------------------------------------------------------ snapshots, forks and resumable runs
     def snapshot(self, first=0, n=None):

@@ -669,6 +669,37 @@ int cda_book_offsets(cda_env* env, int32_t first_market, int32_t n_markets, int6
 int cda_book_pack(cda_env* env, int32_t first_market, int32_t n_markets, const int64_t* offsets_dev, int64_t total_orders, void* orders_out_dev,
                   int64_t capacity_orders, void* stream);
 
+/* ---- scripted opponents: rule-based agents on the device ---------------------------------------------------------------------------------
+ * The laws (pass, noise taker, market maker, order-imbalance trader), their 64-byte cda_script_profile and the integer cda_script_view they read are stated
+ * once, in include/cda_scripted_agents.h (cda_scripted_decide); the reference has no such opponent.  The pointers below named profiles / views are arrays of
+ * those structs.
+ *   cda_scripted_attach   slot_script_dev i32 [N][A] (device): 0 = the slot is not scripted, 1 + k = it plays profiles_dev[k]; profiles_dev: n_profiles
+ *                         (1 .. 16) profiles (device, 8-B aligned).  Both tables are read back and vetted first: an invalid profile or a slot value outside
+ *                         0 .. n_profiles returns CDA_ERR_INVALID and changes nothing (synchronous).  The env KEEPS the two pointers - the caller's resident
+ *                         tensors, the scheme of cda_league.slot_net - so a captured graph stays valid while their contents change; `seed` keys the taker's
+ *                         draws, market_index_base + market is the market's global index in them (the shards of a multi-GPU run draw as the whole would).
+ *   cda_scripted_detach   forgets them.  Every attach and detach moves cda_scripted_epoch (a graph captured under another epoch holds stale launches);
+ *                         while scripts are attached cda_policy_step_supported answers 0, as it does for the tape.
+ *   cda_scripted_actions  ONE launch on `stream`, a wave per market of the range: every scripted slot's action of the market's state NOW, into the five
+ *                         FULL [N][A] action arrays (indexed by global market, as cda_step_range reads them), and - where given - a_cont f32 [N][A][2] = 0, 0,
+ *                         logp f32 [N][A] = 0 and the 32-byte sample record f32 [N][A][8] as the league's random module writes it (category, price,
+ *                         price_offset, 0 | 0, 0; words 6, 7 untouched; 16-B aligned).  Slots that are not scripted keep their bytes; the arena is only
+ *                         read.  The taker's draw is keyed (seed, *counter_dev or 0 when NULL, global market, draw, agent).  Nothing attached: CDA_OK, no launch.
+ *                         cda_mlp_rollout_chain and its league / eval siblings call it between the policy launch and the step.
+ *   cda_scripted_decide_host   the same function on host arrays, no device: item i plays profiles_host[profile_index_host[i]] on views_host[i] with the key
+ *                         (seed, counter, market_host[i], draw_host[i], agent_host[i]).  cda_scripted_profile_check_host: CDA_OK iff every profile is valid. */
+int cda_scripted_attach(cda_env* env, const int32_t* slot_script_dev, const void* profiles_dev, int32_t n_profiles, uint64_t seed, uint64_t market_index_base);
+int cda_scripted_detach(cda_env* env);
+int64_t cda_scripted_epoch(const cda_env* env);
+int cda_scripted_attached(const cda_env* env);
+int cda_scripted_actions(cda_env* env, int32_t first_market, int32_t n_markets, const int64_t* counter_dev, int64_t draw,
+                         int32_t* category, float* size_mean, float* size_sigma, int32_t* price, int32_t* price_offset,
+                         float* a_cont, float* logp, float* record, void* stream);
+int cda_scripted_decide_host(const void* profiles_host, int32_t n_profiles, const int32_t* profile_index_host, const void* views_host, int64_t n,
+                             uint64_t seed, uint64_t counter, const uint64_t* market_host, const uint32_t* draw_host, const uint32_t* agent_host,
+                             int32_t* category, float* size_mean, float* size_sigma, int32_t* price, int32_t* price_offset);
+int cda_scripted_profile_check_host(const void* profiles_host, int32_t n_profiles);
+
 /* ---- per-market parameters: many configurations in one env ----------------------------------------------------------------------------
  * Every market reads the fields below from a row of its own (a device table every env has; cda_create fills each row from the config).  The
  * config's other fields - num_agents, n_hist, book_capacity, book_spill, auto_reset - set shapes, memory and kernel choice and hold for the

@@ -1,0 +1,372 @@
+"""GPU: the scripted opponents on the device (csrc/cda_scripted.inc k_script_actions; CDAVecEnv.set_scripted / scripted_actions / run_scripted; the rollout
+chains; evaluate) against the numpy specification (gym_continuousdoubleauction_amd/scripted.py), word for word.  The specification's inputs are independent
+readings of the same state: book_levels(10), book_agents(), get_state (t_step, positions), market_config (tick) - or the CPU oracle's books and accounts."""
+import dataclasses
+
+import numpy as np
+import pytest
+import torch
+
+import oracle_lib as O
+from gym_continuousdoubleauction_amd import _capi as K
+from gym_continuousdoubleauction_amd import book as B
+from gym_continuousdoubleauction_amd import scripted as S
+from gym_continuousdoubleauction_amd.scripted import Profile
+from test_scripted_host import IMB, MAKER, PASS, TAKER, same_actions, views_of_books
+
+pytestmark = pytest.mark.gpu
+
+RICH = 10 ** 12
+KEYS = ("category", "size_mean", "size_sigma", "price", "price_offset")
+MIXED = [PASS, dataclasses.replace(TAKER, p_trade_q32=1 << 31, max_position=40, size_mean=0.05, size_sigma=0.05),
+         dataclasses.replace(MAKER, max_position=30, skew_position=10, max_orders=3, size_mean=0.02, size_sigma=0.02),
+         dataclasses.replace(MAKER, max_position=8, skew_position=0, max_orders=1, size_mean=0.03, size_sigma=0.0),
+         dataclasses.replace(IMB, depth_levels=1, imb_num=1, imb_den=1, max_position=25, size_mean=0.04, size_sigma=0.02),
+         dataclasses.replace(IMB, depth_levels=10, imb_num=3, imb_den=2, max_position=60, size_mean=0.04, size_sigma=0.02)]
+
+
+def mixed_slots(n, a, k=len(MIXED)):
+    m, j = np.meshgrid(np.arange(n), np.arange(a), indexing="ij")
+    return (1 + (m * 5 + j * 7 + m // 3) % k).astype(np.int32)
+
+
+def spec_on_env(env, seed, counter, draw, base=0, branches=None):
+    """the specification's actions [N, A] from independent readings of the device's state"""
+    n, a = env.n_markets, env.num_agents
+    slots, profiles = env.scripted_slots(), env.scripted_profiles()
+    pix = np.maximum(slots - 1, 0)
+    depth = np.array([p.depth_levels for p in profiles])[pix]
+    states = [env.get_state(i) for i in range(n)]
+    pos = [[int(s.acc[j].net_position) for j in range(a)] for s in states]
+    tick = [int(env.market_config(i)["tick_size"]) for i in range(n)]
+    views = S.views_from_report(env.book_levels(S.MAX_DEPTH), env.book_agents(), pos, [int(s.t_step) for s in states], tick, depth)
+    m, j = np.meshgrid(np.arange(n), np.arange(a), indexing="ij")
+    return S.actions_from_views(profiles, pix, views, seed, counter, base + m, draw, j, branches=branches), slots != 0
+
+
+def device_equals_spec(env, seed, counter, draw, base=0, branches=None, tag=""):
+    want, scripted = spec_on_env(env, seed, counter, draw, base, branches)
+    got = env.scripted_actions(draw=draw, counter=counter)
+    got = tuple(got[k].cpu().numpy() for k in KEYS)
+    for k, g, w in zip(KEYS, got, want):
+        assert np.array_equal(g[scripted].view(np.uint32), w[scripted].view(np.uint32)), (tag, k, np.argwhere((g != w) & scripted)[:4])
+    return got
+
+
+@pytest.mark.parametrize("n,a,tile", [(64, 4, 0), (32, 8, 0), (16, 16, 0), (16, 16, 512), (32, 8, 512)])
+def test_device_equals_specification(n, a, tile):
+    """every slot scripted, the six profiles mixed across slots (all four laws in every market row), two tick sizes; right after reset (empty books), after 50 and
+    after 300 steps of run_scripted"""
+    from gym_continuousdoubleauction_amd import CDAVecEnv
+    cfg = {"num_of_agents": a, "init_cash": 10 ** 9, "max_step": 4096, "is_render": False, "book_capacity": tile}
+    env = CDAVecEnv(cfg, n_markets=n, device="cuda:0", with_info=False, market_configs=[{"tick_size": 1 if i % 2 == 0 else 5} for i in range(n)])
+    if tile:
+        assert env.book_capacity == tile
+    env.reset(seed=900)
+    env.set_scripted(mixed_slots(n, a), MIXED, seed=77, market_index_base=1000)
+    tally = {}
+    device_equals_spec(env, 77, 0, 0, 1000, tally, "after reset")
+    env.run_scripted(50)
+    device_equals_spec(env, 77, 3, 50, 1000, tally, "after 50")
+    ctr = torch.tensor([9], dtype=torch.int64, device="cuda:0")           # the counter read on the device
+    a_dev = env.scripted_actions(draw=50, counter=ctr)
+    a_int = env.scripted_actions(draw=50, counter=9)
+    assert all(torch.equal(a_dev[k], a_int[k]) for k in KEYS)
+    env.run_scripted(250)
+    got = device_equals_spec(env, 77, 1, 300, 1000, tally, "after 300")
+    counts = env.book_counts().cpu().numpy()
+    assert counts[:, :, 0].sum() > 0 and len(set(got[0].reshape(-1).tolist())) >= 4              # books stand, and the laws do different things on them
+    assert int(env.get_state(0).t_step) == 300
+    assert (env.flags().cpu().numpy() == 0).all() and (env.check_invariants().cpu().numpy() == 0).all()
+    env.close()
+
+
+def test_deep_books():
+    """four markets prefilled with 400 + 400 orders: both sides continue in the HBM ring behind the 256-order tile (asserted from the ring counts)"""
+    from fuzz_cases import prefill_book
+    from hip_env import HipEnv
+    from test_hip_book_report import _ring_meta
+    a = 4
+    hip = HipEnv({"num_of_agents": a, "init_cash": RICH, "max_step": 4096, "is_render": False}, 4, with_info=False)
+    hip.reset(np.arange(70, 74, dtype=np.uint64))
+    for i in range(4):
+        prefill_book(hip, i, np.random.default_rng(60 + i), a, 400, 400)
+    env = hip.env
+    for i in range(4):
+        tails, _ = _ring_meta(env, i)
+        assert tails[0] > 0 and tails[1] > 0, (i, tails)
+    deep = [dataclasses.replace(MAKER, max_orders=150), dataclasses.replace(MAKER, max_orders=90, max_position=0, skew_position=0),
+            dataclasses.replace(IMB, depth_levels=10, imb_num=1, imb_den=1), dataclasses.replace(IMB, depth_levels=4)]
+    env.set_scripted(mixed_slots(4, a, 4), deep, seed=5)
+    got = device_equals_spec(env, 5, 0, 0, tag="prefilled")
+    assert (env.book_agents().cpu().numpy()[:, :, :, 0] > 64).any()     # own-order counts beyond one pass of the walk
+    assert set(got[0].reshape(-1).tolist()) & {3, 7}                      # ... and at max_orders: the modify path
+    env.run_scripted(6)
+    device_equals_spec(env, 5, 2, 6, tag="prefilled + 6 steps")
+    assert (env.check_invariants().cpu().numpy() == 0).all()
+    hip.close()
+
+
+def test_wrapped_ring():
+    """the recipe of test_hip_book_report.test_ring_wrap: a 64-slot ring whose live window crosses the ring's end (asserted)"""
+    from hip_env import HipEnv
+    from test_hip_book_report import _ring_meta
+    hip = HipEnv({"num_of_agents": 4, "init_cash": RICH, "max_step": 64, "is_render": False, "book_spill": 64}, 1, with_info=False)
+    hip.reset(np.array([500], dtype=np.uint64))
+
+    def do(tr, typ, side, size, price):
+        hip.place_order(0, tr, typ, side, size, price)
+
+    for k in range(256):
+        do(k % 4, K.T_LIMIT, K.S_BID, 1, 20000 - 2 * k)
+    for k in range(64):
+        do(k % 4, K.T_LIMIT, K.S_BID, 2, 10000 - k)
+    do(0, K.T_MARKET, K.S_ASK, 230, 1)
+    for k in range(166 + 24):
+        do(k % 4, K.T_LIMIT, K.S_BID, 3, 9000 - k)
+    for k in range(6):
+        do(k % 4, K.T_LIMIT, K.S_BID, 1, 19001 - 2 * k)
+    tails, bases = _ring_meta(hip.env, 0)
+    assert tails[0] == 56 and (bases[0] & 63) + tails[0] > 64, (tails, bases)
+    env = hip.env
+    env.set_scripted(np.array([[1, 2, 3, 4]]), [dataclasses.replace(MAKER, max_orders=72), dataclasses.replace(MAKER, max_orders=71),
+                                                dataclasses.replace(IMB, depth_levels=10, imb_num=1, imb_den=1, max_position=10 ** 6), dataclasses.replace(IMB, depth_levels=2)], seed=1)
+    got = device_equals_spec(env, 1, 0, 0, tag="wrapped")
+    # bids only: the imbalance trader buys (its cap lies far above the position it holds from the 230-unit sell that hit its bids; agent 3, cap 5, is capped)
+    assert got[0][0, 2] == 1 and got[0][0, 3] == 0 and int(env.get_state(0).acc[3].net_position) >= 5
+    hip.close()
+
+
+def _set_position(env, market, agent, pos):
+    s = env.get_state(market)
+    s.acc[agent].net_position = pos
+    env.set_state(market, s)
+
+
+def test_hand_built_states_reach_every_branch():
+    """20 markets x 4 agents seeded with place_order / set_state: agent 0 and 1 makers (cap 10, skew 4, 2 orders a side), agent 2 the imbalance trader (3 : 2 over
+    three levels, cap 5), agent 3 a taker that always trades (cap 3) - a pass module in market 0, a taker that never trades in market 1.  The tally at the end
+    names every branch of every law (the maker's: side rule x limit / modify x inside / join) and is a condition on these cases only."""
+    from hip_env import HipEnv
+    n, a = 20, 4
+    hip = HipEnv({"num_of_agents": a, "init_cash": RICH, "max_step": 64, "is_render": False}, n, with_info=False)
+    hip.reset(np.arange(n, dtype=np.uint64) + 10)
+    env = hip.env
+    bid = lambda m, tr, size, price: hip.place_order(m, tr, K.T_LIMIT, K.S_BID, size, price)      # noqa: E731
+    ask = lambda m, tr, size, price: hip.place_order(m, tr, K.T_LIMIT, K.S_ASK, size, price)      # noqa: E731
+    # 0: an empty book.  1: a one-tick spread.  2: a wide spread, the makers at best.  3: wide, the makers behind the best
+    bid(1, 2, 5, 100); ask(1, 2, 5, 101)
+    bid(2, 0, 5, 100); ask(2, 1, 5, 110)
+    bid(3, 2, 5, 100); ask(3, 2, 5, 110); bid(3, 0, 5, 98); ask(3, 1, 5, 112)
+    # 4: max_orders on the makers' sides -> modify.  5: no bids.  6: no asks
+    bid(4, 2, 5, 100); ask(4, 2, 5, 110); bid(4, 0, 1, 98); bid(4, 0, 1, 97); ask(4, 1, 1, 112); ask(4, 1, 1, 113)
+    ask(5, 2, 5, 110)
+    bid(6, 2, 5, 100)
+    # 7: beyond the cap -> the inventory stop.  8: beyond the skew -> the reducing side only
+    bid(7, 2, 5, 100); ask(7, 2, 5, 110); _set_position(env, 7, 0, 11); _set_position(env, 7, 1, -11)
+    bid(8, 2, 5, 100); ask(8, 2, 5, 110); _set_position(env, 8, 0, 5); _set_position(env, 8, 1, -5)
+    # 9 .. 13: the imbalance over / at / under 3 : 2, a fourth level that does not count, the position cap on both sides
+    for m, (bv, av, pos) in zip(range(9, 14), ((31, 20, 0), (20, 31, 0), (30, 20, 0), (31, 20, 5), (20, 31, -5))):
+        bid(m, 0, bv - 2, 100); bid(m, 1, 1, 99); bid(m, 3, 1, 98); bid(m, 0, 50, 90)
+        ask(m, 1, av - 2, 110); ask(m, 0, 1, 111); ask(m, 3, 1, 112)
+        _set_position(env, m, 2, pos)
+    # 14, 15: the taker at its caps
+    _set_position(env, 14, 3, 3); _set_position(env, 15, 3, -3)
+    # 16: a one-tick spread with max_orders behind it -> modify, join.  17: beyond the skew, max_orders behind the best of a wide spread -> modify, inside
+    bid(16, 2, 5, 100); ask(16, 2, 5, 101); bid(16, 0, 1, 98); bid(16, 0, 1, 97); ask(16, 1, 1, 103); ask(16, 1, 1, 104)
+    bid(17, 2, 5, 100); ask(17, 2, 5, 110); ask(17, 0, 1, 112); ask(17, 0, 1, 113); bid(17, 1, 1, 98); bid(17, 1, 1, 97)
+    _set_position(env, 17, 0, 5); _set_position(env, 17, 1, -5)
+    # 18: beyond the skew at a one-tick spread -> limit, join.  19: ... with max_orders on the reducing side -> modify, join
+    bid(18, 2, 5, 100); ask(18, 2, 5, 101); _set_position(env, 18, 0, 5); _set_position(env, 18, 1, -5)
+    bid(19, 2, 5, 100); ask(19, 2, 5, 101); ask(19, 0, 1, 103); ask(19, 0, 1, 104); bid(19, 1, 1, 98); bid(19, 1, 1, 97)
+    _set_position(env, 19, 0, 5); _set_position(env, 19, 1, -5)
+    slots = np.tile(np.array([[1, 1, 2, 3]], np.int32), (n, 1))
+    slots[0, 3] = 4
+    slots[1, 3] = 5
+    env.set_scripted(slots, [MAKER, IMB, TAKER, PASS, dataclasses.replace(TAKER, p_trade_q32=0)], seed=21)
+    tally = {}
+    for draw in range(10):                                               # (ten draws: the taker buys and sells at both caps)
+        got = device_equals_spec(env, 21, 0, draw, branches=tally, tag=f"draw {draw}")
+    cat, off = got[0], got[4]
+    assert cat[0, :2].tolist() == [2, 6] and off[0, :2].tolist() == [1, 1]                      # empty book: bid / ask by parity, join
+    assert cat[1, :2].tolist() == [2, 6] and off[1, :2].tolist() == [1, 1]                      # one tick: join
+    assert off[2, :2].tolist() == [1, 1] and off[3, :2].tolist() == [2, 2]                      # at best: join; behind it: inside
+    assert cat[4, :2].tolist() == [3, 7] and off[4, :2].tolist() == [2, 2]
+    assert off[5, 0] == 1 and off[6, 1] == 1
+    assert cat[7, :2].tolist() == [5, 1] and cat[8, :2].tolist() == [6, 2]
+    assert cat[9:14, 2].tolist() == [1, 5, 0, 0, 0]
+    assert cat[16, :2].tolist() == [3, 7] and off[16, :2].tolist() == [1, 1]
+    assert cat[17, :2].tolist() == [7, 3] and off[17, :2].tolist() == [2, 2]
+    assert cat[18, :2].tolist() == [6, 2] and off[18, :2].tolist() == [1, 1]
+    assert cat[19, :2].tolist() == [7, 3] and off[19, :2].tolist() == [1, 1]
+    assert cat[1, 3] == 0                                                                       # p = 0: the taker idles
+    need = {"law_pass", "taker_buy", "taker_sell", "taker_buy_capped", "taker_sell_capped", "taker_idle", "maker_stop_sell", "maker_stop_buy", "imb_buy", "imb_sell",
+            "imb_balanced", "imb_buy_capped", "imb_sell_capped"}
+    need |= {f"maker_{side}_{what}_{where}" for side in ("alt_bid", "alt_ask", "skew_bid", "skew_ask") for what in ("limit", "modify") for where in ("inside", "join")}
+    assert need <= set(tally), sorted(need - set(tally))
+    hip.close()
+
+
+def test_slots_that_are_not_scripted_keep_their_bytes():
+    from gym_continuousdoubleauction_amd import CDAVecEnv
+    n, a = 24, 8
+    env = CDAVecEnv({"num_of_agents": a, "init_cash": 10 ** 9, "max_step": 4096, "is_render": False}, n_markets=n, device="cuda:0", with_info=False)
+    env.reset(seed=4)
+    slots = mixed_slots(n, a)
+    slots[:, ::2] = 0
+    slots[5] = 0                                                         # a market without any scripted slot
+    g = torch.Generator().manual_seed(1)
+    out = {k: torch.randint(-2 ** 31, 2 ** 31 - 1, (n, a) + sh, generator=g, dtype=torch.int64).to(torch.int32).to("cuda:0") for k, sh in
+           (("category", ()), ("size_mean", ()), ("size_sigma", ()), ("price", ()), ("price_offset", ()), ("a_cont", (2,)), ("logp", ()), ("record", (8,)))}
+    out = {k: (v if k in ("category", "price", "price_offset") else v.view(torch.float32)) for k, v in out.items()}
+    before = {k: v.clone() for k, v in out.items()}
+    env.scripted_actions(draw=3, out=out)                                 # nothing attached: nothing is written
+    assert all(torch.equal(out[k].view(torch.int32), before[k].view(torch.int32)) for k in out)
+    env.set_scripted(slots, MIXED, seed=8)
+    env.run_scripted(20, others="random", action_seed=3)
+    env.scripted_actions(draw=3, out=out, first_market=2, n_markets=20)   # ... and markets outside the range are not touched either
+    want, _ = spec_on_env(env, 8, 0, 3)
+    on = torch.from_numpy(slots != 0).to("cuda:0")
+    on[:2] = False; on[22:] = False
+    for k in out:
+        o, b = out[k].view(torch.int32), before[k].view(torch.int32)
+        assert torch.equal(o[~on], b[~on]), k
+    onh = on.cpu().numpy()
+    for k, w in zip(KEYS, want):
+        assert np.array_equal(out[k].cpu().numpy()[onh].view(np.uint32), w[onh].view(np.uint32)), k
+    rec = out["record"].view(torch.int32)[on].cpu().numpy()
+    assert np.array_equal(rec[:, 0], want[0][onh]) and np.array_equal(rec[:, 1], want[3][onh]) and np.array_equal(rec[:, 2], want[4][onh]) and (rec[:, 3:6] == 0).all()
+    assert np.array_equal(rec[:, 6:], before["record"].view(torch.int32)[on].cpu().numpy()[:, 6:])       # the advantage / return words are the update's
+    assert (out["a_cont"][on] == 0).all() and (out["logp"][on] == 0).all()
+    env.close()
+
+
+CHAIN_N, CHAIN_A, CHAIN_T = 32, 8, 12
+CHAIN_CFG = {"num_of_agents": CHAIN_A, "init_cash": 1000000, "max_step": 4096, "is_render": False}
+
+
+def _chain_env(scripts):
+    from gym_continuousdoubleauction_amd import CDAVecEnv
+    env = CDAVecEnv(dict(CHAIN_CFG, auto_reset=True), n_markets=CHAIN_N, device="cuda:0", with_info=False)
+    env.reset(seed=300)
+    if scripts:
+        slots = mixed_slots(CHAIN_N, CHAIN_A)
+        slots[:, :2] = 0
+        env.set_scripted(slots, MIXED, seed=13, market_index_base=64)
+    return env
+
+
+def _driver(kind):
+    from gym_continuousdoubleauction_amd import mlp
+    pol = mlp.FusedPolicy("cuda:0", seed=1)
+    if kind == "shared":
+        return pol, dict(greedy=False)
+    other = mlp.FusedPolicy("cuda:0", seed=2)
+    bank = mlp.PolicyBank("cuda:0", CHAIN_N, CHAIN_A, n_trainable=1, max_frozen=1, random_seed=13)
+    bank.theta[0].copy_(pol.theta); bank.wb[0].copy_(pol.wb)
+    bank.n_frozen += 1
+    bank.theta[1].copy_(other.theta); bank.wb[1].copy_(other.wb)
+    bank._refresh()
+    slot_net = np.full((CHAIN_N, CHAIN_A), mlp.LEAGUE_RANDOM, np.int32)
+    slot_net[:, 0], slot_net[:, 1] = 0, 1
+    bank.set_slots(torch.from_numpy(slot_net))
+    return bank, dict(greedy=True)
+
+
+@pytest.mark.parametrize("kind", ["league_eval", "shared"])
+def test_chains(kind):
+    """a 12-step chain, 32 x 8, slots 2 .. 7 scripted, two chains: the recorded actions replayed through the oracle give the chain's observations and rewards bit
+    for bit, and at every step the scripted slots' recorded actions are the specification on the ORACLE's books and accounts"""
+    from gym_continuousdoubleauction_amd import mlp
+    n, a, T = CHAIN_N, CHAIN_A, CHAIN_T
+    env = _chain_env(True)
+    driver, kw = _driver(kind)
+    chains = mlp.RolloutChains(env, driver, T, groups=2, seed=5, **kw)
+    b = {k: v.cpu().numpy() for k, v in chains.run().items()}
+    counter = int(chains.counter.item())
+    torch.cuda.synchronize()
+    slots, profiles = env.scripted_slots(), env.scripted_profiles()
+    scripted, pix = slots != 0, np.maximum(slots - 1, 0)
+    depth = np.array([p.depth_levels for p in profiles])[pix]
+    m, j = np.meshgrid(np.arange(n), np.arange(a), indexing="ij")
+    ora = O.OracleEnv(CHAIN_CFG, n_markets=n)
+    assert np.array_equal(ora.reset(seeds=np.arange(300, 300 + n, dtype=np.uint64)).view(np.uint32), b["obs"][0].view(np.uint32))
+    acted = set()
+    for t in range(T):
+        states = [ora.get_state(i) for i in range(n)]
+        views = views_of_books([ora.get_book(i) for i in range(n)], a, [[int(s.acc[x].net_position) for x in range(a)] for s in states],
+                               [int(s.t_step) for s in states], 1, depth)
+        want = S.actions_from_views(profiles, pix, views, 13, counter, 64 + m, t, j)
+        for k, w in zip(KEYS, want):
+            assert np.array_equal(b[k][t][scripted].view(np.uint32), w[scripted].view(np.uint32)), (t, k)
+        acted |= set(want[0][scripted].tolist())
+        assert (b["logp"][t][scripted] == 0).all() and (b["a_cont"][t][scripted] == 0).all()
+        oo, orw, *_ = ora.step(*(b[k][t] for k in KEYS))
+        assert np.array_equal(b["obs"][t + 1].view(np.uint32), oo.view(np.uint32)) and np.array_equal(b["reward"][t].view(np.uint64), orw.view(np.uint64)), t
+    assert len(acted) >= 4                                               # passes, market orders and quotes among them
+    assert (env.flags().cpu().numpy() == 0).all() and (env.check_invariants().cpu().numpy() == 0).all()
+    # step 0: the network slots play what they play in the same chain without scripts
+    plain = _chain_env(False)
+    driver2, kw2 = _driver(kind)
+    b2 = {k: v.cpu().numpy() for k, v in mlp.RolloutChains(plain, driver2, T, groups=2, seed=5, **kw2).run().items()}
+    for k in KEYS:
+        assert np.array_equal(b[k][0][:, :2].view(np.uint32), b2[k][0][:, :2].view(np.uint32)), k
+    assert not np.array_equal(b["category"][0][:, 2:], b2["category"][0][:, 2:])
+    env.close(); plain.close(); ora.close()
+
+
+def test_epochs_and_refusals():
+    from gym_continuousdoubleauction_amd import league_train, mlp, ppo
+    from gym_continuousdoubleauction_amd._lib import lib
+    env = _chain_env(False)
+    supported = int(lib().cda_policy_step_supported(env._h))
+    assert supported == 1 and int(lib().cda_scripted_attached(env._h)) == 0
+    chains = mlp.RolloutChains(env, mlp.FusedPolicy("cuda:0", seed=1), 4, groups=2, seed=5)
+    chains.run()
+    torch.cuda.synchronize()
+    e0 = int(lib().cda_scripted_epoch(env._h))
+    slots = mixed_slots(CHAIN_N, CHAIN_A)
+    slots[:, :2] = 0
+    env.set_scripted(slots, MIXED, seed=1)
+    assert int(lib().cda_scripted_epoch(env._h)) == e0 + 1 and env.script_epoch == 1 and int(lib().cda_policy_step_supported(env._h)) == 0
+    with pytest.raises(RuntimeError, match="scripted"):
+        chains.run()
+    for train, kw in ((ppo.train_fused, {}), (league_train.train_league_fused, {})):
+        with pytest.raises(ValueError, match="scripted"):
+            train(env, iters=1, **kw)
+    # a scripted slot below n_trainable
+    bank, kw = _driver("league_eval")
+    slots[:, 0] = 1
+    env.set_scripted(slots, MIXED, seed=1)
+    with pytest.raises(ValueError, match="trainable"):
+        mlp.RolloutChains(env, bank, 4, groups=2, seed=5, **kw).run()
+    # an invalid profile or slot value is refused and changes nothing
+    e1 = int(lib().cda_scripted_epoch(env._h))
+    bad = torch.from_numpy(S.profiles_array([dataclasses.replace(MAKER, depth_levels=11)], validate=False).view(np.uint8).copy()).to("cuda:0")
+    assert lib().cda_scripted_attach(env._h, env._script.slot_script.data_ptr(), bad.data_ptr(), 1, 0, 0) == K.ERR_INVALID
+    big = torch.full((CHAIN_N, CHAIN_A), 2, dtype=torch.int32, device="cuda:0")
+    good = torch.from_numpy(S.profiles_array([MAKER]).view(np.uint8).copy()).to("cuda:0")
+    assert lib().cda_scripted_attach(env._h, big.data_ptr(), good.data_ptr(), 1, 0, 0) == K.ERR_INVALID
+    assert int(lib().cda_scripted_epoch(env._h)) == e1 and int(lib().cda_scripted_attached(env._h)) == 1
+    with pytest.raises(ValueError):
+        env.set_scripted(slots, [dataclasses.replace(MAKER, max_orders=0)])
+    env.clear_scripted()
+    assert int(lib().cda_policy_step_supported(env._h)) == supported and int(lib().cda_scripted_epoch(env._h)) == e1 + 1 and not env.scripted
+    with pytest.raises(RuntimeError):
+        env.run_scripted(1)
+    env.close()
+
+
+def test_evaluate_against_scripted_opponents():
+    from gym_continuousdoubleauction_amd import CDAVecEnv, mlp
+    from gym_continuousdoubleauction_amd.evaluate import evaluate
+    init_cash = 1000000
+    env = CDAVecEnv({"num_of_agents": 4, "init_cash": init_cash, "max_step": 32, "is_render": False, "auto_reset": True}, n_markets=48, device="cuda:0", with_info=False)
+    res = evaluate(env, mlp.FusedPolicy("cuda:0", seed=3), opponents=["maker", "taker:p_trade_q32=1073741824", "pass"], episodes=2, seed=6)
+    assert not env.scripted and res["nav_conservation_violations"] == 0
+    mods = res["modules"]
+    assert sorted(mods) == ["opponent_0", "opponent_1", "opponent_2", "policy"]
+    for name, mres in mods.items():
+        assert mres["agent_episodes"] > 0, name
+    assert mods["opponent_2"]["trades"] == 0 and mods["opponent_2"]["episode_nav_mean"] == float(init_cash)
+    env.close()
