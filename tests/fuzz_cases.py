@@ -27,10 +27,11 @@ def random_order(rng):
     return "shuffle" if rng.random() < 0.35 else None
 
 
-def prefill_book(env, market, rng, agents, n_bids, n_asks):
+def prefill_book(env, market, rng, agents, n_bids, n_asks, qty=(1, 6), level_orders=(1, 5)):
     """Give `market` of `env` (product or oracle: same get_state / set_state) a deep book through the state dump: n_bids / n_asks
     resting orders (up to 512 per side, far more than the LDS tile) in levels of one to four orders around the market's price,
-    with the traders' escrow (cash_on_hold) set to match.  Both envs get the same book when called with equally seeded `rng`s."""
+    with the traders' escrow (cash_on_hold) set to match.  Both envs get the same book when called with equally seeded `rng`s.
+    qty / level_orders: the half-open ranges an order's quantity and a level's number of orders are drawn from."""
     from decimal import Decimal
 
     from gym_continuousdoubleauction_amd import _capi as K
@@ -39,16 +40,16 @@ def prefill_book(env, market, rng, agents, n_bids, n_asks):
     hold = [0] * agents
     oid = 0
     for side, n, arr in ((0, n_bids, s.bids), (1, n_asks, s.asks)):
-        price, left_in_level = (lp - 1 if side == 0 else lp + 1), int(rng.integers(1, 5))
+        price, left_in_level = (lp - 1 if side == 0 else lp + 1), int(rng.integers(*level_orders))
         for k in range(n):
             if left_in_level == 0:
                 step = int(rng.integers(1, 3))
                 price = max(1, price - step) if side == 0 else price + step
-                left_in_level = int(rng.integers(1, 5))
+                left_in_level = int(rng.integers(*level_orders))
             left_in_level -= 1
             o = arr[k]
             oid += 1
-            o.price, o.qty, o.owner, o.order_id, o.timestamp = price, int(rng.integers(1, 6)), int(rng.integers(0, agents)), oid, oid
+            o.price, o.qty, o.owner, o.order_id, o.timestamp = price, int(rng.integers(*qty)), int(rng.integers(0, agents)), oid, oid
             hold[o.owner] += o.price * o.qty
     s.n_bids, s.n_asks = n_bids, n_asks
     s.lob_time = s.next_order_id = oid

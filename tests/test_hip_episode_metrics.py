@@ -13,6 +13,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+from step_variants import _replay      # noqa: E402  (the actions through the oracle under the env's auto-reset rule; shared with tests/test_hip_step_variants.py)
+
 pytestmark = pytest.mark.gpu
 
 ACTION_KEYS = ("category", "size_mean", "size_sigma", "price", "price_offset")
@@ -35,15 +37,6 @@ def _actions(rng, N, A, aggressive=False):
         cat = np.where(rng.random((N, A)) < 0.5, rng.choice([1, 5], (N, A)), cat).astype(np.int32)
     return (cat, rng.uniform(-1, 1, (N, A)).astype(np.float32), rng.uniform(0, 1, (N, A)).astype(np.float32), rng.integers(0, 10, (N, A)).astype(np.int32),
             rng.integers(0, 3, (N, A)).astype(np.int32))
-
-
-def _replay(ora, em, acts_per_step):
-    """the actions through the oracle with the env's auto-reset rule; feeds the host-side tallies"""
-    for acts in acts_per_step:
-        _, rew, term, trunc, info = ora.step(*acts)
-        ended = em.feed(info, rew, term, trunc, done_mask_of=lambda i: ora.get_state(i).done_mask)
-        if len(ended):
-            ora.reset(mask=(term | trunc).astype(np.uint8))
 
 
 @pytest.mark.parametrize("with_info", [False, True])
@@ -206,16 +199,24 @@ def test_league_rollout_metrics_are_keyed_by_module():
     env.close(); ora.close()
 
 
-@pytest.mark.parametrize("path", ["step", "step_info", "rollout"])
+@pytest.mark.parametrize("path", ["step", "step_info", "rollout", "step+cold", "step+tape", "step_info+cold+tape"])
 def test_a_ledger_fault_in_an_episode_that_auto_resets_mid_run_is_reported(path):
     """a seeded corruption of ONE market's ledger (cash created out of nothing) in an episode that ends and resets itself in the middle of the run: the violation is
-    counted, the market carries the sticky flag after its reset, the trainer-side check raises like the reference's strict_nav_check run"""
+    counted, the market carries the sticky flag after its reset, the trainer-side check raises like the reference's strict_nav_check run.  +cold: the victim's book
+    is prefilled beyond the tile, its episode ends on the general build (slow_step / slow_tstep, the tallies by the market's ST_EP_ON bit, the end handed back to
+    the kernel); +tape: the tape-writing instances (k_tstep)"""
     from decimal import Decimal
     from gym_continuousdoubleauction_amd import CDAVecEnv, _capi as K, mlp
     from gym_continuousdoubleauction_amd import episode_metrics as EM
+    path, *extra = path.split("+")
     N, A, max_step, victim = 64, 4, 6, 37
     env = CDAVecEnv(_cfg(A, max_step), n_markets=N, with_info=(path == "step_info"))
+    if "tape" in extra:
+        env.enable_tape(1024)
     env.reset(seed=99)
+    if "cold" in extra:
+        from fuzz_cases import prefill_book
+        prefill_book(env, victim, np.random.default_rng(6), A, 300, 300)
     env.enable_episode_metrics(True)
     rng = np.random.default_rng(2)
     for _ in range(2):
@@ -229,7 +230,10 @@ def test_a_ledger_fault_in_an_episode_that_auto_resets_mid_run_is_reported(path)
         roll = mlp.RolloutChains(env, mlp.FusedPolicy("cuda:0", seed=3), 16, groups=2, seed=1)
         roll.run()
     else:
-        for _ in range(16):
+        for k in range(16):
+            if k == max_step - 3:                             # before the step that ends the corrupted episode: the victim alone is cold
+                cold = env.book_counts()[:, :, 0].sum(1).cpu().numpy() + A > env.book_capacity
+                assert bool(cold[victim]) == ("cold" in extra) and not np.delete(cold, victim).any()
             env.step(*_actions(rng, N, A))
     torch.cuda.synchronize()
     flags = env.flags().cpu().numpy()

@@ -41,16 +41,23 @@ class _Counting:
         return out
 
 
-def _replay(name, capacity=4096, state_every=16):
+def _replay(name, capacity=4096, state_every=16, metrics=False):
     rec, fx = G.load(name), _fixture(name)
     env = _Counting(_tape_env(rec["config"], 1, capacity))
+    if metrics:                                                                       # the tape-writing instances then tally (the market's ST_EP_ON bit)
+        env.env.enable_episode_metrics(True)
     G.run_group(env, [rec], state_every=state_every)
     return env, rec, fx
 
 
 @pytest.mark.parametrize("name", FIXTURES)
 def test_every_fixture_replays_to_the_reference_tape(name):
-    env, rec, fx = _replay(name, state_every=64 if name.startswith("bigbook") else 16)
+    assert_fixture_replays_to_the_reference_tape(name)
+
+
+def assert_fixture_replays_to_the_reference_tape(name, metrics=False):
+    """(tests/test_hip_step_variants.py replays the fixtures once more with the episode metrics on)"""
+    env, rec, fx = _replay(name, state_every=64 if name.startswith("bigbook") else 16, metrics=metrics)
     got_len = np.array([c[0] for c in env.n_episode], np.int32)
     assert np.array_equal(got_len, fx["tape_len"]), (name, np.flatnonzero(got_len != fx["tape_len"])[:8])
     records, offsets, dropped = env.env.drain_tape()
