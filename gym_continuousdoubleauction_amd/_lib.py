@@ -39,6 +39,7 @@ MLP_SYMBOLS = [
     "cda_mlp_reduce", "cda_mlp_apply", "cda_gae_records_bootstrap", "cda_mlp_values", "cda_mlp_values_counted", "cda_episode_returns", "cda_mlp_league_step", "cda_mlp_league_rollout_chain",
     "cda_gae_records_league", "cda_league_assign", "cda_mlp_wgrad_jobs",
     "cda_mlp_policy_act", "cda_mlp_league_act", "cda_mlp_eval_chain", "cda_mlp_league_eval_chain",
+    "cda_gae_records_slots", "cda_league_assign_scripted",
 ]
 # the same entry points compiled for other history depths carry the suffix _h<H> (include/cda_mlp.h CDA_MLP_HIST_VARIANTS, csrc/cda_mlp_variant.h)
 MLP_HIST_VARIANTS = (1, 2, 3, 6, 7, 8)
@@ -179,6 +180,8 @@ def lib():
     L.cda_mlp_eval_chain.argtypes = [vp, vp, vp, i32, i32, i32, C.POINTER(RolloutBufs), i32, vp]
     L.cda_mlp_league_eval_chain.argtypes = L.cda_mlp_league_rollout_chain.argtypes
     L.cda_league_assign.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp, vp, vp]
+    L.cda_league_assign_scripted.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp]
+    L.cda_gae_records_slots.argtypes = [vp, vp, vp, vp, i32, i64, i32, i32, f32, f32, f32, vp, vp, vp, vp, vp]
     L.cda_step_range_capture.argtypes = [vp, i32, i32] + [vp] * 6 + [vp] * 4 + [C.POINTER(K.InfoPtrs), vp, i32, vp, vp, vp]
     L.cda_policy_step_supported.argtypes = [vp]
     L.cda_policy_step_advised.argtypes = [vp]

@@ -141,6 +141,22 @@ def with_vf_share_layers(args, vf_share_layers):
     return dict(args, vf_share_layers=True) if vf_share_layers else dict(args)
 
 
+def with_scripted(args, profiles, trained_slots=None, scripted_weight=None):
+    """the loop arguments of a run that trains against scripted opponents: the canonical fields of every profile, in order (scripted.profile_record), and
+    trained_slots (ppo.train_fused) / scripted_weight (the league's pool weight).  Added only when there are scripted opponents: a run without them keeps the
+    arguments it had before the keys existed, and check_args refuses a checkpoint of either kind for a run of the other, or one with other opponents"""
+    from .scripted import profile_record
+    profiles = list(profiles or [])
+    if not profiles:
+        return dict(args)
+    out = dict(args, scripted_opponents=[profile_record(p) for p in profiles])
+    if trained_slots is not None:
+        out["trained_slots"] = int(trained_slots)
+    if scripted_weight is not None:
+        out["scripted_weight"] = float(scripted_weight)
+    return out
+
+
 def new_run_id():
     return uuid.uuid4().hex
 

@@ -1736,6 +1736,51 @@ __global__ __launch_bounds__(256) void k_gae_records(const double* __restrict__ 
     __syncthreads();
     if (threadIdx.x < 2) atomicAdd(&stats[threadIdx.x], (part[threadIdx.x][0] + part[threadIdx.x][1]) + (part[threadIdx.x][2] + part[threadIdx.x][3]));
 }
+// k_gae_records' recursion for ONE shared policy that plays slots 0 .. n_slots - 1 of every market only (the other slots are scripted opponents: their records are
+// no policy samples).  One thread per (market, slot < n_slots): the same operands in the same order as k_gae_records' n_train == 0 thread of that column, so words 6, 7
+// are bit-equal to what it writes there; the other slots' records are not touched and stats f64[2] (cleared by the caller) sums the T * N * n_slots trained samples.
+// A kernel of its own: k_gae_records stays the code object it was.
+__global__ __launch_bounds__(256) void k_gae_records_slots(const double* __restrict__ reward, const float* __restrict__ value, const unsigned char* __restrict__ term,
+                                                           const unsigned char* __restrict__ trunc, int T, long long N, int Ag, int n_slots, float reward_scale, float gamma, float lam,
+                                                           const int* __restrict__ fin_index, const float* __restrict__ fin_value, float* __restrict__ rec, double* __restrict__ stats) {
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x, B = N * Ag;
+    double s1 = 0.0, s2 = 0.0;
+    if (j < N * n_slots) {
+        const long long n = j / n_slots;
+        const long long i = n * Ag + (j - n * n_slots);                         // the column of rec / reward: (market n, slot j mod n_slots)
+        float nxt = value[(long long)T * N + n], run = 0.0f;
+        for (int t0 = T - 1; t0 >= 0; t0 -= 8) {                                // eight steps' operands requested together (k_gae_records)
+            float rw[8], vv[8], nd[8], bv[8];
+            #pragma unroll
+            for (int u = 0; u < 8; u++) {
+                const int t = t0 - u >= 0 ? t0 - u : 0;
+                const long long k = (long long)t * B + i, kn = (long long)t * N + n;
+                const bool tm = term[kn] != 0, tr = trunc[kn] != 0;
+                rw[u] = (float)reward[k] * reward_scale; vv[u] = value[kn]; nd[u] = (tm | tr) ? 0.0f : 1.0f;
+                bv[u] = 0.0f;
+                if (fin_index && tr && !tm) { const int fi = fin_index[kn]; if (fi >= 0) bv[u] = fin_value[fi]; }
+            }
+            #pragma unroll
+            for (int u = 0; u < 8; u++) {
+                const int t = t0 - u;
+                if (t >= 0) {
+                    const long long k = (long long)t * B + i;
+                    const float delta = rw[u] + gamma * (nxt * nd[u] + bv[u]) - vv[u];
+                    run = delta + gamma * lam * nd[u] * run;
+                    *reinterpret_cast<float2*>(rec + 8 * k + 6) = make_float2(run, run + vv[u]);
+                    s1 += (double)run; s2 += (double)run * (double)run;
+                    nxt = vv[u];
+                }
+            }
+        }
+    }
+    #pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { s1 += __shfl_down(s1, o, 64); s2 += __shfl_down(s2, o, 64); }
+    __shared__ double part[2][4];
+    if ((threadIdx.x & 63) == 0) { part[0][threadIdx.x >> 6] = s1; part[1][threadIdx.x >> 6] = s2; }
+    __syncthreads();
+    if (threadIdx.x < 2) atomicAdd(&stats[threadIdx.x], (part[threadIdx.x][0] + part[threadIdx.x][1]) + (part[threadIdx.x][2] + part[threadIdx.x][3]));
+}
 // k_ppo_loss32 on sample records: a row's A samples are ONE contiguous piece of A x 32 bytes (the seven separate per-sample arrays cost seven
 // scattered 16-byte gathers per row: 1.3 KB fetched per row for 128 B used)
 __global__ __launch_bounds__(256) void k_ppo_loss_rec(const float* __restrict__ outputs, const float* __restrict__ log_std, const float* __restrict__ rec,
@@ -2181,7 +2226,21 @@ extern "C" int cda_gae_records_bootstrap(const double* reward, const float* valu
                                          const int32_t* fin_index, const float* fin_value, int64_t fin_value_stride, float* rec, double* stats, void* stream) {
     return gae_records(reward, value, terminated, truncated, n_steps, n_markets, num_agents, n_trainable, reward_scale, gamma, lam, rec, stats, stream, fin_index, fin_value, fin_value_stride);
 }
-extern "C" int cda_gae_records_league(const double* reward, const float* value, const uint8_t* terminated, const uint8_t* truncated, int32_t n_steps, int64_t n_markets,
+// ... for one shared policy on slots 0 .. n_slots - 1 of every market (the other slots: scripted opponents): cda_gae_records_bootstrap(n_trainable = 0)'s recursion over
+// those slots only (k_gae_records_slots); fin_index / fin_value may be NULL (no time-limit bootstrap), fin_value is the shared policy's one row.
+extern "C" int cda_gae_records_slots(const double* reward, const float* value, const uint8_t* terminated, const uint8_t* truncated, int32_t n_steps, int64_t n_markets,
+                                     int32_t num_agents, int32_t n_slots, float reward_scale, float gamma, float lam,
+                                     const int32_t* fin_index, const float* fin_value, float* rec, double* stats2, void* stream) {
+    if (!reward || !value || !terminated || !truncated || !rec || !stats2 || n_steps < 1 || n_markets < 1 || num_agents < 1 || num_agents > CDA_MAX_AGENTS ||
+        n_slots < 1 || n_slots > num_agents || (fin_index && !fin_value) || ((uintptr_t)rec & 7) != 0) return CDA_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(stats2, 0, 2 * sizeof(double), st) != hipSuccess) return CDA_ERR_HIP;
+    const long long B = (long long)n_markets * n_slots;
+    hipLaunchKernelGGL(k_gae_records_slots, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, reward, value, (const unsigned char*)terminated, (const unsigned char*)truncated,
+                       (int)n_steps, (long long)n_markets, (int)num_agents, (int)n_slots, reward_scale, gamma, lam, (const int*)fin_index, fin_value, rec, stats2);
+    return hipGetLastError() == hipSuccess ? CDA_OK : CDA_ERR_HIP;
+}
+extern "C" int cda_gae_records_league(const double* reward,const float* value, const uint8_t* terminated, const uint8_t* truncated, int32_t n_steps, int64_t n_markets,
                                       int32_t num_agents, int32_t n_trainable, float reward_scale, float gamma, float lam, float* rec, double* stats2k, void* stream) {
     if (n_trainable < 1) return CDA_ERR_INVALID;
     return gae_records(reward, value, terminated, truncated, n_steps, n_markets, num_agents, n_trainable, reward_scale, gamma, lam, rec, stats2k, stream);
@@ -2281,6 +2340,48 @@ extern "C" int cda_league_assign(const uint32_t* episode_crc, int32_t n_markets,
     const int n = n_markets * num_agents;
     hipLaunchKernelGGL(k_league_assign, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const unsigned int*)episode_crc, (int)n_markets, (int)num_agents,
                        (int)n_trainable, pool_cdf, (const int*)pool_net, (int)pool_size, (int*)slot_net, (int*)slot_pool);
+    return hipGetLastError() == hipSuccess ? CDA_OK : CDA_ERR_HIP;
+}
+
+// k_league_assign with scripted modules in the pool: the same draw, bit for bit (the same freshly seeded MT19937's first double, the same searchsorted on the - longer -
+// cdf), and one more table, pool_script i32 [P]: 0, or 1 + the profile a scripted pool entry plays.  slot_script i32 [N][A] (the env's resident table: k_script_actions
+// reads it at the next step) receives pool_script[draw], 0 in the trainable slots; a scripted entry's pool_net is CDA_LEAGUE_RANDOM (validated by the launcher's caller:
+// the random module's action is what the scripted launch overwrites).  A kernel of its own: k_league_assign stays the code object it was.
+namespace { __global__ __launch_bounds__(256) void k_league_assign_scripted(const unsigned int* __restrict__ episode_crc, int N, int Ag, int n_train, const double* __restrict__ cdf,
+                                                                const int* __restrict__ pool_net, const int* __restrict__ pool_script, int P, int* __restrict__ slot_net,
+                                                                int* __restrict__ slot_script, int* __restrict__ slot_pool) {
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= N * Ag) return;
+    const int n = i / Ag, s = i - n * Ag;
+    if (s < n_train) { slot_net[i] = s; slot_script[i] = 0; if (slot_pool) slot_pool[i] = -1; return; }
+    unsigned int x = episode_crc[n] + (unsigned int)s;                          // (crc + slot) mod 2^32
+    unsigned int m0 = x, m1 = 0, m2 = 0, m397 = 0, m398 = 0;
+    for (unsigned int k = 1; k <= 398; k++) {
+        x = 1812433253u * (x ^ (x >> 30)) + k;
+        if (k == 1) m1 = x; else if (k == 2) m2 = x; else if (k == 397) m397 = x; else if (k == 398) m398 = x;
+    }
+    auto word = [](unsigned int a, unsigned int b, unsigned int c) {             // output k: twist of (mt[k], mt[k + 1], mt[k + 397]), tempered
+        const unsigned int y = (a & 0x80000000u) | (b & 0x7fffffffu);
+        unsigned int v = c ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
+        v ^= v >> 11; v ^= (v << 7) & 0x9d2c5680u; v ^= (v << 15) & 0xefc60000u; v ^= v >> 18;
+        return v;
+    };
+    const unsigned int w0 = word(m0, m1, m397) >> 5, w1 = word(m1, m2, m398) >> 6;
+    const double u = ((double)w0 * 67108864.0 + (double)w1) / 9007199254740992.0;
+    int idx = 0;
+    for (int q = 0; q < P; q++) idx += cdf[q] <= u ? 1 : 0;                      // searchsorted(..., side = "right")
+    if (idx >= P) idx = P - 1;
+    slot_net[i] = pool_net[idx];
+    slot_script[i] = pool_script[idx];
+    if (slot_pool) slot_pool[i] = idx;
+} }
+extern "C" int cda_league_assign_scripted(const uint32_t* episode_crc, int32_t n_markets, int32_t num_agents, int32_t n_trainable, const double* pool_cdf, const int32_t* pool_net,
+                                          const int32_t* pool_script, int32_t pool_size, int32_t* slot_net, int32_t* slot_script, int32_t* slot_pool, void* stream) {
+    if (!episode_crc || !pool_cdf || !pool_net || !pool_script || !slot_net || !slot_script || n_markets < 1 || num_agents < 1 || num_agents > CDA_MAX_AGENTS ||
+        n_trainable < 0 || n_trainable > num_agents || pool_size < 1) return CDA_ERR_INVALID;
+    const int n = n_markets * num_agents;
+    hipLaunchKernelGGL(k_league_assign_scripted, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const unsigned int*)episode_crc, (int)n_markets,
+                       (int)num_agents, (int)n_trainable, pool_cdf, (const int*)pool_net, (const int*)pool_script, (int)pool_size, (int*)slot_net, (int*)slot_script, (int*)slot_pool);
     return hipGetLastError() == hipSuccess ? CDA_OK : CDA_ERR_HIP;
 }
 

@@ -62,6 +62,7 @@
 #define cda_mlp_rollout_chain CDA_MLP_SFX(cda_mlp_rollout_chain)
 #define cda_gae_records CDA_MLP_SFX(cda_gae_records)
 #define cda_gae_records_bootstrap CDA_MLP_SFX(cda_gae_records_bootstrap)
+#define cda_gae_records_slots CDA_MLP_SFX(cda_gae_records_slots)
 #define cda_mlp_values CDA_MLP_SFX(cda_mlp_values)
 #define cda_mlp_values_counted CDA_MLP_SFX(cda_mlp_values_counted)
 #define cda_episode_returns CDA_MLP_SFX(cda_episode_returns)
@@ -74,6 +75,7 @@
 #define cda_mlp_league_eval_chain CDA_MLP_SFX(cda_mlp_league_eval_chain)
 #define cda_gae_records_league CDA_MLP_SFX(cda_gae_records_league)
 #define cda_league_assign CDA_MLP_SFX(cda_league_assign)
+#define cda_league_assign_scripted CDA_MLP_SFX(cda_league_assign_scripted)
 #define cda_mlp_selftest_mfma CDA_MLP_SFX(cda_mlp_selftest_mfma)
 #endif
 #endif

@@ -14,6 +14,10 @@ Reference rule (train/callbk/league_based_self_play_callback.py:1286-1344, `get_
 independent generators, so the first double of each is computed for all seeds at once (`mt19937_first_double`:
 the 624-word `init_genrand` recurrence vectorised over the seed axis, then the tempering of words 0 and 1).
 Module ids and prefixes follow config/tunable_constants.json -> module_id_prefixes of the reference.
+
+Scripted modules (scripted.py: rule-based agents on the device) join the pool through `add_scripted` as `scripted_<i>_<law>`: to the rule above they are
+"otherwise" modules (weight `scripted_weight`, default 1.0), so `assign()` covers them as it stands; `assign_device` then also writes the env's scripted slot
+table (include/cda_mlp.h cda_league_assign_scripted).
 """
 import zlib
 
@@ -21,6 +25,7 @@ import numpy as np
 
 POLICY_PREFIX = "policy_"
 CHAMPION_PREFIX = "champion_"
+SCRIPTED_PREFIX = "scripted_"              # a rule-based module (scripted.py): neither policy_* nor champion_* - the reference rule's "otherwise"
 
 
 def policy_id(i):
@@ -54,7 +59,9 @@ def mt19937_first_double(seeds):
 class LeagueSlotMapper:
     """Batched counterpart of the reference's agent-to-module mapping function."""
 
-    def __init__(self, num_agents, num_trainable, num_fixed_opponents=None, original_opponent_weight=1.0, champion_weight=1.0):
+    def __init__(self, num_agents, num_trainable, num_fixed_opponents=None, original_opponent_weight=1.0, champion_weight=1.0, scripted_weight=1.0):
+        """scripted_weight: the weight of the scripted modules add_scripted() registers; the default 1.0 is the reference rule as written (a module that is neither
+        policy_* nor champion_* weighs 1.0)"""
         self.num_agents = int(num_agents)
         self.num_trainable = int(num_trainable)
         if not 0 <= self.num_trainable <= self.num_agents:
@@ -65,6 +72,8 @@ class LeagueSlotMapper:
         self.available_modules = [policy_id(i) for i in range(self.num_trainable + int(num_fixed_opponents))]
         self.original_opponent_weight = float(original_opponent_weight)
         self.champion_weight = float(champion_weight)
+        self.scripted_weight = float(scripted_weight)
+        self.scripted = {}                                     # scripted module id -> (its index among the scripted modules, its scripted.Profile)
         self.champion_id_counter = 0
 
     def add_champion(self, module_id=None):
@@ -77,7 +86,25 @@ class LeagueSlotMapper:
         self.available_modules.append(module_id)
         return module_id
 
+    def add_scripted(self, profile):
+        """Register a scripted opponent (a scripted.Profile, a name or 'NAME:key=value,...') in the matchmaking pool as module scripted_<i>_<law>, i counting the
+        scripted modules in the order they were added (the index of its profile in the table the env is attached with).  The ids sit behind the fixed opponents and
+        before any champion; they are weighted scripted_weight.  Returns the id."""
+        from .scripted import module_id, parse_profile
+        prof = parse_profile(profile)
+        mid = module_id(len(self.scripted), prof)
+        at = next((i for i, c in enumerate(self.available_modules) if c.startswith(CHAMPION_PREFIX)), len(self.available_modules))
+        self.available_modules.insert(at, mid)
+        self.scripted[mid] = (len(self.scripted), prof)
+        return mid
+
+    def scripted_profiles(self):
+        """the registered scripted modules' profiles, in index order"""
+        return [prof for _, prof in sorted(self.scripted.values(), key=lambda ip: ip[0])]
+
     def remove(self, module_id):
+        if module_id in self.scripted:
+            raise ValueError(f"{module_id} is a scripted module: the env's profile table is indexed by it for the whole run")
         self.available_modules.remove(module_id)
 
     def pool(self):
@@ -85,7 +112,8 @@ class LeagueSlotMapper:
 
     def pool_probabilities(self):
         w = np.array([self.champion_weight if c.startswith(CHAMPION_PREFIX) else
-                      (self.original_opponent_weight if c.startswith(POLICY_PREFIX) else 1.0) for c in self.pool()], dtype=np.float64)
+                      (self.original_opponent_weight if c.startswith(POLICY_PREFIX) else (self.scripted_weight if c in self.scripted else 1.0)) for c in self.pool()],
+                     dtype=np.float64)
         return w / w.sum()
 
     def assign(self, episode_ids):
@@ -114,11 +142,14 @@ class LeagueSlotMapper:
         """zlib.crc32(str(id)) per episode: the host half of the seed rule (the generator half runs on the device, assign_device)"""
         return np.array([zlib.crc32(str(e).encode("utf-8")) for e in episode_ids], dtype=np.uint32)
 
-    def assign_device(self, bank, episode_ids=None, crcs=None, net_of=None, slot_pool=None):
+    def assign_device(self, bank, episode_ids=None, crcs=None, net_of=None, slot_pool=None, slot_script=None):
         """assign() on the device (include/cda_mlp.h cda_league_assign), straight into `bank.slot_net` (mlp.PolicyBank): no host sync, one launch.
         net_of: {module id: bank row} for the pool's network modules (champions); modules not named there play the uniform random law
         (the reference's fixed opponents are RandomRLModules, train/model/model_handler.py:38-53).  slot_pool (optional i32 [N, A] device tensor)
-        receives the draw itself: available_modules[num_trainable + slot_pool] is the module's id (-1: the slot's own trainable policy)."""
+        receives the draw itself: available_modules[num_trainable + slot_pool] is the module's id (-1: the slot's own trainable policy).
+        slot_script (i32 [N, A] device tensor; required once add_scripted() registered a module): the env's resident scripted slot table
+        (CDAVecEnv.scripted_slot_tensor), rewritten in place by the same launch (cda_league_assign_scripted): 1 + the profile index where a scripted module was
+        drawn, 0 elsewhere; a scripted module's slot carries LEAGUE_RANDOM in slot_net."""
         import torch
         from ._lib import check, lib
         from .mlp import LEAGUE_RANDOM
@@ -129,16 +160,33 @@ class LeagueSlotMapper:
             raise ValueError("one episode per market of the bank")
         dev = bank.device
         cand = self.pool()
+        if self.scripted and slot_script is None:
+            raise ValueError("the pool holds scripted modules: assign_device needs slot_script (the env's scripted_slot_tensor())")
+        if slot_script is not None and (tuple(slot_script.shape) != (N, A) or slot_script.dtype != torch.int32 or not slot_script.is_contiguous() or slot_script.device != bank.slot_net.device):
+            raise ValueError(f"slot_script must be a contiguous int32 [{N}, {A}] tensor on the bank's device")
         if not cand:                                          # the reference's fallback for an empty pool: slot a plays policy_a (a random module here)
             bank.slot_net[:, self.num_trainable:] = LEAGUE_RANDOM
             if slot_pool is not None:
                 slot_pool.fill_(-1)
+            if slot_script is not None:
+                slot_script.zero_()
             return bank.slot_net
         cdf = np.cumsum(self.pool_probabilities())
         cdf /= cdf[-1]
         nets = np.array([(net_of or {}).get(c, LEAGUE_RANDOM) for c in cand], dtype=np.int32)
         keep = (torch.from_numpy(np.asarray(crcs, dtype=np.uint32).view(np.int32).copy()).to(dev, non_blocking=True), torch.from_numpy(cdf).to(dev, non_blocking=True),
                 torch.from_numpy(nets).to(dev, non_blocking=True))
+        if slot_script is not None:
+            scr = np.array([1 + self.scripted[c][0] if c in self.scripted else 0 for c in cand], dtype=np.int32)
+            if bool((nets[scr != 0] != LEAGUE_RANDOM).any()):
+                raise ValueError("a scripted module may not be given a bank row (net_of): its slot carries LEAGUE_RANDOM")
+            keep = keep + (torch.from_numpy(scr).to(dev, non_blocking=True),)
+            with torch.cuda.device(dev):
+                check(lib().cda_league_assign_scripted(keep[0].data_ptr(), N, A, self.num_trainable, keep[1].data_ptr(), keep[2].data_ptr(), keep[3].data_ptr(), len(cand),
+                                                       bank.slot_net.data_ptr(), slot_script.data_ptr(), slot_pool.data_ptr() if slot_pool is not None else None,
+                                                       torch.cuda.current_stream(dev).cuda_stream), "cda_league_assign_scripted")
+            self._keep = keep
+            return bank.slot_net
         with torch.cuda.device(dev):
             check(lib().cda_league_assign(keep[0].data_ptr(), N, A, self.num_trainable, keep[1].data_ptr(), keep[2].data_ptr(), len(cand), bank.slot_net.data_ptr(),
                                           slot_pool.data_ptr() if slot_pool is not None else None, torch.cuda.current_stream(dev).cuda_stream), "cda_league_assign")

@@ -172,7 +172,8 @@ def train_league_fused(env, iters=4, horizon=None, num_trainable=2, lr=5e-5, epo
                        std_dev_multiplier=0.1, max_champions=8, min_iterations_between_champions=2, chains=4, minibatch=262144, objective=None, use_graph=True,
                        recorder=None, info_markets=0, run_id="league", log=print, keep=None, allreduce=None, world=1, first_market=0, episode_metrics=True,
                        strict_nav_check=True, state_dependent_log_std=False, hidden=(256, 256),
-                       checkpoint_dir=None, chkpt_freq=0, chkpt_keep=3, restore=None, iters_is_delta=False, activation="tanh", vf_share_layers=False):
+                       checkpoint_dir=None, chkpt_freq=0, chkpt_keep=3, restore=None, iters_is_delta=False, activation="tanh", vf_share_layers=False,
+                       scripted_opponents=None, scripted_weight=1.0, random_opponents=None, _attached=None):
     """League self-play on the fused kernels (include/cda_mlp.h `cda_league`): the reference's training topology - `num_trainable` SEPARATELY trained policies
     (policy_p plays slot p), every other slot drawn per episode from the pool of uniform random modules and frozen champions by the reference's mapping rule
     (computed on the device, league.LeagueSlotMapper.assign_device) - at the speed of the fused loop: ONE policy launch per step serves every module of every
@@ -193,9 +194,40 @@ def train_league_fused(env, iters=4, horizon=None, num_trainable=2, lr=5e-5, epo
     state (champions and their rows, promotion history, champion id counter, pool), the rollout counters, the updates' shuffle state, the KL coefficients and
     the running episode returns: the mapping, episode ids and promotions continue exactly.  Single-process runs only; no recorder.
     activation: `fcnet_activation` of the whole bank (mlp.PolicyBank: trainable policies and their champion snapshots share it); vf_share_layers likewise (RLlib's
-    shared trunk for every net of the bank)."""
-    if getattr(env, "scripted", False):        # (a scripted slot's sample record is no policy sample: it must not reach a loss)
-        raise ValueError("train_league_fused does not train on an env with scripted opponents attached (training against them is out of scope): clear_scripted() first")
+    shared trunk for every net of the bank).
+    scripted_opponents / scripted_weight / random_opponents: scripted modules (scripted.parse_profile's forms: rule-based agents on the device) in the per-episode
+    opponent pool, as modules scripted_<i>_<law> behind the fixed opponents, weighted scripted_weight (1.0 = the reference rule's "otherwise"); random_opponents =
+    the number of uniform random modules in the pool (default A - num_trainable; 0: a pool of scripted modules and champions only).  The profiles are attached to the
+    env once, with an all-zero slot table, before the rollout graphs are captured; at every episode boundary the assignment launch (cda_league_assign_scripted)
+    rewrites the env's resident slot table beside bank.slot_net - no re-attach, no re-capture - and they are detached on exit, also on an exception.  Module returns,
+    per-module episode metrics, the recorder and league.json name them; promotion considers trainable policies only.  A checkpoint's args hold their canonical
+    fields and the weight.  Single-process runs only (ValueError with world > 1); an env that has scripts attached already is refused."""
+    if getattr(env, "scripted", False) and _attached is None:        # (a scripted slot's sample record is no policy sample: it must not reach a loss)
+        raise ValueError("train_league_fused does not take an env with scripted opponents attached: pass them as scripted_opponents=[...] (the league attaches its pool's "
+                         "profiles itself) after clear_scripted()")
+    if scripted_opponents is not None and _attached is None:
+        from . import scripted as SC
+        kw = dict(locals())
+        profiles = [SC.parse_profile(o) for o in scripted_opponents]
+        if not profiles:
+            raise ValueError("scripted_opponents: None or a non-empty list of scripted opponents")
+        if len(profiles) > SC.MAX_PROFILES:
+            raise ValueError(f"at most {SC.MAX_PROFILES} scripted opponents, got {len(profiles)}")
+        if int(world) > 1 or allreduce is not None:
+            raise ValueError("scripted opponents in the league's pool: single-process runs only - data-parallel runs (world > 1) with scripts are out of scope")
+        if not 1 <= int(num_trainable) <= env.num_agents - 1:
+            raise ValueError(f"num_trainable must lie in 1 .. num_agents - 1 = {env.num_agents - 1} for a pool to be drawn from")
+        for name in ("kw", "SC", "env", "_attached"):
+            kw.pop(name, None)
+        import numpy as _np
+        # all-zero table: nobody is scripted until the first assignment writes the draws; the script epoch (and the graphs captured on it) then hold for the whole run
+        env.set_scripted(_np.zeros((env.n_markets, env.num_agents), _np.int32), profiles, seed=seed, market_index_base=int(first_market))
+        try:
+            return train_league_fused(env, _attached=profiles, **kw)
+        finally:
+            if env.scripted:
+                env.clear_scripted()
+    profiles = list(_attached or [])
     import numpy as np
     from . import ppo
     from .mlp import EpisodeReturns, FusedUpdate, PolicyBank, RolloutChains
@@ -213,8 +245,14 @@ def train_league_fused(env, iters=4, horizon=None, num_trainable=2, lr=5e-5, epo
         raise ValueError(f"league checkpoints are taken at episode boundaries only: chkpt_freq ({chkpt_freq}) must be a multiple of max_step / horizon = {per_episode}")
     bank = PolicyBank(dev, N, A, k, max_frozen=max_champions, seed=seed, random_seed=seed + 12345 + 104729 * int(first_market), n_hist=env.n_hist, state_dependent_log_std=state_dependent_log_std, hidden=hidden,
                       activation=activation, vf_share_layers=vf_share_layers)
-    mapper = LeagueSlotMapper(A, k, A - k, original_opponent_weight, champion_weight)
+    n_random = A - k if random_opponents is None else int(random_opponents)
+    if n_random < 0:
+        raise ValueError("random_opponents must be >= 0")
+    mapper = LeagueSlotMapper(A, k, n_random, original_opponent_weight, champion_weight, scripted_weight=scripted_weight)
+    for prof in profiles:
+        mapper.add_scripted(prof)
     league = League(mapper, bank, std_dev_multiplier, max_champions, min_iterations_between_champions)
+    slot_script = env.scripted_slot_tensor() if profiles else None
     ck_state = None
     if resumable:
         from .mlp import has_log_std_head, hidden_widths
@@ -225,6 +263,9 @@ def train_league_fused(env, iters=4, horizon=None, num_trainable=2, lr=5e-5, epo
                     "min_iterations_between_champions": int(min_iterations_between_champions), "original_opponent_weight": float(original_opponent_weight),
                     "champion_weight": float(champion_weight), "run_id": str(run_id)}
         run_args = CK.with_vf_share_layers(CK.with_activation(run_args, bank.activation), bank.vf_share_layers)
+        run_args = CK.with_scripted(run_args, profiles, scripted_weight=scripted_weight)
+        if random_opponents is not None:
+            run_args["random_opponents"] = n_random
         if restore:
             ck_path = CK.resolve_restore(checkpoint_dir, restore)
             ck_state, ck_snap = CK.load_checkpoint(ck_path)
@@ -244,6 +285,8 @@ def train_league_fused(env, iters=4, horizon=None, num_trainable=2, lr=5e-5, epo
     use_kl = obj["kl_coef"] > 0.0
     roll = RolloutChains(env, bank, T, groups=chains, seed=seed + 7919 * int(first_market), use_graphs=use_graph, with_dist=use_kl,
                          capture_ends=bool(obj["bootstrap_truncation"]), info_markets=info_markets if recorder is not None else 0)
+    if keep is not None:
+        keep.update(rollout=roll)                           # (from the start: a `log` callback can read each iteration's buffers through it)
     R = T * N
     rows_mb = max(32, min(R, (max(1, minibatch) // 32) * 32))              # one sample per row: a minibatch of `minibatch` samples is that many rows
     dp = allreduce is not None and world > 1
@@ -291,7 +334,7 @@ def train_league_fused(env, iters=4, horizon=None, num_trainable=2, lr=5e-5, epo
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
         if it % per_episode == 0:                                            # a new episode everywhere: new opponents (one launch; the crcs were computed while the GPU worked)
-            mapper.assign_device(bank, crcs=next_crcs, net_of=league.net_of, slot_pool=slot_pool)
+            mapper.assign_device(bank, crcs=next_crcs, net_of=league.net_of, slot_pool=slot_pool, slot_script=slot_script)
             if episode_metrics:                                              # who plays what during the coming episodes: index into the pool AS IT STANDS NOW
                 torch.where(slot_pool < 0, torch.arange(A, device=dev, dtype=torch.int32).expand(N, A), slot_pool + k, out=module_of)
                 module_names = list(mapper.available_modules)
@@ -364,6 +407,8 @@ def train_league_fused(env, iters=4, horizon=None, num_trainable=2, lr=5e-5, epo
         save(its[-1] + 1)                                       # the final save, when the run ends on an episode boundary
     if keep is not None:
         keep.update(buffers=roll.buf, rollout=roll, updates=upds, slot_pool=slot_pool, returns=returns)
+        if slot_script is not None:
+            keep.update(slot_script=slot_script.clone())                 # (the resident table goes with the detach)
     return bank, league, history
 
 
@@ -416,6 +461,11 @@ def save_league(directory, bank, league):
     os.makedirs(directory, exist_ok=True)
     promoted = {c["id"]: c for c in league.history}
     out = {"format": "cda-league", "version": 1, "trainable": [], "champions": []}
+    scripted_mods = getattr(getattr(league, "mapper", None), "scripted", {})
+    if scripted_mods:                                           # the rule-based modules of the pool: no file, their profile's canonical fields (scripted.profile_record)
+        from .scripted import profile_record
+        out["scripted"] = [{"module": str(mid), "index": int(i), "profile": profile_record(prof)} for mid, (i, prof) in sorted(scripted_mods.items(), key=lambda kv: kv[1][0])]
+        out["scripted_weight"] = float(league.mapper.scripted_weight)
     for p in range(bank.n_trainable):
         fname = f"policy_{p}.pt"
         torch.save(policy_record(bank.theta[p], activation=act, vf_share_layers=vfs), os.path.join(directory, fname))
@@ -431,7 +481,8 @@ def save_league(directory, bank, league):
     return out
 
 
-def main(argv=None):
+def main(argv=None, parse_only=False):
+    """parse_only: return the parsed arguments without touching a device (the flags' tests)"""
     p = argparse.ArgumentParser(description="League self-play (PPO vs random opponents and champion snapshots) on one MI355X.")
     p.add_argument("--markets", type=int, default=1024)
     p.add_argument("--agents", type=int, default=4)
@@ -456,9 +507,17 @@ def main(argv=None):
     p.add_argument("--iters-is-delta", action="store_true", help="with --restore: --iters counts further iterations instead of being the target")
     p.add_argument("--market-configs", default=None, metavar="FILE.json", help="per-market parameters: a JSON list of override dicts, market m runs entry m %% len(list) "
                                                                              "(market_params.PER_MARKET_KEYS; a max_step there may not exceed --episode)")
+    p.add_argument("--scripted-opponent", action="append", default=None, metavar="SPEC",
+                   help="--fused: a scripted module ('pass', 'maker', 'taker', 'imbalance', 'NAME:key=value,...') in the per-episode opponent pool; repeat for several")
+    p.add_argument("--scripted-weight", type=float, default=1.0, metavar="W", help="--fused: the pool weight of every scripted module (1.0 = the reference rule's \"otherwise\")")
+    p.add_argument("--random-opponents", type=int, default=None, metavar="R", help="--fused: uniform random modules in the pool (default: agents - trainable; 0: scripted modules and champions only)")
     args = p.parse_args(argv)
     if not args.fused and (args.checkpoint_dir or args.restore):
         raise SystemExit("--checkpoint-dir / --restore need --fused")
+    if not args.fused and (args.scripted_opponent or args.random_opponents is not None):
+        raise SystemExit("--scripted-opponent / --random-opponents need --fused")
+    if parse_only:
+        return args
     from .vec_env import CDAVecEnv
     from .market_params import load_market_configs, round_robin
     from . import ppo
@@ -474,7 +533,8 @@ def main(argv=None):
     bank, league, hist = train_league_fused(env, iters=args.iters, horizon=args.horizon, num_trainable=k, chains=args.chains,
                                          objective=ppo.RLLIB_DEFAULTS if args.objective == "rllib" else None, state_dependent_log_std=args.log_std_head, hidden=tuple(args.fcnet_hiddens),
                                          checkpoint_dir=args.checkpoint_dir, chkpt_freq=args.chkpt_freq, chkpt_keep=args.chkpt_keep, restore=args.restore,
-                                         iters_is_delta=args.iters_is_delta, activation=args.fcnet_activation, vf_share_layers=args.vf_share_layers)
+                                         iters_is_delta=args.iters_is_delta, activation=args.fcnet_activation, vf_share_layers=args.vf_share_layers,
+                                         scripted_opponents=args.scripted_opponent, scripted_weight=args.scripted_weight, random_opponents=args.random_opponents)
     flags = env.flags()
     _, bad = env.nav_conservation()
     tail = hist[2:] if len(hist) >= 4 else (hist[1:] or hist)          # (two warm-up iterations: graph capture, first replays)
@@ -484,7 +544,8 @@ def main(argv=None):
                                       f"{args.episode} steps, horizon {args.horizon or args.episode}, {args.iters} iterations; hand-written bf16 MFMA network kernels, one policy launch per step "
                                       "for every module, 4 epochs per policy per iteration",
                           "markets": args.markets, "agents": args.agents, "trainable": k, "episode": args.episode, "horizon": args.horizon or args.episode, "chains": args.chains,
-                          "objective": args.objective, "activation": args.fcnet_activation},
+                          "objective": args.objective, "activation": args.fcnet_activation, "scripted_opponents": args.scripted_opponent,
+                          "scripted_weight": args.scripted_weight if args.scripted_opponent else None},
                "iterations": hist, "timed_iterations": len(tail),
                "value": sum(h["agent_steps"] for h in tail) / sum(h["rollout_s"] + h["update_s"] for h in tail), "unit": "agent-steps/s",
                "rollout_agent_steps_per_s": sum(h["agent_steps"] for h in tail) / sum(h["rollout_s"] for h in tail),

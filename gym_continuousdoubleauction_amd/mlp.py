@@ -542,13 +542,21 @@ class RolloutChains:
     greedy: the evaluation chains (cda_mlp_eval_chain / cda_mlp_league_eval_chain): every network slot plays the MODE of its distribution (FusedPolicy.act),
         each step is two launches (mode-action network kernel, env step); random-module slots of a bank still draw."""
 
-    def __init__(self, env, policy, horizon, groups=4, seed=0, use_graphs=True, with_dist=False, capture_ends=False, info_markets=0, greedy=False):
+    def __init__(self, env, policy, horizon, groups=4, seed=0, use_graphs=True, with_dist=False, capture_ends=False, info_markets=0, greedy=False, trained_slots=None):
+        """trained_slots = k (a shared policy in training against scripted opponents, ppo.train_fused): the policy's samples are slots 0 .. k - 1 of every market, the
+        slots behind them are scripted (checked once per script epoch of the env); gae() then defaults to those k slots."""
         from ._lib import RolloutBufs
         from . import _capi as K
         self.env, self.policy, self.T = env, policy, int(horizon)
         self.greedy = bool(greedy)
         self.bank = policy if isinstance(policy, PolicyBank) else None
         N, A, dev, T = env.n_markets, env.num_agents, env.device, int(horizon)
+        self.trained_slots = None if trained_slots is None else int(trained_slots)
+        if self.trained_slots is not None:
+            if self.bank is not None:
+                raise ValueError("trained_slots is the shared policy's setting: a PolicyBank names its trainable slots itself (n_trainable)")
+            if not 1 <= self.trained_slots <= A - 1:
+                raise ValueError(f"trained_slots must lie in 1 .. num_agents - 1 = {A - 1}, got {self.trained_slots}")
         self.L = L = policy.L
         if env.obs_dim != L.OBS:
             raise ValueError(f"the policy is laid out for {L.OBS}-float observations (n_hist = {L.hist}), the env emits {env.obs_dim}")
@@ -633,11 +641,16 @@ class RolloutChains:
         self._check_scripted_slots()                               # (raise before anything is captured; run() looks again when the env's scripts changed)
 
     def _check_scripted_slots(self):
-        """league chains: a scripted opponent may sit in opponent slots only (once per script epoch of the env)"""
-        if self.bank is not None and getattr(self.env, "scripted", False) and self._script_checked != self.env.script_epoch:
+        """a scripted opponent may sit in opponent slots only (once per script epoch of the env): league chains - none below n_trainable; shared-policy chains built
+        with trained_slots = k - slots < k unscripted and every slot >= k scripted (the update reads the leading k records of every row and nothing else)"""
+        if not getattr(self.env, "scripted", False) or self._script_checked == self.env.script_epoch:
+            return
+        if self.bank is not None:
             if bool((self.env.scripted_slots()[:, :self.bank.n_trainable] != 0).any()):
                 raise ValueError(f"a scripted opponent sits in a trainable slot (< n_trainable = {self.bank.n_trainable}): scripted modules play opponent slots only")
-            self._script_checked = self.env.script_epoch
+        elif self.trained_slots is not None:
+            check_trained_slots(self.env.scripted_slots(), self.trained_slots)
+        self._script_checked = self.env.script_epoch
 
     @property
     def counter(self):
@@ -731,13 +744,18 @@ class RolloutChains:
                     cur.wait_event(self._joins[g])
         return self.buf
 
-    def gae(self, gamma=0.99, lam=0.95, reward_scale=1.0):
+    def gae(self, gamma=0.99, lam=0.95, reward_scale=1.0, n_slots=None):
         """advantages and returns of the last run() straight into the sample records (one launch; ppo.gae's recursion; with capture_ends a time-limit
         truncation bootstraps with the value of the episode's captured last observation - one more value launch over the captured list).  Returns
         (records [T * N, A, 8], the sums the update normalises the advantages with, their count); league: the sums are [n_trainable, 2] and the count is
-        per trainable net (T * N: one slot each)."""
+        per trainable net (T * N: one slot each).
+        n_slots = k (shared policy only; default: the chains' trained_slots): the recursion runs over slots 0 .. k - 1 of every market only (cda_gae_records_slots) -
+        the other slots' advantage / return words are not written, the sums cover the trained samples and the count is T * N * k."""
         L, st = _lib(), _stream(self.device)
         k = self.bank.n_trainable if self.bank else 0
+        n_slots = self.trained_slots if n_slots is None else int(n_slots)
+        if n_slots is not None and (self.bank is not None or not 1 <= n_slots <= self.A):
+            raise ValueError("gae(n_slots=k): a shared policy's chains, 1 <= k <= num_agents")
         fin_index = fin_value = None
         if self.capture_ends:
             wb, th = (self.bank.wb, self.bank.theta) if self.bank else (self.policy.wb, self.policy.theta)
@@ -745,6 +763,11 @@ class RolloutChains:
             _check(self.L.fn("cda_mlp_values_counted")(wb.data_ptr(), th.data_ptr(), max(k, 1), self.buf["fin_obs"].data_ptr(), self.fin_cap, self.buf["fin_count"].data_ptr(),
                                                        self.fin_value.data_ptr(), self.fin_cap, st), "cda_mlp_values_counted")
             fin_index, fin_value = self.buf["fin_index"].data_ptr(), self.fin_value.data_ptr()
+        if n_slots is not None:
+            _check(L.cda_gae_records_slots(self.buf["reward"].data_ptr(), self.buf["value"].data_ptr(), self.buf["terminated"].data_ptr(), self.buf["truncated"].data_ptr(),
+                                           self.T, self.N, self.A, n_slots, float(reward_scale), float(gamma), float(lam), fin_index, fin_value,
+                                           self.buf["record"].data_ptr(), self.adv_stats.data_ptr(), st), "cda_gae_records_slots")
+            return self.buf["record"].view(self.T * self.N, self.A, 8), self.adv_stats[0], self.T * self.N * n_slots
         _check(L.cda_gae_records_bootstrap(self.buf["reward"].data_ptr(), self.buf["value"].data_ptr(), self.buf["terminated"].data_ptr(), self.buf["truncated"].data_ptr(),
                                            self.T, self.N, self.A, k, float(reward_scale), float(gamma), float(lam), fin_index, fin_value, self.fin_cap if self.capture_ends else 0,
                                            self.buf["record"].data_ptr(), self.adv_stats.data_ptr(), st), "cda_gae_records_bootstrap")
@@ -763,6 +786,20 @@ class RolloutChains:
             import warnings
             warnings.warn(f"episode-end capture overflowed: {lost} of {lost + self.fin_cap} episode ends of this rollout found no slot (their time-limit bootstrap fell back to 0)")
         return max(0, lost)
+
+
+def check_trained_slots(slots, trained_slots):
+    """the placement a shared policy trains on: slots i32 [N, A] (CDAVecEnv.scripted_slots), slots < trained_slots unscripted, every slot behind them scripted;
+    ValueError otherwise (host arrays only: no device needed)"""
+    import numpy as np
+    slots, k = np.asarray(slots), int(trained_slots)
+    if not 1 <= k <= slots.shape[1] - 1:
+        raise ValueError(f"trained_slots must lie in 1 .. num_agents - 1 = {slots.shape[1] - 1}, got {k}")
+    if bool((slots[:, :k] != 0).any()):
+        raise ValueError(f"a scripted opponent sits in a trained slot (< trained_slots = {k}): scripted modules play the slots behind the trained ones")
+    if bool((slots[:, k:] == 0).any()):
+        raise ValueError(f"slot(s) at or above trained_slots = {k} are not scripted: every slot behind the trained ones must play a scripted profile "
+                         "(an unscripted slot there would play the policy without feeding its update)")
 
 
 class EpisodeReturns:

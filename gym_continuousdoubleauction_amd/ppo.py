@@ -530,7 +530,8 @@ def adapt_kl_coef(kl_coef, sampled_kl, kl_target):
 def train_fused(env, iters=4, horizon=64, lr=5e-5, epochs=4, reward_scale=None, seed=0, log=print, use_graph=True, chains=4, minibatch=262144,
                 gamma=None, lam=None, clip=None, vf_coef=None, ent_coef=None, policy=None, keep=None, sub_batches=None, objective=None, recorder=None, info_markets=0,
                 allreduce=None, world=1, first_market=0, episode_metrics=True, strict_nav_check=True, state_dependent_log_std=False, hidden=(256, 256),
-                checkpoint_dir=None, chkpt_freq=0, chkpt_keep=3, restore=None, iters_is_delta=False, activation="tanh", vf_share_layers=False):
+                checkpoint_dir=None, chkpt_freq=0, chkpt_keep=3, restore=None, iters_is_delta=False, activation="tanh", vf_share_layers=False,
+                trained_slots=None, opponents=None):
     """The PPO loop on the hand-written network kernels (mlp.py, include/cda_mlp.h): rollouts as `chains` independent per-chain launch
     sequences (policy forward + sampling -> env step -> auto reset, one HIP graph per chain, no cross-stream edge inside the horizon), the
     sample records completed by one GAE launch, the update as {gather + forward + loss + back-propagation, weight gradients, reduce, clip + Adam}
@@ -557,9 +558,48 @@ def train_fused(env, iters=4, horizon=64, lr=5e-5, epochs=4, reward_scale=None, 
     the end the env's markets and the learner's state are saved as checkpoint_dir/iter_<n> (n = iterations done), the newest chkpt_keep kept.  restore=True resumes
     from the newest checkpoint under checkpoint_dir, a path from that one: the env is restored instead of reset, and `iters` is the TARGET iteration count
     (iters_is_delta: that many more).  The resumed rollouts are bit-identical to the uninterrupted run's.  history entries carry the global iteration number.
-    Single-process runs only (world == 1), without a recorder; chkpt_freq > 0 needs a checkpoint_dir (ValueError otherwise)."""
-    if getattr(env, "scripted", False):        # (a scripted slot's sample record is no policy sample: it must not reach a loss)
-        raise ValueError("train_fused does not train on an env with scripted opponents attached (training against them is out of scope): clear_scripted() first")
+    Single-process runs only (world == 1), without a recorder; chkpt_freq > 0 needs a checkpoint_dir (ValueError otherwise).
+    trained_slots = k / opponents (training against scripted opponents, scripted.py): slots 0 .. k - 1 of every market play and train the one shared policy, slots
+    k .. A - 1 are scripted.  Either the caller attached the scripts (env.set_scripted; profiles may differ per market and slot) and passes trained_slots=k, or passes
+    opponents=[spec, ...] (scripted.parse_profile's forms): slot k + j of market m then plays opponents[(m + j) % P] (scripted.opponent_slots), attached here with seed
+    `seed` and market base `first_market`, and detached on exit, also on an exception.  The sample records of the scripted slots reach no loss: the advantage sums
+    cover the trained slots (cda_gae_records_slots) and the update reads the leading k records of every row through the record stride.  mean_reward and
+    episode_return are over the trained slots; history[i]["episode_metrics"]["modules"] is keyed policy_0, scripted_<i>_<law>.  ValueError: a scripted slot below k,
+    an unscripted slot at or above k, k outside 1 .. A - 1, opponents on an env that has scripts attached, world > 1 (data-parallel runs with scripted opponents are
+    out of scope); trained_slots=None on an env with scripts attached.  A checkpoint's args hold the profiles' canonical fields and k: a restore with other
+    opponents is refused."""
+    if opponents is not None:
+        from . import scripted as SC
+        kw = dict(locals())
+        opp = list(opponents)
+        if getattr(env, "scripted", False):
+            raise ValueError("train_fused(opponents=...) needs an env without scripted opponents attached: it attaches its own for the run (clear_scripted() first, or "
+                             "keep yours and pass trained_slots alone)")
+        if trained_slots is None:
+            raise ValueError("train_fused(opponents=...) needs trained_slots = the number of leading slots per market that the policy plays and trains")
+        if int(world) > 1 or allreduce is not None:
+            raise ValueError("training against scripted opponents is a single-process run: data-parallel runs (world > 1) with scripts are out of scope")
+        if not opp:
+            raise ValueError("opponents: None or a non-empty list of scripted opponents")
+        profiles = [SC.parse_profile(o) for o in opp]
+        slots = SC.opponent_slots(env.n_markets, env.num_agents, trained_slots, len(profiles))
+        for name in ("kw", "SC", "opp", "env", "opponents"):
+            kw.pop(name, None)
+        env.set_scripted(slots, profiles, seed=seed, market_index_base=int(first_market))       # (before the chains are captured)
+        try:
+            return train_fused(env, opponents=None, **kw)
+        finally:
+            if env.scripted:
+                env.clear_scripted()
+    k_tr = None if trained_slots is None else int(trained_slots)
+    if k_tr is None and getattr(env, "scripted", False):        # (a scripted slot's sample record is no policy sample: it must not reach a loss)
+        raise ValueError("train_fused trains on an env with scripted opponents attached only when told which slots the policy plays: pass trained_slots=k "
+                         "(or clear_scripted() first)")
+    if k_tr is not None:
+        from .mlp import check_trained_slots
+        if int(world) > 1 or allreduce is not None:
+            raise ValueError("training against scripted opponents is a single-process run: data-parallel runs (world > 1) with scripts are out of scope")
+        check_trained_slots(env.scripted_slots(), k_tr)
     from .mlp import EpisodeReturns, FusedPolicy, FusedUpdate, RolloutChains
     obj = dict(PPO_DEFAULTS)
     obj.update(objective or {})
@@ -580,6 +620,8 @@ def train_fused(env, iters=4, horizon=64, lr=5e-5, epochs=4, reward_scale=None, 
                     "hidden": [int(h) for h in hidden_widths(policy.theta)], "state_dependent_log_std": bool(has_log_std_head(policy.theta)),
                     "epochs": int(epochs), "lr": float(lr), "minibatch": int(minibatch), "seed": int(seed), "episode_metrics": bool(episode_metrics)}
         run_args = CK.with_vf_share_layers(CK.with_activation(run_args, policy.activation), getattr(policy, "vf_share_layers", False))
+        if k_tr is not None:
+            run_args = CK.with_scripted(run_args, env.scripted_profiles(), trained_slots=k_tr)
         run_id = CK.new_run_id()
         if restore:
             ck_path = CK.resolve_restore(checkpoint_dir, restore)
@@ -599,13 +641,23 @@ def train_fused(env, iters=4, horizon=64, lr=5e-5, epochs=4, reward_scale=None, 
             env.enable_episode_metrics(True)
     use_kl = obj["kl_coef"] > 0.0
     roll = RolloutChains(env, policy, T, groups=chains, seed=seed + 7919 * int(first_market), use_graphs=use_graph, with_dist=use_kl,
-                         capture_ends=bool(obj["bootstrap_truncation"]), info_markets=info_markets if recorder is not None else 0)
+                         capture_ends=bool(obj["bootstrap_truncation"]), info_markets=info_markets if recorder is not None else 0, trained_slots=k_tr)
+    if keep is not None:
+        keep.update(rollout=roll)                           # (from the start: a `log` callback can read each iteration's buffers through it)
     R = T * N
-    rows_mb = max(32, min(R, (max(1, minibatch // A) // 32) * 32))
+    S_ = A if k_tr is None else k_tr                        # samples per row that feed the update
+    rows_mb = max(32, min(R, (max(1, minibatch // S_) // 32) * 32))
     import os
     sub_batches = int(os.environ.get("CDA_PPO_SUB_BATCHES", "1")) if sub_batches is None else int(sub_batches)
-    upd = FusedUpdate(policy, R, rows_mb, A, sub_batches=sub_batches, allreduce=allreduce, world=world)
+    if k_tr is not None:
+        sub_batches = 1                                     # (the record stride is the fused update kernel's)
+    upd = FusedUpdate(policy, R, rows_mb, S_, sub_batches=sub_batches, allreduce=allreduce, world=world)
     returns = EpisodeReturns(N, A, dev)
+    module_of = module_names = None
+    if k_tr is not None and episode_metrics:                # who plays what: 0 = the policy, 1 + i = attached profile i
+        from . import scripted as SC
+        module_of = env.scripted_slot_tensor().clone()
+        module_names = ["policy_0"] + [SC.module_id(i, p) for i, p in enumerate(env.scripted_profiles())]
     kl_coef = float(obj["kl_coef"])
     history = []
     its = range(int(iters))
@@ -632,16 +684,21 @@ def train_fused(env, iters=4, horizon=64, lr=5e-5, epochs=4, reward_scale=None, 
             records = (records[0], records[1], records[2] * world)
         torch.cuda.synchronize(dev)
         t_roll = time.perf_counter()
-        upd.set_extra(kl_coef=kl_coef, vf_clip=obj["vf_clip"], dist_old=buf.get("dist"), log_std_old=roll.log_std_old if use_kl else None)
+        upd.set_extra(rec_stride=8 * A if k_tr is not None else 0, kl_coef=kl_coef, vf_clip=obj["vf_clip"], dist_old=buf.get("dist"),
+                      log_std_old=roll.log_std_old if use_kl else None)
         stats = upd.run(buf["obs"][:T].view(R, -1), epochs=epochs, clip=obj["clip"], vf_coef=obj["vf_coef"], ent_coef=obj["ent_coef"], lr=lr, max_norm=obj["max_norm"],
                         records=records)
-        em = env.collect_episode_metrics() if episode_metrics else None      # (two small launches, inside the timed region: the episodes that ended during this rollout)
+        # (two small launches, inside the timed region: the episodes that ended during this rollout)
+        em = (env.collect_episode_metrics() if module_of is None else env.collect_episode_metrics(module_of=module_of, n_modules=len(module_names))) if episode_metrics else None
         torch.cuda.synchronize(dev)
         t1 = time.perf_counter()
         acc = returns.update(buf, T).cpu()                                   # (outside the timed region, like everything below: logging only)
         stats = {k: float(v) for k, v in stats.items()}
+        if k_tr is not None:                                                 # the trained slots' statistics (EpisodeReturns keeps per-slot sums)
+            acc = acc[:, :k_tr]
         done = float(acc[1].sum())
-        stats.update(iter=it, mean_reward=float(buf["reward"].mean()), episode_return=(float(acc[0].sum()) / done) if done else None, episodes=done / A,
+        stats.update(iter=it, mean_reward=float((buf["reward"] if k_tr is None else buf["reward"][:, :, :k_tr]).mean()),
+                     episode_return=(float(acc[0].sum()) / done) if done else None, episodes=done / S_,
                      kl_coef=kl_coef, agent_steps=N * A * T, agent_steps_per_s=N * A * T / (t1 - t0), rollout_s=t_roll - t0, update_s=t1 - t_roll)
         kl_coef = adapt_kl_coef(kl_coef, stats["kl"], obj["kl_target"])
         roll.check_capture_overflow()                                       # (outside the timed region; warns)
@@ -649,10 +706,12 @@ def train_fused(env, iters=4, horizon=64, lr=5e-5, epochs=4, reward_scale=None, 
             recorder.record_rollout(roll, iteration=it)
         if em is not None:
             from . import episode_metrics as EM
-            summ = EM.summarise(*em, module_names=["policy_0"])
+            summ = EM.summarise(*em, module_names=module_names or ["policy_0"])
             stats["episode_metrics"] = dict(summ.get("all", {}), episodes=summ["episodes"], nav_conservation_violations=summ["nav_conservation_violations"],
                                             nav_conservation_error=summ["nav_conservation_error"], maker_fill_ratio_max=summ.get("maker_fill_ratio_max"),
                                             episode_len_mean=summ.get("episode_len_mean"))
+            if module_names is not None:
+                stats["episode_metrics"]["modules"] = summ["modules"]
         history.append(stats)
         log(json.dumps(stats))
         if em is not None:
@@ -773,7 +832,8 @@ def train(env, iters=4, horizon=64, lr=5e-5, epochs=4, reward_scale=1e-3, seed=0
     return model, history
 
 
-def main(argv=None):
+def main(argv=None, parse_only=False):
+    """parse_only: return the parsed arguments without touching a device (the flags' tests)"""
     p = argparse.ArgumentParser()
     p.add_argument("--markets", type=int, default=4096)
     p.add_argument("--agents", type=int, default=4)
@@ -804,7 +864,17 @@ def main(argv=None):
     p.add_argument("--iters-is-delta", action="store_true", help="with --restore: --iters counts further iterations instead of being the target")
     p.add_argument("--market-configs", default=None, metavar="FILE.json", help="per-market parameters: a JSON list of override dicts, market m runs entry m %% len(list) "
                                                                              "(market_params.PER_MARKET_KEYS; a max_step there may not exceed --max-step)")
+    p.add_argument("--trained-slots", type=int, default=None, metavar="K", help="fused loop, with --opponent: the policy plays and trains slots 0 .. K - 1 of every market")
+    p.add_argument("--opponent", action="append", default=None, metavar="SPEC",
+                   help="fused loop: a scripted opponent ('pass', 'maker', 'taker', 'imbalance', 'NAME:key=value,...') for the slots behind --trained-slots; repeat for several "
+                        "(slot K + j of market m plays opponent (m + j) mod P)")
     args = p.parse_args(argv)
+    if (args.opponent is None) != (args.trained_slots is None):
+        raise SystemExit("--opponent and --trained-slots go together")
+    if args.opponent is not None and args.legacy:
+        raise SystemExit("--opponent needs the fused loop")
+    if parse_only:
+        return args
     from .vec_env import CDAVecEnv
     from .market_params import load_market_configs, round_robin
     p_groups = max(1, min(args.groups, args.markets))
@@ -827,7 +897,8 @@ def main(argv=None):
         trained, hist = train_fused(env, iters=args.iters, horizon=args.horizon, use_graph=not args.no_graphs, chains=args.chains,
                               objective=RLLIB_DEFAULTS if args.objective == "rllib" else None, state_dependent_log_std=args.log_std_head, hidden=tuple(args.fcnet_hiddens),
                               checkpoint_dir=args.checkpoint_dir, chkpt_freq=args.chkpt_freq, chkpt_keep=args.chkpt_keep, restore=args.restore,
-                              iters_is_delta=args.iters_is_delta, activation=args.fcnet_activation, vf_share_layers=args.vf_share_layers)
+                              iters_is_delta=args.iters_is_delta, activation=args.fcnet_activation, vf_share_layers=args.vf_share_layers,
+                              trained_slots=args.trained_slots, opponents=args.opponent)
     flags = env.flags()
     _, bad = env.nav_conservation()
     tail = hist[2:] if len(hist) >= 4 else (hist[1:] or hist)
@@ -837,6 +908,7 @@ def main(argv=None):
                                       f"4 epochs, 262144-sample minibatches), horizon {args.horizon}, {args.iters} iterations, auto_reset on",
                           "objective": "legacy loop's own" if args.legacy else args.objective, "activation": args.fcnet_activation,
                           "markets": args.markets, "agents": args.agents, "horizon": args.horizon, "iters": args.iters, "env_groups": p_groups,
+                          "trained_slots": args.trained_slots, "opponents": args.opponent,
                           "loop": "legacy (PyTorch network)" if args.legacy else (f"fused: hand-written bf16 MFMA network (csrc/cda_mlp.hip), {args.chains} rollout chains; GAE straight into the sample records (one launch); "
                                                                                       "a minibatch step = {gather + forward + loss + backward in one launch, weight gradients, reduce, Adam}"),
                           "hip_graphs": "none" if args.no_graphs else ("one graph per rollout step (policy + env step + buffer writes), one per minibatch step of the update"

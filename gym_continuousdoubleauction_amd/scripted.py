@@ -101,6 +101,35 @@ def is_scripted_spec(spec):
     return isinstance(spec, Profile) or (isinstance(spec, str) and spec.partition(":")[0] in NAMED)
 
 
+LAW_NAMES = {v: k for k, v in LAWS.items()}
+
+
+def module_id(index, profile):
+    """the module id of scripted opponent `index` of a training run: scripted_<index>_<law> (what episode metrics, module returns and league.json name it by)"""
+    return f"scripted_{int(index)}_{LAW_NAMES[int(profile.law)]}"
+
+
+def profile_record(profile):
+    """the canonical fields of a profile as plain Python numbers (the floats as the float32 the device reads): what a checkpoint's `args` and league.json hold -
+    two specs that parse to the same profile give the same record"""
+    p = parse_profile(profile)
+    return {f.name: (int(getattr(p, f.name)) if f.name in _INT_FIELDS else float(np.float32(getattr(p, f.name)))) for f in dataclasses.fields(Profile)}
+
+
+def opponent_slots(n_markets, num_agents, trained_slots, n_opponents):
+    """the placement ppo.train_fused(opponents=[...]) attaches: i32 [N, A], 0 in slots < trained_slots, slot trained_slots + j of market m plays
+    opponents[(m + j) % P] (the value 1 + that index)"""
+    N, A, k, P = int(n_markets), int(num_agents), int(trained_slots), int(n_opponents)
+    if not 1 <= k <= A - 1:
+        raise ValueError(f"trained_slots must lie in 1 .. num_agents - 1 = {A - 1}, got {k}")
+    if not 1 <= P <= MAX_PROFILES:
+        raise ValueError(f"between 1 and {MAX_PROFILES} scripted opponents, got {P}")
+    out = np.zeros((N, A), np.int32)
+    m, j = np.meshgrid(np.arange(N), np.arange(A - k), indexing="ij")
+    out[:, k:] = 1 + (m + j) % P
+    return out
+
+
 def profiles_array(profiles, validate=True):
     """numpy PROFILE_DTYPE [n] (the 64-byte device layout) of a list of Profiles"""
     out = np.zeros(len(profiles), PROFILE_DTYPE)

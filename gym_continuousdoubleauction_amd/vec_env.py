@@ -766,7 +766,8 @@ class CDAVecEnv:
         """Attach scripted opponents (include/cda.h cda_scripted_attach): slot_script int [N, A], 0 = the slot is not scripted, 1 + k = it plays profiles[k];
         profiles: 1 .. 16 scripted.Profile objects (or names / 'NAME:key=value' strings).  `seed` keys the taker's draws, market_index_base + market is the
         market's index in them.  The two tables become resident tensors the env keeps; rollout chains and run_scripted() then play the laws.  While attached
-        the one-launch policy step is off (cda_policy_step_supported answers 0) and the fused trainers refuse the env."""
+        the one-launch policy step is off (cda_policy_step_supported answers 0); ppo.train_fused trains on the env only when told the trained slots (trained_slots=k)
+        and the league attaches its own (train_league_fused(scripted_opponents=...))."""
         from .scripted import MAX_PROFILES, parse_profile, profiles_array
         profs = [parse_profile(p) for p in profiles]
         if not 1 <= len(profs) <= MAX_PROFILES:
@@ -794,6 +795,14 @@ class CDAVecEnv:
     def scripted_slots(self):
         """the attached slot table as a host array i32 [N, A] (zeros while nothing is attached)"""
         return self._script.slots_host if self._script is not None else np.zeros((self.n_markets, self.num_agents), np.int32)
+
+    def scripted_slot_tensor(self):
+        """the RESIDENT slot table i32 [N, A] on the device - the one k_script_actions reads at every step.  Rewriting it in place (values 0 .. the number of
+        attached profiles; the league's per-episode assignment does, cda_league_assign_scripted) changes who plays the scripts from the next step on without a
+        re-attach: the script epoch, and graphs captured on it, hold.  scripted_slots() stays the table as attached."""
+        if self._script is None:
+            raise RuntimeError("scripted_slot_tensor() needs scripted opponents: call set_scripted() first")
+        return self._script.slot_script
 
     def scripted_profiles(self):
         return list(self._script.profiles) if self._script is not None else []

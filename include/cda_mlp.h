@@ -230,6 +230,15 @@ int cda_gae_records(const double* reward, const float* value, const uint8_t* ter
 int cda_gae_records_bootstrap(const double* reward, const float* value, const uint8_t* terminated, const uint8_t* truncated, int32_t n_steps, int64_t n_markets,
                               int32_t num_agents, int32_t n_trainable, float reward_scale, float gamma, float lam,
                               const int32_t* fin_index, const float* fin_value, int64_t fin_value_stride, float* rec, double* stats, void* stream);
+/* Training against scripted opponents (include/cda.h cda_scripted_attach): ONE shared policy plays and trains slots 0 .. n_slots - 1 of every market, the slots behind
+ * them are scripted - their records hold no policy sample and must reach no loss.  cda_gae_records_bootstrap(n_trainable = 0)'s recursion, thread for thread, over the
+ * slots < n_slots only: words ADV, RET of those slots' records are bit-equal to what it writes there, the other slots' words ADV, RET are NOT written, and stats2 f64[2]
+ * sums the T * N * n_slots trained samples (that product is the count the update normalises with).  value f32 [T+1][N]; fin_index (NULL = no time-limit bootstrap) i32
+ * [T][N], fin_value f32 [capacity].  The update then reads the leading slots through the record stride: cda_mlp_forward_backward(agents_per_row = n_slots,
+ * cda_ppo_extra.rec_stride = 8 * num_agents).  1 <= n_slots <= num_agents. */
+int cda_gae_records_slots(const double* reward, const float* value, const uint8_t* terminated, const uint8_t* truncated, int32_t n_steps, int64_t n_markets,
+                          int32_t num_agents, int32_t n_slots, float reward_scale, float gamma, float lam,
+                          const int32_t* fin_index, const float* fin_value, float* rec, double* stats2, void* stream);
 /* value f32 [n_rows] (net p: + p * value_stride) <- the value network of each of n_nets banked networks on obs f32 [n_rows][168] (one launch). */
 int cda_mlp_values(const void* wb_bank, const float* theta_bank, int32_t n_nets, const float* obs, int64_t n_rows, float* value, int64_t value_stride, void* stream);
 /* ... of the first min(n_rows, *n_rows_dev) rows only (n_rows_dev i32[1] on the device, NULL = all): the captured list's length lives on the device (fin_count) -
@@ -335,6 +344,13 @@ int cda_gae_records_league(const double* reward, const float* value, const uint8
  * itself (index into the pool; -1 for the trainable slots) - what names the module in an episode record. */
 int cda_league_assign(const uint32_t* episode_crc, int32_t n_markets, int32_t num_agents, int32_t n_trainable, const double* pool_cdf, const int32_t* pool_net,
                       int32_t pool_size, int32_t* slot_net, int32_t* slot_pool, void* stream);
+/* ... with scripted modules (include/cda.h cda_scripted_attach) in the pool: cda_league_assign's draw bit for bit - the same generator, the same searchsorted on the
+ * (longer) cdf - and one more table and output: pool_script i32 [pool_size], 0 or 1 + the index of the profile a scripted pool entry plays (its pool_net entry is
+ * CDA_LEAGUE_RANDOM: the scripted launch overwrites the random module's action), and slot_script i32 [N][A] <- pool_script[draw], 0 in the trainable slots and where
+ * a network or the random module plays.  slot_script is the table the env was attached with (resident: rewritten in place per episode, no re-attach, captured rollout
+ * graphs stay valid).  With an all-zero pool_script the other outputs equal cda_league_assign's. */
+int cda_league_assign_scripted(const uint32_t* episode_crc, int32_t n_markets, int32_t num_agents, int32_t n_trainable, const double* pool_cdf, const int32_t* pool_net,
+                               const int32_t* pool_script, int32_t pool_size, int32_t* slot_net, int32_t* slot_script, int32_t* slot_pool, void* stream);
 
 /* Device self-test of the operand / accumulator conventions this file is built on: D f32[32][32] = A bf16-rounded f32[32][16] x
  * B f32[16][32] through one v_mfma_f32_32x32x16_bf16 (host pointers; synchronous). */
