@@ -29,6 +29,7 @@ SYMBOLS = [
     "cda_book_counts", "cda_book_levels", "cda_book_impact", "cda_book_agents", "cda_book_offsets", "cda_book_pack",
     "cda_scripted_attach", "cda_scripted_detach", "cda_scripted_epoch", "cda_scripted_attached", "cda_scripted_actions", "cda_scripted_decide_host",
     "cda_scripted_profile_check_host",
+    "cda_submit_orders", "cda_submit_orders_window", "cda_order_msgs_check_host", "cda_order_msgs_check_agents_host",
 ]
 
 
@@ -214,6 +215,10 @@ def lib():
     L.cda_scripted_actions.argtypes = [vp, i32, i32, vp, i64] + [vp] * 5 + [vp] * 3 + [vp]
     L.cda_scripted_decide_host.argtypes = [vp, i32, vp, vp, i64, u64, u64, vp, vp, vp] + [vp] * 5
     L.cda_scripted_profile_check_host.argtypes = [vp, i32]
+    L.cda_submit_orders.argtypes = [vp, i32, i32, vp, vp, vp, vp, C.c_uint32, vp]
+    L.cda_submit_orders_window.argtypes = [vp, i32, i32, vp, vp, i64, i64, i64, vp, vp, C.c_uint32, vp]
+    L.cda_order_msgs_check_host.argtypes = [vp, vp, i64, C.POINTER(i64)]
+    L.cda_order_msgs_check_agents_host.argtypes = [i32, vp, i64, C.POINTER(i64)]
     L.cda_ppo_loss32.argtypes = [vp] * 10 + [i64, i32, i32, f32, f32, f32, vp, vp, vp, i64, i32, i32, vp]
     L.cda_gae_records.argtypes = [vp, vp, vp, vp, i32, i64, i32, f32, f32, f32, vp, vp, vp]
     L.cda_ppo_loss_records.argtypes = [vp, vp, vp, vp, i64, vp, i64, i32, i32, f32, f32, f32, vp, vp, vp, i64, i32, i32, vp]

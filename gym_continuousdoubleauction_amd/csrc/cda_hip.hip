@@ -330,11 +330,13 @@ struct RunArgs {
 #define CDA_CAP 256
 #define CDA_CAPNS cap256
 #include "cda_kernels.inc"
+#include "cda_orders.inc"
 #undef CDA_CAP
 #undef CDA_CAPNS
 #define CDA_CAP 512
 #define CDA_CAPNS cap512
 #include "cda_kernels.inc"
+#include "cda_orders.inc"
 #undef CDA_CAP
 #undef CDA_CAPNS
 
@@ -1609,3 +1611,5 @@ int64_t cda_state_bytes_per_market(const cda_env* e) { return e ? (int64_t)e->P.
 #include "cda_book_report.inc"
 // scripted opponents (cda_scripted_*): one wave per market turns the market's state into the rule-based slots' actions
 #include "cda_scripted.inc"
+// order streams (cda_submit_orders): explicit per-market message lists through place_order / mark_to_mkt, one wave per market (the kernels: behind cda_kernels.inc above)
+#include "cda_orders.inc"

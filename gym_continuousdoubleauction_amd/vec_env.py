@@ -757,6 +757,80 @@ class CDAVecEnv:
             check(lib().cda_book_pack(self._h, first, n, off.data_ptr(), total, rows.data_ptr() if total else None, total, self._stream()), "cda_book_pack")
         return rows, off
 
+    # ------------------------------------------------------------------ order streams: explicit orders into many markets in one launch (orders.py)
+    def submit_orders(self, streams=None, *, offsets=None, msgs=None, first_market=0, n_markets=None, clear_step_counters=False, results=True, max_per_launch=65536,
+                      max_len=None):
+        """Play a list of explicit messages into every market of a range (include/cda.h cda_submit_orders): one asynchronous launch on the caller's stream, a wave
+        per market, equivalent - bit for bit in the market's record - to place_order() / mark_to_mkt() once per valid message, in order.  No observation frame
+        is pushed and t_step does not move: the next step() sees the book.  On a tape-enabled env the fills are recorded.
+        streams: a list of n per-market sequences of (trader, type, side, size, price[, tag]) or ("mark",) (orders.pack) - or the packed form as tensors /
+        arrays: offsets i64 [n + 1], msgs (orders.MSG_DTYPE, or uint8 / int32 rows of 16 bytes) with market first_market + i owning msgs[offsets[i] : offsets[i + 1]].
+        A message outside the accepted domain (orders.valid) is skipped and reported; a market with an empty stream is not touched.
+        clear_step_counters: clear every account's step counters behind a market's stream, so that seeded or exogenous flow does not reach the next step's reward terms.
+        -> (results, summary): results int32 [total, 4] (orders.RESULT_DTYPE rows: status, n_fills, position_delta, resting_delta; None with results=False),
+        summary int32 [n, 4] = (done, rejected, invalid, fills) per market, invalid = -1 for a market whose offsets are not a stream.  Device tensors.
+        A stream longer than max_per_launch is played in successive launches of at most that many messages per market - the same final state and results -, so
+        that no single launch runs unbounded.  max_len: the longest stream, when the caller knows it; for device offsets the default reads it back (8 bytes)."""
+        from . import orders as OR
+        first, n = self._market_range("submit_orders", first_market, n_markets)
+        if int(max_per_launch) < 1:
+            raise ValueError("max_per_launch must be >= 1")
+        if streams is not None:
+            if offsets is not None or msgs is not None:
+                raise ValueError("submit_orders takes streams or (offsets, msgs), not both")
+            if len(streams) != n:
+                raise ValueError(f"{len(streams)} streams for {n} markets")
+            offsets, msgs = OR.pack(streams)
+        if offsets is None or msgs is None:
+            raise ValueError("submit_orders needs streams or (offsets, msgs)")
+        if isinstance(offsets, np.ndarray) or not isinstance(offsets, torch.Tensor):
+            off_h = np.ascontiguousarray(np.asarray(offsets, np.int64))
+            if max_len is None:
+                max_len = int(np.diff(off_h).max()) if off_h.size > 1 else 0
+            offsets = torch.from_numpy(off_h).to(self.device)
+        if isinstance(msgs, np.ndarray):
+            msgs = torch.from_numpy(np.ascontiguousarray(msgs).view(np.uint8).reshape(-1, 16)).to(self.device)
+        if offsets.dtype != torch.int64 or offsets.numel() != n + 1 or offsets.device != self.device or not offsets.is_contiguous():
+            raise ValueError(f"offsets must be a contiguous int64 [{n + 1}] tensor on {self.device}")
+        if msgs.device != self.device or not msgs.is_contiguous() or (msgs.numel() * msgs.element_size()) % 16 != 0 or msgs.data_ptr() % 16 != 0:
+            raise ValueError(f"msgs must be a contiguous, 16-byte aligned tensor of 16-byte messages on {self.device}")
+        total = msgs.numel() * msgs.element_size() // 16
+        if max_len is None:
+            max_len = int((offsets[1:] - offsets[:-1]).max().item())
+        self.host_epoch += 1
+        self.join()
+        flags = OR.CLEAR_STEP_COUNTERS if clear_step_counters else 0
+        step = int(max_per_launch)
+        with torch.cuda.device(self.device):
+            res = torch.zeros((max(total, 1), 4), dtype=torch.int32, device=self.device)[:total] if results else None
+            summary = None
+            for skip in range(0, max(int(max_len), 1), step):
+                part = torch.empty((n, 4), dtype=torch.int32, device=self.device)
+                check(lib().cda_submit_orders_window(self._h, first, n, offsets.data_ptr(), msgs.data_ptr() if total else offsets.data_ptr(), total, skip, step,
+                                                     res.data_ptr() if results and total else None, part.data_ptr(), flags, self._stream()), "cda_submit_orders")
+                if summary is None:
+                    summary = part
+                else:                                          # (a market whose offsets are not a stream says -1 in every window)
+                    summary = torch.where(summary[:, 2:3] < 0, summary, summary + part)
+        return res, summary
+
+    def seed_books(self, bids, asks, market=None, first_market=0, n_markets=None):
+        """Start markets from a non-empty book: get_book() / book_orders() rows of ONE market (price, qty, owner, order_id, timestamp; queue order) rebuilt by limit
+        orders (orders.from_book) in market `market`, or - market=None - in every market of [first_market, first_market + n_markets), in one launch, with the step
+        counters cleared behind them.  Prices, quantities, owners and queue positions are the dump's; ids and timestamps are new; the escrow is taken from
+        the target accounts, and an order its account cannot afford is rejected (see the returned summary).  Meant for freshly reset markets.  -> (results, summary)
+        of submit_orders."""
+        from . import orders as OR
+        stream = OR.from_book(bids, asks)
+        if market is not None:
+            first_market, n_markets = int(market), 1
+        first, n = self._market_range("seed_books", first_market, n_markets)
+        _, one = OR.pack([stream])
+        L = len(one)
+        msgs = torch.from_numpy(one.view(np.uint8).reshape(-1, 16)).to(self.device).repeat(n, 1)
+        offsets = torch.arange(n + 1, dtype=torch.int64, device=self.device) * L
+        return self.submit_orders(offsets=offsets, msgs=msgs, first_market=first, n_markets=n, clear_step_counters=True, max_len=L)
+
     # ------------------------------------------------------------------ scripted opponents: rule-based agents on the device (scripted.py states the laws)
     @property
     def scripted(self):

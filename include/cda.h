@@ -700,6 +700,56 @@ int cda_scripted_decide_host(const void* profiles_host, int32_t n_profiles, cons
                              int32_t* category, float* size_mean, float* size_sigma, int32_t* price, int32_t* price_offset);
 int cda_scripted_profile_check_host(const void* profiles_host, int32_t n_profiles);
 
+/* ---- order streams: explicit orders into every market of a range, in one launch ------------------------------------------------------------
+ * cda_submit_orders plays, for every market of [first_market, first_market + n_markets), the messages msgs_dev[offsets_dev[i] .. offsets_dev[i + 1])
+ * (i counts from the range's first market) in order: ONE asynchronous launch on `stream`, a wave per market, the market's record loaded once and
+ * stored once.  For every market the stream is equivalent, bit for bit in the market's record (header, tile, HBM ring, accounts, sticky flags,
+ * peak_orders, lob_time, order ids), to calling cda_place_order / cda_mark_to_mkt once per valid message, in order - the same instance of the
+ * matching code (general book, full position-value semantics), the cached level aggregation invalidated as the hook does, no observation frame
+ * pushed, t_step not moved, the episode-metric tallies not touched.  On a tape-enabled env the tape-writing sibling runs: the tape then holds what
+ * the hook would have written call by call.
+ *   validity     a message outside the hook's accepted domain - trader outside 0 .. num_agents-1, type outside 0 .. 4, side outside 0 / 1, size < 1,
+ *                price < 1 for types 1 .. 3 - is SKIPPED: status CDA_ORD_INVALID, zero deltas, counted in the summary; the rest of the stream runs.  A
+ *                CDA_OP_MARK message carries nothing but its type: its other fields are not looked at.  The device validates (the streams live in device
+ *                memory); cda_order_msgs_check_host applies the same rule to host data: *first_bad_out = index of the first invalid message, -1 = none.
+ *                (env NULL: trader is checked against CDA_MAX_AGENTS; cda_order_msgs_check_agents_host takes the agent count itself - neither needs a device.)
+ *   empty        a market whose stream is empty is neither loaded nor stored: its record stays byte-identical.  So does a market none of whose messages
+ *                was valid.
+ *   offsets      non-decreasing.  A negative or decreasing pair makes that market's stream empty and sets its summary's `invalid` to -1.
+ *   results_dev  one cda_order_result per message, indexed like msgs_dev (16-B aligned), or NULL.  summary_dev: int32 [n_markets][4] = messages done,
+ *                rejected, invalid, and fills (16-B aligned), or NULL.
+ *   flags        CDA_ORDERS_CLEAR_STEP_COUNTERS: after a market's stream every account's step counters are cleared (exchg_helper.py:116-120), so that
+ *                seeded or exogenous flow does not reach the next step's reward terms - the one difference from the hook sequence.
+ *   cda_submit_orders_window   the same for the messages [skip, skip + limit) of every market's stream, n_msgs = messages behind msgs_dev (a market whose
+ *                offsets reach beyond them is treated like a decreasing pair; -1 = not known): successive windows give the state of one launch, so a caller
+ *                can bound what a single launch runs.
+ * NULL env / offsets / msgs, a range outside the env, a misaligned pointer, unknown flag bits, skip < 0, limit < 1: CDA_ERR_INVALID, nothing is launched. */
+typedef struct cda_order_msg {       /* one message, 16 bytes, device memory */
+    int32_t price;    /* ticks; ignored for a market order and for CDA_OP_MARK */
+    int32_t size;
+    int16_t trader;   /* 0 .. num_agents-1 */
+    int8_t  type;     /* 0 market, 1 limit, 2 modify, 3 cancel (cda_place_order's), 4 = CDA_OP_MARK: Exchg_Helper.mark_to_mkt, no trader */
+    int8_t  side;     /* 0 bid, 1 ask */
+    int32_t tag;      /* caller's, copied nowhere: for the caller's own bookkeeping */
+} cda_order_msg;
+typedef struct cda_order_result {    /* one result per message, 16 bytes */
+    int32_t status;          /* CDA_ORD_INVALID: not executed; CDA_ORD_REJECTED: Trader._order_approved said no; CDA_ORD_DONE */
+    int32_t n_fills;         /* fills this message caused (self-trades included: one tape record each) */
+    int32_t position_delta;  /* trader's net_position after - before */
+    int32_t resting_delta;   /* resting orders of the market, both sides, tile + HBM ring, after - before */
+} cda_order_result;
+#define CDA_OP_MARK 4
+#define CDA_ORD_INVALID  0
+#define CDA_ORD_REJECTED 1
+#define CDA_ORD_DONE     2
+#define CDA_ORDERS_CLEAR_STEP_COUNTERS 1u
+int cda_submit_orders(cda_env* env, int32_t first_market, int32_t n_markets, const int64_t* offsets_dev, const cda_order_msg* msgs_dev,
+                      cda_order_result* results_dev, int32_t* summary_dev, uint32_t flags, void* stream);
+int cda_submit_orders_window(cda_env* env, int32_t first_market, int32_t n_markets, const int64_t* offsets_dev, const cda_order_msg* msgs_dev, int64_t n_msgs,
+                             int64_t skip, int64_t limit, cda_order_result* results_dev, int32_t* summary_dev, uint32_t flags, void* stream);
+int cda_order_msgs_check_host(const cda_env* env, const cda_order_msg* msgs_host, int64_t n, int64_t* first_bad_out);
+int cda_order_msgs_check_agents_host(int32_t num_agents, const cda_order_msg* msgs_host, int64_t n, int64_t* first_bad_out);
+
 /* ---- per-market parameters: many configurations in one env ----------------------------------------------------------------------------
  * Every market reads the fields below from a row of its own (a device table every env has; cda_create fills each row from the config).  The
  * config's other fields - num_agents, n_hist, book_capacity, book_spill, auto_reset - set shapes, memory and kernel choice and hold for the
