@@ -33,14 +33,18 @@ SYMBOLS = [
 ]
 
 
-# every symbol include/cda_mlp.h declares
+# every symbol include/cda_mlp.h itself declares: the network kernels, compiled once per (history depth, activation, vf_share_layers) - mlp_variant_suffixes()
 MLP_SYMBOLS = [
-    "cda_mlp_tile_rows", "cda_mlp_permutation", "cda_mlp_pack", "cda_mlp_policy_step", "cda_mlp_forward", "cda_mlp_prep_rows", "cda_mlp_forward_train", "cda_mlp_backward",
-    "cda_mlp_wgrad", "cda_mlp_adam", "cda_ppo_loss32", "cda_gae_records", "cda_ppo_loss_records", "cda_mlp_forward_backward", "cda_mlp_rollout_chain", "cda_mlp_selftest_mfma",
-    "cda_mlp_reduce", "cda_mlp_apply", "cda_gae_records_bootstrap", "cda_mlp_values", "cda_mlp_values_counted", "cda_episode_returns", "cda_mlp_league_step", "cda_mlp_league_rollout_chain",
-    "cda_gae_records_league", "cda_league_assign", "cda_mlp_wgrad_jobs",
+    "cda_mlp_tile_rows", "cda_mlp_pack", "cda_mlp_policy_step", "cda_mlp_forward", "cda_mlp_prep_rows", "cda_mlp_forward_train", "cda_mlp_backward",
+    "cda_mlp_wgrad", "cda_mlp_adam", "cda_mlp_forward_backward", "cda_mlp_rollout_chain", "cda_mlp_selftest_mfma",
+    "cda_mlp_reduce", "cda_mlp_apply", "cda_mlp_values", "cda_mlp_values_counted", "cda_mlp_league_step", "cda_mlp_league_rollout_chain",
+    "cda_mlp_wgrad_jobs",
     "cda_mlp_policy_act", "cda_mlp_league_act", "cda_mlp_eval_chain", "cda_mlp_league_eval_chain",
-    "cda_gae_records_slots", "cda_league_assign_scripted",
+]
+# every symbol include/cda_learner.h declares: the learner-side kernels that depend on none of the three (csrc/cda_learner.hip) - ONE copy each, never suffixed
+LEARNER_SYMBOLS = [
+    "cda_mlp_permutation", "cda_ppo_loss32", "cda_ppo_loss_records", "cda_gae_records", "cda_gae_records_bootstrap", "cda_gae_records_slots", "cda_gae_records_league",
+    "cda_episode_returns", "cda_league_assign", "cda_league_assign_scripted",
 ]
 # the same entry points compiled for other history depths carry the suffix _h<H> (include/cda_mlp.h CDA_MLP_HIST_VARIANTS, csrc/cda_mlp_variant.h)
 MLP_HIST_VARIANTS = (1, 2, 3, 6, 7, 8)
@@ -159,7 +163,6 @@ def lib():
     L.cda_mlp_wgrad_jobs.argtypes = []
     L.cda_mlp_wgrad_jobs.restype = i32
     L.cda_mlp_pack.argtypes = [vp, vp, vp]
-    L.cda_mlp_permutation.argtypes = [u64, i64, vp, vp]
     L.cda_mlp_policy_step.argtypes = [vp, vp, vp, i32, i32, i32, u64, vp, i64] + [vp] * 8 + [vp]
     L.cda_mlp_policy_act.argtypes = [vp, vp, vp, i32, i32, i32] + [vp] * 8 + [vp]
     L.cda_mlp_forward.argtypes = [vp, vp, vp, i64, i64, vp, vp]
@@ -170,19 +173,13 @@ def lib():
     L.cda_mlp_adam.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, i64, f32, f32, f32, vp, f32, f32, f32, f32, f32, vp, vp, vp]
     L.cda_mlp_reduce.argtypes = [vp, i32, vp, i32, vp, i64, f32, f32, f32, vp, vp, vp, vp, vp]
     L.cda_mlp_apply.argtypes = [vp, vp, vp, vp, vp, vp, i32, f32, f32, f32, f32, f32, vp, vp]
-    L.cda_gae_records_bootstrap.argtypes = [vp, vp, vp, vp, i32, i64, i32, i32, f32, f32, f32, vp, vp, i64, vp, vp, vp]
-    L.cda_gae_records_league.argtypes = [vp, vp, vp, vp, i32, i64, i32, i32, f32, f32, f32, vp, vp, vp]
     L.cda_mlp_values.argtypes = [vp, vp, i32, vp, i64, vp, i64, vp]
     L.cda_mlp_values_counted.argtypes = [vp, vp, i32, vp, i64, vp, vp, i64, vp]
-    L.cda_episode_returns.argtypes = [vp, vp, vp, i32, i64, i32, vp, vp, vp, vp, vp]
     L.cda_mlp_league_step.argtypes = [C.POINTER(League), vp, i32, i32, i32, u64, vp, i64] + [vp] * 8 + [i64, vp, vp, i64, vp]
     L.cda_mlp_league_rollout_chain.argtypes = [vp, C.POINTER(League), i32, i32, i32, u64, vp, C.POINTER(RolloutBufs), i32, vp]
     L.cda_mlp_league_act.argtypes = L.cda_mlp_league_step.argtypes
     L.cda_mlp_eval_chain.argtypes = [vp, vp, vp, i32, i32, i32, C.POINTER(RolloutBufs), i32, vp]
     L.cda_mlp_league_eval_chain.argtypes = L.cda_mlp_league_rollout_chain.argtypes
-    L.cda_league_assign.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp, vp, vp]
-    L.cda_league_assign_scripted.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp]
-    L.cda_gae_records_slots.argtypes = [vp, vp, vp, vp, i32, i64, i32, i32, f32, f32, f32, vp, vp, vp, vp, vp]
     L.cda_step_range_capture.argtypes = [vp, i32, i32] + [vp] * 6 + [vp] * 4 + [C.POINTER(K.InfoPtrs), vp, i32, vp, vp, vp]
     L.cda_policy_step_supported.argtypes = [vp]
     L.cda_policy_step_advised.argtypes = [vp]
@@ -219,17 +216,25 @@ def lib():
     L.cda_submit_orders_window.argtypes = [vp, i32, i32, vp, vp, i64, i64, i64, vp, vp, C.c_uint32, vp]
     L.cda_order_msgs_check_host.argtypes = [vp, vp, i64, C.POINTER(i64)]
     L.cda_order_msgs_check_agents_host.argtypes = [i32, vp, i64, C.POINTER(i64)]
-    L.cda_ppo_loss32.argtypes = [vp] * 10 + [i64, i32, i32, f32, f32, f32, vp, vp, vp, i64, i32, i32, vp]
-    L.cda_gae_records.argtypes = [vp, vp, vp, vp, i32, i64, i32, f32, f32, f32, vp, vp, vp]
-    L.cda_ppo_loss_records.argtypes = [vp, vp, vp, vp, i64, vp, i64, i32, i32, f32, f32, f32, vp, vp, vp, i64, i32, i32, vp]
     L.cda_mlp_forward_backward.argtypes = [vp, vp, vp, vp, i64, i64, vp, vp, i64, i32, f32, f32, f32, C.POINTER(PpoExtra), vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]
     L.cda_mlp_rollout_chain.argtypes = [vp, vp, vp, i32, i32, i32, u64, vp, C.POINTER(RolloutBufs), i32, vp]
     L.cda_mlp_selftest_mfma.argtypes = [i32, vp, vp, vp]
+    # include/cda_learner.h: bound once, they have no variants
+    L.cda_mlp_permutation.argtypes = [u64, i64, vp, vp]
+    L.cda_ppo_loss32.argtypes = [vp] * 10 + [i64, i32, i32, f32, f32, f32, vp, vp, vp, i64, i32, i32, vp]
+    L.cda_ppo_loss_records.argtypes = [vp, vp, vp, vp, i64, vp, i64, i32, i32, f32, f32, f32, vp, vp, vp, i64, i32, i32, vp]
+    L.cda_gae_records.argtypes = [vp, vp, vp, vp, i32, i64, i32, f32, f32, f32, vp, vp, vp]
+    L.cda_gae_records_bootstrap.argtypes = [vp, vp, vp, vp, i32, i64, i32, i32, f32, f32, f32, vp, vp, i64, vp, vp, vp]
+    L.cda_gae_records_slots.argtypes = [vp, vp, vp, vp, i32, i64, i32, i32, f32, f32, f32, vp, vp, vp, vp, vp]
+    L.cda_gae_records_league.argtypes = [vp, vp, vp, vp, i32, i64, i32, i32, f32, f32, f32, vp, vp, vp]
+    L.cda_episode_returns.argtypes = [vp, vp, vp, i32, i64, i32, vp, vp, vp, vp, vp]
+    L.cda_league_assign.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp, vp, vp]
+    L.cda_league_assign_scripted.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("cda_strerror", "cda_group_range"):
             fn.restype = C.c_int
-    for sfx in mlp_variant_suffixes():                       # same signatures, other observation width / activation
+    for sfx in mlp_variant_suffixes():                       # same signatures, other observation width / activation (LEARNER_SYMBOLS have no variants)
         for name in MLP_SYMBOLS:
             base, var = getattr(L, name), getattr(L, name + sfx)
             var.argtypes, var.restype = base.argtypes, base.restype

@@ -20,8 +20,10 @@
 //   k_mlp_fwd<MT, MODE>   4 waves = 32 MT rows x one network half (256 features: wave w owns 64, two paired tiles); the rollout's policy step
 //                         (MODE_SAMPLE: forward + sampling + records, halves in separate workgroups), the bootstrap value, plain outputs
 //   k_mlp_fb              the update: gather + forward + loss + back-propagation of a 64-row tile half, one launch (the default path)
-//   k_mlp_fwd8 / k_mlp_bwd8 / k_mlp_bwd / k_ppo_loss*   the same steps as separate kernels (FusedUpdate(fused=False); the tests hold both equal)
-//   k_mlp_wgrad, k_grad_reduce, k_adam, k_make_perm, k_prep_rows, k_gae_records
+//   k_mlp_fwd8 / k_mlp_bwd8 / k_mlp_bwd   the same steps as separate kernels, around csrc/cda_learner.hip's loss (FusedUpdate(fused=False); the tests hold both equal)
+//   k_mlp_wgrad, k_grad_reduce, k_adam, k_prep_rows
+// One object file of this source per (history depth, activation, vf_share_layers), every entry point renamed (cda_mlp_variant.h).  What depends on none of the three -
+// the permutation, the unfused loss, GAE into the records, episode returns, league assignment - is csrc/cda_learner.hip, compiled once; nothing here calls into it.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -496,30 +498,6 @@ __global__ __launch_bounds__(512) void k_mlp_fwd8(FwdArgs A) {
     MLP_MARK8(12);
     if (half == 0) __syncthreads();                                             // stage 5: the policy half's matching barrier
     MLP_MARK8(13);
-}
-
-// ---- update: the epoch's shuffle as a keyed bijection (no sort) -----------------------------------------------------------------------
-// perm[i] = walk(i): a bijective mixer on [0, 2^bits) (add, odd multiply, xor-shift: each step invertible), iterated until the value falls
-// below n (cycle walking: < 2 rounds on average, since 2^bits < 2 n).  torch.randperm is a device sort: ~10 launches, 130 us per epoch.
-__device__ __forceinline__ unsigned int perm_mix(unsigned int x, int bits, unsigned long long key) {
-    const unsigned int mask = bits >= 32 ? 0xffffffffu : ((1u << bits) - 1u);
-    const int s1 = (bits + 1) / 2, s2 = (2 * bits + 2) / 3;
-    #pragma unroll
-    for (int r = 0; r < 4; r++) {
-        x = (x + (unsigned int)(key >> (16 * r))) & mask;
-        x = (x * 0x9E3779B1u) & mask;
-        x ^= x >> s1;
-        x = (x * 0x85EBCA6Bu) & mask;
-        x ^= x >> s2;
-    }
-    return x;
-}
-__global__ void k_make_perm(unsigned long long key, long long n, int bits, long long* __restrict__ perm) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    unsigned int x = (unsigned int)i;
-    do { x = perm_mix(x, bits, key); } while ((long long)x >= n);
-    perm[i] = (long long)x;
 }
 
 // ---- update, step 0: gather + convert + both images of the observation rows ---------------------------------------------------
@@ -1550,118 +1528,6 @@ __global__ __launch_bounds__(256) void k_adam(float* __restrict__ theta, float* 
     }
 }
 
-// ---- the loss for int32 actions (cda_ppo.hip's k_ppo_loss, same arithmetic; the env's own action tensors) ----------------------
-template <int N>
-__device__ __forceinline__ void head_probs(const float* l, float* p, float* lp, float& ent) {
-    float mx = l[0];
-    #pragma unroll
-    for (int q = 1; q < N; q++) mx = fmaxf(mx, l[q]);
-    float s = 0.0f;
-    #pragma unroll
-    for (int q = 0; q < N; q++) { p[q] = __expf(l[q] - mx); s += p[q]; }
-    const float ls = __logf(s), inv = 1.0f / s;
-    float hh = 0.0f;
-    #pragma unroll
-    for (int q = 0; q < N; q++) { p[q] *= inv; lp[q] = l[q] - mx - ls; hh -= p[q] * lp[q]; }
-    ent = hh;
-}
-template <int N>
-__device__ __forceinline__ float pick(const float* v, int a) {
-    float r = v[0];
-    #pragma unroll
-    for (int q = 1; q < N; q++) r = (a == q || (q == N - 1 && a > q)) ? v[q] : r;
-    return r;
-}
-__global__ __launch_bounds__(256) void k_ppo_loss32(const float* __restrict__ outputs, const float* __restrict__ log_std,
-                                                    const int* __restrict__ a_cat, const int* __restrict__ a_price, const int* __restrict__ a_off,
-                                                    const float* __restrict__ a_cont, const float* __restrict__ logp_old, const float* __restrict__ adv,
-                                                    const float* __restrict__ ret, const long long* __restrict__ row_index, long long R, long long Rnorm, int agents,
-                                                    int stride, float clip, float vf_coef, float ent_coef, float* __restrict__ d_out, double* __restrict__ sums) {
-    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const float invB = 1.0f / ((float)Rnorm * (float)agents);
-    float pg = 0.0f, vl = 0.0f, en = 0.0f, dls0 = 0.0f, dls1 = 0.0f;
-    if (r < R) {
-        float l[N_LOGITS], d[N_LOGITS], p[N_CAT + N_PRICE + N_OFF], lp[N_CAT + N_PRICE + N_OFF];
-        const float4* lp4 = reinterpret_cast<const float4*>(outputs + r * stride);
-        #pragma unroll
-        for (int q = 0; q < N_LOGITS / 4; q++) { const float4 v = lp4[q]; l[4 * q] = v.x; l[4 * q + 1] = v.y; l[4 * q + 2] = v.z; l[4 * q + 3] = v.w; }
-        const float ls0 = log_std[0], ls1 = log_std[1];
-        const float is0 = __expf(-ls0), is1 = __expf(-ls1);
-        const float HALF_LOG_2PI = 0.918938533204672742f;
-        float h0, h1, h2;
-        head_probs<N_CAT>(l, p, lp, h0);
-        head_probs<N_PRICE>(l + N_CAT, p + N_CAT, lp + N_CAT, h1);
-        head_probs<N_OFF>(l + N_CAT + N_PRICE, p + N_CAT + N_PRICE, lp + N_CAT + N_PRICE, h2);
-        const float ent = h0 + h1 + h2 + 1.0f + 2.0f * HALF_LOG_2PI + ls0 + ls1;
-        const float es = ent_coef * invB;
-        #pragma unroll
-        for (int q = 0; q < N_LOGITS; q++) d[q] = 0.0f;
-        const float val = outputs[r * stride + N_LOGITS];
-        float G = 0.0f, dval = 0.0f;
-        const long long src_row = row_index ? row_index[r] : r;
-        for (int a = 0; a < agents; a++) {
-            const long long i = src_row * agents + a;
-            const int ac = a_cat[i], ap = a_price[i], ao = a_off[i];
-            const float z0 = (a_cont[2 * i] - l[22]) * is0, z1 = (a_cont[2 * i + 1] - l[23]) * is1;
-            const float logp = -0.5f * z0 * z0 - ls0 - HALF_LOG_2PI - 0.5f * z1 * z1 - ls1 - HALF_LOG_2PI +
-                               pick<N_CAT>(lp, ac) + pick<N_PRICE>(lp + N_CAT, ap) + pick<N_OFF>(lp + N_CAT + N_PRICE, ao);
-            const float Av = adv[i], ratio = __expf(logp - logp_old[i]);
-            const float un = ratio * Av, cl = fminf(fmaxf(ratio, 1.0f - clip), 1.0f + clip) * Av;
-            pg -= fminf(un, cl);
-            const float g_logp = (un <= cl) ? -un * invB : 0.0f;
-            const float dv = val - ret[i];
-            vl += dv * dv;
-            dval += 2.0f * vf_coef * dv * invB;
-            en += ent;
-            G += g_logp;
-            #pragma unroll
-            for (int q = 0; q < N_CAT; q++) d[q] += (q == ac) ? g_logp : 0.0f;
-            #pragma unroll
-            for (int q = 0; q < N_PRICE; q++) d[N_CAT + q] += (q == ap) ? g_logp : 0.0f;
-            #pragma unroll
-            for (int q = 0; q < N_OFF; q++) d[N_CAT + N_PRICE + q] += (q == ao) ? g_logp : 0.0f;
-            d[22] += g_logp * z0 * is0;
-            d[23] += g_logp * z1 * is1;
-            dls0 += g_logp * (z0 * z0 - 1.0f) - es;
-            dls1 += g_logp * (z1 * z1 - 1.0f) - es;
-        }
-        const float esA = es * (float)agents;
-        #pragma unroll
-        for (int q = 0; q < N_CAT; q++) d[q] += -G * p[q] + esA * p[q] * (lp[q] + h0);
-        #pragma unroll
-        for (int q = 0; q < N_PRICE; q++) d[N_CAT + q] += -G * p[N_CAT + q] + esA * p[N_CAT + q] * (lp[N_CAT + q] + h1);
-        #pragma unroll
-        for (int q = 0; q < N_OFF; q++) d[N_CAT + N_PRICE + q] += -G * p[N_CAT + N_PRICE + q] + esA * p[N_CAT + N_PRICE + q] * (lp[N_CAT + N_PRICE + q] + h2);
-        float4* dp4 = reinterpret_cast<float4*>(d_out + r * stride);
-        #pragma unroll
-        for (int q = 0; q < N_LOGITS / 4; q++) dp4[q] = make_float4(d[4 * q], d[4 * q + 1], d[4 * q + 2], d[4 * q + 3]);
-        dp4[N_LOGITS / 4] = make_float4(dval, 0.0f, 0.0f, 0.0f);
-        for (int q = N_LOGITS / 4 + 1; q < stride / 4; q++) dp4[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    }
-    float v5[5] = {pg, vl, en, dls0, dls1};
-    __shared__ float part[5][4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    #pragma unroll
-    for (int q = 0; q < 5; q++) {
-        float x = v5[q];
-        #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
-        if (lane == 0) part[q][wave] = x;
-    }
-    __syncthreads();
-    if (threadIdx.x < 5) {
-        const double t = (double)part[threadIdx.x][0] + (double)part[threadIdx.x][1] + (double)part[threadIdx.x][2] + (double)part[threadIdx.x][3];
-        atomicAdd(&sums[threadIdx.x], t);
-    }
-}
-__global__ void k_ppo_finish32(const double* sums, long long B, float vf_coef, float ent_coef, float* out) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        const double pg = sums[0] / (double)B, vl = sums[1] / (double)B, en = sums[2] / (double)B;
-        out[0] = (float)pg; out[1] = (float)vl; out[2] = (float)en; out[3] = (float)(pg + (double)vf_coef * vl - (double)ent_coef * en);
-        out[4] = (float)sums[3]; out[5] = (float)sums[4];
-    }
-}
-
 __global__ void k_ppo_finish_slots(const double* sums, long long B, float vf_coef, float ent_coef, float kl_coef, float* out) {      // the same over CDA_MLP_LOSS_SLOTS slots (out f32[8])
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         double t5[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
@@ -1673,228 +1539,6 @@ __global__ void k_ppo_finish_slots(const double* sums, long long B, float vf_coe
     }
 }
 
-// ---- the rollout's sample records: GAE straight into them, and the loss reading them -----------------------------------------------------
-// One thread per (market, agent) column walks its T steps backwards (ppo.gae's recursion) on the rollout's own buffers - reward f64 [T][N][A]
-// (scaled here), value f32 [T + 1][N] (slot T = the bootstrap value), terminated / truncated u8 [T][N] - and writes advantage and return into
-// words 6, 7 of the step's sample record.  The sums of the advantages and of their squares go to stats f64[2] (cleared by the caller): the
-// update normalises on the fly, (adv - mean) / (std + 1e-8) with the unbiased std, as ppo_update does with torch ops.
-// n_train > 0 (league self-play): slot p < n_train is played by trainable net p, whose values are value[p][T + 1][N] and whose sums go to stats[2 p ..];
-// the other slots' samples feed no update and are skipped.
-__global__ __launch_bounds__(256) void k_gae_records(const double* __restrict__ reward, const float* __restrict__ value, const unsigned char* __restrict__ term,
-                                                     const unsigned char* __restrict__ trunc, int T, long long N, int Ag, int n_train, float reward_scale, float gamma, float lam,
-                                                     const int* __restrict__ fin_index, const float* __restrict__ fin_value, long long fin_value_stride,
-                                                     float* __restrict__ rec, double* __restrict__ stats) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x, B = N * Ag;
-    double s1 = 0.0, s2 = 0.0;
-    const int slot = (int)(i % Ag);
-    if (i < B && (n_train <= 0 || slot < n_train)) {
-        const long long n = i / Ag;
-        if (n_train > 0) { value += (long long)slot * (T + 1) * N; fin_value += (long long)slot * fin_value_stride; }
-        float nxt = value[(long long)T * N + n], run = 0.0f;
-        // eight steps' operands requested together, then the recursion over them (one step at a time, every iteration paid a memory round trip:
-        // 39 us for 64 steps)
-        for (int t0 = T - 1; t0 >= 0; t0 -= 8) {
-            float rw[8], vv[8], nd[8], bv[8];
-            #pragma unroll
-            for (int u = 0; u < 8; u++) {
-                const int t = t0 - u >= 0 ? t0 - u : 0;
-                const long long k = (long long)t * B + i, kn = (long long)t * N + n;
-                const bool tm = term[kn] != 0, tr = trunc[kn] != 0;
-                rw[u] = (float)reward[k] * reward_scale; vv[u] = value[kn]; nd[u] = (tm | tr) ? 0.0f : 1.0f;
-                // a time-limit truncation (not a termination) whose last observation was captured: the step bootstraps with V(that observation) - the value
-                // of the state the episode was cut in - instead of 0; nothing propagates across the episode boundary either way (nd = 0)
-                bv[u] = 0.0f;
-                if (fin_index && tr && !tm) { const int fi = fin_index[kn]; if (fi >= 0) bv[u] = fin_value[fi]; }
-            }
-            #pragma unroll
-            for (int u = 0; u < 8; u++) {
-                const int t = t0 - u;
-                if (t >= 0) {
-                    const long long k = (long long)t * B + i;
-                    const float delta = rw[u] + gamma * (nxt * nd[u] + bv[u]) - vv[u];
-                    run = delta + gamma * lam * nd[u] * run;
-                    *reinterpret_cast<float2*>(rec + 8 * k + 6) = make_float2(run, run + vv[u]);
-                    s1 += (double)run; s2 += (double)run * (double)run;
-                    nxt = vv[u];
-                }
-            }
-        }
-    }
-    if (n_train > 0) {                                                          // per net: a wave reduction and two atomics per (wave, net)
-        for (int p = 0; p < n_train; p++) {
-            double a1 = slot == p ? s1 : 0.0, a2 = slot == p ? s2 : 0.0;
-            #pragma unroll
-            for (int o = 32; o > 0; o >>= 1) { a1 += __shfl_down(a1, o, 64); a2 += __shfl_down(a2, o, 64); }
-            if ((threadIdx.x & 63) == 0) { atomicAdd(&stats[2 * p], a1); atomicAdd(&stats[2 * p + 1], a2); }
-        }
-        return;
-    }
-    #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { s1 += __shfl_down(s1, o, 64); s2 += __shfl_down(s2, o, 64); }
-    __shared__ double part[2][4];
-    if ((threadIdx.x & 63) == 0) { part[0][threadIdx.x >> 6] = s1; part[1][threadIdx.x >> 6] = s2; }
-    __syncthreads();
-    if (threadIdx.x < 2) atomicAdd(&stats[threadIdx.x], (part[threadIdx.x][0] + part[threadIdx.x][1]) + (part[threadIdx.x][2] + part[threadIdx.x][3]));
-}
-// k_gae_records' recursion for ONE shared policy that plays slots 0 .. n_slots - 1 of every market only (the other slots are scripted opponents: their records are
-// no policy samples).  One thread per (market, slot < n_slots): the same operands in the same order as k_gae_records' n_train == 0 thread of that column, so words 6, 7
-// are bit-equal to what it writes there; the other slots' records are not touched and stats f64[2] (cleared by the caller) sums the T * N * n_slots trained samples.
-// A kernel of its own: k_gae_records stays the code object it was.
-__global__ __launch_bounds__(256) void k_gae_records_slots(const double* __restrict__ reward, const float* __restrict__ value, const unsigned char* __restrict__ term,
-                                                           const unsigned char* __restrict__ trunc, int T, long long N, int Ag, int n_slots, float reward_scale, float gamma, float lam,
-                                                           const int* __restrict__ fin_index, const float* __restrict__ fin_value, float* __restrict__ rec, double* __restrict__ stats) {
-    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x, B = N * Ag;
-    double s1 = 0.0, s2 = 0.0;
-    if (j < N * n_slots) {
-        const long long n = j / n_slots;
-        const long long i = n * Ag + (j - n * n_slots);                         // the column of rec / reward: (market n, slot j mod n_slots)
-        float nxt = value[(long long)T * N + n], run = 0.0f;
-        for (int t0 = T - 1; t0 >= 0; t0 -= 8) {                                // eight steps' operands requested together (k_gae_records)
-            float rw[8], vv[8], nd[8], bv[8];
-            #pragma unroll
-            for (int u = 0; u < 8; u++) {
-                const int t = t0 - u >= 0 ? t0 - u : 0;
-                const long long k = (long long)t * B + i, kn = (long long)t * N + n;
-                const bool tm = term[kn] != 0, tr = trunc[kn] != 0;
-                rw[u] = (float)reward[k] * reward_scale; vv[u] = value[kn]; nd[u] = (tm | tr) ? 0.0f : 1.0f;
-                bv[u] = 0.0f;
-                if (fin_index && tr && !tm) { const int fi = fin_index[kn]; if (fi >= 0) bv[u] = fin_value[fi]; }
-            }
-            #pragma unroll
-            for (int u = 0; u < 8; u++) {
-                const int t = t0 - u;
-                if (t >= 0) {
-                    const long long k = (long long)t * B + i;
-                    const float delta = rw[u] + gamma * (nxt * nd[u] + bv[u]) - vv[u];
-                    run = delta + gamma * lam * nd[u] * run;
-                    *reinterpret_cast<float2*>(rec + 8 * k + 6) = make_float2(run, run + vv[u]);
-                    s1 += (double)run; s2 += (double)run * (double)run;
-                    nxt = vv[u];
-                }
-            }
-        }
-    }
-    #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { s1 += __shfl_down(s1, o, 64); s2 += __shfl_down(s2, o, 64); }
-    __shared__ double part[2][4];
-    if ((threadIdx.x & 63) == 0) { part[0][threadIdx.x >> 6] = s1; part[1][threadIdx.x >> 6] = s2; }
-    __syncthreads();
-    if (threadIdx.x < 2) atomicAdd(&stats[threadIdx.x], (part[threadIdx.x][0] + part[threadIdx.x][1]) + (part[threadIdx.x][2] + part[threadIdx.x][3]));
-}
-// k_ppo_loss32 on sample records: a row's A samples are ONE contiguous piece of A x 32 bytes (the seven separate per-sample arrays cost seven
-// scattered 16-byte gathers per row: 1.3 KB fetched per row for 128 B used)
-__global__ __launch_bounds__(256) void k_ppo_loss_rec(const float* __restrict__ outputs, const float* __restrict__ log_std, const float* __restrict__ rec,
-                                                      const double* __restrict__ adv_stats, long long n_stat, const long long* __restrict__ row_index,
-                                                      long long R, long long Rnorm, int agents, int stride, float clip, float vf_coef, float ent_coef,
-                                                      float* __restrict__ d_out, double* __restrict__ sums) {
-    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const float invB = 1.0f / ((float)Rnorm * (float)agents);
-    float adv_mean = 0.0f, adv_rstd = 1.0f;
-    if (adv_stats) {
-        const double m = adv_stats[0] / (double)n_stat, var = (adv_stats[1] - (double)n_stat * m * m) / (double)(n_stat - 1);
-        adv_mean = (float)m; adv_rstd = 1.0f / ((float)sqrt(var > 0.0 ? var : 0.0) + 1e-8f);
-    }
-    float pg = 0.0f, vl = 0.0f, en = 0.0f, dls0 = 0.0f, dls1 = 0.0f;
-    if (r < R) {
-        float l[N_LOGITS], d[N_LOGITS], p[N_CAT + N_PRICE + N_OFF], lp[N_CAT + N_PRICE + N_OFF];
-        const float4* lp4 = reinterpret_cast<const float4*>(outputs + r * stride);
-        #pragma unroll
-        for (int q = 0; q < N_LOGITS / 4; q++) { const float4 v = lp4[q]; l[4 * q] = v.x; l[4 * q + 1] = v.y; l[4 * q + 2] = v.z; l[4 * q + 3] = v.w; }
-        const float ls0 = log_std[0], ls1 = log_std[1];
-        const float is0 = __expf(-ls0), is1 = __expf(-ls1);
-        const float HALF_LOG_2PI = 0.918938533204672742f;
-        float h0, h1, h2;
-        head_probs<N_CAT>(l, p, lp, h0);
-        head_probs<N_PRICE>(l + N_CAT, p + N_CAT, lp + N_CAT, h1);
-        head_probs<N_OFF>(l + N_CAT + N_PRICE, p + N_CAT + N_PRICE, lp + N_CAT + N_PRICE, h2);
-        const float ent = h0 + h1 + h2 + 1.0f + 2.0f * HALF_LOG_2PI + ls0 + ls1;
-        const float es = ent_coef * invB;
-        #pragma unroll
-        for (int q = 0; q < N_LOGITS; q++) d[q] = 0.0f;
-        const float val = outputs[r * stride + N_LOGITS];
-        float G = 0.0f, dval = 0.0f;
-        const long long src_row = row_index ? row_index[r] : r;
-        const float4* rp = reinterpret_cast<const float4*>(rec + src_row * agents * 8);
-        for (int a = 0; a < agents; a++) {
-            const float4 w0 = rp[2 * a], w1 = rp[2 * a + 1];
-            const int ac = __float_as_int(w0.x), ap = __float_as_int(w0.y), ao = __float_as_int(w0.z);
-            const float z0 = (w0.w - l[22]) * is0, z1 = (w1.x - l[23]) * is1;
-            const float logp = -0.5f * z0 * z0 - ls0 - HALF_LOG_2PI - 0.5f * z1 * z1 - ls1 - HALF_LOG_2PI +
-                               pick<N_CAT>(lp, ac) + pick<N_PRICE>(lp + N_CAT, ap) + pick<N_OFF>(lp + N_CAT + N_PRICE, ao);
-            const float Av = (w1.z - adv_mean) * adv_rstd, ratio = __expf(logp - w1.y);
-            const float un = ratio * Av, cl = fminf(fmaxf(ratio, 1.0f - clip), 1.0f + clip) * Av;
-            pg -= fminf(un, cl);
-            const float g_logp = (un <= cl) ? -un * invB : 0.0f;
-            const float dv = val - w1.w;
-            vl += dv * dv;
-            dval += 2.0f * vf_coef * dv * invB;
-            en += ent;
-            G += g_logp;
-            #pragma unroll
-            for (int q = 0; q < N_CAT; q++) d[q] += (q == ac) ? g_logp : 0.0f;
-            #pragma unroll
-            for (int q = 0; q < N_PRICE; q++) d[N_CAT + q] += (q == ap) ? g_logp : 0.0f;
-            #pragma unroll
-            for (int q = 0; q < N_OFF; q++) d[N_CAT + N_PRICE + q] += (q == ao) ? g_logp : 0.0f;
-            d[22] += g_logp * z0 * is0;
-            d[23] += g_logp * z1 * is1;
-            dls0 += g_logp * (z0 * z0 - 1.0f) - es;
-            dls1 += g_logp * (z1 * z1 - 1.0f) - es;
-        }
-        const float esA = es * (float)agents;
-        #pragma unroll
-        for (int q = 0; q < N_CAT; q++) d[q] += -G * p[q] + esA * p[q] * (lp[q] + h0);
-        #pragma unroll
-        for (int q = 0; q < N_PRICE; q++) d[N_CAT + q] += -G * p[N_CAT + q] + esA * p[N_CAT + q] * (lp[N_CAT + q] + h1);
-        #pragma unroll
-        for (int q = 0; q < N_OFF; q++) d[N_CAT + N_PRICE + q] += -G * p[N_CAT + N_PRICE + q] + esA * p[N_CAT + N_PRICE + q] * (lp[N_CAT + N_PRICE + q] + h2);
-        float4* dp4 = reinterpret_cast<float4*>(d_out + r * stride);
-        #pragma unroll
-        for (int q = 0; q < N_LOGITS / 4; q++) dp4[q] = make_float4(d[4 * q], d[4 * q + 1], d[4 * q + 2], d[4 * q + 3]);
-        dp4[N_LOGITS / 4] = make_float4(dval, 0.0f, 0.0f, 0.0f);
-        for (int q = N_LOGITS / 4 + 1; q < stride / 4; q++) dp4[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    }
-    float v5[5] = {pg, vl, en, dls0, dls1};
-    __shared__ float part[5][4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    #pragma unroll
-    for (int q = 0; q < 5; q++) {
-        float x = v5[q];
-        #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
-        if (lane == 0) part[q][wave] = x;
-    }
-    __syncthreads();
-    if (threadIdx.x < 5) {
-        const double t = (double)part[threadIdx.x][0] + (double)part[threadIdx.x][1] + (double)part[threadIdx.x][2] + (double)part[threadIdx.x][3];
-        atomicAdd(&sums[threadIdx.x], t);
-    }
-}
-
-// Returns of COMPLETED episodes from a rollout's buffers: running f64 [N][A] carries every (market, agent)'s return so far across rollouts; a step that ends
-// the market's episode adds the agent's total to done_sum f64 [A] (and 1 to done_count f64 [A]) and restarts it.  One thread per (market, agent), forwards in time.
-__global__ __launch_bounds__(256) void k_episode_returns(const double* __restrict__ reward, const unsigned char* __restrict__ term, const unsigned char* __restrict__ trunc,
-                                                         int T, long long N, int Ag, double* __restrict__ running, double* __restrict__ done_sum, double* __restrict__ done_count,
-                                                         double* __restrict__ per_slot) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x, B = N * Ag;
-    if (i >= B) return;
-    const long long n = i / Ag; const int a = (int)(i - n * Ag);
-    double run = running[i], s = 0.0, c = 0.0;
-    for (int t0 = 0; t0 < T; t0 += 8) {                                         // eight steps' operands requested together (one step at a time: a round trip per step, 72 us for 64)
-        double rw[8]; bool dn[8];
-        #pragma unroll
-        for (int u = 0; u < 8; u++) {
-            const int t = t0 + u < T ? t0 + u : T - 1;
-            rw[u] = reward[(long long)t * B + i]; dn[u] = (term[(long long)t * N + n] | trunc[(long long)t * N + n]) != 0;
-        }
-        #pragma unroll
-        for (int u = 0; u < 8; u++)
-            if (t0 + u < T) { run += rw[u]; if (dn[u]) { s += run; c += 1.0; run = 0.0; } }
-    }
-    running[i] = run;
-    if (c > 0.0) { atomicAdd(&done_sum[a], s); atomicAdd(&done_count[a], c); }
-    if (per_slot) { per_slot[2 * i] = s; per_slot[2 * i + 1] = c; }              // this rollout's completed episodes of (market, agent): sum of returns, number
-}
 __global__ void k_copy_rows(const float* __restrict__ src, float* __restrict__ dst, long long n4) {         // n4 pieces of VW floats
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n4) reinterpret_cast<obsvec*>(dst)[i] = reinterpret_cast<const obsvec*>(src)[i];
@@ -2039,14 +1683,6 @@ extern "C" int cda_mlp_forward(const void* wb, const float* theta, const float* 
     return launch_fwd<MODE_OUT>(A, n_rows >= 32768 ? 4 : rollout_mt(), (hipStream_t)stream);
 }
 
-extern "C" int cda_mlp_permutation(uint64_t key, int64_t n, int64_t* perm, void* stream) {
-    if (!perm || n < 1 || n > ((int64_t)1 << 31)) return CDA_ERR_INVALID;
-    int bits = 1;
-    while (((int64_t)1 << bits) < n) bits++;
-    hipLaunchKernelGGL(k_make_perm, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (unsigned long long)key, (long long)n, bits, (long long*)perm);
-    return hipGetLastError() == hipSuccess ? CDA_OK : CDA_ERR_HIP;
-}
-
 extern "C" int cda_mlp_prep_rows(const float* obs, const int64_t* perm, int64_t n_rows, void* x_rm, void* x_pk, void* stream) {
     if (!obs || !x_rm || !x_pk || n_rows < 32 || (n_rows & 31)) return CDA_ERR_INVALID;
     hipLaunchKernelGGL(k_prep_rows, dim3((unsigned)(n_rows / 32)), dim3(256), 0, (hipStream_t)stream, obs, (const long long*)perm, (long long)n_rows, (__bf16*)x_rm, (__bf16*)x_pk);
@@ -2188,87 +1824,6 @@ extern "C" int cda_mlp_adam(float* theta, float* adam_m, float* adam_v, float* s
     return hipGetLastError() == hipSuccess ? CDA_OK : CDA_ERR_HIP;
 }
 
-extern "C" int cda_ppo_loss32(const float* outputs, const float* log_std, const int32_t* a_cat, const int32_t* a_price, const int32_t* a_off,
-                              const float* a_cont, const float* logp_old, const float* adv, const float* ret, const int64_t* row_index,
-                              int64_t rows, int32_t agents_per_row, int32_t out_stride, float clip, float vf_coef, float ent_coef,
-                              float* d_outputs, double* sums5, float* out6, int64_t norm_rows, int32_t clear, int32_t finish, void* stream) {
-    if (!outputs || !log_std || !a_cat || !a_price || !a_off || !a_cont || !logp_old || !adv || !ret || !d_outputs || !sums5 || !out6 || rows < 1 ||
-        agents_per_row < 1 || agents_per_row > CDA_MAX_AGENTS || out_stride <= N_LOGITS || (out_stride & 3) || norm_rows < 0) return CDA_ERR_INVALID;
-    hipStream_t st = (hipStream_t)stream;
-    const long long rn = norm_rows > 0 ? norm_rows : rows;
-    if (clear && hipMemsetAsync(sums5, 0, 5 * sizeof(double), st) != hipSuccess) return CDA_ERR_HIP;
-    hipLaunchKernelGGL(k_ppo_loss32, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, outputs, log_std, a_cat, a_price, a_off, a_cont, logp_old, adv, ret,
-                       (const long long*)row_index, (long long)rows, rn, (int)agents_per_row, (int)out_stride, clip, vf_coef, ent_coef, d_outputs, sums5);
-    if (finish) hipLaunchKernelGGL(k_ppo_finish32, dim3(1), dim3(64), 0, st, (const double*)sums5, rn * agents_per_row, vf_coef, ent_coef, out6);
-    return hipGetLastError() == hipSuccess ? CDA_OK : CDA_ERR_HIP;
-}
-
-static int gae_records(const double* reward, const float* value, const uint8_t* terminated, const uint8_t* truncated, int32_t n_steps, int64_t n_markets,
-                       int32_t num_agents, int32_t n_train, float reward_scale, float gamma, float lam, float* rec, double* stats, void* stream,
-                       const int32_t* fin_index = NULL, const float* fin_value = NULL, int64_t fin_value_stride = 0) {
-    if (!reward || !value || !terminated || !truncated || !rec || !stats || n_steps < 1 || n_markets < 1 || num_agents < 1 || num_agents > CDA_MAX_AGENTS ||
-        n_train < 0 || n_train > num_agents || (fin_index && !fin_value)) return CDA_ERR_INVALID;
-    hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(stats, 0, 2 * sizeof(double) * (n_train > 0 ? n_train : 1), st) != hipSuccess) return CDA_ERR_HIP;
-    const long long B = (long long)n_markets * num_agents;
-    hipLaunchKernelGGL(k_gae_records, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, reward, value, (const unsigned char*)terminated, (const unsigned char*)truncated,
-                       (int)n_steps, (long long)n_markets, (int)num_agents, (int)n_train, reward_scale, gamma, lam, (const int*)fin_index, fin_value, (long long)fin_value_stride, rec, stats);
-    return hipGetLastError() == hipSuccess ? CDA_OK : CDA_ERR_HIP;
-}
-extern "C" int cda_gae_records(const double* reward, const float* value, const uint8_t* terminated, const uint8_t* truncated, int32_t n_steps, int64_t n_markets,
-                               int32_t num_agents, float reward_scale, float gamma, float lam, float* rec, double* stats2, void* stream) {
-    return gae_records(reward, value, terminated, truncated, n_steps, n_markets, num_agents, 0, reward_scale, gamma, lam, rec, stats2, stream);
-}
-// ... with the time-limit bootstrap: fin_index i32 [T][N] (slot of the step's captured last observation, -1 = none), fin_value f32 [max(n_trainable, 1)][fin_value_stride]
-// (cda_mlp_values on the captured list).  n_trainable = 0: one shared policy (cda_gae_records' layout), > 0: the league's (cda_gae_records_league's).
-extern "C" int cda_gae_records_bootstrap(const double* reward, const float* value, const uint8_t* terminated, const uint8_t* truncated, int32_t n_steps, int64_t n_markets,
-                                         int32_t num_agents, int32_t n_trainable, float reward_scale, float gamma, float lam,
-                                         const int32_t* fin_index, const float* fin_value, int64_t fin_value_stride, float* rec, double* stats, void* stream) {
-    return gae_records(reward, value, terminated, truncated, n_steps, n_markets, num_agents, n_trainable, reward_scale, gamma, lam, rec, stats, stream, fin_index, fin_value, fin_value_stride);
-}
-// ... for one shared policy on slots 0 .. n_slots - 1 of every market (the other slots: scripted opponents): cda_gae_records_bootstrap(n_trainable = 0)'s recursion over
-// those slots only (k_gae_records_slots); fin_index / fin_value may be NULL (no time-limit bootstrap), fin_value is the shared policy's one row.
-extern "C" int cda_gae_records_slots(const double* reward, const float* value, const uint8_t* terminated, const uint8_t* truncated, int32_t n_steps, int64_t n_markets,
-                                     int32_t num_agents, int32_t n_slots, float reward_scale, float gamma, float lam,
-                                     const int32_t* fin_index, const float* fin_value, float* rec, double* stats2, void* stream) {
-    if (!reward || !value || !terminated || !truncated || !rec || !stats2 || n_steps < 1 || n_markets < 1 || num_agents < 1 || num_agents > CDA_MAX_AGENTS ||
-        n_slots < 1 || n_slots > num_agents || (fin_index && !fin_value) || ((uintptr_t)rec & 7) != 0) return CDA_ERR_INVALID;
-    hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(stats2, 0, 2 * sizeof(double), st) != hipSuccess) return CDA_ERR_HIP;
-    const long long B = (long long)n_markets * n_slots;
-    hipLaunchKernelGGL(k_gae_records_slots, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, reward, value, (const unsigned char*)terminated, (const unsigned char*)truncated,
-                       (int)n_steps, (long long)n_markets, (int)num_agents, (int)n_slots, reward_scale, gamma, lam, (const int*)fin_index, fin_value, rec, stats2);
-    return hipGetLastError() == hipSuccess ? CDA_OK : CDA_ERR_HIP;
-}
-extern "C" int cda_gae_records_league(const double* reward,const float* value, const uint8_t* terminated, const uint8_t* truncated, int32_t n_steps, int64_t n_markets,
-                                      int32_t num_agents, int32_t n_trainable, float reward_scale, float gamma, float lam, float* rec, double* stats2k, void* stream) {
-    if (n_trainable < 1) return CDA_ERR_INVALID;
-    return gae_records(reward, value, terminated, truncated, n_steps, n_markets, num_agents, n_trainable, reward_scale, gamma, lam, rec, stats2k, stream);
-}
-
-extern "C" int cda_episode_returns(const double* reward, const uint8_t* terminated, const uint8_t* truncated, int32_t n_steps, int64_t n_markets, int32_t num_agents,
-                                   double* running, double* done_sum, double* done_count, double* per_slot, void* stream) {
-    if (!reward || !terminated || !truncated || !running || !done_sum || !done_count || n_steps < 1 || n_markets < 1 || num_agents < 1 || num_agents > CDA_MAX_AGENTS) return CDA_ERR_INVALID;
-    const long long B = (long long)n_markets * num_agents;
-    hipLaunchKernelGGL(k_episode_returns, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, (hipStream_t)stream, reward, (const unsigned char*)terminated, (const unsigned char*)truncated,
-                       (int)n_steps, (long long)n_markets, (int)num_agents, running, done_sum, done_count, per_slot);
-    return hipGetLastError() == hipSuccess ? CDA_OK : CDA_ERR_HIP;
-}
-
-extern "C" int cda_ppo_loss_records(const float* outputs, const float* log_std, const float* rec, const double* adv_stats2, int64_t adv_count, const int64_t* row_index,
-                                    int64_t rows, int32_t agents_per_row, int32_t out_stride, float clip, float vf_coef, float ent_coef,
-                                    float* d_outputs, double* sums5, float* out6, int64_t norm_rows, int32_t clear, int32_t finish, void* stream) {
-    if (!outputs || !log_std || !rec || !d_outputs || !sums5 || !out6 || rows < 1 || agents_per_row < 1 || agents_per_row > CDA_MAX_AGENTS ||
-        out_stride <= N_LOGITS || (out_stride & 3) || norm_rows < 0 || (adv_stats2 && adv_count < 2)) return CDA_ERR_INVALID;
-    hipStream_t st = (hipStream_t)stream;
-    const long long rn = norm_rows > 0 ? norm_rows : rows;
-    if (clear && hipMemsetAsync(sums5, 0, 5 * sizeof(double), st) != hipSuccess) return CDA_ERR_HIP;
-    hipLaunchKernelGGL(k_ppo_loss_rec, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, outputs, log_std, rec, adv_stats2, (long long)adv_count,
-                       (const long long*)row_index, (long long)rows, rn, (int)agents_per_row, (int)out_stride, clip, vf_coef, ent_coef, d_outputs, sums5);
-    if (finish) hipLaunchKernelGGL(k_ppo_finish32, dim3(1), dim3(64), 0, st, (const double*)sums5, rn * agents_per_row, vf_coef, ent_coef, out6);
-    return hipGetLastError() == hipSuccess ? CDA_OK : CDA_ERR_HIP;
-}
-
 template <int MODE>
 static int league_step(const cda_league* L, const float* obs, int32_t first_market, int32_t n_markets, int32_t num_agents,
                        uint64_t seed, const int64_t* counter_dev, int64_t draw,
@@ -2300,89 +1855,6 @@ extern "C" int cda_mlp_league_act(const cda_league* L, const float* obs, int32_t
                                   float* a_cont, float* logp, float* value, int64_t value_stride, float* rec, float* dist, int64_t dist_stride, void* stream) {
     return league_step<MODE_LEAGUE_GREEDY>(L, obs, first_market, n_markets, num_agents, seed, counter_dev, draw, env_category, env_size_mean, env_size_sigma, env_price,
                                            env_price_offset, a_cont, logp, value, value_stride, rec, dist, dist_stride, stream);
-}
-
-// The reference's agent-to-module mapping (train/callbk/league_based_self_play_callback.py:1286-1344) for every (market, pool slot) at once: slot s >= n_trainable
-// of a market draws np.random.RandomState((crc32(str(episode id)) + s) mod 2^32).choice(pool, p) - ONE random_sample() of a freshly seeded MT19937: the
-// init_genrand recurrence up to word 398, the twist + tempering of outputs 0 and 1, a 53-bit double, searchsorted(cdf, u, side = "right").  A thread per
-// (market, slot): 400 dependent integer steps (the host-side numpy restatement, league.mt19937_first_double, walks the same recurrence over all seeds at
-// once: tens of milliseconds at 2048 x 6 - longer than the episode it assigns).
-namespace { __global__ __launch_bounds__(256) void k_league_assign(const unsigned int* __restrict__ episode_crc, int N, int Ag, int n_train, const double* __restrict__ cdf,
-                                                       const int* __restrict__ pool_net, int P, int* __restrict__ slot_net, int* __restrict__ slot_pool) {
-    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (i >= N * Ag) return;
-    const int n = i / Ag, s = i - n * Ag;
-    if (s < n_train) { slot_net[i] = s; if (slot_pool) slot_pool[i] = -1; return; }
-    unsigned int x = episode_crc[n] + (unsigned int)s;                          // (crc + slot) mod 2^32
-    unsigned int m0 = x, m1 = 0, m2 = 0, m397 = 0, m398 = 0;
-    for (unsigned int k = 1; k <= 398; k++) {
-        x = 1812433253u * (x ^ (x >> 30)) + k;
-        if (k == 1) m1 = x; else if (k == 2) m2 = x; else if (k == 397) m397 = x; else if (k == 398) m398 = x;
-    }
-    auto word = [](unsigned int a, unsigned int b, unsigned int c) {             // output k: twist of (mt[k], mt[k + 1], mt[k + 397]), tempered
-        const unsigned int y = (a & 0x80000000u) | (b & 0x7fffffffu);
-        unsigned int v = c ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
-        v ^= v >> 11; v ^= (v << 7) & 0x9d2c5680u; v ^= (v << 15) & 0xefc60000u; v ^= v >> 18;
-        return v;
-    };
-    const unsigned int w0 = word(m0, m1, m397) >> 5, w1 = word(m1, m2, m398) >> 6;
-    const double u = ((double)w0 * 67108864.0 + (double)w1) / 9007199254740992.0;
-    int idx = 0;
-    for (int q = 0; q < P; q++) idx += cdf[q] <= u ? 1 : 0;                      // searchsorted(..., side = "right")
-    if (idx >= P) idx = P - 1;
-    slot_net[i] = pool_net[idx];
-    if (slot_pool) slot_pool[i] = idx;
-} }
-extern "C" int cda_league_assign(const uint32_t* episode_crc, int32_t n_markets, int32_t num_agents, int32_t n_trainable, const double* pool_cdf, const int32_t* pool_net,
-                                 int32_t pool_size, int32_t* slot_net, int32_t* slot_pool, void* stream) {
-    if (!episode_crc || !pool_cdf || !pool_net || !slot_net || n_markets < 1 || num_agents < 1 || num_agents > CDA_MAX_AGENTS || n_trainable < 0 || n_trainable > num_agents ||
-        pool_size < 1) return CDA_ERR_INVALID;
-    const int n = n_markets * num_agents;
-    hipLaunchKernelGGL(k_league_assign, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const unsigned int*)episode_crc, (int)n_markets, (int)num_agents,
-                       (int)n_trainable, pool_cdf, (const int*)pool_net, (int)pool_size, (int*)slot_net, (int*)slot_pool);
-    return hipGetLastError() == hipSuccess ? CDA_OK : CDA_ERR_HIP;
-}
-
-// k_league_assign with scripted modules in the pool: the same draw, bit for bit (the same freshly seeded MT19937's first double, the same searchsorted on the - longer -
-// cdf), and one more table, pool_script i32 [P]: 0, or 1 + the profile a scripted pool entry plays.  slot_script i32 [N][A] (the env's resident table: k_script_actions
-// reads it at the next step) receives pool_script[draw], 0 in the trainable slots; a scripted entry's pool_net is CDA_LEAGUE_RANDOM (validated by the launcher's caller:
-// the random module's action is what the scripted launch overwrites).  A kernel of its own: k_league_assign stays the code object it was.
-namespace { __global__ __launch_bounds__(256) void k_league_assign_scripted(const unsigned int* __restrict__ episode_crc, int N, int Ag, int n_train, const double* __restrict__ cdf,
-                                                                const int* __restrict__ pool_net, const int* __restrict__ pool_script, int P, int* __restrict__ slot_net,
-                                                                int* __restrict__ slot_script, int* __restrict__ slot_pool) {
-    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (i >= N * Ag) return;
-    const int n = i / Ag, s = i - n * Ag;
-    if (s < n_train) { slot_net[i] = s; slot_script[i] = 0; if (slot_pool) slot_pool[i] = -1; return; }
-    unsigned int x = episode_crc[n] + (unsigned int)s;                          // (crc + slot) mod 2^32
-    unsigned int m0 = x, m1 = 0, m2 = 0, m397 = 0, m398 = 0;
-    for (unsigned int k = 1; k <= 398; k++) {
-        x = 1812433253u * (x ^ (x >> 30)) + k;
-        if (k == 1) m1 = x; else if (k == 2) m2 = x; else if (k == 397) m397 = x; else if (k == 398) m398 = x;
-    }
-    auto word = [](unsigned int a, unsigned int b, unsigned int c) {             // output k: twist of (mt[k], mt[k + 1], mt[k + 397]), tempered
-        const unsigned int y = (a & 0x80000000u) | (b & 0x7fffffffu);
-        unsigned int v = c ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
-        v ^= v >> 11; v ^= (v << 7) & 0x9d2c5680u; v ^= (v << 15) & 0xefc60000u; v ^= v >> 18;
-        return v;
-    };
-    const unsigned int w0 = word(m0, m1, m397) >> 5, w1 = word(m1, m2, m398) >> 6;
-    const double u = ((double)w0 * 67108864.0 + (double)w1) / 9007199254740992.0;
-    int idx = 0;
-    for (int q = 0; q < P; q++) idx += cdf[q] <= u ? 1 : 0;                      // searchsorted(..., side = "right")
-    if (idx >= P) idx = P - 1;
-    slot_net[i] = pool_net[idx];
-    slot_script[i] = pool_script[idx];
-    if (slot_pool) slot_pool[i] = idx;
-} }
-extern "C" int cda_league_assign_scripted(const uint32_t* episode_crc, int32_t n_markets, int32_t num_agents, int32_t n_trainable, const double* pool_cdf, const int32_t* pool_net,
-                                          const int32_t* pool_script, int32_t pool_size, int32_t* slot_net, int32_t* slot_script, int32_t* slot_pool, void* stream) {
-    if (!episode_crc || !pool_cdf || !pool_net || !pool_script || !slot_net || !slot_script || n_markets < 1 || num_agents < 1 || num_agents > CDA_MAX_AGENTS ||
-        n_trainable < 0 || n_trainable > num_agents || pool_size < 1) return CDA_ERR_INVALID;
-    const int n = n_markets * num_agents;
-    hipLaunchKernelGGL(k_league_assign_scripted, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const unsigned int*)episode_crc, (int)n_markets,
-                       (int)num_agents, (int)n_trainable, pool_cdf, (const int*)pool_net, (const int*)pool_script, (int)pool_size, (int*)slot_net, (int*)slot_script, (int*)slot_pool);
-    return hipGetLastError() == hipSuccess ? CDA_OK : CDA_ERR_HIP;
 }
 
 #ifndef CDA_MLP_TIMING          /* (the tools build holds the network kernels only, not the env) */

@@ -37,7 +37,7 @@ __device__ __forceinline__ void obs_spread(float* dst, const float2& v) { dst[0]
 constexpr int ACT_LD = HID + 8;      // LDS row of an activation tile: 264 bf16 = 528 B = 16 x 33
 constexpr int DO_LD = NOUT + 8;      // LDS row of the d_out tile: 40 bf16 = 80 B = 16 x 5
 constexpr int OUTS_LD = NOUT + 1;    // f32 row of the output tile kept in LDS for the sampling epilogue
-constexpr int N_CAT = 9, N_PRICE = 10, N_OFF = 3, N_LOGITS = 24;
+constexpr int N_CAT = CDA_HEAD_CATEGORY, N_PRICE = CDA_HEAD_PRICE, N_OFF = CDA_HEAD_OFFSET, N_LOGITS = CDA_HEAD_LOGITS;      // 9, 10, 3, 24 (include/cda_learner.h)
 constexpr int LPS_LD = N_CAT + N_PRICE + N_OFF + 1;   // 23 floats: odd, conflict free
 
 __device__ __forceinline__ int rowmap(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }

@@ -5,8 +5,8 @@
  * the reference's n_hist; tanh) defines the entry points of include/cda_mlp.h under their own names; a build with -DCDA_MLP_HIST=<H> and / or -DCDA_MLP_ACT=<a>
  * renames every one of them to <name>[_h<H>][_<act>] (cda_mlp_forward_relu, cda_mlp_forward_h6_elu) BEFORE the header is read, so declarations and definitions
  * agree and the objects link into one library (__graft_entry__.build_hip compiles CDA_MLP_HIST_VARIANTS x CDA_MLP_ACT_VARIANTS).  Entry points that depend on
- * neither (GAE, episode returns, league assignment) are renamed too: a few duplicate kilobytes instead of a second source file.  Generated list: keep in step with
- * include/cda_mlp.h (tests/test_capi_load.py checks it).
+ * neither (the permutation, the unfused loss, GAE, episode returns, league assignment) are not here: include/cda_learner.h declares them, csrc/cda_learner.hip is
+ * compiled once and they are never renamed.  Generated list: EVERY function include/cda_mlp.h itself declares, and nothing else (tests/test_capi_load.py checks it).
  * -DCDA_MLP_VFS=1 builds the shared-trunk network (RLlib's vf_share_layers: the value head reads the policy half, the value half is dead) and appends _vfs behind
  * the other suffixes: <name>[_h<H>][_<act>]_vfs (cda_mlp_forward_vfs, cda_mlp_forward_backward_h6_elu_vfs). */
 #ifndef CDA_MLP_VARIANT_H
@@ -50,7 +50,6 @@
 #define cda_mlp_policy_step CDA_MLP_SFX(cda_mlp_policy_step)
 #define cda_mlp_policy_act CDA_MLP_SFX(cda_mlp_policy_act)
 #define cda_mlp_forward CDA_MLP_SFX(cda_mlp_forward)
-#define cda_mlp_permutation CDA_MLP_SFX(cda_mlp_permutation)
 #define cda_mlp_prep_rows CDA_MLP_SFX(cda_mlp_prep_rows)
 #define cda_mlp_forward_train CDA_MLP_SFX(cda_mlp_forward_train)
 #define cda_mlp_backward CDA_MLP_SFX(cda_mlp_backward)
@@ -58,24 +57,15 @@
 #define cda_mlp_adam CDA_MLP_SFX(cda_mlp_adam)
 #define cda_mlp_reduce CDA_MLP_SFX(cda_mlp_reduce)
 #define cda_mlp_apply CDA_MLP_SFX(cda_mlp_apply)
-#define cda_ppo_loss32 CDA_MLP_SFX(cda_ppo_loss32)
 #define cda_mlp_rollout_chain CDA_MLP_SFX(cda_mlp_rollout_chain)
-#define cda_gae_records CDA_MLP_SFX(cda_gae_records)
-#define cda_gae_records_bootstrap CDA_MLP_SFX(cda_gae_records_bootstrap)
-#define cda_gae_records_slots CDA_MLP_SFX(cda_gae_records_slots)
 #define cda_mlp_values CDA_MLP_SFX(cda_mlp_values)
 #define cda_mlp_values_counted CDA_MLP_SFX(cda_mlp_values_counted)
-#define cda_episode_returns CDA_MLP_SFX(cda_episode_returns)
-#define cda_ppo_loss_records CDA_MLP_SFX(cda_ppo_loss_records)
 #define cda_mlp_forward_backward CDA_MLP_SFX(cda_mlp_forward_backward)
 #define cda_mlp_league_step CDA_MLP_SFX(cda_mlp_league_step)
 #define cda_mlp_league_rollout_chain CDA_MLP_SFX(cda_mlp_league_rollout_chain)
 #define cda_mlp_league_act CDA_MLP_SFX(cda_mlp_league_act)
 #define cda_mlp_eval_chain CDA_MLP_SFX(cda_mlp_eval_chain)
 #define cda_mlp_league_eval_chain CDA_MLP_SFX(cda_mlp_league_eval_chain)
-#define cda_gae_records_league CDA_MLP_SFX(cda_gae_records_league)
-#define cda_league_assign CDA_MLP_SFX(cda_league_assign)
-#define cda_league_assign_scripted CDA_MLP_SFX(cda_league_assign_scripted)
 #define cda_mlp_selftest_mfma CDA_MLP_SFX(cda_mlp_selftest_mfma)
 #endif
 #endif

@@ -17,7 +17,7 @@ Module ids and prefixes follow config/tunable_constants.json -> module_id_prefix
 
 Scripted modules (scripted.py: rule-based agents on the device) join the pool through `add_scripted` as `scripted_<i>_<law>`: to the rule above they are
 "otherwise" modules (weight `scripted_weight`, default 1.0), so `assign()` covers them as it stands; `assign_device` then also writes the env's scripted slot
-table (include/cda_mlp.h cda_league_assign_scripted).
+table (include/cda_learner.h cda_league_assign_scripted).
 """
 import zlib
 
@@ -143,7 +143,7 @@ class LeagueSlotMapper:
         return np.array([zlib.crc32(str(e).encode("utf-8")) for e in episode_ids], dtype=np.uint32)
 
     def assign_device(self, bank, episode_ids=None, crcs=None, net_of=None, slot_pool=None, slot_script=None):
-        """assign() on the device (include/cda_mlp.h cda_league_assign), straight into `bank.slot_net` (mlp.PolicyBank): no host sync, one launch.
+        """assign() on the device (include/cda_learner.h cda_league_assign), straight into `bank.slot_net` (mlp.PolicyBank): no host sync, one launch.
         net_of: {module id: bank row} for the pool's network modules (champions); modules not named there play the uniform random law
         (the reference's fixed opponents are RandomRLModules, train/model/model_handler.py:38-53).  slot_pool (optional i32 [N, A] device tensor)
         receives the draw itself: available_modules[num_trainable + slot_pool] is the module's id (-1: the slot's own trainable policy).

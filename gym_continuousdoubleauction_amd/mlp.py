@@ -75,7 +75,10 @@ class Layout:
         self.suffix = ("" if h == 4 else f"_h{h}") + ("" if act == "tanh" else f"_{act}") + ("_vfs" if vfs else "")
 
     def fn(self, name):
-        return getattr(_lib(), name + self.suffix)
+        """the entry point `name` for this layout: the network's (include/cda_mlp.h) carry the suffix, the learner-side ones (include/cda_learner.h: permutation,
+        unfused loss, GAE, episode returns, league assignment) exist once and serve every layout"""
+        from ._lib import LEARNER_SYMBOLS
+        return getattr(_lib(), name if name in LEARNER_SYMBOLS else name + self.suffix)
 
 
 _LAYOUTS = {}
@@ -822,7 +825,8 @@ class EpisodeReturns:
 
 
 class _Fns:
-    """attribute access -> the entry point compiled for a layout's history depth (`_Fns(L).cda_mlp_wgrad` = the library's cda_mlp_wgrad[_h<H>])"""
+    """attribute access -> Layout.fn: the entry point compiled for a layout (`_Fns(L).cda_mlp_wgrad` = the library's cda_mlp_wgrad[_h<H>][_<act>][_vfs];
+    `_Fns(L).cda_ppo_loss32` = the one cda_ppo_loss32)"""
 
     def __init__(self, L):
         self._L = L

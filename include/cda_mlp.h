@@ -84,6 +84,10 @@ extern "C" {
 #define CDA_MLP_BSLAB     1056
 #define CDA_MLP_SCRATCH   512                    /* f64 words of cda_mlp_adam's scratch */
 
+/* The learner-side entry points that depend on none of the above - cda_mlp_permutation, cda_ppo_loss32 / cda_ppo_loss_records, cda_gae_records*, cda_episode_returns,
+ * cda_league_assign* - and the sample records' words (CDA_REC_*): ONE copy each in the library, never suffixed. */
+#include "cda_learner.h"
+
 /* rows per workgroup of the update's forward / backward kernels (32, 64 or 128: CDA_MLP_MT in the environment, default 128) = rows per
  * bias partial of cda_mlp_backward */
 int32_t cda_mlp_tile_rows(void);
@@ -119,10 +123,6 @@ int cda_mlp_policy_act(const void* wb, const float* theta, const float* obs, int
                        float* a_cont, float* logp, float* value, void* stream);
 /* The network outputs alone for rows [first_row, first_row + n_rows) of obs f32[*,168] -> out f32[*,32] (same row indexing). */
 int cda_mlp_forward(const void* wb, const float* theta, const float* obs, int64_t first_row, int64_t n_rows, float* out, void* stream);
-
-/* An epoch's shuffle: perm i64[n] = a pseudo-random PERMUTATION of 0 .. n-1 determined by `key` (a keyed bijective mixer + cycle walking, one
- * launch; the sort behind torch.randperm is ~10 launches). */
-int cda_mlp_permutation(uint64_t key, int64_t n, int64_t* perm, void* stream);
 
 /* Update, step 0: rows of obs f32[*,168] selected by perm i64[n_rows] (NULL = identity) -> x_rm bf16[n_rows][176] (row-major, zero
  * padded) and x_pk (packed, 6 feature tiles).  n_rows % 32 == 0. */
@@ -166,14 +166,6 @@ int cda_mlp_reduce(const float* slab, int32_t n_chunks, const float* bias_slab, 
 int cda_mlp_apply(float* theta, float* adam_m, float* adam_v, const float* step_dev, void* wb, const float* grad, int32_t recompute_norm,
                   float lr, float beta1, float beta2, float eps, float max_norm, double* scratch, void* stream);
 
-/* cda_ppo_loss (cda.h) for int32 action arrays - the env's own action tensors as the rollout kernel wrote them.  norm_rows > 0:
- * the means (and the gradient's 1/B) are over norm_rows * agents_per_row samples instead of rows * agents_per_row (a minibatch
- * processed in several sub-batches); sums5 is then NOT cleared and out6 not written unless finish != 0. */
-int cda_ppo_loss32(const float* outputs, const float* log_std, const int32_t* a_cat, const int32_t* a_price, const int32_t* a_off,
-                   const float* a_cont, const float* logp_old, const float* adv, const float* ret, const int64_t* row_index,
-                   int64_t rows, int32_t agents_per_row, int32_t out_stride, float clip, float vf_coef, float ent_coef,
-                   float* d_outputs, double* sums5, float* out6, int64_t norm_rows, int32_t clear, int32_t finish, void* stream);
-
 /* One whole rollout of one market chain on `stream` (a loop of launches, no host work in between): for t = 0 .. n_steps - 1
  *     cda_mlp_policy_step(obs[t]) -> env actions [t] | a_cont[t] | logp[t] | value[t]
  *     cda_step_range(env, first_market, n_markets, actions [t]) -> obs[t + 1], reward[t], terminated[t], truncated[t]  (+ auto reset)
@@ -193,7 +185,7 @@ typedef struct cda_rollout_bufs {
     double*  reward;         /* [T][N][A] */
     uint8_t* terminated;     /* [T][N] */
     uint8_t* truncated;      /* [T][N] */
-    float*   record;         /* [T][N][A][8] or NULL: the sample records below (words 0..5 written by the policy step) */
+    float*   record;         /* [T][N][A][8] or NULL: the sample records of cda_learner.h (CDA_REC_*; words 0..5 written by the policy step) */
     float*   dist;           /* [T][N][CDA_MLP_DIST_LD = 28] or NULL: the rollout policy's distribution per market-step (22 normalised log-probabilities of the categorical heads | the 2 Gaussian
                                 means) - what the update's KL term needs (cda_ppo_extra) */
     const cda_info_ptrs* info_steps;   /* [T] (host array) or NULL: step t of this chain also writes the info tensors info_steps[t] (Info_Helper.set_info; the chain then runs
@@ -209,36 +201,6 @@ typedef struct cda_rollout_bufs {
 int cda_mlp_rollout_chain(cda_env* env, const void* wb, const float* theta, int32_t first_market, int32_t n_markets, int32_t n_steps,
                           uint64_t seed, const int64_t* counter_dev, const cda_rollout_bufs* bufs, int32_t copy_first_obs, void* stream);
 
-/* Sample records: what the update's loss reads of a sample, as ONE 32-byte record - a row's A samples are then one contiguous piece (the seven
- * separate per-sample arrays cost seven scattered gathers per row).  Words: */
-#define CDA_REC_CATEGORY  0   /* i32 */
-#define CDA_REC_PRICE     1   /* i32 */
-#define CDA_REC_OFFSET    2   /* i32 */
-#define CDA_REC_CONT0     3   /* f32: the raw Gaussian samples */
-#define CDA_REC_CONT1     4
-#define CDA_REC_LOGP      5   /* f32: log-probability under the rollout's policy */
-#define CDA_REC_ADV       6   /* f32: advantage (unnormalised) */
-#define CDA_REC_RET       7   /* f32: return */
-/* Generalised advantage estimation of a whole rollout, straight from its buffers into the records (ppo.gae's recursion, one launch): reward f64
- * [T][N][A] (scaled by reward_scale here), value f32 [T+1][N] (slot T = the bootstrap value), terminated / truncated u8 [T][N] -> words ADV, RET
- * of rec [T][N][A][8]; stats2 f64[2] receives the sum of the advantages and of their squares. */
-int cda_gae_records(const double* reward, const float* value, const uint8_t* terminated, const uint8_t* truncated, int32_t n_steps, int64_t n_markets,
-                    int32_t num_agents, float reward_scale, float gamma, float lam, float* rec, double* stats2, void* stream);
-/* The same with the time-limit bootstrap RLlib applies (a TRUNCATED, not terminated, step's target continues with V(last observation of the cut episode) instead of 0;
- * the device-side auto reset overwrites that observation, so the rollout captures it: cda_rollout_bufs.fin_*): fin_index i32 [T][N], fin_value f32
- * [max(n_trainable, 1)][fin_value_stride] = cda_mlp_values on the captured list.  n_trainable = 0: one shared policy; > 0: the league layout below. */
-int cda_gae_records_bootstrap(const double* reward, const float* value, const uint8_t* terminated, const uint8_t* truncated, int32_t n_steps, int64_t n_markets,
-                              int32_t num_agents, int32_t n_trainable, float reward_scale, float gamma, float lam,
-                              const int32_t* fin_index, const float* fin_value, int64_t fin_value_stride, float* rec, double* stats, void* stream);
-/* Training against scripted opponents (include/cda.h cda_scripted_attach): ONE shared policy plays and trains slots 0 .. n_slots - 1 of every market, the slots behind
- * them are scripted - their records hold no policy sample and must reach no loss.  cda_gae_records_bootstrap(n_trainable = 0)'s recursion, thread for thread, over the
- * slots < n_slots only: words ADV, RET of those slots' records are bit-equal to what it writes there, the other slots' words ADV, RET are NOT written, and stats2 f64[2]
- * sums the T * N * n_slots trained samples (that product is the count the update normalises with).  value f32 [T+1][N]; fin_index (NULL = no time-limit bootstrap) i32
- * [T][N], fin_value f32 [capacity].  The update then reads the leading slots through the record stride: cda_mlp_forward_backward(agents_per_row = n_slots,
- * cda_ppo_extra.rec_stride = 8 * num_agents).  1 <= n_slots <= num_agents. */
-int cda_gae_records_slots(const double* reward, const float* value, const uint8_t* terminated, const uint8_t* truncated, int32_t n_steps, int64_t n_markets,
-                          int32_t num_agents, int32_t n_slots, float reward_scale, float gamma, float lam,
-                          const int32_t* fin_index, const float* fin_value, float* rec, double* stats2, void* stream);
 /* value f32 [n_rows] (net p: + p * value_stride) <- the value network of each of n_nets banked networks on obs f32 [n_rows][168] (one launch). */
 int cda_mlp_values(const void* wb_bank, const float* theta_bank, int32_t n_nets, const float* obs, int64_t n_rows, float* value, int64_t value_stride, void* stream);
 /* ... of the first min(n_rows, *n_rows_dev) rows only (n_rows_dev i32[1] on the device, NULL = all): the captured list's length lives on the device (fin_count) -
@@ -246,16 +208,6 @@ int cda_mlp_values(const void* wb_bank, const float* theta_bank, int32_t n_nets,
  * forward pass over `capacity` rows). */
 int cda_mlp_values_counted(const void* wb_bank, const float* theta_bank, int32_t n_nets, const float* obs, int64_t n_rows, const int32_t* n_rows_dev,
                            float* value, int64_t value_stride, void* stream);
-/* Returns of COMPLETED episodes out of a rollout's buffers (what a learning curve is drawn from when the horizon is shorter than an episode): running f64 [N][A]
- * carries each (market, agent)'s return so far from rollout to rollout; a step that ends the market's episode adds the total to done_sum f64 [A] and 1 to
- * done_count f64 [A] (both accumulate: the caller clears them) and restarts it.  per_slot: what a league needs to credit returns to the MODULE that played a slot. */
-int cda_episode_returns(const double* reward, const uint8_t* terminated, const uint8_t* truncated, int32_t n_steps, int64_t n_markets, int32_t num_agents,
-                        double* running, double* done_sum, double* done_count, double* per_slot /* f64 [N][A][2] or NULL: this rollout's (sum, number) per (market, agent) */, void* stream);
-/* cda_ppo_loss32 reading sample records (rec = [all rows][A][8]; row_index as there).  adv_stats2 (may be NULL) + adv_count: the advantages are
- * normalised on the fly, (adv - mean) / (std + 1e-8) with the unbiased std over the adv_count samples the sums were taken over. */
-int cda_ppo_loss_records(const float* outputs, const float* log_std, const float* rec, const double* adv_stats2, int64_t adv_count, const int64_t* row_index,
-                         int64_t rows, int32_t agents_per_row, int32_t out_stride, float clip, float vf_coef, float ent_coef,
-                         float* d_outputs, double* sums5, float* out6, int64_t norm_rows, int32_t clear, int32_t finish, void* stream);
 
 /* The update's per-row work in ONE launch: the n_rows observation rows obs[perm[i]] (perm NULL: obs[i]) are gathered from the rollout's f32 buffer,
  * run forward, their loss taken from the sample records rec[perm[i]] (cda_ppo_loss_records' rule, advantages normalised on the fly when adv_stats2
@@ -332,25 +284,6 @@ int cda_mlp_eval_chain(cda_env* env, const void* wb, const float* theta, int32_t
                        const cda_rollout_bufs* bufs, int32_t copy_first_obs, void* stream);
 int cda_mlp_league_eval_chain(cda_env* env, const cda_league* league, int32_t first_market, int32_t n_markets, int32_t n_steps,
                               uint64_t seed, const int64_t* counter_dev, const cda_rollout_bufs* bufs, int32_t copy_first_obs, void* stream);
-/* cda_gae_records for a league: value f32 [n_trainable][T+1][N]; slot p < n_trainable gets advantage / return from net p's values, the other slots' records are left
- * alone; stats2k f64 [n_trainable][2]: per net, the sums its update normalises the advantages with. */
-int cda_gae_records_league(const double* reward, const float* value, const uint8_t* terminated, const uint8_t* truncated, int32_t n_steps, int64_t n_markets,
-                           int32_t num_agents, int32_t n_trainable, float reward_scale, float gamma, float lam, float* rec, double* stats2k, void* stream);
-
-/* The reference's agent-to-module mapping fn (league_based_self_play_callback.py:1286-1344) for all markets at once, on the device: slot s < n_trainable -> net s;
- * every other slot draws np.random.RandomState((episode_crc[market] + s) mod 2^32).choice(pool, p = probs) - bit for bit: one freshly seeded MT19937's first
- * random_sample(), searchsorted(cumsum(probs) / cumsum(probs)[-1], u, side = "right") - and receives pool_net[draw] (a bank row or CDA_LEAGUE_RANDOM).
- * episode_crc u32 [N] = zlib.crc32(str(episode id)) (host), pool_cdf f64 [pool_size] the normalised cumulative weights, slot_pool (may be NULL) i32 [N][A]: the draw
- * itself (index into the pool; -1 for the trainable slots) - what names the module in an episode record. */
-int cda_league_assign(const uint32_t* episode_crc, int32_t n_markets, int32_t num_agents, int32_t n_trainable, const double* pool_cdf, const int32_t* pool_net,
-                      int32_t pool_size, int32_t* slot_net, int32_t* slot_pool, void* stream);
-/* ... with scripted modules (include/cda.h cda_scripted_attach) in the pool: cda_league_assign's draw bit for bit - the same generator, the same searchsorted on the
- * (longer) cdf - and one more table and output: pool_script i32 [pool_size], 0 or 1 + the index of the profile a scripted pool entry plays (its pool_net entry is
- * CDA_LEAGUE_RANDOM: the scripted launch overwrites the random module's action), and slot_script i32 [N][A] <- pool_script[draw], 0 in the trainable slots and where
- * a network or the random module plays.  slot_script is the table the env was attached with (resident: rewritten in place per episode, no re-attach, captured rollout
- * graphs stay valid).  With an all-zero pool_script the other outputs equal cda_league_assign's. */
-int cda_league_assign_scripted(const uint32_t* episode_crc, int32_t n_markets, int32_t num_agents, int32_t n_trainable, const double* pool_cdf, const int32_t* pool_net,
-                               const int32_t* pool_script, int32_t pool_size, int32_t* slot_net, int32_t* slot_script, int32_t* slot_pool, void* stream);
 
 /* Device self-test of the operand / accumulator conventions this file is built on: D f32[32][32] = A bf16-rounded f32[32][16] x
  * B f32[16][32] through one v_mfma_f32_32x32x16_bf16 (host pointers; synchronous). */

@@ -12,6 +12,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "cda.h")
 MLP_HEADER = os.path.join(ROOT, "include", "cda_mlp.h")
+LEARNER_HEADER = os.path.join(ROOT, "include", "cda_learner.h")
 
 
 def _declared_symbols(header=HEADER):
@@ -42,6 +43,12 @@ def test_every_declared_symbol_is_exported(hip_lib):
     for name in declared_mlp:
         assert hasattr(L, name), f"{name} declared in include/cda_mlp.h but not exported by libcda_hip.so"
     assert sorted(_lib.MLP_SYMBOLS) == declared_mlp
+    # ... and every symbol of the learner-side header (include/cda_learner.h: the entry points that have no variants)
+    declared_learner = _declared_symbols(LEARNER_HEADER)
+    assert len(declared_learner) >= 10
+    for name in declared_learner:
+        assert hasattr(L, name), f"{name} declared in include/cda_learner.h but not exported by libcda_hip.so"
+    assert sorted(_lib.LEARNER_SYMBOLS) == declared_learner
 
 
 def test_ctypes_layout_matches_c(tmp_path):
@@ -142,7 +149,7 @@ def test_every_network_entry_point_exists_for_every_compiled_history_depth():
     hdr = open(os.path.join(root, "include", "cda_mlp.h")).read()
     variants = [int(x) for x in re.search(r'#define CDA_MLP_HIST_VARIANTS "([0-9 ]+)"', hdr).group(1).split()]
     declared = set(re.findall(r"^(?:int|int32_t)\s+(cda_[a-z0-9_]+)\s*\(", hdr, flags=re.M))
-    assert len(declared) >= 25 and variants == [1, 2, 3, 6, 7, 8]
+    assert len(declared) >= 20 and variants == [1, 2, 3, 6, 7, 8]      # (23: the ten entry points without variants are include/cda_learner.h's)
     renames = set(re.findall(r"#define (cda_[a-z0-9_]+) CDA_MLP_SFX\(\1\)", open(os.path.join(root, "gym_continuousdoubleauction_amd", "csrc", "cda_mlp_variant.h")).read()))
     assert renames == declared, (sorted(declared - renames), sorted(renames - declared))
     from gym_continuousdoubleauction_amd import _lib
@@ -156,8 +163,9 @@ def test_every_network_entry_point_exists_for_every_compiled_history_depth():
 
 
 def test_network_entry_points_refuse_bad_arguments_before_touching_the_device(hip_lib):
-    """include/cda_mlp.h: every entry point of the network / league / learner side, in every compiled history depth, validates first - all-NULL arguments and
-    out-of-range sizes return CDA_ERR_INVALID with no launch (this test runs without a GPU), so a binding bug on the consumer's side is an error code, not a fault."""
+    """include/cda_mlp.h: every entry point of the network / league side, in every compiled history depth, and include/cda_learner.h: every learner-side entry point
+    (one copy, no variants), validates first - all-NULL arguments and out-of-range sizes return CDA_ERR_INVALID with no launch (this test runs without a GPU), so a
+    binding bug on the consumer's side is an error code, not a fault."""
     from gym_continuousdoubleauction_amd import _lib
     L, _ = hip_lib
     INVALID = -1
@@ -191,12 +199,39 @@ def test_network_entry_points_refuse_bad_arguments_before_touching_the_device(hi
         assert wg(one, one, one, one, one, one, 64, 3, one, None) == INVALID and wg(one, one, one, one, one, one, 40, 1, one, None) == INVALID
         vals = getattr(L, "cda_mlp_values" + sfx)
         assert vals(one, one, 0, one, 64, one, 64, None) == INVALID and vals(one, one, 17, one, 64, one, 64, None) == INVALID and vals(one, one, 2, one, 0, one, 64, None) == INVALID
-        assign = getattr(L, "cda_league_assign" + sfx)
-        assert assign(one, 8, 4, 2, one, one, 0, one, None, None) == INVALID and assign(one, 0, 4, 2, one, one, 3, one, None, None) == INVALID
-        assert assign(one, 8, 17, 2, one, one, 3, one, None, None) == INVALID and assign(one, 8, 4, 5, one, one, 3, one, None, None) == INVALID
-        gl = getattr(L, "cda_gae_records_league" + sfx)
-        assert gl(one, one, one, one, 8, 8, 4, 0, 1.0, 0.99, 0.95, one, one, None) == INVALID and gl(one, one, one, one, 8, 8, 4, 5, 1.0, 0.99, 0.95, one, one, None) == INVALID
-        er = getattr(L, "cda_episode_returns" + sfx)
-        assert er(one, one, one, 0, 8, 4, one, one, one, None, None) == INVALID and er(one, one, one, 8, 8, 17, one, one, one, None, None) == INVALID
         red = getattr(L, "cda_mlp_reduce" + sfx)
         assert red(one, 0, one, 1, None, 0, 0.5, 0.01, 0.0, None, one, one, one, None) == INVALID and red(one, 1, one, 1, one, 0, 0.5, 0.01, 0.0, None, one, one, one, None) == INVALID
+    for name in _lib.LEARNER_SYMBOLS:
+        fn = getattr(L, name)
+        assert fn.argtypes and fn(*[zero(t) for t in fn.argtypes]) == INVALID, name
+    assign = L.cda_league_assign
+    assert assign(one, 8, 4, 2, one, one, 0, one, None, None) == INVALID and assign(one, 0, 4, 2, one, one, 3, one, None, None) == INVALID
+    assert assign(one, 8, 17, 2, one, one, 3, one, None, None) == INVALID and assign(one, 8, 4, 5, one, one, 3, one, None, None) == INVALID
+    gl = L.cda_gae_records_league
+    assert gl(one, one, one, one, 8, 8, 4, 0, 1.0, 0.99, 0.95, one, one, None) == INVALID and gl(one, one, one, one, 8, 8, 4, 5, 1.0, 0.99, 0.95, one, one, None) == INVALID
+    er = L.cda_episode_returns
+    assert er(one, one, one, 0, 8, 4, one, one, one, None, None) == INVALID and er(one, one, one, 8, 8, 17, one, one, one, None, None) == INVALID
+
+
+def test_learner_entry_points_exist_once_and_serve_every_layout(hip_lib):
+    """include/cda_learner.h's entry points read neither the history depth nor the activation nor vf_share_layers: the library holds ONE copy of each (no
+    <name>[_h<H>][_<act>][_vfs] is exported for any of them), the two symbol lists are disjoint, and a layout's fn() hands out that one copy for a learner name
+    and the layout's own variant for a network name."""
+    L, _lib = hip_lib
+    from gym_continuousdoubleauction_amd import mlp
+    assert len(_lib.LEARNER_SYMBOLS) == 10 and not set(_lib.LEARNER_SYMBOLS) & set(_lib.MLP_SYMBOLS)
+    syms = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = {ln.split()[-1] for ln in syms.splitlines() if ln.strip()}
+    suffixes = _lib.mlp_variant_suffixes()
+    assert len(suffixes) == 55
+    for name in _lib.LEARNER_SYMBOLS:
+        assert name in exported
+        for sfx in suffixes:
+            assert name + sfx not in exported, name + sfx
+    for name in _lib.MLP_SYMBOLS:
+        assert all(name + sfx in exported for sfx in [""] + suffixes), name
+    lay = mlp.layout(2, "relu", True)
+    for name in _lib.LEARNER_SYMBOLS:
+        assert lay.fn(name) is getattr(L, name) and mlp.layout(4).fn(name) is getattr(L, name)
+    for name in _lib.MLP_SYMBOLS:
+        assert lay.fn(name) is getattr(L, name + "_h2_relu_vfs") and lay.fn(name) is not getattr(L, name)

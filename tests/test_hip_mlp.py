@@ -434,6 +434,47 @@ def test_gae_into_records_and_the_loss_on_records_equal_the_array_path(T):
     env.close()
 
 
+@pytest.mark.parametrize("R,reverse", [(200, False), (300, True)])
+def test_the_two_unfused_loss_kernels_are_one_body(R, reverse):
+    """cda_ppo_loss32 on the seven per-sample arrays and cda_ppo_loss_records on the same samples packed as records (no advantage normalisation: adv_stats2 = NULL)
+    run ONE row body (csrc/cda_learner.hip ppo_loss_rows) on two sample sources: d_outputs agree bit for bit, out-of-range categories (pick clamps them) included.
+    200 rows are one workgroup of 256 with idle tail lanes - the five sums then have a single order of addition and agree bit for bit too; 300 rows are two
+    workgroups (the sums' atomics have no fixed order: not compared), read through a reversed row_index."""
+    from gym_continuousdoubleauction_amd._lib import lib, check
+    A, LD = 4, 32
+    g = torch.Generator().manual_seed(100 + R)
+    out = torch.randn((R, LD), generator=g).to(DEV)
+    log_std = torch.tensor([-0.3, 0.2], dtype=torch.float32, device=DEV)
+    cat = torch.randint(0, 9, (R * A,), generator=g, dtype=torch.int32)
+    cat[5], cat[R * A - 3] = 11, -2                           # out of range on either side
+    price = torch.randint(0, 10, (R * A,), generator=g, dtype=torch.int32)
+    off = torch.randint(0, 3, (R * A,), generator=g, dtype=torch.int32)
+    cont = torch.randn((R * A, 2), generator=g)
+    logp_old = -6.0 + torch.randn((R * A,), generator=g)
+    adv, ret = torch.randn((R * A,), generator=g), torch.randn((R * A,), generator=g)
+    rec = torch.empty((R * A, 8), dtype=torch.float32)
+    rec.view(torch.int32)[:, 0], rec.view(torch.int32)[:, 1], rec.view(torch.int32)[:, 2] = cat, price, off
+    rec[:, 3:5], rec[:, 5], rec[:, 6], rec[:, 7] = cont, logp_old, adv, ret
+    cat, price, off, cont, logp_old, adv, ret, rec = (t.to(DEV).contiguous() for t in (cat, price, off, cont, logp_old, adv, ret, rec))
+    assert torch.equal(rec.view(torch.int32)[:, 0], cat) and torch.equal(rec[:, 6], adv)
+    index = torch.arange(R - 1, -1, -1, dtype=torch.int64, device=DEV) if reverse else None
+    iptr = index.data_ptr() if reverse else None
+    st = torch.cuda.current_stream().cuda_stream
+    d = [torch.full((R, LD), float("nan"), device=DEV) for _ in range(2)]
+    sums = [torch.full((5,), float("nan"), dtype=torch.float64, device=DEV) for _ in range(2)]
+    out6 = [torch.zeros(8, device=DEV) for _ in range(2)]
+    check(lib().cda_ppo_loss32(out.data_ptr(), log_std.data_ptr(), cat.data_ptr(), price.data_ptr(), off.data_ptr(), cont.data_ptr(), logp_old.data_ptr(), adv.data_ptr(),
+                               ret.data_ptr(), iptr, R, A, LD, 0.2, 0.5, 0.01, d[0].data_ptr(), sums[0].data_ptr(), out6[0].data_ptr(), 0, 1, 1, st), "cda_ppo_loss32")
+    check(lib().cda_ppo_loss_records(out.data_ptr(), log_std.data_ptr(), rec.data_ptr(), None, 0, iptr, R, A, LD, 0.2, 0.5, 0.01, d[1].data_ptr(), sums[1].data_ptr(),
+                                     out6[1].data_ptr(), 0, 1, 1, st), "cda_ppo_loss_records")
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(d[0]).all()) and float(d[0][:, :25].abs().max()) > 0 and bool((d[0][:, 25:] == 0).all())
+    assert torch.equal(d[0].view(torch.int32), d[1].view(torch.int32))
+    assert bool(torch.isfinite(sums[0]).all()) and float(sums[0][1]) > 0
+    if not reverse:
+        assert torch.equal(sums[0].view(torch.int64), sums[1].view(torch.int64)) and torch.equal(out6[0].view(torch.int32), out6[1].view(torch.int32))
+
+
 @pytest.mark.parametrize("N,T,A", [(96, 40, 4), (100, 40, 4),    # 3840 rows = 60 whole tiles; 4000 rows: the last tile is half empty
                                    (64, 8, 8), (64, 8, 2), (64, 8, 1), (32, 9, 16), (40, 8, 5)])   # other agent counts: the quad deals agents round four lanes
 def test_fused_forward_loss_backward_equals_the_separate_kernels(N, T, A):

@@ -23,7 +23,7 @@ def _kernels():
     co = os.path.join(ROOT, "gym_continuousdoubleauction_amd", "_kernel_resources.co")
     notes = asm = ""
     try:
-        for blob in code_objects(so):                        # one code object per translation unit (env, PPO helpers, network)
+        for blob in code_objects(so):                        # one code object per translation unit (env, PPO helpers, learner-side kernels, network: one per variant)
             open(co, "wb").write(blob)
             notes += subprocess.run([READELF, "--notes", co], capture_output=True, text=True, check=True).stdout
             asm += subprocess.run([OBJDUMP, "-d", "--no-show-raw-insn", co], capture_output=True, text=True, check=True).stdout
@@ -93,7 +93,7 @@ def test_step_kernels_keep_four_waves_per_simd_and_spill_no_vgpr():
 @pytest.mark.skipif(not (os.path.exists(READELF) and os.path.exists(OBJDUMP) and shutil.which(os.environ.get("HIPCC", "hipcc"))),
                     reason="needs hipcc and the ROCm LLVM tools")
 def test_network_kernels_spill_nothing():
-    """The MFMA kernels of csrc/cda_mlp.hip keep accumulators, operand rings and epilogue values in the 512-entry register file: a spill there
+    """The MFMA kernels of csrc/cda_mlp.hip (and the GAE, episode-return and league-assignment kernels of csrc/cda_learner.hip, which exist once) keep accumulators, operand rings and epilogue values in the 512-entry register file: a spill there
     is scratch traffic inside the k-loop (round 4: 137 spilled VGPRs made the training forward 1.5 x slower until its tail predicates went)."""
     ks, _ = _kernels()
     net = {n: v for n, v in ks.items() if any(k in n for k in ("k_mlp_fwd", "k_mlp_bwd", "k_mlp_wgrad", "k_mlp_fb", "k_grad_reduce", "k_adam", "k_gae_records", "k_grad_norm",

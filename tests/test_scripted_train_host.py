@@ -208,31 +208,29 @@ def hip_lib():
 
 
 def test_new_entry_points_load_with_their_prototypes(hip_lib):
-    """both symbols, in every compiled variant: declared in the header, in the rename list, bound with argtypes; NULL pointers and out-of-range sizes are
-    CDA_ERR_INVALID before anything is launched (no GPU needed)"""
+    """both symbols: declared in the learner-side header (include/cda_learner.h: one copy in the library, so in no rename list), bound with argtypes; NULL pointers
+    and out-of-range sizes are CDA_ERR_INVALID before anything is launched (no GPU needed)"""
     import re
     L, _lib = hip_lib
     INVALID = -1
-    hdr = open(os.path.join(ROOT, "include", "cda_mlp.h")).read()
+    hdr = open(os.path.join(ROOT, "include", "cda_learner.h")).read()
     var = open(os.path.join(ROOT, "gym_continuousdoubleauction_amd", "csrc", "cda_mlp_variant.h")).read()
     vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
     protos = {"cda_gae_records_slots": [vp, vp, vp, vp, i32, i64, i32, i32, f32, f32, f32, vp, vp, vp, vp, vp],
               "cda_league_assign_scripted": [vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp]}
     one = C.c_void_p(64)                                          # non-NULL, never dereferenced: the size checks fail first
     for name, argtypes in protos.items():
-        assert re.search(r"^int\s+%s\s*\(" % name, hdr, flags=re.M) and f"#define {name} CDA_MLP_SFX({name})" in var and name in _lib.MLP_SYMBOLS
+        assert re.search(r"^int\s+%s\s*\(" % name, hdr, flags=re.M) and name not in var and name in _lib.LEARNER_SYMBOLS and name not in _lib.MLP_SYMBOLS
         n_args = len(re.search(r"^int\s+%s\s*\((.*?)\);" % name, hdr, flags=re.M | re.S).group(1).split(","))
         assert n_args == len(argtypes)
-        for sfx in [""] + _lib.mlp_variant_suffixes():
-            fn = getattr(L, name + sfx)
-            assert list(fn.argtypes) == argtypes and fn.restype is C.c_int, name + sfx
-            assert fn(*[None if t is vp else (0.0 if t is f32 else 0) for t in argtypes]) == INVALID, name + sfx
-    for sfx in ("", "_h8", "_relu_vfs"):
-        gs = getattr(L, "cda_gae_records_slots" + sfx)
-        call = lambda T=8, N=8, A=4, k=2, rec=one, fin_index=None, fin_value=None: gs(one, one, one, one, T, N, A, k, 1.0, 0.99, 0.95, fin_index, fin_value, rec, one, None)   # noqa: E731
-        assert call(k=0) == INVALID and call(k=5) == INVALID and call(T=0) == INVALID and call(N=0) == INVALID and call(A=17, k=1) == INVALID
-        assert call(rec=None) == INVALID and call(fin_index=one) == INVALID and call(rec=C.c_void_p(68)) == INVALID
-        asg = getattr(L, "cda_league_assign_scripted" + sfx)
-        acall = lambda N=8, A=4, k=2, P=3, script=one, slot_script=one: asg(one, N, A, k, one, one, script, P, one, slot_script, None, None)   # noqa: E731
-        assert acall(P=0) == INVALID and acall(N=0) == INVALID and acall(A=17) == INVALID and acall(k=5) == INVALID and acall(k=-1) == INVALID
-        assert acall(script=None) == INVALID and acall(slot_script=None) == INVALID
+        fn = getattr(L, name)
+        assert list(fn.argtypes) == argtypes and fn.restype is C.c_int, name
+        assert fn(*[None if t is vp else (0.0 if t is f32 else 0) for t in argtypes]) == INVALID, name
+    gs = L.cda_gae_records_slots
+    call = lambda T=8, N=8, A=4, k=2, rec=one, fin_index=None, fin_value=None: gs(one, one, one, one, T, N, A, k, 1.0, 0.99, 0.95, fin_index, fin_value, rec, one, None)   # noqa: E731
+    assert call(k=0) == INVALID and call(k=5) == INVALID and call(T=0) == INVALID and call(N=0) == INVALID and call(A=17, k=1) == INVALID
+    assert call(rec=None) == INVALID and call(fin_index=one) == INVALID and call(rec=C.c_void_p(68)) == INVALID
+    asg = L.cda_league_assign_scripted
+    acall = lambda N=8, A=4, k=2, P=3, script=one, slot_script=one: asg(one, N, A, k, one, one, script, P, one, slot_script, None, None)   # noqa: E731
+    assert acall(P=0) == INVALID and acall(N=0) == INVALID and acall(A=17) == INVALID and acall(k=5) == INVALID and acall(k=-1) == INVALID
+    assert acall(script=None) == INVALID and acall(slot_script=None) == INVALID
