@@ -1,5 +1,6 @@
 """Random env configurations and action laws shared by the build-container cross-check of the oracle against the reference
-(tests/golden/crosscheck_oracle.py) and the GPU fuzz test of the HIP path against the oracle."""
+(tests/golden/crosscheck_oracle.py) and the GPU fuzz tests of the HIP path against the oracle; service_case() draws, on top of a configuration, what
+the device services (book report, scripted laws, tape reductions, snapshots, order streams) are fuzzed with (tests/test_hip_services_fuzz.py)."""
 import numpy as np
 
 
@@ -83,3 +84,119 @@ def batch_actions(rng, n, a, law, present_p, order=None):
         rank = np.argsort(np.argsort(keys, axis=1), axis=1)                 # 0-based position of each agent in its market's dict
         present = np.where(mask != 0, rank + 1, 0).astype(np.uint8)
     return (cat.astype(np.int32), mean.astype(np.float32), sigma.astype(np.float32), price.astype(np.int32), off.astype(np.int32)), present
+
+
+# ---------------------------------------------------------------------------------------------------------------- service cases
+SERVICE_SEED = 20277                                 # the default CDA_FUZZ_SEED of the services fuzz: tests/test_services_fuzz_host.py holds its cases to the coverage
+SERVICE_CASES = 12
+SERVICE_MARKETS = 24                                 # six workgroups of CDA_WPB = 4 market-waves, the last one full ...
+RAGGED_CASE, RAGGED_MARKETS = 5, 22                  # ... and in one case ragged: two waves of the last workgroup leave at once
+SERVICE_HISTS = (1, 2, 3, 4, 5, 7, 8, 9, 12, 16)
+STREAM_LENGTHS = (0, 1, 63, 64, 65, 129)             # around the order kernel's chunk of 64 messages
+SERVICE_STEPS, SERVICE_STEPS_AFTER, STREAM_SOURCE_STEPS = 40, 16, 16
+# one invalid message of each kind (tests/test_hip_orders.py test_invalid_messages_are_skipped_and_reported): trader = A, type 5, side 2, size 0, price 0 on a limit
+def invalid_messages(a):
+    return [(a, 1, 0, 5, 50, 0), (0, 5, 0, 5, 50, 0), (0, 1, 2, 5, 50, 0), (0, 1, 0, 0, 50, 0), (0, 1, 0, 5, 0, 0)]
+
+
+def tile_of(cfg):
+    """the LDS book tile cda_create picks (include/cda.h book_capacity: 0 = by agent count)"""
+    return int(cfg.get("book_capacity", 0)) or (256 if cfg["num_of_agents"] <= 8 else 512)
+
+
+def row_in_domain(cfg, row):
+    """cda_check_market_params' rule on plain numbers (csrc/cda_hip.hip cfg_ok + row_ok), so that the generator can redraw without a library"""
+    c = dict(cfg, **row)
+    lo, hi = c.get("initial_price_min", 10), c.get("initial_price_max", 10)
+    mn, mx, mul = c.get("min_size", 1), c.get("mkt_max_size", 1), c.get("limit_size_multiple", 1)
+    return (1 <= c.get("tick_size", 1) <= 65536 and 0 <= lo <= hi < (1 << 24) and 0 <= mn <= mx and mul >= 1 and mx * mul + mn <= (1 << 30) // 512
+            and 1 <= c["max_step"] <= cfg["max_step"])
+
+
+def _service_row(rng, cfg, short):
+    row = {"tick_size": int(rng.choice([1, 1, 2, 5, 10, 250]))}
+    lo = int(rng.choice([1, 10, 500, 20000]))
+    row.update(initial_price_min=lo, initial_price_max=lo + int(rng.integers(0, 300)))
+    row.update(min_size=int(rng.integers(1, 5)), mkt_max_size=int(rng.choice([20, 100, 3000])), limit_size_multiple=int(rng.choice([1, 3, 10, 20])))
+    row["max_step"] = int(rng.integers(4, cfg["max_step"] + 1)) if short else int(rng.choice([256, 1000, 4096]))
+    row.update(order_penalty=float(rng.uniform(0, 1)), trade_penalty=float(rng.uniform(0, 1)), drawdown_penalty=float(rng.uniform(0, 1)),
+               passive_bonus=float(rng.uniform(0, 1)), loss_multiplier=float(rng.uniform(1, 3)))
+    return row
+
+
+def _service_profile(rng, law):
+    from gym_continuousdoubleauction_amd.scripted import Profile
+    cap = int(rng.integers(0, 61))
+    den = int(rng.integers(1, 4))
+    return Profile(law=law, size_mean=float(rng.uniform(0, 0.3)), size_sigma=float(rng.uniform(0, 0.3)), max_position=cap, skew_position=int(rng.integers(0, cap + 1)),
+                   max_orders=int(rng.integers(1, 5)), depth_levels=int(rng.integers(1, 11)), imb_num=den + int(rng.integers(0, 4)), imb_den=den,
+                   p_trade_q32=int(rng.choice([0, 1 << 30, 1 << 31, 1 << 32, int(rng.integers(0, 1 << 32))])))
+
+
+def service_case(rng, n_markets=SERVICE_MARKETS):
+    """One case of the services fuzz: random_config's draws first (the config, the law, the subset probability), then everything the services are run with.
+    Pure host code; every value is a plain number, list or numpy array.  The env config is case["cfg"]; case["oracle_cfg"] is the same without the keys the
+    oracle does not take; market m runs case["rows"][m % k] when the case has per-market rows."""
+    cfg, law, present_p = random_config(rng)
+    order = random_order(rng)
+    n, a = int(n_markets), cfg["num_of_agents"]
+    cfg["n_hist"] = int(rng.choice(SERVICE_HISTS))
+    cfg["book_capacity"] = int(rng.choice([0, 0, 256, 512]))
+    # A small explicit ring (a third of all cases) makes a wrapped window reachable.  The oracle's book is unbounded while the device drops (and flags) a rest beyond
+    # tile + ring, so the book must stay inside: the trend law (tiny sizes, mostly limit orders: several resting orders more per step and agent count) is left
+    # out, and service_prefill_sizes keeps a prefilled book of such a case close to the tile.
+    small_ring = law != "trend" and rng.random() < 0.42
+    if small_ring:
+        cfg["book_spill"] = int(rng.choice([64, 128]))
+    short = bool(rng.random() < 0.25)                     # the short horizon: episodes end, and auto reset, inside the case
+    if short:
+        cfg.update(max_step=int(rng.integers(6, 15)), auto_reset=True)
+    rows = None
+    if rng.random() < 0.5:
+        rows, k = [], int(rng.choice([2, 3]))
+        while len(rows) < k:                                  # (validated on the host and redrawn; distinct)
+            row = _service_row(rng, cfg, short)
+            if row_in_domain(cfg, row) and row not in rows:
+                rows.append(row)
+    n_prof = int(rng.integers(3, 7))                          # the four laws in a random order, then two more drawn: the first n_prof of them
+    laws = ([1 + int(x) for x in rng.permutation(4)] + [int(x) for x in rng.integers(1, 5, 2)])[:n_prof]
+    profiles = [_service_profile(rng, int(w)) for w in laws]
+    slots = rng.integers(1, n_prof + 1, (n, a)).astype(np.int32)
+    slots[rng.random((n, a)) < 0.35] = 0
+    lengths = rng.choice(STREAM_LENGTHS, n).astype(np.int64)
+    long_enough = np.flatnonzero(lengths >= 63)
+    case = {
+        "cfg": cfg, "oracle_cfg": {k: v for k, v in cfg.items() if k != "auto_reset"}, "law": law, "present_p": present_p, "order": order, "n_markets": n,
+        "rows": rows, "short": short, "small_ring": small_ring, "tile": tile_of(cfg),
+        "seed": int(rng.integers(0, 2 ** 62)),               # of the test's own generator: reset seeds, actions, positions of the spliced messages
+        "prefill": bool(rng.random() < 0.4), "prefill_seed": int(rng.integers(0, 2 ** 31)),
+        "profiles": profiles, "slots": slots, "script_seed": int(rng.integers(0, 2 ** 62)), "script_base": int(rng.integers(0, 10 ** 6)),
+        "script_draw": int(rng.integers(0, 1000)), "script_counter": int(rng.integers(0, 50)),
+        "stream_lengths": lengths, "mark_every": int(rng.integers(0, 7)),
+        "invalid_markets": sorted(int(x) for x in rng.choice(long_enough if len(long_enough) >= 2 else np.arange(n), 2, replace=False)),
+        "max_per_launch": int(rng.choice([16, 50, 64])), "split_twin": bool(rng.random() < 0.5), "clear_step_counters": bool(rng.random() < 0.5),
+        "bar_steps": int(rng.integers(1, 9)), "n_bars": int(rng.integers(1, 13)),
+        "horizons": sorted({int(x) for x in rng.choice([0, 1, 2, 5, 20, 1000], int(rng.integers(1, 5)))}),
+        "levels": int(rng.integers(1, 41)), "impact_sizes": sorted({int(x) for x in rng.choice([1, 2, 7, 33, 150, 10 ** 6], int(rng.integers(1, 5)))}),
+    }
+    n3 = int(rng.integers(5, 17))                             # the env of another size a sub-range is restored into
+    cnt = int(rng.integers(1, min(n3, n) + 1))
+    case["fork"] = {"n_markets": n3, "n": cnt, "first": int(rng.integers(0, n3 - cnt + 1)), "src_first": int(rng.integers(0, n - cnt + 1))}
+    return case
+
+
+def service_prefill_sizes(case, market):
+    """(n_bids, n_asks) of a prefilled market (every third one of a prefilled case): up to 512 per side - tile and ring both in play; with a small explicit
+    ring each side stays within a quarter of the ring around half the tile: the largest books start beyond the tile, in the ring, and every side has most of its
+    ring left for what the law adds (the device drops and flags a rest beyond tile + ring, the oracle's book is unbounded: such a case would fail on its flags)."""
+    r = np.random.default_rng(case["prefill_seed"] + market)
+    if not case["small_ring"]:
+        return tuple(int(x) for x in r.integers(0, 513, 2))
+    half, quarter = case["tile"] // 2, case["cfg"]["book_spill"] // 4
+    return tuple(int(x) for x in r.integers(half - quarter, half + quarter + 1, 2))
+
+
+def service_cases(seed=SERVICE_SEED, count=SERVICE_CASES):
+    """the first `count` cases of a seed's stream, in order (case RAGGED_CASE with the ragged market count)"""
+    rng = np.random.default_rng(seed)
+    return [service_case(rng, RAGGED_MARKETS if i == RAGGED_CASE else SERVICE_MARKETS) for i in range(count)]

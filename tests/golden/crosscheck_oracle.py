@@ -5,6 +5,13 @@ laws, agent subsets, dict key orders that change every step, books of thousands 
 Nothing is written; the point is the count of episodes that agree.
 
     PYTHONPATH=tests/golden/shim:/root/reference:tests:. python tests/golden/crosscheck_oracle.py [n_episodes] [seed]
+
+With --services the episodes are the cases of the services fuzz (tests/fuzz_cases.py service_case; tests/test_hip_services_fuzz.py trusts the oracle on them): the
+case's config - its redrawn history depth and, in short-horizon cases, its max_step included - once per distinct per-market row, under the case's law, agent
+subsets and dict order, for the case's number of steps (a short-horizon case: one whole episode).  n_episodes then counts cases (default: the fuzz's own
+twelve), seed defaults to the fuzz's.
+
+    PYTHONPATH=tests/golden/shim:/root/reference:tests:. python tests/golden/crosscheck_oracle.py --services [n_cases] [seed]
 """
 import contextlib
 import io
@@ -31,12 +38,31 @@ def random_case(rng, i):
     return f"x{i}", cfg, int(rng.integers(0, 2 ** 63)), T, int(rng.integers(0, 2 ** 31)), law, present_p, random_order(rng)
 
 
+def service_episodes(n, seed):
+    """the (config x row) episodes of the first n service cases: random_case's tuples"""
+    import fuzz_cases as F
+    out = []
+    for i, case in enumerate(F.service_cases(F.SERVICE_SEED if seed is None else seed, F.SERVICE_CASES if n is None else n)):
+        base = {k: v for k, v in case["oracle_cfg"].items() if k not in ("book_capacity", "book_spill")}       # (the reference has no tile and no ring)
+        rng = np.random.default_rng(case["seed"])
+        for j, row in enumerate(case["rows"] or [{}]):
+            cfg = dict(base, **row)
+            T = min(F.SERVICE_STEPS + F.SERVICE_STEPS_AFTER, cfg["max_step"])
+            out.append((f"s{i}r{j}", cfg, int(rng.integers(0, 2 ** 63)), T, int(rng.integers(0, 2 ** 31)), case["law"], case["present_p"], case["order"]))
+    return out
+
+
 def main():
-    n = int(sys.argv[1]) if len(sys.argv) > 1 else 200
-    rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 2024)
+    args = [a for a in sys.argv[1:] if a != "--services"]
+    services = len(args) != len(sys.argv) - 1
+    n = int(args[0]) if args else (None if services else 200)
+    seed = int(args[1]) if len(args) > 1 else (None if services else 2024)
+    episodes = service_episodes(n, seed) if services else None
+    rng = np.random.default_rng(seed)
     steps = 0
+    n = len(episodes) if services else n
     for i in range(n):
-        name, cfg, seed, T, aseed, law, present_p, order = random_case(rng, i)
+        name, cfg, seed, T, aseed, law, present_p, order = episodes[i] if services else random_case(rng, i)
         with contextlib.redirect_stdout(io.StringIO()):
             rec = MG.run_trace(name, cfg, seed, T, aseed, law=law, present_p=present_p, dict_order=order)
         rec = {k: (v if isinstance(v, np.ndarray) else np.asarray(v)) for k, v in rec.items()}
@@ -53,7 +79,7 @@ def main():
             env.close()
         if (i + 1) % 50 == 0:
             print(f"{i + 1} episodes, {steps} steps: all fields identical")
-    print(f"oracle == reference on {n} random episodes ({steps} steps)")
+    print(f"oracle == reference on {n} {'service-case' if services else 'random'} episodes ({steps} steps)")
     return 0
 
 

@@ -37,18 +37,18 @@ def _law(rng, n, a):
 
 
 @functools.lru_cache(maxsize=None)
-def _streams():
+def _streams(a=A, n_hist=4):
     """Six markets' streams, cut from an oracle random-agent run's decoded orders in that run's execution order (another seed per market), a mark behind every 4
-    orders.  Computed once (CPU only) and shared; never modified."""
+    orders.  Computed once per (agents, history depth) (CPU only) and shared; never modified."""
     n, steps = len(LENGTHS), 70
-    src = O.OracleEnv(_cfg(256), n)
+    src = O.OracleEnv(_cfg(256, num_of_agents=a, n_hist=n_hist), n)
     src.reset(SEEDS)
     rng = np.random.default_rng(17)
     la, ex = [], []
     for t in range(steps):
-        _, _, _, _, info = src.step(*_law(rng, n, A))
+        _, _, _, _, info = src.step(*_law(rng, n, a))
         la.append(info["lob_actions"].copy())
-        ex.append(np.array([[src.trace[i].exec_order[j] for j in range(A)] for i in range(n)]))
+        ex.append(np.array([[src.trace[i].exec_order[j] for j in range(a)] for i in range(n)]))
     src.close()
     la, ex = np.stack(la), np.stack(ex)                                  # [T, n, A, 4], [T, n, A]
     out = []
@@ -92,12 +92,16 @@ def _np(t):
     return t.cpu().numpy()
 
 
-@pytest.mark.parametrize("cap", [256, 512])
-def test_a_stream_equals_the_hooks_and_the_oracle_at_the_chunk_edges(cap):
-    streams = _streams()
-    hip, ora = _envs(cap)
-    hooks, _ = _envs(cap, oracle=False)
-    assert hip.env.book_capacity == cap
+# The kernel's message stage lies in LDS behind CDA_WPB x lds_bytes_per_wave(num_agents, n_hist): 3 agents at depth 1 put it nearest, 16 agents at depth 16 farthest;
+# the stream source is the same oracle recipe with that agent count.  (The first two rows are the module's A = 4 at the default depth.)
+@pytest.mark.parametrize("cap,a,n_hist", [(256, A, 4), (512, A, 4)] + [(cap, a, h) for a in (3, 16) for h in (1, 16) for cap in (256, 512)],
+                         ids=["256", "512"] + [f"{cap}-A{a}-h{h}" for a in (3, 16) for h in (1, 16) for cap in (256, 512)])
+def test_a_stream_equals_the_hooks_and_the_oracle_at_the_chunk_edges(cap, a, n_hist):
+    streams = _streams(a, n_hist)
+    shape = {} if (a, n_hist) == (A, 4) else {"num_of_agents": a, "n_hist": n_hist}
+    hip, ora = _envs(cap, **shape)
+    hooks, _ = _envs(cap, oracle=False, **shape)
+    assert hip.env.book_capacity == cap and hip.env.num_agents == a and hip.env.n_hist == n_hist
     empty_before = (bytes(hip.get_state(0)), hip.get_book(0, 0).tobytes(), hip.get_book(0, 1).tobytes(), hip.raw_snapshot()[0].tobytes())
     res, summary = hip.env.submit_orders([list(s) for s in streams])
     for i, st in enumerate(streams):

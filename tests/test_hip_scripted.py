@@ -44,12 +44,30 @@ def spec_on_env(env, seed, counter, draw, base=0, branches=None):
     return S.actions_from_views(profiles, pix, views, seed, counter, base + m, draw, j, branches=branches), slots != 0
 
 
-def device_equals_spec(env, seed, counter, draw, base=0, branches=None, tag=""):
+def spec_on_dumps(env, seed, counter, draw, base=0):
+    """spec_on_env fed from HOST dumps: the views come from get_book() through book.py (report_from_books), not from the device's book_levels / book_agents - an
+    error the report kernels and k_script_actions shared would cancel out in spec_on_env, not here"""
+    n, a = env.n_markets, env.num_agents
+    slots, profiles = env.scripted_slots(), env.scripted_profiles()
+    pix = np.maximum(slots - 1, 0)
+    depth = np.array([p.depth_levels for p in profiles])[pix]
+    states = [env.get_state(i) for i in range(n)]
+    views = views_of_books([env.get_book(i) for i in range(n)], a, [[int(s.acc[j].net_position) for j in range(a)] for s in states], [int(s.t_step) for s in states],
+                           [int(env.market_config(i)["tick_size"]) for i in range(n)], depth)
+    m, j = np.meshgrid(np.arange(n), np.arange(a), indexing="ij")
+    return S.actions_from_views(profiles, pix, views, seed, counter, base + m, draw, j), slots != 0
+
+
+def device_equals_spec(env, seed, counter, draw, base=0, branches=None, tag="", dumps=False):
     want, scripted = spec_on_env(env, seed, counter, draw, base, branches)
     got = env.scripted_actions(draw=draw, counter=counter)
     got = tuple(got[k].cpu().numpy() for k in KEYS)
     for k, g, w in zip(KEYS, got, want):
         assert np.array_equal(g[scripted].view(np.uint32), w[scripted].view(np.uint32)), (tag, k, np.argwhere((g != w) & scripted)[:4])
+    if dumps:                                                # ... and against the same specification on independent input
+        want, _ = spec_on_dumps(env, seed, counter, draw, base)
+        for k, g, w in zip(KEYS, got, want):
+            assert np.array_equal(g[scripted].view(np.uint32), w[scripted].view(np.uint32)), (tag, "dump-fed", k, np.argwhere((g != w) & scripted)[:4])
     return got
 
 
@@ -67,7 +85,7 @@ def test_device_equals_specification(n, a, tile):
     tally = {}
     device_equals_spec(env, 77, 0, 0, 1000, tally, "after reset")
     env.run_scripted(50)
-    device_equals_spec(env, 77, 3, 50, 1000, tally, "after 50")
+    device_equals_spec(env, 77, 3, 50, 1000, tally, "after 50", dumps=True)
     ctr = torch.tensor([9], dtype=torch.int64, device="cuda:0")           # the counter read on the device
     a_dev = env.scripted_actions(draw=50, counter=ctr)
     a_int = env.scripted_actions(draw=50, counter=9)

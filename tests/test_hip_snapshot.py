@@ -52,19 +52,23 @@ def _same_dumps(x, y):
         assert s1 == s2 and np.array_equal(b1, b2) and np.array_equal(a1, a2)
 
 
-def test_round_trip_is_bit_exact():
-    cfg = {"num_of_agents": 4, "init_cash": 1000000, "max_step": 320, "is_render": False, "auto_reset": True}
-    env = CDAVecEnv(cfg, n_markets=1024, device="cuda:0", with_info=True)
+def _round_trip(n, a, shape):
+    cfg = dict({"num_of_agents": a, "init_cash": 1000000, "max_step": 320, "is_render": False, "auto_reset": True}, **shape)
+    env = CDAVecEnv(cfg, n_markets=n, device="cuda:0", with_info=True)
     env.reset(seed=17)
     env.enable_episode_metrics(True)
     env.run_random(300, action_seed=5)
     torch.cuda.synchronize()
     rng = np.random.default_rng(3)
-    acts = [_actions(rng, 1024, 4, env.device) for _ in range(40)]          # crosses the episode end at step 320: auto resets + credited episodes
+    acts = [_actions(rng, n, a, env.device) for _ in range(40)]             # crosses the episode end at step 320: auto resets + credited episodes
     obs0 = env.obs.clone()
     snap = env.snapshot()
-    assert len(snap) == 1024 and snap.nbytes < 1024 * (env.state_bytes_per_market() + 4096)
-    sample = list(range(0, 1024, 97))
+    # compact: the header, the offset table and per market one 256-byte aligned section = record + 32 bytes of ring metadata + the metric rows (csrc/cda_snapshot.inc;
+    # random agents' books stay inside the tile, so no ring window follows) - at 4 agents well below the record + 4096 bytes
+    pad = lambda x: -(-x // 256) * 256      # noqa: E731
+    section = pad(env.state_bytes_per_market() + 32 + 8 * (a * K.EM_AGENT_FIELDS + K.EM_ENV_FIELDS))
+    assert len(snap) == n and snap.nbytes == 256 + pad(8 * (n + 1)) + n * section and (a > 4 or snap.nbytes < n * (env.state_bytes_per_market() + 4096))
+    sample = list(range(0, n, 97 if n > 97 else 7))
     first = _run(env, acts)
     dump1 = _dump(env, sample)
     em1 = [t.clone() for t in env.collect_episode_metrics()]
@@ -78,8 +82,19 @@ def test_round_trip_is_bit_exact():
     _same_runs(first, second)
     _same_dumps(dump1, _dump(env, sample))
     em2 = env.collect_episode_metrics()
-    assert all(torch.equal(a.view(torch.int64), b.view(torch.int64)) for a, b in zip(em1, em2))
+    assert all(torch.equal(x.view(torch.int64), y.view(torch.int64)) for x, y in zip(em1, em2))
     env.close()
+
+
+def test_round_trip_is_bit_exact():
+    _round_trip(1024, 4, {})
+
+
+@pytest.mark.parametrize("a,n_hist", [(3, 1), (16, 16)])
+def test_round_trip_is_bit_exact_at_the_smallest_and_the_largest_record(a, n_hist):
+    """test_round_trip_is_bit_exact where the section sizes, the metric rows and the re-emitted observation are smallest and largest: 3 agents at history depth 1,
+    16 agents (tile 512) at depth 16; 96 markets"""
+    _round_trip(96, a, {"n_hist": n_hist})
 
 
 def _deep_env(tile, spill, n=3):
