@@ -21,6 +21,7 @@ CHECKPOINT_FORMAT = "cda-train-checkpoint"
 CHECKPOINT_VERSION = 1
 STATE_FILE = "state.pt"
 ENV_FILE = "env.snap"
+LOOPS = {"ppo": "ppo.train_fused", "league": "league_train.train_league_fused"}        # checkpoint kind -> the loop that writes it
 _NAME = re.compile(r"^iter_(\d+)$")
 
 
@@ -219,3 +220,60 @@ def check_resumable(checkpoint_dir, chkpt_freq, restore, world=1, allreduce=None
     if resumable and recorder is not None:
         raise ValueError("checkpoint / restore: an episode recorder's files cannot be resumed; run without a recorder")
     return resumable
+
+
+# ---- the life cycle of a run ------------------------------------------------------------------------------------------------------
+def run_args(policy, env, horizon, chains, objective, epochs, lr, minibatch, seed, episode_metrics):
+    """the part of a checkpoint's `args` that both fused loops write (each adds its own keys), from a policy (the league: the bank's first), the env and the loop
+    arguments.  Reads the policy's parameters on the host, so the loops build it for a resumable run only."""
+    from .mlp import has_log_std_head, hidden_widths
+    args = {"markets": int(env.n_markets), "agents": int(env.num_agents), "horizon": int(horizon), "chains": int(chains),
+            "objective": {k: float(v) for k, v in objective.items()}, "hidden": [int(h) for h in hidden_widths(policy.theta)],
+            "state_dependent_log_std": bool(has_log_std_head(policy.theta)), "epochs": int(epochs), "lr": float(lr), "minibatch": int(minibatch),
+            "seed": int(seed), "episode_metrics": bool(episode_metrics)}
+    return with_vf_share_layers(with_activation(args, policy.activation), getattr(policy, "vf_share_layers", False))
+
+
+class Run:
+    """One run of a fused loop (kind: a key of LOOPS), resumable or not: check_resumable's refusals (raised here), the checkpoint a restore continues (`state`, `snapshot`, `path`:
+    None on a fresh run), the run id, the iterations to run (`its`) and the ones a checkpoint follows.  A resumable run calls open(args) once its argument record exists."""
+
+    def __init__(self, kind, checkpoint_dir=None, chkpt_freq=0, chkpt_keep=3, restore=None, iters=0, iters_is_delta=False, world=1, allreduce=None, recorder=None, run_id=None):
+        self.resumable = check_resumable(checkpoint_dir, chkpt_freq, restore, world=world, allreduce=allreduce, recorder=recorder)
+        self.kind, self.checkpoint_dir, self.chkpt_freq, self.chkpt_keep, self.run_id = kind, checkpoint_dir, int(chkpt_freq), chkpt_keep, run_id
+        self._restore, self._iters, self.its = restore, (iters, iters_is_delta), iteration_range(0, iters, iters_is_delta)
+        self.args = self.path = self.state = self.snapshot = None
+
+    def open(self, args):
+        """args: the argument record.  A restore loads its checkpoint (ValueError: another loop's, or other arguments) and continues its run id and iteration count"""
+        self.args, self.run_id = args, new_run_id() if self.run_id is None else self.run_id
+        if self._restore:
+            self.path = resolve_restore(self.checkpoint_dir, self._restore)
+            self.state, self.snapshot = load_checkpoint(self.path)
+            if self.state["kind"] != self.kind:
+                raise ValueError(f"{self.path} is a {self.state['kind']!r} checkpoint, not a {LOOPS[self.kind]} one")
+            check_args(self.state["args"], args)
+            self.run_id, self.its = self.state["run_id"], iteration_range(self.state["iteration"], *self._iters)
+
+    def start_env(self, env, seed, first_market, episode_metrics):
+        """the env as the first iteration finds it: the checkpoint's markets on a restore, else reset with the seed of its first (global) market"""
+        if self.state is not None:
+            if episode_metrics:                                     # (before the restore: the snapshot carries the metrics setting and the running tallies)
+                env.enable_episode_metrics(True)
+            env.restore(self.snapshot)
+        else:
+            env.reset(seed=seed + int(first_market))
+            if episode_metrics:
+                env.enable_episode_metrics(True)
+
+    def save(self, n_done, state, env, extra_dirs=None):
+        """checkpoint_dir/iter_<n_done>: the loop's `state` under this run's kind, id and arguments, and the env's markets"""
+        state = dict({"kind": self.kind, "run_id": self.run_id, "args": self.args}, **state)
+        return save_checkpoint(self.checkpoint_dir, n_done, state, env.snapshot(), keep=self.chkpt_keep, extra_dirs=extra_dirs)
+
+    def after_iteration(self, it, save, may_save=None):
+        """save(n_done) after every chkpt_freq-th iteration, and after the run's last one where may_save(n_done) allows (None: anywhere; the league: at an episode boundary)"""
+        due = self.chkpt_freq > 0 and (it + 1) % self.chkpt_freq == 0
+        final = it == self.its[-1] and (may_save is None or may_save(it + 1))
+        if self.checkpoint_dir is not None and (due or final):
+            save(it + 1)

@@ -8,6 +8,8 @@ the check, train/train.py:1109-1164 (`_check_nav_conservation`: a violation stop
 The reference logs one value per EPISODE and lets RLlib's MetricsLogger average a window of ten; a batch of N markets ends N episodes at once, so the figures
 here are the means over the episodes that ended since the last collection (sums of the per-episode numerators and denominators where the reference's own
 statistic is a ratio of sums, e.g. the fractions of one episode)."""
+import json
+
 import numpy as np
 
 from . import _capi as K
@@ -97,3 +99,19 @@ def check_nav_conservation(iteration, summary, strict=True, log=None):
             log(msg + " Continuing: strict_nav_check is off.")
         return
     raise NavConservationError(msg)
+
+
+def log_iteration(it, stats, em, module_names, history, log, strict=True, shape=None, allreduce=None):
+    """The end of a fused loop's iteration, outside its timed region: em, collected inside it (CDAVecEnv.collect_episode_metrics; None: metrics off), is summarised into
+    stats["episode_metrics"] (as shape(summary), if given), the iteration goes to `history` and the log, then NAV conservation is checked.  allreduce: a data-parallel run
+    first sums the tables' additive columns over all shards (the min / max columns stay this rank's)."""
+    summ = None
+    if em is not None:
+        if allreduce is not None:
+            allreduce(em[0]); allreduce(em[1])
+        summ = summarise(*em, module_names=module_names)
+        stats["episode_metrics"] = summ if shape is None else shape(summ)
+    history.append(stats)
+    log(json.dumps(stats))
+    if summ is not None:
+        check_nav_conservation(it, summ, strict=strict, log=log)

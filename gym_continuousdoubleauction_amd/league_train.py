@@ -19,12 +19,14 @@ Two loops:
     python -m gym_continuousdoubleauction_amd.league_train --markets 1024 --agents 4 --iters 6
 """
 import argparse
+import contextlib
 import copy
 import json
 import os
 import shutil
 import time
 
+import numpy as np
 import torch
 
 from . import ppo
@@ -142,7 +144,6 @@ class League:
 
     def maybe_promote(self, returns, iteration):
         """the reference's end-of-iteration decision; returns the new champion's id or None"""
-        import numpy as np
         k = self.mapper.num_trainable
         valid = [v for v in returns.values() if np.isfinite(v)]
         if not valid:
@@ -173,7 +174,7 @@ def train_league_fused(env, iters=4, horizon=None, num_trainable=2, lr=5e-5, epo
                        recorder=None, info_markets=0, run_id="league", log=print, keep=None, allreduce=None, world=1, first_market=0, episode_metrics=True,
                        strict_nav_check=True, state_dependent_log_std=False, hidden=(256, 256),
                        checkpoint_dir=None, chkpt_freq=0, chkpt_keep=3, restore=None, iters_is_delta=False, activation="tanh", vf_share_layers=False,
-                       scripted_opponents=None, scripted_weight=1.0, random_opponents=None, _attached=None):
+                       scripted_opponents=None, scripted_weight=1.0, random_opponents=None):
     """League self-play on the fused kernels (include/cda_mlp.h `cda_league`): the reference's training topology - `num_trainable` SEPARATELY trained policies
     (policy_p plays slot p), every other slot drawn per episode from the pool of uniform random modules and frozen champions by the reference's mapping rule
     (computed on the device, league.LeagueSlotMapper.assign_device) - at the speed of the fused loop: ONE policy launch per step serves every module of every
@@ -199,15 +200,15 @@ def train_league_fused(env, iters=4, horizon=None, num_trainable=2, lr=5e-5, epo
     opponent pool, as modules scripted_<i>_<law> behind the fixed opponents, weighted scripted_weight (1.0 = the reference rule's "otherwise"); random_opponents =
     the number of uniform random modules in the pool (default A - num_trainable; 0: a pool of scripted modules and champions only).  The profiles are attached to the
     env once, with an all-zero slot table, before the rollout graphs are captured; at every episode boundary the assignment launch (cda_league_assign_scripted)
-    rewrites the env's resident slot table beside bank.slot_net - no re-attach, no re-capture - and they are detached on exit, also on an exception.  Module returns,
+    rewrites the env's resident slot table beside bank.slot_net - no re-attach, no re-capture - and they are detached on exit, also on an exception (scripted.attached).  Module returns,
     per-module episode metrics, the recorder and league.json name them; promotion considers trainable policies only.  A checkpoint's args hold their canonical
     fields and the weight.  Single-process runs only (ValueError with world > 1); an env that has scripts attached already is refused."""
-    if getattr(env, "scripted", False) and _attached is None:        # (a scripted slot's sample record is no policy sample: it must not reach a loss)
+    if getattr(env, "scripted", False):                              # (a scripted slot's sample record is no policy sample: it must not reach a loss)
         raise ValueError("train_league_fused does not take an env with scripted opponents attached: pass them as scripted_opponents=[...] (the league attaches its pool's "
                          "profiles itself) after clear_scripted()")
-    if scripted_opponents is not None and _attached is None:
+    attach, profiles = contextlib.nullcontext(), []
+    if scripted_opponents is not None:
         from . import scripted as SC
-        kw = dict(locals())
         profiles = [SC.parse_profile(o) for o in scripted_opponents]
         if not profiles:
             raise ValueError("scripted_opponents: None or a non-empty list of scripted opponents")
@@ -217,32 +218,32 @@ def train_league_fused(env, iters=4, horizon=None, num_trainable=2, lr=5e-5, epo
             raise ValueError("scripted opponents in the league's pool: single-process runs only - data-parallel runs (world > 1) with scripts are out of scope")
         if not 1 <= int(num_trainable) <= env.num_agents - 1:
             raise ValueError(f"num_trainable must lie in 1 .. num_agents - 1 = {env.num_agents - 1} for a pool to be drawn from")
-        for name in ("kw", "SC", "env", "_attached"):
-            kw.pop(name, None)
-        import numpy as _np
         # all-zero table: nobody is scripted until the first assignment writes the draws; the script epoch (and the graphs captured on it) then hold for the whole run
-        env.set_scripted(_np.zeros((env.n_markets, env.num_agents), _np.int32), profiles, seed=seed, market_index_base=int(first_market))
-        try:
-            return train_league_fused(env, _attached=profiles, **kw)
-        finally:
-            if env.scripted:
-                env.clear_scripted()
-    profiles = list(_attached or [])
-    import numpy as np
-    from . import ppo
+        attach = SC.attached(env, np.zeros((env.n_markets, env.num_agents), np.int32), profiles, seed=seed, market_index_base=int(first_market))
+    with attach:
+        return _train_league_fused(env, profiles, ppo.merged_objective(objective), iters=iters, horizon=horizon, num_trainable=num_trainable, lr=lr, epochs=epochs, seed=seed,
+                                   original_opponent_weight=original_opponent_weight, champion_weight=champion_weight, std_dev_multiplier=std_dev_multiplier, max_champions=max_champions,
+                                   min_iterations_between_champions=min_iterations_between_champions, chains=chains, minibatch=minibatch, use_graph=use_graph, recorder=recorder,
+                                   info_markets=info_markets, run_id=run_id, log=log, keep=keep, allreduce=allreduce, world=world, first_market=first_market, episode_metrics=episode_metrics,
+                                   strict_nav_check=strict_nav_check, state_dependent_log_std=state_dependent_log_std, hidden=hidden, activation=activation, vf_share_layers=vf_share_layers,
+                                   scripted_weight=scripted_weight, random_opponents=random_opponents, ck=dict(checkpoint_dir=checkpoint_dir, chkpt_freq=chkpt_freq, chkpt_keep=chkpt_keep, restore=restore, iters_is_delta=iters_is_delta))
+
+
+def _train_league_fused(env, profiles, obj, *, iters, horizon, num_trainable, lr, epochs, seed, original_opponent_weight, champion_weight, std_dev_multiplier, max_champions,
+                        min_iterations_between_champions, chains, minibatch, use_graph, recorder, info_markets, run_id, log, keep, allreduce, world, first_market,
+                        episode_metrics, strict_nav_check, state_dependent_log_std, hidden, activation, vf_share_layers, scripted_weight, random_opponents, ck):
+    """train_league_fused's loop.  profiles: the pool's scripted modules, attached to the env ([]: none); obj: the merged objective; ck: checkpoint.Run's keywords"""
+    from . import checkpoint as CK, episode_metrics as EM
     from .mlp import EpisodeReturns, FusedUpdate, PolicyBank, RolloutChains
-    obj = dict(ppo.PPO_DEFAULTS)
-    obj.update(objective or {})
     dev = env.obs.device
     N, A, k = env.n_markets, env.num_agents, int(num_trainable)
     T = int(horizon or env.max_step)
     if int(env.max_step) % T:
         raise ValueError("the horizon must divide the episode length (max_step)")
     per_episode = int(env.max_step) // T
-    from . import checkpoint as CK
-    resumable = CK.check_resumable(checkpoint_dir, chkpt_freq, restore, world=world, allreduce=allreduce, recorder=recorder)
-    if resumable and int(chkpt_freq) % per_episode:
-        raise ValueError(f"league checkpoints are taken at episode boundaries only: chkpt_freq ({chkpt_freq}) must be a multiple of max_step / horizon = {per_episode}")
+    run = CK.Run("league", iters=iters, world=world, allreduce=allreduce, recorder=recorder, run_id=run_id, **ck)
+    if run.resumable and run.chkpt_freq % per_episode:
+        raise ValueError(f"league checkpoints are taken at episode boundaries only: chkpt_freq ({run.chkpt_freq}) must be a multiple of max_step / horizon = {per_episode}")
     bank = PolicyBank(dev, N, A, k, max_frozen=max_champions, seed=seed, random_seed=seed + 12345 + 104729 * int(first_market), n_hist=env.n_hist, state_dependent_log_std=state_dependent_log_std, hidden=hidden,
                       activation=activation, vf_share_layers=vf_share_layers)
     n_random = A - k if random_opponents is None else int(random_opponents)
@@ -253,34 +254,15 @@ def train_league_fused(env, iters=4, horizon=None, num_trainable=2, lr=5e-5, epo
         mapper.add_scripted(prof)
     league = League(mapper, bank, std_dev_multiplier, max_champions, min_iterations_between_champions)
     slot_script = env.scripted_slot_tensor() if profiles else None
-    ck_state = None
-    if resumable:
-        from .mlp import has_log_std_head, hidden_widths
-        run_args = {"markets": int(N), "agents": int(A), "horizon": int(T), "max_step": int(env.max_step), "chains": int(chains), "trainable": int(k),
-                    "objective": {kk: float(v) for kk, v in obj.items()}, "hidden": [int(h) for h in hidden_widths(bank.policies[0].theta)],
-                    "state_dependent_log_std": bool(has_log_std_head(bank.policies[0].theta)), "epochs": int(epochs), "lr": float(lr), "minibatch": int(minibatch),
-                    "seed": int(seed), "episode_metrics": bool(episode_metrics), "max_champions": int(max_champions), "std_dev_multiplier": float(std_dev_multiplier),
-                    "min_iterations_between_champions": int(min_iterations_between_champions), "original_opponent_weight": float(original_opponent_weight),
-                    "champion_weight": float(champion_weight), "run_id": str(run_id)}
-        run_args = CK.with_vf_share_layers(CK.with_activation(run_args, bank.activation), bank.vf_share_layers)
-        run_args = CK.with_scripted(run_args, profiles, scripted_weight=scripted_weight)
-        if random_opponents is not None:
-            run_args["random_opponents"] = n_random
-        if restore:
-            ck_path = CK.resolve_restore(checkpoint_dir, restore)
-            ck_state, ck_snap = CK.load_checkpoint(ck_path)
-            if ck_state["kind"] != "league":
-                raise ValueError(f"{ck_path} is a {ck_state['kind']!r} checkpoint, not a league_train.train_league_fused one")
-            CK.check_args(ck_state["args"], run_args)
-    if ck_state is not None:
-        if episode_metrics:                                     # (before the restore: the snapshot carries the metrics setting and the running tallies)
-            env.enable_episode_metrics(True)
-        env.restore(ck_snap)
-        _load_league_state(os.path.join(ck_path, "league"), ck_state, bank, league)
-    else:
-        env.reset(seed=seed + int(first_market))
-        if episode_metrics:
-            env.enable_episode_metrics(True)
+    if run.resumable:
+        args = dict(CK.run_args(bank.policies[0], env, T, chains, obj, epochs, lr, minibatch, seed, episode_metrics), max_step=int(env.max_step), trainable=int(k),
+                    max_champions=int(max_champions), std_dev_multiplier=float(std_dev_multiplier), min_iterations_between_champions=int(min_iterations_between_champions),
+                    original_opponent_weight=float(original_opponent_weight), champion_weight=float(champion_weight), run_id=str(run_id))
+        args = CK.with_scripted(args, profiles, scripted_weight=scripted_weight)
+        run.open(args if random_opponents is None else dict(args, random_opponents=n_random))     # (the key only when the argument is given: checkpoints from before it existed resume)
+    run.start_env(env, seed, first_market, episode_metrics)
+    if run.state is not None:
+        _load_league_state(os.path.join(run.path, "league"), run.state, bank, league)
     module_of, module_names = torch.zeros((N, A), dtype=torch.int32, device=dev), list(mapper.available_modules)
     use_kl = obj["kl_coef"] > 0.0
     roll = RolloutChains(env, bank, T, groups=chains, seed=seed + 7919 * int(first_market), use_graphs=use_graph, with_dist=use_kl,
@@ -308,29 +290,23 @@ def train_league_fused(env, iters=4, horizon=None, num_trainable=2, lr=5e-5, epo
         recorder.episode_namer = lambda m, e: f"{run_id}-episode{e}-market{m}"
         recorder.init_cash = env.market_rows(0, N)["init_cash"].astype("int64") if getattr(env, "per_market", False) else int(env.config.get("init_cash", 1000000))
     history = []
-    its = range(int(iters))
-    if resumable:
-        its = CK.iteration_range(ck_state["iteration"] if ck_state is not None else 0, iters, iters_is_delta)
-        if ck_state is not None:
-            CK.load_rollout_record(roll, ck_state["rollout"])
-            for p in range(k):
-                CK.load_update_record(upds[p], ck_state["updates"][p])
-            CK.load_returns_record(returns, ck_state["returns"])
-            kl_coefs = [float(x) for x in ck_state["kl_coefs"]]
-            next_crcs = mapper.episode_crcs(episode_ids(int(ck_state["iteration"]) // per_episode))
+    if run.state is not None:
+        CK.load_rollout_record(roll, run.state["rollout"])
+        for p in range(k):
+            CK.load_update_record(upds[p], run.state["updates"][p])
+        CK.load_returns_record(returns, run.state["returns"])
+        kl_coefs = [float(x) for x in run.state["kl_coefs"]]
+        next_crcs = mapper.episode_crcs(episode_ids(int(run.state["iteration"]) // per_episode))
 
     def save(n_done):
-        tmp = os.path.join(checkpoint_dir, CK.checkpoint_name(n_done) + ".league")
+        tmp = os.path.join(run.checkpoint_dir, CK.checkpoint_name(n_done) + ".league")
         shutil.rmtree(tmp, ignore_errors=True)
         save_league(tmp, bank, league)                          # the bank rows as policy files
-        state = {"kind": "league", "run_id": run_id, "args": run_args, "nets": [CK.net_record(pol) for pol in bank.policies],
-                 "wb": bank.wb.detach().cpu().clone(), "n_frozen": int(bank.n_frozen), "league": _league_record(league),
-                 "rollout": CK.rollout_record(roll), "updates": [CK.update_record(u) for u in upds], "returns": CK.returns_record(returns),
-                 "kl_coefs": [float(x) for x in kl_coefs]}
-        path = CK.save_checkpoint(checkpoint_dir, n_done, state, env.snapshot(), keep=chkpt_keep, extra_dirs={"league": tmp})
-        return path
-    saved_at = None
-    for it in its:
+        state = {"nets": [CK.net_record(pol) for pol in bank.policies], "wb": bank.wb.detach().cpu().clone(), "n_frozen": int(bank.n_frozen),
+                 "league": _league_record(league), "rollout": CK.rollout_record(roll), "updates": [CK.update_record(u) for u in upds],
+                 "returns": CK.returns_record(returns), "kl_coefs": [float(x) for x in kl_coefs]}
+        return run.save(n_done, state, env, extra_dirs={"league": tmp})
+    for it in run.its:
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
         if it % per_episode == 0:                                            # a new episode everywhere: new opponents (one launch; the crcs were computed while the GPU worked)
@@ -390,21 +366,8 @@ def train_league_fused(env, iters=4, horizon=None, num_trainable=2, lr=5e-5, epo
         roll.check_capture_overflow()                                       # (outside the timed region; warns)
         if recorder is not None and roll.info is not None:
             recorder.record_rollout(roll, iteration=it)
-        if em is not None:
-            from . import episode_metrics as EM
-            if dp:                                                           # the additive columns over all shards (min / max columns stay this rank's)
-                allreduce(em[0]); allreduce(em[1])
-            summ = EM.summarise(*em, module_names=module_names)
-            stats_h["episode_metrics"] = summ
-        history.append(stats_h)
-        log(json.dumps(stats_h))
-        if em is not None:
-            EM.check_nav_conservation(it, summ, strict=strict_nav_check, log=log)
-        if checkpoint_dir is not None and chkpt_freq > 0 and (it + 1) % int(chkpt_freq) == 0:      # (a multiple of per_episode: an episode boundary)
-            save(it + 1)
-            saved_at = it + 1
-    if checkpoint_dir is not None and len(its) > 0 and saved_at != its[-1] + 1 and (its[-1] + 1) % per_episode == 0:
-        save(its[-1] + 1)                                       # the final save, when the run ends on an episode boundary
+        EM.log_iteration(it, stats_h, em, module_names, history, log, strict=strict_nav_check, allreduce=allreduce if dp else None)     # (the whole summary, per module)
+        run.after_iteration(it, save, may_save=lambda n_done: n_done % per_episode == 0)     # (episode boundaries only: chkpt_freq is a multiple of per_episode)
     if keep is not None:
         keep.update(buffers=roll.buf, rollout=roll, updates=upds, slot_pool=slot_pool, returns=returns)
         if slot_script is not None:
@@ -491,22 +454,8 @@ def main(argv=None, parse_only=False):
     p.add_argument("--fused", action="store_true", help="the league on the hand-written network kernels (train_league_fused): the reference's topology at the fused loop's speed")
     p.add_argument("--trainable", type=int, default=None, help="separately trained policies (default: 2 with --fused, the reference's num_trained_agents; 1 otherwise)")
     p.add_argument("--horizon", type=int, default=None, help="--fused: rollout length (divides --episode; default = --episode)")
-    p.add_argument("--chains", type=int, default=4)
-    p.add_argument("--objective", choices=("ppo", "rllib"), default="ppo")
-    p.add_argument("--fcnet-hiddens", type=int, nargs=2, default=(256, 256), metavar=("H1", "H2"), help="hidden widths of the trainable policies (config/train_config.json:49), <= 256 each")
-    p.add_argument("--fcnet-activation", choices=("tanh", "relu", "elu", "linear"), default="tanh",
-                   help="--fused: the hidden activation of every policy in the bank (config/train_config.json:50)")
-    p.add_argument("--vf-share-layers", action="store_true", help="--fused: one trunk for policy and value in every net of the bank (RLlib's vf_share_layers, config/train_config.json:51)")
-    p.add_argument("--log-std-head", action="store_true", help="the trainable policies carry the state-dependent log-std head (RLlib's default module for Box actions)")
-    p.add_argument("--out", default=None, help="write a JSON summary to this file")
     p.add_argument("--save-dir", default=None, help="--fused: write the trainable policies, the champion snapshots and league.json here (save_league)")
-    p.add_argument("--checkpoint-dir", default=None, help="--fused: save resumable checkpoints (env markets, bank, league, learner state) as <dir>/iter_<n>")
-    p.add_argument("--chkpt-freq", type=int, default=0, help="--fused: checkpoint every N iterations, a multiple of episode / horizon (0: only a final one on an episode boundary)")
-    p.add_argument("--chkpt-keep", type=int, default=3, help="--fused: keep the newest N checkpoints")
-    p.add_argument("--restore", nargs="?", const=True, default=None, metavar="PATH", help="--fused: resume from the newest checkpoint under --checkpoint-dir, or from PATH")
-    p.add_argument("--iters-is-delta", action="store_true", help="with --restore: --iters counts further iterations instead of being the target")
-    p.add_argument("--market-configs", default=None, metavar="FILE.json", help="per-market parameters: a JSON list of override dicts, market m runs entry m %% len(list) "
-                                                                             "(market_params.PER_MARKET_KEYS; a max_step there may not exceed --episode)")
+    ppo.add_shared_flags(p, cap="--episode")                   # the network, the objective, resumable runs and --market-configs
     p.add_argument("--scripted-opponent", action="append", default=None, metavar="SPEC",
                    help="--fused: a scripted module ('pass', 'maker', 'taker', 'imbalance', 'NAME:key=value,...') in the per-episode opponent pool; repeat for several")
     p.add_argument("--scripted-weight", type=float, default=1.0, metavar="W", help="--fused: the pool weight of every scripted module (1.0 = the reference rule's \"otherwise\")")
@@ -520,7 +469,6 @@ def main(argv=None, parse_only=False):
         return args
     from .vec_env import CDAVecEnv
     from .market_params import load_market_configs, round_robin
-    from . import ppo
     cfg = {"num_of_agents": args.agents, "init_cash": 1000000, "max_step": args.episode, "is_render": False}
     mcfg = round_robin(load_market_configs(args.market_configs), args.markets) if args.market_configs else None
     if not args.fused:
@@ -535,9 +483,6 @@ def main(argv=None, parse_only=False):
                                          checkpoint_dir=args.checkpoint_dir, chkpt_freq=args.chkpt_freq, chkpt_keep=args.chkpt_keep, restore=args.restore,
                                          iters_is_delta=args.iters_is_delta, activation=args.fcnet_activation, vf_share_layers=args.vf_share_layers,
                                          scripted_opponents=args.scripted_opponent, scripted_weight=args.scripted_weight, random_opponents=args.random_opponents)
-    flags = env.flags()
-    _, bad = env.nav_conservation()
-    tail = hist[2:] if len(hist) >= 4 else (hist[1:] or hist)          # (two warm-up iterations: graph capture, first replays)
     summary = {"metric": "agent-steps/sec end to end (league rollout + one PPO update per trainable policy)",
                "config": {"workload": f"{args.markets} markets x {args.agents} agents, {k} separately trained policies (policy_p plays slot p) against modules drawn per episode "
                                       f"and slot from {args.agents - k} uniform random modules + up to 8 champion snapshots (the reference's mapping rule, on the device); episode "
@@ -546,19 +491,11 @@ def main(argv=None, parse_only=False):
                           "markets": args.markets, "agents": args.agents, "trainable": k, "episode": args.episode, "horizon": args.horizon or args.episode, "chains": args.chains,
                           "objective": args.objective, "activation": args.fcnet_activation, "scripted_opponents": args.scripted_opponent,
                           "scripted_weight": args.scripted_weight if args.scripted_opponent else None},
-               "iterations": hist, "timed_iterations": len(tail),
-               "value": sum(h["agent_steps"] for h in tail) / sum(h["rollout_s"] + h["update_s"] for h in tail), "unit": "agent-steps/s",
-               "rollout_agent_steps_per_s": sum(h["agent_steps"] for h in tail) / sum(h["rollout_s"] for h in tail),
-               "champions": league.history, "flagged_markets": int((flags != 0).sum().item()), "nav_conservation_violations": int(bad.sum().item()),
-               "invariant_violations": int((env.check_invariants() != 0).sum().item())}
+               "iterations": hist, "champions": league.history}
     if args.save_dir:
         save_league(args.save_dir, bank, league)
         summary["saved"] = args.save_dir
-    print(json.dumps(summary))
-    if args.out:
-        with open(args.out, "w") as fh:
-            json.dump(summary, fh, indent=1)
-    env.close()
+    ppo.finish_summary(summary, env, hist, args.out)
 
 
 if __name__ == "__main__":

@@ -18,6 +18,7 @@ at 8, for the same numbers; `shared_obs=False` is the plain one-forward-per-samp
     python -m gym_continuousdoubleauction_amd.ppo --markets 4096 --agents 4 --horizon 64 --iters 4
 """
 import argparse
+import contextlib
 import json
 import math
 import time
@@ -527,6 +528,11 @@ def adapt_kl_coef(kl_coef, sampled_kl, kl_target):
     return kl_coef
 
 
+def merged_objective(objective=None, **overrides):
+    """PPO_DEFAULTS, then `objective` (a dict over its keys), then every override that is not None: what the fused loops optimise"""
+    return {**PPO_DEFAULTS, **(objective or {}), **{k: v for k, v in overrides.items() if v is not None}}
+
+
 def train_fused(env, iters=4, horizon=64, lr=5e-5, epochs=4, reward_scale=None, seed=0, log=print, use_graph=True, chains=4, minibatch=262144,
                 gamma=None, lam=None, clip=None, vf_coef=None, ent_coef=None, policy=None, keep=None, sub_batches=None, objective=None, recorder=None, info_markets=0,
                 allreduce=None, world=1, first_market=0, episode_metrics=True, strict_nav_check=True, state_dependent_log_std=False, hidden=(256, 256),
@@ -562,83 +568,58 @@ def train_fused(env, iters=4, horizon=64, lr=5e-5, epochs=4, reward_scale=None, 
     trained_slots = k / opponents (training against scripted opponents, scripted.py): slots 0 .. k - 1 of every market play and train the one shared policy, slots
     k .. A - 1 are scripted.  Either the caller attached the scripts (env.set_scripted; profiles may differ per market and slot) and passes trained_slots=k, or passes
     opponents=[spec, ...] (scripted.parse_profile's forms): slot k + j of market m then plays opponents[(m + j) % P] (scripted.opponent_slots), attached here with seed
-    `seed` and market base `first_market`, and detached on exit, also on an exception.  The sample records of the scripted slots reach no loss: the advantage sums
+    `seed` and market base `first_market`, and detached on exit, also on an exception (scripted.attached).  The sample records of the scripted slots reach no loss: the advantage sums
     cover the trained slots (cda_gae_records_slots) and the update reads the leading k records of every row through the record stride.  mean_reward and
     episode_return are over the trained slots; history[i]["episode_metrics"]["modules"] is keyed policy_0, scripted_<i>_<law>.  ValueError: a scripted slot below k,
     an unscripted slot at or above k, k outside 1 .. A - 1, opponents on an env that has scripts attached, world > 1 (data-parallel runs with scripted opponents are
     out of scope); trained_slots=None on an env with scripts attached.  A checkpoint's args hold the profiles' canonical fields and k: a restore with other
     opponents is refused."""
+    attach = contextlib.nullcontext()
     if opponents is not None:
-        from . import scripted as SC
-        kw = dict(locals())
-        opp = list(opponents)
         if getattr(env, "scripted", False):
             raise ValueError("train_fused(opponents=...) needs an env without scripted opponents attached: it attaches its own for the run (clear_scripted() first, or "
                              "keep yours and pass trained_slots alone)")
         if trained_slots is None:
             raise ValueError("train_fused(opponents=...) needs trained_slots = the number of leading slots per market that the policy plays and trains")
-        if int(world) > 1 or allreduce is not None:
-            raise ValueError("training against scripted opponents is a single-process run: data-parallel runs (world > 1) with scripts are out of scope")
-        if not opp:
-            raise ValueError("opponents: None or a non-empty list of scripted opponents")
-        profiles = [SC.parse_profile(o) for o in opp]
-        slots = SC.opponent_slots(env.n_markets, env.num_agents, trained_slots, len(profiles))
-        for name in ("kw", "SC", "opp", "env", "opponents"):
-            kw.pop(name, None)
-        env.set_scripted(slots, profiles, seed=seed, market_index_base=int(first_market))       # (before the chains are captured)
-        try:
-            return train_fused(env, opponents=None, **kw)
-        finally:
-            if env.scripted:
-                env.clear_scripted()
-    k_tr = None if trained_slots is None else int(trained_slots)
-    if k_tr is None and getattr(env, "scripted", False):        # (a scripted slot's sample record is no policy sample: it must not reach a loss)
+    elif trained_slots is None and getattr(env, "scripted", False):         # (a scripted slot's sample record is no policy sample: it must not reach a loss)
         raise ValueError("train_fused trains on an env with scripted opponents attached only when told which slots the policy plays: pass trained_slots=k "
                          "(or clear_scripted() first)")
-    if k_tr is not None:
-        from .mlp import check_trained_slots
-        if int(world) > 1 or allreduce is not None:
-            raise ValueError("training against scripted opponents is a single-process run: data-parallel runs (world > 1) with scripts are out of scope")
-        check_trained_slots(env.scripted_slots(), k_tr)
+    if trained_slots is not None and (int(world) > 1 or allreduce is not None):
+        raise ValueError("training against scripted opponents is a single-process run: data-parallel runs (world > 1) with scripts are out of scope")
+    if opponents is not None:
+        from . import scripted as SC
+        profiles = [SC.parse_profile(o) for o in opponents]
+        if not profiles:
+            raise ValueError("opponents: None or a non-empty list of scripted opponents")
+        attach = SC.attached(env, SC.opponent_slots(env.n_markets, env.num_agents, trained_slots, len(profiles)), profiles, seed=seed, market_index_base=int(first_market))
+    with attach:
+        k_tr = None if trained_slots is None else int(trained_slots)
+        if k_tr is not None:
+            from .mlp import check_trained_slots
+            check_trained_slots(env.scripted_slots(), k_tr)
+        obj = merged_objective(objective, gamma=gamma, lam=lam, clip=clip, vf_coef=vf_coef, ent_coef=ent_coef, reward_scale=reward_scale)
+        return _train_fused(env, k_tr, obj, iters=iters, horizon=horizon, lr=lr, epochs=epochs, seed=seed, log=log, use_graph=use_graph, chains=chains, minibatch=minibatch,
+                            policy=policy, keep=keep, sub_batches=sub_batches, recorder=recorder, info_markets=info_markets, allreduce=allreduce, world=world, first_market=first_market,
+                            episode_metrics=episode_metrics, strict_nav_check=strict_nav_check, state_dependent_log_std=state_dependent_log_std, hidden=hidden, activation=activation,
+                            vf_share_layers=vf_share_layers, ck=dict(checkpoint_dir=checkpoint_dir, chkpt_freq=chkpt_freq, chkpt_keep=chkpt_keep, restore=restore, iters_is_delta=iters_is_delta))
+
+
+def _train_fused(env, k_tr, obj, *, iters, horizon, lr, epochs, seed, log, use_graph, chains, minibatch, policy, keep, sub_batches, recorder, info_markets, allreduce, world,
+                 first_market, episode_metrics, strict_nav_check, state_dependent_log_std, hidden, activation, vf_share_layers, ck):
+    """train_fused's loop: k_tr = the trained slots (None: every slot; the scripts are attached), obj = the merged objective, ck = the checkpoint keywords (checkpoint.Run's)"""
+    from . import checkpoint as CK, episode_metrics as EM
     from .mlp import EpisodeReturns, FusedPolicy, FusedUpdate, RolloutChains
-    obj = dict(PPO_DEFAULTS)
-    obj.update(objective or {})
-    for k_, v_ in (("gamma", gamma), ("lam", lam), ("clip", clip), ("vf_coef", vf_coef), ("ent_coef", ent_coef), ("reward_scale", reward_scale)):
-        if v_ is not None:
-            obj[k_] = v_
     dev = env.obs.device
     N, A, T = env.n_markets, env.num_agents, int(horizon)
     if policy is None:
         policy = FusedPolicy(dev, seed=seed, n_hist=env.n_hist, state_dependent_log_std=state_dependent_log_std, hidden=hidden, activation=activation,
                              vf_share_layers=vf_share_layers)
-    from . import checkpoint as CK
-    resumable = CK.check_resumable(checkpoint_dir, chkpt_freq, restore, world=world, allreduce=allreduce, recorder=recorder)
-    ck_state = None
-    if resumable:
-        from .mlp import has_log_std_head, hidden_widths
-        run_args = {"markets": int(N), "agents": int(A), "horizon": int(T), "chains": int(chains), "objective": {k: float(v) for k, v in obj.items()},
-                    "hidden": [int(h) for h in hidden_widths(policy.theta)], "state_dependent_log_std": bool(has_log_std_head(policy.theta)),
-                    "epochs": int(epochs), "lr": float(lr), "minibatch": int(minibatch), "seed": int(seed), "episode_metrics": bool(episode_metrics)}
-        run_args = CK.with_vf_share_layers(CK.with_activation(run_args, policy.activation), getattr(policy, "vf_share_layers", False))
-        if k_tr is not None:
-            run_args = CK.with_scripted(run_args, env.scripted_profiles(), trained_slots=k_tr)
-        run_id = CK.new_run_id()
-        if restore:
-            ck_path = CK.resolve_restore(checkpoint_dir, restore)
-            ck_state, ck_snap = CK.load_checkpoint(ck_path)
-            if ck_state["kind"] != "ppo":
-                raise ValueError(f"{ck_path} is a {ck_state['kind']!r} checkpoint, not a ppo.train_fused one")
-            CK.check_args(ck_state["args"], run_args)
-            run_id = ck_state["run_id"]
-    if ck_state is not None:
-        if episode_metrics:                                     # (before the restore: the snapshot carries the metrics setting and the running tallies)
-            env.enable_episode_metrics(True)
-        env.restore(ck_snap)
-        CK.load_net_record(policy, ck_state["nets"][0])
-    else:
-        env.reset(seed=seed + int(first_market))
-        if episode_metrics:
-            env.enable_episode_metrics(True)
+    run = CK.Run("ppo", iters=iters, world=world, allreduce=allreduce, recorder=recorder, **ck)
+    if run.resumable:                                       # (scripts are attached only with trained slots, and the other way round)
+        run.open(CK.with_scripted(CK.run_args(policy, env, T, chains, obj, epochs, lr, minibatch, seed, episode_metrics), env.scripted_profiles(), trained_slots=k_tr))
+    run.start_env(env, seed, first_market, episode_metrics)
+    if run.state is not None:
+        CK.load_net_record(policy, run.state["nets"][0])
     use_kl = obj["kl_coef"] > 0.0
     roll = RolloutChains(env, policy, T, groups=chains, seed=seed + 7919 * int(first_market), use_graphs=use_graph, with_dist=use_kl,
                          capture_ends=bool(obj["bootstrap_truncation"]), info_markets=info_markets if recorder is not None else 0, trained_slots=k_tr)
@@ -660,21 +641,20 @@ def train_fused(env, iters=4, horizon=64, lr=5e-5, epochs=4, reward_scale=None, 
         module_names = ["policy_0"] + [SC.module_id(i, p) for i, p in enumerate(env.scripted_profiles())]
     kl_coef = float(obj["kl_coef"])
     history = []
-    its = range(int(iters))
-    if resumable:
-        its = CK.iteration_range(ck_state["iteration"] if ck_state is not None else 0, iters, iters_is_delta)
-        if ck_state is not None:
-            CK.load_rollout_record(roll, ck_state["rollout"])
-            CK.load_update_record(upd, ck_state["update"])
-            CK.load_returns_record(returns, ck_state["returns"])
-            kl_coef = float(ck_state["kl_coef"])
+    if run.state is not None:
+        CK.load_rollout_record(roll, run.state["rollout"])
+        CK.load_update_record(upd, run.state["update"])
+        CK.load_returns_record(returns, run.state["returns"])
+        kl_coef = float(run.state["kl_coef"])
 
     def save(n_done):
-        state = {"kind": "ppo", "run_id": run_id, "args": run_args, "nets": [CK.net_record(policy)], "rollout": CK.rollout_record(roll),
-                 "update": CK.update_record(upd), "returns": CK.returns_record(returns), "kl_coef": float(kl_coef)}
-        return CK.save_checkpoint(checkpoint_dir, n_done, state, env.snapshot(), keep=chkpt_keep)
-    saved_at = None
-    for it in its:
+        return run.save(n_done, {"nets": [CK.net_record(policy)], "rollout": CK.rollout_record(roll), "update": CK.update_record(upd),
+                                 "returns": CK.returns_record(returns), "kl_coef": float(kl_coef)}, env)
+
+    def em_shape(summ):                                     # the one policy's figures flat; per module only with scripted opponents
+        top = {k: summ.get(k) for k in ("episodes", "nav_conservation_violations", "nav_conservation_error", "maker_fill_ratio_max", "episode_len_mean")}
+        return dict(summ.get("all", {}), **top, **({"modules": summ["modules"]} if module_names is not None else {}))
+    for it in run.its:
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
         buf = roll.run()
@@ -704,23 +684,8 @@ def train_fused(env, iters=4, horizon=64, lr=5e-5, epochs=4, reward_scale=None, 
         roll.check_capture_overflow()                                       # (outside the timed region; warns)
         if recorder is not None and roll.info is not None:
             recorder.record_rollout(roll, iteration=it)
-        if em is not None:
-            from . import episode_metrics as EM
-            summ = EM.summarise(*em, module_names=module_names or ["policy_0"])
-            stats["episode_metrics"] = dict(summ.get("all", {}), episodes=summ["episodes"], nav_conservation_violations=summ["nav_conservation_violations"],
-                                            nav_conservation_error=summ["nav_conservation_error"], maker_fill_ratio_max=summ.get("maker_fill_ratio_max"),
-                                            episode_len_mean=summ.get("episode_len_mean"))
-            if module_names is not None:
-                stats["episode_metrics"]["modules"] = summ["modules"]
-        history.append(stats)
-        log(json.dumps(stats))
-        if em is not None:
-            EM.check_nav_conservation(it, summ, strict=strict_nav_check, log=log)
-        if checkpoint_dir is not None and chkpt_freq > 0 and (it + 1) % int(chkpt_freq) == 0:
-            save(it + 1)
-            saved_at = it + 1
-    if checkpoint_dir is not None and len(its) > 0 and saved_at != its[-1] + 1:
-        save(its[-1] + 1)                                       # the final save
+        EM.log_iteration(it, stats, em, module_names or ["policy_0"], history, log, strict=strict_nav_check, shape=em_shape, allreduce=None)     # (None: a data-parallel run logs its own rank's)
+        run.after_iteration(it, save)
     if keep is not None:
         keep.update(buffers=roll.buf, rollout=roll, update=upd)
     return policy, history
@@ -832,6 +797,41 @@ def train(env, iters=4, horizon=64, lr=5e-5, epochs=4, reward_scale=1e-3, seed=0
     return model, history
 
 
+def add_shared_flags(p, cap):
+    """the flags of both command lines (this one's and league_train's): chains, the summary file, the network, the objective, resumable runs, per-market parameters (cap: max_step's flag)"""
+    p.add_argument("--chains", type=int, default=4, help="fused loops: independent rollout chains (market groups on their own streams)")
+    p.add_argument("--out", default=None, help="write a JSON summary (config, per-iteration stats, end-of-run env checks) to this file")
+    p.add_argument("--fcnet-hiddens", type=int, nargs=2, default=(256, 256), metavar=("H1", "H2"), help="fused loops: the two hidden widths of a trained network (config/train_config.json:49), <= 256 each")
+    p.add_argument("--fcnet-activation", choices=("tanh", "relu", "elu", "linear"), default="tanh", help="the hidden activation of every network (config/train_config.json:50; not tanh: the rollout takes two launches per step)")
+    p.add_argument("--vf-share-layers", action="store_true", help="one trunk for policy and value in every network (RLlib's vf_share_layers, config/train_config.json:51; the rollout takes two launches per step)")
+    p.add_argument("--log-std-head", action="store_true", help="fused loops: the state-dependent log-std head (RLlib's default module for Box actions) instead of a free log_std vector")
+    p.add_argument("--objective", choices=("ppo", "rllib"), default="ppo", help="fused loops: PPO_DEFAULTS, or RLLIB_DEFAULTS = the objective the reference's RLlib run optimises (clip 0.3, lambda 1, "
+                                                                              "vf coeff 1, entropy 0, vf clip 10, adaptive KL penalty, no gradient clipping, truncation bootstrap)")
+    p.add_argument("--checkpoint-dir", default=None, help="fused loops: save resumable checkpoints (env markets + learner state) as <dir>/iter_<n> (checkpoint.py)")
+    p.add_argument("--chkpt-freq", type=int, default=0, help="fused loops: checkpoint every N iterations (0: only the final one); the league: N a multiple of episode / horizon, no final one off an episode boundary")
+    p.add_argument("--chkpt-keep", type=int, default=3, help="fused loops: keep the newest N checkpoints")
+    p.add_argument("--restore", nargs="?", const=True, default=None, metavar="PATH", help="fused loops: resume from the newest checkpoint under --checkpoint-dir, or from PATH")
+    p.add_argument("--iters-is-delta", action="store_true", help="with --restore: --iters counts further iterations instead of being the target")
+    p.add_argument("--market-configs", default=None, metavar="FILE.json", help="per-market parameters: a JSON list of override dicts, market m runs entry m %% len(list) "
+                                                                             f"(market_params.PER_MARKET_KEYS; a max_step there may not exceed {cap})")
+
+
+def finish_summary(summary, env, hist, out):
+    """the end of both command lines: the JSON summary gets the throughput over the timed iterations and the env's own checks, is printed and written to `out`; the env is closed"""
+    flags = env.flags()
+    _, bad = env.nav_conservation()
+    tail = hist[2:] if len(hist) >= 4 else (hist[1:] or hist)      # two warm-up iterations (graph capture in the first; the second now and then pays a one-off 40-ms stall on a fresh box)
+    summary.update({"timed_iterations": len(tail), "value": sum(h["agent_steps"] for h in tail) / sum(h["rollout_s"] + h["update_s"] for h in tail),
+                    "rollout_agent_steps_per_s": sum(h["agent_steps"] for h in tail) / sum(h["rollout_s"] for h in tail), "unit": "agent-steps/s",
+                    "flagged_markets": int((flags != 0).sum().item()), "nav_conservation_violations": int(bad.sum().item()),
+                    "invariant_violations": int((env.check_invariants() != 0).sum().item())})
+    print(json.dumps(summary))
+    if out:
+        with open(out, "w") as fh:
+            json.dump(summary, fh, indent=1)
+    env.close()
+
+
 def main(argv=None, parse_only=False):
     """parse_only: return the parsed arguments without touching a device (the flags' tests)"""
     p = argparse.ArgumentParser()
@@ -845,25 +845,9 @@ def main(argv=None, parse_only=False):
     p.add_argument("--groups", type=int, default=1, help="market groups of the env step (independent launch chains, vec_env.CDAVecEnv)")
     p.add_argument("--no-graphs", action="store_true", help="eager rollout and update (no HIP graphs)")
     p.add_argument("--per-sample-forward", action="store_true", help="run the network once per (market, agent) sample instead of once per market-step (shared_obs=False)")
-    p.add_argument("--out", default=None, help="write a JSON summary (config, per-iteration stats, end-of-run env checks) to this file")
     p.add_argument("--legacy", action="store_true", help="the round-3 loop: PyTorch network (library GEMMs, autograd), one graph per rollout step")
-    p.add_argument("--chains", type=int, default=4, help="fused loop: independent rollout chains (market groups on their own streams)")
-    p.add_argument("--fcnet-hiddens", type=int, nargs=2, default=(256, 256), metavar=("H1", "H2"), help="fused loop: the two hidden widths (config/train_config.json:49), <= 256 each")
-    p.add_argument("--fcnet-activation", choices=("tanh", "relu", "elu", "linear"), default="tanh",
-                   help="the hidden activation of both networks (config/train_config.json:50; both loops; not tanh: the rollout takes two launches per step)")
-    p.add_argument("--vf-share-layers", action="store_true",
-                   help="one trunk for policy and value (RLlib's vf_share_layers, config/train_config.json:51; both loops; the rollout takes two launches per step)")
-    p.add_argument("--log-std-head", action="store_true", help="fused loop: the state-dependent log-std head (RLlib's default module for Box actions) instead of a free log_std vector")
-    p.add_argument("--objective", choices=("ppo", "rllib"), default="ppo", help="fused loop: PPO_DEFAULTS, or RLLIB_DEFAULTS = the objective the reference's RLlib run optimises "
-                                                                              "(clip 0.3, lambda 1, vf coeff 1, entropy 0, vf clip 10, adaptive KL penalty, no gradient clipping, truncation bootstrap)")
     p.add_argument("--save", default=None, metavar="PATH", help="fused loop: write the trained policy to this file (mlp.save_policy; evaluate.py reads it)")
-    p.add_argument("--checkpoint-dir", default=None, help="fused loop: save resumable checkpoints (env markets + learner state) as <dir>/iter_<n> (checkpoint.py)")
-    p.add_argument("--chkpt-freq", type=int, default=0, help="fused loop: checkpoint every N iterations (0: only the final one, when --checkpoint-dir is given)")
-    p.add_argument("--chkpt-keep", type=int, default=3, help="fused loop: keep the newest N checkpoints")
-    p.add_argument("--restore", nargs="?", const=True, default=None, metavar="PATH", help="fused loop: resume from the newest checkpoint under --checkpoint-dir, or from PATH")
-    p.add_argument("--iters-is-delta", action="store_true", help="with --restore: --iters counts further iterations instead of being the target")
-    p.add_argument("--market-configs", default=None, metavar="FILE.json", help="per-market parameters: a JSON list of override dicts, market m runs entry m %% len(list) "
-                                                                             "(market_params.PER_MARKET_KEYS; a max_step there may not exceed --max-step)")
+    add_shared_flags(p, cap="--max-step")                      # the network, the objective, resumable runs and --market-configs
     p.add_argument("--trained-slots", type=int, default=None, metavar="K", help="fused loop, with --opponent: the policy plays and trains slots 0 .. K - 1 of every market")
     p.add_argument("--opponent", action="append", default=None, metavar="SPEC",
                    help="fused loop: a scripted opponent ('pass', 'maker', 'taker', 'imbalance', 'NAME:key=value,...') for the slots behind --trained-slots; repeat for several "
@@ -899,9 +883,6 @@ def main(argv=None, parse_only=False):
                               checkpoint_dir=args.checkpoint_dir, chkpt_freq=args.chkpt_freq, chkpt_keep=args.chkpt_keep, restore=args.restore,
                               iters_is_delta=args.iters_is_delta, activation=args.fcnet_activation, vf_share_layers=args.vf_share_layers,
                               trained_slots=args.trained_slots, opponents=args.opponent)
-    flags = env.flags()
-    _, bad = env.nav_conservation()
-    tail = hist[2:] if len(hist) >= 4 else (hist[1:] or hist)
     summary = {"metric": "agent-steps/sec end to end (rollout + PPO update), BASELINE configs[4]",
                "config": {"workload": f"{args.markets} markets x {args.agents} agents, " + ("PyTorch-ROCm PPO policy (library GEMMs, autograd)" if args.legacy else
                                       "PPO policy on the hand-written bf16 MFMA network kernels") + f" in the loop (256x256 {args.fcnet_activation} actor and critic, "
@@ -917,22 +898,12 @@ def main(argv=None, parse_only=False):
                           "network_forward": "once per (market, agent) sample" if args.per_sample_forward else
                                              "once per market-step: the market's agents share the observation, the policy is shared, so their logits and value are one row "
                                              "(same samples, same loss, same gradients; ppo.py module docstring)"},
-               "iterations": hist,
-               # the first two iterations are warm-up (graph capture in the first; the second now and then pays a one-off 40-ms stall on a fresh box)
-               "timed_iterations": len(tail),
-               "value": sum(h["agent_steps"] for h in tail) / sum(h["rollout_s"] + h["update_s"] for h in tail),
-               "rollout_agent_steps_per_s": sum(h["agent_steps"] for h in tail) / sum(h["rollout_s"] for h in tail),
-               "unit": "agent-steps/s", "flagged_markets": int((flags != 0).sum().item()), "nav_conservation_violations": int(bad.sum().item()),
-               "invariant_violations": int((env.check_invariants() != 0).sum().item())}
+               "iterations": hist}
     if args.save:
         from .mlp import save_policy
         save_policy(args.save, trained)
         summary["saved"] = args.save
-    print(json.dumps(summary))
-    if args.out:
-        with open(args.out, "w") as fh:
-            json.dump(summary, fh, indent=1)
-    env.close()
+    finish_summary(summary, env, hist, args.out)
 
 
 if __name__ == "__main__":

@@ -6,6 +6,7 @@ A law reads a VIEW of one (market, agent) pair - integers only - and, for the ta
     vol[2] (the volume of the first depth_levels levels of each side).
 Prices are what the book stores: multiples of the market's tick_size, so a spread of "one tick" is best_ask - best_bid == tick.
 It answers the env's Dict action: (category, size_mean, size_sigma, price, price_offset); a pass is (0, 0.0, 0.0, 0, 1)."""
+import contextlib
 import dataclasses
 
 import numpy as np
@@ -128,6 +129,17 @@ def opponent_slots(n_markets, num_agents, trained_slots, n_opponents):
     m, j = np.meshgrid(np.arange(N), np.arange(A - k), indexing="ij")
     out[:, k:] = 1 + (m + j) % P
     return out
+
+
+@contextlib.contextmanager
+def attached(env, slot_script, profiles, seed=0, market_index_base=0):
+    """scripted opponents attached to `env` (CDAVecEnv.set_scripted's arguments) for a `with` block - a training run; detached on any exit, if still attached then"""
+    env.set_scripted(slot_script, profiles, seed=seed, market_index_base=market_index_base)
+    try:
+        yield
+    finally:
+        if env.scripted:
+            env.clear_scripted()
 
 
 def profiles_array(profiles, validate=True):

@@ -199,3 +199,118 @@ def test_staged_extra_directories_move_into_the_checkpoint(tmp_path):
     (extra / "league.json").write_text("{}")
     p = CK.save_checkpoint(d, 4, _state(), keep=3, extra_dirs={"league": str(extra)})
     assert os.path.isfile(os.path.join(p, "league", "league.json")) and not extra.exists()
+
+
+def test_argument_record_builder_writes_the_loops_keys_exactly():
+    """checkpoint.run_args - the part of a checkpoint's `args` both fused loops write - on stand-ins for the policy and the env: tanh / not tanh, separate / shared
+    trunk, with / without scripted opponents.  The expected dicts are what the loops' inline code wrote before the builder existed, for the same inputs: check_args
+    compares the union of the keys, so one key more, one less or one other value would refuse every checkpoint written until now."""
+    import types
+    from gym_continuousdoubleauction_amd import ppo
+    from gym_continuousdoubleauction_amd.mlp import init_theta
+
+    def policy(activation, vfs, head, hidden):
+        theta = init_theta(168, generator=torch.Generator().manual_seed(0), state_dependent_log_std=head, hidden=hidden, vf_share_layers=vfs)
+        return types.SimpleNamespace(theta=theta, activation=activation, vf_share_layers=vfs)
+    ppo_objective = {"gamma": 0.99, "lam": 0.95, "clip": 0.2, "vf_coef": 0.5, "ent_coef": 0.01, "max_norm": 0.5, "kl_coef": 0.0, "kl_target": 0.01, "vf_clip": 0.0,
+                     "bootstrap_truncation": 0.0, "reward_scale": 0.001}
+    rllib_objective = {"gamma": 0.99, "lam": 1.0, "clip": 0.3, "vf_coef": 1.0, "ent_coef": 0.0, "max_norm": float("inf"), "kl_coef": 0.2, "kl_target": 0.01, "vf_clip": 10.0,
+                       "bootstrap_truncation": 1.0, "reward_scale": 1.0}
+    plain = CK.run_args(policy("tanh", False, False, (256, 256)), types.SimpleNamespace(n_markets=256, num_agents=4), 32, 2, ppo.PPO_DEFAULTS, 4, 5e-5, 262144, 0, True)
+    assert plain == {"markets": 256, "agents": 4, "horizon": 32, "chains": 2, "objective": ppo_objective, "hidden": [256, 256], "state_dependent_log_std": False,
+                     "epochs": 4, "lr": 5e-05, "minibatch": 262144, "seed": 0, "episode_metrics": True}
+    assert CK.with_scripted(plain, [], trained_slots=None) == plain             # (train_fused without scripted opponents: the record as it is)
+    other = CK.run_args(policy("relu", True, True, (128, 64)), types.SimpleNamespace(n_markets=48, num_agents=6), 16, 3, ppo.RLLIB_DEFAULTS, 2, 1e-4, 4096, 7, False)
+    common = {"markets": 48, "agents": 6, "horizon": 16, "chains": 3, "objective": rllib_objective, "hidden": [128, 64], "state_dependent_log_std": True,
+              "epochs": 2, "lr": 0.0001, "minibatch": 4096, "seed": 7, "episode_metrics": False, "activation": "relu", "vf_share_layers": True}
+    assert other == common
+    maker = {"law": 3, "size_mean": 0.05000000074505806, "size_sigma": 0.019999999552965164, "max_position": 200, "skew_position": 60, "max_orders": 3,
+             "depth_levels": 1, "imb_num": 1, "imb_den": 1, "p_trade_q32": 0}
+    taker = {"law": 2, "size_mean": 0.10000000149011612, "size_sigma": 0.05000000074505806, "max_position": 500, "skew_position": 0, "max_orders": 1,
+             "depth_levels": 1, "imb_num": 1, "imb_den": 1, "p_trade_q32": 1073741824}
+    imbalance = {"law": 4, "size_mean": 0.10000000149011612, "size_sigma": 0.05000000074505806, "max_position": 300, "skew_position": 0, "max_orders": 1,
+                 "depth_levels": 3, "imb_num": 2, "imb_den": 1, "p_trade_q32": 0}
+    # train_fused(trained_slots=2, opponents=[...]) ...
+    assert CK.with_scripted(other, ["maker", "taker:p_trade_q32=1073741824"], trained_slots=2) == dict(common, scripted_opponents=[maker, taker], trained_slots=2)
+    # ... and train_league_fused's own keys on top of the common ones, with a scripted module in the pool
+    league = dict(other, max_step=32, trainable=1, max_champions=4, std_dev_multiplier=0.5, min_iterations_between_champions=1, original_opponent_weight=2.0,
+                  champion_weight=1.5, run_id="lg")
+    assert CK.with_scripted(league, ["imbalance:depth_levels=3"], scripted_weight=2.5) == {
+        "markets": 48, "agents": 6, "horizon": 16, "max_step": 32, "chains": 3, "trainable": 1, "objective": rllib_objective, "hidden": [128, 64],
+        "state_dependent_log_std": True, "epochs": 2, "lr": 0.0001, "minibatch": 4096, "seed": 7, "episode_metrics": False, "max_champions": 4,
+        "std_dev_multiplier": 0.5, "min_iterations_between_champions": 1, "original_opponent_weight": 2.0, "champion_weight": 1.5, "run_id": "lg",
+        "activation": "relu", "vf_share_layers": True, "scripted_opponents": [imbalance], "scripted_weight": 2.5}
+    # an activation that is not tanh on separate networks, a shared trunk under tanh: one key each
+    elu = CK.run_args(policy("elu", False, False, (256, 256)), types.SimpleNamespace(n_markets=256, num_agents=4), 32, 2, ppo.PPO_DEFAULTS, 4, 5e-5, 262144, 0, True)
+    assert elu == dict(plain, activation="elu")
+    shared = CK.run_args(policy("tanh", True, False, (256, 256)), types.SimpleNamespace(n_markets=256, num_agents=4), 32, 2, ppo.PPO_DEFAULTS, 4, 5e-5, 262144, 0, True)
+    assert shared == dict(plain, vf_share_layers=True)
+
+
+class _NoMarkets:
+    """an env whose markets need no saving"""
+
+    def snapshot(self):
+        return None
+
+
+def _save_points(tmp_path, iters, chkpt_freq, may_save=None, **kw):
+    """the iterations a Run runs and the n_done it saves after, with a save function that only records"""
+    run = CK.Run("ppo", checkpoint_dir=str(tmp_path / "ck"), chkpt_freq=chkpt_freq, iters=iters, **kw)
+    if run.resumable:
+        run.open({"markets": 4})
+    saved = []
+    for it in run.its:
+        run.after_iteration(it, saved.append, may_save=may_save)
+    return list(run.its), saved
+
+
+def test_run_life_cycle_save_points_and_refusals(tmp_path):
+    boundary = lambda n: n % 2 == 0                                           # noqa: E731 - the league's rule at two rollouts per episode
+    assert _save_points(tmp_path, 5, 2) == ([0, 1, 2, 3, 4], [2, 4, 5])        # every second iteration and the final one
+    assert _save_points(tmp_path, 4, 2) == ([0, 1, 2, 3], [2, 4])              # the final save is skipped when the last iteration was just saved
+    assert _save_points(tmp_path, 3, 0) == ([0, 1, 2], [3])                    # chkpt_freq 0: the final one only
+    assert _save_points(tmp_path, 5, 2, boundary) == ([0, 1, 2, 3, 4], [2, 4])  # ... and off an episode boundary
+    assert _save_points(tmp_path, 4, 0, boundary) == ([0, 1, 2, 3], [4]) and _save_points(tmp_path, 3, 0, boundary) == ([0, 1, 2], [])
+    assert _save_points(tmp_path, 0, 1) == ([], [])
+    # not resumable: every iteration, no save, no argument record, no run id
+    run = CK.Run("ppo", iters=3)
+    saved = []
+    for it in run.its:
+        run.after_iteration(it, saved.append)
+    assert (run.resumable, list(run.its), saved, run.args, run.state, run.run_id) == (False, [0, 1, 2], [], None, None, None)
+    # a restore: the checkpoint's run id and iteration count; iters is the target, or - iters_is_delta - that many more
+    d = str(tmp_path / "ck")
+    CK.save_checkpoint(d, 3, {"kind": "ppo", "run_id": "first", "args": {"markets": 4}}, keep=3)
+    assert _save_points(tmp_path, 5, 2, restore=True) == ([3, 4], [4, 5])
+    assert _save_points(tmp_path, 3, 1, restore=True) == ([], [])               # at the target already: nothing runs, nothing is saved
+    assert _save_points(tmp_path, 2, 0, restore=os.path.join(d, "iter_3"), iters_is_delta=True) == ([3, 4], [5])
+    assert _save_points(tmp_path, 3, 2, boundary, restore=True, iters_is_delta=True) == ([3, 4, 5], [4, 6])
+    run = CK.Run("ppo", checkpoint_dir=d, restore=True, iters=5)
+    fresh = CK.Run("ppo", checkpoint_dir=d, iters=5)
+    again = CK.Run("ppo", checkpoint_dir=d, iters=5)
+    for r in (run, fresh, again):
+        r.open({"markets": 4})
+    assert run.run_id == "first" and run.path == os.path.join(d, "iter_3") and run.state["iteration"] == 3 and run.snapshot is None
+    assert fresh.state is None and len(fresh.run_id) == 32 and fresh.run_id != again.run_id
+    given = CK.Run("league", checkpoint_dir=d, run_id="league")
+    given.open({"markets": 4})
+    assert given.run_id == "league"
+    # another loop's checkpoint, another run's arguments
+    with pytest.raises(ValueError, match=r"is a 'ppo' checkpoint, not a league_train.train_league_fused one"):
+        CK.Run("league", checkpoint_dir=d, restore=True).open({"markets": 4})
+    CK.save_checkpoint(d, 4, {"kind": "league", "run_id": "lg", "args": {"markets": 4}}, keep=3)
+    with pytest.raises(ValueError, match=r"is a 'league' checkpoint, not a ppo.train_fused one"):
+        CK.Run("ppo", checkpoint_dir=d, restore=True).open({"markets": 4})
+    for now, field in (({"markets": 8}, "markets"), ({"markets": 4, "activation": "relu"}, "activation"), ({}, "markets")):
+        with pytest.raises(ValueError, match=f"checkpoint was written by a run with {field}"):
+            CK.Run("ppo", checkpoint_dir=d, restore=os.path.join(d, "iter_3")).open(now)
+    # the refusals of check_resumable are the constructor's
+    for kw, reason in ((dict(chkpt_freq=2), "checkpoint_dir"), (dict(checkpoint_dir=d, world=2), "world"), (dict(checkpoint_dir=d, recorder=object()), "recorder")):
+        with pytest.raises(ValueError, match=reason):
+            CK.Run("ppo", **kw)
+    # what a run saves: the loop's state under its kind, id and arguments
+    run = CK.Run("ppo", checkpoint_dir=str(tmp_path / "w"), run_id="mine")
+    run.open({"markets": 4})
+    rec, _ = CK.load_checkpoint(run.save(2, {"kl_coef": 0.5}, _NoMarkets()))
+    assert {k: rec[k] for k in ("kind", "run_id", "args", "kl_coef", "iteration")} == {"kind": "ppo", "run_id": "mine", "args": {"markets": 4}, "kl_coef": 0.5, "iteration": 2}
