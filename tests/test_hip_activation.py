@@ -18,43 +18,13 @@ ACTS = ("relu", "elu", "linear")
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
 
 
+import mlp_variants as V      # noqa: E402  (the helpers every per-variant test of the network shares)
+
+_obs, _train_forward, _images, _full_backward = V.obs, V.train_forward, V.images, V.full_backward
+
+
 def _policy(act, n_hist=4, seed=3, scale=1.0, hidden=(256, 256)):
-    from gym_continuousdoubleauction_amd import mlp
-    th = mlp.init_theta(42 * n_hist, generator=torch.Generator().manual_seed(seed), hidden=hidden)
-    L = mlp.layout(n_hist)
-    th[:L.OFF_LS] *= scale
-    return mlp.FusedPolicy(DEV, theta=th, activation=act)
-
-
-def _obs(n, n_hist=4, seed=5):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(n, 42 * n_hist, generator=g) * 1.5
-    x[:, ::7] = 0.0
-    return x
-
-
-def _train_forward(p, x):
-    """prep_rows + forward_train of this policy's depth and activation: the packed images of the observation rows and of h1 / h2, the outputs"""
-    L = p.L
-    n = x.shape[0]
-    bf = torch.bfloat16
-    tile = int(L.fn("cda_mlp_tile_rows")())
-    pad = (n + tile - 1) // tile * tile
-    ws = {"x_rm": torch.zeros(n * L.KX, dtype=bf, device=DEV), "x_pk": torch.zeros(n * 32 * L.XT, dtype=bf, device=DEV),
-          "h1p": torch.zeros(pad * 512, dtype=bf, device=DEV), "h2p": torch.zeros(pad * 512, dtype=bf, device=DEV),
-          "out": torch.zeros((pad, 32), dtype=torch.float32, device=DEV), "pad": pad, "tiles": pad // tile}
-    xd = x.to(DEV).contiguous()
-    st = torch.cuda.current_stream().cuda_stream
-    from gym_continuousdoubleauction_amd._lib import check
-    check(L.fn("cda_mlp_prep_rows")(xd.data_ptr(), None, n, ws["x_rm"].data_ptr(), ws["x_pk"].data_ptr(), st), "prep")
-    check(L.fn("cda_mlp_forward_train")(p.wb.data_ptr(), p.theta.data_ptr(), ws["x_rm"].data_ptr(), n, ws["h1p"].data_ptr(), ws["h2p"].data_ptr(), ws["out"].data_ptr(), st), "fwd")
-    torch.cuda.synchronize()
-    return ws
-
-
-def _images(ws, n):
-    from gym_continuousdoubleauction_amd import mlp
-    return (mlp.unpack_rows(ws["h1p"][:n * 512], n, 512, paired=True).double(), mlp.unpack_rows(ws["h2p"][:n * 512], n, 512, paired=True).double())
+    return V.policy(n_hist, act, False, seed, scale, False, hidden)
 
 
 @pytest.mark.parametrize("n_hist", [1, 4, 8])
@@ -112,29 +82,6 @@ def test_small_pre_activations(act):
         want = mlp.act_fn(act)(b.double()).expand(32, 512)
         ulp = torch.exp2(torch.floor(torch.log2(want.abs())) - 7)
         assert bool(((g - want).abs() <= ulp).all()), float(((g - want).abs() / ulp).max())
-
-
-def _full_backward(p, x, d_out, chunks):
-    from gym_continuousdoubleauction_amd import mlp
-    from gym_continuousdoubleauction_amd._lib import check
-    L = p.L
-    n = x.shape[0]
-    ws = _train_forward(p, x)
-    bf = torch.bfloat16
-    pad, tiles = ws["pad"], ws["tiles"]
-    ws.update(dz1p=torch.zeros(pad * 512, dtype=bf, device=DEV), dz2p=torch.zeros(pad * 512, dtype=bf, device=DEV), doutp=torch.zeros(pad * 32, dtype=bf, device=DEV),
-              bias_slab=torch.zeros(tiles * mlp.BSLAB, dtype=torch.float32, device=DEV), slab=torch.zeros(chunks * L.SLAB, dtype=torch.float32, device=DEV),
-              grad=torch.zeros(L.PARAMS, dtype=torch.float32, device=DEV), norm2=torch.zeros(512, dtype=torch.float64, device=DEV))
-    dd = d_out.to(DEV).float().contiguous()
-    st = torch.cuda.current_stream().cuda_stream
-    check(L.fn("cda_mlp_backward")(p.wb.data_ptr(), dd.data_ptr(), ws["h1p"].data_ptr(), ws["h2p"].data_ptr(), n, ws["dz1p"].data_ptr(), ws["dz2p"].data_ptr(),
-                                   ws["doutp"].data_ptr(), ws["bias_slab"].data_ptr(), st), "bwd")
-    check(L.fn("cda_mlp_wgrad")(ws["x_pk"].data_ptr(), ws["h1p"].data_ptr(), ws["h2p"].data_ptr(), ws["dz1p"].data_ptr(), ws["dz2p"].data_ptr(), ws["doutp"].data_ptr(), n, chunks,
-                                ws["slab"].data_ptr(), st), "wgrad")
-    check(L.fn("cda_mlp_adam")(p.theta.data_ptr(), p.adam_m.data_ptr(), p.adam_v.data_ptr(), p.adam_step.data_ptr(), p.wb.data_ptr(), ws["slab"].data_ptr(), chunks,
-                               ws["bias_slab"].data_ptr(), tiles, None, 0, 0.0, 0.0, 0.0, None, 0.0, 0.9, 0.999, 1e-8, 0.5, ws["grad"].data_ptr(), ws["norm2"].data_ptr(), st), "adam")
-    torch.cuda.synchronize()
-    return ws
 
 
 @pytest.mark.parametrize("n_hist", [1, 4, 8])

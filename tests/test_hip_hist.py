@@ -1,7 +1,9 @@
 """GPU: the network kernels at other history depths.  The reference trains with n_hist = 4 (168-float observations: the unsuffixed entry points);
 the library also holds the same kernels compiled for n_hist 1, 2, 3, 6, 7 and 8 (include/cda_mlp.h CDA_MLP_HIST_VARIANTS: <name>_h<H>; mlp.layout(n_hist)) - 42 .. 336
 inputs: other k-step counts of layer 1, 8-byte instead of 16-byte row requests for odd depths, another split of the dW1 panel over the weight-gradient jobs (two x-tile
-groups at n_hist 8), one workgroup of the update kernel per CU at n_hist 8.  Same checks as tests/test_hip_mlp.py / test_hip_league.py, per depth."""
+groups at n_hist 8), one workgroup of the update kernel per CU at n_hist 8.  Same checks as tests/test_hip_mlp.py / test_hip_league.py, per depth.
+This file walks the depth axis at tanh and a separate trunk; the cross product with the other activations and the shared trunk (56 objects) is walked, object by
+object, in tests/test_hip_mlp_variants.py."""
 import math
 
 import numpy as np

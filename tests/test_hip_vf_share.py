@@ -19,62 +19,18 @@ H = 256
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
 
 
+import mlp_variants as V      # noqa: E402  (the helpers every per-variant test of the network shares)
+
+_obs, _train_forward, _images, _full_backward, _perturb_value_half, _trunk_tiles = V.obs, V.train_forward, V.images, V.full_backward, V.perturb_value_half, V.trunk_tiles
+
+
 def _theta(n_hist=4, seed=3, scale=1.0, sd=False, hidden=(256, 256)):
-    from gym_continuousdoubleauction_amd import mlp
-    th = mlp.init_theta(42 * n_hist, generator=torch.Generator().manual_seed(seed), state_dependent_log_std=sd, hidden=hidden, vf_share_layers=True)
-    th[:mlp.layout(n_hist).OFF_LS] *= scale
-    return th
+    return V.theta(n_hist, True, seed, scale, sd, hidden)
 
 
 def _policy(act="tanh", n_hist=4, seed=3, scale=1.0, sd=False, hidden=(256, 256)):
     from gym_continuousdoubleauction_amd import mlp
     return mlp.FusedPolicy(DEV, theta=_theta(n_hist, seed, scale, sd, hidden), activation=act, vf_share_layers=True)
-
-
-def _obs(n, n_hist=4, seed=5):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(n, 42 * n_hist, generator=g) * 1.5
-    x[:, ::7] = 0.0
-    return x
-
-
-def _perturb_value_half(p, seed=99):
-    """non-zero entries in theta's value half (behind the policy object's back), re-packed: a shared-trunk kernel must not read them"""
-    from gym_continuousdoubleauction_amd import mlp
-    g = torch.Generator().manual_seed(seed)
-    th = p.theta.cpu()
-    for a, b in mlp.value_half(p.L):
-        th[a:b] = torch.randn(b - a, generator=g) * 0.3
-    p.theta.copy_(th.to(DEV))
-    p.pack()
-
-
-def _train_forward(p, x):
-    L = p.L
-    n = x.shape[0]
-    bf = torch.bfloat16
-    tile = int(L.fn("cda_mlp_tile_rows")())
-    pad = (n + tile - 1) // tile * tile
-    ws = {"x_rm": torch.zeros(n * L.KX, dtype=bf, device=DEV), "x_pk": torch.zeros(n * 32 * L.XT, dtype=bf, device=DEV),
-          "h1p": torch.zeros(pad * 512, dtype=bf, device=DEV), "h2p": torch.zeros(pad * 512, dtype=bf, device=DEV),
-          "out": torch.zeros((pad, 32), dtype=torch.float32, device=DEV), "pad": pad, "tiles": pad // tile}
-    xd = x.to(DEV).contiguous()
-    st = torch.cuda.current_stream().cuda_stream
-    from gym_continuousdoubleauction_amd._lib import check
-    check(L.fn("cda_mlp_prep_rows")(xd.data_ptr(), None, n, ws["x_rm"].data_ptr(), ws["x_pk"].data_ptr(), st), "prep")
-    check(L.fn("cda_mlp_forward_train")(p.wb.data_ptr(), p.theta.data_ptr(), ws["x_rm"].data_ptr(), n, ws["h1p"].data_ptr(), ws["h2p"].data_ptr(), ws["out"].data_ptr(), st), "fwd")
-    torch.cuda.synchronize()
-    return ws
-
-
-def _images(ws, n):
-    from gym_continuousdoubleauction_amd import mlp
-    return (mlp.unpack_rows(ws["h1p"][:n * 512], n, 512, paired=True).double(), mlp.unpack_rows(ws["h2p"][:n * 512], n, 512, paired=True).double())
-
-
-def _trunk_tiles(packed, n):
-    """the trunk's (half 0's) feature tiles of a packed hidden image [n / 32][16 tiles][1024 bf16]"""
-    return packed[:n * 512].view(n // 32, 16, 1024)[:, :8]
 
 
 @pytest.mark.parametrize("n_hist", [1, 4, 8])
@@ -113,31 +69,6 @@ def test_forward_and_stored_activations_equal_the_rounded_reference(act, n_hist)
     assert torch.equal(_trunk_tiles(ws["h2p"], n).view(torch.int16), _trunk_tiles(ws2["h2p"], n).view(torch.int16))
     for k in s1:
         assert torch.equal(s1[k].view(torch.uint8), s2[k].view(torch.uint8)), k
-
-
-def _full_backward(p, x, d_out, chunks):
-    from gym_continuousdoubleauction_amd import mlp
-    from gym_continuousdoubleauction_amd._lib import check
-    L = p.L
-    n = x.shape[0]
-    ws = _train_forward(p, x)
-    bf = torch.bfloat16
-    pad, tiles = ws["pad"], ws["tiles"]
-    ws.update(dz1p=torch.zeros(pad * 512, dtype=bf, device=DEV), dz2p=torch.zeros(pad * 512, dtype=bf, device=DEV), doutp=torch.zeros(pad * 32, dtype=bf, device=DEV),
-              bias_slab=torch.full((tiles * mlp.BSLAB,), float("nan"), dtype=torch.float32, device=DEV),
-              slab=torch.full((chunks * L.SLAB,), float("nan"), dtype=torch.float32, device=DEV),
-              grad=torch.zeros(L.PARAMS, dtype=torch.float32, device=DEV), norm2=torch.zeros(512, dtype=torch.float64, device=DEV))
-    dd = d_out.to(DEV).float().contiguous()
-    st = torch.cuda.current_stream().cuda_stream
-    check(L.fn("cda_mlp_backward")(p.wb.data_ptr(), dd.data_ptr(), ws["h1p"].data_ptr(), ws["h2p"].data_ptr(), n, ws["dz1p"].data_ptr(), ws["dz2p"].data_ptr(),
-                                   ws["doutp"].data_ptr(), ws["bias_slab"].data_ptr(), st), "bwd")
-    # (the slab starts as NaN: the entries the shared trunk's weight-gradient jobs do not write must not be read)
-    check(L.fn("cda_mlp_wgrad")(ws["x_pk"].data_ptr(), ws["h1p"].data_ptr(), ws["h2p"].data_ptr(), ws["dz1p"].data_ptr(), ws["dz2p"].data_ptr(), ws["doutp"].data_ptr(), n, chunks,
-                                ws["slab"].data_ptr(), st), "wgrad")
-    check(L.fn("cda_mlp_adam")(p.theta.data_ptr(), p.adam_m.data_ptr(), p.adam_v.data_ptr(), p.adam_step.data_ptr(), p.wb.data_ptr(), ws["slab"].data_ptr(), chunks,
-                               ws["bias_slab"].data_ptr(), tiles, None, 0, 0.0, 0.0, 0.0, None, 0.0, 0.9, 0.999, 1e-8, 0.5, ws["grad"].data_ptr(), ws["norm2"].data_ptr(), st), "adam")
-    torch.cuda.synchronize()
-    return ws
 
 
 @pytest.mark.parametrize("n_hist", [1, 4, 8])
