@@ -30,6 +30,7 @@ SYMBOLS = [
     "cda_scripted_attach", "cda_scripted_detach", "cda_scripted_epoch", "cda_scripted_attached", "cda_scripted_actions", "cda_scripted_decide_host",
     "cda_scripted_profile_check_host",
     "cda_submit_orders", "cda_submit_orders_window", "cda_order_msgs_check_host", "cda_order_msgs_check_agents_host",
+    "cda_schedule_attach", "cda_schedule_detach", "cda_schedule_attached", "cda_schedule_epoch", "cda_schedule_counts", "cda_schedule_play", "cda_schedule_check_host",
 ]
 
 
@@ -216,6 +217,14 @@ def lib():
     L.cda_submit_orders_window.argtypes = [vp, i32, i32, vp, vp, i64, i64, i64, vp, vp, C.c_uint32, vp]
     L.cda_order_msgs_check_host.argtypes = [vp, vp, i64, C.POINTER(i64)]
     L.cda_order_msgs_check_agents_host.argtypes = [i32, vp, i64, C.POINTER(i64)]
+    L.cda_schedule_attach.argtypes = [vp, vp, vp, i32, i32, vp, i64, C.c_uint32]
+    L.cda_schedule_detach.argtypes = [vp]
+    L.cda_schedule_attached.argtypes = [vp]
+    L.cda_schedule_epoch.argtypes = [vp]
+    L.cda_schedule_epoch.restype = i64
+    L.cda_schedule_counts.argtypes = [vp, i32, i32, vp, vp]
+    L.cda_schedule_play.argtypes = [vp, i32, i32, vp]
+    L.cda_schedule_check_host.argtypes = [i32, i32, vp, vp, i32, i32, i64]
     L.cda_mlp_forward_backward.argtypes = [vp, vp, vp, vp, i64, i64, vp, vp, i64, i32, f32, f32, f32, C.POINTER(PpoExtra), vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]
     L.cda_mlp_rollout_chain.argtypes = [vp, vp, vp, i32, i32, i32, u64, vp, C.POINTER(RolloutBufs), i32, vp]
     L.cda_mlp_selftest_mfma.argtypes = [i32, vp, vp, vp]

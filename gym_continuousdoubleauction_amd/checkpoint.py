@@ -158,6 +158,13 @@ def with_scripted(args, profiles, trained_slots=None, scripted_weight=None):
     return out
 
 
+def with_order_schedule(args, digest):
+    """the loop arguments of a run on an env with an order schedule attached (CDAVecEnv.set_order_schedule): the schedule's digest (orders.schedule_digest) under
+    "order_schedule".  Added only when a schedule is attached: a run without one keeps the arguments it had before the key existed, and check_args refuses a
+    checkpoint written with another schedule, or with none, and the other way round"""
+    return dict(args, order_schedule=str(digest)) if digest else dict(args)
+
+
 def new_run_id():
     return uuid.uuid4().hex
 

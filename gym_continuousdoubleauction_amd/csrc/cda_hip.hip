@@ -331,12 +331,14 @@ struct RunArgs {
 #define CDA_CAPNS cap256
 #include "cda_kernels.inc"
 #include "cda_orders.inc"
+#include "cda_schedule.inc"
 #undef CDA_CAP
 #undef CDA_CAPNS
 #define CDA_CAP 512
 #define CDA_CAPNS cap512
 #include "cda_kernels.inc"
 #include "cda_orders.inc"
+#include "cda_schedule.inc"
 #undef CDA_CAP
 #undef CDA_CAPNS
 
@@ -639,7 +641,12 @@ struct cda_env {
     uint32_t* snap_flag;     // cda_snapshot_restore: the check pass's verdict (allocated at the first restore)
     TapeArgs tape;           // cda_tape_enable: the trade tape's rings and counters (ring == NULL: off - the launches are then the ones of an env without a tape)
     ScriptArgs script;       // cda_scripted_attach: the caller's resident slot table and profiles (slot == NULL: nothing attached - cda_scripted_actions launches nothing)
+    cda::SchedArgs sched;    // cda_schedule_attach: the caller's resident order schedule and the env's own counters table (sched_of == NULL: nothing attached - no launch)
+    int64_t sched_epoch;     // moved by every cda_schedule_attach / cda_schedule_detach
 };
+// csrc/cda_schedule.inc (included at the end): the attached order schedule's windows of [first, first + n), queued on `stream` ahead of a step; a no-op while none is attached
+static int schedule_play(cda_env* e, int32_t first, int32_t n, hipStream_t stream);
+static void schedule_free(cda_env* e);
 // csrc/cda_tape.inc (included at the end): the tape's counters follow a reset / a restore queued on `stream`; no-ops while the tape is off
 static int tape_after_reset(cda_env* e, int32_t first, int32_t n, const uint8_t* mask, hipStream_t stream);
 static int tape_after_restore(cda_env* e, int32_t first, int32_t n, hipStream_t stream);
@@ -849,6 +856,7 @@ int cda_destroy(cda_env* e) {
     if (e->em_partials) (void)hipFree(e->em_partials);
     if (e->snap_flag) (void)hipFree(e->snap_flag);
     tape_free(e);
+    schedule_free(e);
     if (e->rows) (void)hipFree(e->rows);
     free(e->rows_host);
     free(e);
@@ -902,6 +910,7 @@ int cda_reset(cda_env* e, const uint64_t* seeds, const uint8_t* mask, float* obs
 
 // one launch of k_step (+ the auto-reset pass) over [first, first + n) on `stream`; arguments validated by the callers
 static int launch_step(cda_env* e, int32_t first, int32_t n, const StepArgs& S0, hipStream_t stream) {
+    if (e->sched.sched_of) { const int rcs = schedule_play(e, first, n, stream); if (rcs) return rcs; }      // an attached order schedule: the markets' windows first
     const size_t smem = smem_for(e, CDA_WPB) + ZIG_LDS_BYTES;
     const bool tally = e->P.lay.ep_on != 0;               // episode metrics on: the instances that tally (their code is not even in the others)
 #define CDA_LAUNCH_STEP(ns) do { \
@@ -1022,7 +1031,7 @@ static int grant_policy_step_lds(const cda_env* e) {
 int cda_policy_step_supported(const cda_env* e) {
     if (!e) return 0;
     const int lds = e->cap == 256 ? policy_step_lds(e) : 0;
-    return lds > 0 && lds <= 160 * 1024 && e->P.cfg.num_agents <= 8 && !e->handback && !e->tape.ring && !e->script.slot;      // (no k_policy_step instance writes the trade tape or asks a scripted law)
+    return lds > 0 && lds <= 160 * 1024 && e->P.cfg.num_agents <= 8 && !e->handback && !e->tape.ring && !e->script.slot && !e->sched.sched_of;      // (no k_policy_step instance writes the trade tape, asks a scripted law or plays an order schedule)
 }
 // ... and whether it pays: every workgroup of k_policy_step streams the whole network for its sixteen rows, so the one launch wins while all of the env's
 // workgroups are resident at once (N <= 16 x CUs: 4096 markets on an MI355X - policy in the loop 278 -> 301-308 M at 4096 x 4) and loses to the batched policy
@@ -1168,6 +1177,7 @@ int cda_run_random(cda_env* e, int32_t n_steps, uint64_t action_seed, uint64_t m
                    float* obs_out, double* episode_return_out, uint8_t* terminated_out, uint8_t* truncated_out,
                    int32_t* steps_taken_out, void* stream) {
     if (!e || n_steps < 0) return CDA_ERR_INVALID;
+    if (e->sched.sched_of) return CDA_ERR_UNSUPPORTED;               // (k_run_random steps inside one launch: it cannot play an order schedule between its steps)
     HIPCHK(hipSetDevice(e->device));
     RunArgs R;
     R.n_steps = n_steps; R.seed = action_seed; R.market_base = market_index_base;
@@ -1613,3 +1623,5 @@ int64_t cda_state_bytes_per_market(const cda_env* e) { return e ? (int64_t)e->P.
 #include "cda_scripted.inc"
 // order streams (cda_submit_orders): explicit per-market message lists through place_order / mark_to_mkt, one wave per market (the kernels: behind cda_kernels.inc above)
 #include "cda_orders.inc"
+// order schedules (cda_schedule_*): per market and per step of its episode a window of messages, played ahead of every step through the same walk
+#include "cda_schedule.inc"

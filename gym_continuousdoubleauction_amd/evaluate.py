@@ -296,6 +296,8 @@ def main(argv=None):
     p.add_argument("--tape", default=None, metavar="FILE.npz", help="record every fill of the evaluated episodes (the trade tape) and save the records with their market, episode and module ids")
     p.add_argument("--exec-report", default=None, metavar="K[,K...]", help="with --tape: add per-module inventory, turnover and mark-outs at these step horizons, reduced "
                    "on the device from every market's last finished episode")
+    p.add_argument("--order-schedule", default=None, metavar="FILE.npz", help="attach this order schedule (orders.save_schedule) to the env: per-step order flow played ahead "
+                   "of every step of the evaluated episodes")
     args = p.parse_args(argv)
     exec_horizons = None
     if args.exec_report is not None:
@@ -311,6 +313,8 @@ def main(argv=None):
     env = CDAVecEnv({"num_of_agents": args.agents, "init_cash": 1000000, "max_step": args.max_step, "is_render": False, "auto_reset": True, "n_hist": n_hist},
                     n_markets=args.markets, device="cuda:0", with_info=False)
     try:
+        if args.order_schedule:
+            env.load_order_schedule(args.order_schedule)
         res = evaluate(env, args.policy, opponents=args.opponent, trained_slots=args.trained_slots, episodes=args.episodes,
                        mode="sample" if args.sample else "greedy", seed=args.seed, tape=args.tape, exec_horizons=exec_horizons)
     finally:

@@ -258,7 +258,7 @@ def _train_league_fused(env, profiles, obj, *, iters, horizon, num_trainable, lr
         args = dict(CK.run_args(bank.policies[0], env, T, chains, obj, epochs, lr, minibatch, seed, episode_metrics), max_step=int(env.max_step), trainable=int(k),
                     max_champions=int(max_champions), std_dev_multiplier=float(std_dev_multiplier), min_iterations_between_champions=int(min_iterations_between_champions),
                     original_opponent_weight=float(original_opponent_weight), champion_weight=float(champion_weight), run_id=str(run_id))
-        args = CK.with_scripted(args, profiles, scripted_weight=scripted_weight)
+        args = CK.with_order_schedule(CK.with_scripted(args, profiles, scripted_weight=scripted_weight), env.order_schedule_digest())
         run.open(args if random_opponents is None else dict(args, random_opponents=n_random))     # (the key only when the argument is given: checkpoints from before it existed resume)
     run.start_env(env, seed, first_market, episode_metrics)
     if run.state is not None:
@@ -465,6 +465,8 @@ def main(argv=None, parse_only=False):
         raise SystemExit("--checkpoint-dir / --restore need --fused")
     if not args.fused and (args.scripted_opponent or args.random_opponents is not None):
         raise SystemExit("--scripted-opponent / --random-opponents need --fused")
+    if not args.fused and args.order_schedule:
+        raise SystemExit("--order-schedule needs --fused")
     if parse_only:
         return args
     from .vec_env import CDAVecEnv
@@ -477,6 +479,8 @@ def main(argv=None, parse_only=False):
         env.close()
         return
     env = CDAVecEnv(dict(cfg, auto_reset=True), n_markets=args.markets, device="cuda:0", with_info=False, market_configs=mcfg)
+    if args.order_schedule:
+        env.load_order_schedule(args.order_schedule)
     k = args.trainable or 2
     bank, league, hist = train_league_fused(env, iters=args.iters, horizon=args.horizon, num_trainable=k, chains=args.chains,
                                          objective=ppo.RLLIB_DEFAULTS if args.objective == "rllib" else None, state_dependent_log_std=args.log_std_head, hidden=tuple(args.fcnet_hiddens),
@@ -489,7 +493,7 @@ def main(argv=None, parse_only=False):
                                       f"{args.episode} steps, horizon {args.horizon or args.episode}, {args.iters} iterations; hand-written bf16 MFMA network kernels, one policy launch per step "
                                       "for every module, 4 epochs per policy per iteration",
                           "markets": args.markets, "agents": args.agents, "trainable": k, "episode": args.episode, "horizon": args.horizon or args.episode, "chains": args.chains,
-                          "objective": args.objective, "activation": args.fcnet_activation, "scripted_opponents": args.scripted_opponent,
+                          "objective": args.objective, "activation": args.fcnet_activation, "scripted_opponents": args.scripted_opponent, "order_schedule": args.order_schedule,
                           "scripted_weight": args.scripted_weight if args.scripted_opponent else None},
                "iterations": hist, "champions": league.history}
     if args.save_dir:

@@ -687,6 +687,8 @@ class RolloutChains:
         self._graph_tape_epoch = getattr(self.env, "tape_epoch", 0)
         # ... and the scripted launches (or none) of the env's scripted opponents as attached now (CDAVecEnv.set_scripted / clear_scripted)
         self._graph_script_epoch = getattr(self.env, "script_epoch", 0)
+        # ... and the order schedule's launch and tables (or none) as attached now (CDAVecEnv.set_order_schedule / clear_order_schedule)
+        self._graph_schedule_epoch = getattr(self.env, "schedule_epoch", 0)
 
     def run(self):
         """one rollout of `horizon` steps; returns the buffer dict (views stay valid; the next run() overwrites them)"""
@@ -698,6 +700,9 @@ class RolloutChains:
         if self.graphs is not None and self._graph_script_epoch != getattr(self.env, "script_epoch", 0):
             raise RuntimeError("the env's scripted opponents were attached or detached after this RolloutChains captured its graphs: they would replay the "
                                "launches of the earlier setting - build a new RolloutChains")
+        if self.graphs is not None and self._graph_schedule_epoch != getattr(self.env, "schedule_epoch", 0):
+            raise RuntimeError("the env's order schedule was attached, replaced or detached after this RolloutChains captured its graphs: they would replay the "
+                               "launches and tables of the earlier setting - build a new RolloutChains")
         self._check_scripted_slots()
         if not self._have_obs or self._env_epoch != getattr(self.env, "host_epoch", 0):
             # the very first rollout - and the first one after the markets were reset / stepped from the HOST (env.host_epoch) - starts from the env's own

@@ -1,7 +1,9 @@
 """Order streams (include/cda.h cda_submit_orders; CDAVecEnv.submit_orders / seed_books): explicit messages - market, limit, modify, cancel orders and
 mark_to_mkt - played into many markets in one launch.  This module is the host side: the 16-byte message and result records as numpy structured types,
 packing per-market lists into the CSR form the device reads, the validity rule, converters from what the env already hands out (info["lob_actions"], a
-Level-3 book dump), and the plain-Python statement of what a result record holds.  Nothing here touches a device."""
+Level-3 book dump), and the plain-Python statement of what a result record holds; and the host side of order schedules (include/cda.h cda_schedule_*;
+CDAVecEnv.set_order_schedule): packing rows of per-step windows, cutting a recorded episode into them, the seed window, files and the digest a checkpoint
+keeps.  Nothing here touches a device."""
 import numpy as np
 
 from . import _capi as K
@@ -16,6 +18,8 @@ OP_MARK = 4                                         # CDA_OP_MARK: Exchg_Helper.
 ORD_INVALID, ORD_REJECTED, ORD_DONE = 0, 1, 2       # CDA_ORD_*
 CLEAR_STEP_COUNTERS = 1                             # CDA_ORDERS_CLEAR_STEP_COUNTERS
 SUMMARY_FIELDS = ("done", "rejected", "invalid", "fills")
+SCHEDULE_LOOP, SCHEDULE_CLEAR_STEP_COUNTERS = 1, 2  # CDA_SCHEDULE_*
+SCHEDULE_FAULTS = {1: "sched_of out of range", 2: "negative start", 3: "decreasing row", 4: "end beyond n_msgs"}     # CDA_SCHEDULE_BAD_*
 
 MARK = ("mark",)
 
@@ -163,3 +167,114 @@ def summary_of(results):
     """the [4] summary row (done, rejected, invalid, fills) of one market's result records"""
     r = np.asarray(results)
     return np.array([(r["status"] == ORD_DONE).sum(), (r["status"] == ORD_REJECTED).sum(), (r["status"] == ORD_INVALID).sum(), r["n_fills"].sum()], np.int32)
+
+
+# ---- order schedules -------------------------------------------------------------------------------------------------------------
+class PackedSchedule:
+    """An order schedule in the form the device reads: step_offsets int64 [n_sched, S + 1] into msgs (MSG_DTYPE [total]); row r owns, for step t of an episode,
+    msgs[step_offsets[r, t] : step_offsets[r, t + 1]]."""
+
+    def __init__(self, step_offsets, msgs):
+        self.step_offsets = np.ascontiguousarray(np.asarray(step_offsets, np.int64))
+        m = np.asarray(msgs)
+        self.msgs = np.ascontiguousarray(m if m.dtype == MSG_DTYPE else m.view(np.uint8).reshape(-1).view(MSG_DTYPE))
+        if self.step_offsets.ndim != 2 or self.step_offsets.shape[0] < 1 or self.step_offsets.shape[1] < 2:
+            raise ValueError(f"step_offsets must be [n_sched >= 1, S + 1 >= 2], got {self.step_offsets.shape}")
+
+    def __iter__(self):                                 # step_offsets, msgs = pack_schedule(rows)
+        return iter((self.step_offsets, self.msgs))
+
+    n_sched = property(lambda self: self.step_offsets.shape[0])
+    n_steps = property(lambda self: self.step_offsets.shape[1] - 1)
+
+    def window(self, r, t):
+        return self.msgs[int(self.step_offsets[r, t]):int(self.step_offsets[r, t + 1])]
+
+    def rows(self):
+        """the inverse of pack_schedule()"""
+        return [unpack(self.step_offsets[r], self.msgs) for r in range(self.n_sched)]
+
+
+def pack_schedule(rows):
+    """rows[r][t] = the messages of step t of schedule row r (each a sequence pack() takes) -> PackedSchedule.  Every row must hold the same number S >= 1 of
+    windows; a window may be empty."""
+    rows = [list(r) for r in rows]
+    if not rows or not rows[0] or any(len(r) != len(rows[0]) for r in rows):
+        raise ValueError("a schedule needs >= 1 rows of the same number >= 1 of windows")
+    S = len(rows[0])
+    off, msgs = pack([w for r in rows for w in r])
+    step_offsets = np.empty((len(rows), S + 1), np.int64)
+    for r in range(len(rows)):
+        step_offsets[r] = off[r * S:r * S + S + 1]
+    return PackedSchedule(step_offsets, msgs)
+
+
+def schedule_from_lob_actions(lob_actions, exec_order=None, traders=None):
+    """The per-step split of from_lob_actions(): T windows, window t = step t's decoded orders (info["lob_actions"] rows [T, A, 4]) in the order they executed,
+    restricted to the slots in `traders` (None = every slot) - a recorded episode's opponents as one schedule row."""
+    la = np.asarray(lob_actions)
+    if la.ndim != 3 or la.shape[2] != 4:
+        raise ValueError(f"lob_actions must be [T, A, 4], got {la.shape}")
+    keep = None if traders is None else {int(a) for a in traders}
+    out = []
+    for t in range(la.shape[0]):
+        step = from_lob_actions(la[t:t + 1], None if exec_order is None else np.asarray(exec_order)[t:t + 1])
+        out.append([(m[0], m[1], m[2], m[3], m[4], t) for m in step if keep is None or m[0] in keep])
+    return out
+
+
+def schedule_with_seed(bids, asks, rows):
+    """every row with from_book(bids, asks) prepended as window 0: the book every episode of a scheduled market starts from (the rows' own windows move one step back)"""
+    seed = from_book(bids, asks)
+    return [[list(seed)] + [list(w) for w in r] for r in rows]
+
+
+def schedule_check(sched, sched_of, num_agents, n_markets=None):
+    """cda_schedule_attach's rule on host data, stated here in Python (cda_schedule_check_host is the library's): None, or the name of the first fault
+    (SCHEDULE_FAULTS)"""
+    so = np.asarray(sched_of, np.int64).reshape(-1)
+    off = sched.step_offsets
+    if (so < -1).any() or (so >= sched.n_sched).any():
+        return SCHEDULE_FAULTS[1]
+    for r in range(sched.n_sched):
+        if off[r, 0] < 0:
+            return SCHEDULE_FAULTS[2]
+        if (np.diff(off[r]) < 0).any():
+            return SCHEDULE_FAULTS[3]
+        if off[r, -1] > len(sched.msgs):
+            return SCHEDULE_FAULTS[4]
+    return None
+
+
+def _flag_bits(loop, clear_step_counters):
+    return (SCHEDULE_LOOP if loop else 0) | (SCHEDULE_CLEAR_STEP_COUNTERS if clear_step_counters else 0)
+
+
+def save_schedule(path, sched, market_schedule=None, loop=False, clear_step_counters=False):
+    """a PackedSchedule (+ the per-market row table and the flags, when given) as one .npz"""
+    arrs = {"step_offsets": sched.step_offsets, "msgs": sched.msgs.view(np.uint8).reshape(-1, 16), "flags": np.array([_flag_bits(loop, clear_step_counters)], np.int64)}
+    if market_schedule is not None:
+        arrs["market_schedule"] = np.ascontiguousarray(np.asarray(market_schedule, np.int32))
+    with open(path, "wb") as fh:
+        np.savez(fh, **arrs)
+
+
+def load_schedule(path):
+    """-> (PackedSchedule, market_schedule int32 [N] or None, loop, clear_step_counters)"""
+    with np.load(path) as z:
+        sched = PackedSchedule(z["step_offsets"], z["msgs"].reshape(-1).view(MSG_DTYPE))
+        ms = z["market_schedule"].astype(np.int32) if "market_schedule" in z.files else None
+        flags = int(z["flags"][0])
+    if flags & ~(SCHEDULE_LOOP | SCHEDULE_CLEAR_STEP_COUNTERS):
+        raise ValueError(f"{path}: unknown schedule flag bits {flags:#x}")
+    return sched, ms, bool(flags & SCHEDULE_LOOP), bool(flags & SCHEDULE_CLEAR_STEP_COUNTERS)
+
+
+def schedule_digest(sched, sched_of, loop=False, clear_step_counters=False):
+    """sha256 (hex) over the packed arrays, the per-market row table and the flags: what a training checkpoint keeps of the schedule it ran with"""
+    import hashlib
+    h = hashlib.sha256()
+    for a in (np.array(sched.step_offsets.shape, np.int64), sched.step_offsets, np.array([len(sched.msgs)], np.int64), sched.msgs.view(np.uint8),
+              np.ascontiguousarray(np.asarray(sched_of, np.int32)), np.array([_flag_bits(loop, clear_step_counters)], np.int64)):
+        h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()

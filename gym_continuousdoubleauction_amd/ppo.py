@@ -616,7 +616,8 @@ def _train_fused(env, k_tr, obj, *, iters, horizon, lr, epochs, seed, log, use_g
                              vf_share_layers=vf_share_layers)
     run = CK.Run("ppo", iters=iters, world=world, allreduce=allreduce, recorder=recorder, **ck)
     if run.resumable:                                       # (scripts are attached only with trained slots, and the other way round)
-        run.open(CK.with_scripted(CK.run_args(policy, env, T, chains, obj, epochs, lr, minibatch, seed, episode_metrics), env.scripted_profiles(), trained_slots=k_tr))
+        run.open(CK.with_order_schedule(CK.with_scripted(CK.run_args(policy, env, T, chains, obj, epochs, lr, minibatch, seed, episode_metrics), env.scripted_profiles(),
+                                                         trained_slots=k_tr), env.order_schedule_digest()))      # (an attached order schedule: its digest)
     run.start_env(env, seed, first_market, episode_metrics)
     if run.state is not None:
         CK.load_net_record(policy, run.state["nets"][0])
@@ -812,6 +813,8 @@ def add_shared_flags(p, cap):
     p.add_argument("--chkpt-keep", type=int, default=3, help="fused loops: keep the newest N checkpoints")
     p.add_argument("--restore", nargs="?", const=True, default=None, metavar="PATH", help="fused loops: resume from the newest checkpoint under --checkpoint-dir, or from PATH")
     p.add_argument("--iters-is-delta", action="store_true", help="with --restore: --iters counts further iterations instead of being the target")
+    p.add_argument("--order-schedule", default=None, metavar="FILE.npz", help="fused loops: attach this order schedule (orders.save_schedule) to the env - per-step order flow "
+                                                                            "played ahead of every step, window 0 = every episode's seed book")
     p.add_argument("--market-configs", default=None, metavar="FILE.json", help="per-market parameters: a JSON list of override dicts, market m runs entry m %% len(list) "
                                                                              f"(market_params.PER_MARKET_KEYS; a max_step there may not exceed {cap})")
 
@@ -872,6 +875,10 @@ def main(argv=None, parse_only=False):
         args.legacy = True
     if args.legacy and (args.checkpoint_dir or args.restore):
         raise SystemExit("--checkpoint-dir / --restore need the fused loop")
+    if args.order_schedule:
+        if args.legacy:
+            raise SystemExit("--order-schedule needs the fused loop")
+        env.load_order_schedule(args.order_schedule)
     if args.save and args.legacy:
         raise SystemExit("--save needs the fused loop (the legacy loop's network is a PyTorch module)")
     if args.legacy:
@@ -889,7 +896,7 @@ def main(argv=None, parse_only=False):
                                       f"4 epochs, 262144-sample minibatches), horizon {args.horizon}, {args.iters} iterations, auto_reset on",
                           "objective": "legacy loop's own" if args.legacy else args.objective, "activation": args.fcnet_activation,
                           "markets": args.markets, "agents": args.agents, "horizon": args.horizon, "iters": args.iters, "env_groups": p_groups,
-                          "trained_slots": args.trained_slots, "opponents": args.opponent,
+                          "trained_slots": args.trained_slots, "opponents": args.opponent, "order_schedule": args.order_schedule,
                           "loop": "legacy (PyTorch network)" if args.legacy else (f"fused: hand-written bf16 MFMA network (csrc/cda_mlp.hip), {args.chains} rollout chains; GAE straight into the sample records (one launch); "
                                                                                       "a minibatch step = {gather + forward + loss + backward in one launch, weight gradients, reduce, Adam}"),
                           "hip_graphs": "none" if args.no_graphs else ("one graph per rollout step (policy + env step + buffer writes), one per minibatch step of the update"

@@ -21,6 +21,8 @@ ACTION_KEYS = ("category", "size_mean", "size_sigma", "price", "price_offset")
 
 # what set_scripted keeps: the two resident device tables (slot_script i32 [N, A], profiles u8 [n, 64]), the Profile objects, the draws' keys, and the slot table on the host
 AttachedScripts = collections.namedtuple("AttachedScripts", "slot_script profiles_dev profiles seed market_index_base slots_host")
+# what set_order_schedule keeps: the three resident device tables (sched_of i32 [N], step_offsets i64 [n_sched, S + 1], msgs u8 [total, 16]), the host form and the digest
+AttachedSchedule = collections.namedtuple("AttachedSchedule", "sched_of step_offsets msgs packed sched_of_host loop clear_step_counters digest")
 
 
 class CDAVecEnv:
@@ -46,6 +48,7 @@ class CDAVecEnv:
         self._tape_cursor = None            # drain_tape's default cursor (i64 [N], device) while the tape is on
         self.script_epoch = 0               # bumped by set_scripted / clear_scripted: graphs captured on this env's rollout chains hold the scripted launches (or none) of then
         self._script = None                 # set_scripted: an AttachedScripts (None while nothing is attached)
+        self._schedule = None               # set_order_schedule: an AttachedSchedule (None while nothing is attached)
         self.num_agents = self.cfg_struct.num_agents
         self.n_hist = self.cfg_struct.n_hist
         self.obs_dim = self.n_hist * K.SNAPSHOT_DIM
@@ -416,6 +419,9 @@ class CDAVecEnv:
         counter-based sampler of include/cda_random_agents.h) play up to `n_steps` steps, each market stopping at its own
         episode end.  Returns (obs f32[N,obs_dim], episode_return f64[N,A], terminated, truncated, steps_taken i32[N]);
         bit-identical to `n_steps` calls of step() on `random_actions(t)`."""
+        if self._schedule is not None:
+            raise CDAError("run_random() cannot honour the attached order schedule (the whole episode runs inside one launch; cda_run_random answers "
+                           "CDA_ERR_UNSUPPORTED): step the env, or clear_order_schedule() first")
         self.host_epoch += 1
         N, A, dev = self.n_markets, self.num_agents, self.device
         self.join()
@@ -830,6 +836,86 @@ class CDAVecEnv:
         msgs = torch.from_numpy(one.view(np.uint8).reshape(-1, 16)).to(self.device).repeat(n, 1)
         offsets = torch.arange(n + 1, dtype=torch.int64, device=self.device) * L
         return self.submit_orders(offsets=offsets, msgs=msgs, first_market=first, n_markets=n, clear_step_counters=True, max_len=L)
+
+    # ------------------------------------------------------------------ order schedules: per-step order flow played inside steps and rollouts (orders.py)
+    @property
+    def order_schedule(self):
+        """whether an order schedule is attached"""
+        return self._schedule is not None
+
+    @property
+    def schedule_epoch(self):
+        """moved by every set_order_schedule / clear_order_schedule (cda_schedule_epoch): graphs captured on this env's step launches hold the schedule launch (or
+        none) and the tables of the epoch they were captured under"""
+        return int(lib().cda_schedule_epoch(self._h))
+
+    def order_schedule_digest(self):
+        """orders.schedule_digest of the attached schedule, None while nothing is attached (what a training checkpoint keeps)"""
+        return self._schedule.digest if self._schedule is not None else None
+
+    def set_order_schedule(self, schedule, market_schedule=None, loop=False, clear_step_counters=False):
+        """Attach an order schedule (include/cda.h cda_schedule_attach): from now on every step - step(), run_scripted(), the rollout / evaluation / league chains -
+        first plays, per market, the window of the market's current t_step into it, through the matching code of place_order(), then steps.  Window 0 is the
+        seed book of every episode (the device-side auto reset included), windows 1 .. are background flow ahead of the step's own orders.
+        schedule: rows[r][t] = the messages of step t of row r (orders.pack_schedule), or an orders.PackedSchedule.
+        market_schedule: int [N], market i plays row market_schedule[i], -1 = none; None = market i plays row i % n_sched.
+        loop: t_step wraps around the schedule's S windows; without it a step beyond them plays nothing.
+        clear_step_counters: clear every account's step counters behind a played window (as submit_orders); off, a scheduled fill reaches the step's reward
+        terms like any fill inside the step.
+        A schedule replaces the one attached; the counters (order_schedule_counts) restart.  While attached run_random() raises and the one-launch policy
+        step is off."""
+        from . import orders as OR
+        packed = schedule if isinstance(schedule, OR.PackedSchedule) else OR.pack_schedule(schedule)
+        N = self.n_markets
+        so = (np.arange(N) % packed.n_sched).astype(np.int32) if market_schedule is None else np.ascontiguousarray(np.asarray(
+            market_schedule.detach().cpu().numpy() if hasattr(market_schedule, "detach") else market_schedule).astype(np.int64))
+        if so.shape != (N,):
+            raise ValueError(f"market_schedule must have shape {(N,)}, got {so.shape}")
+        why = OR.schedule_check(packed, so, self.num_agents)
+        if why is not None:
+            raise ValueError(f"not an order schedule: {why}")
+        so = so.astype(np.int32)
+        so_t = torch.from_numpy(so).to(self.device)
+        off_t = torch.from_numpy(packed.step_offsets).to(self.device)
+        total = len(packed.msgs)
+        msg_t = torch.from_numpy(np.ascontiguousarray(packed.msgs).view(np.uint8).reshape(-1, 16).copy()).to(self.device) if total else torch.zeros((1, 16), dtype=torch.uint8, device=self.device)
+        flags = (OR.SCHEDULE_LOOP if loop else 0) | (OR.SCHEDULE_CLEAR_STEP_COUNTERS if clear_step_counters else 0)
+        self.sync()
+        with torch.cuda.device(self.device):
+            check(lib().cda_schedule_attach(self._h, so_t.data_ptr(), off_t.data_ptr(), packed.n_sched, packed.n_steps, msg_t.data_ptr(), total, flags), "cda_schedule_attach")
+        self._schedule = AttachedSchedule(so_t, off_t, msg_t, packed, so, bool(loop), bool(clear_step_counters), OR.schedule_digest(packed, so, loop, clear_step_counters))
+
+    def load_order_schedule(self, path):
+        """set_order_schedule from a file of orders.save_schedule (the command lines' --order-schedule): the file's row table - by default market i plays row
+        i % n_sched - and flags"""
+        from . import orders as OR
+        packed, ms, loop, clear = OR.load_schedule(path)
+        if ms is not None and len(ms) != self.n_markets:
+            raise ValueError(f"{path}: market_schedule names rows for {len(ms)} markets, the env has {self.n_markets}")
+        self.set_order_schedule(packed, market_schedule=ms, loop=loop, clear_step_counters=clear)
+
+    def clear_order_schedule(self):
+        self.sync()
+        check(lib().cda_schedule_detach(self._h), "cda_schedule_detach")
+        self._schedule = None
+
+    def order_schedule_counts(self, first_market=0, n_markets=None):
+        """i64 [n, 4] (device) = messages done, rejected, invalid, fills the attached schedule played into every market since it was attached (cda_schedule_counts)"""
+        first, n = self._market_range("order_schedule_counts", first_market, n_markets)
+        self.join()
+        out = torch.empty((n, 4), dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            check(lib().cda_schedule_counts(self._h, first, n, out.data_ptr(), self._stream()), "cda_schedule_counts")
+        return out
+
+    def play_order_schedule(self, first_market=0, n_markets=None):
+        """The launch every step issues first, on its own (cda_schedule_play): every market's window of its current t_step, on the caller's stream; nothing
+        attached: nothing happens.  For tests and custom loops - a step() behind it plays the same window again."""
+        first, n = self._market_range("play_order_schedule", first_market, n_markets)
+        self.host_epoch += 1
+        self.join()
+        with torch.cuda.device(self.device):
+            check(lib().cda_schedule_play(self._h, first, n, self._stream()), "cda_schedule_play")
 
     # ------------------------------------------------------------------ scripted opponents: rule-based agents on the device (scripted.py states the laws)
     @property

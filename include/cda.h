@@ -750,6 +750,52 @@ int cda_submit_orders_window(cda_env* env, int32_t first_market, int32_t n_marke
 int cda_order_msgs_check_host(const cda_env* env, const cda_order_msg* msgs_host, int64_t n, int64_t* first_bad_out);
 int cda_order_msgs_check_agents_host(int32_t num_agents, const cda_order_msg* msgs_host, int64_t n, int64_t* first_bad_out);
 
+/* ---- order schedules: per-step order flow played inside steps and rollouts --------------------------------------------------------------------
+ * An order schedule is attached to the env.  It holds n_sched rows of n_steps windows each: step_offsets_dev, int64 [n_sched][n_steps + 1], indexes one
+ * array of cda_order_msg - row r owns, for step t of an episode, the messages msgs_dev[off[r][t] .. off[r][t + 1]); sched_of_dev, int32 [n_markets], names
+ * every market's row (-1 = none; many markets may share a row).  All three live in caller-owned device memory that must stay valid, and unchanged, while
+ * attached.  Every step entry point (cda_step, cda_step_range, cda_step_range_capture, cda_step_groups, cda_step_groups_handback - hence the rollout,
+ * evaluation and league chains of include/cda_mlp.h, which step through them) first plays, on the same stream, the window of each market's current t_step,
+ * then runs the step: window 0 is the seed book of every episode - the in-kernel auto reset included -, windows 1 .. are background flow that arrives
+ * before the step's own orders execute (the agents decided on the state at the end of the previous step).
+ *   which window   for market i of the range nothing plays when no schedule is attached, sched_of[i] < 0, or the market's episode is over (all agents
+ *                  done, or t_step >= its max_step).  Otherwise t = t_step[i]; with CDA_SCHEDULE_LOOP t %= n_steps, without it t >= n_steps plays nothing.
+ *   the play       the window's messages run in order under exactly the contract of cda_submit_orders above: each valid message equals one
+ *                  cda_place_order / cda_mark_to_mkt call, invalid ones are skipped and counted, no observation frame is pushed, t_step does not move,
+ *                  the episode-metric tallies are not touched, the cached level aggregation is invalidated when an order was placed, and a market whose
+ *                  window is empty or holds nothing valid is neither loaded nor stored - its record stays byte-identical.  On a tape-enabled env the
+ *                  tape-writing sibling runs.  The trader of a message is an ordinary agent slot (NAV conservation stays exact).
+ *   flags          CDA_SCHEDULE_LOOP (above); CDA_SCHEDULE_CLEAR_STEP_COUNTERS = CDA_ORDERS_CLEAR_STEP_COUNTERS behind every played window - off, a
+ *                  scheduled fill reaches the step's reward terms like any fill inside the step.
+ *   cda_schedule_attach   reads both index tables back and vets them before the env changes (cda_schedule_check_host's rule; pointers aligned 4 / 8 /
+ *                  16; no unknown flag bits): one fault returns CDA_ERR_INVALID and changes nothing.  It waits for the device to be idle, zeroes the
+ *                  counters and moves cda_schedule_epoch; so does cda_schedule_detach (a graph captured under another epoch holds stale launches).
+ *   cda_schedule_counts   the env-owned cumulative table, int64 [n_markets][4] = messages done, rejected, invalid, fills since the attach, rows
+ *                  [first, first + n) copied to out_dev on `stream` (a market that never played a window: zeros).
+ *   cda_schedule_play     the launch the step entry points issue first, on its own: a no-op while nothing is attached.  For tests and custom loops - a
+ *                  caller who ALSO steps through the entry points plays the window twice.
+ *   cda_schedule_check_host   the attach rule on host data, no device: CDA_OK, CDA_ERR_INVALID for a NULL / non-positive argument, or which table is
+ *                  wrong - CDA_SCHEDULE_BAD_SCHED_OF (a value outside -1 .. n_sched-1), _BAD_START (a row starts below 0), _BAD_ROW (a row decreases),
+ *                  _BAD_END (a row ends beyond n_msgs).
+ * While a schedule is attached cda_policy_step_supported answers 0 (the chains take the two launches, as with scripted opponents) and cda_run_random
+ * returns CDA_ERR_UNSUPPORTED.  Snapshot blobs carry no schedule: restoring keeps the target env's attachment, and t_step - in the blob - puts a restored
+ * market at the right window. */
+#define CDA_SCHEDULE_LOOP 1u
+#define CDA_SCHEDULE_CLEAR_STEP_COUNTERS 2u
+#define CDA_SCHEDULE_BAD_SCHED_OF 1
+#define CDA_SCHEDULE_BAD_START    2
+#define CDA_SCHEDULE_BAD_ROW      3
+#define CDA_SCHEDULE_BAD_END      4
+int cda_schedule_attach(cda_env* env, const int32_t* sched_of_dev, const int64_t* step_offsets_dev, int32_t n_sched, int32_t n_steps,
+                        const cda_order_msg* msgs_dev, int64_t n_msgs, uint32_t flags);
+int cda_schedule_detach(cda_env* env);
+int cda_schedule_attached(const cda_env* env);
+int64_t cda_schedule_epoch(const cda_env* env);
+int cda_schedule_counts(cda_env* env, int32_t first_market, int32_t n_markets, int64_t* out_dev, void* stream);
+int cda_schedule_play(cda_env* env, int32_t first_market, int32_t n_markets, void* stream);
+int cda_schedule_check_host(int32_t num_agents, int32_t n_markets, const int32_t* sched_of, const int64_t* step_offsets, int32_t n_sched, int32_t n_steps,
+                            int64_t n_msgs);
+
 /* ---- per-market parameters: many configurations in one env ----------------------------------------------------------------------------
  * Every market reads the fields below from a row of its own (a device table every env has; cda_create fills each row from the config).  The
  * config's other fields - num_agents, n_hist, book_capacity, book_spill, auto_reset - set shapes, memory and kernel choice and hold for the
