@@ -625,6 +625,16 @@ __global__ void k_selftest_rng(uint64_t seed, int lo, int hi, int n_steps, int n
 // ==========================================================================================
 // scripted opponents (include/cda_scripted_agents.h, csrc/cda_scripted.inc): what cda_scripted_attach keeps - caller-owned device memory, as slot_net is
 struct ScriptArgs { const int32_t* slot; const cda_script_profile* profiles; int32_t n_profiles; int32_t pad; uint64_t seed, market_base; int64_t epoch; };
+// the quote tape (include/cda.h cda_quotes_*, csrc/cda_quotes.inc): a market's meta row - eight int32 words - and what cda_quotes_enable keeps
+struct QuoteMeta {               // 32 B per market
+    int64_t n_total;             // records since the quotes were enabled (the ring slot of record j is j % capacity)
+    int32_t n_episode;           // records of the current episode: the steps first .. first + n_episode - 1
+    int32_t n_prev;              // records of the episode before it
+    int32_t first, prev_first;   // the step of each episode's first record (0 unless a restore moved the clock)
+    int32_t gap;                 // records of abandoned episode fragments between the previous episode and the current one
+    int32_t flags;               // bit 0: the current episode's head was never recorded (partial); bit 1: the previous one's
+};
+struct QuoteArgs { uint4* ring; QuoteMeta* meta; uint32_t cap; uint32_t pad; };      // ring: uint4[n_markets][cap][2]
 struct cda_env {
     Params P;
     int device;
@@ -643,7 +653,11 @@ struct cda_env {
     ScriptArgs script;       // cda_scripted_attach: the caller's resident slot table and profiles (slot == NULL: nothing attached - cda_scripted_actions launches nothing)
     cda::SchedArgs sched;    // cda_schedule_attach: the caller's resident order schedule and the env's own counters table (sched_of == NULL: nothing attached - no launch)
     int64_t sched_epoch;     // moved by every cda_schedule_attach / cda_schedule_detach
+    QuoteArgs quotes;        // cda_quotes_enable: the quote tape's rings and meta rows (ring == NULL: off - no launch)
 };
+// csrc/cda_quotes.inc (included at the end): the top of the book of [first, first + n), recorded on `stream` ahead of a step; a no-op while quotes are off
+static int quotes_record(cda_env* e, int32_t first, int32_t n, hipStream_t stream);
+static void quotes_free(cda_env* e);
 // csrc/cda_schedule.inc (included at the end): the attached order schedule's windows of [first, first + n), queued on `stream` ahead of a step; a no-op while none is attached
 static int schedule_play(cda_env* e, int32_t first, int32_t n, hipStream_t stream);
 static void schedule_free(cda_env* e);
@@ -857,6 +871,7 @@ int cda_destroy(cda_env* e) {
     if (e->snap_flag) (void)hipFree(e->snap_flag);
     tape_free(e);
     schedule_free(e);
+    quotes_free(e);
     if (e->rows) (void)hipFree(e->rows);
     free(e->rows_host);
     free(e);
@@ -911,6 +926,7 @@ int cda_reset(cda_env* e, const uint64_t* seeds, const uint8_t* mask, float* obs
 // one launch of k_step (+ the auto-reset pass) over [first, first + n) on `stream`; arguments validated by the callers
 static int launch_step(cda_env* e, int32_t first, int32_t n, const StepArgs& S0, hipStream_t stream) {
     if (e->sched.sched_of) { const int rcs = schedule_play(e, first, n, stream); if (rcs) return rcs; }      // an attached order schedule: the markets' windows first
+    if (e->quotes.ring) { const int rcq = quotes_record(e, first, n, stream); if (rcq) return rcq; }          // quotes on: the book as this step's orders meet it
     const size_t smem = smem_for(e, CDA_WPB) + ZIG_LDS_BYTES;
     const bool tally = e->P.lay.ep_on != 0;               // episode metrics on: the instances that tally (their code is not even in the others)
 #define CDA_LAUNCH_STEP(ns) do { \
@@ -1031,7 +1047,7 @@ static int grant_policy_step_lds(const cda_env* e) {
 int cda_policy_step_supported(const cda_env* e) {
     if (!e) return 0;
     const int lds = e->cap == 256 ? policy_step_lds(e) : 0;
-    return lds > 0 && lds <= 160 * 1024 && e->P.cfg.num_agents <= 8 && !e->handback && !e->tape.ring && !e->script.slot && !e->sched.sched_of;      // (no k_policy_step instance writes the trade tape, asks a scripted law or plays an order schedule)
+    return lds > 0 && lds <= 160 * 1024 && e->P.cfg.num_agents <= 8 && !e->handback && !e->tape.ring && !e->script.slot && !e->sched.sched_of && !e->quotes.ring;      // (no k_policy_step instance writes the trade tape, asks a scripted law, plays an order schedule or records quotes)
 }
 // ... and whether it pays: every workgroup of k_policy_step streams the whole network for its sixteen rows, so the one launch wins while all of the env's
 // workgroups are resident at once (N <= 16 x CUs: 4096 markets on an MI355X - policy in the loop 278 -> 301-308 M at 4096 x 4) and loses to the batched policy
@@ -1178,6 +1194,7 @@ int cda_run_random(cda_env* e, int32_t n_steps, uint64_t action_seed, uint64_t m
                    int32_t* steps_taken_out, void* stream) {
     if (!e || n_steps < 0) return CDA_ERR_INVALID;
     if (e->sched.sched_of) return CDA_ERR_UNSUPPORTED;               // (k_run_random steps inside one launch: it cannot play an order schedule between its steps)
+    if (e->quotes.ring) return CDA_ERR_UNSUPPORTED;                  // (... nor record the quotes between them)
     HIPCHK(hipSetDevice(e->device));
     RunArgs R;
     R.n_steps = n_steps; R.seed = action_seed; R.market_base = market_index_base;
@@ -1625,3 +1642,5 @@ int64_t cda_state_bytes_per_market(const cda_env* e) { return e ? (int64_t)e->P.
 #include "cda_orders.inc"
 // order schedules (cda_schedule_*): per market and per step of its episode a window of messages, played ahead of every step through the same walk
 #include "cda_schedule.inc"
+// the quote tape (cda_quotes_*, cda_quote_*, cda_tape_spreads): the top of the book per step, recorded ahead of every step, and the reductions over it
+#include "cda_quotes.inc"

@@ -472,6 +472,25 @@ class CDAEnv(_DictSurface):
         """The current episode's fills as the reference's env.LOB.tape holds them: a list of transaction_record dicts, newest last (tape.to_reference_records)."""
         return _tape_of(self._vec, 0)
 
+    # -- the quote tape (the top of the book ahead of every step): off by default -----------
+    def enable_quotes(self, capacity=1024):
+        """Record the top of the book ahead of every step on the device from now on (CDAVecEnv.enable_quotes); `capacity` bounds the steps `quotes` can return."""
+        self._vec.enable_quotes(capacity)
+
+    def disable_quotes(self):
+        self._vec.disable_quotes()
+
+    @property
+    def quotes(self):
+        """The current episode's quotes, one per step taken, oldest first: a structured array of quotes.QUOTE_DTYPE (step, flags, bid_price, ask_price,
+        bid_volume, ask_volume, bid_orders, ask_orders) - the book as each step's orders met it.  `quotes_of("previous")`: the episode before."""
+        return self.quotes_of("current")
+
+    def quotes_of(self, episode="current"):
+        if not self._vec.quotes_enabled:
+            raise RuntimeError("the quote tape is off (it is opt-in): call enable_quotes() before the episode whose quotes you want to read")
+        return self._vec.quote_episode(0, episode)
+
     def tape_bars(self, bar_steps, n_bars=None, episode="current"):
         """Price / volume bars of this market's current (or previous) episode, reduced on the device (CDAVecEnv.tape_bars): a structured array of tape.BAR_DTYPE,
         one element per bar of `bar_steps` env steps."""

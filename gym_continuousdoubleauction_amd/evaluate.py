@@ -12,7 +12,7 @@ the greedy chains); mode="sample" runs the same loop on the sampling kernels.
 
 CLI: python -m gym_continuousdoubleauction_amd.evaluate --policy P [--opponent random|FILE ...] --markets --agents --max-step --episodes --trained-slots
      (a scripted opponent: pass | maker | taker | imbalance | NAME:key=value,...)
-     [--sample] --seed --out JSON [--tape FILE.npz [--exec-report K[,K...]]]
+     [--sample] --seed --out JSON [--tape FILE.npz [--exec-report K[,K...]] [--spread-report K[,K...]]] [--quotes FILE.npz]
 """
 import argparse
 import dataclasses
@@ -115,8 +115,30 @@ def _execution_report(env, horizons, module_of, names, episode0, keep):
     return out
 
 
+def _spread_report(env, horizons, module_of, names, episode0, keep):
+    """evaluate(spread_horizons=...): the spread tables (CDAVecEnv.tape_spreads) of every market's previous episode, folded per module; a market counts as in
+    _execution_report."""
+    from .quotes import SPREAD_FIELDS, spread_summary, spreads_by_module
+    spreads, info = env.tape_spreads(horizons, episode="previous")
+    counted = env.tape_counts()["episode"].to(torch.int64) > torch.from_numpy(np.asarray(episode0)).to(env.device, torch.int64)
+    n_mod = len(names)
+    slot_module = torch.where(counted[:, None], module_of.to(torch.int64), torch.full_like(module_of, n_mod, dtype=torch.int64))      # row n_mod: not counted
+    sp_h, info_h, sel = spreads_by_module(spreads, slot_module, n_mod + 1).cpu().numpy(), info.cpu().numpy(), counted.cpu().numpy()
+    out = {"about": {"horizons": list(horizons), "episode": "previous", "markets": int(sel.sum()), "tape_records": int(info_h[sel, 0].sum()),
+                     "tape_records_lost": int(info_h[sel, 1].sum()), "quotes_lost": int(info_h[sel, 2].sum()), "partial_markets": int((info_h[sel, 3] != 0).sum()),
+                     "spread_words": list(SPREAD_FIELDS)},
+           "modules": {}}
+    for i, name in enumerate(names):
+        block = spread_summary(sp_h[i], horizons=horizons)
+        block["rows"] = sp_h[i].tolist()
+        out["modules"][name] = block
+    if keep is not None:
+        keep["spread_tables"] = {"spreads": spreads.cpu().numpy(), "info": info_h, "counted": sel}
+    return out
+
+
 def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="greedy", seed=0, groups=None, keep=None, tape=None, tape_capacity=4096,
-             exec_horizons=None):
+             exec_horizons=None, quotes=None, spread_horizons=None):
     """Play `policy` (a FusedPolicy or a policy file) on `env` (a CDAVecEnv with auto_reset) for episodes * max_step steps; return per-module results.
     opponents: None = self-play; else a list of "random", FusedPolicy objects, policy files or scripted opponents - "pass", "maker", "taker", "imbalance",
     "NAME:key=value,..." or a scripted.Profile (rule-based agents on the device: their slots carry LEAGUE_RANDOM in slot_net and their profile in the env's slot_script,
@@ -135,7 +157,13 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
     horizons (CDAVecEnv.tape_exec on the device, folded per module by tape.exec_by_module, read through tape.exec_summary, the integer rows beside the ratios) -
     and result["execution"], which says what it covers: the PREVIOUS episode on the tape of every market that completed one, i.e. each market's last finished
     episode, with the records lost to the ring (a tape_capacity below an episode's fills) and the open fills reported, not hidden.  Without it the result is
-    unchanged, key for key."""
+    unchanged, key for key.
+    quotes (a path, optional): record the top of the book ahead of every step of the evaluated episodes on the device (CDAVecEnv.enable_quotes, two episodes of
+    capacity) and save every market's last finished episode as an .npz (quotes.save): records i32 [N, max_step, 8] with `counts`, `info` (quote_series' rows), the
+    slot -> module map `modules` and `module_names`.  The env's quote tape must be OFF (ValueError otherwise); it is off again afterwards.
+    spread_horizons (step counts, optional; needs `tape`; the quotes are recorded whether or not `quotes` names a file): add a "spreads" block to every module -
+    effective and realised half-spread and impact per share, by role (CDAVecEnv.tape_spreads, folded by quotes.spreads_by_module, read through
+    quotes.spread_summary, the integer rows beside the ratios) - and result["spreads"], which says what it covers, as the execution report does."""
     from .mlp import LEAGUE_RANDOM, FusedPolicy, PolicyBank, RolloutChains, read_policy
     if mode not in ("greedy", "sample"):
         raise ValueError(f"mode must be 'greedy' or 'sample' (got {mode!r})")
@@ -146,6 +174,15 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
         exec_horizons = _horizons(exec_horizons)
         if tape is None:
             raise ValueError("evaluate(exec_horizons=...) reads the trade tape of the evaluated episodes: pass tape=FILE.npz as well (the tape is off by default)")
+    if spread_horizons is not None:
+        from .quotes import _horizons as _spread_hz
+        spread_horizons = _spread_hz(spread_horizons)
+        if tape is None:
+            raise ValueError("evaluate(spread_horizons=...) joins the trade tape of the evaluated episodes to their quotes: pass tape=FILE.npz as well")
+    with_quotes = quotes is not None or spread_horizons is not None
+    if with_quotes and env.quotes_enabled:
+        raise ValueError("evaluate(quotes=... / spread_horizons=...) needs an env whose quote tape is off: it enables one of its own for the evaluated episodes "
+                         "(disable_quotes() first)")
     dev, N, A = env.device, env.n_markets, env.num_agents
     pol = _as_policy(policy, dev)
     opp = None if opponents is None else list(opponents)
@@ -183,6 +220,8 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
                          "drain the running tape yourself with drain_tape(cursor=...))")
     if tape is not None:
         env.enable_tape(tape_capacity)                                  # (likewise: the chains' graphs hold the tape-writing step instances)
+    if with_quotes:
+        env.enable_quotes(min(1 << 20, 2 * max(1, int(env.max_step))))  # (likewise: the recorder's launch; the finished episode and the running one both fit)
     tape_parts, tape_dropped = [], np.zeros(N, np.int64)
     try:
         if opp is None:
@@ -240,6 +279,13 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
         execution = None
         if exec_horizons is not None:
             execution = _execution_report(env, exec_horizons, module_of, names, tape_ep0, keep)
+        spread_rep = None
+        if spread_horizons is not None:
+            spread_rep = _spread_report(env, spread_horizons, module_of, names, tape_ep0, keep)
+        if quotes is not None:
+            from .quotes import save as save_quotes
+            rec, cnt, qinfo = env.quote_series(int(env.max_step), episode="previous")
+            save_quotes(quotes, rec, counts=cnt, info=qinfo, modules=modules.astype(np.int32), module_names=np.array(names))
         if tape is not None:
             from .tape import save_tape
             rows = np.concatenate([p[0] for p in tape_parts]) if tape_parts else np.zeros((0, 8), np.int32)
@@ -251,6 +297,8 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
         env.enable_episode_metrics(prev_metrics)
         if tape is not None:
             env.disable_tape()
+        if with_quotes and env.quotes_enabled:
+            env.disable_quotes()
         if scripts and env.scripted:
             env.clear_scripted()
     table_h, env_h = table.cpu().numpy(), env_row.cpu().numpy()
@@ -275,6 +323,10 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
         result["execution"] = execution["about"]
         for name in names:
             mods[name]["execution"] = execution["modules"][name]
+    if spread_rep is not None:
+        result["spreads"] = spread_rep["about"]
+        for name in names:
+            mods[name]["spreads"] = spread_rep["modules"][name]
     if keep is not None:
         keep["chains"], keep["modules"], keep["tables"] = chains, modules, (table_h, env_h)
         keep["actions"] = {key: torch.cat([a[key] for a in acts]) for key in acts[0]}
@@ -296,6 +348,9 @@ def main(argv=None):
     p.add_argument("--tape", default=None, metavar="FILE.npz", help="record every fill of the evaluated episodes (the trade tape) and save the records with their market, episode and module ids")
     p.add_argument("--exec-report", default=None, metavar="K[,K...]", help="with --tape: add per-module inventory, turnover and mark-outs at these step horizons, reduced "
                    "on the device from every market's last finished episode")
+    p.add_argument("--quotes", default=None, metavar="FILE.npz", help="record the top of the book ahead of every step (the quote tape) and save every market's last finished episode")
+    p.add_argument("--spread-report", default=None, metavar="K[,K...]", help="with --tape: add per-module effective spread, realised spread and impact per share at these step "
+                   "horizons, by role - the trade tape joined to the quotes on the device")
     p.add_argument("--order-schedule", default=None, metavar="FILE.npz", help="attach this order schedule (orders.save_schedule) to the env: per-step order flow played ahead "
                    "of every step of the evaluated episodes")
     args = p.parse_args(argv)
@@ -307,6 +362,14 @@ def main(argv=None):
             exec_horizons = [int(k) for k in args.exec_report.split(",")]
         except ValueError:
             p.error(f"--exec-report takes step counts separated by commas, got {args.exec_report!r}")
+    spread_horizons = None
+    if args.spread_report is not None:
+        if args.tape is None:
+            p.error("--spread-report joins the trade tape to the quotes: give --tape FILE.npz as well")
+        try:
+            spread_horizons = [int(k) for k in args.spread_report.split(",")]
+        except ValueError:
+            p.error(f"--spread-report takes step counts separated by commas, got {args.spread_report!r}")
     from .mlp import layout_of_params, read_policy
     from .vec_env import CDAVecEnv
     n_hist = layout_of_params(read_policy(args.policy).numel()).hist             # (the hidden activation comes with the file: load_policy)
@@ -316,7 +379,8 @@ def main(argv=None):
         if args.order_schedule:
             env.load_order_schedule(args.order_schedule)
         res = evaluate(env, args.policy, opponents=args.opponent, trained_slots=args.trained_slots, episodes=args.episodes,
-                       mode="sample" if args.sample else "greedy", seed=args.seed, tape=args.tape, exec_horizons=exec_horizons)
+                       mode="sample" if args.sample else "greedy", seed=args.seed, tape=args.tape, exec_horizons=exec_horizons,
+                       quotes=args.quotes, spread_horizons=spread_horizons)
     finally:
         env.close()
     res.pop("summary")

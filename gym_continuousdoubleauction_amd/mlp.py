@@ -689,6 +689,8 @@ class RolloutChains:
         self._graph_script_epoch = getattr(self.env, "script_epoch", 0)
         # ... and the order schedule's launch and tables (or none) as attached now (CDAVecEnv.set_order_schedule / clear_order_schedule)
         self._graph_schedule_epoch = getattr(self.env, "schedule_epoch", 0)
+        # ... and the quote recorder's launch and ring (or none) as enabled now (CDAVecEnv.enable_quotes / disable_quotes)
+        self._graph_quote_epoch = getattr(self.env, "quote_epoch", 0)
 
     def run(self):
         """one rollout of `horizon` steps; returns the buffer dict (views stay valid; the next run() overwrites them)"""
@@ -703,6 +705,9 @@ class RolloutChains:
         if self.graphs is not None and self._graph_schedule_epoch != getattr(self.env, "schedule_epoch", 0):
             raise RuntimeError("the env's order schedule was attached, replaced or detached after this RolloutChains captured its graphs: they would replay the "
                                "launches and tables of the earlier setting - build a new RolloutChains")
+        if self.graphs is not None and self._graph_quote_epoch != getattr(self.env, "quote_epoch", 0):
+            raise RuntimeError("the env's quote tape was enabled or disabled after this RolloutChains captured its graphs: they would replay the recorder's launch "
+                               "and ring of the earlier setting - build a new RolloutChains")
         self._check_scripted_slots()
         if not self._have_obs or self._env_epoch != getattr(self.env, "host_epoch", 0):
             # the very first rollout - and the first one after the markets were reset / stepped from the HOST (env.host_epoch) - starts from the env's own

@@ -46,6 +46,7 @@ class CDAVecEnv:
                                             # their own copy of the observations across calls (mlp.RolloutChains) compare it to know when theirs is stale
         self.tape_epoch = 0                 # bumped by enable_tape / disable_tape: graphs captured on this env's step launches hold the setting they were captured under
         self._tape_cursor = None            # drain_tape's default cursor (i64 [N], device) while the tape is on
+        self.quote_epoch = 0                # bumped by enable_quotes / disable_quotes: captured graphs hold the recorder's launch (or none) of their capture
         self.script_epoch = 0               # bumped by set_scripted / clear_scripted: graphs captured on this env's rollout chains hold the scripted launches (or none) of then
         self._script = None                 # set_scripted: an AttachedScripts (None while nothing is attached)
         self._schedule = None               # set_order_schedule: an AttachedSchedule (None while nothing is attached)
@@ -710,6 +711,111 @@ class CDAVecEnv:
         k = max(1, min(n_ep, self.tape_capacity))
         rec, cnt = self.tape_last(k, int(market), 1)
         return rec[0, :int(cnt[0].item())].cpu().numpy()
+
+    # ------------------------------------------------------------------ the quote tape: the top of the book per step, recorded on the device (quotes.py)
+    @property
+    def quotes_enabled(self):
+        return int(lib().cda_quotes_capacity(self._h)) > 0
+
+    @property
+    def quote_capacity(self):
+        return int(lib().cda_quotes_capacity(self._h))
+
+    def enable_quotes(self, capacity=1024):
+        """From now on every step entry point first records, per market whose episode is not over, the top of the book the step's orders will meet - best price,
+        that level's volume and its order count per side (quotes.QUOTE_DTYPE) - into the market's ring of `capacity` records on the device (include/cda.h
+        cda_quotes_enable), behind an attached order schedule's window and ahead of the step.  Off by default; rings start empty.  While it is on the one-launch
+        policy step is off (rollout chains take their two-launch path) and run_random is refused.  Do not toggle it between the capture and the replay of a graph
+        that holds this env's step launches (mlp.RolloutChains checks)."""
+        capacity = int(capacity)
+        if not 1 <= capacity <= (1 << 20):
+            raise ValueError(f"quote capacity must be in 1 .. {1 << 20} steps, got {capacity}")
+        self.sync()
+        check(lib().cda_quotes_enable(self._h, capacity), "cda_quotes_enable")
+        self.quote_epoch += 1                                     # (captured graphs of this env's step launches are stale from here on)
+
+    def disable_quotes(self):
+        self.sync()
+        check(lib().cda_quotes_disable(self._h), "cda_quotes_disable")
+        self.quote_epoch += 1
+
+    def _need_quotes(self, what):
+        if not self.quotes_enabled:
+            raise RuntimeError(f"{what} needs the quote tape: call enable_quotes() first (it is off by default)")
+
+    def quote_meta(self, first_market=0, n_markets=None):
+        """Every market's meta row as the readers see it - rolled to the market's clock by the episode rule (quotes.roll) - i32 [n, 8], a device tensor;
+        quotes.meta_from_words names the words, quotes.span says what the ring holds of either episode."""
+        self._need_quotes("quote_meta()")
+        first, n = self._market_range("quote_meta", first_market, n_markets)
+        self.join()
+        with torch.cuda.device(self.device):
+            out = torch.empty((n, 8), dtype=torch.int32, device=self.device)
+            check(lib().cda_quote_meta(self._h, first, n, out.data_ptr(), self._stream()), "cda_quote_meta")
+        return out
+
+    def quote_series(self, k=None, episode="current", first_market=0, n_markets=None):
+        """The held quotes of one remembered episode, oldest first (include/cda.h cda_quote_series): (records i32 [n, k, 8] - quotes.QUOTE_DTYPE rows; rows beyond
+        the count are zero -, counts i32 [n], info i32 [n, 4] = records returned, records of the episode's head the ring had overwritten, step of
+        the first returned record, partial flag), device tensors.  An episode longer than k returns its LAST k records.  k defaults to the
+        smaller of the ring's capacity and the largest max_step.  episode: "current", or "previous" = the episode that ended at the market's last reset."""
+        self._need_quotes("quote_series()")
+        first, n = self._market_range("quote_series", first_market, n_markets)
+        which = self._tape_which(episode)
+        if k is None:
+            top = int(self.market_rows()["max_step"].max()) if self.per_market else int(self.max_step)
+            k = max(1, min(self.quote_capacity, top))
+        if int(k) < 1:
+            raise ValueError(f"quote_series: k must be >= 1, got {k}")
+        self.join()
+        with torch.cuda.device(self.device):
+            rec = torch.empty((n, int(k), K.QUOTE_WORDS), dtype=torch.int32, device=self.device)
+            cnt = torch.empty(n, dtype=torch.int32, device=self.device)
+            info = torch.empty((n, 4), dtype=torch.int32, device=self.device)
+            check(lib().cda_quote_series(self._h, first, n, which, int(k), rec.data_ptr(), cnt.data_ptr(), info.data_ptr(), self._stream()), "cda_quote_series")
+        return rec, cnt, info
+
+    def quote_stats(self, episode="current", first_market=0, n_markets=None):
+        """The statistics of one remembered episode's held quotes, reduced on the device in one launch (include/cda.h cda_quote_stats; quotes.stats_from_quotes is
+        its specification, word for word): (stats i64 [n, 16] - quotes.STAT_FIELDS -, info i32 [n, 4] = records aggregated, records lost to the ring, step of the
+        first held record, partial flag), device tensors.  quotes.stats_summary turns a row into the ratios."""
+        self._need_quotes("quote_stats()")
+        first, n = self._market_range("quote_stats", first_market, n_markets)
+        which = self._tape_which(episode)
+        self.join()
+        with torch.cuda.device(self.device):
+            stats = torch.empty((n, K.QUOTE_STAT_WORDS), dtype=torch.int64, device=self.device)
+            info = torch.empty((n, 4), dtype=torch.int32, device=self.device)
+            check(lib().cda_quote_stats(self._h, first, n, which, stats.data_ptr(), info.data_ptr(), self._stream()), "cda_quote_stats")
+        return stats, info
+
+    def tape_spreads(self, horizons=(1, 5, 20), episode="current", first_market=0, n_markets=None):
+        """The spread report of one remembered episode: the trade tape joined to the quotes by step, reduced on the device in one launch (include/cda.h
+        cda_tape_spreads; quotes.spreads_from_records is its specification, word for word).  Needs the trade tape AND the quote tape.  -> (spreads i64
+        [n, A, H, 2, 6], info i32 [n, 4]), device tensors: per agent, horizon and role (0 = maker, 1 = taker) quotes.SPREAD_FIELDS - cost_now = the sum of
+        side x (2 price - m2(s)) x quantity, cost_later the same against m2(s + k), the scored quantity and fills, the fills whose s + k lies beyond the last held
+        quote (open) and those whose quote at s or s + k is one-sided or no longer held (unquoted).  info: tape records aggregated, tape records lost, quote records
+        lost, partial bits (1 tape, 2 quotes).  horizons: 1 .. 8 step counts >= 0.  quotes.spread_summary turns a row into the per-share ratios."""
+        from .quotes import SPREAD_WORDS, _horizons
+        self._need_tape("tape_spreads()")
+        self._need_quotes("tape_spreads()")
+        first, n = self._market_range("tape_spreads", first_market, n_markets)
+        which = self._tape_which(episode)
+        hz = _horizons(horizons)
+        self.join()
+        a = self.num_agents
+        with torch.cuda.device(self.device):
+            out = torch.empty((n, a, len(hz), 2, SPREAD_WORDS), dtype=torch.int64, device=self.device)
+            info = torch.empty((n, 4), dtype=torch.int32, device=self.device)
+            check(lib().cda_tape_spreads(self._h, first, n, which, (C.c_int32 * len(hz))(*hz), len(hz), out.data_ptr(), info.data_ptr(), self._stream()),
+                  "cda_tape_spreads")
+        return out, info
+
+    def quote_episode(self, market=0, episode="current"):
+        """One market's held quotes of an episode, oldest first, as a structured host array (quotes.QUOTE_DTYPE)."""
+        from .quotes import as_quotes
+        rec, cnt, _ = self.quote_series(None, episode, int(market), 1)
+        return as_quotes(rec[0, :int(cnt[0].item())].cpu().numpy()).copy()
 
     # ------------------------------------------------------------------ the book report: reductions over the standing book, on the device
     def _book_call(self, name, first_market, n_markets, shape, dtype, *mid):

@@ -633,6 +633,76 @@ int cda_tape_flows(cda_env* env, int32_t first_market, int32_t n_markets, int32_
 int cda_tape_exec(cda_env* env, int32_t first_market, int32_t n_markets, int32_t which, const int32_t* horizons_dev_or_host, int32_t n_horizons,
                   int64_t* stats_out_dev, int64_t* markouts_out_dev, int32_t* info_out_dev, void* stream);
 
+/* ---- quote tape: the top of the book per step, recorded on the device -----------------------------------------------------------------
+ * The trade tape keeps the prints; this keeps the other half of a market-data feed, the quotes over time.  cda_quotes_enable(env, capacity_steps):
+ * from now on every step launch of this env (cda_step*, cda_step_range*, cda_step_groups*, the rollout, evaluation and league chains - everything
+ * that steps) first records, for every market of its range whose episode is not over, one cda_quote_record into the market's ring of
+ * `capacity_steps` records (1 .. CDA_QUOTE_CAP_MAX, any value; memory of its own beside the arena): the recorder's launch runs behind the attached
+ * order schedule's and ahead of the step kernel, so the quote of step t is the book that step t's agent orders meet.  The step kernels are the ones
+ * of an env without quotes; the market record, cda_market_state, state dumps and snapshot blobs do not change.  OFF by default.  While it is on
+ * cda_policy_step_supported answers 0 (rollout chains take their two-launch path) and cda_run_random returns CDA_ERR_UNSUPPORTED (it steps inside
+ * one launch).  Enable / disable are synchronous; do not toggle between the capture and the replay of a graph that holds step launches.
+ * A record: the step index t, flags, and per side the best price, the summed quantity of that price level - followed into the HBM tier of the book
+ * where the level is deeper than the tile - and the number of its orders.  An absent side stores zeros; a volume or count beyond INT32_MAX stores
+ * INT32_MAX and sets CDA_QUOTE_SATURATED.
+ * Episodes.  Per market a meta row of eight int32 words: n_total (64 bits, words 0 - 1: records since enable; record j lies in slot j % capacity),
+ * n_episode (records of the current episode), n_prev, first / prev_first (the step of each episode's first record), gap, flags (bit 0: the current
+ * episode's head was never recorded - partial -, bit 1: the previous one's).  Recorder and readers apply ONE rule, a pure function of the row and
+ * the market's current t_step: t_step == first + n_episode - nothing changes; t_step == 0 with n_episode > 0 - the market was reset: the held
+ * episode becomes the previous one, the current one starts empty; anything else - a snapshot restore moved the clock: the current episode restarts
+ * at t_step, empty and partial (unless t_step is 0), what it held stays in the ring as `gap` records between the previous episode and the new
+ * current one.  The readers apply the rule lazily: right behind a step whose in-kernel auto reset ended an episode, CDA_TAPE_PREVIOUS already names
+ * that episode, as it does on the trade tape.  The ring is never cleared: what it holds of an episode is the episode's intersection with the last
+ * `capacity` records; the readers report the rest as lost.
+ *   cda_quote_meta     the rolled meta rows -> meta_out_dev i32 [n][8].
+ *   cda_quote_series   the held records of the episode `which` (CDA_TAPE_CURRENT / CDA_TAPE_PREVIOUS), oldest first, the last k of them where it
+ *                      holds more -> records_out_dev [n][k] cda_quote_record (device, 16-B aligned; rows beyond the count are zero), counts_out_dev
+ *                      i32 [n] (may be NULL), info_out_dev i32 [n][4] (may be NULL): {records returned, records of the episode's head the ring had
+ *                      overwritten, step of the first returned record, partial}.
+ *   cda_quote_stats    stats_out_dev i64 [n][CDA_QUOTE_STAT_WORDS] over the held records (8-B aligned), in order: steps; two-sided, bid-only,
+ *                      ask-only and empty steps; over the two-sided steps the sum, sum of squares, minimum and maximum of the spread (ask - bid; 0
+ *                      and 0 without any), the sum of m2 = bid + ask (twice the mid, kept integer), the sums of the bid and of the ask best-level
+ *                      volume; over consecutive held steps that are both two-sided their number, the number of m2 changes, the sum of |m2' - m2|
+ *                      and of (m2' - m2)^2 (the realised variance of the mid, times four).  info_out_dev as cda_quote_series (records aggregated
+ *                      first).
+ *   cda_tape_spreads   the trade tape joined to the quotes by step; needs both services on.  spreads_out_dev i64 [n][A][n_horizons][2][6] (8-B
+ *                      aligned; A = num_agents; role 0 = maker = counter_id, 1 = taker = init_id): over the agent's non-self fills in that role - step s,
+ *                      price p, quantity q, side = +1 where the agent bought, -1 where it sold; m2(t) of the quote of step t - {cost_now = sum of
+ *                      side (2p - m2(s)) q, cost_later = sum of side (2p - m2(s + k)) q, qty, fills - all four over the fills whose quotes at s and at
+ *                      s + k are both held and two-sided -, open = fills with s + k beyond the last held quote step (counted, never extrapolated),
+ *                      unquoted = the other fills: a quote at s or s + k that is one-sided or no longer held}.  horizons_host: n_horizons int32 >= 0
+ *                      (host memory, read during the call), 1 <= n_horizons <= CDA_TAPE_MAX_HORIZONS.  info_out_dev i32 [n][4] (may be NULL): {tape
+ *                      records aggregated, tape records lost to its ring, quote records lost to theirs, partial bits: 1 tape, 2 quotes}.  Both
+ *                      episodes are named by `which`; the tape's and the quotes' notion of it agree wherever steps and resets alone moved the clock.
+ * One launch each, a wave per market, exact integers, no atomics on global memory.  A NULL pointer, a range outside the env, a misaligned output,
+ * capacity_steps or k < 1, another `which`, n_horizons outside its bounds or a negative horizon: CDA_ERR_INVALID, nothing is launched.
+ * CDA_ERR_UNSUPPORTED from the readers while a service they need is off. */
+#define CDA_QUOTE_WORDS      8
+#define CDA_QUOTE_CAP_MAX    (1 << 20)
+#define CDA_QUOTE_STAT_WORDS 16
+#define CDA_QUOTE_BID        1
+#define CDA_QUOTE_ASK        2
+#define CDA_QUOTE_SATURATED  4
+typedef struct cda_quote_record {
+    int32_t step;                      /* the env step index t of the episode: the book as step t's orders meet it */
+    int32_t flags;                     /* CDA_QUOTE_BID | CDA_QUOTE_ASK: the side has a best level; CDA_QUOTE_SATURATED */
+    int32_t bid_price;                 /* best prices, as the book holds them; 0 on an absent side */
+    int32_t ask_price;
+    int32_t bid_volume;                /* summed quantity of the best level */
+    int32_t ask_volume;
+    int32_t bid_orders;                /* orders on the best level */
+    int32_t ask_orders;
+} cda_quote_record;
+int cda_quotes_enable(cda_env* env, int64_t capacity_steps);
+int cda_quotes_disable(cda_env* env);
+int64_t cda_quotes_capacity(const cda_env* env);
+int cda_quote_meta(cda_env* env, int32_t first_market, int32_t n_markets, int32_t* meta_out_dev, void* stream);
+int cda_quote_series(cda_env* env, int32_t first_market, int32_t n_markets, int32_t which, int32_t k, void* records_out_dev, int32_t* counts_out_dev,
+                     int32_t* info_out_dev, void* stream);
+int cda_quote_stats(cda_env* env, int32_t first_market, int32_t n_markets, int32_t which, int64_t* stats_out_dev, int32_t* info_out_dev, void* stream);
+int cda_tape_spreads(cda_env* env, int32_t first_market, int32_t n_markets, int32_t which, const int32_t* horizons_host, int32_t n_horizons,
+                     int64_t* spreads_out_dev, int32_t* info_out_dev, void* stream);
+
 /* ---- the book report: reductions over the STANDING book, on the device ------------------------------------------------------------------
  * The resting orders of markets [first_market, first_market + n_markets), read where they lie - the record's tile and, behind it, the HBM spill
  * ring - by one wave per (market, side), one launch each, on `stream`; no call synchronises the host and none writes the arena.  A side is walked
