@@ -48,6 +48,8 @@ LEARNER_SYMBOLS = [
     "cda_mlp_permutation", "cda_ppo_loss32", "cda_ppo_loss_records", "cda_gae_records", "cda_gae_records_bootstrap", "cda_gae_records_slots", "cda_gae_records_league",
     "cda_episode_returns", "cda_league_assign", "cda_league_assign_scripted",
 ]
+# every symbol include/cda_imitate.h declares: behaviour cloning's two kernels (csrc/cda_learner.hip) - like the learner-side ones, ONE copy each, never suffixed
+IMITATE_SYMBOLS = ["cda_bc_records", "cda_bc_loss_records"]
 # the same entry points compiled for other history depths carry the suffix _h<H> (include/cda_mlp.h CDA_MLP_HIST_VARIANTS, csrc/cda_mlp_variant.h)
 MLP_HIST_VARIANTS = (1, 2, 3, 6, 7, 8)
 # ... and compiled for the other hidden activations (RLlib's fcnet_activation; tanh is the unsuffixed default), at every depth including 4, carry the suffix _<act>
@@ -248,6 +250,9 @@ def lib():
     L.cda_episode_returns.argtypes = [vp, vp, vp, i32, i64, i32, vp, vp, vp, vp, vp]
     L.cda_league_assign.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp, vp, vp]
     L.cda_league_assign_scripted.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp]
+    # include/cda_imitate.h: likewise
+    L.cda_bc_records.argtypes = [vp] * 8 + [i32, i64, i32, vp, vp, vp]
+    L.cda_bc_loss_records.argtypes = [vp, vp, vp, vp, i64, i32, i32, f32, f32, f32, vp, vp, vp, i64, i32, i32, vp, vp, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("cda_strerror", "cda_group_range"):

@@ -1,10 +1,12 @@
 // cda_learner.hip - the learner-side kernels that do not depend on the network's shape (include/cda_learner.h): the epoch's keyed permutation, the unfused PPO
-// loss on int32 action arrays and on sample records, GAE straight into the records, the returns of completed episodes, the league's slot assignment.
+// loss on int32 action arrays and on sample records, GAE straight into the records, the returns of completed episodes, the league's slot assignment; and behaviour
+// cloning (include/cda_imitate.h): demonstrations packed into sample records and their negative log-likelihood, on the PPO loss's own head_probs / pick / RecordSamples.
 // csrc/cda_mlp.hip is compiled once per (history depth, activation, vf_share_layers) with every entry point renamed (csrc/cda_mlp_variant.h); nothing here reads
 // any of the three, so this file is compiled ONCE and its entry points keep their names for every variant.  Nothing in cda_mlp.hip calls into this file.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/cda_learner.h"
+#include "../../include/cda_imitate.h"
 
 // The library is built with -ffp-contract=off (the env kernels' f64 sums must match CPython's).  These kernels came out of csrc/cda_mlp.hip, which switches
 // contraction back on for itself, and they keep it: without the pragma the compiler splits their fused multiply-adds (the v_fma_f64 of the advantage variance in
@@ -498,5 +500,183 @@ extern "C" int cda_league_assign_scripted(const uint32_t* episode_crc, int32_t n
     const int n = n_markets * num_agents;
     hipLaunchKernelGGL(k_league_assign_scripted, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const unsigned int*)episode_crc, (int)n_markets,
                        (int)num_agents, (int)n_trainable, pool_cdf, (const int*)pool_net, (const int*)pool_script, (int)pool_size, (int*)slot_net, (int*)slot_script, (int*)slot_pool);
+    return hipGetLastError() == hipSuccess ? CDA_OK : CDA_ERR_HIP;
+}
+
+// ---- behaviour cloning (include/cda_imitate.h): demonstrations -> sample records, and their negative log-likelihood in the PPO loss's position ---------------------
+namespace {
+// One thread per (step, market, agent): the five env action words of the sample -> words 0..5 of its record, as two vector stores (k_script_actions' shape: a 16-byte
+// half, then the 8 bytes in front of ADV | RET, which stay what they were).  The Gaussian targets of an env action invert ppo.to_env_actions' squash on the action
+// clamped to the bound; a policy sample's are copied.  Word LOGP carries the weight.  stats f64[2] += (sum of the weights, samples with weight > 0).
+__global__ __launch_bounds__(256) void k_bc_records(const int* __restrict__ cat, const int* __restrict__ price, const int* __restrict__ off, const float* __restrict__ size_mean,
+                                                    const float* __restrict__ size_sigma, const float* __restrict__ a_cont, const int* __restrict__ slot_src,
+                                                    const float* __restrict__ slot_weight, long long total, long long NA, float* __restrict__ rec, double* __restrict__ stats) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    float w = 0.0f;
+    if (i < total) {
+        const long long col = i % NA;
+        const int src = slot_src[col];
+        w = (src == CDA_BC_SRC_ENV || src == CDA_BC_SRC_POLICY) ? slot_weight[col] : 0.0f;
+        float x0, x1;
+        if (src == CDA_BC_SRC_POLICY && a_cont) {
+            const float2 x = *reinterpret_cast<const float2*>(a_cont + 2 * i);
+            x0 = x.x; x1 = x.y;
+        } else {
+            const float M = CDA_BC_SQUASH_BOUND;
+            const float m = fminf(fmaxf(size_mean[i], -M), M), s = fminf(fmaxf(size_sigma[i], 1.0f - M), M);
+            x0 = atanhf(m);
+            x1 = logf(s / (1.0f - s));
+        }
+        *reinterpret_cast<float4*>(rec + 8 * i) = make_float4(__int_as_float(cat[i]), __int_as_float(price[i]), __int_as_float(off[i]), x0);
+        *reinterpret_cast<float2*>(rec + 8 * i + 4) = make_float2(x1, w);
+    }
+    double s1 = (double)w, s2 = w > 0.0f ? 1.0 : 0.0;
+    #pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { s1 += __shfl_down(s1, o, 64); s2 += __shfl_down(s2, o, 64); }
+    __shared__ double part[2][4];
+    if ((threadIdx.x & 63) == 0) { part[0][threadIdx.x >> 6] = s1; part[1][threadIdx.x >> 6] = s2; }
+    __syncthreads();
+    if (threadIdx.x < 2) atomicAdd(&stats[threadIdx.x], (part[threadIdx.x][0] + part[threadIdx.x][1]) + (part[threadIdx.x][2] + part[threadIdx.x][3]));
+}
+
+template <int N>
+__device__ __forceinline__ int clamp_label(int a) { return a < 0 ? 0 : (a > N - 1 ? N - 1 : a); }      // what pick<N> reads for label a
+template <int N>
+__device__ __forceinline__ int argmax_low(const float* v) {                                             // ties to the lowest index
+    int b = 0;
+    #pragma unroll
+    for (int q = 1; q < N; q++) b = v[q] > v[b] ? q : b;
+    return b;
+}
+// ppo_loss_rows' shape - one output row per thread, 256 rows per workgroup, the row's samples out of the records, wave shuffle + an LDS partial per wave + one f64
+// atomic per word and workgroup - with the weighted negative log-likelihood in the surrogate's place: dL / dlogp of a sample is -k w whatever the policy thinks of it.
+// A sample's word LOGP is its weight (RecordSamples hands it out as logp_old), word RET its return; word ADV is not read.
+__global__ __launch_bounds__(256) void k_bc_loss_rec(const float* __restrict__ outputs, const float* __restrict__ log_std, const float* __restrict__ rec,
+                                                     const long long* __restrict__ row_index, long long R, long long Rnorm, int agents, int stride, float vf_coef, float ent_coef,
+                                                     float loss_scale, float* __restrict__ d_out, double* __restrict__ sums, float* __restrict__ logp_out, double* __restrict__ bc_stats) {
+    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const float invB = 1.0f / ((float)Rnorm * (float)agents);
+    const float k = loss_scale * invB;
+    float nl = 0.0f, vl = 0.0f, en = 0.0f, dls0 = 0.0f, dls1 = 0.0f;
+    float bs[7] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (r < R) {
+        RecordSamples src(rec, nullptr, 0);
+        float l[N_LOGITS], d[N_LOGITS], p[N_CAT + N_PRICE + N_OFF], lp[N_CAT + N_PRICE + N_OFF];
+        const float4* lp4 = reinterpret_cast<const float4*>(outputs + r * stride);
+        #pragma unroll
+        for (int q = 0; q < N_LOGITS / 4; q++) { const float4 v = lp4[q]; l[4 * q] = v.x; l[4 * q + 1] = v.y; l[4 * q + 2] = v.z; l[4 * q + 3] = v.w; }
+        const float ls0 = log_std[0], ls1 = log_std[1];
+        const float is0 = __expf(-ls0), is1 = __expf(-ls1);
+        const float HALF_LOG_2PI = 0.918938533204672742f;
+        float h0, h1, h2;
+        head_probs<N_CAT>(l, p, lp, h0);
+        head_probs<N_PRICE>(l + N_CAT, p + N_CAT, lp + N_CAT, h1);
+        head_probs<N_OFF>(l + N_CAT + N_PRICE, p + N_CAT + N_PRICE, lp + N_CAT + N_PRICE, h2);
+        const float ent = h0 + h1 + h2 + 1.0f + 2.0f * HALF_LOG_2PI + ls0 + ls1;
+        const float es = ent_coef * k;
+        const int best_c = argmax_low<N_CAT>(l), best_p = argmax_low<N_PRICE>(l + N_CAT), best_o = argmax_low<N_OFF>(l + N_CAT + N_PRICE);
+        #pragma unroll
+        for (int q = 0; q < N_LOGITS; q++) d[q] = 0.0f;
+        const float val = outputs[r * stride + N_LOGITS];
+        float G = 0.0f, W = 0.0f, dval = 0.0f;
+        src.seek(row_index ? row_index[r] : r, agents);
+        for (int a = 0; a < agents; a++) {
+            const Sample s = src.get(a);
+            const int ac = clamp_label<N_CAT>(s.cat), ap = clamp_label<N_PRICE>(s.price), ao = clamp_label<N_OFF>(s.off);
+            const float w = s.logp_old;
+            const float e0 = s.cont0 - l[22], e1 = s.cont1 - l[23];
+            const float z0 = e0 * is0, z1 = e1 * is1;
+            const float logp = -0.5f * z0 * z0 - ls0 - HALF_LOG_2PI - 0.5f * z1 * z1 - ls1 - HALF_LOG_2PI +
+                               pick<N_CAT>(lp, ac) + pick<N_PRICE>(lp + N_CAT, ap) + pick<N_OFF>(lp + N_CAT + N_PRICE, ao);
+            if (logp_out) logp_out[r * agents + a] = logp;
+            const float g_logp = -w * k;
+            const float dv = val - s.ret;
+            nl -= w * logp;
+            vl += w * dv * dv;
+            dval += 2.0f * vf_coef * dv * w * k;
+            en += w * ent;
+            G += g_logp;
+            W += w;
+            #pragma unroll
+            for (int q = 0; q < N_CAT; q++) d[q] += (q == ac) ? g_logp : 0.0f;
+            #pragma unroll
+            for (int q = 0; q < N_PRICE; q++) d[N_CAT + q] += (q == ap) ? g_logp : 0.0f;
+            #pragma unroll
+            for (int q = 0; q < N_OFF; q++) d[N_CAT + N_PRICE + q] += (q == ao) ? g_logp : 0.0f;
+            d[22] += g_logp * z0 * is0;
+            d[23] += g_logp * z1 * is1;
+            dls0 += g_logp * (z0 * z0 - 1.0f) - es * w;
+            dls1 += g_logp * (z1 * z1 - 1.0f) - es * w;
+            bs[0] += w; bs[1] += ac == best_c ? w : 0.0f; bs[2] += ap == best_p ? w : 0.0f; bs[3] += ao == best_o ? w : 0.0f;
+            bs[4] += w * e0 * e0; bs[5] += w * e1 * e1; bs[6] += w > 0.0f ? 1.0f : 0.0f;
+        }
+        const float esW = es * W;
+        #pragma unroll
+        for (int q = 0; q < N_CAT; q++) d[q] += -G * p[q] + esW * p[q] * (lp[q] + h0);
+        #pragma unroll
+        for (int q = 0; q < N_PRICE; q++) d[N_CAT + q] += -G * p[N_CAT + q] + esW * p[N_CAT + q] * (lp[N_CAT + q] + h1);
+        #pragma unroll
+        for (int q = 0; q < N_OFF; q++) d[N_CAT + N_PRICE + q] += -G * p[N_CAT + N_PRICE + q] + esW * p[N_CAT + N_PRICE + q] * (lp[N_CAT + N_PRICE + q] + h2);
+        float4* dp4 = reinterpret_cast<float4*>(d_out + r * stride);
+        #pragma unroll
+        for (int q = 0; q < N_LOGITS / 4; q++) dp4[q] = make_float4(d[4 * q], d[4 * q + 1], d[4 * q + 2], d[4 * q + 3]);
+        dp4[N_LOGITS / 4] = make_float4(dval, 0.0f, 0.0f, 0.0f);
+        for (int q = N_LOGITS / 4 + 1; q < stride / 4; q++) dp4[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+    // words 0..2 carry loss_scale, not k: the finishing step divides them by B (k_ppo_finish32 here, cda_mlp_adam's in the update)
+    float v5[5] = {nl * loss_scale, vl * loss_scale, en * loss_scale, dls0, dls1};
+    __shared__ float part[5][4];
+    __shared__ double bpart[7][4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    #pragma unroll
+    for (int q = 0; q < 5; q++) {
+        float x = v5[q];
+        #pragma unroll
+        for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
+        if (lane == 0) part[q][wave] = x;
+    }
+    if (bc_stats) {                                                             // (uniform: the statistics cost nothing where nobody reads them)
+        #pragma unroll
+        for (int q = 0; q < 7; q++) {
+            double x = (double)bs[q];
+            #pragma unroll
+            for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
+            if (lane == 0) bpart[q][wave] = x;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 5) {
+        const double t = (double)part[threadIdx.x][0] + (double)part[threadIdx.x][1] + (double)part[threadIdx.x][2] + (double)part[threadIdx.x][3];
+        atomicAdd(&sums[threadIdx.x], t);
+    }
+    if (bc_stats && threadIdx.x >= 64 && threadIdx.x < 64 + 7) {
+        const int q = threadIdx.x - 64;
+        atomicAdd(&bc_stats[q], (bpart[q][0] + bpart[q][1]) + (bpart[q][2] + bpart[q][3]));
+    }
+}
+}  // namespace
+
+extern "C" int cda_bc_records(const int32_t* category, const int32_t* price, const int32_t* price_offset, const float* size_mean, const float* size_sigma, const float* a_cont,
+                              const int32_t* slot_src, const float* slot_weight, int32_t n_steps, int64_t n_markets, int32_t num_agents, float* rec, double* stats2, void* stream) {
+    if (!category || !price || !price_offset || !size_mean || !size_sigma || !slot_src || !slot_weight || !rec || !stats2 || n_steps < 1 || n_markets < 1 ||
+        num_agents < 1 || num_agents > CDA_MAX_AGENTS || ((uintptr_t)rec & 15) != 0 || ((uintptr_t)a_cont & 7) != 0) return CDA_ERR_INVALID;
+    const long long NA = (long long)n_markets * num_agents, total = NA * n_steps;
+    if (total > ((long long)1 << 31) * 256) return CDA_ERR_INVALID;            // (the grid's x dimension)
+    hipLaunchKernelGGL(k_bc_records, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const int*)category, (const int*)price, (const int*)price_offset,
+                       size_mean, size_sigma, a_cont, (const int*)slot_src, slot_weight, total, NA, rec, stats2);
+    return hipGetLastError() == hipSuccess ? CDA_OK : CDA_ERR_HIP;
+}
+
+extern "C" int cda_bc_loss_records(const float* outputs, const float* log_std, const float* rec, const int64_t* row_index, int64_t rows, int32_t agents_per_row,
+                                   int32_t out_stride, float vf_coef, float ent_coef, float loss_scale, float* d_outputs, double* sums5, float* out6, int64_t norm_rows,
+                                   int32_t clear, int32_t finish, float* logp_out, double* bc_stats, void* stream) {
+    if (!outputs || !log_std || !rec || !d_outputs || !sums5 || !out6 || rows < 1 || agents_per_row < 1 || agents_per_row > CDA_MAX_AGENTS ||
+        out_stride <= N_LOGITS || (out_stride & 3) || norm_rows < 0 || ((uintptr_t)rec & 15) != 0) return CDA_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    const long long rn = norm_rows > 0 ? norm_rows : rows;
+    if (clear && hipMemsetAsync(sums5, 0, 5 * sizeof(double), st) != hipSuccess) return CDA_ERR_HIP;
+    hipLaunchKernelGGL(k_bc_loss_rec, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, outputs, log_std, rec, (const long long*)row_index, (long long)rows, rn,
+                       (int)agents_per_row, (int)out_stride, vf_coef, ent_coef, loss_scale, d_outputs, sums5, logp_out, bc_stats);
+    if (finish) hipLaunchKernelGGL(k_ppo_finish32, dim3(1), dim3(64), 0, st, (const double*)sums5, rn * agents_per_row, vf_coef, ent_coef, out6);
     return hipGetLastError() == hipSuccess ? CDA_OK : CDA_ERR_HIP;
 }

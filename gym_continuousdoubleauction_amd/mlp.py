@@ -76,9 +76,9 @@ class Layout:
 
     def fn(self, name):
         """the entry point `name` for this layout: the network's (include/cda_mlp.h) carry the suffix, the learner-side ones (include/cda_learner.h: permutation,
-        unfused loss, GAE, episode returns, league assignment) exist once and serve every layout"""
-        from ._lib import LEARNER_SYMBOLS
-        return getattr(_lib(), name if name in LEARNER_SYMBOLS else name + self.suffix)
+        unfused loss, GAE, episode returns, league assignment) and behaviour cloning's (include/cda_imitate.h) exist once and serve every layout"""
+        from ._lib import IMITATE_SYMBOLS, LEARNER_SYMBOLS
+        return getattr(_lib(), name if (name in LEARNER_SYMBOLS or name in IMITATE_SYMBOLS) else name + self.suffix)
 
 
 _LAYOUTS = {}
@@ -913,6 +913,15 @@ class FusedUpdate:
         x.log_std_old = log_std_old.data_ptr() if (log_std_old is not None and kl_coef) else None
         self._extra, self._kl, self._extra_keep = x, float(kl_coef), (dist_old, log_std_old)
 
+    def _loss_records(self, records, first, n_rows, norm_rows, clip, vf_coef, ent_coef, clear, finish, st):
+        """the loss launch of the separate-kernel step on sample records: rows perm[first .. first + n_rows) of self.out -> self.d_out and the sums (PPO's clipped surrogate
+        here; imitate.BCUpdate puts the behaviour-cloning loss in this position)"""
+        rec, stats, count = records
+        _check(_Fns(self.L).cda_ppo_loss_records(self.out.data_ptr(), self.p.theta.data_ptr() + self.L.OFF_LS * 4, rec if isinstance(rec, int) else rec.data_ptr(),
+                                                 stats.data_ptr() if stats is not None else None, int(count), self.perm.data_ptr() + first * 8, n_rows, self.A, NOUT,
+                                                 float(clip), float(vf_coef), float(ent_coef), self.d_out.data_ptr(), self.sums5.data_ptr(), self.out6.data_ptr(), norm_rows,
+                                                 clear, finish, st), "cda_ppo_loss_records")
+
     def minibatch_step(self, s, rows, acts, logp_old, adv, ret, clip, vf_coef, ent_coef, lr, betas, eps, max_norm, apply=True, records=None, obs_rows=None,
                        debug_outputs=False):
         """rows [s, s + rows) of the prepared (shuffled) observations: one optimiser step.  obs_rows (with records, fused=True): the unshuffled f32
@@ -958,11 +967,7 @@ class FusedUpdate:
             _check(L.cda_mlp_forward_train(p.wb.data_ptr(), p.theta.data_ptr(), x_rm, rs, self.h1p.data_ptr(), self.h2p.data_ptr(), self.out.data_ptr(), st), "cda_mlp_forward_train")
             last = k == sub - 1
             if records is not None:
-                rec, stats, count = records
-                _check(L.cda_ppo_loss_records(self.out.data_ptr(), p.theta.data_ptr() + self.L.OFF_LS * 4, ptr(rec), stats.data_ptr() if stats is not None else None, int(count),
-                                              self.perm.data_ptr() + o * 8, rs, self.A, NOUT, float(clip), float(vf_coef), float(ent_coef), self.d_out.data_ptr(),
-                                              self.sums5.data_ptr(), self.out6.data_ptr(), rows, 0 if (apply or k) else 1, 0 if (apply or not last) else 1, st),
-                       "cda_ppo_loss_records")
+                self._loss_records(records, o, rs, rows, clip, vf_coef, ent_coef, 0 if (apply or k) else 1, 0 if (apply or not last) else 1, st)
             else:
               _check(L.cda_ppo_loss32(self.out.data_ptr(), p.theta.data_ptr() + self.L.OFF_LS * 4, acts[0].data_ptr(), acts[1].data_ptr(), acts[2].data_ptr(), acts[3].data_ptr(),
                                     logp_old.data_ptr(), adv.data_ptr(), ret.data_ptr(), self.perm.data_ptr() + o * 8, rs, self.A, NOUT,

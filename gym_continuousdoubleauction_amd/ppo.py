@@ -850,6 +850,8 @@ def main(argv=None, parse_only=False):
     p.add_argument("--per-sample-forward", action="store_true", help="run the network once per (market, agent) sample instead of once per market-step (shared_obs=False)")
     p.add_argument("--legacy", action="store_true", help="the round-3 loop: PyTorch network (library GEMMs, autograd), one graph per rollout step")
     p.add_argument("--save", default=None, metavar="PATH", help="fused loop: write the trained policy to this file (mlp.save_policy; evaluate.py reads it)")
+    p.add_argument("--init-policy", default=None, metavar="FILE", help="fused loop: start from this policy file (mlp.load_policy: a behaviour-cloned one of imitate.py, an earlier "
+                                                                        "run's --save) instead of a fresh network; the file brings its own widths, activation and trunk")
     add_shared_flags(p, cap="--max-step")                      # the network, the objective, resumable runs and --market-configs
     p.add_argument("--trained-slots", type=int, default=None, metavar="K", help="fused loop, with --opponent: the policy plays and trains slots 0 .. K - 1 of every market")
     p.add_argument("--opponent", action="append", default=None, metavar="SPEC",
@@ -881,6 +883,12 @@ def main(argv=None, parse_only=False):
         env.load_order_schedule(args.order_schedule)
     if args.save and args.legacy:
         raise SystemExit("--save needs the fused loop (the legacy loop's network is a PyTorch module)")
+    if args.init_policy and args.legacy:
+        raise SystemExit("--init-policy needs the fused loop (a policy file holds the fused network's parameter vector)")
+    init_policy = None
+    if args.init_policy:
+        from .mlp import load_policy
+        init_policy = load_policy(args.init_policy, env.obs.device)
     if args.legacy:
         _, hist = train(env, iters=args.iters, horizon=args.horizon, amp=not args.fp32_update, shared_obs=not args.per_sample_forward, use_graph=not args.no_graphs,
                         activation=args.fcnet_activation, vf_share_layers=args.vf_share_layers)
@@ -889,7 +897,7 @@ def main(argv=None, parse_only=False):
                               objective=RLLIB_DEFAULTS if args.objective == "rllib" else None, state_dependent_log_std=args.log_std_head, hidden=tuple(args.fcnet_hiddens),
                               checkpoint_dir=args.checkpoint_dir, chkpt_freq=args.chkpt_freq, chkpt_keep=args.chkpt_keep, restore=args.restore,
                               iters_is_delta=args.iters_is_delta, activation=args.fcnet_activation, vf_share_layers=args.vf_share_layers,
-                              trained_slots=args.trained_slots, opponents=args.opponent)
+                              trained_slots=args.trained_slots, opponents=args.opponent, policy=init_policy)
     summary = {"metric": "agent-steps/sec end to end (rollout + PPO update), BASELINE configs[4]",
                "config": {"workload": f"{args.markets} markets x {args.agents} agents, " + ("PyTorch-ROCm PPO policy (library GEMMs, autograd)" if args.legacy else
                                       "PPO policy on the hand-written bf16 MFMA network kernels") + f" in the loop (256x256 {args.fcnet_activation} actor and critic, "

@@ -7,8 +7,8 @@
 Every function of A (kernels and out-of-line device functions) is looked up in B under the same mangled name; its instruction text is compared
 after dropping addresses and the `// <address>` comments (branch offsets are relative, so they compare as they are) and what only says WHERE a
 function lies or which kernels exist beside it: the pc-relative literal behind s_getpc_b64 (the distance to a callee or a table), the ordinal of the
-calling kernel that a call passes in s15 (the module's LDS kernel id: it counts every kernel of the code object), the alignment padding (s_nop) behind a
-function's last instruction.
+calling kernel that a call passes in s15 (the module's LDS kernel id: it counts every kernel of the code object), the alignment padding (s_nop, or the zero
+fill objdump prints as "...") behind a function's last instruction.
 Prints one line per function that differs or is missing, the functions only B has, and a summary; exit status 1 if a function of A differs.
 Also compares the kernels' metadata (registers, spills, scratch, LDS, kernarg size)."""
 import os
@@ -34,7 +34,7 @@ def bodies(co):
         elif cur is not None and line.strip():
             cur.append(re.sub(r"\s*//.*$", "", line).strip())
     for name, body in out.items():
-        while body and body[-1].startswith("s_nop"):
+        while body and (body[-1].startswith("s_nop") or body[-1] == "..."):      # ("...": the zero fill objdump elides between a function and the next one's alignment)
             body.pop()
         for i, ins in enumerate(body):                       # s15 set within a few instructions of a call: the kernel's ordinal
             if re.match(r"s_mov_b32 s15, \d+$", ins) and any("s_swappc_b64" in x for x in body[i + 1:i + 160]):
