@@ -1,6 +1,7 @@
 """Random env configurations and action laws shared by the build-container cross-check of the oracle against the reference
 (tests/golden/crosscheck_oracle.py) and the GPU fuzz tests of the HIP path against the oracle; service_case() draws, on top of a configuration, what
-the device services (book report, scripted laws, tape reductions, snapshots, order streams) are fuzzed with (tests/test_hip_services_fuzz.py)."""
+the device services are fuzzed with (tests/test_hip_services_fuzz.py: the legs steps, book_report, scripted, tape, snapshot, order_stream, steps_after and end),
+and service_extras(), from a generator of its own, what the legs quotes and schedule are run with - ten legs in all."""
 import numpy as np
 
 
@@ -113,6 +114,36 @@ def row_in_domain(cfg, row):
             and 1 <= c["max_step"] <= cfg["max_step"])
 
 
+def granted_ring(cfg):
+    """the HBM ring per side cda_create grants a config (csrc/cda_hip.hip), device memory permitting: what was asked for - automatic: num_agents x max_step, at
+    least 1024 - rounded up to a power of two; an automatic ring is halved while the config's largest order size times tile + ring would leave int32, an explicit
+    one (book_spill > 0) that would is refused: ValueError"""
+    from gym_continuousdoubleauction_amd import _capi as K
+    c = K.make_config(cfg)[1]
+    if c["book_spill"] < 0:
+        return 0
+    want = c["book_spill"] if c["book_spill"] > 0 else max(1024, c["num_of_agents"] * c["max_step"])
+    ring = 64
+    while ring < want and ring < (1 << 20):
+        ring <<= 1
+    scale = c["mkt_max_size"] * c["limit_size_multiple"] + c["min_size"]
+    while ring > 64 and scale * (tile_of(cfg) + ring) > 0x7fffffff:
+        if c["book_spill"] > 0:
+            raise ValueError(f"cda_create refuses book_spill {c['book_spill']} for order sizes up to {scale}")
+        ring >>= 1
+    return ring
+
+
+def row_fits_ring(cfg, row):
+    """cda_set_market_params' further rule (csrc/cda_hip.hip): the env's ring was cut for the CONFIG's order sizes, and a row must keep to that ring - its largest
+    decodable size times tile + ring stays in int32.  (CDA_FUZZ_SEED=90417 drew, as case 110, 16 agents x 4096 steps - a ring of 65536 - with a row of sizes up to
+    60003: the env refused it at construction.)"""
+    from gym_continuousdoubleauction_amd import _capi as K
+    c = K.make_config(dict(cfg, **row))[1]
+    ring = granted_ring(cfg)
+    return ring == 0 or (c["mkt_max_size"] * c["limit_size_multiple"] + c["min_size"]) * (tile_of(cfg) + ring) <= 0x7fffffff
+
+
 def _service_row(rng, cfg, short):
     row = {"tick_size": int(rng.choice([1, 1, 2, 5, 10, 250]))}
     lo = int(rng.choice([1, 10, 500, 20000]))
@@ -156,7 +187,7 @@ def service_case(rng, n_markets=SERVICE_MARKETS):
         rows, k = [], int(rng.choice([2, 3]))
         while len(rows) < k:                                  # (validated on the host and redrawn; distinct)
             row = _service_row(rng, cfg, short)
-            if row_in_domain(cfg, row) and row not in rows:
+            if row_in_domain(cfg, row) and row_fits_ring(cfg, row) and row not in rows:
                 rows.append(row)
     n_prof = int(rng.integers(3, 7))                          # the four laws in a random order, then two more drawn: the first n_prof of them
     laws = ([1 + int(x) for x in rng.permutation(4)] + [int(x) for x in rng.integers(1, 5, 2)])[:n_prof]
@@ -194,6 +225,95 @@ def service_prefill_sizes(case, market):
         return tuple(int(x) for x in r.integers(0, 513, 2))
     half, quarter = case["tile"] // 2, case["cfg"]["book_spill"] // 4
     return tuple(int(x) for x in r.integers(half - quarter, half + quarter + 1, 2))
+
+
+# ---------------------------------------------------------------------------------------------------------------- what the quotes and schedule legs are run with
+EXTRAS_STREAM = 0x5C4ED                              # service_extras' own generator: [case["seed"], EXTRAS_STREAM]
+QUOTE_CAPACITIES = (8, 24, 40, 64, 128)              # quote rings: 8 and 24 wrap inside the 56 steps of a long case; 24 and 40 are no powers of two
+SCHEDULE_EDGES = (63, 64, 65, 130)                   # schedule_util.EDGE_LENGTHS without 0 and 1: around the message walk's chunk of 64
+SCHEDULE_WINDOW_MAX = max(SCHEDULE_EDGES)            # the longest window (the five invalid messages go into a small one: 9 + 5 at the most)
+INVALID_KINDS = 5                                    # len(invalid_messages(a))
+SERVICE_STEPS_TAIL = 10                              # 40 + 16 + 10 steps = 66 quotes of one episode: more than the quote readers' pass of 64 records
+
+
+def schedule_reach(case, n_windows, loop):
+    """THE WINDOW RULE: the windows of a schedule of `n_windows` windows that the schedule leg of `case` reaches in every market that plays a row.  The leg is
+    SERVICE_STEPS_AFTER = 16 steps behind SERVICE_STEPS = 40 steps (the order stream between them moves no clock).
+      long horizon    every market is at t_step 40 .. 55: with loop the windows {t % n_windows}, without it the windows 40 .. min(n_windows, 56) - 1.
+      short horizon   every episode is shorter than 16 steps, so every market passes every t_step 0 .. H - 1 of its own horizon H >= H_min (the smallest max_step of
+                      the case, rows included): the windows 0 .. min(n_windows, H_min) - 1, with loop or without.
+    service_extras puts messages into these windows only, so every drawn length is played."""
+    lo, hi = SERVICE_STEPS, SERVICE_STEPS + SERVICE_STEPS_AFTER
+    if case["short"]:
+        h_min = min([case["cfg"]["max_step"]] + [r["max_step"] for r in case["rows"] or []])
+        return list(range(min(n_windows, h_min)))
+    if loop:
+        return sorted({t % n_windows for t in range(lo, hi)})
+    return list(range(lo, min(n_windows, hi)))
+
+
+def short_quote_capacity(case, r):
+    """the quote ring of a short-horizon case (auto reset, per-market horizons of 4 .. 14 steps): no power of two, and with H the case's longest horizon in
+    H + 1 .. H + H // 2 - a whole episode fits, one and a half do not: once a longest-horizon market's current episode is half way, its previous one has lost
+    its head"""
+    h = max([x["max_step"] for x in case["rows"]] if case["rows"] else [case["cfg"]["max_step"]])
+    hi = h + max(1, h // 2)
+    k = int(r.integers(h + 1, hi + 1))
+    if k & (k - 1) == 0:                                  # 8 or 16: the neighbour inside the range
+        k = k + 1 if k + 1 <= hi else k - 1
+    return k
+
+
+def service_extras(case):
+    """What the two legs added behind service_case - quotes and schedule - are run with, drawn from a generator of ITS OWN ([case["seed"], EXTRAS_STREAM]): not one
+    draw is taken from the stream service_case draws from, so service_extras changes no case of any seed.  (What did change other seeds' streams, in the same
+    commit, is service_case's own redraw of a row the env would refuse - row_fits_ring: from the first such row on, a seed's later cases are other cases.  The
+    default seed draws no such row: its twelve cases are what they were.)  Plain numbers, lists and numpy arrays:
+      quote_capacity     the quote rings' capacity (QUOTE_CAPACITIES; short_quote_capacity in a short-horizon case)
+      tail_steps         steps of the law behind the schedule leg: SERVICE_STEPS_TAIL where a ring holds more than one pass of the readers (64 records) and the
+                         horizon is long - the episode then holds 66 quotes, and the statistics' carry from one pass into the next is in play -, else 0
+      schedule           n_rows (1 .. 3), n_windows (S), market_schedule int [n_markets] (at least one -1, every row played by at least two markets), loop,
+                         clear_step_counters
+      lengths[r][t]      messages of window t of row r, the five invalid messages included: mostly 0 (sparse flow); per row two or more windows of
+                         schedule_reach(), the first of them one of SCHEDULE_EDGES, the others small counts.  On a small ring (case["small_ring"]) every window
+                         is 1 .. 4 messages: the flow stays a few orders per step, as the law's, and the book inside tile + ring.
+      reach              schedule_reach(case, S, loop)
+      invalid            row, window, positions: where one invalid message of each kind (invalid_messages) is spliced into a small window, and a market that plays it"""
+    r = np.random.default_rng([case["seed"], EXTRAS_STREAM])
+    n = case["n_markets"]
+    n_rows, loop, clear = int(r.integers(1, 4)), bool(r.random() < 0.5), bool(r.random() < 0.5)
+    if case["short"]:
+        S = int(r.integers(3, 7))
+    elif loop:
+        S = int(r.integers(5, 13))
+    else:
+        S = SERVICE_STEPS + int(r.integers(8, SERVICE_STEPS_AFTER + 1))      # 48 .. 56: the leg's last steps may lie beyond the schedule
+    reach = schedule_reach(case, S, loop)
+    lengths = np.zeros((n_rows, S), np.int64)
+    small = []
+    for row in range(n_rows):
+        k = int(r.integers(2, max(2, len(reach) // 2) + 1))
+        at = [int(x) for x in r.choice(reach, k, replace=False)]
+        for j, t in enumerate(at):
+            lengths[row, t] = int(r.integers(1, 5)) if case["small_ring"] else int(r.choice(SCHEDULE_EDGES)) if j == 0 else int(r.integers(1, 10))
+        small += [(row, t) for t in (at if case["small_ring"] else at[1:])]
+    perm = [int(x) for x in r.permutation(n)]
+    ms = r.integers(0, n_rows, n).astype(np.int64)
+    ms[r.random(n) < 0.2] = -1
+    ms[perm[0]] = -1
+    for row in range(n_rows):
+        ms[perm[1 + 2 * row]] = ms[perm[2 + 2 * row]] = row
+    bad_row, bad_window = small[int(r.integers(0, len(small)))]
+    positions = sorted(int(x) for x in r.integers(0, lengths[bad_row, bad_window] + 1, INVALID_KINDS))
+    lengths[bad_row, bad_window] += INVALID_KINDS
+    if case["short"]:
+        capacity = short_quote_capacity(case, r)
+    else:
+        capacity = int(r.choice(QUOTE_CAPACITIES))
+    return {"quote_capacity": capacity, "tail_steps": SERVICE_STEPS_TAIL if capacity > 64 and not case["short"] else 0,
+            "schedule": {"n_rows": n_rows, "n_windows": S, "market_schedule": ms, "loop": loop, "clear_step_counters": clear},
+            "lengths": [[int(x) for x in row] for row in lengths], "reach": reach,
+            "invalid": {"row": bad_row, "window": bad_window, "positions": positions, "market": int(np.flatnonzero(ms == bad_row)[0])}}
 
 
 def service_cases(seed=SERVICE_SEED, count=SERVICE_CASES):

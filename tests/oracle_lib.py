@@ -161,7 +161,8 @@ class OracleEnv:
         assert lib().oracle_get_book(self.h, market, side, None, 0, C.byref(n)) == 0
         buf = (K.Order * max(n.value, 1))()
         assert lib().oracle_get_book(self.h, market, side, C.cast(buf, C.c_void_p), n.value, C.byref(n)) == 0
-        return np.ctypeslib.as_array(buf).view(np.int32).reshape(-1, 5)[: n.value].copy()
+        # (np.frombuffer: np.ctypeslib.as_array parses the structure's format string on every call - the largest single cost of the services fuzz's host side)
+        return np.frombuffer(buf, dtype=np.int32).reshape(-1, 5)[: n.value].copy()
 
     def place_order(self, market, trader, type_, side, size, price):
         rc = lib().oracle_place_order(self.h, market, trader, type_, side, size, price)

@@ -88,7 +88,7 @@ def episode_over(state, num_agents, max_step):
 class Scheduled:
     """The specification of an attached order schedule, on an env with the hooks' call shapes: play(i) runs market i's window of its current t_step through
     place_order / mark_to_mkt; step() plays every market, steps, and - auto_reset - resets the markets whose episode ended.  counts: [N, 4] = done, rejected,
-    invalid, fills, as the device's table."""
+    invalid, fills, as the device's table.  max_step: the config's horizon, or one per market (per-market parameter rows: the market's own row's)."""
 
     def __init__(self, env, rows, sched_of, num_agents, max_step, loop=False, clear_step_counters=False, auto_reset=True):
         self.env, self.rows, self.sched_of, self.A, self.max_step = env, rows, list(sched_of), num_agents, max_step
@@ -96,12 +96,15 @@ class Scheduled:
         self.counts = np.zeros((len(self.sched_of), 4), np.int64)
         self.played = []                                   # (market, row, window, messages) of every non-empty play
 
+    def horizon(self, i):
+        return int(self.max_step[i]) if np.ndim(self.max_step) else self.max_step
+
     def window(self, i):
         r = self.sched_of[i]
         if r < 0:
             return None
         s = self.env.get_state(i)
-        if episode_over(s, self.A, self.max_step):
+        if episode_over(s, self.A, self.horizon(i)):
             return None
         t, S = s.t_step, len(self.rows[r])
         if self.loop:
@@ -121,12 +124,13 @@ class Scheduled:
         self.played.append((i, rt[0], rt[1], len(msgs)))
         if not good:
             return
+        before = self.env.get_state(i)
         for m in good:
-            before = self.env.get_state(i)
             play_hooks(self.env, i, [m])
             after = self.env.get_state(i)
             rej = m != OR.MARK and after.acc[m[0]].num_rejected_step != before.acc[m[0]].num_rejected_step
             self.counts[i, 1 if rej else 0] += 1
+            before = after                                 # (one dump per message: the state behind a message is the state ahead of the next)
         if self.clear:
             s = self.env.get_state(i)
             for a in range(self.A):

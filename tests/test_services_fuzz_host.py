@@ -76,7 +76,7 @@ def test_every_row_passes_the_library_check_and_every_profile_the_hosts(cases):
         base = K.make_config(c["cfg"])[1]
         K.make_config(c["oracle_cfg"])
         for row in c["rows"] or []:
-            assert F.row_in_domain(c["cfg"], row), (i, row)
+            assert F.row_in_domain(c["cfg"], row) and F.row_fits_ring(c["cfg"], row), (i, row)
             rows = (K.MarketParams * 1)(row_of(market_config(base, row)))
             validate_rows(base, rows)                                           # raises ValueError on a refused row
             n_rows += 1
@@ -95,6 +95,131 @@ def test_every_row_passes_the_library_check_and_every_profile_the_hosts(cases):
         assert not F.row_in_domain(cfg, row), bad
         with pytest.raises(ValueError):
             rows_of(K.make_config(cfg)[1], [row])
+
+
+# ---- the twelve default cases are what they were before service_extras came: their seed fields and shapes, literals taken from the commit before it ----
+DEFAULT_SEEDS = [649081748879560493, 2698841326163019393, 2505966728131038087, 789277998334646751, 2575916902629827419, 2024318441497068961,
+                 2047527317627600816, 6912268489781382, 4059451142223408395, 1124075379147082851, 1955962979324153592, 1152983785470081220]
+# (num_of_agents, n_hist, tile, short, bool(rows))
+DEFAULT_SHAPES = [(2, 9, 512, False, True), (16, 16, 512, False, False), (2, 8, 256, False, False), (8, 4, 512, False, True), (12, 1, 256, False, False),
+                  (4, 9, 256, False, False), (4, 8, 256, False, True), (8, 5, 512, False, False), (5, 4, 256, False, True), (5, 9, 256, True, True),
+                  (8, 3, 256, False, False), (5, 5, 512, False, True)]
+
+
+def test_service_extras_left_the_default_cases_alone(cases):
+    assert [c["seed"] for c in cases] == DEFAULT_SEEDS
+    assert [(c["cfg"]["num_of_agents"], c["cfg"]["n_hist"], c["tile"], c["short"], bool(c["rows"])) for c in cases] == DEFAULT_SHAPES
+    # drawing the extras draws nothing from the cases' stream: the cases drawn with the extras taken in between are the same cases
+    rng = np.random.default_rng(F.SERVICE_SEED)
+    for i, c in enumerate(cases):
+        again = F.service_case(rng, F.RAGGED_MARKETS if i == F.RAGGED_CASE else F.SERVICE_MARKETS)
+        F.service_extras(again)
+        assert again["seed"] == c["seed"] and again["cfg"] == c["cfg"] and again["fork"] == c["fork"] and np.array_equal(again["slots"], c["slots"]), i
+    a, b = F.service_extras(cases[3]), F.service_extras(cases[3])                # ... and the extras are a function of the case
+    assert a["lengths"] == b["lengths"] and np.array_equal(a["schedule"]["market_schedule"], b["schedule"]["market_schedule"]) and a["invalid"] == b["invalid"]
+
+
+def test_the_extras_of_the_default_cases_cover_what_the_new_legs_rely_on(cases):
+    import schedule_util as U
+    assert set(F.SCHEDULE_EDGES) == set(U.EDGE_LENGTHS) - {0, 1} and F.INVALID_KINDS == len(F.invalid_messages(4))
+    extras = [F.service_extras(c) for c in cases]
+    caps = [x["quote_capacity"] for x in extras]
+    assert any(k & (k - 1) for k in caps)                      # a capacity that is no power of two
+    for c, x in zip(cases, extras):                            # short auto-reset episodes get a small ring that is no power of two: it wraps across the resets
+        if c["short"]:
+            k, h_max = x["quote_capacity"], max([r["max_step"] for r in c["rows"] or []] + ([] if c["rows"] else [c["cfg"]["max_step"]]))
+            assert k & (k - 1) and h_max < k <= h_max + max(1, h_max // 2), (k, h_max)      # an episode of the longest horizon fits, one and a half do not: a previous episode loses its head
+        else:
+            assert x["quote_capacity"] in F.QUOTE_CAPACITIES
+    for c in F.service_cases(F.SERVICE_SEED + 2, 60):          # ... at every horizon the generator can draw
+        if c["short"]:
+            k, h_max = F.service_extras(c)["quote_capacity"], max([r["max_step"] for r in c["rows"] or []] + ([] if c["rows"] else [c["cfg"]["max_step"]]))
+            assert k & (k - 1) and h_max < k <= h_max + max(1, h_max // 2), (k, h_max)
+    assert any(c["short"] and c["rows"] for c in cases)
+    assert any(x["quote_capacity"] < 40 and not c["short"] for c, x in zip(cases, extras))          # ... and one that wraps inside the 56 steps of a long case
+    assert {x["schedule"]["loop"] for x in extras} == {True, False} and {x["schedule"]["clear_step_counters"] for x in extras} == {True, False}
+    seen = set()
+    for i, (c, x) in enumerate(zip(cases, extras)):
+        sc, n = x["schedule"], c["n_markets"]
+        ms, S, lengths = sc["market_schedule"], sc["n_windows"], np.array(x["lengths"])
+        assert 1 <= sc["n_rows"] <= 3 and lengths.shape == (sc["n_rows"], S) and ms.shape == (n,) and ms.min() == -1 and ms.max() == sc["n_rows"] - 1, i
+        assert all((ms == r).sum() >= 2 for r in range(sc["n_rows"])), i                            # every row is played, and shared
+        # THE WINDOW RULE (fuzz_cases.schedule_reach): messages lie in windows the leg reaches, and nowhere else
+        reach = F.schedule_reach(c, S, sc["loop"])
+        assert x["reach"] == reach and len(reach) >= 3, i
+        if c["short"]:
+            h_min = min([c["cfg"]["max_step"]] + [r["max_step"] for r in c["rows"] or []])
+            assert h_min < F.SERVICE_STEPS_AFTER and reach == list(range(min(S, h_min))), i        # every market passes every t_step of its episode inside the leg
+        else:
+            steps = range(F.SERVICE_STEPS, F.SERVICE_STEPS + F.SERVICE_STEPS_AFTER)
+            assert reach == sorted({t % S for t in steps} if sc["loop"] else {t for t in steps if t < S}), i
+        for r in range(sc["n_rows"]):
+            on = np.flatnonzero(lengths[r])
+            assert len(on) >= 2 and set(on.tolist()) <= set(reach), (i, r)
+            assert len(on) <= max(2, S // 2), (i, r)                                               # sparse flow
+        assert lengths.max() <= F.SCHEDULE_WINDOW_MAX and (not c["small_ring"] or lengths.max() <= 4 + F.INVALID_KINDS), i
+        bad = x["invalid"]
+        assert lengths[bad["row"], bad["window"]] >= F.INVALID_KINDS and ms[bad["market"]] == bad["row"] and len(bad["positions"]) == F.INVALID_KINDS, i
+        assert max(bad["positions"]) <= lengths[bad["row"], bad["window"]] - F.INVALID_KINDS, i
+        seen |= {int(v) for v in lengths.reshape(-1)}
+    assert set(F.SCHEDULE_EDGES) <= seen, seen
+
+
+@pytest.fixture(scope="module")
+def dry(cases):
+    """the oracle-only dry run of the default cases (tests/services_fuzz_util.py dry_run), once for the module"""
+    import services_fuzz_util as SU
+    return [(i, c, x, SU.dry_run(c, x)) for i, c in enumerate(cases) for x in [F.service_extras(c)]]
+
+
+def test_an_oracle_only_dry_run_shows_the_conditions_the_gpu_comparison_relies_on(dry):
+    """Steps, stream and schedule of every default case on the oracles alone, no device: conditions on the INPUTS, which on the GPU would hide behind a flag
+    mismatch.  (1) on a small ring the book stays inside tile + ring - both sides together, the oracle's own census, inside steps too: then neither side can -
+    through the whole case, scheduled flow included; (2) no tape can drop a record: the bound behind TAPE_CAPACITY, from the messages each market really got;
+    (3) every case plays at least two non-empty windows - and the drawn lengths are all reached, scheduled fills and rejections occur.  Measured: 3 to 5 s for the
+    twelve cases together (0.12 to 1.7 s each) on a built tree, so all twelve are kept.  (4) the play past the row's horizon has markets to move in some case."""
+    import services_fuzz_util as SU
+    fills = rejected = 0
+    reached = set()
+    for i, c, x, d in dry:
+        assert not d["flags"].any(), i
+        if c["small_ring"]:
+            assert d["peak_total"] <= c["tile"] + c["cfg"]["book_spill"] and d["peak_side"] <= d["peak_total"], (i, d["peak_total"], d["peak_side"])
+        assert d["tape_bound"] < SU.TAPE_CAPACITY, (i, d["tape_bound"])
+        windows = {(r, w) for _, r, w, _ in d["played"]}
+        drawn = {(r, w) for r, row in enumerate(x["lengths"]) for w, k in enumerate(row) if k}
+        assert len(windows) >= 2 and windows == drawn, (i, sorted(drawn - windows))                 # every drawn window is played somewhere
+        assert all(k == x["lengths"][r][w] for _, r, w, k in d["played"]), i
+        per_market = np.zeros(c["n_markets"], np.int64)
+        for m, _, _, k in d["played"]:
+            per_market[m] += k
+        assert per_market.max() <= SU.SCHEDULE_PLAYS * F.SCHEDULE_WINDOW_MAX, i                     # the term of the TAPE_CAPACITY bound
+        for m, t in d["past_horizon"].items():                 # over by the market's own row, live by the config, and a window with messages under that clock
+            sc, hz = x["schedule"], SU.horizons(c)
+            assert sc["loop"] and hz[m] <= t < c["cfg"]["max_step"] and x["lengths"][sc["market_schedule"][m]][t % sc["n_windows"]] > 0, (i, m, t)
+        assert (d["counts"][x["schedule"]["market_schedule"] < 0] == 0).all(), i
+        bad = x["invalid"]
+        assert d["counts"][bad["market"], 2] >= F.INVALID_KINDS and d["counts"][:, 2].sum() % F.INVALID_KINDS == 0, i
+        fills += d["trades"]
+        rejected += int(d["counts"][:, 1].sum())
+        reached |= {k for *_, k in d["played"]}
+    assert fills > 0 and rejected > 0
+    assert set(F.SCHEDULE_EDGES) <= reached, reached
+    assert all(d["trades"] > 0 for *_, d in dry)                                                    # scheduled fills in every case
+    assert sum(len(d["past_horizon"]) >= 2 for *_, d in dry) >= 2                                   # cases whose schedule meets markets past their own row's horizon
+
+
+def test_a_row_keeps_to_the_ring_the_env_was_cut_for():
+    """cda_set_market_params refuses a row whose largest order size times tile + ring leaves int32 - the ring is cut for the config's sizes at construction.  A soak
+    found it: CDA_FUZZ_SEED=90417, case 110 was refused by the env.  The generator now redraws such a row; the stream of that seed draws no such row any more."""
+    cfg = {"num_of_agents": 16, "init_cash": 1000000, "max_step": 4096, "is_render": False, "n_hist": 12, "book_capacity": 512}
+    assert F.granted_ring(cfg) == 65536 and F.granted_ring(dict(cfg, book_spill=100)) == 128 and F.granted_ring(dict(cfg, book_spill=-1)) == 0
+    assert F.granted_ring(dict(cfg, mkt_max_size=3000, limit_size_multiple=20, min_size=3)) == 32768      # 60003 x (512 + 65536) > 2^31 - 1: halved once
+    row = {"tick_size": 1, "initial_price_min": 20000, "initial_price_max": 20021, "min_size": 3, "mkt_max_size": 3000, "limit_size_multiple": 20, "max_step": 4096}
+    assert F.row_in_domain(cfg, row) and not F.row_fits_ring(cfg, row)
+    assert F.row_fits_ring(cfg, dict(row, mkt_max_size=100)) and F.row_fits_ring(dict(cfg, max_step=1024), row) and F.row_fits_ring(dict(cfg, book_spill=-1), row)
+    for c in F.service_cases(90417, 120):
+        assert all(F.row_fits_ring(c["cfg"], r) for r in c["rows"] or []), c["cfg"]
 
 
 PINNED = (8, 50000, 1, "uniform")
