@@ -706,7 +706,8 @@ static int cfg_ok(const cda_config* c) {
     if (c->tick_size < 1 || c->tick_size > CDA_TICK_MAX) return CDA_ERR_UNSUPPORTED;
     if (c->initial_price_max < c->initial_price_min || c->initial_price_min < 0) return CDA_ERR_INVALID;
     if (c->initial_price_max >= (1 << 24)) return CDA_ERR_INVALID;      // prices live below 2^24 ticks (the clamp of step_market; the libm sweeps cover exactly that domain)
-    if (c->min_size < 0 || c->mkt_max_size < c->min_size || c->limit_size_multiple < 1) return CDA_ERR_INVALID;
+    // min_size >= 1: the decoded size is rint(|sample|) + min_size, and an order of quantity 0 has no behaviour in the reference (its process_order exits)
+    if (c->min_size < 1 || c->mkt_max_size < c->min_size || c->limit_size_multiple < 1) return CDA_ERR_INVALID;
     // Sizes are int32 on the device and a price level sums up to CDA_BOOK_CAP_MAX of them: the largest decodable size is
     // (mkt_max_size * limit_size_multiple - min_size) / 2 * |mean| + sigma * z + min_size, clamped at 1e9 (flagged).  Keep
     // the configured scale itself well inside int32 so that neither the product nor a level sum can wrap silently.

@@ -72,7 +72,9 @@ typedef struct cda_config {
     int64_t init_cash;           /* init_cash            (1000000) - integer, > -2^62 */
     int32_t initial_price_min;   /* initial_price_min    (10)      */
     int32_t initial_price_max;   /* initial_price_max    (100)     */
-    int32_t min_size;            /* min_size             (1)       */
+    int32_t min_size;            /* min_size             (1) - at least 1: a decoded size is rint(|sample|) + min_size, and the reference has no behaviour for an order
+                                    of quantity 0 (its process_order exits); with the two below: min_size <= mkt_max_size, limit_size_multiple >= 1 and
+                                    mkt_max_size * limit_size_multiple + min_size <= 2^30 / CDA_BOOK_CAP_MAX = 2^21 */
     int32_t mkt_max_size;        /* mkt_max_size         (100)     */
     int32_t limit_size_multiple; /* limit_size_multiple  (10)      */
     int32_t auto_reset;          /* extension, 0 = off (the reference has no such key; parity runs leave it 0). 1: a market whose

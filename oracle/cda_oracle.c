@@ -824,14 +824,38 @@ static void market_step(const struct oracle_env* e, market_t* m, int mi,
 /* ======================================================================================
  * exported API (host pointers everywhere)
  * ==================================================================================== */
+/* the product's domain (csrc/cda_hip.hip cfg_ok + row_ok), comparison for comparison: what the device refuses the oracle refuses with the same code */
 static int cfg_ok(const cda_config* c) {
     if (c->num_agents < 1 || c->num_agents > CDA_MAX_AGENTS) return CDA_ERR_INVALID;
     if (c->n_hist < 1 || c->n_hist > CDA_MAX_HIST) return CDA_ERR_INVALID;
     if (c->tick_size < 1 || c->tick_size > CDA_TICK_MAX) return CDA_ERR_UNSUPPORTED;
-    if (c->initial_price_max < c->initial_price_min) return CDA_ERR_INVALID;
-    if (c->min_size < 0 || c->mkt_max_size < c->min_size || c->limit_size_multiple < 1) return CDA_ERR_INVALID;
-    if (c->book_capacity != 0 && c->book_capacity != CDA_BOOK_CAP && c->book_capacity != CDA_BOOK_CAP_MAX) return CDA_ERR_INVALID;
+    if (c->initial_price_max < c->initial_price_min || c->initial_price_min < 0) return CDA_ERR_INVALID;
+    if (c->initial_price_max >= (1 << 24)) return CDA_ERR_INVALID;
+    /* min_size >= 1: the reference exits on an order of quantity 0 (process_order), so there is nothing to follow */
+    if (c->min_size < 1 || c->mkt_max_size < c->min_size || c->limit_size_multiple < 1) return CDA_ERR_INVALID;
+    if ((int64_t)c->mkt_max_size * (int64_t)c->limit_size_multiple + (int64_t)c->min_size > (int64_t)(1 << 30) / CDA_BOOK_CAP_MAX) return CDA_ERR_INVALID;
     if (c->book_spill < -1 || c->book_spill > CDA_SPILL_MAX) return CDA_ERR_INVALID;
+    if (c->max_step < 1) return CDA_ERR_INVALID;
+    if (c->book_capacity != 0 && c->book_capacity != CDA_BOOK_CAP && c->book_capacity != CDA_BOOK_CAP_MAX) return CDA_ERR_INVALID;
+    if (c->init_cash > (1LL << 62) || c->init_cash < -(1LL << 62)) return CDA_ERR_INVALID;
+    if (c->auto_reset != 0 && c->auto_reset != 1) return CDA_ERR_INVALID;
+    return CDA_OK;
+}
+/* cda_check_market_params' rule (the oracle itself plays one config per env: a test builds one oracle per row) */
+int oracle_check_market_params(const cda_config* env_cfg, int32_t n, const cda_market_params* rows) {
+    if (!env_cfg || n < 0 || (n > 0 && !rows)) return CDA_ERR_INVALID;
+    int rc = cfg_ok(env_cfg);
+    if (rc) return rc;
+    for (int32_t i = 0; i < n; i++) {
+        const cda_market_params* r = rows + i;
+        if (r->reserved != 0) return CDA_ERR_INVALID;
+        cda_config c = *env_cfg;
+        c.max_step = r->max_step; c.tick_size = r->tick_size; c.init_cash = r->init_cash;
+        c.initial_price_min = r->initial_price_min; c.initial_price_max = r->initial_price_max;
+        c.min_size = r->min_size; c.mkt_max_size = r->mkt_max_size; c.limit_size_multiple = r->limit_size_multiple;
+        if ((rc = cfg_ok(&c))) return rc;
+        if (r->max_step > env_cfg->max_step) return CDA_ERR_INVALID;
+    }
     return CDA_OK;
 }
 

@@ -24,6 +24,8 @@ typedef struct oracle_trace {
 } oracle_trace;
 
 int oracle_create(const cda_config* cfg, int32_t n_markets, oracle_env** out);
+/* the product's cda_check_market_params on the oracle's own copy of the domain rules (no env needed) */
+int oracle_check_market_params(const cda_config* env_cfg, int32_t n, const cda_market_params* rows);
 int oracle_destroy(oracle_env* env);
 int oracle_reset(oracle_env* env, const uint64_t* seeds, const uint8_t* mask, float* obs_out);
 int oracle_step(oracle_env* env,

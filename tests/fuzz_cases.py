@@ -1,7 +1,9 @@
 """Random env configurations and action laws shared by the build-container cross-check of the oracle against the reference
 (tests/golden/crosscheck_oracle.py) and the GPU fuzz tests of the HIP path against the oracle; service_case() draws, on top of a configuration, what
 the device services are fuzzed with (tests/test_hip_services_fuzz.py: the legs steps, book_report, scripted, tape, snapshot, order_stream, steps_after and end),
-and service_extras(), from a generator of its own, what the legs quotes and schedule are run with - ten legs in all."""
+and service_extras(), from a generator of its own, what the legs quotes and schedule are run with - ten legs in all.  edge_case() / edge_cases() draw, again from a
+generator of their own, configurations on the border of the accepted domain (tests/test_hip_config_edges.py; tests/test_config_edges_host.py holds them to
+their coverage), and in_reach() states when such a case is one the device and the oracle must agree on bit for bit."""
 import numpy as np
 
 
@@ -110,8 +112,8 @@ def row_in_domain(cfg, row):
     c = dict(cfg, **row)
     lo, hi = c.get("initial_price_min", 10), c.get("initial_price_max", 10)
     mn, mx, mul = c.get("min_size", 1), c.get("mkt_max_size", 1), c.get("limit_size_multiple", 1)
-    return (1 <= c.get("tick_size", 1) <= 65536 and 0 <= lo <= hi < (1 << 24) and 0 <= mn <= mx and mul >= 1 and mx * mul + mn <= (1 << 30) // 512
-            and 1 <= c["max_step"] <= cfg["max_step"])
+    return (1 <= c.get("tick_size", 1) <= 65536 and 0 <= lo <= hi < (1 << 24) and 1 <= mn <= mx and mul >= 1 and mx * mul + mn <= (1 << 30) // 512
+            and 1 <= c["max_step"] <= cfg["max_step"] and abs(c.get("init_cash", 0)) <= 1 << 62)
 
 
 def granted_ring(cfg):
@@ -320,3 +322,145 @@ def service_cases(seed=SERVICE_SEED, count=SERVICE_CASES):
     """the first `count` cases of a seed's stream, in order (case RAGGED_CASE with the ragged market count)"""
     rng = np.random.default_rng(seed)
     return [service_case(rng, RAGGED_MARKETS if i == RAGGED_CASE else SERVICE_MARKETS) for i in range(count)]
+
+
+# ---------------------------------------------------------------------------------------------------------------- the edges of the accepted config domain
+EDGE_SEED = 86031                                    # the default CDA_FUZZ_SEED of tests/test_hip_config_edges.py: tests/test_config_edges_host.py holds its cases to the coverage
+EDGE_CASES = 32                                      # case i plays 1 + i % 16 agents: every agent count twice
+EDGE_STREAM = 0xED6E5                                # edge_cases' own generator: [seed, EDGE_STREAM] - not one draw from random_config's callers' streams
+EDGE_MARKETS, EDGE_STEPS = SERVICE_MARKETS, 48
+EDGE_RAGGED_CASE = 7                                 # the one case of RAGGED_MARKETS markets
+PRICE_TOP = (1 << 24) - 1                            # the largest price of the domain (csrc/cda_hip.hip cfg_ok; a decoded price beyond it is clamped and flagged)
+SCALE_MAX = (1 << 30) // 512                         # the largest mkt_max_size * limit_size_multiple + min_size
+CASH_MAX = 1 << 62
+HEADROOM_TICKS = 64                                  # a market of a top-of-the-domain price band starts at least this many ticks below 2^24 (see _edge_seeds)
+# factor -> its levels.  A "max" level (sizes, prices or tick at the top of the domain) brings init_cash = 2^62 with it, so that the case trades instead of
+# rejecting; such a level is therefore never combined with a level of init_cash, and a top price band not with a short horizon either (an in-episode reset
+# draws a start price the generator has no hold on).
+EDGE_LEVELS = {
+    "init_cash": (-CASH_MAX, -1, 0, 1, CASH_MAX - 1, CASH_MAX),
+    "tick_size": (65535, 65536),
+    "price": ("zero", "one", "tick", "top"),        # (0, 0), (1, 1), (tick, tick), (2^23, 2^24 - 1)
+    "scale": ("mkt", "mul1024", "mul"),             # 2^21 as mkt_max_size = 2^21 - min_size, mul = 1; as mul = 2^10; as mkt_max_size = 1, mul = 2^21 - min_size
+    "flat_size": (True,),                           # mkt_max_size == min_size
+    "max_step": (1, 2, 3),
+    "n_hist": (1, 16),
+    "book_capacity": (256, 512),
+}
+EDGE_LEADS = [(f, v) for f, levels in EDGE_LEVELS.items() for v in levels]       # case i holds EDGE_LEADS[i % 23] for sure, and up to two more factors drawn
+# company for three cases, by case index: the three largest-scale leads fall on 13 to 15 agents (tile 512, where cda_create halves the automatic ring down to 256
+# slots) - one of them is played on the small tile, where the int32 rule leaves 512 slots; init_cash = 0 is played a second time at a horizon of one step,
+# where both causes of an episode's end meet on every step; and init_cash = 1 is played a second time where it can trade: an order is approved when cash >= price
+# x opening size (the reference's Trader._order_approved), so with 1 of cash only one unit at a price of 1 - a start price of 1 (bids are clamped up to one tick,
+# an ask one tick inside the empty side's first level lands on 1) and mkt_max_size == min_size = 1 (a market order's size is then rint(|sigma z|) + 1)
+EDGE_ALSO = {13: (("book_capacity", 256),), 25: (("max_step", 1),), 26: (("price", "one"), ("flat_size", True))}
+_EDGE_MAX = {("tick_size", 65535), ("tick_size", 65536), ("price", "top"), ("scale", "mkt"), ("scale", "mul1024"), ("scale", "mul")}
+
+
+def _edge_allowed(held, factor, level):
+    """may (factor, level) join the levels a case holds already?"""
+    if factor in held or (factor == "flat_size" and "scale" in held) or (factor == "scale" and "flat_size" in held):
+        return False
+    has_max, has_cash = any((f, v) in _EDGE_MAX for f, v in held.items()), "init_cash" in held
+    has_top, has_short = held.get("price") == "top", "max_step" in held
+    if (factor, level) in _EDGE_MAX and has_cash or factor == "init_cash" and has_max:
+        return False
+    if (factor, level) == ("price", "top") and has_short or factor == "max_step" and has_top:
+        return False
+    return True
+
+
+def _edge_seeds(rng, n, cfg):
+    """reset seeds of a case.  Under a price band that ends at 2^24 - 1 only seeds whose market starts HEADROOM_TICKS ticks or more below the top are kept: the
+    reference (and the oracle) decode prices beyond 2^24 where the device clamps and flags (tests/test_hip_domain_flags.py test_price_clamp_edge), so a case
+    that is to agree bit for bit has to stay below in what it decodes.  The start price is reset's first draw, integers(lo, hi, endpoint=True) of the seed's
+    PCG64 stream (tests/test_config_edges_host.py checks this restatement against the oracle)."""
+    lo, hi = cfg.get("initial_price_min", 10), cfg.get("initial_price_max", 100)
+    room = PRICE_TOP - HEADROOM_TICKS * cfg.get("tick_size", 1)
+    seeds = []
+    while len(seeds) < n:
+        s = int(rng.integers(0, 2 ** 63))
+        if hi <= room or int(np.random.default_rng(s).integers(lo, hi, endpoint=True)) <= room:
+            seeds.append(s)
+    return np.array(seeds, np.uint64)
+
+
+def edge_case(rng, agents=None, lead=None, n_markets=EDGE_MARKETS, also=()):
+    """One case on the border of the accepted domain: an ordinary random_config draw (from `rng`, the edge generator's own) with the agent count set, `lead` = a
+    (factor, level) of EDGE_LEVELS held for sure (None: drawn), `also` = further such pairs, and up to two more factors drawn, each moved to one of its levels.  Pure host code.
+    The case: cfg (the env's config; oracle_cfg: the same, the oracle takes every key), edges {factor: level}, law / present_p / order as the configuration fuzz draws
+    them, n_markets, steps (EDGE_STEPS, 3 * max_step + 2 on a short horizon), seeds (uint64 per market), seed (of the test's own action generator), tile."""
+    cfg, law, present_p = random_config(rng)
+    order = random_order(rng)
+    if agents is not None:
+        cfg["num_of_agents"] = int(agents)
+    if lead is None:
+        lead = EDGE_LEADS[int(rng.integers(0, len(EDGE_LEADS)))]
+    held = {lead[0]: lead[1]}
+    for f, v in also:
+        assert _edge_allowed(held, f, v), (held, f, v)
+        held[f] = v
+    for _ in range(int(rng.integers(0, 3))):
+        f, v = EDGE_LEADS[int(rng.integers(0, len(EDGE_LEADS)))]
+        if len(held) < 3 and _edge_allowed(held, f, v):       # one to three factors at an edge
+            held[f] = v
+    if any((f, v) in _EDGE_MAX for f, v in held.items()):
+        cfg["init_cash"] = CASH_MAX
+    for f in ("init_cash", "tick_size", "max_step", "n_hist", "book_capacity"):
+        if f in held:
+            cfg[f] = held[f]
+    tick = cfg.get("tick_size", 1)
+    if "price" in held:
+        lo, hi = {"zero": (0, 0), "one": (1, 1), "tick": (tick, tick), "top": (1 << 23, PRICE_TOP)}[held["price"]]
+        cfg.update(initial_price_min=lo, initial_price_max=hi)
+    mn = cfg.get("min_size", 1)
+    if held.get("scale") == "mkt":
+        cfg.update(min_size=mn, mkt_max_size=SCALE_MAX - mn, limit_size_multiple=1)
+    elif held.get("scale") == "mul1024":                  # 2047 * 1024 + 1024
+        cfg.update(min_size=1024, mkt_max_size=(SCALE_MAX - 1024) // 1024, limit_size_multiple=1024)
+    elif held.get("scale") == "mul":
+        cfg.update(min_size=1, mkt_max_size=1, limit_size_multiple=SCALE_MAX - 1)
+    elif held.get("flat_size"):
+        if cfg["init_cash"] == 1:                             # (see EDGE_ALSO: one unit is all that 1 of cash buys)
+            mn = 1
+        cfg.update(min_size=mn, mkt_max_size=mn, limit_size_multiple=cfg.get("limit_size_multiple", 10))
+    short = "max_step" in held
+    n = int(n_markets)
+    return {"cfg": cfg, "oracle_cfg": dict(cfg), "edges": held, "law": law, "present_p": present_p, "order": order, "n_markets": n, "short": short,
+            "broke": cfg["init_cash"] <= 0, "steps": 3 * cfg["max_step"] + 2 if short else EDGE_STEPS, "tile": tile_of(cfg),
+            "seeds": _edge_seeds(rng, n, cfg), "seed": int(rng.integers(0, 2 ** 62))}
+
+
+def edge_cases(seed=EDGE_SEED, count=EDGE_CASES):
+    """the first `count` edge cases of a seed, in order: case i plays 1 + i % 16 agents and holds EDGE_LEADS[i % len(EDGE_LEADS)] (with EDGE_ALSO's company);
+    case EDGE_RAGGED_CASE has the ragged market count"""
+    rng = np.random.default_rng([int(seed), EDGE_STREAM])
+    return [edge_case(rng, 1 + i % 16, EDGE_LEADS[i % len(EDGE_LEADS)], RAGGED_MARKETS if i == EDGE_RAGGED_CASE else EDGE_MARKETS,
+                      also=EDGE_ALSO.get(i, ())) for i in range(count)]
+
+
+def edge_actions(case):
+    """the case's own action stream: a generator to hand to batch_actions step by step"""
+    return np.random.default_rng([case["seed"], EDGE_STREAM])
+
+
+def in_reach(case, oracle_env, trace=None):
+    """Is `case`, as far as `oracle_env` has played it, one the device must reproduce bit for bit?  None if so, else the reason as a string:
+      every price the oracle decoded in its last step is below 2^24 (`trace`, default oracle_env.trace: beyond, the device clamps and flags where the reference goes on);
+      every side of every book is within the LDS tile + the granted HBM ring (the oracle's book is unbounded, the device drops and flags a rest beyond);
+      the oracle's flags are 0.
+    Call it after every step: the decoded prices are the last step's."""
+    trace = oracle_env.trace if trace is None else trace
+    a = case["cfg"]["num_of_agents"]
+    for m in range(oracle_env.n):
+        worst = max(trace[m].dec_price[:a])
+        if worst > PRICE_TOP:
+            return f"market {m} decoded the price {worst} >= 2^24"
+    room = case["tile"] + granted_ring(case["cfg"])
+    for m in range(oracle_env.n):
+        nb, na = oracle_env.book_size(m)
+        if max(nb, na) > room:
+            return f"market {m} holds {nb} bids / {na} asks, the device {room} per side"
+    if oracle_env.flags().any():
+        return f"the oracle's flags are {oracle_env.flags()}"
+    return None

@@ -12,6 +12,12 @@ subsets and dict order, for the case's number of steps (a short-horizon case: on
 twelve), seed defaults to the fuzz's.
 
     PYTHONPATH=tests/golden/shim:/root/reference:tests:. python tests/golden/crosscheck_oracle.py --services [n_cases] [seed]
+
+With --edges the episodes are the cases of the config-edge tests (tests/fuzz_cases.py edge_cases; tests/test_hip_config_edges.py trusts the oracle on them): per case
+EDGE_EPISODES episodes, from the case's first reset seeds, under its config, law, agent subsets and dict order, for the case's number of steps (at most one
+horizon: the reference has no in-episode reset).  n then counts cases (default: the tests' own 32), seed defaults to theirs.
+
+    PYTHONPATH=tests/golden/shim:/root/reference:tests:. python tests/golden/crosscheck_oracle.py --edges [n_cases] [seed]
 """
 import contextlib
 import io
@@ -52,17 +58,35 @@ def service_episodes(n, seed):
     return out
 
 
+EDGE_EPISODES = 4
+
+
+def edge_episodes(n, seed):
+    """EDGE_EPISODES episodes of each of the first n edge cases: random_case's tuples"""
+    import fuzz_cases as F
+    out = []
+    for i, case in enumerate(F.edge_cases(F.EDGE_SEED if seed is None else seed, F.EDGE_CASES if n is None else n)):
+        cfg = {k: v for k, v in case["oracle_cfg"].items() if k not in ("book_capacity", "book_spill")}       # (the reference has no tile and no ring)
+        rng = np.random.default_rng(case["seed"])
+        for j in range(EDGE_EPISODES):
+            out.append((f"e{i}m{j}", cfg, int(case["seeds"][j]), min(case["steps"], cfg["max_step"]), int(rng.integers(0, 2 ** 31)), case["law"], case["present_p"],
+                        case["order"]))
+    return out
+
+
 def main():
-    args = [a for a in sys.argv[1:] if a != "--services"]
-    services = len(args) != len(sys.argv) - 1
-    n = int(args[0]) if args else (None if services else 200)
-    seed = int(args[1]) if len(args) > 1 else (None if services else 2024)
-    episodes = service_episodes(n, seed) if services else None
+    modes = [a for a in sys.argv[1:] if a in ("--services", "--edges")]
+    args = [a for a in sys.argv[1:] if a not in ("--services", "--edges")]
+    edges = "--edges" in modes
+    listed = bool(modes)                                  # --services or --edges: the episodes are listed up front, not drawn one by one
+    n = int(args[0]) if args else (None if listed else 200)
+    seed = int(args[1]) if len(args) > 1 else (None if listed else 2024)
+    episodes = (edge_episodes(n, seed) if edges else service_episodes(n, seed)) if listed else None
     rng = np.random.default_rng(seed)
     steps = 0
-    n = len(episodes) if services else n
+    n = len(episodes) if listed else n
     for i in range(n):
-        name, cfg, seed, T, aseed, law, present_p, order = episodes[i] if services else random_case(rng, i)
+        name, cfg, seed, T, aseed, law, present_p, order = episodes[i] if listed else random_case(rng, i)
         with contextlib.redirect_stdout(io.StringIO()):
             rec = MG.run_trace(name, cfg, seed, T, aseed, law=law, present_p=present_p, dict_order=order)
         rec = {k: (v if isinstance(v, np.ndarray) else np.asarray(v)) for k, v in rec.items()}
@@ -79,7 +103,8 @@ def main():
             env.close()
         if (i + 1) % 50 == 0:
             print(f"{i + 1} episodes, {steps} steps: all fields identical")
-    print(f"oracle == reference on {n} {'service-case' if services else 'random'} episodes ({steps} steps)")
+    kind = ("edge-case" if edges else "service-case") if listed else "random"
+    print(f"oracle == reference on {n} {kind} episodes ({steps} steps)")
     return 0
 
 

@@ -328,6 +328,28 @@ def main():
     add("tick3_floor_s302", dict(base4, tick_size=3, initial_price_min=1, initial_price_max=7), 302, 192, 7302)
     add("tick7_aggr8_s303", dict(base8, tick_size=7, initial_price_min=20, initial_price_max=60), 303, 160, 7303, law="aggressive")
     add("tick250_edges_s304", dict(base4, tick_size=250, initial_price_min=100, initial_price_max=3000), 304, 160, 7304, law="edges")
+    # the border of the accepted config domain (csrc/cda_hip.hip cfg_ok): agent counts no other trace plays, balances of 0, -1 and 2^62, a start price of 0, the
+    # largest tick under a price band that ends at 2^24 - 1, the largest size scale (mkt_max_size * limit_size_multiple + min_size = 2^21), both at 16 agents,
+    # a horizon of one step (reset with seed=None before every further step) and the deepest history.  Short traces: 48 steps at the most.  Every decoded price
+    # stays below 2^24 (tests/test_config_edges_host.py asserts it): beyond, the device clamps and flags where the reference goes on.
+    big = 1 << 62
+    edge = {"init_cash": 1000000, "max_step": 64, "is_render": False}
+    add("edge_A1_s401", dict(edge, num_of_agents=1), 401, 48, 7401)                                   # one agent: it trades with itself
+    add("edge_A7_s402", dict(edge, num_of_agents=7), 402, 48, 7402, law="aggressive")
+    add("edge_A13_s403", dict(edge, num_of_agents=13), 403, 48, 7403, law="aggressive", present_p=0.8, dict_order="shuffle")
+    add("edge_cash0_s404", dict(edge, num_of_agents=4, init_cash=0), 404, 24, 7404)                    # every agent bankrupt at the first mark: terminated every step
+    add("edge_cashneg_s405", dict(edge, num_of_agents=3, init_cash=-1), 405, 24, 7405, law="aggressive")
+    add("edge_cashmax_s406", dict(edge, num_of_agents=4, init_cash=big), 406, 48, 7406, law="aggressive")
+    add("edge_price0_s407", dict(edge, num_of_agents=4, initial_price_min=0, initial_price_max=0), 407, 48, 7407)
+    add("edge_pricetop_tickmax_s408", dict(edge, num_of_agents=4, init_cash=big, tick_size=65536, initial_price_min=1 << 23, initial_price_max=(1 << 24) - 1), 408, 48, 7408,
+        law="aggressive")
+    add("edge_tickmax_floor_s413", dict(edge, num_of_agents=4, init_cash=big, tick_size=65536, initial_price_min=1, initial_price_max=1), 413, 48, 7413, law="aggressive")   # pr < tick -> tick
+    # (three agents: tests/test_hip_market_params.py replays every 4-agent trace as a ROW of one env, whose ring is cut for the base config's sizes, not for 2^21)
+    add("edge_scalemax_s409", dict(edge, num_of_agents=3, init_cash=big, min_size=1, mkt_max_size=(1 << 21) - 1, limit_size_multiple=1), 409, 48, 7409)
+    add("edge_A16_allmax_s410", dict(edge, num_of_agents=16, init_cash=big, tick_size=1000, initial_price_min=1 << 23, initial_price_max=(1 << 24) - 1, min_size=1024,
+                                     mkt_max_size=2047, limit_size_multiple=1024), 410, 48, 7410, law="aggressive")
+    add("edge_step1_s411", dict(edge, num_of_agents=5, max_step=1), 411, 8, 7411, reseed_at={t: None for t in range(1, 8)})
+    add("edge_hist16_s412", dict(edge, num_of_agents=6, n_hist=16), 412, 48, 7412)
     for name, rec in traces.items():
         np.savez_compressed(os.path.join(out_dir, f"trace_{name}.npz"), **rec)
     if only:

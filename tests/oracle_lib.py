@@ -35,6 +35,7 @@ def lib():
         _lib = C.CDLL(_SO)
         vp = C.c_void_p
         _lib.oracle_create.argtypes = [C.POINTER(K.Config), C.c_int32, C.POINTER(vp)]
+        _lib.oracle_check_market_params.argtypes = [C.POINTER(K.Config), C.c_int32, C.POINTER(K.MarketParams)]
         _lib.oracle_destroy.argtypes = [vp]
         _lib.oracle_reset.argtypes = [vp, vp, vp, vp]
         _lib.oracle_step.argtypes = [vp] + [vp] * 6 + [vp] * 4 + [C.POINTER(K.InfoPtrs), vp]
@@ -131,11 +132,16 @@ class OracleEnv:
         assert rc == 0, rc
         return self.obs, self.reward, self.term, self.trunc, self.info
 
-    def run_random(self, step0, n_steps, action_seed=0, market_index_base=0, first=0, count=None):
-        """Random agents of include/cda_random_agents.h: steps step0 .. step0+n_steps-1 of markets [first, first+count)."""
+    def run_random(self, step0, n_steps, action_seed=0, market_index_base=0, first=0, count=None, info=False):
+        """Random agents of include/cda_random_agents.h: steps step0 .. step0+n_steps-1 of markets [first, first+count); info=True: self.info holds the last
+        step's info tensors of those markets (lob_actions: the decoded orders)."""
         count = self.n - first if count is None else count
-        rc = lib().oracle_run_random_range(self.h, first, count, step0, n_steps, action_seed, market_index_base,
-                                           _ptr(self.obs), _ptr(self.reward), _ptr(self.term), _ptr(self.trunc))
+        if info:
+            rc = lib().oracle_run_random_range_info(self.h, first, count, step0, n_steps, action_seed, market_index_base,
+                                                    _ptr(self.obs), _ptr(self.reward), _ptr(self.term), _ptr(self.trunc), C.byref(self._info_ptrs))
+        else:
+            rc = lib().oracle_run_random_range(self.h, first, count, step0, n_steps, action_seed, market_index_base,
+                                               _ptr(self.obs), _ptr(self.reward), _ptr(self.term), _ptr(self.trunc))
         assert rc == 0, rc
         return self.obs, self.reward, self.term, self.trunc
 

@@ -36,7 +36,7 @@ def _base():
     {"max_step": 257},
     {"mkt_max_size": 300000, "limit_size_multiple": 10},
     {"num_of_agents": 5}, {"n_hist": 3},
-    {"min_size": -1}, {"init_cash": 2 ** 63 - 1},
+    {"min_size": -1}, {"min_size": 0}, {"init_cash": 2 ** 63 - 1},
 ])
 def test_a_bad_row_is_refused_on_the_host(lib, bad):
     from gym_continuousdoubleauction_amd.market_params import rows_of
@@ -52,7 +52,7 @@ def test_the_library_check_is_the_envs_own(lib):
     assert (r.max_step, r.tick_size, r.init_cash, r.loss_multiplier) == (256, 1, 1000000, 1.5)
     assert lib.cda_check_market_params(C.byref(cfg), 1, C.byref(r)) == 0
     for field, value, rc in (("tick_size", 0, K.ERR_UNSUPPORTED), ("tick_size", 65537, K.ERR_UNSUPPORTED), ("max_step", 257, K.ERR_INVALID), ("max_step", 0, K.ERR_INVALID),
-                             ("initial_price_max", 1 << 24, K.ERR_INVALID), ("limit_size_multiple", 0, K.ERR_INVALID), ("reserved", 1, K.ERR_INVALID)):
+                             ("initial_price_max", 1 << 24, K.ERR_INVALID), ("limit_size_multiple", 0, K.ERR_INVALID), ("min_size", 0, K.ERR_INVALID), ("reserved", 1, K.ERR_INVALID)):
         b = K.MarketParams.from_buffer_copy(r)
         setattr(b, field, value)
         assert lib.cda_check_market_params(C.byref(cfg), 1, C.byref(b)) == rc, field

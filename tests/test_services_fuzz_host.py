@@ -90,7 +90,7 @@ def test_every_row_passes_the_library_check_and_every_profile_the_hosts(cases):
     # the generator's own statement of the rule refuses what the library refuses
     cfg = cases[0]["cfg"]
     for bad in ({"tick_size": 0}, {"initial_price_min": 50, "initial_price_max": 10}, {"max_step": cfg["max_step"] + 1}, {"mkt_max_size": 300000, "limit_size_multiple": 10},
-                {"min_size": -1}, {"initial_price_max": 1 << 24}):
+                {"min_size": -1}, {"min_size": 0}, {"initial_price_max": 1 << 24}):
         row = dict({"max_step": cfg["max_step"]}, **bad)
         assert not F.row_in_domain(cfg, row), bad
         with pytest.raises(ValueError):
