@@ -237,8 +237,7 @@ int cda_book_counts(cda_env* e, int32_t first_market, int32_t n_markets, int32_t
     HIPCHK(hipSetDevice(e->device));
     hipLaunchKernelGGL(k_book_counts, book_grid(n_markets), dim3(64 * CDA_WPB), 0, (hipStream_t)stream, (const uint8_t*)e->arena, e->P, (int)e->cap, (int)first_market,
                        (int)n_markets, counts_out_dev);
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    return launch_status();
 }
 int cda_book_levels(cda_env* e, int32_t first_market, int32_t n_markets, int32_t max_levels, int64_t* levels_out_dev, void* stream) {
     if (!BOOK_RANGE_ARGS_OK(e, levels_out_dev, first_market, n_markets) || max_levels < 1 || max_levels > CDA_BOOK_MAX_LEVELS || ((uintptr_t)levels_out_dev & 7) != 0)
@@ -247,8 +246,7 @@ int cda_book_levels(cda_env* e, int32_t first_market, int32_t n_markets, int32_t
     HIPCHK(hipSetDevice(e->device));
     hipLaunchKernelGGL(k_book_levels, book_grid(n_markets), dim3(64 * CDA_WPB), 0, (hipStream_t)stream, (const uint8_t*)e->arena, e->P, (int)e->cap, (int)first_market,
                        (int)n_markets, (int)max_levels, (long long*)levels_out_dev);
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    return launch_status();
 }
 int cda_book_impact(cda_env* e, int32_t first_market, int32_t n_markets, const int64_t* sizes_host, int32_t n_sizes, int64_t* impact_out_dev, void* stream) {
     if (!BOOK_RANGE_ARGS_OK(e, impact_out_dev, first_market, n_markets) || !sizes_host || n_sizes < 1 || n_sizes > CDA_BOOK_MAX_SIZES || ((uintptr_t)impact_out_dev & 7) != 0)
@@ -263,8 +261,7 @@ int cda_book_impact(cda_env* e, int32_t first_market, int32_t n_markets, const i
     HIPCHK(hipSetDevice(e->device));
     hipLaunchKernelGGL(k_book_impact, book_grid(n_markets), dim3(64 * CDA_WPB), 0, (hipStream_t)stream, (const uint8_t*)e->arena, e->P, (int)e->cap, (int)first_market,
                        (int)n_markets, S, (int)n_sizes, (long long*)impact_out_dev);
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    return launch_status();
 }
 int cda_book_agents(cda_env* e, int32_t first_market, int32_t n_markets, int64_t* agents_out_dev, void* stream) {
     if (!BOOK_RANGE_ARGS_OK(e, agents_out_dev, first_market, n_markets) || ((uintptr_t)agents_out_dev & 7) != 0) return CDA_ERR_INVALID;
@@ -272,8 +269,7 @@ int cda_book_agents(cda_env* e, int32_t first_market, int32_t n_markets, int64_t
     HIPCHK(hipSetDevice(e->device));
     hipLaunchKernelGGL(k_book_agents, book_grid(n_markets), dim3(64 * CDA_WPB), 0, (hipStream_t)stream, (const uint8_t*)e->arena, e->P, (int)e->cap, (int)first_market,
                        (int)n_markets, (int)e->P.cfg.num_agents, (long long*)agents_out_dev);
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    return launch_status();
 }
 int cda_book_offsets(cda_env* e, int32_t first_market, int32_t n_markets, int64_t* offsets_dev, void* stream) {
     if (!BOOK_RANGE_ARGS_OK(e, offsets_dev, first_market, n_markets) || ((uintptr_t)offsets_dev & 7) != 0) return CDA_ERR_INVALID;
@@ -281,8 +277,7 @@ int cda_book_offsets(cda_env* e, int32_t first_market, int32_t n_markets, int64_
     HIPCHK(hipSetDevice(e->device));
     hipLaunchKernelGGL(k_book_offsets, dim3(1), dim3(BOOK_SCAN_THREADS), 0, (hipStream_t)stream, (const uint8_t*)e->arena, e->P, (int)e->cap, (int)first_market, (int)n_markets,
                        (long long*)offsets_dev);
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    return launch_status();
 }
 int cda_book_pack(cda_env* e, int32_t first_market, int32_t n_markets, const int64_t* offsets_dev, int64_t total_orders, void* orders_out_dev, int64_t capacity_orders,
                   void* stream) {
@@ -292,8 +287,7 @@ int cda_book_pack(cda_env* e, int32_t first_market, int32_t n_markets, const int
     HIPCHK(hipSetDevice(e->device));
     hipLaunchKernelGGL(k_book_pack, book_grid(n_markets), dim3(64 * CDA_WPB), 0, (hipStream_t)stream, (const uint8_t*)e->arena, e->P, (int)e->cap, (int)first_market,
                        (int)n_markets, (const long long*)offsets_dev, (int32_t*)orders_out_dev, (long long)capacity_orders);
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    return launch_status();
 }
 
 }  // extern "C"

@@ -13,6 +13,8 @@
 //                      k_place_order   Trader.place_order     agent/trader.py:49-106   (test hook, 1 market)
 //                      k_mark_to_mkt   Exchg_Helper.mark_to_mkt                         (test hook, 1 market)
 //                      k_raw_snapshot  agg_LOB_raw            exchg/state_helper.py:159-160
+//   cda_hist_variants.inc  the loop over the compiled history depths of the policy network (4 and CDA_HIST_DEPTHS): includes a body file once per depth
+//   cda_cap_table.inc      cda::CapKernels, and per book capacity the table of that namespace's kernels (included behind the per-capacity includes below)
 //   cda_snapshot.inc k_snap_offsets, k_snap_pack, k_snap_check, k_snap_restore and the cda_snapshot_* entry points (included at the end)
 //   cda_book_report.inc  k_book_counts, k_book_levels, k_book_impact, k_book_agents, k_book_offsets, k_book_pack: read-only reductions over the
 //                    standing book (tile + spill ring), one wave per (market, side), and the cda_book_* entry points (included at the end)
@@ -36,42 +38,14 @@
 #include <type_traits>
 #include <mutex>
 #include "../../include/cda_mlp.h"          // the network's layout constants (n_hist = 4): k_policy_step evaluates the policy inside the step kernel
-namespace cda { namespace mlpdev {
-#include "cda_mlp_dev.inc"
-} }
-// ... and for the other compiled history depths (CDA_MLP_HIST_VARIANTS): the header's layout macros follow CDA_MLP_HIST
-#undef CDA_MLP_HIST
-#define CDA_MLP_HIST 1
-namespace cda { namespace mlpdev_h1 {
-#include "cda_mlp_dev.inc"
-} }
-#undef CDA_MLP_HIST
-#define CDA_MLP_HIST 2
-namespace cda { namespace mlpdev_h2 {
-#include "cda_mlp_dev.inc"
-} }
-#undef CDA_MLP_HIST
-#define CDA_MLP_HIST 3
-namespace cda { namespace mlpdev_h3 {
-#include "cda_mlp_dev.inc"
-} }
-#undef CDA_MLP_HIST
-#define CDA_MLP_HIST 6
-namespace cda { namespace mlpdev_h6 {
-#include "cda_mlp_dev.inc"
-} }
-#undef CDA_MLP_HIST
-#define CDA_MLP_HIST 7
-namespace cda { namespace mlpdev_h7 {
-#include "cda_mlp_dev.inc"
-} }
-#undef CDA_MLP_HIST
-#define CDA_MLP_HIST 8
-namespace cda { namespace mlpdev_h8 {
-#include "cda_mlp_dev.inc"
-} }
-#undef CDA_MLP_HIST
-#define CDA_MLP_HIST 4
+// cda_mlp_dev.inc once per compiled history depth, as cda::mlpdev (n_hist 4) and cda::mlpdev_h<H> (cda_hist_variants.inc: the header's layout macros follow CDA_MLP_HIST)
+#define CDA_HIST_BODY "cda_mlp_dev.inc"
+#define CDA_HIST_OPEN namespace cda { namespace CDA_HIST_SFX(mlpdev) {
+#define CDA_HIST_CLOSE } }
+#include "cda_hist_variants.inc"
+#undef CDA_HIST_BODY
+#undef CDA_HIST_OPEN
+#undef CDA_HIST_CLOSE
 #pragma clang fp contract(off)              // (the includes above switched contraction on for the network's arithmetic; everything below is the env's)
 
 using namespace cda;
@@ -332,6 +306,7 @@ struct RunArgs {
 #include "cda_kernels.inc"
 #include "cda_orders.inc"
 #include "cda_schedule.inc"
+#include "cda_cap_table.inc"
 #undef CDA_CAP
 #undef CDA_CAPNS
 #define CDA_CAP 512
@@ -339,8 +314,11 @@ struct RunArgs {
 #include "cda_kernels.inc"
 #include "cda_orders.inc"
 #include "cda_schedule.inc"
+#include "cda_cap_table.inc"
 #undef CDA_CAP
 #undef CDA_CAPNS
+// the kernels of an env's book capacity (cda_create asks once; cda_env::k)
+static const CapKernels* cap_kernels(int cap) { return cap == 512 ? &cda::cap512::kernels : &cda::cap256::kernels; }
 
 // Sum-of-NAV conservation check, one thread per market (callbk/league_based_self_play_callback.py:679-704)
 __global__ void k_nav_conservation(const uint8_t* arena, Params P, double tol, double* err_out, uint8_t* viol_out) {
@@ -364,7 +342,7 @@ __global__ void k_nav_conservation(const uint8_t* arena, Params P, double tol, d
 // short (account.py:196-213).
 __host__ __device__ static inline int book_phys_rt(int cap, int s, int i) { return s == 0 ? i : cap - 1 - i; }     // cda_book.inc book_phys with a run-time capacity
 // order i of side sd of a market, wherever it lives: the first `tile_n` orders in the record's tile, the rest in the spill ring
-struct BookView {
+struct __attribute__((visibility("hidden"))) BookView {        // (hidden: the host reads books through it too, and the library exports the C-ABI only)
     const int32_t* tile; const int32_t* spill; int cap, spill_cap; int tile_n[2], tail_n[2], tail_base[2];
     __host__ __device__ int total(int sd) const { return tile_n[sd] + tail_n[sd]; }
     __host__ __device__ int32_t get(int sd, int f, int i) const {
@@ -638,7 +616,8 @@ struct QuoteArgs { uint4* ring; QuoteMeta* meta; uint32_t cap; uint32_t pad; }; 
 struct cda_env {
     Params P;
     int device;
-    int cap;                 // book capacity of this env: 256 or 512 (selects the cap256:: / cap512:: kernels)
+    int cap;                 // book capacity of this env: 256 or 512
+    const CapKernels* k;     // ... and that capacity's market-wave kernels (cda_cap_table.inc)
     uint8_t* arena;
     size_t arena_bytes;
     uint8_t* done_buf;       // auto_reset: u8[N] behind the market records - terminated | truncated of the last step
@@ -675,6 +654,37 @@ static int hip_fail(hipError_t e, const char* what) {
     return CDA_ERR_HIP;
 }
 #define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) return hip_fail(_e, #x); } while (0)
+// Scratch that frees itself on every way out of an entry point: host memory and device memory.  (Not std::vector: an allocation that fails is a status code here.)
+namespace {                  // (internal: the library exports the C-ABI and nothing else)
+template <class T> struct HostBuf {
+    T* p = nullptr;
+    HostBuf() {}
+    explicit HostBuf(size_t n) { alloc(n); }
+    HostBuf(const HostBuf&) = delete;
+    HostBuf& operator=(const HostBuf&) = delete;
+    ~HostBuf() { free(p); }
+    bool alloc(size_t n, bool zeroed = false) { p = (T*)(zeroed ? calloc(n, sizeof(T)) : malloc(n * sizeof(T))); return p != nullptr; }      // (once per buffer)
+    operator T*() const { return p; }
+};
+template <class T> struct DevBuf {
+    T* p = nullptr;
+    DevBuf() {}
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t bytes) { return hipMalloc((void**)&p, bytes); }      // (once per buffer)
+    T* release() { T* r = p; p = nullptr; return r; }                            // the buffer becomes a service's (its *_free owns it from here)
+    operator T*() const { return p; }
+};
+}
+static int launch_status() { HIPCHK(hipGetLastError()); return CDA_OK; }      // of the launches an entry point has just queued: what it returns
+template <class K, class... A>
+static void launch(K kern, const Launch& l, A... a) { hipLaunchKernelGGL(kern, l.grid, l.block, l.smem, l.stream, a...); }
+// n threads in blocks of `block`, one per item (a market, mostly)
+template <class K, class... A>
+static void launch_1d(K kern, int n, int block, size_t smem, hipStream_t stream, A... a) {
+    launch(kern, Launch{dim3((unsigned)((n + block - 1) / block)), dim3(block), smem, stream}, a...);
+}
 
 extern "C" {
 
@@ -700,6 +710,12 @@ int cda_default_config(cda_config* c) {
     return CDA_OK;
 }
 
+// Sizes are int32 on the device and a price level sums up to a side's orders of them (the observation's raw snapshot): the largest decodable size is
+// (mkt_max_size * limit_size_multiple - min_size) / 2 * |mean| + sigma * z + min_size, clamped at 1e9 (flagged).  The configured scale times `orders` must stay within
+// `limit`, so that neither the product nor a level sum can wrap silently.  (All three positive: cfg_ok checks that first.)
+static bool size_scale_ok(int32_t mkt_max_size, int32_t limit_size_multiple, int32_t min_size, int64_t orders, int64_t limit) {
+    return (int64_t)mkt_max_size * (int64_t)limit_size_multiple + (int64_t)min_size <= limit / orders;
+}
 static int cfg_ok(const cda_config* c) {
     if (c->num_agents < 1 || c->num_agents > CDA_MAX_AGENTS) return CDA_ERR_INVALID;
     if (c->n_hist < 1 || c->n_hist > CDA_MAX_HIST) return CDA_ERR_INVALID;
@@ -708,10 +724,8 @@ static int cfg_ok(const cda_config* c) {
     if (c->initial_price_max >= (1 << 24)) return CDA_ERR_INVALID;      // prices live below 2^24 ticks (the clamp of step_market; the libm sweeps cover exactly that domain)
     // min_size >= 1: the decoded size is rint(|sample|) + min_size, and an order of quantity 0 has no behaviour in the reference (its process_order exits)
     if (c->min_size < 1 || c->mkt_max_size < c->min_size || c->limit_size_multiple < 1) return CDA_ERR_INVALID;
-    // Sizes are int32 on the device and a price level sums up to CDA_BOOK_CAP_MAX of them: the largest decodable size is
-    // (mkt_max_size * limit_size_multiple - min_size) / 2 * |mean| + sigma * z + min_size, clamped at 1e9 (flagged).  Keep
-    // the configured scale itself well inside int32 so that neither the product nor a level sum can wrap silently.
-    if ((int64_t)c->mkt_max_size * (int64_t)c->limit_size_multiple + (int64_t)c->min_size > (int64_t)(1 << 30) / CDA_BOOK_CAP_MAX) return CDA_ERR_INVALID;
+    // a tile of CDA_BOOK_CAP_MAX orders: the configured scale itself stays well inside int32
+    if (!size_scale_ok(c->mkt_max_size, c->limit_size_multiple, c->min_size, CDA_BOOK_CAP_MAX, 1 << 30)) return CDA_ERR_INVALID;
     if (c->book_spill < -1 || c->book_spill > CDA_SPILL_MAX) return CDA_ERR_INVALID;
     if (c->max_step < 1) return CDA_ERR_INVALID;
     if (c->book_capacity != 0 && c->book_capacity != 256 && c->book_capacity != 512) return CDA_ERR_INVALID;
@@ -721,12 +735,13 @@ static int cfg_ok(const cda_config* c) {
 }
 
 // ---- per-market parameters ---------------------------------------------------------------------------------------------------------------------
+// what a parameter row and the config share, field for field
+#define CDA_ROW_FIELDS(X) X(max_step) X(tick_size) X(init_cash) X(initial_price_min) X(initial_price_max) X(min_size) X(mkt_max_size) X(limit_size_multiple) \
+    X(order_penalty) X(trade_penalty) X(drawdown_penalty) X(passive_bonus) X(loss_multiplier)
 static void row_into_config(cda_config* c, const cda_market_params* r) {
-    c->max_step = r->max_step; c->tick_size = r->tick_size; c->init_cash = r->init_cash;
-    c->initial_price_min = r->initial_price_min; c->initial_price_max = r->initial_price_max;
-    c->min_size = r->min_size; c->mkt_max_size = r->mkt_max_size; c->limit_size_multiple = r->limit_size_multiple;
-    c->order_penalty = r->order_penalty; c->trade_penalty = r->trade_penalty; c->drawdown_penalty = r->drawdown_penalty;
-    c->passive_bonus = r->passive_bonus; c->loss_multiplier = r->loss_multiplier;
+#define CDA_X(f) c->f = r->f;
+    CDA_ROW_FIELDS(CDA_X)
+#undef CDA_X
 }
 // a row is valid when the env's config with the row merged in passes cfg_ok (one set of domain rules) and its horizon is within the env's:
 // the automatic spill ring was sized from the env's max_step
@@ -739,7 +754,7 @@ static int row_ok(const cda_config* env_cfg, const cda_market_params* r) {
     if (r->max_step > env_cfg->max_step) return CDA_ERR_INVALID;
     return CDA_OK;
 }
-// the device form of a row (the size scales with exactly the expressions cda_create has always used)
+// the device form of a row (cda_create takes the env-wide size scales, Params::mkt_mul / lim_mul, from the config's row)
 static MktRow device_row(const cda_market_params* r) {
     MktRow d;
     memset(&d, 0, sizeof d);
@@ -755,11 +770,9 @@ static MktRow device_row(const cda_market_params* r) {
 int cda_market_params_from_config(const cda_config* c, cda_market_params* r) {
     if (!c || !r) return CDA_ERR_INVALID;
     memset(r, 0, sizeof *r);
-    r->max_step = c->max_step; r->tick_size = c->tick_size; r->init_cash = c->init_cash;
-    r->initial_price_min = c->initial_price_min; r->initial_price_max = c->initial_price_max;
-    r->min_size = c->min_size; r->mkt_max_size = c->mkt_max_size; r->limit_size_multiple = c->limit_size_multiple;
-    r->order_penalty = c->order_penalty; r->trade_penalty = c->trade_penalty; r->drawdown_penalty = c->drawdown_penalty;
-    r->passive_bonus = c->passive_bonus; r->loss_multiplier = c->loss_multiplier;
+#define CDA_X(f) r->f = c->f;
+    CDA_ROW_FIELDS(CDA_X)
+#undef CDA_X
     return CDA_OK;
 }
 
@@ -772,13 +785,26 @@ int cda_check_market_params(const cda_config* env_cfg, int32_t n, const cda_mark
 }
 
 // launch the capacity variant of a market-wave kernel that matches the env
-#define LAUNCH_CAP(e, kern, grid, block, smem, stream, ...) do { \
-    if ((e)->cap == 512) hipLaunchKernelGGL(cda::cap512::kern, grid, block, smem, stream, __VA_ARGS__); \
-    else hipLaunchKernelGGL(cda::cap256::kern, grid, block, smem, stream, __VA_ARGS__); } while (0)
 static dim3 grid_for(int n) { return dim3((unsigned)((n + CDA_WPB - 1) / CDA_WPB)); }
 static size_t smem_for(const cda_env* e, int waves) {
-    const int per = e->cap == 512 ? cda::cap512::lds_bytes_per_wave(e->P.cfg.num_agents, e->P.cfg.n_hist) : cda::cap256::lds_bytes_per_wave(e->P.cfg.num_agents, e->P.cfg.n_hist);
-    return (size_t)DEC_TABLE_BYTES + (size_t)waves * (size_t)per;
+    return (size_t)DEC_TABLE_BYTES + (size_t)waves * (size_t)e->k->lds_bytes_per_wave(e->P.cfg.num_agents, e->P.cfg.n_hist);
+}
+// the launch of a market-wave kernel over n markets (one wave each, CDA_WPB per workgroup; `extra` bytes of LDS behind the images), and of the one-market test hooks
+static Launch waves_for(const cda_env* e, int n, size_t extra, hipStream_t stream) { return Launch{grid_for(n), dim3(64 * CDA_WPB), smem_for(e, CDA_WPB) + extra, stream}; }
+static Launch one_wave(const cda_env* e) { return Launch{dim3(1), dim3(64), smem_for(e, 1), 0}; }
+
+static int range_ok(const cda_env* e, int32_t first, int32_t n) { return first >= 0 && n >= 1 && (int64_t)first + (int64_t)n <= (int64_t)e->P.n_markets; }
+// everything an env can own, in cda_destroy's order; a half-built env (cda_create's failure paths) holds NULL where nothing was allocated yet
+static void env_free(cda_env* e) {
+    if (e->arena) (void)hipFree(e->arena);
+    if (e->em_partials) (void)hipFree(e->em_partials);
+    if (e->snap_flag) (void)hipFree(e->snap_flag);
+    tape_free(e);
+    schedule_free(e);
+    quotes_free(e);
+    if (e->rows) (void)hipFree(e->rows);
+    free(e->rows_host);
+    free(e);
 }
 
 static int grant_policy_step_lds(const cda_env* e);
@@ -795,10 +821,13 @@ int cda_create(const cda_config* cfg, int32_t n_markets, int32_t device, cda_env
     // book capacity: as asked, else by the agent count (census, profiles/r02: random agents hold up to 83 / 129 / 235 resting
     // orders per market at 4 / 8 / 16 agents over 4096 steps; the flip-heavy law overflows 256 at 16 agents)
     e->cap = cfg->book_capacity ? cfg->book_capacity : (cfg->num_agents <= 8 ? 256 : 512);
+    e->k = cap_kernels(e->cap);
     Params& P = e->P;
     P.cfg = *cfg; P.n_markets = n_markets;
-    P.mkt_mul = (float)((double)(cfg->mkt_max_size - cfg->min_size) / 2.0);
-    P.lim_mul = (float)((double)((int64_t)cfg->mkt_max_size * (int64_t)cfg->limit_size_multiple - (int64_t)cfg->min_size) / 2.0);
+    cda_market_params r0;                                  // the config as a parameter row: every market's until cda_set_market_params
+    cda_market_params_from_config(cfg, &r0);
+    const MktRow d0 = device_row(&r0);
+    P.mkt_mul = d0.mkt_mul; P.lim_mul = d0.lim_mul;
     P.lay = record_layout(cfg->num_agents, cfg->n_hist, e->cap);
     // HBM tier of the book: a ring of spill_cap orders per side behind every market's tile.  Automatic size: a side gains at
     // most one resting order per agent and step, so num_agents * max_step (+ the tile) can never be exceeded inside an episode -
@@ -820,9 +849,8 @@ int cda_create(const cda_config* cfg, int32_t n_markets, int32_t device, cda_env
             while (capv > CDA_SPILL_MIN && spill_region_bytes((int32_t)capv) * (size_t)n_markets > free_b / 4) capv >>= 1;
         // a price level's size is summed in int32 (the observation's raw snapshot): the largest decodable order size times the
         // orders one side can hold must stay below 2^31 - the same rule cfg_ok applies to the tile alone
-        const int64_t scale = (int64_t)cfg->mkt_max_size * (int64_t)cfg->limit_size_multiple + (int64_t)cfg->min_size;
-        while (capv > CDA_SPILL_MIN && scale * ((int64_t)e->cap + capv) > 0x7fffffffLL) {
-            if (cfg->book_spill > 0) { free(e); return CDA_ERR_INVALID; }
+        while (capv > CDA_SPILL_MIN && !size_scale_ok(cfg->mkt_max_size, cfg->limit_size_multiple, cfg->min_size, (int64_t)e->cap + capv, 0x7fffffffLL)) {
+            if (cfg->book_spill > 0) { env_free(e); return CDA_ERR_INVALID; }
             capv >>= 1;
         }
         P.lay.spill_cap = (int32_t)capv;
@@ -830,35 +858,28 @@ int cda_create(const cda_config* cfg, int32_t n_markets, int32_t device, cda_env
     const size_t records = (size_t)P.lay.stride * (size_t)n_markets;
     e->arena_bytes = spill_arena_off(P) + spill_region_bytes(P.lay.spill_cap) * (size_t)n_markets;
     hipError_t he = hipMalloc((void**)&e->arena, e->arena_bytes);
-    if (he != hipSuccess) { free(e); return he == hipErrorOutOfMemory ? CDA_ERR_NOMEM : hip_fail(he, "hipMalloc"); }
+    if (he != hipSuccess) { e->arena = NULL; env_free(e); return he == hipErrorOutOfMemory ? CDA_ERR_NOMEM : hip_fail(he, "hipMalloc"); }
     e->done_buf = e->arena + records;
     P.ep_tol = 1e-6;
     // the per-market parameter table, every row the config's (also the CDA_ROW_PAD rows behind the last market)
     {
         const size_t nrows = (size_t)n_markets + CDA_ROW_PAD;
         e->rows_host = (cda_market_params*)malloc(sizeof(cda_market_params) * (size_t)n_markets);
-        MktRow* staged = (MktRow*)malloc(sizeof(MktRow) * nrows);
+        HostBuf<MktRow> staged(nrows);
         he = (e->rows_host && staged) ? hipMalloc((void**)&e->rows, sizeof(MktRow) * nrows) : hipErrorOutOfMemory;
         if (he == hipSuccess) {
-            cda_market_params r0;
-            cda_market_params_from_config(cfg, &r0);
-            const MktRow d0 = device_row(&r0);
             for (size_t i = 0; i < nrows; i++) staged[i] = d0;
             for (int32_t i = 0; i < n_markets; i++) e->rows_host[i] = r0;
             he = hipMemcpy(e->rows, staged, sizeof(MktRow) * nrows, hipMemcpyHostToDevice);
         }
-        free(staged);
-        if (he != hipSuccess) {
-            (void)hipFree(e->arena); if (e->rows) (void)hipFree(e->rows); free(e->rows_host); free(e);
-            return he == hipErrorOutOfMemory ? CDA_ERR_NOMEM : hip_fail(he, "market parameter table");
-        }
+        if (he != hipSuccess) { env_free(e); return he == hipErrorOutOfMemory ? CDA_ERR_NOMEM : hip_fail(he, "market parameter table"); }
         P.rows = e->rows;
     }
-    hipLaunchKernelGGL(k_init_arena, dim3((unsigned)((n_markets + 255) / 256)), dim3(256), 0, 0, e->arena, P);
+    launch_1d(k_init_arena, n_markets, 256, 0, 0, e->arena, P);
     he = hipMemsetAsync(e->arena + em_agent_off(P), 0, spill_arena_off(P) - em_agent_off(P), 0);          // the episode-metric accumulators
     if (he == hipSuccess) he = hipMalloc((void**)&e->em_partials, (size_t)EM_BLOCKS * (CDA_EM_MAX_MODULES * CDA_EM_AGENT_FIELDS + CDA_EM_ENV_FIELDS) * sizeof(double));
     if (he == hipSuccess) he = hipDeviceSynchronize();
-    if (he != hipSuccess) { (void)hipFree(e->arena); (void)hipFree(e->rows); free(e->rows_host); if (e->em_partials) (void)hipFree(e->em_partials); free(e); return hip_fail(he, "k_init_arena"); }
+    if (he != hipSuccess) { env_free(e); return hip_fail(he, "k_init_arena"); }
     if (cda_policy_step_supported(e)) (void)grant_policy_step_lds(e);          // (a refusal resurfaces as CDA_ERR_HIP at the first cda_policy_step_range)
     *out = e;
     return CDA_OK;
@@ -867,55 +888,43 @@ int cda_create(const cda_config* cfg, int32_t n_markets, int32_t device, cda_env
 int cda_destroy(cda_env* e) {
     if (!e) return CDA_OK;
     (void)hipSetDevice(e->device);
-    (void)hipFree(e->arena);
-    if (e->em_partials) (void)hipFree(e->em_partials);
-    if (e->snap_flag) (void)hipFree(e->snap_flag);
-    tape_free(e);
-    schedule_free(e);
-    quotes_free(e);
-    if (e->rows) (void)hipFree(e->rows);
-    free(e->rows_host);
-    free(e);
+    env_free(e);
     return CDA_OK;
 }
 
 int cda_set_market_params(cda_env* e, int32_t first_market, int32_t n_markets, const cda_market_params* rows_host) {
-    if (!e || !rows_host || n_markets < 1 || first_market < 0 || (int64_t)first_market + (int64_t)n_markets > (int64_t)e->P.n_markets) return CDA_ERR_INVALID;
+    if (!e || !rows_host || !range_ok(e, first_market, n_markets)) return CDA_ERR_INVALID;
     const int64_t cap = e->cap, ring = e->P.lay.spill_cap;
     for (int32_t i = 0; i < n_markets; i++) {
         const cda_market_params* r = rows_host + i;
         const int rc = row_ok(&e->P.cfg, r);
         if (rc) return rc;
         // cda_create cut the ring so that the largest decodable size times the orders of a side stays in int32: a row must keep to that ring
-        const int64_t scale = (int64_t)r->mkt_max_size * (int64_t)r->limit_size_multiple + (int64_t)r->min_size;
-        if (ring > 0 && scale * (cap + ring) > 0x7fffffffLL) return CDA_ERR_INVALID;
+        if (ring > 0 && !size_scale_ok(r->mkt_max_size, r->limit_size_multiple, r->min_size, cap + ring, 0x7fffffffLL)) return CDA_ERR_INVALID;
     }
-    MktRow* staged = (MktRow*)malloc(sizeof(MktRow) * (size_t)n_markets);
+    HostBuf<MktRow> staged((size_t)n_markets);
     if (!staged) return CDA_ERR_NOMEM;
     for (int32_t i = 0; i < n_markets; i++) staged[i] = device_row(rows_host + i);
     hipError_t he = hipSetDevice(e->device);
     // a launch in flight on any stream reads the rows it started with: the table is rewritten once the device is idle
     if (he == hipSuccess) he = hipDeviceSynchronize();
     if (he == hipSuccess) he = hipMemcpy(e->rows + first_market, staged, sizeof(MktRow) * (size_t)n_markets, hipMemcpyHostToDevice);
-    free(staged);
     if (he != hipSuccess) return hip_fail(he, "cda_set_market_params");
     memcpy(e->rows_host + first_market, rows_host, sizeof(cda_market_params) * (size_t)n_markets);
     return CDA_OK;
 }
 
 int cda_get_market_params(const cda_env* e, int32_t first_market, int32_t n_markets, cda_market_params* rows_host_out) {
-    if (!e || !rows_host_out || n_markets < 1 || first_market < 0 || (int64_t)first_market + (int64_t)n_markets > (int64_t)e->P.n_markets) return CDA_ERR_INVALID;
+    if (!e || !rows_host_out || !range_ok(e, first_market, n_markets)) return CDA_ERR_INVALID;
     memcpy(rows_host_out, e->rows_host + first_market, sizeof(cda_market_params) * (size_t)n_markets);
     return CDA_OK;
 }
 
-static int range_ok(const cda_env* e, int32_t first, int32_t n) { return first >= 0 && n >= 1 && (int64_t)first + (int64_t)n <= (int64_t)e->P.n_markets; }
-
 int cda_reset_range(cda_env* e, int32_t first_market, int32_t n_markets, const uint64_t* seeds, const uint8_t* mask, float* obs_out, void* stream) {
     if (!e || !range_ok(e, first_market, n_markets)) return CDA_ERR_INVALID;
     HIPCHK(hipSetDevice(e->device));
-    LAUNCH_CAP(e, k_reset, grid_for(n_markets), dim3(64 * CDA_WPB), smem_for(e, CDA_WPB), (hipStream_t)stream, e->arena, e->P, seeds, mask, obs_out,
-                       (int)first_market, (int)(first_market + n_markets), e->handback, handback_stride_of(e->P.cfg.num_agents), 0, FinCapture{NULL, NULL, NULL, 0});
+    launch(e->k->reset, waves_for(e, n_markets, 0, (hipStream_t)stream), e->arena, e->P, seeds, mask, obs_out, (int)first_market, (int)(first_market + n_markets),
+           e->handback, handback_stride_of(e->P.cfg.num_agents), 0, FinCapture{NULL, NULL, NULL, 0});
     HIPCHK(hipGetLastError());
     return tape_after_reset(e, first_market, n_markets, mask, (hipStream_t)stream);
 }
@@ -928,31 +937,17 @@ int cda_reset(cda_env* e, const uint64_t* seeds, const uint8_t* mask, float* obs
 static int launch_step(cda_env* e, int32_t first, int32_t n, const StepArgs& S0, hipStream_t stream) {
     if (e->sched.sched_of) { const int rcs = schedule_play(e, first, n, stream); if (rcs) return rcs; }      // an attached order schedule: the markets' windows first
     if (e->quotes.ring) { const int rcq = quotes_record(e, first, n, stream); if (rcq) return rcq; }          // quotes on: the book as this step's orders meet it
-    const size_t smem = smem_for(e, CDA_WPB) + ZIG_LDS_BYTES;
-    const bool tally = e->P.lay.ep_on != 0;               // episode metrics on: the instances that tally (their code is not even in the others)
-#define CDA_LAUNCH_STEP(ns) do { \
-        cda::ns::StepKernArgs K; K.arena = e->arena; K.P = e->P; K.S = S0; K.S.first_market = first; K.S.end_market = first + n; \
-        if (K.S.has_info) { if (tally) hipLaunchKernelGGL((cda::ns::k_step<true, true>), grid_for(n), dim3(64 * CDA_WPB), smem, stream, K); \
-                            else hipLaunchKernelGGL((cda::ns::k_step<true, false>), grid_for(n), dim3(64 * CDA_WPB), smem, stream, K); } \
-        else { if (tally) hipLaunchKernelGGL((cda::ns::k_step<false, true>), grid_for(n), dim3(64 * CDA_WPB), smem, stream, K); \
-               else hipLaunchKernelGGL((cda::ns::k_step<false, false>), grid_for(n), dim3(64 * CDA_WPB), smem, stream, K); } } while (0)
-    // the trade tape is on: the instances that write it (k_tstep: the tape's block behind k_step's arguments; the tallies by the market's ST_EP_ON bit)
-#define CDA_LAUNCH_TSTEP(ns) do { \
-        cda::ns::TStepKernArgs KT; KT.K.arena = e->arena; KT.K.P = e->P; KT.K.S = S0; KT.K.S.first_market = first; KT.K.S.end_market = first + n; KT.T = e->tape; \
-        if (KT.K.S.has_info) hipLaunchKernelGGL((cda::ns::k_tstep<true>), grid_for(n), dim3(64 * CDA_WPB), smem, stream, KT); \
-        else hipLaunchKernelGGL((cda::ns::k_tstep<false>), grid_for(n), dim3(64 * CDA_WPB), smem, stream, KT); } while (0)
-    if (e->tape.ring) { if (e->cap == 512) CDA_LAUNCH_TSTEP(cap512); else CDA_LAUNCH_TSTEP(cap256); }
-    else if (e->cap == 512) CDA_LAUNCH_STEP(cap512); else CDA_LAUNCH_STEP(cap256);
-#undef CDA_LAUNCH_TSTEP
-#undef CDA_LAUNCH_STEP
+    StepArgs S = S0;
+    S.first_market = first; S.end_market = first + n;
+    // the instance by (trade tape on, info tensors, episode-metric tallies: their code is not even in the instances without)
+    e->k->step[e->tape.ring != NULL][S.has_info != 0][e->P.lay.ep_on != 0](waves_for(e, n, ZIG_LDS_BYTES, stream), e->arena, e->P, S, e->tape);
     HIPCHK(hipGetLastError());
     // auto_reset: in the info-less kernel a market whose episode ended resets itself as the kernel's last act (reset_after_step in
     // cda_kernels.inc); with info tensors the pass is a launch of its own behind the step (every market-wave of it exits at once unless its
     // episode just ended)
     if (e->P.cfg.auto_reset && S0.has_info) {
-        LAUNCH_CAP(e, k_reset, grid_for(n), dim3(64 * CDA_WPB), smem_for(e, CDA_WPB), stream, e->arena, e->P,
-                           (const uint64_t*)NULL, (const uint8_t*)e->done_buf, S0.obs_out, (int)first, (int)(first + n),
-                           e->handback, handback_stride_of(e->P.cfg.num_agents), 1, FinCapture{S0.fin_obs, S0.fin_count, S0.fin_index_out, S0.fin_cap});
+        launch(e->k->reset, waves_for(e, n, 0, stream), e->arena, e->P, (const uint64_t*)NULL, (const uint8_t*)e->done_buf, S0.obs_out, (int)first, (int)(first + n),
+               e->handback, handback_stride_of(e->P.cfg.num_agents), 1, FinCapture{S0.fin_obs, S0.fin_count, S0.fin_index_out, S0.fin_cap});
         HIPCHK(hipGetLastError());
         return tape_after_reset(e, first, n, e->done_buf, stream);
     }
@@ -975,17 +970,12 @@ static int fill_step_args(cda_env* e, StepArgs& S, const int32_t* category, cons
     return CDA_OK;
 }
 
-int cda_step_range(cda_env* e, int32_t first_market, int32_t n_markets,
-                   const int32_t* category, const float* size_mean, const float* size_sigma,
-                   const int32_t* price, const int32_t* price_offset, const uint8_t* present,
-                   float* obs_out, double* reward_out, uint8_t* terminated_out, uint8_t* truncated_out,
-                   const cda_info_ptrs* info_out, void* stream) {
-    StepArgs S;
-    int rc = fill_step_args(e, S, category, size_mean, size_sigma, price, price_offset, present, obs_out, reward_out, terminated_out, truncated_out, info_out);
-    if (rc) return rc;
-    if (!range_ok(e, first_market, n_markets)) return CDA_ERR_INVALID;
-    HIPCHK(hipSetDevice(e->device));
-    return launch_step(e, first_market, n_markets, S, (hipStream_t)stream);
+// the episode-end capture of a step (fin_index_out == NULL: off): an auto_reset env, with somewhere to put the final observations and their count
+static int capture_args(const cda_env* e, StepArgs& S, float* fin_obs, int32_t fin_cap, int32_t* fin_count, int32_t* fin_index_out) {
+    if (!fin_index_out) return CDA_OK;
+    if (!e->P.cfg.auto_reset || !fin_obs || !fin_count || fin_cap < 1) return CDA_ERR_INVALID;
+    S.fin_obs = fin_obs; S.fin_count = fin_count; S.fin_index_out = fin_index_out; S.fin_cap = fin_cap;
+    return CDA_OK;
 }
 
 int cda_step_range_capture(cda_env* e, int32_t first_market, int32_t n_markets,
@@ -997,37 +987,32 @@ int cda_step_range_capture(cda_env* e, int32_t first_market, int32_t n_markets,
     int rc = fill_step_args(e, S, category, size_mean, size_sigma, price, price_offset, present, obs_out, reward_out, terminated_out, truncated_out, info_out);
     if (rc) return rc;
     if (!range_ok(e, first_market, n_markets)) return CDA_ERR_INVALID;
-    if (fin_index_out) {
-        if (!e->P.cfg.auto_reset || !fin_obs || !fin_count || fin_cap < 1) return CDA_ERR_INVALID;
-        S.fin_obs = fin_obs; S.fin_count = fin_count; S.fin_index_out = fin_index_out; S.fin_cap = fin_cap;
-    }
+    if ((rc = capture_args(e, S, fin_obs, fin_cap, fin_count, fin_index_out))) return rc;
     HIPCHK(hipSetDevice(e->device));
     return launch_step(e, first_market, n_markets, S, (hipStream_t)stream);
 }
 
+int cda_step_range(cda_env* e, int32_t first_market, int32_t n_markets,
+                   const int32_t* category, const float* size_mean, const float* size_sigma,
+                   const int32_t* price, const int32_t* price_offset, const uint8_t* present,
+                   float* obs_out, double* reward_out, uint8_t* terminated_out, uint8_t* truncated_out,
+                   const cda_info_ptrs* info_out, void* stream) {
+    return cda_step_range_capture(e, first_market, n_markets, category, size_mean, size_sigma, price, price_offset, present, obs_out, reward_out, terminated_out, truncated_out,
+                                  info_out, NULL, 0, NULL, NULL, stream);
+}
+
 // The policy inside the step kernel (k_policy_step, cda_kernels.inc): what include/cda_mlp.h's rollout chains launch per step when the env qualifies.
-static int policy_step_lds(const cda_env* e) {            // dynamic LDS of k_policy_step at this env's shape; 0 = no instance for its history depth
+typedef void (*policy_step_kern_t)(cda::cap256::PolicyStepKernArgs);
+struct PolicyStep { int lds; policy_step_kern_t kern[2]; };      // dynamic LDS of k_policy_step at this env's shape (0 = no instance for its history depth); the instances without / with the episode-metric tallies
+static PolicyStep policy_step_of(const cda_env* e) {
     const cda_config& c = e->P.cfg;
     switch (c.n_hist) {
-        case 4: return cda::cap256::policy_step_lds_bytes(c.num_agents, c.n_hist);
-        case 1: return cda::cap256::policy_step_lds_bytes_h1(c.num_agents, c.n_hist);
-        case 2: return cda::cap256::policy_step_lds_bytes_h2(c.num_agents, c.n_hist);
-        case 3: return cda::cap256::policy_step_lds_bytes_h3(c.num_agents, c.n_hist);
-        case 6: return cda::cap256::policy_step_lds_bytes_h6(c.num_agents, c.n_hist);
-        case 7: return cda::cap256::policy_step_lds_bytes_h7(c.num_agents, c.n_hist);
-        case 8: return cda::cap256::policy_step_lds_bytes_h8(c.num_agents, c.n_hist);
-        default: return 0;
-    }
-}
-// the instance of k_policy_step for a history depth (NULL: none compiled), with / without the episode-metric tallies
-typedef void (*policy_step_kern_t)(cda::cap256::PolicyStepKernArgs);
-static policy_step_kern_t policy_step_kernel(int hist, bool tally) {
-    switch (hist) {
-        case 4: return tally ? cda::cap256::k_policy_step<true> : cda::cap256::k_policy_step<false>;
-#define CDA_PS_CASE(h) case h: return tally ? cda::cap256::k_policy_step_h##h<true> : cda::cap256::k_policy_step_h##h<false>;
-        CDA_PS_CASE(1) CDA_PS_CASE(2) CDA_PS_CASE(3) CDA_PS_CASE(6) CDA_PS_CASE(7) CDA_PS_CASE(8)
+#define CDA_PS_CASE(h, sfx) case h: return {cda::cap256::policy_step_lds_bytes##sfx(c.num_agents, c.n_hist), {cda::cap256::k_policy_step##sfx<false>, cda::cap256::k_policy_step##sfx<true>}};
+#define CDA_PS_DEPTH(h) CDA_PS_CASE(h, _h##h)
+        CDA_PS_CASE(4, ) CDA_HIST_DEPTHS(CDA_PS_DEPTH)
+#undef CDA_PS_DEPTH
 #undef CDA_PS_CASE
-        default: return nullptr;
+        default: return {0, {nullptr, nullptr}};
     }
 }
 // More than 64 KB of dynamic LDS has to be granted per device and kernel instance: once, under a lock (envs are created and stepped from several host threads - one per
@@ -1038,16 +1023,16 @@ static int grant_policy_step_lds(const cda_env* e) {
     const int hist = e->P.cfg.n_hist, slot = hist;
     std::lock_guard<std::mutex> lock(mu);
     if (granted[slot] >> (e->device & 63) & 1ull) return 0;
-    const policy_step_kern_t ks[2] = {policy_step_kernel(hist, false), policy_step_kernel(hist, true)};
-    if (!ks[0] || !ks[1]) return 1;
+    const PolicyStep ps = policy_step_of(e);
+    if (!ps.kern[0] || !ps.kern[1]) return 1;
     for (int k = 0; k < 2; k++)
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(ks[k]), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return 1;
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(ps.kern[k]), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return 1;
     granted[slot] |= 1ull << (e->device & 63);
     return 0;
 }
 int cda_policy_step_supported(const cda_env* e) {
     if (!e) return 0;
-    const int lds = e->cap == 256 ? policy_step_lds(e) : 0;
+    const int lds = e->cap == 256 ? policy_step_of(e).lds : 0;
     return lds > 0 && lds <= 160 * 1024 && e->P.cfg.num_agents <= 8 && !e->handback && !e->tape.ring && !e->script.slot && !e->sched.sched_of && !e->quotes.ring;      // (no k_policy_step instance writes the trade tape, asks a scripted law, plays an order schedule or records quotes)
 }
 // ... and whether it pays: every workgroup of k_policy_step streams the whole network for its sixteen rows, so the one launch wins while all of the env's
@@ -1071,13 +1056,11 @@ int cda_policy_step_range(cda_env* e, int32_t first_market, int32_t n_markets, c
     int rc = fill_step_args(e, S, category, size_mean, size_sigma, price, price_offset, NULL, obs_out, reward_out, terminated_out, truncated_out, NULL);
     if (rc) return rc;
     if (!range_ok(e, first_market, n_markets)) return CDA_ERR_INVALID;
-    if (fin_index_out) {
-        if (!e->P.cfg.auto_reset || !fin_obs || !fin_count || fin_cap < 1) return CDA_ERR_INVALID;
-        S.fin_obs = fin_obs; S.fin_count = fin_count; S.fin_index_out = fin_index_out; S.fin_cap = fin_cap;
-    }
+    if ((rc = capture_args(e, S, fin_obs, fin_cap, fin_count, fin_index_out))) return rc;
     HIPCHK(hipSetDevice(e->device));
-    const size_t smem = (size_t)policy_step_lds(e);
-    const policy_step_kern_t kern = policy_step_kernel(e->P.cfg.n_hist, e->P.lay.ep_on != 0);
+    const PolicyStep ps = policy_step_of(e);
+    const size_t smem = (size_t)ps.lds;
+    const policy_step_kern_t kern = ps.kern[e->P.lay.ep_on != 0];
     if (!kern) return CDA_ERR_UNSUPPORTED;
     if (grant_policy_step_lds(e)) return CDA_ERR_HIP;     // (normally a no-op: cda_create granted it - outside any stream capture)
     cda::cap256::PolicyStepKernArgs KA;
@@ -1086,8 +1069,7 @@ int cda_policy_step_range(cda_env* e, int32_t first_market, int32_t n_markets, c
     KA.F.category = category; KA.F.size_mean = size_mean; KA.F.size_sigma = size_sigma; KA.F.price = price; KA.F.price_offset = price_offset;
     KA.F.a_cont = a_cont; KA.F.logp = logp; KA.F.value = value; KA.F.rec = rec; KA.F.dist = dist;
     hipLaunchKernelGGL(kern, dim3((unsigned)((n_markets + cda::cap256::PS_WPB - 1) / cda::cap256::PS_WPB)), dim3(64 * cda::cap256::PS_WPB), smem, (hipStream_t)stream, KA);
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    return launch_status();
 }
 
 int cda_step(cda_env* e, const int32_t* category, const float* size_mean, const float* size_sigma,
@@ -1104,25 +1086,6 @@ void cda_group_range(int32_t n_markets, int32_t n_groups, int32_t group, int32_t
     const int64_t lo = (int64_t)n_markets * group / n_groups, hi = (int64_t)n_markets * (group + 1) / n_groups;
     if (first_out) *first_out = (int32_t)lo;
     if (count_out) *count_out = (int32_t)(hi - lo);
-}
-
-int cda_step_groups(cda_env* e, int32_t n_groups,
-                    const int32_t* category, const float* size_mean, const float* size_sigma,
-                    const int32_t* price, const int32_t* price_offset, const uint8_t* present,
-                    float* obs_out, double* reward_out, uint8_t* terminated_out, uint8_t* truncated_out,
-                    const cda_info_ptrs* info_out, void* const* streams) {
-    StepArgs S;
-    int rc = fill_step_args(e, S, category, size_mean, size_sigma, price, price_offset, present, obs_out, reward_out, terminated_out, truncated_out, info_out);
-    if (rc) return rc;
-    if (!streams || n_groups < 1 || n_groups > e->P.n_markets || n_groups > CDA_MAX_GROUPS) return CDA_ERR_INVALID;
-    HIPCHK(hipSetDevice(e->device));
-    for (int32_t g = 0; g < n_groups; g++) {
-        int32_t first, n;
-        cda_group_range(e->P.n_markets, n_groups, g, &first, &n);
-        rc = launch_step(e, first, n, S, (hipStream_t)streams[g]);
-        if (rc) return rc;
-    }
-    return CDA_OK;
 }
 
 // ---- the hand-back of every chain, natively: RCCL is called directly (resolved from the copy already loaded in the process) ----
@@ -1148,22 +1111,38 @@ static int handback_chain(cda_env* e, int32_t first, int32_t count, hipStream_t 
     hipLaunchKernelGGL(k_handback_unpack, dim3((unsigned)(((size_t)world * count + 3) / 4)), dim3(256), 0, stream, src, (int)world, (int)count,
                        (long long)(e->hb_row_stride > 0 ? e->hb_row_stride : e->P.n_markets), (long long)first, (int)A, (int)H, (int)stride, (long long)e->hb_rows_total,
                        obs_full, reward_full, term_full, trunc_full);
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    return launch_status();
 }
-int cda_handback_groups(cda_env* e, int32_t n_groups, void* const* streams, void* const* comms, int32_t world, void* const* gathered,
-                        float* obs_full, double* reward_full, uint8_t* terminated_full, uint8_t* truncated_full) {
-    if (!e || !e->handback || !streams || n_groups < 1 || n_groups > e->P.n_markets || n_groups > CDA_MAX_GROUPS || world < 1) return CDA_ERR_INVALID;
-    if (!obs_full || !reward_full || !terminated_full || !truncated_full || (world > 1 && (!comms || !gathered))) return CDA_ERR_INVALID;
+// what the chains' hand-back needs beside their streams: per chain a communicator and a gather buffer (more than one rank), and the full arrays they rebuild
+struct Handback { void* const* comms; int32_t world; void* const* gathered; float* obs_full; double* reward_full; uint8_t* term_full; uint8_t* trunc_full; };
+// n_groups chains over an env's markets, each on its own stream: its step (S), then ITS collective and rebuild (hb); either may be absent
+static int run_groups(cda_env* e, int32_t n_groups, void* const* streams, const StepArgs* S, const Handback* hb) {
+    if (!streams || n_groups < 1 || n_groups > e->P.n_markets || n_groups > CDA_MAX_GROUPS) return CDA_ERR_INVALID;
+    if (hb && (!e->handback || hb->world < 1 || !hb->obs_full || !hb->reward_full || !hb->term_full || !hb->trunc_full || (hb->world > 1 && (!hb->comms || !hb->gathered)))) return CDA_ERR_INVALID;
     HIPCHK(hipSetDevice(e->device));
     for (int32_t g = 0; g < n_groups; g++) {
         int32_t first, n;
         cda_group_range(e->P.n_markets, n_groups, g, &first, &n);
-        int rc = handback_chain(e, first, n, (hipStream_t)streams[g], comms ? comms[g] : NULL, world, gathered ? gathered[g] : NULL,
-                                obs_full, reward_full, terminated_full, truncated_full);
+        int rc = S ? launch_step(e, first, n, *S, (hipStream_t)streams[g]) : CDA_OK;
+        if (!rc && hb) rc = handback_chain(e, first, n, (hipStream_t)streams[g], hb->comms ? hb->comms[g] : NULL, hb->world, hb->gathered ? hb->gathered[g] : NULL,
+                                           hb->obs_full, hb->reward_full, hb->term_full, hb->trunc_full);
         if (rc) return rc;
     }
     return CDA_OK;
+}
+int cda_step_groups(cda_env* e, int32_t n_groups,
+                    const int32_t* category, const float* size_mean, const float* size_sigma,
+                    const int32_t* price, const int32_t* price_offset, const uint8_t* present,
+                    float* obs_out, double* reward_out, uint8_t* terminated_out, uint8_t* truncated_out,
+                    const cda_info_ptrs* info_out, void* const* streams) {
+    StepArgs S;
+    const int rc = fill_step_args(e, S, category, size_mean, size_sigma, price, price_offset, present, obs_out, reward_out, terminated_out, truncated_out, info_out);
+    return rc ? rc : run_groups(e, n_groups, streams, &S, NULL);
+}
+int cda_handback_groups(cda_env* e, int32_t n_groups, void* const* streams, void* const* comms, int32_t world, void* const* gathered,
+                        float* obs_full, double* reward_full, uint8_t* terminated_full, uint8_t* truncated_full) {
+    const Handback hb = {comms, world, gathered, obs_full, reward_full, terminated_full, truncated_full};
+    return e ? run_groups(e, n_groups, streams, NULL, &hb) : CDA_ERR_INVALID;
 }
 int cda_step_groups_handback(cda_env* e, int32_t n_groups,
                              const int32_t* category, const float* size_mean, const float* size_sigma,
@@ -1173,21 +1152,9 @@ int cda_step_groups_handback(cda_env* e, int32_t n_groups,
                              void* const* comms, int32_t world, void* const* gathered,
                              float* obs_full, double* reward_full, uint8_t* terminated_full, uint8_t* truncated_full) {
     StepArgs S;
-    int rc = fill_step_args(e, S, category, size_mean, size_sigma, price, price_offset, present, obs_out, reward_out, terminated_out, truncated_out, info_out);
-    if (rc) return rc;
-    if (!e->handback || !streams || n_groups < 1 || n_groups > e->P.n_markets || n_groups > CDA_MAX_GROUPS || world < 1) return CDA_ERR_INVALID;
-    if (!obs_full || !reward_full || !terminated_full || !truncated_full || (world > 1 && (!comms || !gathered))) return CDA_ERR_INVALID;
-    HIPCHK(hipSetDevice(e->device));
-    for (int32_t g = 0; g < n_groups; g++) {                 // every chain: its step, then ITS collective and rebuild, all on its own stream
-        int32_t first, n;
-        cda_group_range(e->P.n_markets, n_groups, g, &first, &n);
-        rc = launch_step(e, first, n, S, (hipStream_t)streams[g]);
-        if (rc) return rc;
-        rc = handback_chain(e, first, n, (hipStream_t)streams[g], comms ? comms[g] : NULL, world, gathered ? gathered[g] : NULL,
-                            obs_full, reward_full, terminated_full, truncated_full);
-        if (rc) return rc;
-    }
-    return CDA_OK;
+    const Handback hb = {comms, world, gathered, obs_full, reward_full, terminated_full, truncated_full};
+    const int rc = fill_step_args(e, S, category, size_mean, size_sigma, price, price_offset, present, obs_out, reward_out, terminated_out, truncated_out, info_out);
+    return rc ? rc : run_groups(e, n_groups, streams, &S, &hb);
 }
 
 int cda_run_random(cda_env* e, int32_t n_steps, uint64_t action_seed, uint64_t market_index_base,
@@ -1201,17 +1168,8 @@ int cda_run_random(cda_env* e, int32_t n_steps, uint64_t action_seed, uint64_t m
     R.n_steps = n_steps; R.seed = action_seed; R.market_base = market_index_base;
     R.obs_out = obs_out; R.return_out = episode_return_out; R.terminated_out = terminated_out; R.truncated_out = truncated_out;
     R.steps_out = steps_taken_out;
-#define CDA_LAUNCH_RUN(ns) do { cda::ns::RunKernArgs K; K.arena = e->arena; K.P = e->P; K.R = R; \
-        if (e->P.lay.ep_on) hipLaunchKernelGGL(cda::ns::k_run_random<true>, grid_for(e->P.n_markets), dim3(64 * CDA_WPB), smem_for(e, CDA_WPB) + ZIG_LDS_BYTES, (hipStream_t)stream, K); \
-        else hipLaunchKernelGGL(cda::ns::k_run_random<false>, grid_for(e->P.n_markets), dim3(64 * CDA_WPB), smem_for(e, CDA_WPB) + ZIG_LDS_BYTES, (hipStream_t)stream, K); } while (0)
-#define CDA_LAUNCH_TRUN(ns) do { cda::ns::TRunKernArgs KT; KT.K.arena = e->arena; KT.K.P = e->P; KT.K.R = R; KT.T = e->tape; \
-        hipLaunchKernelGGL(cda::ns::k_tape_run, grid_for(e->P.n_markets), dim3(64 * CDA_WPB), smem_for(e, CDA_WPB) + ZIG_LDS_BYTES, (hipStream_t)stream, KT); } while (0)
-    if (e->tape.ring) { if (e->cap == 512) CDA_LAUNCH_TRUN(cap512); else CDA_LAUNCH_TRUN(cap256); }
-    else if (e->cap == 512) CDA_LAUNCH_RUN(cap512); else CDA_LAUNCH_RUN(cap256);
-#undef CDA_LAUNCH_TRUN
-#undef CDA_LAUNCH_RUN
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    e->k->run_random[e->tape.ring != NULL][e->P.lay.ep_on != 0](waves_for(e, e->P.n_markets, ZIG_LDS_BYTES, (hipStream_t)stream), e->arena, e->P, R, e->tape);
+    return launch_status();
 }
 
 int cda_random_actions_host(uint64_t action_seed, uint64_t market_index_base, int32_t step, int32_t n_markets, int32_t num_agents,
@@ -1238,8 +1196,7 @@ int cda_random_actions(uint64_t action_seed, uint64_t market_index_base, int32_t
     const size_t blocks = (total + 255) / 256;
     hipLaunchKernelGGL(k_random_actions, dim3((unsigned)(blocks > 65535 ? 65535 : blocks)), dim3(256), 0, (hipStream_t)stream, action_seed, market_index_base,
                        (int)step0, (int)n_steps, (int)n_markets, (int)num_agents, category, size_mean, size_sigma, price, price_offset);
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    return launch_status();
 }
 
 int32_t cda_handback_stride(int32_t num_agents) { return num_agents >= 1 && num_agents <= CDA_MAX_AGENTS ? handback_stride_of(num_agents) : 0; }
@@ -1269,25 +1226,22 @@ int cda_handback_unpack(const void* records_dev, int32_t n_segments, int32_t seg
     hipLaunchKernelGGL(k_handback_unpack, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)records_dev, (int)n_segments,
                        (int)seg_records, (long long)seg_row_stride, (long long)row0, (int)num_agents, (int)n_hist, (int)handback_stride_of(num_agents),
                        (long long)n_rows_total, obs_full, reward_full, terminated_full, truncated_full);
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    return launch_status();
 }
 
 int cda_book_peak(cda_env* e, int32_t* peak_out, void* stream) {
     if (!e || !peak_out) return CDA_ERR_INVALID;
     HIPCHK(hipSetDevice(e->device));
-    hipLaunchKernelGGL(k_book_peak, dim3((unsigned)((e->P.n_markets + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const uint8_t*)e->arena, e->P, peak_out);
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    launch_1d(k_book_peak, e->P.n_markets, 256, 0, (hipStream_t)stream, (const uint8_t*)e->arena, e->P, peak_out);
+    return launch_status();
 }
 
 int cda_nav_conservation(cda_env* e, double tolerance, double* abs_error_out, uint8_t* violated_out, void* stream) {
     if (!e || !abs_error_out) return CDA_ERR_INVALID;
     HIPCHK(hipSetDevice(e->device));
-    hipLaunchKernelGGL(k_nav_conservation, dim3((unsigned)((e->P.n_markets + 63) / 64)), dim3(64), DEC_TABLE_BYTES, (hipStream_t)stream,
-                       (const uint8_t*)e->arena, e->P, tolerance, abs_error_out, violated_out);
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    launch_1d(k_nav_conservation, e->P.n_markets, 64, DEC_TABLE_BYTES, (hipStream_t)stream,
+              (const uint8_t*)e->arena, e->P, tolerance, abs_error_out, violated_out);
+    return launch_status();
 }
 
 int cda_episode_metrics_enable(cda_env* e, int32_t on, double nav_tolerance) {
@@ -1296,7 +1250,7 @@ int cda_episode_metrics_enable(cda_env* e, int32_t on, double nav_tolerance) {
     HIPCHK(hipDeviceSynchronize());
     e->P.lay.ep_on = on;
     e->P.ep_tol = nav_tolerance;
-    hipLaunchKernelGGL(k_ep_enable, dim3((unsigned)((e->P.n_markets + 255) / 256)), dim3(256), 0, 0, e->arena, e->P, (int)on);
+    launch_1d(k_ep_enable, e->P.n_markets, 256, 0, 0, e->arena, e->P, (int)on);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     return CDA_OK;
@@ -1307,8 +1261,7 @@ int cda_episode_metrics_collect(cda_env* e, const int32_t* module_of, int32_t n_
     hipLaunchKernelGGL(k_em_partial, dim3(EM_BLOCKS), dim3(256), 0, (hipStream_t)stream, e->arena, e->P, module_of, (int)n_modules, (int)(clear != 0), e->em_partials);
     const int n_out = n_modules * CDA_EM_AGENT_FIELDS + CDA_EM_ENV_FIELDS;
     hipLaunchKernelGGL(k_em_final, dim3((unsigned)n_out), dim3(64), 0, (hipStream_t)stream, (const double*)e->em_partials, (int)n_modules, agent_out, env_out);
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    return launch_status();
 }
 
 int cda_place_order(cda_env* e, int32_t market, int32_t trader, int32_t type, int32_t side, int32_t size, int32_t price) {
@@ -1316,8 +1269,8 @@ int cda_place_order(cda_env* e, int32_t market, int32_t trader, int32_t type, in
     if (type < 0 || type > 3 || side < 0 || side > 1 || size < 1) return CDA_ERR_INVALID;
     if (type != 0 && price < 1) return CDA_ERR_INVALID;
     HIPCHK(hipSetDevice(e->device));
-    if (e->tape.ring) LAUNCH_CAP(e, k_tape_place_order, dim3(1), dim3(64), smem_for(e, 1), 0, e->arena, e->P, market, trader, type, side, size, price, e->tape);
-    else LAUNCH_CAP(e, k_place_order, dim3(1), dim3(64), smem_for(e, 1), 0, e->arena, e->P, market, trader, type, side, size, price);
+    if (e->tape.ring) launch(e->k->tape_place_order, one_wave(e), e->arena, e->P, market, trader, type, side, size, price, e->tape);
+    else launch(e->k->place_order, one_wave(e), e->arena, e->P, market, trader, type, side, size, price);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     return CDA_OK;
@@ -1325,101 +1278,126 @@ int cda_place_order(cda_env* e, int32_t market, int32_t trader, int32_t type, in
 int cda_mark_to_mkt(cda_env* e, int32_t market) {
     if (!e || market < 0 || market >= e->P.n_markets) return CDA_ERR_INVALID;
     HIPCHK(hipSetDevice(e->device));
-    LAUNCH_CAP(e, k_mark_to_mkt, dim3(1), dim3(64), smem_for(e, 1), 0, e->arena, e->P, market);
+    launch(e->k->mark_to_mkt, one_wave(e), e->arena, e->P, market);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     return CDA_OK;
+}
+
+// ---- a market's record on the host: one statement of each layout, used in both directions (cda_get_book, cda_get_state, cda_set_state) --------------------------
+// header words <-> cda_market_state: X(first header word, field)
+#define CDA_STATE_U64(X) X(H_RNG_STATE_LO, rng_state_lo) X(H_RNG_STATE_HI, rng_state_hi) X(H_RNG_INC_LO, rng_inc_lo) X(H_RNG_INC_HI, rng_inc_hi)
+#define CDA_STATE_U32(X) X(H_HAS_U32, rng_has_uint32) X(H_UINTEGER, rng_uinteger) X(H_T_STEP, t_step) X(H_LOB_TIME, lob_time) X(H_NEXT_OID, next_order_id) \
+    X(H_LAST_PRICE, last_price) X(H_HAS_TRADE, has_trade) X(H_LAST_TRADE_PRICE, last_trade_price) X(H_DONE_MASK, done_mask) X(H_FLAGS, flags)
+static void state_from_header(cda_market_state* s, const uint32_t* h) {
+#define CDA_X64(w, f) s->f = (uint64_t)h[w] | ((uint64_t)h[w + 1] << 32);
+#define CDA_X32(w, f) s->f = (decltype(s->f))h[w];
+    CDA_STATE_U64(CDA_X64) CDA_STATE_U32(CDA_X32)
+#undef CDA_X64
+#undef CDA_X32
+}
+static void header_from_state(uint32_t* h, const cda_market_state* s) {
+#define CDA_X64(w, f) h[w] = (uint32_t)s->f; h[w + 1] = (uint32_t)(s->f >> 32);
+#define CDA_X32(w, f) h[w] = (uint32_t)s->f;
+    CDA_STATE_U64(CDA_X64) CDA_STATE_U32(CDA_X32)
+#undef CDA_X64
+#undef CDA_X32
+}
+// Acc <-> cda_account_state: X(Acc's field, the state's)
+#define CDA_ACC_FIELDS(X) X(cash, cash) X(hold, cash_on_hold) X(posval, position_val) X(vwap, vwap) X(nav, nav) X(prev_nav, prev_nav) X(max_nav, max_nav) \
+    X(net_position, net_position) X(num_trades, num_trades) X(num_trades_step, num_trades_step) X(num_passive_fills_step, num_passive_fills_step) \
+    X(order_step_placed, order_step_placed) X(num_rejected_step, num_rejected_step)
+static void state_from_acc(cda_account_state* o, const Acc& a) {
+#define CDA_X(af, sf) o->sf = a.af;
+    CDA_ACC_FIELDS(CDA_X)
+#undef CDA_X
+}
+static void acc_from_state(Acc& a, const cda_account_state* o) {
+#define CDA_X(af, sf) a.af = o->sf;
+    CDA_ACC_FIELDS(CDA_X)
+#undef CDA_X
+}
+// the four book words of an order (price, quantity, order id << 4 | owner, timestamp) <-> cda_order; false: owner or order id outside what the third word holds
+static cda_order order_from_words(const int32_t f[BOOK_FIELDS]) {
+    cda_order o;
+    o.price = f[0]; o.qty = f[1]; o.owner = f[2] & 15; o.order_id = (int32_t)((uint32_t)f[2] >> 4); o.timestamp = f[3];
+    return o;
+}
+static bool words_from_order(int32_t f[BOOK_FIELDS], const cda_order& o, int num_agents) {
+    if (o.owner < 0 || o.owner >= num_agents || o.order_id < 0 || o.order_id >= (1 << 27)) return false;
+    f[0] = o.price; f[1] = o.qty; f[2] = (int32_t)(((uint32_t)o.order_id << 4) | (uint32_t)o.owner); f[3] = o.timestamp;
+    return true;
+}
+static uint8_t* dev_record(const cda_env* e, int32_t market) { return e->arena + (size_t)market * (size_t)e->P.lay.stride; }
+static uint8_t* dev_spill(const cda_env* e, int32_t market) { return e->arena + spill_arena_off(e->P) + (size_t)market * spill_region_bytes(e->P.lay.spill_cap); }
+// the device idle, then `market`'s record on the host
+static int fetch_record(cda_env* e, int32_t market, HostBuf<uint8_t>& rec) {
+    HIPCHK(hipDeviceSynchronize());
+    if (!rec.alloc((size_t)e->P.lay.stride)) return CDA_ERR_NOMEM;
+    const hipError_t he = hipMemcpy(rec, dev_record(e, market), (size_t)e->P.lay.stride, hipMemcpyDeviceToHost);
+    return he == hipSuccess ? CDA_OK : hip_fail(he, "hipMemcpy D2H");
 }
 
 // one side of a market's book in queue order -> out[0 .. min(n, max_orders)); `rec` = host copy of the market record
 static int read_book_side(cda_env* e, int32_t market, const uint8_t* rec, int sd, cda_order* out, int32_t max_orders, int32_t* n_out) {
     const Params& P = e->P;
     const uint32_t* h = (const uint32_t*)rec;
-    const int32_t* tile = (const int32_t*)(rec + P.lay.book_off);
+    const int spill_cap = P.lay.spill_cap;
     int32_t shdr[16] = {0};
-    const bool has_tail = P.lay.spill_cap > 0 && (h[H_STATUS] & (uint32_t)(ST_TAIL_BID << sd)) != 0;
-    const uint8_t* sp = e->arena + spill_arena_off(P) + (size_t)market * spill_region_bytes(P.lay.spill_cap);
-    if (has_tail) HIPCHK(hipMemcpy(shdr, sp, sizeof shdr, hipMemcpyDeviceToHost));
-    const int tile_n = (int)(sd == 0 ? h[H_N_BIDS] : h[H_N_ASKS]), tail_n = has_tail ? shdr[sd] : 0, base = shdr[2 + sd];
-    if (tile_n < 0 || tile_n > e->cap || tail_n < 0 || tail_n > P.lay.spill_cap) return CDA_ERR_INVALID;
-    *n_out = tile_n + tail_n;
-    int32_t* ring = NULL;
-    const int want_tail = max_orders > tile_n ? (tail_n < max_orders - tile_n ? tail_n : max_orders - tile_n) : 0;
-    if (want_tail > 0) {                                 // the side's four ring arrays, whole (a dump is not a hot path)
-        const size_t bytes = (size_t)BOOK_FIELDS * (size_t)P.lay.spill_cap * 4;
-        ring = (int32_t*)malloc(bytes);
-        if (!ring) return CDA_ERR_NOMEM;
-        hipError_t he = hipMemcpy(ring, sp + 64 + (size_t)sd * bytes, bytes, hipMemcpyDeviceToHost);
-        if (he != hipSuccess) { free(ring); return hip_fail(he, "hipMemcpy D2H (spill ring)"); }
+    if (spill_cap > 0 && (h[H_STATUS] & (uint32_t)(ST_TAIL_BID << sd)) != 0) HIPCHK(hipMemcpy(shdr, dev_spill(e, market), sizeof shdr, hipMemcpyDeviceToHost));
+    BookView bv = book_view(h, (const int32_t*)(rec + P.lay.book_off), shdr, e->cap, spill_cap);
+    if (bv.tile_n[sd] < 0 || bv.tile_n[sd] > e->cap || bv.tail_n[sd] < 0 || bv.tail_n[sd] > spill_cap) return CDA_ERR_INVALID;
+    *n_out = bv.total(sd);
+    const int n = bv.total(sd) < max_orders ? bv.total(sd) : max_orders;
+    HostBuf<int32_t> region;                             // the market's spill region as the view indexes it: the header and THIS side's four ring arrays, whole
+    if (n > bv.tile_n[sd]) {                             // (a dump is not a hot path)
+        const size_t side_words = (size_t)BOOK_FIELDS * (size_t)spill_cap;
+        if (!region.alloc(16 + 2 * side_words)) return CDA_ERR_NOMEM;
+        memcpy(region, shdr, sizeof shdr);
+        const hipError_t he = hipMemcpy(region + 16 + (size_t)sd * side_words, dev_spill(e, market) + 64 + (size_t)sd * side_words * 4, side_words * 4, hipMemcpyDeviceToHost);
+        if (he != hipSuccess) return hip_fail(he, "hipMemcpy D2H (spill ring)");
+        bv.spill = region;
     }
-    for (int i = 0; i < tile_n + want_tail && i < max_orders; i++) {
+    for (int i = 0; i < n; i++) {
         int32_t f[BOOK_FIELDS];
-        for (int k = 0; k < BOOK_FIELDS; k++) {
-            if (i < tile_n) f[k] = tile[k * e->cap + book_phys_rt(e->cap, sd, i)];
-            else f[k] = ring[(size_t)k * (size_t)P.lay.spill_cap + ((uint32_t)(base + (i - tile_n)) & (uint32_t)(P.lay.spill_cap - 1))];
-        }
-        out[i].price = f[0]; out[i].qty = f[1]; out[i].owner = f[2] & 15; out[i].order_id = (int32_t)((uint32_t)f[2] >> 4); out[i].timestamp = f[3];
+        for (int k = 0; k < BOOK_FIELDS; k++) f[k] = bv.get(sd, k, i);
+        out[i] = order_from_words(f);
     }
-    free(ring);
     return CDA_OK;
 }
 int cda_get_book(cda_env* e, int32_t market, int32_t side, cda_order* orders_out_host, int32_t max_orders, int32_t* n_out_host) {
     if (!e || market < 0 || market >= e->P.n_markets || side < 0 || side > 1 || max_orders < 0 || (max_orders > 0 && !orders_out_host) || !n_out_host) return CDA_ERR_INVALID;
     HIPCHK(hipSetDevice(e->device));
-    const Params& P = e->P;
-    HIPCHK(hipDeviceSynchronize());
-    uint8_t* rec = (uint8_t*)malloc((size_t)P.lay.stride);
-    if (!rec) return CDA_ERR_NOMEM;
-    hipError_t he = hipMemcpy(rec, e->arena + (size_t)market * (size_t)P.lay.stride, (size_t)P.lay.stride, hipMemcpyDeviceToHost);
-    if (he != hipSuccess) { free(rec); return hip_fail(he, "hipMemcpy D2H"); }
-    int rc = read_book_side(e, market, rec, side, orders_out_host, max_orders, n_out_host);
-    free(rec);
-    return rc;
+    HostBuf<uint8_t> rec;
+    const int rc = fetch_record(e, market, rec);
+    if (rc) return rc;
+    return read_book_side(e, market, rec, side, orders_out_host, max_orders, n_out_host);
 }
 
 int cda_get_state(cda_env* e, int32_t market, cda_market_state* s) {
     if (!e || !s || market < 0 || market >= e->P.n_markets) return CDA_ERR_INVALID;
     HIPCHK(hipSetDevice(e->device));
     const Params& P = e->P;
-    HIPCHK(hipDeviceSynchronize());
-    uint8_t* rec = (uint8_t*)malloc((size_t)P.lay.stride);
-    if (!rec) return CDA_ERR_NOMEM;
-    hipError_t he = hipMemcpy(rec, e->arena + (size_t)market * (size_t)P.lay.stride, (size_t)P.lay.stride, hipMemcpyDeviceToHost);
-    if (he != hipSuccess) { free(rec); return hip_fail(he, "hipMemcpy D2H"); }
+    HostBuf<uint8_t> rec;
+    int rc = fetch_record(e, market, rec);
+    if (rc) return rc;
     memset(s, 0, sizeof *s);
-    const uint32_t* h = (const uint32_t*)rec;
-    s->rng_state_lo = (uint64_t)h[H_RNG_STATE_LO] | ((uint64_t)h[H_RNG_STATE_LO + 1] << 32);
-    s->rng_state_hi = (uint64_t)h[H_RNG_STATE_HI] | ((uint64_t)h[H_RNG_STATE_HI + 1] << 32);
-    s->rng_inc_lo = (uint64_t)h[H_RNG_INC_LO] | ((uint64_t)h[H_RNG_INC_LO + 1] << 32);
-    s->rng_inc_hi = (uint64_t)h[H_RNG_INC_HI] | ((uint64_t)h[H_RNG_INC_HI + 1] << 32);
-    s->rng_has_uint32 = h[H_HAS_U32]; s->rng_uinteger = h[H_UINTEGER];
-    s->t_step = (int32_t)h[H_T_STEP]; s->lob_time = (int32_t)h[H_LOB_TIME]; s->next_order_id = (int32_t)h[H_NEXT_OID];
-    s->last_price = (int32_t)h[H_LAST_PRICE]; s->has_trade = (int32_t)h[H_HAS_TRADE]; s->last_trade_price = (int32_t)h[H_LAST_TRADE_PRICE];
-    s->done_mask = h[H_DONE_MASK]; s->flags = h[H_FLAGS];
+    const uint32_t* h = (const uint32_t*)(const uint8_t*)rec;
+    state_from_header(s, h);
     {
         int32_t nn[2] = {0, 0};
-        for (int sd = 0; sd < 2; sd++) {
-            int rc = read_book_side(e, market, rec, sd, sd == 0 ? s->bids : s->asks, CDA_BOOK_CAP_MAX, &nn[sd]);
-            if (rc) { free(rec); return rc; }
-        }
+        for (int sd = 0; sd < 2; sd++)
+            if ((rc = read_book_side(e, market, rec, sd, sd == 0 ? s->bids : s->asks, CDA_BOOK_CAP_MAX, &nn[sd]))) return rc;
         s->n_bids = nn[0]; s->n_asks = nn[1];              // the true lengths; the arrays hold the first CDA_BOOK_CAP_MAX of each side
     }
     const Acc* ap = (const Acc*)(rec + P.lay.acc_off);
-    for (int a = 0; a < P.cfg.num_agents; a++) {
-        cda_account_state* o = &s->acc[a];
-        o->cash = ap[a].cash; o->cash_on_hold = ap[a].hold; o->position_val = ap[a].posval; o->vwap = ap[a].vwap;
-        o->nav = ap[a].nav; o->prev_nav = ap[a].prev_nav; o->max_nav = ap[a].max_nav;
-        o->net_position = ap[a].net_position; o->num_trades = ap[a].num_trades;
-        o->num_trades_step = ap[a].num_trades_step; o->num_passive_fills_step = ap[a].num_passive_fills_step;
-        o->order_step_placed = ap[a].order_step_placed; o->num_rejected_step = ap[a].num_rejected_step;
-    }
+    for (int a = 0; a < P.cfg.num_agents; a++) state_from_acc(&s->acc[a], ap[a]);
     const float* hp = (const float*)(rec + P.lay.hist_off);
     int H = P.cfg.n_hist, head = (int)h[H_HIST_HEAD];
     for (int j = 0; j < H; j++) {
         int slot = (head + j) % H;
         memcpy(s->hist + j * CDA_SNAPSHOT_DIM, hp + slot * CDA_SNAPSHOT_DIM, sizeof(float) * CDA_SNAPSHOT_DIM);
     }
-    free(rec);
     return CDA_OK;
 }
 
@@ -1433,26 +1411,27 @@ int cda_set_state(cda_env* e, int32_t market, const cda_market_state* s) {
     HIPCHK(hipSetDevice(e->device));
     const Params& P = e->P;
     const int CAP = e->cap;
-    HIPCHK(hipDeviceSynchronize());
-    uint8_t* rec = (uint8_t*)calloc(1, (size_t)P.lay.stride);
-    if (!rec) return CDA_ERR_NOMEM;
-    uint32_t* h = (uint32_t*)rec;
-    uint8_t* dev_rec = e->arena + (size_t)market * (size_t)P.lay.stride;
-    uint8_t* dev_spill = e->arena + spill_arena_off(P) + (size_t)market * spill_region_bytes(P.lay.spill_cap);
-    const bool keep_book = s->n_bids > CDA_BOOK_CAP_MAX || s->n_asks > CDA_BOOK_CAP_MAX;
-    int32_t* bp = (int32_t*)(rec + P.lay.book_off);
-    if (keep_book) {
-        hipError_t he = hipMemcpy(rec, dev_rec, (size_t)P.lay.stride, hipMemcpyDeviceToHost);
-        if (he != hipSuccess) { free(rec); return hip_fail(he, "hipMemcpy D2H"); }
+    HostBuf<uint8_t> rec;
+    HostBuf<int32_t> ring;                                  // a restored book's two spill rings, if it has a tail
+    const size_t side_words = (size_t)BOOK_FIELDS * (size_t)P.lay.spill_cap;
+    uint32_t* h;
+    if (s->n_bids > CDA_BOOK_CAP_MAX || s->n_asks > CDA_BOOK_CAP_MAX) {          // keep the book
+        const int rc = fetch_record(e, market, rec);
+        if (rc) return rc;
+        h = (uint32_t*)(uint8_t*)rec;
         int32_t shdr[16] = {0};
         if (P.lay.spill_cap > 0 && (h[H_STATUS] & ST_TAIL_ANY)) {
-            he = hipMemcpy(shdr, dev_spill, sizeof shdr, hipMemcpyDeviceToHost);
-            if (he != hipSuccess) { free(rec); return hip_fail(he, "hipMemcpy D2H"); }
+            const hipError_t he = hipMemcpy(shdr, dev_spill(e, market), sizeof shdr, hipMemcpyDeviceToHost);
+            if (he != hipSuccess) return hip_fail(he, "hipMemcpy D2H");
         }
-        const int cur_b = (int)h[H_N_BIDS] + ((h[H_STATUS] & ST_TAIL_BID) ? shdr[0] : 0), cur_a = (int)h[H_N_ASKS] + ((h[H_STATUS] & ST_TAIL_ASK) ? shdr[1] : 0);
-        if (cur_b != s->n_bids || cur_a != s->n_asks) { free(rec); return CDA_ERR_INVALID; }
+        const BookView bv = book_view(h, NULL, shdr, CAP, P.lay.spill_cap);
+        if (bv.total(0) != s->n_bids || bv.total(1) != s->n_asks) return CDA_ERR_INVALID;
         h[H_STATUS] &= ~(uint32_t)ST_LEVELS_VALID;
     } else {
+        HIPCHK(hipDeviceSynchronize());
+        if (!rec.alloc((size_t)P.lay.stride, true)) return CDA_ERR_NOMEM;
+        h = (uint32_t*)(uint8_t*)rec;
+        int32_t* bp = (int32_t*)(rec + P.lay.book_off);
         // tile / tail split of a restored book: everything in the tile when it fits, else the tile is shared evenly
         int tb = s->n_bids, ta = s->n_asks;
         if (tb + ta > CAP) {
@@ -1461,18 +1440,15 @@ int cda_set_state(cda_env* e, int32_t market, const cda_market_state* s) {
             tb = s->n_bids < CAP - ta ? s->n_bids : CAP - ta;
         }
         const int tail_n[2] = {s->n_bids - tb, s->n_asks - ta}, tile_n[2] = {tb, ta};
-        if (tail_n[0] > P.lay.spill_cap || tail_n[1] > P.lay.spill_cap) { free(rec); return CDA_ERR_INVALID; }
+        if (tail_n[0] > P.lay.spill_cap || tail_n[1] > P.lay.spill_cap) return CDA_ERR_INVALID;
         h[H_N_BIDS] = (uint32_t)tb; h[H_N_ASKS] = (uint32_t)ta;
         h[H_STATUS] = (tail_n[0] > 0 ? ST_TAIL_BID : 0) | (tail_n[1] > 0 ? ST_TAIL_ASK : 0) | (P.lay.ep_on ? ST_EP_ON : 0);
-        int32_t* ring = NULL;
-        const size_t side_bytes = (size_t)BOOK_FIELDS * (size_t)P.lay.spill_cap * 4;
-        if (tail_n[0] > 0 || tail_n[1] > 0) { ring = (int32_t*)calloc(1, 2 * side_bytes); if (!ring) { free(rec); return CDA_ERR_NOMEM; } }
+        if ((tail_n[0] > 0 || tail_n[1] > 0) && !ring.alloc(2 * side_words, true)) return CDA_ERR_NOMEM;
         for (int sd = 0; sd < 2; sd++) {
             const int n = sd == 0 ? s->n_bids : s->n_asks;
             for (int i = 0; i < n; i++) {
-                const cda_order* o = sd == 0 ? &s->bids[i] : &s->asks[i];
-                if (o->owner < 0 || o->owner >= P.cfg.num_agents || o->order_id < 0 || o->order_id >= (1 << 27)) { free(rec); free(ring); return CDA_ERR_INVALID; }
-                const int32_t f[BOOK_FIELDS] = {o->price, o->qty, (int32_t)(((uint32_t)o->order_id << 4) | (uint32_t)o->owner), o->timestamp};
+                int32_t f[BOOK_FIELDS];
+                if (!words_from_order(f, sd == 0 ? s->bids[i] : s->asks[i], P.cfg.num_agents)) return CDA_ERR_INVALID;
                 for (int k = 0; k < BOOK_FIELDS; k++) {
                     if (i < tile_n[sd]) bp[k * CAP + book_phys_rt(CAP, sd, i)] = f[k];
                     else ring[((size_t)sd * BOOK_FIELDS + (size_t)k) * (size_t)P.lay.spill_cap + (size_t)(i - tile_n[sd])] = f[k];
@@ -1481,36 +1457,20 @@ int cda_set_state(cda_env* e, int32_t market, const cda_market_state* s) {
         }
         if (ring) {
             const int32_t shdr[16] = {tail_n[0], tail_n[1], 0, 0};
-            hipError_t he = hipMemcpy(dev_spill, shdr, sizeof shdr, hipMemcpyHostToDevice);
-            if (he == hipSuccess) he = hipMemcpy(dev_spill + 64, ring, 2 * side_bytes, hipMemcpyHostToDevice);
-            free(ring);
-            if (he != hipSuccess) { free(rec); return hip_fail(he, "hipMemcpy H2D (spill ring)"); }
+            hipError_t he = hipMemcpy(dev_spill(e, market), shdr, sizeof shdr, hipMemcpyHostToDevice);
+            if (he == hipSuccess) he = hipMemcpy(dev_spill(e, market) + 64, ring, 2 * side_words * 4, hipMemcpyHostToDevice);
+            if (he != hipSuccess) return hip_fail(he, "hipMemcpy H2D (spill ring)");
         }
         h[H_PEAK_ORDERS] = (uint32_t)(s->n_bids + s->n_asks);
     }
-    h[H_RNG_STATE_LO] = (uint32_t)s->rng_state_lo; h[H_RNG_STATE_LO + 1] = (uint32_t)(s->rng_state_lo >> 32);
-    h[H_RNG_STATE_HI] = (uint32_t)s->rng_state_hi; h[H_RNG_STATE_HI + 1] = (uint32_t)(s->rng_state_hi >> 32);
-    h[H_RNG_INC_LO] = (uint32_t)s->rng_inc_lo; h[H_RNG_INC_LO + 1] = (uint32_t)(s->rng_inc_lo >> 32);
-    h[H_RNG_INC_HI] = (uint32_t)s->rng_inc_hi; h[H_RNG_INC_HI + 1] = (uint32_t)(s->rng_inc_hi >> 32);
-    h[H_HAS_U32] = s->rng_has_uint32; h[H_UINTEGER] = s->rng_uinteger;
-    h[H_T_STEP] = (uint32_t)s->t_step; h[H_LOB_TIME] = (uint32_t)s->lob_time; h[H_NEXT_OID] = (uint32_t)s->next_order_id;
-    h[H_LAST_PRICE] = (uint32_t)s->last_price; h[H_HAS_TRADE] = (uint32_t)s->has_trade; h[H_LAST_TRADE_PRICE] = (uint32_t)s->last_trade_price;
-    h[H_DONE_MASK] = s->done_mask; h[H_FLAGS] = s->flags;
+    header_from_state(h, s);
     h[H_SEEDED] = 1; h[H_HIST_HEAD] = 0;
     Acc* ap = (Acc*)(rec + P.lay.acc_off);
-    for (int a = 0; a < P.cfg.num_agents; a++) {
-        const cda_account_state* o = &s->acc[a];
-        ap[a].cash = o->cash; ap[a].hold = o->cash_on_hold; ap[a].posval = o->position_val; ap[a].vwap = o->vwap;
-        ap[a].nav = o->nav; ap[a].prev_nav = o->prev_nav; ap[a].max_nav = o->max_nav;
-        ap[a].net_position = o->net_position; ap[a].num_trades = o->num_trades;
-        ap[a].num_trades_step = o->num_trades_step; ap[a].num_passive_fills_step = o->num_passive_fills_step;
-        ap[a].order_step_placed = o->order_step_placed; ap[a].num_rejected_step = o->num_rejected_step;
-    }
+    for (int a = 0; a < P.cfg.num_agents; a++) acc_from_state(ap[a], &s->acc[a]);
     memcpy(rec + P.lay.hist_off, s->hist, sizeof(float) * (size_t)P.cfg.n_hist * CDA_SNAPSHOT_DIM);
     // (the running episode tallies behind the book tile are not part of the dump: they stay as they are)
-    hipError_t he = hipMemcpy(rec + P.lay.ep_off, dev_rec + P.lay.ep_off, (size_t)P.cfg.num_agents * sizeof(EpStats), hipMemcpyDeviceToHost);
-    if (he == hipSuccess) he = hipMemcpy(dev_rec, rec, (size_t)P.lay.stride, hipMemcpyHostToDevice);
-    free(rec);
+    hipError_t he = hipMemcpy(rec + P.lay.ep_off, dev_record(e, market) + P.lay.ep_off, (size_t)P.cfg.num_agents * sizeof(EpStats), hipMemcpyDeviceToHost);
+    if (he == hipSuccess) he = hipMemcpy(dev_record(e, market), rec, (size_t)P.lay.stride, hipMemcpyHostToDevice);
     if (he != hipSuccess) return hip_fail(he, "hipMemcpy H2D");
     return CDA_OK;
 }
@@ -1518,24 +1478,21 @@ int cda_set_state(cda_env* e, int32_t market, const cda_market_state* s) {
 int cda_get_raw_snapshot(cda_env* e, float* raw_out, void* stream) {
     if (!e || !raw_out) return CDA_ERR_INVALID;
     HIPCHK(hipSetDevice(e->device));
-    LAUNCH_CAP(e, k_raw_snapshot, grid_for(e->P.n_markets), dim3(64 * CDA_WPB), smem_for(e, CDA_WPB), (hipStream_t)stream, e->arena, e->P, raw_out);
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    launch(e->k->raw_snapshot, waves_for(e, e->P.n_markets, 0, (hipStream_t)stream), e->arena, e->P, raw_out);
+    return launch_status();
 }
 int cda_last_flags(cda_env* e, uint32_t* flags_out, void* stream) {
     if (!e || !flags_out) return CDA_ERR_INVALID;
     HIPCHK(hipSetDevice(e->device));
-    hipLaunchKernelGGL(k_flags, dim3((unsigned)((e->P.n_markets + 255) / 256)), dim3(256), 0, (hipStream_t)stream, e->arena, e->P, flags_out);
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    launch_1d(k_flags, e->P.n_markets, 256, 0, (hipStream_t)stream, e->arena, e->P, flags_out);
+    return launch_status();
 }
 
 int cda_check_invariants(cda_env* e, uint32_t* violations_out, void* stream) {
     if (!e || !violations_out) return CDA_ERR_INVALID;
     HIPCHK(hipSetDevice(e->device));
-    hipLaunchKernelGGL(k_check_invariants, dim3((unsigned)((e->P.n_markets + 63) / 64)), dim3(64), 0, (hipStream_t)stream, (const uint8_t*)e->arena, e->P, e->cap, violations_out);
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    launch_1d(k_check_invariants, e->P.n_markets, 64, 0, (hipStream_t)stream, (const uint8_t*)e->arena, e->P, e->cap, violations_out);
+    return launch_status();
 }
 
 int cda_selftest_dec(int32_t device, int32_t op, int32_t n, const cda_dec* a_host, const cda_dec* b_host, cda_dec* out_host) {
@@ -1544,16 +1501,15 @@ int cda_selftest_dec(int32_t device, int32_t op, int32_t n, const cda_dec* a_hos
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return CDA_ERR_NO_DEVICE;
     HIPCHK(hipSetDevice(device));
     if (n == 0) return CDA_OK;
-    cda_dec *da = NULL, *db = NULL, *dout = NULL;
+    DevBuf<cda_dec> da, db, dout;
     size_t bytes = (size_t)n * sizeof(cda_dec);
-    HIPCHK(hipMalloc((void**)&da, bytes)); HIPCHK(hipMalloc((void**)&dout, bytes));
+    HIPCHK(da.alloc(bytes)); HIPCHK(dout.alloc(bytes));
     HIPCHK(hipMemcpy(da, a_host, bytes, hipMemcpyHostToDevice));
-    if (b_host) { HIPCHK(hipMalloc((void**)&db, bytes)); HIPCHK(hipMemcpy(db, b_host, bytes, hipMemcpyHostToDevice)); }
-    hipLaunchKernelGGL(k_selftest_dec, dim3((unsigned)((n + 63) / 64)), dim3(64), DEC_TABLE_BYTES, 0, op, n, da, db, dout);
+    if (b_host) { HIPCHK(db.alloc(bytes)); HIPCHK(hipMemcpy(db, b_host, bytes, hipMemcpyHostToDevice)); }
+    launch_1d(k_selftest_dec, n, 64, DEC_TABLE_BYTES, 0, op, n, (const cda_dec*)da, (const cda_dec*)db, (cda_dec*)dout);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(out_host, dout, bytes, hipMemcpyDeviceToHost));
-    (void)hipFree(da); (void)hipFree(dout); if (db) (void)hipFree(db);
     return CDA_OK;
 }
 
@@ -1563,15 +1519,14 @@ int cda_selftest_libm(int32_t device, int32_t op, int32_t n, const double* x_hos
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return CDA_ERR_NO_DEVICE;
     HIPCHK(hipSetDevice(device));
     if (n == 0) return CDA_OK;
-    double *dx = NULL, *dy = NULL;
+    DevBuf<double> dx, dy;
     const size_t bytes = (size_t)n * sizeof(double);
-    HIPCHK(hipMalloc((void**)&dx, bytes)); HIPCHK(hipMalloc((void**)&dy, bytes));
+    HIPCHK(dx.alloc(bytes)); HIPCHK(dy.alloc(bytes));
     HIPCHK(hipMemcpy(dx, x_host, bytes, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_selftest_libm, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (int)op, (int)n, dx, dy);
+    launch_1d(k_selftest_libm, n, 256, 0, 0, (int)op, (int)n, (const double*)dx, (double*)dy);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(y_host, dy, bytes, hipMemcpyDeviceToHost));
-    (void)hipFree(dx); (void)hipFree(dy);
     return CDA_OK;
 }
 /* the SAME source compiled for the host: needs no GPU (the CPU suite checks the restatement against the machine's libm) */
@@ -1587,17 +1542,16 @@ int cda_selftest_rng(int32_t device, uint64_t seed, int32_t lo, int32_t hi, int3
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return CDA_ERR_NO_DEVICE;
     HIPCHK(hipSetDevice(device));
-    int32_t* dfi = NULL; double* dn = NULL; int32_t* dp = NULL; uint64_t* dfs = NULL;
+    DevBuf<int32_t> dfi, dp; DevBuf<double> dn; DevBuf<uint64_t> dfs;
     size_t nb = sizeof(double) * (size_t)n_steps * (size_t)n_normals + 8, pb = sizeof(int32_t) * (size_t)n_steps * (size_t)perm_n + 8;
-    HIPCHK(hipMalloc((void**)&dfi, 8)); HIPCHK(hipMalloc((void**)&dn, nb)); HIPCHK(hipMalloc((void**)&dp, pb)); HIPCHK(hipMalloc((void**)&dfs, 64));
-    hipLaunchKernelGGL(k_selftest_rng, dim3(1), dim3(64), 0, 0, seed, lo, hi, n_steps, n_normals, perm_n, dfi, dn, dp, dfs);
+    HIPCHK(dfi.alloc(8)); HIPCHK(dn.alloc(nb)); HIPCHK(dp.alloc(pb)); HIPCHK(dfs.alloc(64));
+    hipLaunchKernelGGL(k_selftest_rng, dim3(1), dim3(64), 0, 0, seed, lo, hi, n_steps, n_normals, perm_n, (int32_t*)dfi, (double*)dn, (int32_t*)dp, (uint64_t*)dfs);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(first_int_host, dfi, 4, hipMemcpyDeviceToHost));
     if (normals_host && n_steps * n_normals) HIPCHK(hipMemcpy(normals_host, dn, nb - 8, hipMemcpyDeviceToHost));
     if (perms_host && n_steps * perm_n) HIPCHK(hipMemcpy(perms_host, dp, pb - 8, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(final_state_host, dfs, 48, hipMemcpyDeviceToHost));
-    (void)hipFree(dfi); (void)hipFree(dn); (void)hipFree(dp); (void)hipFree(dfs);
     return CDA_OK;
 }
 

@@ -719,55 +719,17 @@ constexpr int PS_WPB = 16;
 #endif
 constexpr int PS_PF = CDA_PS_PF;                 // weight ring depth (k-steps in flight per wave)
 // one instance per compiled history depth (n_hist 4 under the plain name; the others as <name>_h<H>: include/cda_mlp.h CDA_MLP_HIST_VARIANTS)
-#define PS_NS mlpdev
-#define PS_NAME(x) x
-#include "cda_policy_step.inc"
+#define PS_NS CDA_HIST_SFX(mlpdev)
+#define PS_NAME(x) CDA_HIST_SFX(x)
+#define CDA_HIST_BODY "cda_policy_step.inc"
+#define CDA_HIST_OPEN
+#define CDA_HIST_CLOSE
+#include "cda_hist_variants.inc"
+#undef CDA_HIST_BODY
+#undef CDA_HIST_OPEN
+#undef CDA_HIST_CLOSE
 #undef PS_NS
 #undef PS_NAME
-#undef CDA_MLP_HIST
-#define CDA_MLP_HIST 1
-#define PS_NS mlpdev_h1
-#define PS_NAME(x) x##_h1
-#include "cda_policy_step.inc"
-#undef PS_NS
-#undef PS_NAME
-#undef CDA_MLP_HIST
-#define CDA_MLP_HIST 2
-#define PS_NS mlpdev_h2
-#define PS_NAME(x) x##_h2
-#include "cda_policy_step.inc"
-#undef PS_NS
-#undef PS_NAME
-#undef CDA_MLP_HIST
-#define CDA_MLP_HIST 3
-#define PS_NS mlpdev_h3
-#define PS_NAME(x) x##_h3
-#include "cda_policy_step.inc"
-#undef PS_NS
-#undef PS_NAME
-#undef CDA_MLP_HIST
-#define CDA_MLP_HIST 6
-#define PS_NS mlpdev_h6
-#define PS_NAME(x) x##_h6
-#include "cda_policy_step.inc"
-#undef PS_NS
-#undef PS_NAME
-#undef CDA_MLP_HIST
-#define CDA_MLP_HIST 7
-#define PS_NS mlpdev_h7
-#define PS_NAME(x) x##_h7
-#include "cda_policy_step.inc"
-#undef PS_NS
-#undef PS_NAME
-#undef CDA_MLP_HIST
-#define CDA_MLP_HIST 8
-#define PS_NS mlpdev_h8
-#define PS_NAME(x) x##_h8
-#include "cda_policy_step.inc"
-#undef PS_NS
-#undef PS_NAME
-#undef CDA_MLP_HIST
-#define CDA_MLP_HIST 4
 #endif
 
 struct RunKernArgs { uint8_t* arena; Params P; RunArgs R; };

@@ -49,7 +49,7 @@ __device__ __forceinline__ bool order_msg_valid(const uint4& q, int A) {
     return trader >= 0 && trader < A && type >= 0 && type <= 3 && side >= 0 && side <= 1 && size >= 1 && (type == 0 || price >= 1);
 }
 
-// the wave's message chunk: 64 x 16 bytes of the workgroup's dynamic LDS behind the CDA_WPB market images (ORDER_STAGE_BYTES per wave on top of smem_for)
+// the wave's message chunk: 64 x 16 bytes of the workgroup's dynamic LDS behind the CDA_WPB market images (ORDER_STAGE_BYTES per wave on top of the images)
 __device__ __forceinline__ uint4* order_stage(const Params& P, int wave) {
     return reinterpret_cast<uint4*>(cda_smem + DEC_TABLE_BYTES + (size_t)CDA_WPB * (size_t)lds_bytes_per_wave(P.cfg.num_agents, P.cfg.n_hist) + (size_t)wave * ORDER_STAGE_BYTES);
 }
@@ -204,10 +204,10 @@ int cda_submit_orders_window(cda_env* e, int32_t first_market, int32_t n_markets
     cda::OrderStreamArgs S;
     S.offsets = (const long long*)offsets_dev; S.msgs = (const uint4*)msgs_dev; S.results = (uint4*)results_dev; S.summary = (uint4*)summary_dev;
     S.n_msgs = n_msgs; S.skip = skip; S.limit = limit; S.first = first_market; S.n = n_markets; S.flags = flags;
-    if (e->tape.ring) LAUNCH_CAP(e, k_tape_order_stream, grid_for(n_markets), dim3(64 * CDA_WPB), smem_for(e, CDA_WPB) + (size_t)CDA_WPB * cda::ORDER_STAGE_BYTES, (hipStream_t)stream, e->arena, e->P, S, e->tape);
-    else LAUNCH_CAP(e, k_order_stream, grid_for(n_markets), dim3(64 * CDA_WPB), smem_for(e, CDA_WPB) + (size_t)CDA_WPB * cda::ORDER_STAGE_BYTES, (hipStream_t)stream, e->arena, e->P, S);
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    const cda::Launch l = waves_for(e, n_markets, (size_t)CDA_WPB * cda::ORDER_STAGE_BYTES, (hipStream_t)stream);
+    if (e->tape.ring) launch(e->k->tape_order_stream, l, e->arena, e->P, S, e->tape);
+    else launch(e->k->order_stream, l, e->arena, e->P, S);
+    return launch_status();
 }
 int cda_submit_orders(cda_env* e, int32_t first_market, int32_t n_markets, const int64_t* offsets_dev, const cda_order_msg* msgs_dev, cda_order_result* results_dev,
                       int32_t* summary_dev, uint32_t flags, void* stream) {

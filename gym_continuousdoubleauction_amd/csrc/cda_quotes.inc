@@ -302,8 +302,7 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_tape_spreads(const uint8_t* ar
 static int quotes_record(cda_env* e, int32_t first, int32_t n, hipStream_t stream) {
     if (!e->quotes.ring) return CDA_OK;
     hipLaunchKernelGGL(k_quote_record, grid_for(n), dim3(64 * CDA_WPB), 0, stream, (const uint8_t*)e->arena, e->P, e->quotes, (int)e->cap, (int)first, (int)n);
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    return launch_status();
 }
 static void quotes_free(cda_env* e) {
     if (e->quotes.ring) (void)hipFree(e->quotes.ring);
@@ -319,14 +318,13 @@ int cda_quotes_enable(cda_env* e, int64_t capacity_steps) {
     HIPCHK(hipDeviceSynchronize());
     quotes_free(e);
     const size_t n = (size_t)e->P.n_markets;
-    uint4* ring = NULL; QuoteMeta* meta = NULL;
-    if (hipMalloc((void**)&ring, n * (size_t)capacity_steps * sizeof(cda_quote_record)) != hipSuccess) { (void)hipGetLastError(); return CDA_ERR_NOMEM; }
-    if (hipMalloc((void**)&meta, n * sizeof(QuoteMeta)) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(ring); return CDA_ERR_NOMEM; }
+    DevBuf<uint4> ring; DevBuf<QuoteMeta> meta;
+    if (ring.alloc(n * (size_t)capacity_steps * sizeof(cda_quote_record)) != hipSuccess || meta.alloc(n * sizeof(QuoteMeta)) != hipSuccess) { (void)hipGetLastError(); return CDA_ERR_NOMEM; }
     hipError_t he = hipMemset(ring, 0, n * (size_t)capacity_steps * sizeof(cda_quote_record));
     if (he == hipSuccess) he = hipMemset(meta, 0, n * sizeof(QuoteMeta));
     if (he == hipSuccess) he = hipDeviceSynchronize();
-    if (he != hipSuccess) { (void)hipFree(ring); (void)hipFree(meta); return hip_fail(he, "cda_quotes_enable"); }
-    e->quotes.ring = ring; e->quotes.meta = meta; e->quotes.cap = (uint32_t)capacity_steps; e->quotes.pad = 0;
+    if (he != hipSuccess) return hip_fail(he, "cda_quotes_enable");
+    e->quotes.ring = ring.release(); e->quotes.meta = meta.release(); e->quotes.cap = (uint32_t)capacity_steps; e->quotes.pad = 0;
     return CDA_OK;
 }
 int cda_quotes_disable(cda_env* e) {
@@ -347,8 +345,7 @@ int cda_quote_meta(cda_env* e, int32_t first_market, int32_t n_markets, int32_t*
     HIPCHK(hipSetDevice(e->device));
     hipLaunchKernelGGL(k_quote_meta, quote_grid(n_markets), dim3(64 * CDA_WPB), 0, (hipStream_t)stream, (const uint8_t*)e->arena, e->P, e->quotes, (int)first_market,
                        (int)n_markets, meta_out_dev);
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    return launch_status();
 }
 int cda_quote_series(cda_env* e, int32_t first_market, int32_t n_markets, int32_t which, int32_t k, void* records_out_dev, int32_t* counts_out_dev, int32_t* info_out_dev,
                      void* stream) {
@@ -358,8 +355,7 @@ int cda_quote_series(cda_env* e, int32_t first_market, int32_t n_markets, int32_
     HIPCHK(hipSetDevice(e->device));
     hipLaunchKernelGGL(k_quote_series, quote_grid(n_markets), dim3(64 * CDA_WPB), 0, (hipStream_t)stream, (const uint8_t*)e->arena, e->P, e->quotes, (int)first_market,
                        (int)n_markets, (int)which, (int)k, (uint4*)records_out_dev, counts_out_dev, info_out_dev);
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    return launch_status();
 }
 int cda_quote_stats(cda_env* e, int32_t first_market, int32_t n_markets, int32_t which, int64_t* stats_out_dev, int32_t* info_out_dev, void* stream) {
     if (!e || !stats_out_dev || !QUOTE_WHICH_OK(which) || !range_ok(e, first_market, n_markets) || ((uintptr_t)stats_out_dev & 7) != 0 ||
@@ -368,8 +364,7 @@ int cda_quote_stats(cda_env* e, int32_t first_market, int32_t n_markets, int32_t
     HIPCHK(hipSetDevice(e->device));
     hipLaunchKernelGGL(k_quote_stats, quote_grid(n_markets), dim3(64 * CDA_WPB), 0, (hipStream_t)stream, (const uint8_t*)e->arena, e->P, e->quotes, (int)first_market,
                        (int)n_markets, (int)which, (long long*)stats_out_dev, info_out_dev);
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    return launch_status();
 }
 int cda_tape_spreads(cda_env* e, int32_t first_market, int32_t n_markets, int32_t which, const int32_t* horizons_host, int32_t n_horizons, int64_t* spreads_out_dev,
                      int32_t* info_out_dev, void* stream) {
@@ -387,8 +382,7 @@ int cda_tape_spreads(cda_env* e, int32_t first_market, int32_t n_markets, int32_
     const size_t lds = (size_t)CDA_WPB * (size_t)e->P.cfg.num_agents * (size_t)n_horizons * 2 * SP_WORDS * sizeof(unsigned long long);      // <= 4 x 16 x 8 x 12 x 8 = 48 KiB
     hipLaunchKernelGGL(k_tape_spreads, quote_grid(n_markets), dim3(64 * CDA_WPB), lds, (hipStream_t)stream, (const uint8_t*)e->arena, e->P, e->tape, e->quotes,
                        (int)first_market, (int)n_markets, (int)which, (int)e->P.cfg.num_agents, (int)n_horizons, hz, (long long*)spreads_out_dev, info_out_dev);
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    return launch_status();
 }
 
 }  // extern "C"

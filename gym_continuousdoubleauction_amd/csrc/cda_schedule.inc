@@ -159,11 +159,10 @@ __global__ __launch_bounds__(64 * CDA_WPB, CDA_MIN_WAVES) void k_tsched_orders(u
 // the launch every step entry point issues first (launch_step); arguments validated by the callers
 static int schedule_play(cda_env* e, int32_t first, int32_t n, hipStream_t stream) {
     if (!e->sched.sched_of) return CDA_OK;
-    const size_t smem = smem_for(e, CDA_WPB) + (size_t)CDA_WPB * cda::ORDER_STAGE_BYTES;
-    if (e->tape.ring) LAUNCH_CAP(e, k_tsched_orders, grid_for(n), dim3(64 * CDA_WPB), smem, stream, e->arena, e->P, e->sched, (int)first, (int)n, e->tape);
-    else LAUNCH_CAP(e, k_sched_orders, grid_for(n), dim3(64 * CDA_WPB), smem, stream, e->arena, e->P, e->sched, (int)first, (int)n);
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    const cda::Launch l = waves_for(e, n, (size_t)CDA_WPB * cda::ORDER_STAGE_BYTES, stream);
+    if (e->tape.ring) launch(e->k->tsched_orders, l, e->arena, e->P, e->sched, (int)first, (int)n, e->tape);
+    else launch(e->k->sched_orders, l, e->arena, e->P, e->sched, (int)first, (int)n);
+    return launch_status();
 }
 static void schedule_free(cda_env* e) {
     if (e->sched.counts) (void)hipFree(e->sched.counts);
@@ -192,22 +191,22 @@ int cda_schedule_attach(cda_env* e, const int32_t* sched_of_dev, const int64_t* 
     // both index tables are read back and vetted before the env changes: one fault changes nothing
     HIPCHK(hipSetDevice(e->device));
     const size_t n_off = (size_t)n_sched * (size_t)(n_steps + 1), N = (size_t)e->P.n_markets;
-    int32_t* so = (int32_t*)malloc(N * sizeof(int32_t));
-    int64_t* off = (int64_t*)malloc(n_off * sizeof(int64_t));
-    if (!so || !off) { free(so); free(off); return CDA_ERR_NOMEM; }
+    HostBuf<int32_t> so(N);
+    HostBuf<int64_t> off(n_off);
+    if (!so || !off) return CDA_ERR_NOMEM;
     hipError_t he = hipMemcpy(so, sched_of_dev, N * sizeof(int32_t), hipMemcpyDeviceToHost);
     if (he == hipSuccess) he = hipMemcpy(off, step_offsets_dev, n_off * sizeof(int64_t), hipMemcpyDeviceToHost);
-    const int bad = he == hipSuccess ? cda_schedule_check_host(e->P.cfg.num_agents, e->P.n_markets, so, off, n_sched, n_steps, n_msgs) : 0;
-    free(so); free(off);
     if (he != hipSuccess) return hip_fail(he, "hipMemcpy(schedule tables)");
-    if (bad) return CDA_ERR_INVALID;
+    if (cda_schedule_check_host(e->P.cfg.num_agents, e->P.n_markets, so, off, n_sched, n_steps, n_msgs)) return CDA_ERR_INVALID;
     // a launch in flight reads the schedule it started with: the counters are cleared and the attachment changes once the device is idle
     HIPCHK(hipDeviceSynchronize());
+    DevBuf<long long> fresh;                                         // the counters table of a first attach: the env's (schedule_free) once it is cleared
     long long* counts = e->sched.counts;
-    if (!counts) HIPCHK(hipMalloc((void**)&counts, N * 4 * sizeof(long long)));
+    if (!counts) { HIPCHK(fresh.alloc(N * 4 * sizeof(long long))); counts = fresh; }
     he = hipMemset(counts, 0, N * 4 * sizeof(long long));
     if (he == hipSuccess) he = hipDeviceSynchronize();
-    if (he != hipSuccess) { if (!e->sched.counts) (void)hipFree(counts); return hip_fail(he, "hipMemset(schedule counters)"); }
+    if (he != hipSuccess) return hip_fail(he, "hipMemset(schedule counters)");
+    (void)fresh.release();
     e->sched.sched_of = sched_of_dev; e->sched.offsets = (const long long*)step_offsets_dev; e->sched.msgs = (const uint4*)msgs_dev; e->sched.counts = counts;
     e->sched.n_msgs = n_msgs; e->sched.n_sched = n_sched; e->sched.n_steps = n_steps; e->sched.flags = flags; e->sched.pad = 0;
     e->sched_epoch++;

@@ -96,12 +96,11 @@ int cda_scripted_attach(cda_env* e, const int32_t* slot_script_dev, const void* 
     HIPCHK(hipMemcpy(host, profiles_dev, (size_t)n_profiles * sizeof(cda_script_profile), hipMemcpyDeviceToHost));
     for (int k = 0; k < n_profiles; k++) if (!cda_script_profile_valid(&host[k])) return CDA_ERR_INVALID;
     const size_t slots = (size_t)e->P.n_markets * (size_t)e->P.cfg.num_agents;
-    int32_t* sl = (int32_t*)malloc(slots * sizeof(int32_t));
+    HostBuf<int32_t> sl(slots);
     if (!sl) return CDA_ERR_NOMEM;
     const hipError_t he = hipMemcpy(sl, slot_script_dev, slots * sizeof(int32_t), hipMemcpyDeviceToHost);
     bool ok = he == hipSuccess;
     for (size_t i = 0; ok && i < slots; i++) ok = sl[i] >= 0 && sl[i] <= n_profiles;
-    free(sl);
     if (he != hipSuccess) return hip_fail(he, "hipMemcpy(slot_script)");
     if (!ok) return CDA_ERR_INVALID;
     e->script.slot = slot_script_dev; e->script.profiles = (const cda_script_profile*)profiles_dev; e->script.n_profiles = n_profiles;
@@ -128,8 +127,7 @@ int cda_scripted_actions(cda_env* e, int32_t first_market, int32_t n_markets, co
     HIPCHK(hipSetDevice(e->device));
     hipLaunchKernelGGL(k_script_actions, grid_for(n_markets), dim3(64 * CDA_WPB), 0, (hipStream_t)stream, (const uint8_t*)e->arena, e->P, (int)e->cap, (int)first_market,
                        (int)n_markets, e->script, (const long long*)counter_dev, (long long)draw, category, size_mean, size_sigma, price, price_offset, a_cont, logp, record);
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    return launch_status();
 }
 
 int cda_scripted_decide_host(const void* profiles_host, int32_t n_profiles, const int32_t* profile_index_host, const void* views_host, int64_t n,

@@ -224,8 +224,7 @@ int cda_snapshot_offsets(cda_env* e, int32_t first_market, int32_t n_markets, in
     HIPCHK(hipSetDevice(e->device));
     hipLaunchKernelGGL(k_snap_offsets, dim3(1), dim3(SNAP_SCAN_THREADS), 0, (hipStream_t)stream, (const uint8_t*)e->arena, e->P, (int)first_market, (int)n_markets,
                        (long long*)offsets_dev);
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    return launch_status();
 }
 
 int cda_snapshot_pack(cda_env* e, int32_t first_market, int32_t n_markets, const int64_t* offsets_dev, void* blob_dev, int64_t blob_bytes, void* stream) {
@@ -244,8 +243,7 @@ int cda_snapshot_pack(cda_env* e, int32_t first_market, int32_t n_markets, const
     const dim3 grid((unsigned)((n_markets + CDA_WPB - 1) / CDA_WPB)), block(64 * CDA_WPB);
     hipLaunchKernelGGL(k_snap_pack<CDA_SNAP_NT_STORES != 0>, grid, block, 0, (hipStream_t)stream, (const uint8_t*)e->arena, e->P, (int)first_market, (int)n_markets,
                        (const long long*)offsets_dev, (uint8_t*)blob_dev, (long long)blob_bytes, A);
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    return launch_status();
 }
 
 // the config fields that must agree (book_spill may differ: the window is rebased; book_capacity is compared as the tile the env got)
@@ -275,7 +273,7 @@ int cda_snapshot_restore(cda_env* e, int32_t first_market, const void* blob_dev,
     if ((int64_t)src_first + (int64_t)n_markets > (int64_t)h.n_markets) return CDA_ERR_INVALID;
     if (!e->snap_flag) HIPCHK(hipMalloc((void**)&e->snap_flag, sizeof(uint32_t)));
     HIPCHK(hipMemsetAsync(e->snap_flag, 0, sizeof(uint32_t), st));
-    hipLaunchKernelGGL(k_snap_check, dim3((unsigned)((n_markets + 255) / 256)), dim3(256), 0, st, (const uint8_t*)blob_dev, (long long)h.total_bytes, (int)src_first,
+    launch_1d(k_snap_check, n_markets, 256, 0, st, (const uint8_t*)blob_dev, (long long)h.total_bytes, (int)src_first,
                        (int)n_markets, e->P, e->cap, e->snap_flag);
     HIPCHK(hipGetLastError());
     uint32_t bad = 1;

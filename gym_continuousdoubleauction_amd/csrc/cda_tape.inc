@@ -127,15 +127,13 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_tape_last(TapeArgs T, int firs
 // a reset of [first, first + n) under `mask` (NULL = all) has been queued on `stream`: the tape's counters follow it
 static int tape_after_reset(cda_env* e, int32_t first, int32_t n, const uint8_t* mask, hipStream_t stream) {
     if (!e->tape.ring) return CDA_OK;
-    hipLaunchKernelGGL(k_tape_episode, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, e->tape.meta, mask, (int)first, (int)(first + n));
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    launch_1d(k_tape_episode, n, 256, 0, stream, e->tape.meta, mask, (int)first, (int)(first + n));
+    return launch_status();
 }
 static int tape_after_restore(cda_env* e, int32_t first, int32_t n, hipStream_t stream) {
     if (!e->tape.ring) return CDA_OK;
-    hipLaunchKernelGGL(k_tape_partial, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, e->tape.meta, (int)first, (int)(first + n));
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    launch_1d(k_tape_partial, n, 256, 0, stream, e->tape.meta, (int)first, (int)(first + n));
+    return launch_status();
 }
 static void tape_free(cda_env* e) {
     if (e->tape.ring) (void)hipFree(e->tape.ring);
@@ -152,14 +150,13 @@ int cda_tape_enable(cda_env* e, int64_t capacity_records) {
     tape_free(e);
     if (capacity_records == 0) return CDA_OK;
     const size_t n = (size_t)e->P.n_markets;
-    uint4* ring = NULL; TapeMeta* meta = NULL;
-    if (hipMalloc((void**)&ring, n * (size_t)capacity_records * sizeof(cda_tape_record)) != hipSuccess) { (void)hipGetLastError(); return CDA_ERR_NOMEM; }
-    if (hipMalloc((void**)&meta, n * sizeof(TapeMeta)) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(ring); return CDA_ERR_NOMEM; }
+    DevBuf<uint4> ring; DevBuf<TapeMeta> meta;
+    if (ring.alloc(n * (size_t)capacity_records * sizeof(cda_tape_record)) != hipSuccess || meta.alloc(n * sizeof(TapeMeta)) != hipSuccess) { (void)hipGetLastError(); return CDA_ERR_NOMEM; }
     hipError_t he = hipMemset(ring, 0, n * (size_t)capacity_records * sizeof(cda_tape_record));
     if (he == hipSuccess) he = hipMemset(meta, 0, n * sizeof(TapeMeta));
     if (he == hipSuccess) he = hipDeviceSynchronize();
-    if (he != hipSuccess) { (void)hipFree(ring); (void)hipFree(meta); return hip_fail(he, "cda_tape_enable"); }
-    e->tape.ring = ring; e->tape.meta = meta; e->tape.cap = (uint32_t)capacity_records; e->tape.pad = 0;
+    if (he != hipSuccess) return hip_fail(he, "cda_tape_enable");
+    e->tape.ring = ring.release(); e->tape.meta = meta.release(); e->tape.cap = (uint32_t)capacity_records; e->tape.pad = 0;
     return CDA_OK;
 }
 int64_t cda_tape_capacity(const cda_env* e) { return e && e->tape.ring ? (int64_t)e->tape.cap : 0; }
@@ -168,10 +165,9 @@ int cda_tape_counts_ex(cda_env* e, int64_t* n_total_dev, int32_t* n_episode_dev,
     if (!e) return CDA_ERR_INVALID;
     if (!e->tape.ring) return CDA_ERR_UNSUPPORTED;
     HIPCHK(hipSetDevice(e->device));
-    hipLaunchKernelGGL(k_tape_counts, dim3((unsigned)((e->P.n_markets + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const TapeMeta*)e->tape.meta, (int)e->P.n_markets,
+    launch_1d(k_tape_counts, e->P.n_markets, 256, 0, (hipStream_t)stream, (const TapeMeta*)e->tape.meta, (int)e->P.n_markets,
                        (long long*)n_total_dev, n_episode_dev, episode_dev, partial_dev, n_previous_dev);
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    return launch_status();
 }
 int cda_tape_counts(cda_env* e, int64_t* n_total_dev, int32_t* n_episode_dev, int32_t* episode_dev, int32_t* partial_dev, void* stream) {
     return cda_tape_counts_ex(e, n_total_dev, n_episode_dev, episode_dev, partial_dev, NULL, stream);
@@ -182,8 +178,7 @@ int cda_tape_offsets(cda_env* e, int32_t first_market, int32_t n_markets, const 
     HIPCHK(hipSetDevice(e->device));
     hipLaunchKernelGGL(k_tape_offsets, dim3(1), dim3(TAPE_SCAN_THREADS), 0, (hipStream_t)stream, (const TapeMeta*)e->tape.meta, e->tape.cap, (int)first_market, (int)n_markets,
                        (const long long*)cursor_dev, (long long*)offsets_dev, (long long*)dropped_dev);
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    return launch_status();
 }
 int cda_tape_pack(cda_env* e, int32_t first_market, int32_t n_markets, int64_t* cursor_dev, const int64_t* offsets_dev, void* records_out_dev, int64_t capacity_records,
                   void* stream) {
@@ -193,8 +188,7 @@ int cda_tape_pack(cda_env* e, int32_t first_market, int32_t n_markets, int64_t* 
     HIPCHK(hipSetDevice(e->device));
     hipLaunchKernelGGL(k_tape_pack, dim3((unsigned)((n_markets + CDA_WPB - 1) / CDA_WPB)), dim3(64 * CDA_WPB), 0, (hipStream_t)stream, e->tape, (int)first_market, (int)n_markets,
                        (long long*)cursor_dev, (const long long*)offsets_dev, (uint4*)records_out_dev, (long long)capacity_records);
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    return launch_status();
 }
 int cda_tape_last_of(cda_env* e, int32_t first_market, int32_t n_markets, int32_t which, int32_t k, void* records_out_dev, int32_t* counts_out_dev, void* stream) {
     if (!e || !records_out_dev || k < 1 || (which != CDA_TAPE_CURRENT && which != CDA_TAPE_PREVIOUS) || !range_ok(e, first_market, n_markets) || ((uintptr_t)records_out_dev & 15) != 0) return CDA_ERR_INVALID;
@@ -202,8 +196,7 @@ int cda_tape_last_of(cda_env* e, int32_t first_market, int32_t n_markets, int32_
     HIPCHK(hipSetDevice(e->device));
     hipLaunchKernelGGL(k_tape_last, dim3((unsigned)((n_markets + CDA_WPB - 1) / CDA_WPB)), dim3(64 * CDA_WPB), 0, (hipStream_t)stream, e->tape, (int)first_market, (int)n_markets,
                        (int)which, (int)k, (uint4*)records_out_dev, counts_out_dev);
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    return launch_status();
 }
 int cda_tape_last(cda_env* e, int32_t first_market, int32_t n_markets, int32_t k, void* records_out_dev, int32_t* counts_out_dev, void* stream) {
     return cda_tape_last_of(e, first_market, n_markets, CDA_TAPE_CURRENT, k, records_out_dev, counts_out_dev, stream);

@@ -157,8 +157,7 @@ int cda_tape_bars(cda_env* e, int32_t first_market, int32_t n_markets, int32_t w
     HIPCHK(hipSetDevice(e->device));
     hipLaunchKernelGGL(k_tape_bars, dim3((unsigned)((n_markets + CDA_WPB - 1) / CDA_WPB)), dim3(64 * CDA_WPB), 0, (hipStream_t)stream, e->tape, (int)first_market, (int)n_markets,
                        (int)which, (int)bar_steps, (int)n_bars, (uint4*)bars_out_dev, info_out_dev);
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    return launch_status();
 }
 int cda_tape_flows(cda_env* e, int32_t first_market, int32_t n_markets, int32_t which, int64_t* flows_out_dev, int32_t* info_out_dev, void* stream) {
     if (!e || !flows_out_dev || (which != CDA_TAPE_CURRENT && which != CDA_TAPE_PREVIOUS) || !range_ok(e, first_market, n_markets) ||
@@ -168,8 +167,7 @@ int cda_tape_flows(cda_env* e, int32_t first_market, int32_t n_markets, int32_t 
     HIPCHK(hipSetDevice(e->device));
     hipLaunchKernelGGL(k_tape_flows, dim3((unsigned)((n_markets + CDA_WPB - 1) / CDA_WPB)), dim3(64 * CDA_WPB), 0, (hipStream_t)stream, e->tape, (int)first_market, (int)n_markets,
                        (int)which, (int)e->P.cfg.num_agents, (long long*)flows_out_dev, info_out_dev);
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    return launch_status();
 }
 
 }  // extern "C"

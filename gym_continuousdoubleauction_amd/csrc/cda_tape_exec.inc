@@ -186,8 +186,7 @@ int cda_tape_exec(cda_env* e, int32_t first_market, int32_t n_markets, int32_t w
     const size_t lds = (size_t)CDA_WPB * (size_t)e->P.cfg.num_agents * (size_t)(CDA_TAPE_STAT_WORDS + 8 * n_horizons) * sizeof(unsigned long long);
     hipLaunchKernelGGL(k_tape_exec, dim3((unsigned)((n_markets + CDA_WPB - 1) / CDA_WPB)), dim3(64 * CDA_WPB), lds, (hipStream_t)stream, e->tape, (int)first_market, (int)n_markets,
                        (int)which, (int)e->P.cfg.num_agents, (int)n_horizons, hz, (long long*)stats_out_dev, (long long*)markouts_out_dev, info_out_dev);
-    HIPCHK(hipGetLastError());
-    return CDA_OK;
+    return launch_status();
 }
 
 }  // extern "C"

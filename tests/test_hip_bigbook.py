@@ -199,3 +199,94 @@ def test_a_full_ring_is_flagged_never_silent():
     assert none.flags()[0] & K.FLAG_BOOK_OVERFLOW and none.get_state(0).n_bids == 256
     assert auto.flags()[0] == 0 and auto.get_state(0).n_bids == 300
     none.close(); auto.close()
+
+
+# ---- the host's view of a record (cda_get_book, cda_get_state, cda_set_state) on a ring whose base has moved ------------------------------------
+_RING_CFG = {"num_of_agents": 2, "init_cash": 10 ** 12, "max_step": 64, "is_render": False, "book_spill": 64}
+
+
+def _ring_market(with_oracle=True):
+    """1 market, 2 agents, tile 256, ring 64.  280 resting bids at falling prices fill the tile and start the tail behind it (ring base 0); a bid
+    above all of them then enters a full tile, whose last 32 orders are PREPENDED to the tail (tile_push_to_tail: base - 32, slots that wrap around the
+    ring's end); a market sell takes the top few.  The side: 225 - few orders in the tile, 56 in a ring that starts at slot 32 of 64."""
+    from hip_env import HipEnv
+    envs = [HipEnv(_RING_CFG, 1)] + ([O.OracleEnv(_RING_CFG, 1)] if with_oracle else [])
+    assert envs[0].env.book_spill == 64 and envs[0].env.book_capacity == 256
+    for e in envs:
+        e.reset(np.array([7], np.uint64))
+        for k in range(280):
+            e.place_order(0, k % 2, K.T_LIMIT, K.S_BID, 1 + k % 7, 10000 - k)
+        e.place_order(0, 1, K.T_LIMIT, K.S_BID, 3, 10001)
+        e.place_order(0, 0, K.T_MARKET, K.S_ASK, 3 + 1 + 2 + 3 + 2, 1)          # the orders at 10001 .. 9998 and part of the one at 9997
+    assert envs[0].flags()[0] == 0
+    return envs
+
+
+def _raw_get_book(hip, side, max_orders):
+    import ctypes as C
+    from gym_continuousdoubleauction_amd._lib import lib
+    n = C.c_int32(-1)
+    buf = (K.Order * max(max_orders, 1))()
+    rc = lib().cda_get_book(hip.env._h, 0, side, C.cast(buf, C.c_void_p) if max_orders else None, max_orders, C.byref(n))
+    assert rc == 0, rc
+    return np.ctypeslib.as_array(buf).view(np.int32).reshape(-1, 5)[:min(max_orders, n.value)].copy(), n.value
+
+
+def test_get_book_prefixes_on_a_ring_whose_base_has_moved():
+    hip, ora = _ring_market()
+    want = ora.get_book(0, K.S_BID)
+    total = len(want)
+    assert total == 281 - 4 and len(ora.get_book(0, K.S_ASK)) == 0
+    # nothing; inside the tile; one short of the tile's least (221) and most (256) possible count; between tile and total; the total; more than there is
+    for m in (0, 1, 10, 220, 257, total - 30, total - 1, total, total + 9):
+        got, n = _raw_get_book(hip, K.S_BID, m)
+        assert n == total, (m, n)
+        assert got.shape == want[:m].shape and np.array_equal(got, want[:m]), m
+    assert _raw_get_book(hip, K.S_ASK, 5)[1] == 0
+    assert (hip.env.check_invariants().cpu().numpy() == 0).all()
+    hip.close(); ora.close()
+
+
+def test_a_refused_set_state_changes_nothing():
+    import ctypes as C
+    from gym_continuousdoubleauction_amd._lib import lib
+    (hip,) = _ring_market(with_oracle=False)
+    before = bytes(hip.get_state(0))
+
+    def state(n_bids, bad_owner_at):
+        s = hip.get_state(0)
+        s.n_bids, s.n_asks = n_bids, 0
+        for k in range(n_bids):
+            b = s.bids[k]
+            b.price, b.qty, b.owner, b.order_id, b.timestamp = 20000 - k, 1, k % 2, k + 1, k + 1
+        if bad_owner_at is not None:
+            s.bids[bad_owner_at].owner = 2                                    # two agents: owners 0 and 1
+        return s
+
+    cases = {"owner out of range in the tile part": state(10, 3),
+             "owner out of range in the ring part": state(300, 290),          # 256 in the tile, 44 in the ring
+             "a tail longer than the ring": state(400, None)}                 # 256 in the tile, 144 > 64 behind it
+    for tag, s in cases.items():
+        assert lib().cda_set_state(hip.env._h, 0, C.byref(s)) == K.ERR_INVALID, tag
+        assert bytes(hip.get_state(0)) == before, tag
+        assert (hip.env.check_invariants().cpu().numpy() == 0).all(), tag
+    hip.close()
+
+
+def test_get_state_set_state_is_the_identity_on_a_moved_ring():
+    hip, ora = _ring_market()
+    s0 = hip.get_state(0)
+    assert bytes(s0) == bytes(ora.get_state(0))
+    hip.set_state(0, s0)                                                      # (re-split: 256 in the tile, the rest in a ring that starts at slot 0 again)
+    assert bytes(hip.get_state(0)) == bytes(s0)
+    _same_books(hip, ora, [0])
+    assert (hip.env.check_invariants().cpu().numpy() == 0).all()
+    acts = _trend(np.random.default_rng(5), 1, 2, 0, 0)
+    ho, hr, ht, htr, _ = hip.step(*acts)
+    oo, orw, ot, otr, _ = ora.step(*acts)
+    assert np.array_equal(ho.view(np.uint32), oo.view(np.uint32)) and np.array_equal(hr.view(np.uint64), orw.view(np.uint64))
+    assert np.array_equal(ht, ot) and np.array_equal(htr, otr)
+    _same_books(hip, ora, [0])
+    assert bytes(hip.get_state(0)) == bytes(ora.get_state(0))
+    assert hip.flags()[0] == 0 and (hip.env.check_invariants().cpu().numpy() == 0).all()
+    hip.close(); ora.close()
