@@ -603,6 +603,13 @@ __global__ void k_selftest_rng(uint64_t seed, int lo, int hi, int n_steps, int n
 // ==========================================================================================
 // scripted opponents (include/cda_scripted_agents.h, csrc/cda_scripted.inc): what cda_scripted_attach keeps - caller-owned device memory, as slot_net is
 struct ScriptArgs { const int32_t* slot; const cda_script_profile* profiles; int32_t n_profiles; int32_t pad; uint64_t seed, market_base; int64_t epoch; };
+// the label tap (include/cda.h cda_label_tap_attach, csrc/cda_scripted_label.inc): a second slot table and profile array with keys of their own, the mix word and the
+// six label buffers [rows][N][A] - caller-owned device memory, all of it
+struct LabelArgs {
+    const int32_t* slot; const cda_script_profile* profiles; int32_t n_profiles; int32_t rows; uint64_t seed, market_base;
+    const uint64_t* mix_q32;                                         // read by the kernel at every launch (NULL: never mixed)
+    int32_t* cat; float* mean; float* sigma; int32_t* price; int32_t* off; int32_t* played;      // played == NULL: not written
+};
 // the quote tape (include/cda.h cda_quotes_*, csrc/cda_quotes.inc): a market's meta row - eight int32 words - and what cda_quotes_enable keeps
 struct QuoteMeta {               // 32 B per market
     int64_t n_total;             // records since the quotes were enabled (the ring slot of record j is j % capacity)
@@ -630,6 +637,8 @@ struct cda_env {
     uint32_t* snap_flag;     // cda_snapshot_restore: the check pass's verdict (allocated at the first restore)
     TapeArgs tape;           // cda_tape_enable: the trade tape's rings and counters (ring == NULL: off - the launches are then the ones of an env without a tape)
     ScriptArgs script;       // cda_scripted_attach: the caller's resident slot table and profiles (slot == NULL: nothing attached - cda_scripted_actions launches nothing)
+    LabelArgs label;         // cda_label_tap_attach: the label table, its profiles, the mix word and the label buffers (slot == NULL: no tap - cda_scripted_step_actions is cda_scripted_actions)
+    int64_t label_epoch;     // moved by every cda_label_tap_attach / cda_label_tap_detach
     cda::SchedArgs sched;    // cda_schedule_attach: the caller's resident order schedule and the env's own counters table (sched_of == NULL: nothing attached - no launch)
     int64_t sched_epoch;     // moved by every cda_schedule_attach / cda_schedule_detach
     QuoteArgs quotes;        // cda_quotes_enable: the quote tape's rings and meta rows (ring == NULL: off - no launch)
@@ -1033,7 +1042,7 @@ static int grant_policy_step_lds(const cda_env* e) {
 int cda_policy_step_supported(const cda_env* e) {
     if (!e) return 0;
     const int lds = e->cap == 256 ? policy_step_of(e).lds : 0;
-    return lds > 0 && lds <= 160 * 1024 && e->P.cfg.num_agents <= 8 && !e->handback && !e->tape.ring && !e->script.slot && !e->sched.sched_of && !e->quotes.ring;      // (no k_policy_step instance writes the trade tape, asks a scripted law, plays an order schedule or records quotes)
+    return lds > 0 && lds <= 160 * 1024 && e->P.cfg.num_agents <= 8 && !e->handback && !e->tape.ring && !e->script.slot && !e->label.slot && !e->sched.sched_of && !e->quotes.ring;      // (no k_policy_step instance writes the trade tape, asks a scripted law, plays an order schedule or records quotes)
 }
 // ... and whether it pays: every workgroup of k_policy_step streams the whole network for its sixteen rows, so the one launch wins while all of the env's
 // workgroups are resident at once (N <= 16 x CUs: 4096 markets on an MI355X - policy in the loop 278 -> 301-308 M at 4096 x 4) and loses to the batched policy
@@ -1599,3 +1608,5 @@ int64_t cda_state_bytes_per_market(const cda_env* e) { return e ? (int64_t)e->P.
 #include "cda_schedule.inc"
 // the quote tape (cda_quotes_*, cda_quote_*, cda_tape_spreads): the top of the book per step, recorded ahead of every step, and the reductions over it
 #include "cda_quotes.inc"
+// the label tap (cda_label_*): a law's answer for slots it does not play, beside a rollout's buffers - one walk of the book serves the attached table and the label table
+#include "cda_scripted_label.inc"

@@ -1922,8 +1922,8 @@ static int rollout_chain(cda_env* env, const cda_league* L, const void* wb, cons
         } else rc = greedy ? launch_fwd<MODE_GREEDY>(P, rollout_mt(), st) : launch_fwd<MODE_SAMPLE>(P, rollout_mt(), st);
         if (rc) return rc;
         // scripted opponents (include/cda.h cda_scripted_attach): their slots' actions of the state the step is about to see, over what the policy launch wrote
-        // there; nothing attached: no launch
-        rc = cda_scripted_actions(env, first_market, n_markets, counter_dev, t, B->category + o, B->size_mean + o, B->size_sigma + o, B->price + o, B->price_offset + o,
+        // there; nothing attached: no launch.  With a label tap (cda_label_tap_attach) the same launch also labels the tapped slots into row t of the tap's buffers
+        rc = cda_scripted_step_actions(env, first_market, n_markets, counter_dev, t, B->category + o, B->size_mean + o, B->size_sigma + o, B->price + o, B->price_offset + o,
                                   B->a_cont + 2 * o, B->logp + o, B->record ? B->record + 8 * o : NULL, stream);
         if (rc) return rc;
         rc = cda_step_range_capture(env, first_market, n_markets, B->category + o, B->size_mean + o, B->size_sigma + o, B->price + o, B->price_offset + o, NULL,

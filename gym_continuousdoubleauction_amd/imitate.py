@@ -4,11 +4,13 @@ A rollout records the five env action tensors of EVERY slot - the scripted oppon
 market-step.  `Demonstrations` packs those actions into sample records (cda_bc_records: labels, raw Gaussian targets, a weight per sample); `BCUpdate` is
 mlp.FusedUpdate's separate-kernel minibatch step with cda_bc_loss_records in the loss position - the network kernels (forward, backward, weight gradients, Adam)
 are the PPO update's own, so every compiled variant (history depth, activation, vf_share_layers) trains; `pretrain` clones scripted experts (or distils a teacher
-policy) into a policy that `ppo.train_fused(policy=...)`, the league and `evaluate` take as it is.
+policy) into a policy that `ppo.train_fused(policy=...)`, the league and `evaluate` take as it is; `dagger` clones an expert from its LABELS of the learner's own states (the
+env's label tap, csrc/cda_scripted_label.inc), aggregated in a `DaggerBuffer`.
 
 `records_spec` and `bc_loss_spec` are the numpy / float64 statements of the two kernels (importable without a GPU): what the tests hold the kernels to.
 
     python -m gym_continuousdoubleauction_amd.imitate --expert maker --markets 1024 --agents 4 --iters 8 --horizon 64 --save maker.pt
+    python -m gym_continuousdoubleauction_amd.imitate --dagger --label-expert maker --opponent taker --beta 0.5 --iters 8 --horizon 64 --save maker.pt
 """
 import argparse
 import contextlib
@@ -177,6 +179,21 @@ class Demonstrations:
         s = stats.cpu()
         return cls(b["obs"][:T].reshape(T * N, -1).clone(), rec.view(T * N, A, 8), N, float(s[0]), int(s[1]))
 
+    @classmethod
+    def from_labels(cls, chains, tap, slot_src, slot_weight=None):
+        """the last run() of a mlp.RolloutChains on an env with a label tap (CDAVecEnv.label_tap) as demonstrations: the chain's observations with the tap's LABELS - what
+        the label law would have done in each slot's place - in the position of the actions: one cda_bc_records launch over rows 0 .. T - 1 of the label buffers.
+        slot_src / slot_weight: host tables [N, A], 1 (an env action: the label's five words) where a labelled slot counts, 0 elsewhere; a label is no policy sample, so
+        2 is refused."""
+        T, N, A = chains.T, chains.N, chains.A
+        if T > int(tap["rows"]):
+            raise ValueError(f"the tap holds {tap['rows']} rows, the rollout {T} steps")
+        if bool((np.asarray(slot_src) == SRC_POLICY).any()):
+            raise ValueError("labels are env actions (slot_src 1): there is no raw Gaussian sample to copy for slot_src 2")
+        rec, stats = pack_records(tap["category"][:T], tap["price"][:T], tap["price_offset"][:T], tap["size_mean"][:T], tap["size_sigma"][:T], None, slot_src, slot_weight)
+        s = stats.cpu()
+        return cls(chains.buf["obs"][:T].reshape(T * N, -1).clone(), rec.view(T * N, A, 8), N, float(s[0]), int(s[1]))
+
     def save(self, path):
         with open(path, "wb") as fh:                                            # (a file object: numpy appends no suffix to the name)
             np.savez(fh, format=DEMO_FORMAT, version=DEMO_VERSION, obs=self.obs.cpu().numpy(), rec=self.rec.cpu().numpy(), n_markets=self.n_markets,
@@ -203,6 +220,40 @@ class Demonstrations:
             rec = self.rec.view(self.T, N, self.A, 8)[:, ix].reshape(self.T * len(idx), self.A, 8)
             parts.append(Demonstrations(obs, rec, len(idx)))
         return tuple(parts)
+
+
+class DaggerBuffer:
+    """DAgger's aggregate D <- D u D_i at a fixed size: `capacity_iters` blocks of `rows_per_iter` rows each, block j % capacity_iters holding the j-th set of
+    demonstrations added (the oldest is overwritten once the buffer is full).  Rows not yet filled carry weight 0 - a loss skips them, and Demonstrations.loss_scale
+    normalises by the weight sum - so a BCUpdate is built ONCE, at the full size, and `demos` is always the whole buffer.  weight_sum and count are those of the
+    concatenation of the blocks it holds.  Plain tensors: device="cpu" needs no GPU."""
+
+    def __init__(self, capacity_iters, rows_per_iter, num_agents, obs_dim, n_markets, device="cpu"):
+        self.K, self.rows, self.A, self.n_markets = int(capacity_iters), int(rows_per_iter), int(num_agents), int(n_markets)
+        if self.K < 1 or self.rows < 1 or self.rows % self.n_markets:
+            raise ValueError("a DaggerBuffer holds capacity_iters >= 1 blocks of rows_per_iter rows, a multiple of n_markets")
+        self.obs = torch.zeros((self.K * self.rows, int(obs_dim)), dtype=torch.float32, device=device)
+        self.rec = torch.zeros((self.K * self.rows, self.A, 8), dtype=torch.float32, device=device)
+        self.added = 0
+        self._weight, self._count = [0.0] * self.K, [0] * self.K
+
+    filled = property(lambda self: min(self.added, self.K))
+
+    def add(self, demos):
+        """copy one iteration's demonstrations into the next block (wrapping); returns the block's index"""
+        if demos.R != self.rows or demos.A != self.A or demos.obs.shape[1] != self.obs.shape[1] or demos.n_markets != self.n_markets:
+            raise ValueError(f"this buffer takes blocks of {self.rows} rows x {self.A} agents of {self.obs.shape[1]}-float observations over {self.n_markets} markets")
+        j = self.added % self.K
+        self.obs[j * self.rows:(j + 1) * self.rows].copy_(demos.obs)
+        self.rec[j * self.rows:(j + 1) * self.rows].copy_(demos.rec)
+        self._weight[j], self._count[j] = demos.weight_sum, demos.count
+        self.added += 1
+        return j
+
+    @property
+    def demos(self):
+        """the whole buffer as Demonstrations (views, no copy): block-major, the unfilled blocks at weight 0"""
+        return Demonstrations(self.obs, self.rec, self.n_markets, float(sum(self._weight)), int(sum(self._count)))
 
 
 # ---- the update ---------------------------------------------------------------------------------------------------------------------------
@@ -367,6 +418,96 @@ def pretrain(env, experts=None, learner_slots=1, iters=8, horizon=64, epochs=4, 
     return policy, history
 
 
+def dagger(env, label_expert, opponents=None, learner_slots=1, iters=8, horizon=64, beta=1.0, beta_decay=0.5, aggregate=None, label_opponents=False, epochs=4, lr=1e-3,
+           seed=0, policy=None, hidden=(256, 256), activation="tanh", vf_share_layers=False, holdout=0.125, log=print, minibatch=65536, chains=4, use_graph=True, keep=None):
+    """DAgger (Ross, Gordon & Bagnell 2011) on the device: clone `label_expert` (a scripted.parse_profile spec) from labels of the LEARNER's own states.  pretrain()'s
+    demonstrations are the expert's answers to the expert's situation; here a label tap (CDAVecEnv.set_label_tap) asks the law, inside every step of the captured
+    rollout chains, what it would do in the learner's slot - with the learner's position, resting orders and place in the queue.
+    The learner plays the leading learner_slots slots of every market.  The slots behind them play `opponents` ([spec, ...]), attached as pretrain attaches experts -
+    slot learner_slots + j of market m plays opponents[(m + j) % P] -, or the league's uniform random module when opponents is None.  The tap labels the leading slots
+    with label_expert and, with label_opponents, every opponent slot with its own profile (its label is then its action).  Iteration i: set_label_mix(beta *
+    beta_decay ** i) - with that probability a learner slot plays the label instead of its sample (label_tap['played']) -, one rollout of `horizon` steps, the labels
+    packed as demonstrations (Demonstrations.from_labels), the training markets' share added to a DaggerBuffer of `aggregate` iterations (None: all `iters`, the
+    classic aggregate), `epochs` passes of ONE BCUpdate over the buffer, and the evaluation of this iteration's held-out markets (`holdout`) before and after.
+    Scripts and tap are detached on exit.  Returns (FusedPolicy, history): history[i] = {"iter", "beta", "train", "held_before", "held", "on_policy_agreement"} - the
+    last one the share of learner-slot samples with played == 0 whose executed category equals the label (reduced on the device; NaN when every sample was mixed in,
+    as at beta = 1).  Out of scope: a tap on the league chains' update, in checkpoints and snapshots, on the dict facades, data-parallel runs; a policy with the
+    state-dependent log-std head is refused."""
+    from . import scripted as SC
+    from .mlp import LEAGUE_RANDOM, FusedPolicy, PolicyBank, RolloutChains
+    if getattr(env, "scripted", False) or getattr(env, "label_tap", None) is not None:
+        raise ValueError("dagger attaches its own scripted opponents and label tap for the run: it needs an env without either (clear_scripted() / clear_label_tap() first)")
+    dev, N, A, T, k = env.obs.device, env.n_markets, env.num_agents, int(horizon), int(learner_slots)
+    if not 1 <= k <= A or (opponents is not None and k > A - 1):
+        raise ValueError(f"learner_slots must lie in 1 .. num_agents{' - 1' if opponents is not None else ''}, got {k}")
+    if not (0.0 <= float(beta) <= 1.0 and 0.0 <= float(beta_decay) <= 1.0):
+        raise ValueError("beta and beta_decay lie in [0, 1]")
+    if policy is None:
+        policy = FusedPolicy(dev, seed=seed, n_hist=env.n_hist, hidden=hidden, activation=activation, vf_share_layers=vf_share_layers)
+    if bool(getattr(policy, "state_dependent_log_std", False)):
+        raise ValueError("behaviour cloning runs the separate update kernels, which do not train the state-dependent log-std head: clone into a policy with a free log_std vector")
+    expert = SC.parse_profile(label_expert)
+    tap_profiles, slot_label = [expert], np.zeros((N, A), np.int32)
+    slot_label[:, :k] = 1
+    attach, bank = contextlib.nullcontext(), None
+    if opponents is not None:
+        opp = [SC.parse_profile(o) for o in opponents]
+        if not opp:
+            raise ValueError("opponents: None (random modules) or a non-empty list of scripted opponents")
+        opp_slots = SC.opponent_slots(N, A, k, len(opp))
+        attach = SC.attached(env, opp_slots, opp, seed=seed)
+        if label_opponents:
+            if 1 + len(opp) > SC.MAX_PROFILES:
+                raise ValueError(f"label_opponents: the tap's table holds the expert and the opponents, at most {SC.MAX_PROFILES} profiles")
+            tap_profiles += opp
+            slot_label[:, k:] = 1 + opp_slots[:, k:]
+    elif label_opponents:
+        raise ValueError("label_opponents needs scripted opponents: a random module has no law to label with")
+    else:                                                                      # the league chain: bank row 0 = the learner (refreshed from `policy` ahead of every rollout)
+        bank = PolicyBank(dev, N, A, 1, max_frozen=0, seed=seed, random_seed=seed, n_hist=policy.L.hist, activation=policy.activation, vf_share_layers=policy.vf_share_layers)
+        slot_net = np.full((N, A), LEAGUE_RANDOM, np.int32)
+        slot_net[:, :k] = 0
+        bank.set_slots(torch.from_numpy(slot_net))
+    slot_src = (slot_label != 0).astype(np.int32) * SRC_ENV
+    K = int(iters) if aggregate is None else int(aggregate)
+    if K < 1:
+        raise ValueError("aggregate: None or the number of iterations the buffer holds, at least 1")
+    env.reset(seed=seed)
+    history, upd, buf = [], None, None
+    with attach:
+        env.set_label_tap(slot_label, tap_profiles, rows=T, seed=seed, mix=beta)
+        try:
+            tap = env.label_tap
+            roll = RolloutChains(env, bank if bank is not None else policy, T, groups=chains, seed=seed, use_graphs=use_graph)
+            for it in range(int(iters)):
+                b = float(beta) * float(beta_decay) ** it
+                env.set_label_mix(b)
+                if bank is not None:
+                    bank.theta[0].copy_(policy.theta); bank.wb[0].copy_(policy.wb)
+                roll.run()
+                on = tap["played"][:T, :, :k] == 0
+                hit = (on & (roll.buf["category"][:, :, :k] == tap["category"][:T, :, :k])).sum().double() / on.sum().double()
+                train, held = Demonstrations.from_labels(roll, tap, slot_src).split(holdout, seed)
+                if upd is None:
+                    buf = DaggerBuffer(K, train.R, A, train.obs.shape[1], train.n_markets, device=dev)
+                    n_rows = buf.obs.shape[0] // 32 * 32
+                    if n_rows < 32:
+                        raise ValueError("DAgger needs at least 32 market-steps of training demonstrations in its buffer")
+                    upd = BCUpdate(policy, n_rows, _rows_mb(n_rows, A, minibatch), A)
+                buf.add(train)
+                before = upd.evaluate(held)
+                h = {"iter": it, "beta": b, "train": upd.run(buf.demos, epochs=epochs, lr=lr), "held_before": before, "held": upd.evaluate(held),
+                     "on_policy_agreement": float(hit)}
+                history.append(h)
+                log(json.dumps(h))
+            if keep is not None:
+                keep.update(train=train, held=held, update=upd, rollout=roll, buffer=buf, slot_src=slot_src, slot_label=slot_label)
+        finally:
+            if env.label_tap is not None:
+                env.clear_label_tap()
+    return policy, history
+
+
 def main(argv=None, parse_only=False):
     """parse_only: return the parsed arguments without touching a device (the flags' tests)"""
     p = argparse.ArgumentParser(description="clone scripted experts (or recorded demonstrations, or a teacher policy) into a policy file")
@@ -393,8 +534,22 @@ def main(argv=None, parse_only=False):
     p.add_argument("--demos-out", default=None, metavar="FILE.npz", help="save the last iteration's demonstrations (all markets)")
     p.add_argument("--demos", default=None, metavar="FILE.npz", help="clone these recorded demonstrations instead of rolling out (no env is created)")
     p.add_argument("--out", default=None, help="write a JSON summary to this file")
+    p.add_argument("--dagger", action="store_true", help="DAgger: label the learner's own states with --label-expert through the env's label tap (needs --label-expert; "
+                                                         "goes without --expert, --teacher and --demos)")
+    p.add_argument("--label-expert", default=None, metavar="SPEC", help="--dagger: the scripted law whose answers in the learner's slots are the labels")
+    p.add_argument("--opponent", action="append", default=None, metavar="SPEC", help="--dagger: a scripted opponent behind the learner's slots; repeat for several (default: random modules)")
+    p.add_argument("--beta", type=float, default=1.0, metavar="B", help="--dagger: the probability with which the learner's slot plays the label in iteration 0")
+    p.add_argument("--beta-decay", type=float, default=0.5, metavar="D", help="--dagger: iteration i mixes with beta * D ** i")
+    p.add_argument("--aggregate", type=int, default=None, metavar="K", help="--dagger: the iterations the aggregated data set holds (default: all of them)")
     args = p.parse_args(argv)
-    if args.demos is None and args.expert is None and args.teacher is None:
+    if args.dagger:
+        if args.label_expert is None:
+            raise SystemExit("--dagger needs --label-expert")
+        if args.expert is not None or args.teacher is not None or args.demos is not None or args.demos_out is not None:
+            raise SystemExit("--dagger makes its own demonstrations: it goes without --expert, --teacher, --demos and --demos-out")
+    elif args.label_expert is not None or args.opponent is not None:
+        raise SystemExit("--label-expert and --opponent belong to --dagger")
+    elif args.demos is None and args.expert is None and args.teacher is None:
         raise SystemExit("one of --expert, --teacher or --demos is needed")
     if args.demos is not None and (args.expert is not None or args.teacher is not None or args.demos_out is not None):
         raise SystemExit("--demos replaces the rollouts: it goes without --expert, --teacher and --demos-out")
@@ -415,13 +570,20 @@ def main(argv=None, parse_only=False):
         env = CDAVecEnv({"num_of_agents": args.agents, "init_cash": 1000000, "max_step": args.max_step, "is_render": False, "auto_reset": True, "n_hist": args.n_hist},
                         n_markets=args.markets, device="cuda:0", with_info=False)
         keep = {}
-        policy, hist = pretrain(env, experts=args.expert, learner_slots=args.learner_slots, iters=args.iters, horizon=args.horizon, epochs=args.epochs, lr=args.lr,
-                                seed=args.seed, policy=policy, holdout=args.holdout, teacher=args.teacher, minibatch=args.minibatch, keep=keep, **net)
+        if args.dagger:
+            policy, hist = dagger(env, args.label_expert, opponents=args.opponent, learner_slots=args.learner_slots, iters=args.iters, horizon=args.horizon, beta=args.beta,
+                                  beta_decay=args.beta_decay, aggregate=args.aggregate, epochs=args.epochs, lr=args.lr, seed=args.seed, policy=policy, holdout=args.holdout,
+                                  minibatch=args.minibatch, **net)
+        else:
+            policy, hist = pretrain(env, experts=args.expert, learner_slots=args.learner_slots, iters=args.iters, horizon=args.horizon, epochs=args.epochs, lr=args.lr,
+                                    seed=args.seed, policy=policy, holdout=args.holdout, teacher=args.teacher, minibatch=args.minibatch, keep=keep, **net)
         if args.demos_out:
             Demonstrations.from_rollout(keep["rollout"], keep["slot_src"]).save(args.demos_out)
         checks = {"flagged_markets": int((env.flags() != 0).sum().item()), "invariant_violations": int((env.check_invariants() != 0).sum().item())}
         env.close()
     summary = {"experts": args.expert, "teacher": args.teacher, "demos": args.demos, "iterations": hist, **checks}
+    if args.dagger:
+        summary.update(dagger=True, label_expert=args.label_expert, opponents=args.opponent)
     if args.save:
         save_policy(args.save, policy)
         summary["saved"] = args.save

@@ -203,6 +203,8 @@ def train_league_fused(env, iters=4, horizon=None, num_trainable=2, lr=5e-5, epo
     rewrites the env's resident slot table beside bank.slot_net - no re-attach, no re-capture - and they are detached on exit, also on an exception (scripted.attached).  Module returns,
     per-module episode metrics, the recorder and league.json name them; promotion considers trainable policies only.  A checkpoint's args hold their canonical
     fields and the weight.  Single-process runs only (ValueError with world > 1); an env that has scripts attached already is refused."""
+    if getattr(env, "label_tap", None) is not None:                  # (an action the label tap mixed in is no policy sample)
+        raise ValueError("train_league_fused does not take an env with a label tap attached: an action the tap mixed in is not a sample of a policy (clear_label_tap() first)")
     if getattr(env, "scripted", False):                              # (a scripted slot's sample record is no policy sample: it must not reach a loss)
         raise ValueError("train_league_fused does not take an env with scripted opponents attached: pass them as scripted_opponents=[...] (the league attaches its pool's "
                          "profiles itself) after clear_scripted()")

@@ -642,6 +642,13 @@ class RolloutChains:
         self.use_graphs = bool(use_graphs)
         self.join_mode = "events"
         self._check_scripted_slots()                               # (raise before anything is captured; run() looks again when the env's scripts changed)
+        self._check_label_tap()
+
+    def _check_label_tap(self):
+        """a label tap (CDAVecEnv.set_label_tap) holds one row per step: a horizon beyond its rows is refused, here and not by the native call in the middle of a capture"""
+        tap = getattr(self.env, "label_tap", None)
+        if tap is not None and self.T > tap["rows"]:
+            raise ValueError(f"the env's label tap holds {tap['rows']} rows, this rollout has a horizon of {self.T} steps: attach the tap with rows >= the horizon")
 
     def _check_scripted_slots(self):
         """a scripted opponent may sit in opponent slots only (once per script epoch of the env): league chains - none below n_trainable; shared-policy chains built
@@ -691,6 +698,8 @@ class RolloutChains:
         self._graph_schedule_epoch = getattr(self.env, "schedule_epoch", 0)
         # ... and the quote recorder's launch and ring (or none) as enabled now (CDAVecEnv.enable_quotes / disable_quotes)
         self._graph_quote_epoch = getattr(self.env, "quote_epoch", 0)
+        # ... and the label tap's launch and buffers (or none) as attached now (CDAVecEnv.set_label_tap / clear_label_tap; set_label_mix moves nothing)
+        self._graph_label_epoch = getattr(self.env, "label_epoch", 0)
 
     def run(self):
         """one rollout of `horizon` steps; returns the buffer dict (views stay valid; the next run() overwrites them)"""
@@ -708,7 +717,11 @@ class RolloutChains:
         if self.graphs is not None and self._graph_quote_epoch != getattr(self.env, "quote_epoch", 0):
             raise RuntimeError("the env's quote tape was enabled or disabled after this RolloutChains captured its graphs: they would replay the recorder's launch "
                                "and ring of the earlier setting - build a new RolloutChains")
+        if self.graphs is not None and self._graph_label_epoch != getattr(self.env, "label_epoch", 0):
+            raise RuntimeError("the env's label tap was attached or detached after this RolloutChains captured its graphs: they would replay the launches and "
+                               "label buffers of the earlier setting - build a new RolloutChains")
         self._check_scripted_slots()
+        self._check_label_tap()
         if not self._have_obs or self._env_epoch != getattr(self.env, "host_epoch", 0):
             # the very first rollout - and the first one after the markets were reset / stepped from the HOST (env.host_epoch) - starts from the env's own
             # observation tensor; every other rollout continues from its predecessor's last observation (the chains do not write env.obs)

@@ -574,6 +574,8 @@ def train_fused(env, iters=4, horizon=64, lr=5e-5, epochs=4, reward_scale=None, 
     an unscripted slot at or above k, k outside 1 .. A - 1, opponents on an env that has scripts attached, world > 1 (data-parallel runs with scripted opponents are
     out of scope); trained_slots=None on an env with scripts attached.  A checkpoint's args hold the profiles' canonical fields and k: a restore with other
     opponents is refused."""
+    if getattr(env, "label_tap", None) is not None:                         # (a mixed-in label is no policy sample either)
+        raise ValueError("train_fused does not take an env with a label tap attached: an action the tap mixed in is not a sample of the policy (clear_label_tap() first)")
     attach = contextlib.nullcontext()
     if opponents is not None:
         if getattr(env, "scripted", False):

@@ -166,6 +166,49 @@ def taker_draw(seed, counter, market, draw, agent):
     return mix((h0 + (((int(draw) & 0xffffffff) << 32) | (int(agent) & 0xffffffff))) & _M64)
 
 
+MIX_DOMAIN = 0xa4093822299f31d0              # include/cda_scripted_agents.h CDA_SCRIPT_MIX_DOMAIN
+
+
+def mix_draw(seed, counter, market, draw, agent):
+    """the label tap's mixing draw (cda_script_mix_draw): taker_draw's construction under MIX_DOMAIN"""
+    h0 = mix(((int(seed) ^ MIX_DOMAIN) + int(counter) * 0x9e3779b97f4a7c15 + int(market) * 0xd1342543de82ef95) & _M64)
+    return mix((h0 + (((int(draw) & 0xffffffff) << 32) | (int(agent) & 0xffffffff))) & _M64)
+
+
+def mix_played(seed, counter, market, draw, agent, mix_q32):
+    """the mix decision on arrays (cda_label_mix_host): i32, 1 where the low 32 bits of mix_draw lie below mix_q32 (0 .. 2^32); market / draw / agent broadcast"""
+    if not 0 <= int(mix_q32) <= 1 << 32:
+        raise ValueError("mix_q32 outside 0 .. 2^32")
+    mk, dr, ag = np.broadcast_arrays(np.asarray(market), np.asarray(draw), np.asarray(agent))
+    out = np.zeros(mk.shape, np.int32)
+    of, mf, df, af = out.reshape(-1), mk.reshape(-1), dr.reshape(-1), ag.reshape(-1)
+    for i in range(of.size):
+        of[i] = (mix_draw(seed, counter, int(mf[i]), int(df[i]), int(af[i])) & 0xffffffff) < int(mix_q32)
+    return out
+
+
+def mix_q32_of(beta):
+    """beta in [0, 1] as the device's mix word: round(beta * 2^32), 0 = never, 2^32 = always"""
+    b = float(beta)
+    if not 0.0 <= b <= 1.0:
+        raise ValueError(f"the mixing probability must lie in [0, 1], got {beta}")
+    return int(round(b * (1 << 32)))
+
+
+def label_spec(profiles, slot_label, views, seed=0, counter=0, market=0, draw=0, agent=0, mix_q32=0, slot_script=None):
+    """k_script_label's label side, stated over actions_from_views: slot_label (0 = not labelled, 1 + k = labelled by profiles[k]) and views (VIEW_DTYPE, each view's
+    vol summed over ITS label profile's depth_levels) of one shape, keyed (seed, counter, market, draw, agent) - the LABEL table's keys.  Returns (the five label
+    arrays, labelled bool, played i32): the labels are meaningful where `labelled`; played = mix_played(...) where the slot is labelled and not attached
+    (slot_script, same shape, nonzero = an attached slot; None = none is), 0 elsewhere."""
+    sl = np.asarray(slot_label)
+    labelled = (sl >= 1) & (sl <= len(profiles))
+    acts = actions_from_views(profiles, np.where(labelled, sl - 1, 0), views, seed, counter, market, draw, agent)
+    mixable = labelled if slot_script is None else labelled & (np.asarray(slot_script) == 0)
+    played = np.where(mixable, mix_played(seed, counter, np.broadcast_to(np.asarray(market), sl.shape), np.broadcast_to(np.asarray(draw), sl.shape),
+                                          np.broadcast_to(np.asarray(agent), sl.shape), mix_q32), 0).astype(np.int32)
+    return acts, labelled, played
+
+
 def decide(p, view, seed=0, counter=0, market=0, draw=0, agent=0):
     """One action: (category, size_mean f32, size_sigma f32, price, price_offset, branch).  `view`: a mapping / VIEW_DTYPE record; `branch` names the rule that
     fired (the tests' tally)."""

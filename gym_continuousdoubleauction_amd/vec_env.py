@@ -50,6 +50,8 @@ class CDAVecEnv:
         self.script_epoch = 0               # bumped by set_scripted / clear_scripted: graphs captured on this env's rollout chains hold the scripted launches (or none) of then
         self._script = None                 # set_scripted: an AttachedScripts (None while nothing is attached)
         self._schedule = None               # set_order_schedule: an AttachedSchedule (None while nothing is attached)
+        self.label_epoch = 0                # bumped by set_label_tap / clear_label_tap (not by set_label_mix): captured graphs hold the tap's launch and buffers of their capture
+        self.label_tap = None               # set_label_tap: a dict of the tap's tensors and settings (None while no tap is attached)
         self.num_agents = self.cfg_struct.num_agents
         self.n_hist = self.cfg_struct.n_hist
         self.obs_dim = self.n_hist * K.SNAPSHOT_DIM
@@ -1130,6 +1132,87 @@ class CDAVecEnv:
             ret = self.step(acts)
         self._script_draw = d + int(n_steps)
         return ret
+
+    # ------------------------------------------------------------------ the label tap: a law's answer for slots it does not play (DAgger; imitate.dagger)
+    def _label_tables(self, slot_label, profiles):
+        from .scripted import MAX_PROFILES, parse_profile, profiles_array
+        profs = [parse_profile(p) for p in profiles]
+        if not 1 <= len(profs) <= MAX_PROFILES:
+            raise ValueError(f"between 1 and {MAX_PROFILES} profiles, got {len(profs)}")
+        slots = np.ascontiguousarray(np.asarray(slot_label.detach().cpu().numpy() if hasattr(slot_label, "detach") else slot_label).astype(np.int64))
+        if slots.shape != (self.n_markets, self.num_agents):
+            raise ValueError(f"slot_label must have shape {(self.n_markets, self.num_agents)}, got {slots.shape}")
+        if slots.min() < 0 or slots.max() > len(profs):
+            raise ValueError(f"slot_label values must lie in 0 .. {len(profs)} (0 = not labelled, 1 + k = profile k)")
+        slot_t = torch.from_numpy(slots.astype(np.int32)).to(self.device)
+        prof_t = torch.from_numpy(profiles_array(profs).view(np.uint8).reshape(len(profs), 64).copy()).to(self.device)
+        return profs, slots.astype(np.int32), slot_t, prof_t
+
+    def set_label_tap(self, slot_label, profiles, rows, seed=0, market_index_base=0, mix=0.0):
+        """Attach a label tap (include/cda.h cda_label_tap_attach): slot_label int [N, A], 0 = the slot is not labelled, 1 + k = profiles[k] (scripted.parse_profile's
+        forms) is asked about it at every step of a rollout chain - about the slot's own position and resting orders, whoever plays it.  The answers land in row t of the
+        tap's buffers, so chains of a horizon up to `rows` may run.  label_tap is then a dict of what the env owns: 'category', 'size_mean', 'size_sigma', 'price',
+        'price_offset', 'played' [rows, N, A], 'mix_q32' (i64 [1]: the device word), the resident tables 'slot_label' i32 [N, A] and 'profiles' u8 [n, 64], and 'rows',
+        'seed', 'market_index_base', 'profile_list' (the Profiles), 'slots_host'.  mix = beta in [0, 1]: a labelled slot that is not
+        scripted plays its label with that probability (label_tap['played'] says where); set_label_mix changes it in place.  `seed` / market_index_base key the label
+        law's draws and the mixing draw.  While attached the one-launch policy step is off.  Not saved by checkpoints or snapshots; single-process runs only."""
+        from .scripted import mix_q32_of
+        rows = int(rows)
+        if rows < 1:
+            raise ValueError("the tap needs at least one row")
+        q = mix_q32_of(mix)
+        profs, slots, slot_t, prof_t = self._label_tables(slot_label, profiles)
+        N, A, dev = self.n_markets, self.num_agents, self.device
+        tap = {k: torch.zeros((rows, N, A), dtype=torch.float32 if k in ("size_mean", "size_sigma") else torch.int32, device=dev) for k in ACTION_KEYS + ("played",)}
+        tap["mix_q32"] = torch.tensor([q], dtype=torch.int64, device=dev)
+        seed, base = int(seed) & (2 ** 64 - 1), int(market_index_base) & (2 ** 64 - 1)
+        self.sync()
+        with torch.cuda.device(dev):
+            check(lib().cda_label_tap_attach(self._h, slot_t.data_ptr(), prof_t.data_ptr(), len(profs), seed, base, tap["mix_q32"].data_ptr(), rows,
+                                             *(tap[k].data_ptr() for k in ACTION_KEYS), tap["played"].data_ptr()), "cda_label_tap_attach")
+        tap.update(slot_label=slot_t, profiles=prof_t, rows=rows, seed=seed, market_index_base=base, profile_list=profs, slots_host=slots)
+        self.label_tap = tap
+        self.label_epoch += 1
+
+    def set_label_mix(self, beta):
+        """beta in [0, 1]: the probability with which a labelled, unscripted slot plays its label from the next launch on - an in-place write of the device word the
+        kernel reads, so captured graphs follow it and label_epoch does not move"""
+        from .scripted import mix_q32_of
+        if self.label_tap is None:
+            raise RuntimeError("set_label_mix() needs a label tap: call set_label_tap() first")
+        self.label_tap["mix_q32"].fill_(mix_q32_of(beta))
+
+    def clear_label_tap(self):
+        self.sync()
+        check(lib().cda_label_tap_detach(self._h), "cda_label_tap_detach")
+        self.label_tap = None
+        self.label_epoch += 1
+
+    def label_actions(self, slot_label, profiles, seed=0, counter=0, draw=0, market_index_base=0, out=None, first_market=0, n_markets=None):
+        """What profiles[slot_label - 1] would do in every labelled slot's place NOW (include/cda.h cda_label_actions; scripted.label_spec states it): one launch, no
+        tap needed, no mixing, the env's actions untouched.  out: a dict of the five [N, A] action tensors, written only where slot_label names a profile; None = fresh
+        tensors holding a pass elsewhere.  counter: an int, or an i64 [1] device tensor.  (seed, counter, market_index_base + market, draw, agent) key the law's draws."""
+        first, n = self._market_range("label_actions", first_market, n_markets)
+        profs, _slots, slot_t, prof_t = self._label_tables(slot_label, profiles)
+        if out is None:
+            out = self._action_buffers()
+        dts = {"category": torch.int32, "size_mean": torch.float32, "size_sigma": torch.float32, "price": torch.int32, "price_offset": torch.int32}
+        for k in ACTION_KEYS:
+            t = out[k]
+            assert t.dtype == dts[k] and t.is_contiguous() and t.device == self.device and t.numel() == self.n_markets * self.num_agents, k
+        if isinstance(counter, torch.Tensor):
+            assert counter.dtype == torch.int64 and counter.device == self.device and counter.numel() >= 1
+            ctr = counter
+        else:
+            ctr = None if int(counter) == 0 else torch.tensor([int(counter)], dtype=torch.int64, device=self.device)
+        self.join()
+        with torch.cuda.device(self.device):
+            check(lib().cda_label_actions(self._h, first, n, slot_t.data_ptr(), prof_t.data_ptr(), len(profs), int(seed) & (2 ** 64 - 1), int(market_index_base) & (2 ** 64 - 1),
+                                          ctr.data_ptr() if ctr is not None else None, int(draw), *(out[k].data_ptr() for k in ACTION_KEYS), self._stream()), "cda_label_actions")
+        cur = torch.cuda.current_stream(self.device)
+        for t in (slot_t, prof_t) + ((ctr,) if ctr is not None else ()):
+            t.record_stream(cur)
+        return out
 
     # ------------------------------------------------------------------ snapshots, forks and resumable runs
     def snapshot(self, first=0, n=None):

@@ -772,6 +772,44 @@ int cda_scripted_decide_host(const void* profiles_host, int32_t n_profiles, cons
                              int32_t* category, float* size_mean, float* size_sigma, int32_t* price, int32_t* price_offset);
 int cda_scripted_profile_check_host(const void* profiles_host, int32_t n_profiles);
 
+/* ---- the label tap: a law's answer for slots it does not play (DAgger) -------------------------------------------------------------------
+ * Behaviour cloning records what the scripted slots did in THEIR situation.  The tap asks a law about any slot - the learner's, with the learner's position and
+ * resting orders - at every step of a rollout chain, keeps the answer beside the rollout's buffers and, for DAgger's beta-mixture, lets it replace the slot's
+ * action with a given probability.  One kernel (csrc/cda_scripted_label.inc k_script_label) serves the attached scripts and the label table in one walk of the book.
+ *   cda_label_tap_attach  slot_label_dev i32 [N][A] (device): 0 = not labelled, 1 + k = labelled by profiles_dev[k] (n_profiles 1 .. 16, device, 8-B aligned), with
+ *                         `seed` and market_index_base of its own.  mix_q32_dev: ONE u64 in device memory, 0 .. 2^32, read by the kernel at every launch - the host
+ *                         may rewrite it between replays of a captured graph.  rows: the rows of the six label buffers, each [rows][N][A] (category, price,
+ *                         price_offset, played i32; size_mean, size_sigma f32; 4-B aligned).  Both tables and the mix word are read back and vetted first: an invalid
+ *                         profile, a slot value outside 0 .. n_profiles, a mix word above 2^32, a bad alignment or rows < 1 returns CDA_ERR_INVALID and changes
+ *                         nothing (synchronous).  The env KEEPS every pointer: the caller's resident memory, as with cda_scripted_attach.
+ *   cda_label_tap_detach  forgets them.  Every attach and detach moves cda_label_tap_epoch; while a tap is attached cda_policy_step_supported answers 0.
+ *   cda_scripted_step_actions   what a rollout chain calls between the policy launch and step t (cda_mlp_rollout_chain and its siblings).  No tap: it IS
+ *                         cda_scripted_actions with draw = t - the same kernel and launch, or none.  Tap attached: ONE k_script_label launch.  An attached slot gets
+ *                         exactly what cda_scripted_actions writes.  A labelled slot's five words go to row t of the label buffers, and `played` gets 0 or 1:
+ *                         for a labelled slot that is NOT attached, w = cda_script_mix_draw(label seed, *counter_dev or 0, market_index_base + market, t, agent)
+ *                         (include/cda_scripted_agents.h), and if (w & 0xffffffff) < *mix_q32_dev the label also overwrites the slot's env action - a_cont, logp and
+ *                         the record as a scripted slot's - and played = 1.  A slot both attached and labelled plays its attached law and is never mixed.  A slot
+ *                         named in neither table keeps all its bytes.  t >= rows: CDA_ERR_INVALID before any launch.
+ *   cda_label_actions     the labels of the state NOW, one launch, no tap needed: the given table's answers into five [N][A] arrays (global market index), written only
+ *                         where the table names a profile (a value outside 1 .. n_profiles names none); no mixing, the env's actions are not touched.  Asynchronous:
+ *                         the tables are not read back.
+ *   cda_label_mix_host    the mix decision on host arrays: played_out[i] = (cda_script_mix_draw(seed, counter, market[i], draw[i], agent[i]) & 0xffffffff) < mix_q32.
+ * Not covered: the league chains' UPDATE (a mixed-in action is no policy sample), checkpoints and snapshots (a tap is not saved), the dict facades, data-parallel runs. */
+int cda_label_tap_attach(cda_env* env, const int32_t* slot_label_dev, const void* profiles_dev, int32_t n_profiles, uint64_t seed, uint64_t market_index_base,
+                         const uint64_t* mix_q32_dev, int32_t rows, int32_t* category, float* size_mean, float* size_sigma, int32_t* price, int32_t* price_offset,
+                         int32_t* played);
+int cda_label_tap_detach(cda_env* env);
+int cda_label_tap_attached(const cda_env* env);
+int64_t cda_label_tap_epoch(const cda_env* env);
+int cda_scripted_step_actions(cda_env* env, int32_t first_market, int32_t n_markets, const int64_t* counter_dev, int32_t t,
+                              int32_t* category, float* size_mean, float* size_sigma, int32_t* price, int32_t* price_offset,
+                              float* a_cont, float* logp, float* record, void* stream);
+int cda_label_actions(cda_env* env, int32_t first_market, int32_t n_markets, const int32_t* slot_label_dev, const void* profiles_dev, int32_t n_profiles, uint64_t seed,
+                      uint64_t market_index_base, const int64_t* counter_dev, int64_t draw, int32_t* category, float* size_mean, float* size_sigma, int32_t* price,
+                      int32_t* price_offset, void* stream);
+int cda_label_mix_host(uint64_t seed, uint64_t counter, const uint64_t* market_host, const uint32_t* draw_host, const uint32_t* agent_host, int64_t n, uint64_t mix_q32,
+                       int32_t* played_out);
+
 /* ---- order streams: explicit orders into every market of a range, in one launch ------------------------------------------------------------
  * cda_submit_orders plays, for every market of [first_market, first_market + n_markets), the messages msgs_dev[offsets_dev[i] .. offsets_dev[i + 1])
  * (i counts from the range's first market) in order: ONE asynchronous launch on `stream`, a wave per market, the market's record loaded once and

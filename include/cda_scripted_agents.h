@@ -67,6 +67,16 @@ CDA_RA_FN uint64_t cda_script_draw(uint64_t seed, uint64_t counter, uint64_t mar
     return cda_ra_mix(h0 + (((uint64_t)draw << 32) | (uint64_t)agent));
 }
 
+/* DAgger's mixing draw (csrc/cda_scripted_label.inc k_script_label, cda_label_mix_host): cda_script_draw's construction in a third domain (the next 64
+ * fraction bits of pi, 0xa4093822299f31d0), so whether a label is played is independent of what a taker with the same seed draws.  The label replaces the
+ * slot's action when the low 32 bits lie below mix_q32 (0 .. 2^32: 0 = never, 2^32 = always). */
+#define CDA_SCRIPT_MIX_DOMAIN 0xa4093822299f31d0ULL
+
+CDA_RA_FN uint64_t cda_script_mix_draw(uint64_t seed, uint64_t counter, uint64_t market, uint32_t draw, uint32_t agent) {
+    const uint64_t h0 = cda_ra_mix((seed ^ CDA_SCRIPT_MIX_DOMAIN) + counter * 0x9e3779b97f4a7c15ULL + market * 0xd1342543de82ef95ULL);
+    return cda_ra_mix(h0 + (((uint64_t)draw << 32) | (uint64_t)agent));
+}
+
 CDA_RA_FN void cda_scripted_decide(const cda_script_profile* pf, const cda_script_view* v, uint64_t seed, uint64_t counter, uint64_t market, uint32_t draw,
                                    uint32_t agent, int32_t* category, float* size_mean, float* size_sigma, int32_t* price, int32_t* price_offset) {
     int32_t cat = 0, off = 1;
