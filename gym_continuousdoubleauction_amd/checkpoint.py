@@ -263,15 +263,20 @@ class Run:
             self.run_id, self.its = self.state["run_id"], iteration_range(self.state["iteration"], *self._iters)
 
     def start_env(self, env, seed, first_market, episode_metrics):
-        """the env as the first iteration finds it: the checkpoint's markets on a restore, else reset with the seed of its first (global) market"""
-        if self.state is not None:
-            if episode_metrics:                                     # (before the restore: the snapshot carries the metrics setting and the running tallies)
+        """the env as the first iteration finds it: the checkpoint's markets on a restore, else reset with the seed of its first (global) market; its episode metrics
+        in the state the loop was asked for, BOTH ways - an env that comes with them on runs an episode_metrics=False loop with them off (nothing would collect the
+        accumulators), and the rollout graphs are captured after this"""
+        def set_metrics():
+            if episode_metrics:
                 env.enable_episode_metrics(True)
+            elif bool(getattr(env, "episode_metrics_on", False)):
+                env.enable_episode_metrics(False)
+        if self.state is not None:
+            set_metrics()                                           # (before the restore: the snapshot carries the metrics setting and the running tallies)
             env.restore(self.snapshot)
         else:
             env.reset(seed=seed + int(first_market))
-            if episode_metrics:
-                env.enable_episode_metrics(True)
+            set_metrics()
 
     def save(self, n_done, state, env, extra_dirs=None):
         """checkpoint_dir/iter_<n_done>: the loop's `state` under this run's kind, id and arguments, and the env's markets"""

@@ -68,12 +68,7 @@ def summarise(agent_table, env_row, module_names=None):
         out["terminated_fraction"] = float(e[K.EM_ENV_TERMINATED]) / float(e[K.EM_ENV_EPISODES])
     if e[K.EM_ENV_MAKER_MAX_N] > 0:
         out["maker_fill_ratio_max"] = float(e[K.EM_ENV_MAKER_MAX_SUM]) / float(e[K.EM_ENV_MAKER_MAX_N])      # mean over the episodes of their most maker-like agent (:344-372)
-    tot = t.sum(axis=0)                                                   # every column is a sum, except:
-    played = t[:, K.EM_EPISODES] > 0
-    if played.any():
-        tot[K.EM_NAV_MIN], tot[K.EM_NAV_MAX] = t[played, K.EM_NAV_MIN].min(), t[played, K.EM_NAV_MAX].max()
-        tot[K.EM_MAKER_RATIO_MAX] = t[played, K.EM_MAKER_RATIO_MAX].max()
-    allr = _row(tot)
+    allr = _row(_merge_agent_rows([t[i:i + 1] for i in range(t.shape[0])])[0]) if t.shape[0] else None      # every module folded into one row, by the one merge rule
     if allr is not None:
         out["all"] = allr
     names = list(module_names) if module_names is not None else [f"module_{i}" for i in range(t.shape[0])]
@@ -84,6 +79,100 @@ def summarise(agent_table, env_row, module_names=None):
             mods[names[i]] = r
     out["modules"] = mods
     return out
+
+
+# ---- one merge rule: how two tables of cda_episode_metrics_collect become one (the device's em_combine / em_identity and the env row's fmax, restated by column) ----
+AGENT_MIN_COLUMNS = (K.EM_NAV_MIN,)                                  # identity +inf
+AGENT_MAX_COLUMNS = (K.EM_NAV_MAX, K.EM_MAKER_RATIO_MAX)             # identity -inf
+ENV_MAX_COLUMNS = (K.EM_ENV_NAV_ERROR_MAX,)                          # identity 0 (an absolute error)
+AGENT_SUM_COLUMNS = tuple(f for f in range(K.EM_AGENT_FIELDS) if f not in AGENT_MIN_COLUMNS + AGENT_MAX_COLUMNS)
+ENV_SUM_COLUMNS = tuple(f for f in range(K.EM_ENV_FIELDS) if f not in ENV_MAX_COLUMNS)
+
+
+def _host(x):
+    return np.array(x.detach().cpu().numpy() if hasattr(x, "detach") else x, dtype=np.float64)
+
+
+def _with_identities(a):
+    """a copy of an agent table in which a module that played nothing (EM_EPISODES == 0: k_em_final reports zeros for it) holds the identities of MIN and MAX;
+    works on numpy arrays and torch tensors alike"""
+    a = a.clone() if hasattr(a, "clone") else a.copy()
+    idle = ~(a[:, K.EM_EPISODES] > 0)
+    for f in AGENT_MIN_COLUMNS:
+        a[idle, f] = float("inf")
+    for f in AGENT_MAX_COLUMNS:
+        a[idle, f] = float("-inf")
+    return a
+
+
+def _merge_agent_rows(tables):
+    """agent tables f64 [M, EM_AGENT_FIELDS] (numpy) -> their merge [M, EM_AGENT_FIELDS]: MIN / MAX over the tables in which the module played, SUM elsewhere.  A
+    module that played in none keeps the first table's words in the MIN / MAX columns (k_em_final's zeros - or the raw identities, untouched)"""
+    stack = np.stack([_with_identities(a) for a in tables])
+    out = stack.sum(axis=0)
+    for f in AGENT_MIN_COLUMNS:
+        out[:, f] = stack[:, :, f].min(axis=0)
+    for f in AGENT_MAX_COLUMNS:
+        out[:, f] = stack[:, :, f].max(axis=0)
+    idle = ~(out[:, K.EM_EPISODES] > 0)
+    for f in AGENT_MIN_COLUMNS + AGENT_MAX_COLUMNS:
+        out[idle, f] = tables[0][idle, f]
+    return out
+
+
+def merge_tables(tables):
+    """[(agent_table [M, EM_AGENT_FIELDS], env_row [EM_ENV_FIELDS]), ...] of the same modules (device or host) -> the one (agent_table, env_row), f64 numpy, that a
+    collection over the union of their markets gives: em_combine by column - MIN for EM_NAV_MIN, MAX for EM_NAV_MAX, EM_MAKER_RATIO_MAX and EM_ENV_NAV_ERROR_MAX, SUM for
+    every other column (the sums in list order).  A table in which a module played nothing (zeros) does not touch that module's MIN / MAX; infinities pass through."""
+    tables = [(_host(a), _host(e)) for a, e in tables]
+    if not tables:
+        raise ValueError("merge_tables needs at least one (agent_table, env_row)")
+    if any(a.shape != tables[0][0].shape or e.shape != tables[0][1].shape for a, e in tables):
+        raise ValueError("merge_tables: the tables must cover the same modules (equal shapes)")
+    env = np.stack([e for _, e in tables])
+    out_env = env.sum(axis=0)
+    for f in ENV_MAX_COLUMNS:
+        out_env[f] = env[:, f].max()
+    return _merge_agent_rows([a for a, _ in tables]), out_env
+
+
+def check_allreduce(allreduce):
+    """TypeError unless `allreduce` takes op= ("sum" / "min" / "max": parallel.make_grad_allreduce's callable): the tables' MIN and MAX columns must not be summed"""
+    import inspect
+    try:
+        params = inspect.signature(allreduce).parameters
+    except (TypeError, ValueError):
+        params = {}
+    if "op" not in params and not any(p.kind is inspect.Parameter.VAR_KEYWORD for p in params.values()):
+        raise TypeError("episode metrics over data-parallel ranks need an all-reduce that can take the minimum and the maximum: a callable(tensor, op='sum' | 'min' | "
+                        "'max') such as parallel.make_grad_allreduce's. This one takes no `op`; summing the min / max columns would report wrong figures "
+                        "(or pass episode_metrics=False)")
+
+
+def allreduce_tables(em, allreduce):
+    """merge_tables over the ranks of a data-parallel run: em = this rank's (agent_table, env_row), allreduce(tensor, op=) reduces in place over the ranks.  Three
+    collectives (the SUM, MIN and MAX columns packed into one tensor each); returns new torch tensors on em's device, equal on every rank."""
+    import torch
+    check_allreduce(allreduce)
+    agent, env = torch.as_tensor(em[0]), torch.as_tensor(em[1])
+    a = _with_identities(agent)
+    M = a.shape[0]
+    packs = {"sum": torch.cat([a[:, list(AGENT_SUM_COLUMNS)].reshape(-1), env[list(ENV_SUM_COLUMNS)]]),
+             "min": a[:, list(AGENT_MIN_COLUMNS)].reshape(-1).clone(),
+             "max": torch.cat([a[:, list(AGENT_MAX_COLUMNS)].reshape(-1), env[list(ENV_MAX_COLUMNS)]])}
+    for op in ("sum", "min", "max"):                        # (one fixed order on every rank)
+        allreduce(packs[op], op=op)
+    out_a, out_e = torch.empty_like(a), torch.empty_like(env)
+    ns, nx = M * len(AGENT_SUM_COLUMNS), M * len(AGENT_MAX_COLUMNS)
+    out_a[:, list(AGENT_SUM_COLUMNS)] = packs["sum"][:ns].view(M, -1)
+    out_e[list(ENV_SUM_COLUMNS)] = packs["sum"][ns:]
+    out_a[:, list(AGENT_MIN_COLUMNS)] = packs["min"].view(M, -1)
+    out_a[:, list(AGENT_MAX_COLUMNS)] = packs["max"][:nx].view(M, -1)
+    out_e[list(ENV_MAX_COLUMNS)] = packs["max"][nx:]
+    idle = ~(out_a[:, K.EM_EPISODES] > 0)
+    for f in AGENT_MIN_COLUMNS + AGENT_MAX_COLUMNS:         # a module that played on no rank: this rank's own words (k_em_final's zeros)
+        out_a[idle, f] = agent[idle, f]
+    return out_a, out_e
 
 
 def check_nav_conservation(iteration, summary, strict=True, log=None):
@@ -104,11 +193,13 @@ def check_nav_conservation(iteration, summary, strict=True, log=None):
 def log_iteration(it, stats, em, module_names, history, log, strict=True, shape=None, allreduce=None):
     """The end of a fused loop's iteration, outside its timed region: em, collected inside it (CDAVecEnv.collect_episode_metrics; None: metrics off), is summarised into
     stats["episode_metrics"] (as shape(summary), if given), the iteration goes to `history` and the log, then NAV conservation is checked.  allreduce: a data-parallel run
-    first sums the tables' additive columns over all shards (the min / max columns stay this rank's)."""
+    first merges the ranks' tables by the device's own rule (allreduce_tables: the additive columns summed, EM_NAV_MIN by MIN, the *_MAX columns by MAX), so every rank
+    summarises, logs and checks the GLOBAL figures - and a violation on any shard raises on every rank in the same iteration.  A callable without an `op` keyword is
+    refused (TypeError), never summed."""
     summ = None
     if em is not None:
         if allreduce is not None:
-            allreduce(em[0]); allreduce(em[1])
+            em = allreduce_tables(em, allreduce)
         summ = summarise(*em, module_names=module_names)
         stats["episode_metrics"] = summ if shape is None else shape(summ)
     history.append(stats)

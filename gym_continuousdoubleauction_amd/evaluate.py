@@ -213,7 +213,8 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
     if total < 1:
         raise ValueError("episodes * max_step must be at least 1")
     T = _horizon(total)
-    prev_metrics = bool(getattr(env, "episode_metrics_on", False))
+    prev_metrics = bool(getattr(env, "episode_metrics_on", False))       # the caller's setting, tolerance included: put back as it was afterwards
+    prev_tolerance = float(getattr(env, "episode_metrics_tolerance", 1e-6))
     env.enable_episode_metrics(True)                                    # before the chains are captured
     if tape is not None and env.tape_enabled:
         raise ValueError("evaluate(tape=...) needs an env whose trade tape is off: it enables a tape of its own for the evaluated episodes (disable_tape() first, or "
@@ -294,7 +295,7 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
                       init_module=modules[market, rows[:, 6]].astype(np.int32), counter_module=modules[market, rows[:, 3]].astype(np.int32),
                       module_names=np.array(names), modules=modules.astype(np.int32))
     finally:
-        env.enable_episode_metrics(prev_metrics)
+        env.enable_episode_metrics(prev_metrics, nav_tolerance=prev_tolerance)
         if tape is not None:
             env.disable_tape()
         if with_quotes and env.quotes_enabled:

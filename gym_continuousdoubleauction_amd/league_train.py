@@ -187,7 +187,8 @@ def train_league_fused(env, iters=4, horizon=None, num_trainable=2, lr=5e-5, epo
     allreduce / world / first_market: the data-parallel learner of ppo.train_fused for the league - every rank rolls out and back-propagates its own shard of
     markets (global indices [first_market, first_market + N): env seeds, sampling keys and EPISODE IDS follow them, so the opponents a market meets do not depend
     on the GPU count), the ranks sum each policy's gradient (one all-reduce of 0.9 MB per policy and minibatch step) and advantage sums, and the per-module returns
-    behind the promotion rule - so every rank promotes the same champions in lockstep.
+    behind the promotion rule - so every rank promotes the same champions in lockstep - and merge their episode-metric tables by the device's rule
+    (episode_metrics.allreduce_tables: MIN / MAX / SUM by column; the callable must take op=), so every rank logs and checks the global figures.
     checkpoint_dir / chkpt_freq / chkpt_keep / restore / iters_is_delta (all off by default): a resumable run, as in ppo.train_fused (checkpoint.py).  A league
     checkpoint is taken only at an EPISODE BOUNDARY ((it + 1) % per_episode == 0, where no opponent window is open): chkpt_freq must be a multiple of
     max_step / horizon (ValueError otherwise), and the final save is skipped when the run does not end on a boundary.  It holds the env snapshot, every
@@ -262,6 +263,8 @@ def _train_league_fused(env, profiles, obj, *, iters, horizon, num_trainable, lr
                     original_opponent_weight=float(original_opponent_weight), champion_weight=float(champion_weight), run_id=str(run_id))
         args = CK.with_order_schedule(CK.with_scripted(args, profiles, scripted_weight=scripted_weight), env.order_schedule_digest())
         run.open(args if random_opponents is None else dict(args, random_opponents=n_random))     # (the key only when the argument is given: checkpoints from before it existed resume)
+    if allreduce is not None and world > 1 and episode_metrics:          # (before anything runs: the tables' MIN / MAX columns need op= on the collective)
+        EM.check_allreduce(allreduce)
     run.start_env(env, seed, first_market, episode_metrics)
     if run.state is not None:
         _load_league_state(os.path.join(run.path, "league"), run.state, bank, league)

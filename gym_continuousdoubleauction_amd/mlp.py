@@ -700,6 +700,13 @@ class RolloutChains:
         self._graph_quote_epoch = getattr(self.env, "quote_epoch", 0)
         # ... and the label tap's launch and buffers (or none) as attached now (CDAVecEnv.set_label_tap / clear_label_tap; set_label_mix moves nothing)
         self._graph_label_epoch = getattr(self.env, "label_epoch", 0)
+        # ... and the step instances (tallying or not) and the NAV tolerance of the env's episode-metrics setting as it is now (CDAVecEnv.enable_episode_metrics). The
+        # SETTING is remembered, not a count of calls: a toggle there and back (evaluate() on a caller's env) leaves the graphs valid
+        self._graph_episode_metrics = self._episode_metrics_setting()
+
+    def _episode_metrics_setting(self):
+        on = bool(getattr(self.env, "episode_metrics_on", False))
+        return on, float(getattr(self.env, "episode_metrics_tolerance", 1e-6)) if on else None      # (off: nothing reads the tolerance)
 
     def run(self):
         """one rollout of `horizon` steps; returns the buffer dict (views stay valid; the next run() overwrites them)"""
@@ -720,6 +727,10 @@ class RolloutChains:
         if self.graphs is not None and self._graph_label_epoch != getattr(self.env, "label_epoch", 0):
             raise RuntimeError("the env's label tap was attached or detached after this RolloutChains captured its graphs: they would replay the launches and "
                                "label buffers of the earlier setting - build a new RolloutChains")
+        if self.graphs is not None and self._graph_episode_metrics != self._episode_metrics_setting():
+            raise RuntimeError("the env's episode metrics were enabled or disabled, or their nav_tolerance changed, after this RolloutChains captured its graphs "
+                               f"(captured with (on, nav_tolerance) = {self._graph_episode_metrics}, the env now has {self._episode_metrics_setting()}): they would replay "
+                               "the step kernels and the tolerance of the earlier setting, and the NAV check would see nothing - build a new RolloutChains")
         self._check_scripted_slots()
         self._check_label_tap()
         if not self._have_obs or self._env_epoch != getattr(self.env, "host_epoch", 0):

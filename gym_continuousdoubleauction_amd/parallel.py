@@ -154,12 +154,16 @@ def make_grad_allreduce(dist=None, group=None):
     """The one collective of a data-parallel learner (SURVEY 8(e) "if the learner is itself data-parallel over the same shards, the all-gather can be skipped
     entirely"): callable(tensor) -> the tensor summed in place over the ranks, on the caller's stream semantics of torch.distributed (RCCL: enqueued behind the
     current stream's work, the current stream ordered behind it; gloo: through the host).  mlp.FusedUpdate calls it on the 0.9-MB gradient between the reduce and
-    the optimiser launches of every minibatch step; ppo.train_fused also on the two advantage sums of a rollout."""
+    the optimiser launches of every minibatch step; ppo.train_fused also on the two advantage sums of a rollout.
+    op = "min" / "max": the same collective with ReduceOp.MIN / MAX - what the episode metrics' non-additive columns travel with, once per iteration and outside the
+    timed region (episode_metrics.allreduce_tables)."""
     import torch.distributed as tdist
     d = dist or tdist
 
-    def allreduce(t):
-        d.all_reduce(t, op=d.ReduceOp.SUM, group=group)
+    def allreduce(t, op="sum"):
+        if op not in ("sum", "min", "max"):
+            raise ValueError(f"op must be 'sum', 'min' or 'max' (got {op!r})")
+        d.all_reduce(t, op={"sum": d.ReduceOp.SUM, "min": d.ReduceOp.MIN, "max": d.ReduceOp.MAX}[op], group=group)
         return t
     return allreduce
 

@@ -548,11 +548,14 @@ def train_fused(env, iters=4, horizon=64, lr=5e-5, epochs=4, reward_scale=None, 
     allreduce / world / first_market: a DATA-PARALLEL learner (one process per GPU): every rank runs this loop on its own env shard (its markets are the global
     markets [first_market, first_market + N): seeds and sampling keys follow the global index), rolls out and back-propagates locally, and the ranks sum the
     gradient (parallel.make_grad_allreduce: one all-reduce of 0.9 MB per minibatch step, mlp.FusedUpdate) and the two advantage sums of a rollout - no
-    observation ever crosses the fabric.  Every rank starts from the same parameters (same `seed`) and applies the same steps.
+    observation ever crosses the fabric.  Every rank starts from the same parameters (same `seed`) and applies the same steps.  With episode_metrics the ranks also merge
+    their metric tables once per iteration, outside the timed region (episode_metrics.allreduce_tables: the callable must take op="sum" | "min" | "max", TypeError
+    otherwise): every rank's history holds the global figures and a NAV violation on any shard raises on every rank in the same iteration.
     episode_metrics (default on): every episode that ends anywhere inside a rollout is checked (exact sum of NAV) and tallied ON THE DEVICE, in the cold path of the
     in-kernel auto reset (CDAVecEnv.enable_episode_metrics); history[i]["episode_metrics"] holds what the reference's callback logs per episode
     (episode_metrics.summarise: pass / rejection fractions, reward-term means and variance shares, NAV / drawdown / inventory at the episode's end, the most maker-like
     agent's passive share) and a violation raises NavConservationError like the reference's strict_nav_check run (train/train.py:1125-1164); strict_nav_check=False logs it.
+    The env is put into the state asked for before the rollout graphs are captured: episode_metrics=False switches the metrics of an env that has them on off.
     state_dependent_log_std: a fresh policy gets RLlib's default head for Box actions (two log-stds per row from the policy network: mlp.FusedPolicy); a given `policy`
     brings its own.  hidden: `fcnet_hiddens` of a fresh policy, <= 256 each (mlp.init_theta).  activation: `fcnet_activation` of a fresh policy (mlp.ACTIVATIONS;
     a given `policy` brings its own); a network that is not tanh rolls out with two launches per step (k_policy_step is the tanh network's).  vf_share_layers: RLlib's
@@ -620,6 +623,9 @@ def _train_fused(env, k_tr, obj, *, iters, horizon, lr, epochs, seed, log, use_g
     if run.resumable:                                       # (scripts are attached only with trained slots, and the other way round)
         run.open(CK.with_order_schedule(CK.with_scripted(CK.run_args(policy, env, T, chains, obj, epochs, lr, minibatch, seed, episode_metrics), env.scripted_profiles(),
                                                          trained_slots=k_tr), env.order_schedule_digest()))      # (an attached order schedule: its digest)
+    dp = allreduce is not None and world > 1
+    if dp and episode_metrics:                              # (before anything runs: the tables' MIN / MAX columns need op= on the collective)
+        EM.check_allreduce(allreduce)
     run.start_env(env, seed, first_market, episode_metrics)
     if run.state is not None:
         CK.load_net_record(policy, run.state["nets"][0])
@@ -655,7 +661,7 @@ def _train_fused(env, k_tr, obj, *, iters, horizon, lr, epochs, seed, log, use_g
                                  "returns": CK.returns_record(returns), "kl_coef": float(kl_coef)}, env)
 
     def em_shape(summ):                                     # the one policy's figures flat; per module only with scripted opponents
-        top = {k: summ.get(k) for k in ("episodes", "nav_conservation_violations", "nav_conservation_error", "maker_fill_ratio_max", "episode_len_mean")}
+        top = {k: summ.get(k) for k in ("episodes", "nav_conservation_violations", "nav_conservation_error", "nav_conservation_error_sum", "maker_fill_ratio_max", "episode_len_mean")}
         return dict(summ.get("all", {}), **top, **({"modules": summ["modules"]} if module_names is not None else {}))
     for it in run.its:
         torch.cuda.synchronize(dev)
@@ -687,7 +693,8 @@ def _train_fused(env, k_tr, obj, *, iters, horizon, lr, epochs, seed, log, use_g
         roll.check_capture_overflow()                                       # (outside the timed region; warns)
         if recorder is not None and roll.info is not None:
             recorder.record_rollout(roll, iteration=it)
-        EM.log_iteration(it, stats, em, module_names or ["policy_0"], history, log, strict=strict_nav_check, shape=em_shape, allreduce=None)     # (None: a data-parallel run logs its own rank's)
+        # (data parallel: the ranks' tables merged first - every rank logs the global figures and a violation on any shard stops every rank in this iteration)
+        EM.log_iteration(it, stats, em, module_names or ["policy_0"], history, log, strict=strict_nav_check, shape=em_shape, allreduce=allreduce if dp else None)
         run.after_iteration(it, save)
     if keep is not None:
         keep.update(buffers=roll.buf, rollout=roll, update=upd)

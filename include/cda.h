@@ -346,6 +346,13 @@ int cda_nav_conservation(cda_env* env, double tolerance, double* abs_error_out, 
  *     CDA_FLAG_NAV_CONSERVATION bit (it survives the auto reset) and counts a violation; the tallies and the last step's account figures are added
  *     to per-(market, agent) and per-market accumulators;  a reset of a market whose episode is NOT over discards its running tallies (an episode
  *     the reference's callback never sees end either).
+ * An episode IN FLIGHT at the call: cda_episode_metrics_enable (on or off) zeroes every market's running tallies and touches nothing else.  An episode that is
+ * under way at an enable is therefore still checked and credited at its end, with the tallies (passes, rejections, placed, trades, passive fills, reward-term sums,
+ * return - and the maker ratio formed from them) of the steps AFTER the enable only, while its step count (CDA_EM_AGENT_STEPS, CDA_EM_ENV_STEPS: the episode's
+ * t_step) and the end-of-episode account figures (NAV, drawdown, position, num_trades, bankrupt, the conservation check) are the whole episode's.  A disable stops
+ * the tallying and the crediting at once - an episode that ends while the metrics are off is never credited; one that is still under way when they are enabled
+ * again falls under the rule above - and keeps the accumulators: a collection after it returns what was credited before it.  The setting (on, nav_tolerance) is an argument of every step
+ * launch: a captured graph of step launches holds the setting of its capture and must not be replayed under another (mlp.RolloutChains.run refuses).
  * cda_episode_metrics_collect reduces the accumulators over the markets, by module: module_of i32[N,A] (device; NULL = every slot is module 0) names
  * the module that played slot a of market i during the episodes collected (league self-play: the draw of cda_league_assign; values outside
  * [0, n_modules) are skipped) -> agent_out f64[n_modules, CDA_EM_AGENT_FIELDS], env_out f64[CDA_EM_ENV_FIELDS] (device), in a FIXED order (two launches;

@@ -122,6 +122,23 @@ def assert_tables_equal(dev_agent, dev_env, ref_agent, ref_env, what=""):
     assert np.allclose(de, ref_env, rtol=1e-12, atol=0), (what, de, ref_env)
 
 
+def assert_summary_is_consistent(summary, what=""):
+    """what any summary of real episodes satisfies and a table merged with the wrong operator does not (a SUM of two ranks' minima lies above the mean): for `all`
+    and every module min <= mean <= max of the episode-end NAV, all finite; the best maker ratio is a ratio; the largest conservation error is one of the summed"""
+    import math
+    rows = dict(summary.get("modules", {}))
+    if "all" in summary:
+        rows["all"] = summary["all"]
+    elif "episode_nav_min" in summary:                      # (ppo.train_fused's shape: the one policy's figures flat beside the env's)
+        rows["all"] = summary
+    for name, r in rows.items():
+        lo, mean, hi = r["episode_nav_min"], r["episode_nav_mean"], r["episode_nav_max"]
+        assert math.isfinite(lo) and math.isfinite(mean) and math.isfinite(hi) and lo <= mean <= hi, (what, name, lo, mean, hi)
+        if "maker_fill_ratio_best" in r:
+            assert 0.0 <= r["maker_fill_ratio_mean"] <= r["maker_fill_ratio_best"] <= 1.0, (what, name, r["maker_fill_ratio_mean"], r["maker_fill_ratio_best"])
+    assert 0.0 <= summary["nav_conservation_error"] <= summary["nav_conservation_error_sum"], (what, summary["nav_conservation_error"], summary["nav_conservation_error_sum"])
+
+
 def abs_sums(em, module_of=None, n_modules=1):
     """before em.table(): per module and field the sum of |x| over the (market, agent) rows the table adds, the number of those rows, and the same for the env
     row's per-market sums - what the summation-order bound of assert_tables_within_order_bound scales with"""

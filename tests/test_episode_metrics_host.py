@@ -95,3 +95,200 @@ def test_the_helper_restates_the_callbacks_tallies():
     assert not em.violating
     em.feed(info(["1010.5", "989.6"], [0, 0], [0, 0], [0, 0], [0, 0], [0, 0], [z5, z5], [0, 0], [0, 0], [0, 0]), np.zeros((1, 2)), np.array([0]), np.array([1]))
     assert len(em.violating) == 1 and em.violating[0][1] == Decimal("0.1")
+
+
+# ---- one merge rule (episode_metrics.merge_tables / allreduce_tables): the device's em_combine by column, on the host and over data-parallel ranks -------------------
+def _pairs_table(modules, n_modules=4, errors=(), tolerance=1e-6):
+    """a table as k_em_final leaves it, from per module a list of (episode, agent) pairs (nav, maker ratio or None); every figure a multiple of 2^-10, so that the sums
+    are exact in f64 whatever their order.  errors: |sum(NAV) - A * init_cash| of the episodes behind the env row"""
+    t, e = np.zeros((n_modules, K.EM_AGENT_FIELDS)), np.zeros(K.EM_ENV_FIELDS)
+    for m, pairs in modules.items():
+        navs = [p[0] for p in pairs]
+        ratios = [p[1] for p in pairs if p[1] is not None]
+        t[m, K.EM_EPISODES], t[m, K.EM_AGENT_STEPS], t[m, K.EM_PASSES], t[m, K.EM_TRADES] = len(pairs), 5 * len(pairs), 2 * len(pairs), 6 * len(ratios)
+        t[m, K.EM_NAV_SUM], t[m, K.EM_NAV_MIN], t[m, K.EM_NAV_MAX] = sum(navs), min(navs), max(navs)
+        t[m, K.EM_RETURN_SUM], t[m, K.EM_RETURN_SQ] = sum(n - 1000 for n in navs), sum((n - 1000) ** 2 for n in navs)
+        t[m, K.EM_TERM_SUM], t[m, K.EM_TERM_SQ] = t[m, K.EM_RETURN_SUM], t[m, K.EM_RETURN_SQ]
+        t[m, K.EM_MAKER_RATIO_N], t[m, K.EM_MAKER_RATIO_SUM], t[m, K.EM_MAKER_RATIO_MAX] = len(ratios), sum(ratios), max(ratios, default=0.0)
+    e[K.EM_ENV_EPISODES], e[K.EM_ENV_STEPS] = len(errors), 5 * len(errors)
+    e[K.EM_ENV_NAV_ERROR_SUM], e[K.EM_ENV_NAV_ERROR_MAX] = sum(errors), max(errors, default=0.0)
+    e[K.EM_ENV_NAV_VIOLATIONS] = sum(1 for x in errors if x > tolerance)
+    return t, e
+
+
+def _rank_tables():
+    """three ranks' tables over four modules: module 0 played on every rank, module 1 on rank 0 only, module 2 on ranks 1 and 2, module 3 nowhere"""
+    return [_pairs_table({0: [(1000.5, 0.75), (999.5, None)], 1: [(1003.0, 0.5), (997.0, 0.25)]}, errors=(0.0, 2.0 ** -30)),
+            _pairs_table({0: [(1010.0, None), (990.0, 1.0)], 2: [(1000.0, None)]}, errors=(0.0,)),
+            _pairs_table({0: [(998.25, 0.125)], 2: [(1001.75, 0.375), (998.25, None)]}, errors=(12.5, 2.0 ** -30))]
+
+
+def _same(x, y):
+    return all(np.array_equal(np.asarray(a).view(np.uint64), np.asarray(b).view(np.uint64)) for a, b in zip(x, y))
+
+
+def test_merge_tables_is_the_devices_rule_by_column():
+    """MIN for EM_NAV_MIN, MAX for EM_NAV_MAX / EM_MAKER_RATIO_MAX / EM_ENV_NAV_ERROR_MAX, SUM elsewhere; a rank on which a module played nothing (zeros in its row)
+    does not touch that module's minimum or maximum"""
+    from episode_metrics_util import assert_summary_is_consistent
+    ranks = _rank_tables()
+    t, e = EM.merge_tables(ranks)
+    assert set(EM.AGENT_MIN_COLUMNS) == {K.EM_NAV_MIN} and set(EM.AGENT_MAX_COLUMNS) == {K.EM_NAV_MAX, K.EM_MAKER_RATIO_MAX} and set(EM.ENV_MAX_COLUMNS) == {K.EM_ENV_NAV_ERROR_MAX}
+    assert sorted(EM.AGENT_SUM_COLUMNS + EM.AGENT_MIN_COLUMNS + EM.AGENT_MAX_COLUMNS) == list(range(K.EM_AGENT_FIELDS))
+    assert sorted(EM.ENV_SUM_COLUMNS + EM.ENV_MAX_COLUMNS) == list(range(K.EM_ENV_FIELDS))
+    want = _pairs_table({0: [(1000.5, 0.75), (999.5, None), (1010.0, None), (990.0, 1.0), (998.25, 0.125)], 1: [(1003.0, 0.5), (997.0, 0.25)],
+                         2: [(1000.0, None), (1001.75, 0.375), (998.25, None)]}, errors=(0.0, 2.0 ** -30, 0.0, 12.5, 2.0 ** -30))      # the union of the pairs, collected at once
+    assert _same((t, e), want)
+    assert t[0, K.EM_NAV_MIN] == 990.0 and t[1, K.EM_NAV_MIN] == 997.0 and t[2, K.EM_NAV_MIN] == 998.25 and t[2, K.EM_NAV_MAX] == 1001.75      # one rank only / two of three
+    assert not t[3].any()                                                      # played nowhere: k_em_final's zeros, not infinities
+    assert e[K.EM_ENV_NAV_ERROR_MAX] == 12.5 and e[K.EM_ENV_NAV_VIOLATIONS] == 1 and e[K.EM_ENV_EPISODES] == 5
+    s = EM.summarise(t, e, module_names=["policy_0", "policy_1", "champion_1", "champion_2"])
+    assert set(s["modules"]) == {"policy_0", "policy_1", "champion_1"}
+    assert_summary_is_consistent(s, "merged")
+    assert s["all"]["episode_nav_min"] == 990.0 and s["all"]["episode_nav_max"] == 1010.0 and s["all"]["maker_fill_ratio_best"] == 1.0
+    assert s["modules"]["policy_1"]["episode_nav_min"] == 997.0 and s["modules"]["policy_1"]["episode_nav_mean"] == 1000.0
+    # ... which a SUM over the ranks - what the data-parallel league did - breaks: the "minimum" of module 0 comes out near three init_cash
+    summed = EM.summarise(sum(r[0] for r in ranks), sum(r[1] for r in ranks))
+    assert summed["modules"]["module_0"]["episode_nav_min"] > summed["modules"]["module_0"]["episode_nav_mean"]
+    with pytest.raises(AssertionError):
+        assert_summary_is_consistent(summed, "summed")
+
+
+def test_merge_of_one_table_is_the_identity_and_the_merge_is_associative():
+    a, b, c = _rank_tables()
+    for x in (a, b, c):
+        assert _same(EM.merge_tables([x]), x)
+    abc = EM.merge_tables([a, b, c])
+    assert _same(EM.merge_tables([EM.merge_tables([a, b]), c]), abc) and _same(EM.merge_tables([a, EM.merge_tables([b, c])]), abc)
+    assert _same(EM.merge_tables([c, a, b]), abc)                               # (exact figures: commutative to the bit as well)
+    # the raw identities of a module that never played (+inf / -inf: em_identity) pass through untouched, alone and beside a rank on which it did play
+    raw = (a[0].copy(), a[1].copy())
+    raw[0][3, K.EM_NAV_MIN], raw[0][3, K.EM_NAV_MAX], raw[0][3, K.EM_MAKER_RATIO_MAX] = np.inf, -np.inf, -np.inf
+    assert _same(EM.merge_tables([raw]), raw) and _same(EM.merge_tables([raw, raw])[0][3], raw[0][3])
+    played = _pairs_table({3: [(1002.0, 0.5)]}, errors=(0.0,))
+    assert _same(EM.merge_tables([raw, played])[0][3], played[0][3]) and _same(EM.merge_tables([played, raw])[0][3], played[0][3])
+    with pytest.raises(ValueError):
+        EM.merge_tables([a, (b[0][:2], b[1])])
+    with pytest.raises(ValueError):
+        EM.merge_tables([])
+
+
+def test_summarise_folds_the_modules_with_the_same_columns():
+    """`all` is the merge of the module rows: a module that played nothing (a row of zeros) contributes neither a minimum of 0 nor a maximum of 0"""
+    t, e = _pairs_table({1: [(-3.5, None)], 2: [(-1.25, 0.5)]}, errors=(0.0,))           # (negative NAVs: a zero from an idle row would be the maximum)
+    s = EM.summarise(t, e)
+    assert s["all"]["episode_nav_min"] == -3.5 and s["all"]["episode_nav_max"] == -1.25 and s["all"]["agent_episodes"] == 2 and s["all"]["maker_fill_ratio_best"] == 0.5
+    assert "all" not in EM.summarise(np.zeros((2, K.EM_AGENT_FIELDS)), np.zeros(K.EM_ENV_FIELDS))
+
+
+class _ThreadRanks:
+    """two Python threads as two ranks: allreduce(rank) is the callable a rank passes to the loops (tensor, op=) - a rendezvous on a Barrier whose timeout turns a
+    collective that one rank never enters into BrokenBarrierError on the other instead of a wait"""
+
+    def __init__(self, world=2, timeout=20.0):
+        import threading
+        self.world, self.barrier, self.slots, self.calls = world, threading.Barrier(world, timeout=timeout), [None] * world, [[] for _ in range(world)]
+
+    def allreduce(self, rank):
+        import torch
+
+        def allreduce(t, op="sum"):
+            self.calls[rank].append((op, tuple(t.shape)))
+            self.slots[rank] = t.clone()
+            self.barrier.wait()
+            stack = torch.stack(self.slots)
+            r = stack.sum(0) if op == "sum" else (stack.min(0).values if op == "min" else stack.max(0).values)
+            self.barrier.wait()                                                # (everyone has read the slots before anyone writes the next collective's)
+            t.copy_(r)
+            return t
+        return allreduce
+
+    def run(self, body):
+        """body(rank, allreduce) on every rank's thread -> what each returned (an exception that escaped is returned too)"""
+        import threading
+        out = [None] * self.world
+
+        def target(rank):
+            try:
+                out[rank] = body(rank, self.allreduce(rank))
+            except BaseException as ex:  # noqa: BLE001 - handed to the test's thread
+                out[rank] = ex
+        threads = [threading.Thread(target=target, args=(r,), daemon=True) for r in range(self.world)]
+        for th in threads:
+            th.start()
+        for th in threads:
+            th.join(60.0)
+        assert not any(th.is_alive() for th in threads), "a rank is still waiting"
+        return out
+
+
+@pytest.mark.parametrize("strict", [True, False])
+def test_a_violation_on_one_rank_stops_every_rank_in_the_same_iteration(strict):
+    """log_iteration over two ranks: rank 1's shard holds the one violated episode of iteration 1.  Both ranks merge first, so both see it: strict - both raise
+    NavConservationError in iteration 1 with the same message (neither is left waiting in the next collective); lenient - both log it and go on to iteration 2"""
+    import torch
+    a, b, c = _rank_tables()
+    names = ["policy_0", "policy_1", "champion_1", "champion_2"]
+    tables = [(a, b), (a, c), (b, a), (b, b)]                                  # per iteration: (rank 0's, rank 1's); c carries the violation
+    ranks = _ThreadRanks()
+
+    def body(rank, allreduce):
+        history, logged, raised = [], [], None
+        for it in range(4):
+            t, e = tables[it][rank]
+            em = (torch.from_numpy(t.copy()), torch.from_numpy(e.copy()))
+            try:
+                EM.log_iteration(it, {"iter": it}, em, names, history, logged.append, strict=strict, allreduce=allreduce)
+            except EM.NavConservationError as ex:
+                raised = (it, str(ex))
+                break                                                          # a stopped run enters no further collective
+        return history, logged, raised
+    out = ranks.run(body)
+    assert not any(isinstance(o, BaseException) for o in out), out
+    (h0, l0, r0), (h1, l1, r1) = out
+    assert h0 == h1 and l0 == l1 and r0 == r1                                  # every rank logs the global figures, to the word
+    assert ranks.calls[0] == ranks.calls[1] and [op for op, _ in ranks.calls[0][:3]] == ["sum", "min", "max"]
+    if strict:
+        assert r0 is not None and r0[0] == 1 and "1 episode(s) during iteration 1" in r0[1] and "= 12.5)" in r0[1] and len(h0) == 2
+    else:
+        assert r0 is None and len(h0) == 4 and sum("strict_nav_check is off" in m for m in l0) == 1 and "iteration 1" in [m for m in l0 if "strict_nav_check" in m][0]
+    want = EM.summarise(*EM.merge_tables([a, c]), module_names=names)
+    assert h0[1]["episode_metrics"] == want and want["nav_conservation_violations"] == 1 and want["episodes"] == 4
+
+
+def test_an_allreduce_that_cannot_take_min_and_max_is_refused_not_summed():
+    import torch
+    a, b, _ = _rank_tables()
+    em = (torch.from_numpy(a[0].copy()), torch.from_numpy(a[1].copy()))
+    calls = []
+
+    def sum_only(t):
+        calls.append(t)
+        return t
+    with pytest.raises(TypeError, match="min"):
+        EM.log_iteration(0, {}, em, None, [], lambda s: None, allreduce=sum_only)
+    with pytest.raises(TypeError, match="min"):
+        EM.check_allreduce(lambda t: t)
+    assert not calls and _same((em[0].numpy(), em[1].numpy()), a)               # refused before anything travelled
+    EM.check_allreduce(lambda t, op="sum": t)
+    EM.check_allreduce(lambda t, **kw: t)
+    from gym_continuousdoubleauction_amd.parallel import make_grad_allreduce
+
+    class _Dist:                                                               # (torch.distributed's names: what the product's callable maps op= to)
+        class ReduceOp:
+            SUM, MIN, MAX = "SUM", "MIN", "MAX"
+
+        def __init__(self):
+            self.seen = []
+
+        def all_reduce(self, t, op, group=None):
+            self.seen.append(op)
+    d = _Dist()
+    ar = make_grad_allreduce(d)
+    EM.check_allreduce(ar)
+    out = EM.allreduce_tables(em, ar)                                          # one rank: the merge of one table
+    assert d.seen == ["SUM", "MIN", "MAX"] and _same((out[0].numpy(), out[1].numpy()), a)
+    ar(torch.zeros(1))
+    assert d.seen[-1] == "SUM"                                                 # the gradient's call is unchanged
+    with pytest.raises(ValueError):
+        ar(torch.zeros(1), op="prod")

@@ -132,3 +132,61 @@ def test_league_data_parallel_ranks_stay_in_lockstep(tmp_path):
     assert a["champions"] == b["champions"] and len(a["champions"]) == 2
     assert a["returns"] == b["returns"] and a["returns"][0] is not None
     assert not torch.equal(a["slot_net"], b["slot_net"]) and a["flags"] == b["flags"] == 0
+
+
+# ---- episode metrics over data-parallel ranks: one table, merged by the device's rule, on every rank -----------------------------------------------------------------
+def _metrics_worker(rank, world, port, outdir):
+    import datetime
+    import torch.distributed as dist
+    sys.path.insert(0, ROOT)
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120))      # (a collective that one rank misses ends the other, it does not wait)
+    torch.cuda.set_device(0)
+    from gym_continuousdoubleauction_amd import CDAVecEnv, ppo
+    from gym_continuousdoubleauction_amd.league_train import train_league_fused
+    from gym_continuousdoubleauction_amd.parallel import make_grad_allreduce
+    N, out = 64, {}
+
+    def cfg(A, max_step):
+        return {"num_of_agents": A, "init_cash": 3000, "max_step": max_step, "is_render": False, "auto_reset": True}
+    for name, A, T in (("league", 8, 16), ("ppo", 4, 8)):
+        env = CDAVecEnv(cfg(A, T), n_markets=N, with_info=False)
+        keep, ends = {}, []
+        log = lambda s: ends.append(int((keep["rollout"].buf["terminated"] | keep["rollout"].buf["truncated"]).sum().item()))      # noqa: E731  (this rank's own ends, per iteration)
+        kw = dict(iters=2, horizon=T, epochs=1, chains=2, keep=keep, log=log, allreduce=make_grad_allreduce(dist), world=world, first_market=rank * N)
+        hist = train_league_fused(env, num_trainable=2, **kw)[-1] if name == "league" else ppo.train_fused(env, **kw)[-1]
+        torch.cuda.synchronize()
+        out[name] = {"metrics": [h["episode_metrics"] for h in hist], "ends": ends, "flags": int((env.flags() != 0).sum())}
+        env.close()
+    torch.save(out, os.path.join(outdir, f"metrics_{rank}.pt"))
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_episode_metrics_are_the_global_figures_on_every_rank(tmp_path):
+    """train_league_fused and train_fused, two ranks on one GPU over gloo: every rank's history holds the SAME episode metrics - the ranks' tables merged by the
+    device's rule (episode_metrics.allreduce_tables), not summed and not each rank's own - so `episodes` is the sum of the ranks' own episode ends, min <= mean <= max
+    holds, and a violation would stop both ranks in the same iteration (that scenario itself: tests/test_episode_metrics_host.py, on threads)"""
+    import time
+    import torch.multiprocessing as mp
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from episode_metrics_util import assert_summary_is_consistent
+    ctx = mp.spawn(_metrics_worker, args=(2, 31600 + os.getpid() % 300, str(tmp_path)), nprocs=2, join=False)
+    deadline = time.monotonic() + 300.0
+    while not ctx.join(timeout=5.0):                                            # (raises if a worker failed; one attempt, under a time limit)
+        if time.monotonic() > deadline:
+            for p in ctx.processes:
+                p.kill()
+            pytest.fail("the two ranks did not finish within 300 s")
+    a, b = (torch.load(tmp_path / f"metrics_{r}.pt") for r in range(2))
+    for name in ("league", "ppo"):
+        ma, mb = a[name]["metrics"], b[name]["metrics"]
+        assert len(ma) == 2 and ma == mb, name                                   # equal on both ranks, to the last figure
+        assert a[name]["flags"] == b[name]["flags"] == 0
+        for i in range(2):
+            assert ma[i]["episodes"] == a[name]["ends"][i] + b[name]["ends"][i] and min(a[name]["ends"][i], b[name]["ends"][i]) >= 64, (name, i, a[name]["ends"], b[name]["ends"])
+            assert ma[i]["nav_conservation_violations"] == 0
+            assert_summary_is_consistent(ma[i], f"{name} iteration {i}")
+    assert set(a["league"]["metrics"][0]["modules"]) >= {"policy_0", "policy_1"} and a["league"]["metrics"][0]["all"]["agent_episodes"] == 8 * a["league"]["metrics"][0]["episodes"]
+    assert a["ppo"]["metrics"][0]["agent_episodes"] == 4 * a["ppo"]["metrics"][0]["episodes"]

@@ -356,3 +356,329 @@ def test_episode_returns_equal_the_float64_recursion(T):
         assert (np.abs(acc[0] - want) <= bound).all(), (rnd, acc[0], want)
         print(f"\n[episode returns] T {T} rollout {rnd}: worst done_sum error / (2 n eps sum|x|) = {float((np.abs(acc[0] - want) / bound).max()):.3g}")
     assert (np.abs(running[256:320]) > 0).all()
+
+
+# ---- the metrics setting and captured rollouts; the training loops and evaluate() leave the setting they were asked for -------------------------------------------------
+ROLLOUT_CASES = [("shared", 1, "2"), ("shared", 2, "2"), ("shared", 1, "0"), ("shared", 2, "0"),      # the one-launch k_policy_step (where the env qualifies) / two launches per step
+                 ("league", 1, None), ("league", 2, None), ("greedy", 1, None), ("greedy", 2, None)]    # (neither ever takes the one-launch step)
+
+
+class _RolloutCase:
+    """the smallest rollout of test_fused_rollout_metrics_equal_the_oracle_replay (40 x 4, n_hist 2, 5-step episodes, 14 steps: ends fall inside every rollout), its
+    greedy chains, or a league's (PolicyBank, 64 x 8): an env, the driver of its chains, the oracle twin and the host-side tallies"""
+    T, max_step, cash, seed = 14, 5, 20000, 880
+
+    def __init__(self, kind, one_launch=None, monkeypatch=None, oracle=True):
+        from gym_continuousdoubleauction_amd import CDAVecEnv, mlp
+        from episode_metrics_util import OracleEpisodeMetrics
+        if one_launch is not None:
+            monkeypatch.setenv("CDA_POLICY_STEP", one_launch)
+        self.kind, self.greedy = kind, kind == "greedy"
+        self.module_of, self.n_mod = None, 1
+        if kind == "league":
+            from gym_continuousdoubleauction_amd.league import LeagueSlotMapper
+            self.N, self.A, k = 64, 8, 2
+            self.cfg = _cfg(self.A, self.max_step, self.cash)
+            self.env = CDAVecEnv(self.cfg, n_markets=self.N, with_info=False)
+            self.env.reset(seed=self.seed)
+            bank = mlp.PolicyBank("cuda:0", self.N, self.A, k, max_frozen=4, seed=5, random_seed=9)
+            mapper = LeagueSlotMapper(self.A, k, self.A - k, 1.0, 3.0)
+            net_of = {}
+            for _ in range(2):
+                cid = mapper.add_champion()
+                net_of[cid] = bank.snapshot(0)
+            slot_pool = torch.full((self.N, self.A), -1, dtype=torch.int32, device="cuda:0")
+            mapper.assign_device(bank, episode_ids=[f"e0-m{i}" for i in range(self.N)], net_of=net_of, slot_pool=slot_pool)
+            self.module_of = torch.where(slot_pool < 0, torch.arange(self.A, device="cuda:0", dtype=torch.int32).expand(self.N, self.A), slot_pool + k).to(torch.int32).contiguous()
+            self.n_mod, self.driver = len(mapper.available_modules), bank
+        else:
+            self.N, self.A = 40, 4
+            self.cfg = _cfg(self.A, self.max_step, self.cash, n_hist=2)
+            self.env = CDAVecEnv(self.cfg, n_markets=self.N, with_info=False)
+            self.env.reset(seed=self.seed)
+            self.driver = mlp.FusedPolicy("cuda:0", seed=3, n_hist=2)
+        self.ora = _oracle(self.cfg, self.N, self.seed) if oracle else None
+        self.em = OracleEpisodeMetrics(self.N, self.A, self.cash) if oracle else None
+
+    def chains(self, groups, seed=17, use_graphs=True):
+        from gym_continuousdoubleauction_amd import mlp
+        return mlp.RolloutChains(self.env, self.driver, self.T, groups=groups, seed=seed, greedy=self.greedy, use_graphs=use_graphs)
+
+    def run(self, roll):
+        """one rollout on the device, the same actions through the oracle; returns the rollout's buffers on the host"""
+        b = {k: v.cpu().numpy().copy() for k, v in roll.run().items()}
+        torch.cuda.synchronize()
+        if self.ora is not None:
+            _replay(self.ora, self.em, [tuple(b[k][t] for k in ACTION_KEYS) for t in range(self.T)])
+        return b
+
+    def oracle_enable(self):
+        """include/cda.h, an episode in flight at cda_episode_metrics_enable: the running tallies restart from zero, the episode's step count goes on (the
+        header's t_step), its end-of-episode account figures are the whole episode's; nothing that ended while the metrics were off was credited"""
+        em = self.em
+        em.term_sum[:] = 0; em.term_sq[:] = 0; em.ret[:] = 0; em.cnt[:] = 0
+        em.F[:] = 0; em.M[:] = 0; em.violating.clear()
+        return em.steps.copy()
+
+    def collect(self):
+        dev = [t.cpu().numpy() for t in (self.env.collect_episode_metrics() if self.module_of is None else
+                                         self.env.collect_episode_metrics(module_of=self.module_of, n_modules=self.n_mod))]
+        return dev
+
+    def reference(self):
+        return self.em.table(None if self.module_of is None else self.module_of.cpu().numpy(), self.n_mod)
+
+    def close(self):
+        self.env.close()
+        if self.ora is not None:
+            self.ora.close()
+
+
+def _assert_zero_tables(dev, what):
+    assert not dev[0].any() and not dev[1].any(), (what, dev[1])
+
+
+@pytest.mark.parametrize("kind,groups,one_launch", ROLLOUT_CASES)
+def test_a_captured_rollout_refuses_a_changed_metrics_setting(kind, groups, one_launch, monkeypatch):
+    """The step instance (tallying or not) and the tolerance are arguments frozen into the captured graphs.  Captured with the metrics off and replayed after an enable
+    the rollout tallied nothing: collect returned zero episodes and the strict NAV check passed with nothing checked.  run() now refuses, as for the tape, the scripts,
+    the schedule, the quotes and the label tap - enable after capture, disable after capture, a changed nav_tolerance alone - and a FRESH RolloutChains on the same
+    env then tallies: its tables are the oracle replay's, with a non-zero episode count"""
+    from gym_continuousdoubleauction_amd import _capi as K
+    from episode_metrics_util import assert_tables_equal
+    c = _RolloutCase(kind, one_launch, monkeypatch)
+    if one_launch is not None:
+        from gym_continuousdoubleauction_amd._lib import lib
+        assert lib().cda_policy_step_supported(c.env._h) == 1                   # ("2": the one-launch step wherever supported - this env is; "0": never)
+    roll = c.chains(groups)
+    c.run(roll)                                                                  # the capture: metrics off
+    assert roll.graphs is not None
+    c.env.enable_episode_metrics(True)
+    in_flight = c.oracle_enable()
+    with pytest.raises(RuntimeError, match="episode metrics"):
+        roll.run()
+    with pytest.raises(RuntimeError, match="episode metrics"):                  # (and again: the refusal is no one-off)
+        roll.run()
+    _assert_zero_tables(c.collect(), "nothing ran, nothing was credited")
+    assert (in_flight > 0).any()                                                 # episodes are under way at the enable: credited at their end by the in-flight rule
+    fresh = c.chains(groups, seed=23)
+    c.run(fresh)                                                                 # captured with the metrics on
+    dev, ref = c.collect(), c.reference()
+    assert dev[1][K.EM_ENV_EPISODES] >= 2 * c.N and dev[0][:, K.EM_EPISODES].sum() >= 2 * c.N * c.A      # the count the replayed off-graphs left at zero
+    assert_tables_equal(dev[0], dev[1], *ref, what="fresh chains after the refusal")
+    c.env.enable_episode_metrics(False)                                          # the reverse order: captured on, replayed off
+    with pytest.raises(RuntimeError, match="episode metrics"):
+        fresh.run()
+    c.env.enable_episode_metrics(True, nav_tolerance=1e-3)                       # on again, but with another tolerance: the graphs hold 1e-6
+    with pytest.raises(RuntimeError, match="nav_tolerance"):
+        fresh.run()
+    assert (c.env.flags() == 0).all()
+    c.close()
+
+
+@pytest.mark.parametrize("kind,groups,one_launch", ROLLOUT_CASES)
+def test_a_toggle_there_and_back_keeps_the_captured_rollout(kind, groups, one_launch, monkeypatch):
+    """evaluate() enables the metrics on a caller's env and puts the caller's setting back: the SETTING is what the graphs hold, so chains captured before stay valid.
+    Off: the next rollout is bit for bit, in every buffer, the one of a twin env that was never toggled.  On: the tables are the oracle replay's under the in-flight
+    rule of include/cda.h - every episode that started after the second enable whole, the ones under way at it with the tallies of their remaining steps"""
+    from gym_continuousdoubleauction_amd import _capi as K
+    from episode_metrics_util import assert_tables_equal
+    c, twin = _RolloutCase(kind, one_launch, monkeypatch), _RolloutCase(kind, one_launch, monkeypatch, oracle=False)
+    roll, roll_twin = c.chains(groups), twin.chains(groups)
+    first, first_twin = c.run(roll), twin.run(roll_twin)
+    assert all(np.array_equal(first[k].view(np.uint8), first_twin[k].view(np.uint8)) for k in first)
+    c.env.enable_episode_metrics(True)                                           # what evaluate() does to an env whose metrics are off ...
+    c.env.enable_episode_metrics(False)                                          # ... and its finally clause
+    second, second_twin = c.run(roll), twin.run(roll_twin)
+    assert set(second) == set(second_twin) and len(second) >= 13
+    for k in second:
+        assert np.array_equal(second[k].view(np.uint8), second_twin[k].view(np.uint8)), (k, "the toggled env's rollout left its twin's")
+    assert not np.array_equal(second["reward"], first["reward"])
+    for i in (0, c.N - 1):
+        assert bytes(c.env.get_state(i)) == bytes(twin.env.get_state(i))
+    _assert_zero_tables(c.collect(), "off again: nothing tallied")
+    twin.close()
+    # the on setting: captured on, toggled off and on again with the same tolerance
+    c.env.enable_episode_metrics(True)
+    c.oracle_enable()
+    on = c.chains(groups, seed=29)
+    c.run(on)
+    dev, ref = c.collect(), c.reference()
+    assert_tables_equal(dev[0], dev[1], *ref, what="the capturing rollout")
+    c.env.enable_episode_metrics(False)
+    c.env.enable_episode_metrics(True)
+    in_flight = c.oracle_enable()
+    assert (in_flight > 0).any()
+    c.run(on)                                                                    # not refused
+    dev, ref = c.collect(), c.reference()
+    assert dev[1][K.EM_ENV_EPISODES] >= 2 * c.N
+    assert_tables_equal(dev[0], dev[1], *ref, what="after the toggle there and back")
+    c.close()
+
+
+@pytest.mark.parametrize("kind,groups,one_launch", [("shared", 2, "2"), ("shared", 1, "0"), ("league", 2, None), ("greedy", 1, None)])
+def test_direct_launch_chains_follow_the_setting_and_an_episode_in_flight_is_credited_by_the_rule(kind, groups, one_launch, monkeypatch):
+    """use_graphs=False freezes nothing: every run() launches with the env's setting of that moment.  Pins include/cda.h's rule for an episode under way at an enable:
+    credited at its end, its tallies those of the steps after the enable, its step count and account figures the whole episode's"""
+    from gym_continuousdoubleauction_amd import _capi as K
+    from episode_metrics_util import assert_tables_equal
+    c = _RolloutCase(kind, one_launch, monkeypatch)
+    roll = c.chains(groups, use_graphs=False)
+    c.run(roll)                                                                  # off
+    _assert_zero_tables(c.collect(), "off")
+    c.env.enable_episode_metrics(True)
+    in_flight = c.oracle_enable()
+    assert roll.graphs is None and (in_flight == c.T % c.max_step).sum() >= c.N // 2      # most markets are 4 steps into a 5-step episode
+    c.run(roll)
+    dev, ref = c.collect(), c.reference()
+    assert dev[1][K.EM_ENV_EPISODES] >= 2 * c.N
+    assert_tables_equal(dev[0], dev[1], *ref, what="on: follows the enable")
+    # the in-flight episodes' steps count whole: the credited steps and the ones still under way are the rollout's plus what had run before the enable
+    assert dev[1][K.EM_ENV_STEPS] + c.em.steps.sum() == c.N * c.T + in_flight.sum()
+    c.env.enable_episode_metrics(False)
+    c.run(roll)
+    _assert_zero_tables(c.collect(), "off again: follows the disable")
+    c.env.enable_episode_metrics(True, nav_tolerance=1e-3)
+    c.oracle_enable()
+    c.run(roll)
+    dev, ref = c.collect(), c.reference()
+    assert_tables_equal(dev[0], dev[1], *ref, what="on again, another tolerance")
+    assert (c.env.flags() == 0).all()
+    c.close()
+
+
+def _ends(roll):
+    return int((roll.buf["terminated"] | roll.buf["truncated"]).sum().item())
+
+
+def test_a_training_loop_without_metrics_turns_them_off_on_an_env_that_has_them_on():
+    """train_fused / train_league_fused(episode_metrics=False) on an env whose metrics are on: nothing would collect what the tallying kernels accumulate, so the
+    loops set the state they were asked for - off - before their chains capture, and nothing accumulates"""
+    from gym_continuousdoubleauction_amd import CDAVecEnv, ppo
+    from gym_continuousdoubleauction_amd.league_train import train_league_fused
+    quiet = dict(iters=1, horizon=5, epochs=1, chains=2, log=lambda s: None, episode_metrics=False)
+    for A in (4, 8):
+        env = CDAVecEnv(_cfg(A, 5, 20000), n_markets=64, with_info=False)
+        env.reset(seed=3)
+        env.enable_episode_metrics(True, nav_tolerance=1e-3)
+        keep = {}
+        out = (ppo.train_fused(env, keep=keep, **quiet) if A == 4 else train_league_fused(env, num_trainable=2, keep=keep, **quiet))
+        history = out[-1]
+        assert _ends(keep["rollout"]) >= 64                                      # episodes did end during the loop
+        assert env.episode_metrics_on is False and "episode_metrics" not in history[0]
+        _assert_zero_tables([t.cpu().numpy() for t in env.collect_episode_metrics()], f"{A} agents: accumulated during a loop that collects nothing")
+        env.close()
+
+
+def test_a_data_parallel_loop_refuses_an_allreduce_that_can_only_sum():
+    """the ranks' tables hold MIN and MAX columns: a callable without op= is refused by both loops before anything runs (never summed); without episode metrics
+    the same callable is taken, as before"""
+    from gym_continuousdoubleauction_amd import CDAVecEnv, ppo
+    from gym_continuousdoubleauction_amd.league_train import train_league_fused
+    quiet = dict(iters=1, horizon=5, epochs=1, chains=2, log=lambda s: None, allreduce=lambda t: t, world=2)
+    env = CDAVecEnv(_cfg(4, 5, 20000), n_markets=64, with_info=False)
+    host_epoch = env.host_epoch
+    with pytest.raises(TypeError, match="min"):
+        ppo.train_fused(env, **quiet)
+    with pytest.raises(TypeError, match="min"):
+        train_league_fused(env, num_trainable=2, **quiet)
+    assert env.host_epoch == host_epoch and not getattr(env, "episode_metrics_on", False)      # not reset, not enabled: refused first
+    _, history = ppo.train_fused(env, episode_metrics=False, **quiet)
+    assert len(history) == 1 and "episode_metrics" not in history[0]
+    env.close()
+
+
+def test_train_fused_reports_every_episode_end_of_its_rollouts():
+    """episode_metrics=True on an env that comes with them off: history[i]["episode_metrics"]["episodes"] is the number of episode ends in iteration i's
+    terminated | truncated buffers (8-step rollouts over 5-step episodes: three ends per market over the two, early terminations on top)"""
+    from gym_continuousdoubleauction_amd import CDAVecEnv, ppo
+    env = CDAVecEnv(_cfg(4, 5, 3000), n_markets=64, with_info=False)
+    keep, ends = {}, []
+    _, history = ppo.train_fused(env, iters=2, horizon=8, epochs=1, chains=2, keep=keep, log=lambda s: ends.append(_ends(keep["rollout"])), episode_metrics=True)
+    assert env.episode_metrics_on is True and len(ends) == 2 and min(ends) >= 64 and sum(ends) >= 3 * 64
+    assert [h["episode_metrics"]["episodes"] for h in history] == ends
+    assert all(h["episode_metrics"]["nav_conservation_violations"] == 0 for h in history) and (env.flags() == 0).all()
+    env.close()
+
+
+def test_evaluate_puts_the_callers_tolerance_back():
+    """evaluate() on an env with enable_episode_metrics(True, nav_tolerance=1e-3): afterwards the setting is the caller's, tolerance included - a ledger fault of
+    1e-4 seeded after the call (the recipe of test_a_ledger_fault_in_an_episode_that_auto_resets_mid_run_is_reported) is within it and is not flagged"""
+    from decimal import Decimal
+    from gym_continuousdoubleauction_amd import CDAVecEnv, _capi as K, mlp
+    from gym_continuousdoubleauction_amd import episode_metrics as EM
+    from gym_continuousdoubleauction_amd.evaluate import evaluate
+    N, A, max_step, victim = 64, 4, 6, 37
+    env = CDAVecEnv(_cfg(A, max_step), n_markets=N, with_info=False)
+    env.reset(seed=99)
+    env.enable_episode_metrics(True, nav_tolerance=1e-3)
+    res = evaluate(env, mlp.FusedPolicy("cuda:0", seed=3), episodes=1, seed=1, groups=2)
+    assert res["episodes"] >= N
+    assert env.episode_metrics_on is True and env.episode_metrics_tolerance == 1e-3
+    env.reset(seed=99)
+    env.collect_episode_metrics()
+    rng = np.random.default_rng(2)
+    for _ in range(2):
+        env.step(*_actions(rng, N, A))
+    st = env.get_state(victim)
+    for field in ("cash", "nav", "prev_nav", "max_nav"):                        # agent 2 finds a hundredth of a cent that nobody lost: inside 1e-3, outside 1e-6
+        d = getattr(st.acc[2], field)
+        setattr(st.acc[2], field, K.decimal_to_dec(K.dec_to_decimal(d) + Decimal("0.0001")))
+    env.set_state(victim, st)
+    for _ in range(max_step + 2):
+        env.step(*_actions(rng, N, A))
+    torch.cuda.synchronize()
+    assert not (env.flags().cpu().numpy() & K.FLAG_NAV_CONSERVATION).any()
+    s = EM.summarise(*env.collect_episode_metrics())
+    assert s["episodes"] >= N and s["nav_conservation_violations"] == 0 and s["nav_conservation_error"] == 1e-4      # seen, and within the caller's tolerance
+    EM.check_nav_conservation(0, s, strict=True)
+    env.close()
+
+
+def test_shard_tables_merge_into_the_union_envs_table():
+    """episode_metrics.merge_tables against the device's own reduction: env U steps 2N markets, S0 and S1 its halves (markets are seeded by global index and independent,
+    so U's records ARE the shards': asserted on the state dumps).  Three modules, one of them only in S0's markets.  merge([S0's tables, S1's]) is U's table: integer,
+    min and max columns bit for bit, the f64 sums within the order bound (U adds its rows in another order than the two shards and the host)"""
+    from gym_continuousdoubleauction_amd import CDAVecEnv, _capi as K
+    from gym_continuousdoubleauction_amd import episode_metrics as EM
+    from episode_metrics_util import OracleEpisodeMetrics, abs_sums, assert_summary_is_consistent, assert_tables_within_order_bound
+    N, A, max_step, T, seed, cash, n_mod = 32, 4, 5, 14, 640, 3000, 3
+    cfg = _cfg(A, max_step, cash)
+    envs = [CDAVecEnv(cfg, n_markets=n, with_info=False) for n in (2 * N, N, N)]
+    for env, s in zip(envs, (seed, seed, seed + N)):
+        env.reset(seed=s)
+        env.enable_episode_metrics(True)
+    U, S0, S1 = envs
+    rng = np.random.default_rng(12)
+    steps = [_actions(rng, 2 * N, A, aggressive=True) for _ in range(T)]
+    for acts in steps:
+        U.step(*acts)
+        S0.step(*(x[:N] for x in acts))
+        S1.step(*(x[N:] for x in acts))
+    for i in range(2 * N):
+        assert bytes(U.get_state(i)) == bytes((S0 if i < N else S1).get_state(i % N)), i
+    module_of = ((np.arange(2 * N)[:, None] + np.arange(A)[None, :]) % 2).astype(np.int32)
+    module_of[:N:3, 0] = 2                                                        # module 2 plays in the first shard's markets only
+    tables = []
+    for env, rows in ((U, slice(0, 2 * N)), (S0, slice(0, N)), (S1, slice(N, 2 * N))):
+        mo = torch.from_numpy(np.ascontiguousarray(module_of[rows])).to(env.device)
+        tables.append([t.cpu().numpy() for t in env.collect_episode_metrics(module_of=mo, n_modules=n_mod)])
+    union, shard0, shard1 = tables
+    assert shard0[0][2, K.EM_EPISODES] > 0 and not shard1[0][2].any()
+    assert not np.array_equal(shard0[0], union[0]) and not np.array_equal(shard1[0], union[0]) and min(shard0[1][0], shard1[1][0]) >= 2 * N and shard0[1][0] + shard1[1][0] == union[1][0]
+    merged = EM.merge_tables([shard0, shard1])
+    ora, em = _oracle(cfg, 2 * N, seed), OracleEpisodeMetrics(2 * N, A, cash)     # (the oracle's rows give the bound its scale - and hold U itself to the replay)
+    _replay(ora, em, steps)
+    sums = abs_sums(em, module_of, n_mod)
+    ref = em.table(module_of, n_mod)
+    assert em.F is not None and ref[0][:, K.EM_TRADES].sum() > 100 and ref[0][:, K.EM_MAKER_RATIO_N].sum() > 0
+    worst = assert_tables_within_order_bound(merged[0], merged[1], union[0], union[1], sums, what="merge of the shards against the union env")
+    worst_ref = assert_tables_within_order_bound(union[0], union[1], *ref, sums, what="the union env against the oracle")
+    print(f"\n[merge of shard tables] worst f64 sum error / (2 n eps sum|x|): merged vs union {worst:.3g}, union vs oracle {worst_ref:.3g}")
+    assert_summary_is_consistent(EM.summarise(*merged), "merged shards")
+    naive = (shard0[0] + shard1[0], shard0[1] + shard1[1])                        # a SUM over the shards is NOT the union's table
+    assert naive[0][0, K.EM_NAV_MIN] != union[0][0, K.EM_NAV_MIN] and naive[0][0, K.EM_NAV_MAX] != union[0][0, K.EM_NAV_MAX]
+    for env in envs:
+        assert (env.flags() == 0).all()
+        env.close()
+    ora.close()
