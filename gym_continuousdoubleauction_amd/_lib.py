@@ -21,6 +21,7 @@ SYMBOLS = [
     "cda_step_range", "cda_reset_range", "cda_step_groups", "cda_group_range", "cda_random_actions", "cda_book_peak", "cda_check_invariants", "cda_selftest_libm", "cda_selftest_libm_host", "cda_book_capacity",
     "cda_get_book", "cda_book_spill", "cda_book_spill_wanted", "cda_num_agents", "cda_handback_stride", "cda_set_handback", "cda_set_handback_geometry", "cda_handback_unpack", "cda_ppo_loss", "cda_policy_sample", "cda_gae", "cda_store_slots", "cda_step_groups_handback", "cda_handback_groups",
     "cda_step_range_capture", "cda_policy_step_supported", "cda_policy_step_advised", "cda_policy_step_range",
+    "cda_net_step_supported", "cda_net_step_advised", "cda_net_step_range", "cda_policy_step_launch_count",
     "cda_episode_metrics_enable", "cda_episode_metrics_collect",
     "cda_snapshot_table_bytes", "cda_snapshot_offsets", "cda_snapshot_pack", "cda_snapshot_check_header", "cda_snapshot_restore",
     "cda_market_params_from_config", "cda_check_market_params", "cda_set_market_params", "cda_get_market_params",
@@ -189,6 +190,11 @@ def lib():
     L.cda_policy_step_supported.argtypes = [vp]
     L.cda_policy_step_advised.argtypes = [vp]
     L.cda_policy_step_range.argtypes = [vp, i32, i32, vp, vp, vp, u64, vp, i64] + [vp] * 5 + [vp] * 5 + [vp] * 4 + [vp, i32, vp, vp, vp]
+    L.cda_net_step_supported.argtypes = [vp, i32, i32]
+    L.cda_net_step_advised.argtypes = [vp, i32, i32]
+    L.cda_net_step_range.argtypes = [vp, i32, i32] + L.cda_policy_step_range.argtypes[1:]
+    L.cda_policy_step_launch_count.argtypes = [vp]
+    L.cda_policy_step_launch_count.restype = i64
     L.cda_episode_metrics_enable.argtypes = [vp, i32, C.c_double]
     L.cda_episode_metrics_collect.argtypes = [vp, vp, i32, vp, vp, i32, vp]
     L.cda_tape_enable.argtypes = [vp, i64]

@@ -642,6 +642,7 @@ struct cda_env {
     cda::SchedArgs sched;    // cda_schedule_attach: the caller's resident order schedule and the env's own counters table (sched_of == NULL: nothing attached - no launch)
     int64_t sched_epoch;     // moved by every cda_schedule_attach / cda_schedule_detach
     QuoteArgs quotes;        // cda_quotes_enable: the quote tape's rings and meta rows (ring == NULL: off - no launch)
+    int64_t one_launch_steps;   // cda_policy_step_launch_count: k_policy_step / k_net_step launches enqueued since cda_create (host side; a captured enqueue counts once)
 };
 // csrc/cda_quotes.inc (included at the end): the top of the book of [first, first + n), recorded on `stream` ahead of a step; a no-op while quotes are off
 static int quotes_record(cda_env* e, int32_t first, int32_t n, hipStream_t stream);
@@ -1024,18 +1025,33 @@ static PolicyStep policy_step_of(const cda_env* e) {
         default: return {0, {nullptr, nullptr}};
     }
 }
+// ... and the k_net_step instances of the env's history depth (every other network: activation and trunk are arguments; the same dynamic LDS)
+typedef void (*net_step_kern_t)(cda::cap256::NetStepKernArgs);
+struct NetStep { net_step_kern_t kern[2]; };
+static NetStep net_step_of(const cda_env* e) {
+    switch (e->P.cfg.n_hist) {
+#define CDA_NS_CASE(h, sfx) case h: return {{cda::cap256::k_net_step##sfx<false>, cda::cap256::k_net_step##sfx<true>}};
+#define CDA_NS_DEPTH(h) CDA_NS_CASE(h, _h##h)
+        CDA_NS_CASE(4, ) CDA_HIST_DEPTHS(CDA_NS_DEPTH)
+#undef CDA_NS_DEPTH
+#undef CDA_NS_CASE
+        default: return {{nullptr, nullptr}};
+    }
+}
 // More than 64 KB of dynamic LDS has to be granted per device and kernel instance: once, under a lock (envs are created and stepped from several host threads - one per
 // GPU in the guarded collectives of parallel.py), at cda_create - not lazily inside the launch path, whose first call sits inside a stream capture (round-5 ADVICE).
 static int grant_policy_step_lds(const cda_env* e) {
     static std::mutex mu;
-    static unsigned long long granted[CDA_MAX_HIST + 1] = {0};      // per history-depth instance: a bit per device (both tally variants together)
+    static unsigned long long granted[CDA_MAX_HIST + 1] = {0};      // per history-depth instance: a bit per device (both tally variants of both families together: the env does not know the network)
     const int hist = e->P.cfg.n_hist, slot = hist;
     std::lock_guard<std::mutex> lock(mu);
     if (granted[slot] >> (e->device & 63) & 1ull) return 0;
     const PolicyStep ps = policy_step_of(e);
-    if (!ps.kern[0] || !ps.kern[1]) return 1;
+    const NetStep ns = net_step_of(e);
+    if (!ps.kern[0] || !ps.kern[1] || !ns.kern[0] || !ns.kern[1]) return 1;
     for (int k = 0; k < 2; k++)
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(ps.kern[k]), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return 1;
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(ps.kern[k]), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
+            hipFuncSetAttribute(reinterpret_cast<const void*>(ns.kern[k]), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return 1;
     granted[slot] |= 1ull << (e->device & 63);
     return 0;
 }
@@ -1053,12 +1069,13 @@ int cda_policy_step_advised(const cda_env* e) {
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device) != hipSuccess || cus < 1) return 0;
     return (long long)e->P.n_markets <= 16LL * cus;
 }
-int cda_policy_step_range(cda_env* e, int32_t first_market, int32_t n_markets, const void* wb, const float* theta, const float* obs_in,
-                          uint64_t seed, const int64_t* counter_dev, int64_t draw,
-                          int32_t* category, float* size_mean, float* size_sigma, int32_t* price, int32_t* price_offset,
-                          float* a_cont, float* logp, float* value, float* rec, float* dist,
-                          float* obs_out, double* reward_out, uint8_t* terminated_out, uint8_t* truncated_out,
-                          float* fin_obs, int32_t fin_cap, int32_t* fin_count, int32_t* fin_index_out, void* stream) {
+// one launch of k_policy_step (net == NULL) or of k_net_step (the network *net names) over [first_market, first_market + n_markets)
+static int policy_step_enqueue(cda_env* e, const cda::cap256::NetArgs* net, int32_t first_market, int32_t n_markets, const void* wb, const float* theta, const float* obs_in,
+                               uint64_t seed, const int64_t* counter_dev, int64_t draw,
+                               int32_t* category, float* size_mean, float* size_sigma, int32_t* price, int32_t* price_offset,
+                               float* a_cont, float* logp, float* value, float* rec, float* dist,
+                               float* obs_out, double* reward_out, uint8_t* terminated_out, uint8_t* truncated_out,
+                               float* fin_obs, int32_t fin_cap, int32_t* fin_count, int32_t* fin_index_out, void* stream) {
     if (!e || !wb || !theta || !obs_in || !counter_dev || !a_cont || !logp || !value) return CDA_ERR_INVALID;
     if (!cda_policy_step_supported(e)) return CDA_ERR_UNSUPPORTED;
     StepArgs S;
@@ -1069,17 +1086,60 @@ int cda_policy_step_range(cda_env* e, int32_t first_market, int32_t n_markets, c
     HIPCHK(hipSetDevice(e->device));
     const PolicyStep ps = policy_step_of(e);
     const size_t smem = (size_t)ps.lds;
-    const policy_step_kern_t kern = ps.kern[e->P.lay.ep_on != 0];
-    if (!kern) return CDA_ERR_UNSUPPORTED;
+    const int tally = e->P.lay.ep_on != 0;
+    const NetStep ns = net_step_of(e);
+    if (!ps.kern[tally] || !ns.kern[tally]) return CDA_ERR_UNSUPPORTED;
     if (grant_policy_step_lds(e)) return CDA_ERR_HIP;     // (normally a no-op: cda_create granted it - outside any stream capture)
     cda::cap256::PolicyStepKernArgs KA;
     KA.K.arena = e->arena; KA.K.P = e->P; KA.K.S = S; KA.K.S.first_market = first_market; KA.K.S.end_market = first_market + n_markets;
     KA.F.obs_in = obs_in; KA.F.wb = wb; KA.F.theta = theta; KA.F.seed = seed; KA.F.counter = (const long long*)counter_dev; KA.F.draw = draw;
     KA.F.category = category; KA.F.size_mean = size_mean; KA.F.size_sigma = size_sigma; KA.F.price = price; KA.F.price_offset = price_offset;
     KA.F.a_cont = a_cont; KA.F.logp = logp; KA.F.value = value; KA.F.rec = rec; KA.F.dist = dist;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((n_markets + cda::cap256::PS_WPB - 1) / cda::cap256::PS_WPB)), dim3(64 * cda::cap256::PS_WPB), smem, (hipStream_t)stream, KA);
-    return launch_status();
+    const dim3 grid((unsigned)((n_markets + cda::cap256::PS_WPB - 1) / cda::cap256::PS_WPB)), block(64 * cda::cap256::PS_WPB);
+    if (net) {
+        cda::cap256::NetStepKernArgs KN;
+        KN.K = KA.K; KN.F = KA.F; KN.N = *net;
+        hipLaunchKernelGGL(ns.kern[tally], grid, block, smem, (hipStream_t)stream, KN);
+    } else hipLaunchKernelGGL(ps.kern[tally], grid, block, smem, (hipStream_t)stream, KA);
+    const int rcl = launch_status();
+    if (rcl == CDA_OK) e->one_launch_steps++;
+    return rcl;
 }
+int cda_policy_step_range(cda_env* e, int32_t first_market, int32_t n_markets, const void* wb, const float* theta, const float* obs_in,
+                          uint64_t seed, const int64_t* counter_dev, int64_t draw,
+                          int32_t* category, float* size_mean, float* size_sigma, int32_t* price, int32_t* price_offset,
+                          float* a_cont, float* logp, float* value, float* rec, float* dist,
+                          float* obs_out, double* reward_out, uint8_t* terminated_out, uint8_t* truncated_out,
+                          float* fin_obs, int32_t fin_cap, int32_t* fin_count, int32_t* fin_index_out, void* stream) {
+    return policy_step_enqueue(e, NULL, first_market, n_markets, wb, theta, obs_in, seed, counter_dev, draw, category, size_mean, size_sigma, price, price_offset,
+                               a_cont, logp, value, rec, dist, obs_out, reward_out, terminated_out, truncated_out, fin_obs, fin_cap, fin_count, fin_index_out, stream);
+}
+// ... for a network with another hidden activation (csrc/cda_mlp_dev.inc ActT<> code: 0 tanh, 1 relu, 2 elu, 3 linear) and / or the shared trunk: k_net_step, the
+// same kernel with the two choices read from its arguments.  (0, 0) IS cda_policy_step_range.  The env conditions are cda_policy_step_supported's for every network.
+static int net_code_ok(int32_t activation, int32_t vf_share_layers) { return activation >= 0 && activation <= 3 && (vf_share_layers == 0 || vf_share_layers == 1); }
+int cda_net_step_supported(const cda_env* e, int32_t activation, int32_t vf_share_layers) {
+    if (!net_code_ok(activation, vf_share_layers)) return CDA_ERR_INVALID;
+    return cda_policy_step_supported(e);
+}
+// (profiles/net_step/cost.txt: the rule of cda_policy_step_advised, N <= 16 x CUs, for every network)
+int cda_net_step_advised(const cda_env* e, int32_t activation, int32_t vf_share_layers) {
+    if (!net_code_ok(activation, vf_share_layers)) return CDA_ERR_INVALID;
+    return cda_policy_step_advised(e);
+}
+int cda_net_step_range(cda_env* e, int32_t activation, int32_t vf_share_layers,
+                       int32_t first_market, int32_t n_markets, const void* wb, const float* theta, const float* obs_in,
+                       uint64_t seed, const int64_t* counter_dev, int64_t draw,
+                       int32_t* category, float* size_mean, float* size_sigma, int32_t* price, int32_t* price_offset,
+                       float* a_cont, float* logp, float* value, float* rec, float* dist,
+                       float* obs_out, double* reward_out, uint8_t* terminated_out, uint8_t* truncated_out,
+                       float* fin_obs, int32_t fin_cap, int32_t* fin_count, int32_t* fin_index_out, void* stream) {
+    if (!net_code_ok(activation, vf_share_layers)) return CDA_ERR_INVALID;
+    const cda::cap256::NetArgs net = {activation, vf_share_layers};
+    return policy_step_enqueue(e, activation == 0 && vf_share_layers == 0 ? NULL : &net, first_market, n_markets, wb, theta, obs_in, seed, counter_dev, draw,
+                               category, size_mean, size_sigma, price, price_offset, a_cont, logp, value, rec, dist, obs_out, reward_out, terminated_out, truncated_out,
+                               fin_obs, fin_cap, fin_count, fin_index_out, stream);
+}
+int64_t cda_policy_step_launch_count(const cda_env* e) { return e ? e->one_launch_steps : 0; }
 
 int cda_step(cda_env* e, const int32_t* category, const float* size_mean, const float* size_sigma,
              const int32_t* price, const int32_t* price_offset, const uint8_t* present,

@@ -724,7 +724,13 @@ constexpr int PS_PF = CDA_PS_PF;                 // weight ring depth (k-steps i
 #define CDA_HIST_BODY "cda_policy_step.inc"
 #define CDA_HIST_OPEN
 #define CDA_HIST_CLOSE
+#define PS_NET 0
+#define PS_KERNEL k_policy_step
+#define PS_KERNARGS PolicyStepKernArgs
 #include "cda_hist_variants.inc"
+#undef PS_NET
+#undef PS_KERNEL
+#undef PS_KERNARGS
 #undef CDA_HIST_BODY
 #undef CDA_HIST_OPEN
 #undef CDA_HIST_CLOSE
@@ -939,4 +945,33 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_raw_snapshot(uint8_t* arena, P
     aggregate_levels<true>(L, m, lane);
     if (lane < CDA_RAW_DIM) raw_out[(size_t)mi * CDA_RAW_DIM + (size_t)lane] = raw_value(L, lane);
 }
+#if CDA_CAP == 256
+// ------------------------------------------------------------------------------------------
+// k_net_step - k_policy_step for every OTHER network the project trains (fcnet_activation relu / elu / linear, and vf_share_layers with any activation)
+// ------------------------------------------------------------------------------------------
+// The body file of k_policy_step once more: one instance per history depth, the hidden activation (csrc/cda_mlp_dev.inc ActT<> code) and the trunk chosen at run time
+// by two scalars of its arguments, both uniform branches inside the forward (forward16_net: the activation in the two hidden-layer epilogues, never around the MFMA
+// layers; a shared trunk idles waves 8 .. 15 through the forward).  One kernel per (activation, trunk) pair would be 7 x 14 more instances in a translation unit
+// that compiles serially.  Everything behind the forward is k_policy_step's code.  The scalars live in a struct of their own behind PolicyArgs: k_policy_step's
+// arguments keep their size.  (Defined behind every other kernel of the tile: the existing kernels then come out of the compiler instruction for instruction as before.)
+struct NetArgs { int32_t activation; int32_t shared_trunk; };
+struct NetStepKernArgs { StepKernArgs K; PolicyArgs F; NetArgs N; };      // K first, as in PolicyStepKernArgs
+#define PS_NS CDA_HIST_SFX(mlpdev)
+#define PS_NAME(x) CDA_HIST_SFX(x)
+#define CDA_HIST_BODY "cda_policy_step.inc"
+#define CDA_HIST_OPEN
+#define CDA_HIST_CLOSE
+#define PS_NET 1
+#define PS_KERNEL k_net_step
+#define PS_KERNARGS NetStepKernArgs
+#include "cda_hist_variants.inc"
+#undef PS_NET
+#undef PS_KERNEL
+#undef PS_KERNARGS
+#undef CDA_HIST_BODY
+#undef CDA_HIST_OPEN
+#undef CDA_HIST_CLOSE
+#undef PS_NS
+#undef PS_NAME
+#endif
 } }  // namespace cda::CDA_CAPNS

@@ -1881,23 +1881,33 @@ static int rollout_chain(cda_env* env, const cda_league* L, const void* wb, cons
     // One launch per step where the env qualifies (include/cda.h cda_policy_step_range: the policy evaluated inside the step kernel) - one shared policy,
     // no info chain; CDA_POLICY_STEP=0 in the environment keeps the two launches (A / B runs, tests of both paths).
     bool one_launch = false;
+    constexpr bool NET_STEP = CDA_MLP_ACT != 0 || CDA_MLP_VFS != 0;
     {
         const char* ev = getenv("CDA_POLICY_STEP");              // read per call: an A / B run toggles it between two rollouts of one process
         const int want = ev ? atoi(ev) : 1;
         // (the env's history depth is this build's: checked above.  CDA_POLICY_STEP=2: wherever supported, also where the batched policy kernel is the faster one)
-        // (k_policy_step is compiled with the tanh network only: an object of another activation (CDA_MLP_ACT) always takes the two launches)
-        // (... and a separate value network: a shared-trunk object (CDA_MLP_VFS) takes the two launches as well)
-        one_launch = CDA_MLP_ACT == 0 && !CDA_MLP_VFS && !greedy && want != 0 && !L && !B->info_steps && (want == 2 ? cda_policy_step_supported(env) : cda_policy_step_advised(env));
+        // (the default object - tanh, its own value network - launches k_policy_step, compiled with that network; an object of another activation (CDA_MLP_ACT) or the
+        // shared trunk (CDA_MLP_VFS) launches k_net_step, which reads both from its arguments: include/cda.h cda_net_step_range)
+        const bool ok = NET_STEP ? (want == 2 ? cda_net_step_supported(env, CDA_MLP_ACT, CDA_MLP_VFS) : cda_net_step_advised(env, CDA_MLP_ACT, CDA_MLP_VFS)) == 1
+                                 : (want == 2 ? cda_policy_step_supported(env) : cda_policy_step_advised(env)) != 0;
+        one_launch = !greedy && want != 0 && !L && !B->info_steps && ok;
     }
     for (int32_t t = 0; t < n_steps; t++) {
         const size_t o = (size_t)t * NA;
         if (one_launch) {
-            const int rc1 = cda_policy_step_range(env, first_market, n_markets, wb, theta, B->obs + (size_t)t * N * OBS, seed, counter_dev, t,
-                                                  B->category + o, B->size_mean + o, B->size_sigma + o, B->price + o, B->price_offset + o,
-                                                  B->a_cont + 2 * o, B->logp + o, B->value + (size_t)t * N, B->record ? B->record + 8 * o : NULL,
-                                                  B->dist ? B->dist + (size_t)t * N * CDA_MLP_DIST_LD : NULL,
-                                                  B->obs + (size_t)(t + 1) * N * OBS, B->reward + o, B->terminated + (size_t)t * N, B->truncated + (size_t)t * N,
-                                                  B->fin_obs, B->fin_cap, B->fin_count, B->fin_index ? B->fin_index + (size_t)t * N : NULL, stream);
+            float* const rec_t = B->record ? B->record + 8 * o : NULL;
+            float* const dist_t = B->dist ? B->dist + (size_t)t * N * CDA_MLP_DIST_LD : NULL;
+            int32_t* const fin_t = B->fin_index ? B->fin_index + (size_t)t * N : NULL;
+            const int rc1 = NET_STEP ? cda_net_step_range(env, CDA_MLP_ACT, CDA_MLP_VFS, first_market, n_markets, wb, theta, B->obs + (size_t)t * N * OBS, seed, counter_dev, t,
+                                                          B->category + o, B->size_mean + o, B->size_sigma + o, B->price + o, B->price_offset + o,
+                                                          B->a_cont + 2 * o, B->logp + o, B->value + (size_t)t * N, rec_t, dist_t,
+                                                          B->obs + (size_t)(t + 1) * N * OBS, B->reward + o, B->terminated + (size_t)t * N, B->truncated + (size_t)t * N,
+                                                          B->fin_obs, B->fin_cap, B->fin_count, fin_t, stream)
+                                     : cda_policy_step_range(env, first_market, n_markets, wb, theta, B->obs + (size_t)t * N * OBS, seed, counter_dev, t,
+                                                             B->category + o, B->size_mean + o, B->size_sigma + o, B->price + o, B->price_offset + o,
+                                                             B->a_cont + 2 * o, B->logp + o, B->value + (size_t)t * N, rec_t, dist_t,
+                                                             B->obs + (size_t)(t + 1) * N * OBS, B->reward + o, B->terminated + (size_t)t * N, B->truncated + (size_t)t * N,
+                                                             B->fin_obs, B->fin_cap, B->fin_count, fin_t, stream);
             if (rc1 == CDA_OK) continue;
             if (t != 0) return rc1;
             one_launch = false;                                  // refused at the first step (nothing has run yet): the two launches take over

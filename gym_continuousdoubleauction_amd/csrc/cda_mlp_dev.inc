@@ -295,3 +295,58 @@ __device__ __forceinline__ void forward16(const __bf16* __restrict__ wb, const f
     }
     __syncthreads();
 }
+// forward16 with the network chosen at RUN time (k_net_step: one kernel instance per history depth for every activation and both trunks): `act` = the ActT<> code
+// 0 .. 3 and `shared` = the shared trunk (CDA_MLP_VFS's network), both uniform over the workgroup.  The choice is made in the two hidden-layer epilogues only - the
+// MFMA layers are the same code for every network, per output element ActT<act>::apply's own expression on the same accumulator: bit for bit forward16's (and so
+// k_mlp_fwd's) outputs of the object compiled with that activation.  Shared trunk: only half 0 exists (Wo row 24 is packed into half 0) - waves 8 .. 15 skip the
+// three MFMA phases and only meet the barriers (the k loops are NOT re-split over them: the summation order is k_mlp_fwd's), and wave 0's head tile owns every
+// output column, the value's 24 included.  R1 of a wave that skips (shared && w >= 8) is never read: its caller need not prime it.
+template <int ACT>
+__device__ __forceinline__ void act_store16(__bf16* dst, const f32x16& acc, float bias_scaled, int h) {
+    #pragma unroll
+    for (int r = 0; r < 8; r++) dst[rowmap(r, h) * ACT_LD] = (__bf16)ActT<ACT>::apply(acc[r], bias_scaled);
+}
+__device__ __forceinline__ void act_store16_by_code(int act, __bf16* dst, const f32x16& acc, float bias_scaled, int h) {
+    switch (act) {                                                               // (uniform: a scalar branch)
+        case 0: act_store16<0>(dst, acc, bias_scaled, h); break;
+        case 1: act_store16<1>(dst, acc, bias_scaled, h); break;
+        case 2: act_store16<2>(dst, acc, bias_scaled, h); break;
+        default: act_store16<3>(dst, acc, bias_scaled, h); break;
+    }
+}
+template <int PF>
+__device__ __forceinline__ void forward16_net(const __bf16* __restrict__ wb, const float* __restrict__ theta, const Fwd16Lds& T, int w, int lane,
+                                              WRing<1, KX / 16, PF, false>& R1, int act, bool shared) {
+    const int q = lane & 31, h = lane >> 5;
+    const int half = w >> 3, grp = (w >> 1) & 3, jt = w & 1;
+    const int f = 256 * half + 64 * grp + 2 * q + jt;
+    const float bias_scale = act == 0 ? ActT<0>::BIAS_SCALE : 1.0f;              // ActT<1 .. 3>::BIAS_SCALE (x * 1 = x: the other objects' bias bit for bit)
+    static_assert(ActT<1>::BIAS_SCALE == 1.0f && ActT<2>::BIAS_SCALE == 1.0f && ActT<3>::BIAS_SCALE == 1.0f, "BIAS_SCALE follows the activation");
+    const float b1 = theta[CDA_MLP_OFF_B1 + f] * bias_scale, b2 = theta[CDA_MLP_OFF_B2 + f] * bias_scale, bo = theta[CDA_MLP_OFF_BO + q];
+    const bool work = !(shared && half);                                         // the value half of a shared trunk does not exist
+    const bool heads = (w & 7) == 0 && work;
+    WRing<1, HID / 16, PF, false> R2, RO;
+    f32x16 acc = zero16();
+    if (work) {
+        layer_mma16(T.xs, XS_LD, R1, lane, acc);                                 // layer 1
+        R2.prime(wb + CDA_MLP_WB_W2 + ((size_t)half * HID + 64 * grp) * HID + (size_t)jt * (HID / 16) * 512, HID, lane);
+        act_store16_by_code(act, T.h1 + (half * F16_ROWS) * ACT_LD + 64 * grp + 2 * q + jt, acc, b1, h);
+    }
+    __syncthreads();
+    if (work) {
+        acc = zero16();
+        layer_mma16(T.h1 + (half * F16_ROWS) * ACT_LD, ACT_LD, R2, lane, acc);   // layer 2
+        if (heads) RO.prime(wb + CDA_MLP_WB_WO + (size_t)half * NOUT * HID, HID, lane);
+        act_store16_by_code(act, T.h2 + (half * F16_ROWS) * ACT_LD + 64 * grp + 2 * q + jt, acc, b2, h);
+    }
+    __syncthreads();
+    if (heads) {
+        acc = zero16();
+        layer_mma16(T.h2 + (half * F16_ROWS) * ACT_LD, ACT_LD, RO, lane, acc);   // heads
+        if (shared || (half == 0 ? q != N_LOGITS : q == N_LOGITS)) {
+            #pragma unroll
+            for (int r = 0; r < 8; r++) T.outs[rowmap(r, h) * OUTS_LD + q] = acc[r] + bo;
+        }
+    }
+    __syncthreads();
+}

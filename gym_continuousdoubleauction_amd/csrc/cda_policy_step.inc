@@ -1,11 +1,15 @@
 // cda_policy_step.inc - k_policy_step for ONE history depth of the observation (the network's input width): included from cda_kernels.inc (256-order tile only)
 // once per compiled depth with  CDA_MLP_HIST = the depth (include/cda_mlp.h's layout macros follow it),  PS_NS = the namespace csrc/cda_mlp_dev.inc was included
 // into at that depth,  PS_NAME(x) = x with the depth's suffix.  The kernel itself is described at its first inclusion (cda_kernels.inc).
+// Included for TWO kernel families:  PS_NET = 0, PS_KERNEL = k_policy_step, PS_KERNARGS = PolicyStepKernArgs  (the tanh network with its own value network, fixed at
+// compile time: forward16) and  PS_NET = 1, PS_KERNEL = k_net_step, PS_KERNARGS = NetStepKernArgs  (activation and trunk read from the arguments: forward16_net).
+#if !PS_NET
 __host__ __device__ constexpr int PS_NAME(policy_step_lds_bytes)(int agents, int n_hist) {
     return DEC_TABLE_BYTES + ZIG_LDS_BYTES + PS_WPB * lds_bytes_per_wave(agents, n_hist) + 16 + PS_NS::F16_LDS_BYTES;
 }
+#endif
 template <bool TALLY>
-__global__ __launch_bounds__(64 * PS_WPB, 1) void PS_NAME(k_policy_step)(PolicyStepKernArgs KA) {
+__global__ __launch_bounds__(64 * PS_WPB, 1) void PS_NAME(PS_KERNEL)(PS_KERNARGS KA) {
     uint8_t* const arena = KA.K.arena;
     const Params& P = KA.K.P;
     const StepArgs& S = KA.K.S;
@@ -44,12 +48,19 @@ __global__ __launch_bounds__(64 * PS_WPB, 1) void PS_NAME(k_policy_step)(PolicyS
         }
         PS_NS::WRing<1, PS_NS::KX / 16, PS_PF, false> R1;
         const int half = wave >> 3, grp = (wave >> 1) & 3, jt = wave & 1;
+#if PS_NET
+        if (!(KA.N.shared_trunk && half))                          // (a shared trunk has no value half: waves 8 .. 15 only meet the forward's barriers)
+#endif
         R1.prime(reinterpret_cast<const __bf16*>(F.wb) + CDA_MLP_WB_W1 + (size_t)(256 * half + 64 * grp) * PS_NS::KX + (size_t)jt * (PS_NS::KX / 16) * 512, PS_NS::KX, lane);
         #pragma unroll
         for (int u = 0; u < PER; u++) { const int c = lane + 64 * u; if (c < CH) PS_NS::obs_to_bf16(T.xs + wave * PS_NS::XS_LD + c * PS_NS::VW, v[u], false); }
         if (wave < 4) stage_tables_commit(tq); else __syncthreads();   // (one barrier either way: the tables and the observation tile are in LDS)
         PH_MARK(ph, 35);
+#if PS_NET
+        PS_NS::forward16_net<PS_PF>(reinterpret_cast<const __bf16*>(F.wb), F.theta, T, wave, lane, R1, KA.N.activation, KA.N.shared_trunk != 0);
+#else
         PS_NS::forward16<PS_PF>(reinterpret_cast<const __bf16*>(F.wb), F.theta, T, wave, lane, R1);
+#endif
         PH_MARK(ph, 36);
     }
     if (!live) return;

@@ -12,6 +12,7 @@ runs once per market-step.
 """
 import ctypes as C
 import math
+import os
 
 import torch
 
@@ -667,6 +668,35 @@ class RolloutChains:
         """the rollout counter the LAST run() sampled with (i64 [1], a fresh device tensor): what cda_mlp_policy_step needs to reproduce its draws"""
         return self._counters[:1] - 1
 
+    @property
+    def launches_per_step(self):
+        """1 where the plain chains' steps are ONE launch (the policy inside the step kernel: include/cda.h cda_policy_step_range, cda_net_step_range), else 2 (network
+        kernel, then step kernel) - csrc/cda_mlp.hip rollout_chain's own rule: a shared sampling policy whose activation and trunk the library is asked about, on an env
+        that qualifies; CDA_POLICY_STEP=0 in the environment keeps the two launches, =2 takes the one wherever supported, anything else where advised.  League, greedy
+        and info chains always take two.  Captured graphs keep the path they were captured with."""
+        if self.graphs is not None:
+            return self._captured_launches
+        return self._launches_now()
+
+    def _launches_now(self):
+        if self.bank is not None or self.greedy:
+            return 2
+        want = os.environ.get("CDA_POLICY_STEP")
+        try:
+            want = 1 if want is None else int(want.strip() or 0)      # (atoi: what does not parse is 0)
+        except ValueError:
+            want = 0
+        if want == 0:
+            return 2
+        act, vfs = ACTIVATIONS.index(self.policy.activation), int(self.policy.vf_share_layers)
+        lib = _lib()
+        return 1 if (lib.cda_net_step_supported if want == 2 else lib.cda_net_step_advised)(self.env._h, act, vfs) == 1 else 2
+
+    def policy_step_launches(self):
+        """one-launch steps enqueued on the env since it was created (include/cda.h cda_policy_step_launch_count: host side - a captured enqueue counts once, replays
+        of the graph do not): which path the rollouts took"""
+        return int(_lib().cda_policy_step_launch_count(self.env._h))
+
     def _enqueue(self, g, copy_first_obs):
         first, cnt = self.ranges[g]
         st = torch.cuda.current_stream(self.device).cuda_stream
@@ -689,6 +719,7 @@ class RolloutChains:
             with torch.cuda.graph(gr, stream=s if s is not None else self._capture_stream):
                 self._enqueue(g, True)
             graphs.append(gr)
+        self._captured_launches = self._launches_now()             # (the chains read CDA_POLICY_STEP as they are enqueued: the graphs keep that path)
         self.graphs = graphs
         # the graphs hold the step instances and arguments of the env's trade-tape setting as it is now (tape-writing kernels and the rings' addresses, or neither)
         self._graph_tape_epoch = getattr(self.env, "tape_epoch", 0)

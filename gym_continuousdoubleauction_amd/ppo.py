@@ -558,8 +558,9 @@ def train_fused(env, iters=4, horizon=64, lr=5e-5, epochs=4, reward_scale=None, 
     The env is put into the state asked for before the rollout graphs are captured: episode_metrics=False switches the metrics of an env that has them on off.
     state_dependent_log_std: a fresh policy gets RLlib's default head for Box actions (two log-stds per row from the policy network: mlp.FusedPolicy); a given `policy`
     brings its own.  hidden: `fcnet_hiddens` of a fresh policy, <= 256 each (mlp.init_theta).  activation: `fcnet_activation` of a fresh policy (mlp.ACTIVATIONS;
-    a given `policy` brings its own); a network that is not tanh rolls out with two launches per step (k_policy_step is the tanh network's).  vf_share_layers: RLlib's
-    shared trunk for a fresh policy (mlp.FusedPolicy; a given `policy` brings its own) - it too rolls out with two launches per step.
+    a given `policy` brings its own).  vf_share_layers: RLlib's shared trunk for a fresh policy (mlp.FusedPolicy; a given `policy` brings its own).  Every
+    activation and either trunk rolls out with ONE launch per chain and step where the env qualifies (the policy inside the step kernel: k_policy_step for the
+    default network, k_net_step for every other - include/cda.h cda_net_step_range; mlp.RolloutChains.launches_per_step says which path the chains take).
     Needs a HIP CDAVecEnv with auto_reset and 168-float observations.  Returns (FusedPolicy, history); `keep` (a dict) receives the last
     rollout's buffers and the RolloutChains object.  history[i]: losses, `mean_reward` (of the rollout's slice of the episodes - it depends on WHICH part of
     the episodes the slice covers) and `episode_return` (mean return of the episodes that were COMPLETED during the iteration, None if none was).

@@ -242,6 +242,26 @@ int cda_policy_step_range(cda_env* env, int32_t first_market, int32_t n_markets,
                           float* a_cont, float* logp, float* value, float* rec, float* dist,
                           float* obs_out, double* reward_out, uint8_t* terminated_out, uint8_t* truncated_out,
                           float* fin_obs, int32_t fin_cap, int32_t* fin_count, int32_t* fin_index_out, void* stream);
+/* The same ONE launch for every other network of include/cda_mlp.h: activation = the hidden activation's code (0 tanh, 1 relu, 2 elu, 3 linear: CDA_MLP_ACT of the
+ * network objects), vf_share_layers = 1 for the shared trunk (the _vfs objects; wb / theta are that network's images).  cda_policy_step_range is the tanh network with
+ * its own value network, fixed at compile time (k_policy_step); these entry points launch k_net_step, one kernel per history depth that reads the two choices from
+ * its arguments - the activation in the two hidden layers' epilogues, the trunk by idling the value half's waves - and is otherwise the same code: bit for bit the
+ * actions, log-probabilities, values, records and step outputs of that network's cda_mlp_policy_step followed by cda_step_range_capture.  (0, 0) forwards to
+ * cda_policy_step_range.  An activation outside 0 .. 3 or vf_share_layers outside 0 / 1: CDA_ERR_INVALID from all three, before anything is launched.
+ * cda_net_step_supported: cda_policy_step_supported's conditions on the env - they do not depend on the network; cda_net_step_advised: cda_policy_step_advised's
+ * rule, N <= 16 x CUs, for every network (profiles/net_step/cost.txt).  cda_net_step_range's arguments behind the two codes are cda_policy_step_range's. */
+int cda_net_step_supported(const cda_env* env, int32_t activation, int32_t vf_share_layers);
+int cda_net_step_advised(const cda_env* env, int32_t activation, int32_t vf_share_layers);
+int cda_net_step_range(cda_env* env, int32_t activation, int32_t vf_share_layers,
+                       int32_t first_market, int32_t n_markets, const void* wb, const float* theta, const float* obs_in,
+                       uint64_t seed, const int64_t* counter_dev, int64_t draw,
+                       int32_t* category, float* size_mean, float* size_sigma, int32_t* price, int32_t* price_offset,
+                       float* a_cont, float* logp, float* value, float* rec, float* dist,
+                       float* obs_out, double* reward_out, uint8_t* terminated_out, uint8_t* truncated_out,
+                       float* fin_obs, int32_t fin_cap, int32_t* fin_count, int32_t* fin_index_out, void* stream);
+/* One-launch steps (cda_policy_step_range / cda_net_step_range launches) enqueued on this env since cda_create: a host-side counter - an enqueue inside a stream
+ * capture counts once, replays of the captured graph do not.  Tells a caller (and a test) which path a rollout chain took.  NULL env: 0. */
+int64_t cda_policy_step_launch_count(const cda_env* env);
 /* cda_step as n_groups (<= CDA_MAX_GROUPS) launches, group g = the markets cda_group_range() names, on streams[g].
  * One host call; each group is an independent chain of launches on its own stream, so one group's slowest market
  * overlaps the other groups' work instead of stalling the whole batch.  The outputs of group g are complete when
