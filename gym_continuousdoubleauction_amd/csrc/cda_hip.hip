@@ -1668,5 +1668,7 @@ int64_t cda_state_bytes_per_market(const cda_env* e) { return e ? (int64_t)e->P.
 #include "cda_schedule.inc"
 // the quote tape (cda_quotes_*, cda_quote_*, cda_tape_spreads): the top of the book per step, recorded ahead of every step, and the reductions over it
 #include "cda_quotes.inc"
+// the stylised-facts report (cda_quote_returns, cda_tape_signs, cda_tape_flow_returns): return and order-flow statistics of a remembered episode
+#include "cda_stylised.inc"
 // the label tap (cda_label_*): a law's answer for slots it does not play, beside a rollout's buffers - one walk of the book serves the attached table and the label table
 #include "cda_scripted_label.inc"

@@ -13,6 +13,7 @@ the greedy chains); mode="sample" runs the same loop on the sampling kernels.
 CLI: python -m gym_continuousdoubleauction_amd.evaluate --policy P [--opponent random|FILE ...] --markets --agents --max-step --episodes --trained-slots
      (a scripted opponent: pass | maker | taker | imbalance | NAME:key=value,...)
      [--sample] --seed --out JSON [--tape FILE.npz [--exec-report K[,K...]] [--spread-report K[,K...]]] [--quotes FILE.npz]
+     [--stylised-facts L[,L...] [--bar-steps K]]
 """
 import argparse
 import dataclasses
@@ -137,8 +138,47 @@ def _spread_report(env, horizons, module_of, names, episode0, keep):
     return out
 
 
+STYLISED_HIST_HALF = 16                                              # the return histogram of evaluate(stylised_facts=...): -16 .. 16 ticks, the ends clipped
+VARIANCE_RATIO_BARS = 5                                              # ... and, at one-step bars, the longer bar its variance ratio compares against
+
+
+def _stylised_report(env, lags, bar_steps, episode0, keep):
+    """evaluate(stylised_facts=...): the three stylised-facts reductions (CDAVecEnv.quote_returns / tape_signs / tape_flow_returns) of every market's previous
+    episode, pooled over the markets that count (as in _execution_report) and read through stylised.summary.  The joined table takes lag 0 and the first seven
+    lags; where bar_steps is 1 the variance ratio compares against bars of VARIANCE_RATIO_BARS steps, else bars of one step against bars of bar_steps."""
+    from . import stylised as SF
+    flow_lags = [0] + list(lags)[:SF.MAX_LAGS - 1]
+    top = int(env.market_rows()["max_step"].max()) if env.per_market else int(env.max_step)
+    ret = env.quote_returns(lags, bar_steps, hist_half=STYLISED_HIST_HALF, episode="previous")
+    other = VARIANCE_RATIO_BARS if int(bar_steps) == 1 else 1
+    ret_other = env.quote_returns(lags, other, hist_half=STYLISED_HIST_HALF, episode="previous") if SF.n_points(top, other) <= SF.MAX_BARS else None
+    sig = env.tape_signs(lags, episode="previous")
+    flo = env.tape_flow_returns(flow_lags, bar_steps, episode="previous")
+    counted = env.tape_counts()["episode"].to(torch.int64) > torch.from_numpy(np.asarray(episode0)).to(env.device, torch.int64)
+
+    def pooled(t):                                                   # the sum over the markets that count, on the device; a few hundred words come to the host
+        return SF.pool(t[counted]).cpu().numpy()
+    r1, rk = (ret, ret_other) if int(bar_steps) == 1 else (ret_other, ret)
+    block = SF.summary(returns=[pooled(t) for t in ret[:3]], signs=[pooled(t) for t in sig[:2]], flows=[pooled(t) for t in flo[:2]], lags=lags, flow_lags=flow_lags,
+                       bar_steps=bar_steps)
+    if ret_other is not None:
+        k = max(int(bar_steps), other)
+        block["returns"]["variance_ratio"] = {"k": k, "value": SF.variance_ratio(pooled(r1[0]), pooled(rk[0]), k)}
+    sel = counted.cpu().numpy()
+    qi, ti, fi = ret[3].cpu().numpy(), sig[2].cpu().numpy(), flo[2].cpu().numpy()
+    block["about"] = {"lags": list(lags), "flow_lags": flow_lags, "bar_steps": int(bar_steps), "hist_half": STYLISED_HIST_HALF, "episode": "previous",
+                      "markets": int(sel.sum()), "quotes": int(qi[sel, 0].sum()), "quotes_lost": int(qi[sel, 1].sum()), "tape_records": int(ti[sel, 0].sum()),
+                      "tape_records_lost": int(ti[sel, 1].sum()), "partial_markets": int((fi[sel, 3] != 0).sum())}
+    block["rows"] = {"returns": pooled(ret[0]).tolist(), "returns_lagged": pooled(ret[1]).tolist(), "returns_hist": pooled(ret[2]).tolist(),
+                     "signs": pooled(sig[0]).tolist(), "signs_lagged": pooled(sig[1]).tolist(), "flows_lagged": pooled(flo[0]).tolist(), "flows": pooled(flo[1]).tolist()}
+    if keep is not None:
+        keep["stylised_tables"] = {"returns": [t.cpu().numpy() for t in ret], "signs": [t.cpu().numpy() for t in sig], "flows": [t.cpu().numpy() for t in flo],
+                                   "counted": sel, "flow_lags": flow_lags}
+    return block
+
+
 def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="greedy", seed=0, groups=None, keep=None, tape=None, tape_capacity=4096,
-             exec_horizons=None, quotes=None, spread_horizons=None):
+             exec_horizons=None, quotes=None, spread_horizons=None, stylised_facts=None, bar_steps=1):
     """Play `policy` (a FusedPolicy or a policy file) on `env` (a CDAVecEnv with auto_reset) for episodes * max_step steps; return per-module results.
     opponents: None = self-play; else a list of "random", FusedPolicy objects, policy files or scripted opponents - "pass", "maker", "taker", "imbalance",
     "NAME:key=value,..." or a scripted.Profile (rule-based agents on the device: their slots carry LEAGUE_RANDOM in slot_net and their profile in the env's slot_script,
@@ -163,7 +203,12 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
     slot -> module map `modules` and `module_names`.  The env's quote tape must be OFF (ValueError otherwise); it is off again afterwards.
     spread_horizons (step counts, optional; needs `tape`; the quotes are recorded whether or not `quotes` names a file): add a "spreads" block to every module -
     effective and realised half-spread and impact per share, by role (CDAVecEnv.tape_spreads, folded by quotes.spreads_by_module, read through
-    quotes.spread_summary, the integer rows beside the ratios) - and result["spreads"], which says what it covers, as the execution report does."""
+    quotes.spread_summary, the integer rows beside the ratios) - and result["spreads"], which says what it covers, as the execution report does.
+    stylised_facts (lags, optional; bar_steps: the bar size, in env steps): switch BOTH tapes on for the evaluated episodes - with or without a `tape` / `quotes`
+    file - and add result["stylised_facts"]: the return, order-flow-sign and flow-return statistics of every market's last finished episode (CDAVecEnv.quote_returns,
+    tape_signs, tape_flow_returns on the device), pooled over the markets (stylised.pool) and read through stylised.summary - autocorrelations of returns and of
+    their magnitudes, the leverage correlation, variance ratio, excess kurtosis, sign autocorrelation, Kyle's lambda and R^2 per lag - with the pooled integer rows
+    beside the figures and what they cover ("about"), records lost to a ring reported, not hidden."""
     from .mlp import LEAGUE_RANDOM, FusedPolicy, PolicyBank, RolloutChains, read_policy
     if mode not in ("greedy", "sample"):
         raise ValueError(f"mode must be 'greedy' or 'sample' (got {mode!r})")
@@ -179,9 +224,16 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
         spread_horizons = _spread_hz(spread_horizons)
         if tape is None:
             raise ValueError("evaluate(spread_horizons=...) joins the trade tape of the evaluated episodes to their quotes: pass tape=FILE.npz as well")
-    with_quotes = quotes is not None or spread_horizons is not None
+    if stylised_facts is not None:
+        from .stylised import MAX_BARS, _bar_steps, _lags, n_points
+        stylised_facts, bar_steps = _lags(stylised_facts, 1), _bar_steps(bar_steps)
+        top = int(env.market_rows()["max_step"].max()) if env.per_market else int(env.max_step)
+        if n_points(top, bar_steps) > MAX_BARS:
+            raise ValueError(f"evaluate(stylised_facts=...): an episode of {top} steps has more than {MAX_BARS} bars of {bar_steps} steps: raise bar_steps")
+    with_tape = tape is not None or stylised_facts is not None
+    with_quotes = quotes is not None or spread_horizons is not None or stylised_facts is not None
     if with_quotes and env.quotes_enabled:
-        raise ValueError("evaluate(quotes=... / spread_horizons=...) needs an env whose quote tape is off: it enables one of its own for the evaluated episodes "
+        raise ValueError("evaluate(quotes=... / spread_horizons=... / stylised_facts=...) needs an env whose quote tape is off: it enables one of its own for the evaluated episodes "
                          "(disable_quotes() first)")
     dev, N, A = env.device, env.n_markets, env.num_agents
     pol = _as_policy(policy, dev)
@@ -216,10 +268,10 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
     prev_metrics = bool(getattr(env, "episode_metrics_on", False))       # the caller's setting, tolerance included: put back as it was afterwards
     prev_tolerance = float(getattr(env, "episode_metrics_tolerance", 1e-6))
     env.enable_episode_metrics(True)                                    # before the chains are captured
-    if tape is not None and env.tape_enabled:
-        raise ValueError("evaluate(tape=...) needs an env whose trade tape is off: it enables a tape of its own for the evaluated episodes (disable_tape() first, or "
+    if with_tape and env.tape_enabled:
+        raise ValueError("evaluate(tape=... / stylised_facts=...) needs an env whose trade tape is off: it enables a tape of its own for the evaluated episodes (disable_tape() first, or "
                          "drain the running tape yourself with drain_tape(cursor=...))")
-    if tape is not None:
+    if with_tape:
         env.enable_tape(tape_capacity)                                  # (likewise: the chains' graphs hold the tape-writing step instances)
     if with_quotes:
         env.enable_quotes(min(1 << 20, 2 * max(1, int(env.max_step))))  # (likewise: the recorder's launch; the finished episode and the running one both fit)
@@ -259,8 +311,8 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
         torch.cuda.synchronize(dev)
         t0 = time.perf_counter()
         for c in range(total // T):
-            before = {k: v.cpu().numpy() for k, v in env.tape_counts().items()} if tape is not None else None
-            if tape is not None and c == 0:
+            before = {k: v.cpu().numpy() for k, v in env.tape_counts().items()} if with_tape else None
+            if with_tape and c == 0:
                 tape_ep0 = before["episode"].copy()                      # the first evaluated episode of every market
             buf = chains.run()
             if tape is not None:
@@ -283,6 +335,9 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
         spread_rep = None
         if spread_horizons is not None:
             spread_rep = _spread_report(env, spread_horizons, module_of, names, tape_ep0, keep)
+        stylised_rep = None
+        if stylised_facts is not None:
+            stylised_rep = _stylised_report(env, stylised_facts, bar_steps, tape_ep0, keep)
         if quotes is not None:
             from .quotes import save as save_quotes
             rec, cnt, qinfo = env.quote_series(int(env.max_step), episode="previous")
@@ -296,7 +351,7 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
                       module_names=np.array(names), modules=modules.astype(np.int32))
     finally:
         env.enable_episode_metrics(prev_metrics, nav_tolerance=prev_tolerance)
-        if tape is not None:
+        if with_tape:
             env.disable_tape()
         if with_quotes and env.quotes_enabled:
             env.disable_quotes()
@@ -328,6 +383,8 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
         result["spreads"] = spread_rep["about"]
         for name in names:
             mods[name]["spreads"] = spread_rep["modules"][name]
+    if stylised_rep is not None:
+        result["stylised_facts"] = stylised_rep
     if keep is not None:
         keep["chains"], keep["modules"], keep["tables"] = chains, modules, (table_h, env_h)
         keep["actions"] = {key: torch.cat([a[key] for a in acts]) for key in acts[0]}
@@ -352,6 +409,10 @@ def main(argv=None):
     p.add_argument("--quotes", default=None, metavar="FILE.npz", help="record the top of the book ahead of every step (the quote tape) and save every market's last finished episode")
     p.add_argument("--spread-report", default=None, metavar="K[,K...]", help="with --tape: add per-module effective spread, realised spread and impact per share at these step "
                    "horizons, by role - the trade tape joined to the quotes on the device")
+    p.add_argument("--stylised-facts", default=None, metavar="L[,L...]", help="add the stylised-facts block - return autocorrelations, volatility clustering, tails, order-flow "
+                   "sign persistence, price impact of signed volume - at these lags, reduced on the device from every market's last finished episode (switches the trade "
+                   "tape and the quote tape on)")
+    p.add_argument("--bar-steps", type=int, default=1, metavar="K", help="with --stylised-facts: the bar size in env steps (default 1)")
     p.add_argument("--order-schedule", default=None, metavar="FILE.npz", help="attach this order schedule (orders.save_schedule) to the env: per-step order flow played ahead "
                    "of every step of the evaluated episodes")
     args = p.parse_args(argv)
@@ -371,6 +432,12 @@ def main(argv=None):
             spread_horizons = [int(k) for k in args.spread_report.split(",")]
         except ValueError:
             p.error(f"--spread-report takes step counts separated by commas, got {args.spread_report!r}")
+    stylised_facts = None
+    if args.stylised_facts is not None:
+        try:
+            stylised_facts = [int(k) for k in args.stylised_facts.split(",")]
+        except ValueError:
+            p.error(f"--stylised-facts takes lags separated by commas, got {args.stylised_facts!r}")
     from .mlp import layout_of_params, read_policy
     from .vec_env import CDAVecEnv
     n_hist = layout_of_params(read_policy(args.policy).numel()).hist             # (the hidden activation comes with the file: load_policy)
@@ -381,7 +448,7 @@ def main(argv=None):
             env.load_order_schedule(args.order_schedule)
         res = evaluate(env, args.policy, opponents=args.opponent, trained_slots=args.trained_slots, episodes=args.episodes,
                        mode="sample" if args.sample else "greedy", seed=args.seed, tape=args.tape, exec_horizons=exec_horizons,
-                       quotes=args.quotes, spread_horizons=spread_horizons)
+                       quotes=args.quotes, spread_horizons=spread_horizons, stylised_facts=stylised_facts, bar_steps=args.bar_steps)
     finally:
         env.close()
     res.pop("summary")

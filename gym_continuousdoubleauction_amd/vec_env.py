@@ -813,6 +813,82 @@ class CDAVecEnv:
                   "cda_tape_spreads")
         return out, info
 
+    # ------------------------------------------------------------------ the stylised-facts report: return and order-flow statistics of an episode (stylised.py)
+    def _stylised_points(self, what, first, n, bar_steps):
+        """bar_steps, checked: the bar points of the longest episode of the range must fit a wave's LDS (include/cda.h CDA_STYL_MAX_BARS)"""
+        from .stylised import MAX_BARS, _bar_steps, n_points
+        bar = _bar_steps(bar_steps)
+        top = int(self.market_rows(first, n)["max_step"].max()) if self.per_market else int(self.max_step)
+        if n_points(top, bar) > MAX_BARS:
+            raise ValueError(f"{what}: an episode of {top} steps has {n_points(top, bar)} bar points at bar_steps = {bar}, more than {MAX_BARS}: raise bar_steps")
+        return bar
+
+    def quote_returns(self, lags=(1, 2, 5, 10), bar_steps=1, hist_half=16, episode="current", first_market=0, n_markets=None):
+        """The return statistics of one remembered episode's held quotes, reduced on the device in one launch (include/cda.h cda_quote_returns;
+        stylised.returns_from_quotes is its specification, word for word).  Needs the quote tape.  -> (base i64 [n, 8] - stylised.RETURN_FIELDS: bar points held,
+        defined returns, missing ones, sum_r, sum_abs, sum_r2, up, down -, lagged i64 [n, L, 4] - RETURN_LAG_FIELDS per lag: n, rr, aa, ra -, hist i64
+        [n, 2 hist_half + 1] - returns in ticks of the market's own row, the end bins hold the clipped mass -, info i32 [n, 4] as quote_stats), device tensors.
+        The return at bar point p is m2((p + 1) bar_steps) - m2(p bar_steps), in half price units.  lags: 1 .. 8 values >= 1, in bars; every word is additive:
+        stylised.pool sums over markets, stylised.summary turns pooled tables into autocorrelations, variance ratio, kurtosis."""
+        from .stylised import MAX_HIST_HALF, RETURN_FIELDS, RETURN_LAG_FIELDS, _lags
+        self._need_quotes("quote_returns()")
+        first, n = self._market_range("quote_returns", first_market, n_markets)
+        which = self._tape_which(episode)
+        lg = _lags(lags, 1)
+        if not 1 <= int(hist_half) <= MAX_HIST_HALF:
+            raise ValueError(f"quote_returns: hist_half must be in 1 .. {MAX_HIST_HALF}, got {hist_half}")
+        bar = self._stylised_points("quote_returns", first, n, bar_steps)
+        self.join()
+        with torch.cuda.device(self.device):
+            base = torch.empty((n, len(RETURN_FIELDS)), dtype=torch.int64, device=self.device)
+            lagged = torch.empty((n, len(lg), len(RETURN_LAG_FIELDS)), dtype=torch.int64, device=self.device)
+            hist = torch.empty((n, 2 * int(hist_half) + 1), dtype=torch.int64, device=self.device)
+            info = torch.empty((n, 4), dtype=torch.int32, device=self.device)
+            check(lib().cda_quote_returns(self._h, first, n, which, (C.c_int32 * len(lg))(*lg), len(lg), bar, int(hist_half), base.data_ptr(), lagged.data_ptr(),
+                                          hist.data_ptr(), info.data_ptr(), self._stream()), "cda_quote_returns")
+        return base, lagged, hist, info
+
+    def tape_signs(self, lags=(1, 2, 5, 10), episode="current", first_market=0, n_markets=None):
+        """The order-flow sign statistics of one remembered episode's held fills, in tape order, reduced on the device in one launch (include/cda.h cda_tape_signs;
+        stylised.signs_from_records is its specification, word for word).  Needs the trade tape.  -> (base i64 [n, 8] - stylised.SIGN_FIELDS: fills, buys, sells,
+        buy_qty, sell_qty, self_fills, runs, steps_with_fills -, lagged i64 [n, L, 4] - SIGN_LAG_FIELDS per lag, in TRADE time: n, ss, qq, same_step -, info i32
+        [n, 4] as tape_flows), device tensors.  lags: 1 .. 8 values >= 1, in fills."""
+        from .stylised import SIGN_FIELDS, SIGN_LAG_FIELDS, _lags
+        self._need_tape("tape_signs()")
+        first, n = self._market_range("tape_signs", first_market, n_markets)
+        which = self._tape_which(episode)
+        lg = _lags(lags, 1)
+        self.join()
+        with torch.cuda.device(self.device):
+            base = torch.empty((n, len(SIGN_FIELDS)), dtype=torch.int64, device=self.device)
+            lagged = torch.empty((n, len(lg), len(SIGN_LAG_FIELDS)), dtype=torch.int64, device=self.device)
+            info = torch.empty((n, 4), dtype=torch.int32, device=self.device)
+            check(lib().cda_tape_signs(self._h, first, n, which, (C.c_int32 * len(lg))(*lg), len(lg), base.data_ptr(), lagged.data_ptr(), info.data_ptr(),
+                                       self._stream()), "cda_tape_signs")
+        return base, lagged, info
+
+    def tape_flow_returns(self, lags=(0, 1, 5), bar_steps=1, episode="current", first_market=0, n_markets=None):
+        """Signed volume joined to returns, bar by bar, of one remembered episode, reduced on the device in one launch (include/cda.h cda_tape_flow_returns;
+        stylised.flow_returns_from_records is its specification, word for word).  Needs the trade tape AND the quote tape.  -> (lagged i64 [n, L, 6] -
+        stylised.FLOW_LAG_FIELDS per lag l >= 0 over the kept bars b whose return r_(b + l) is defined: n, q = sum Q_b, r, qr, qq, rr; lag 0 is the impact
+        regression -, base i64 [n, 4] - FLOW_FIELDS: fills and quantity of the kept bars, the kept bars with fills, bars_excluded (the bars up to the first held
+        fill's where the tape ring has lost the episode's head) -, info i32 [n, 4] as tape_spreads), device tensors.  lags: 1 .. 8 values >= 0, in bars."""
+        from .stylised import FLOW_FIELDS, FLOW_LAG_FIELDS, _lags
+        self._need_tape("tape_flow_returns()")
+        self._need_quotes("tape_flow_returns()")
+        first, n = self._market_range("tape_flow_returns", first_market, n_markets)
+        which = self._tape_which(episode)
+        lg = _lags(lags, 0)
+        bar = self._stylised_points("tape_flow_returns", first, n, bar_steps)
+        self.join()
+        with torch.cuda.device(self.device):
+            lagged = torch.empty((n, len(lg), len(FLOW_LAG_FIELDS)), dtype=torch.int64, device=self.device)
+            base = torch.empty((n, len(FLOW_FIELDS)), dtype=torch.int64, device=self.device)
+            info = torch.empty((n, 4), dtype=torch.int32, device=self.device)
+            check(lib().cda_tape_flow_returns(self._h, first, n, which, (C.c_int32 * len(lg))(*lg), len(lg), bar, lagged.data_ptr(), base.data_ptr(), info.data_ptr(),
+                                              self._stream()), "cda_tape_flow_returns")
+        return lagged, base, info
+
     def quote_episode(self, market=0, episode="current"):
         """One market's held quotes of an episode, oldest first, as a structured host array (quotes.QUOTE_DTYPE)."""
         from .quotes import as_quotes

@@ -732,6 +732,63 @@ int cda_quote_stats(cda_env* env, int32_t first_market, int32_t n_markets, int32
 int cda_tape_spreads(cda_env* env, int32_t first_market, int32_t n_markets, int32_t which, const int32_t* horizons_host, int32_t n_horizons,
                      int64_t* spreads_out_dev, int32_t* info_out_dev, void* stream);
 
+/* ---- the stylised-facts report: return and order-flow statistics of one remembered episode, on the device -----------------------------
+ * The time-series structure of the market the agents produce - what an agent-based market is validated against: are mid-price returns
+ * uncorrelated while their magnitudes cluster, how fat are the return tails, how persistent is the sign of order flow, how much does signed
+ * volume move the price.  Three reductions, each over the episode `which` names (CDA_TAPE_CURRENT / CDA_TAPE_PREVIOUS) of the markets
+ * [first_market, first_market + n_markets), one launch on `stream`, a wave per market, no atomics on global memory; stylised.py states every
+ * word in numpy.  EVERY output word is an additive int64 sum (two's-complement wrap, as cda_quote_stats' dm2_sq): a fold over markets, episodes
+ * or ranks is a plain sum; there are no min / max words.  The sums are exact while bid + ask < 2^31, a bar's signed volume |Q_b| < 2^31 (it is
+ * kept as an int32 word) and no sum leaves int64: a market has at most CDA_STYL_MAX_BARS = 2^12 bars, so |r| < 2^25 and |Q_b| < 2^25 always
+ * suffice (2^12 products below 2^50), and a tape holds at most 2^20 fills, so quantities below 2^21 always suffice for cda_tape_signs' qq.
+ * Definitions.  m2(s) = bid_price + ask_price of the quote record of episode step s, defined iff the record is held and two-sided.  The bar points
+ * are the steps s with s % bar_steps == 0 on the episode's absolute step grid (a lost head does not shift it); point p is step p x bar_steps.  The
+ * return at point p is r_p = m2((p + 1) bar_steps) - m2(p bar_steps), defined iff both are (half price units, as dm2).  The sign of a fill is +1
+ * where the initiator bought (its side bit is 0), -1 where it sold; self-trades are fills like any other and are counted separately.
+ * lags_host: n_lags int32 (host memory, read during the call), 1 <= n_lags <= CDA_STYL_MAX_LAGS, each lag in 1 .. CDA_STYL_MAX_LAG (0 allowed
+ * for cda_tape_flow_returns); a lag that runs past the end of the episode yields zeros.  The bar points of the longest episode of the range,
+ * ceil(largest max_step of its rows / bar_steps), must be at most CDA_STYL_MAX_BARS (a wave keeps a whole episode's points in LDS): checked on
+ * the host, before the launch.
+ *   cda_quote_returns      needs the quote tape.  base_out_dev i64 [n][8]: bars (the points held), returns (the returns that are defined), missing
+ *                          (adjacent held point pairs with an endpoint that is not two-sided), sum_r, sum_abs, sum_r2, up, down (returns > 0, < 0).
+ *                          lagged_out_dev i64 [n][n_lags][4], per lag l over the points where r_p and r_(p + l) are both defined: n, rr = sum r r',
+ *                          aa = sum |r| |r'| (volatility clustering), ra = sum r |r'| (the leverage term).  hist_out_dev i64 [n][2 hist_half + 1]:
+ *                          bin clamp(r / tick, -hist_half, hist_half) + hist_half, tick = the tick_size of the market's own row (prices are multiples
+ *                          of it: the division is exact); the end bins hold the clipped mass.  1 <= hist_half <= CDA_STYL_MAX_HIST_HALF.
+ *                          info_out_dev i32 [n][4] (may be NULL) as cda_quote_stats fills it.  At bar_steps 1: returns == cda_quote_stats' pairs,
+ *                          sum_r2 == dm2_sq, sum_abs == abs_dm2.
+ *   cda_tape_signs         needs the trade tape; over the held fills in tape order.  base_out_dev i64 [n][8]: fills, buys, sells, buy_qty, sell_qty,
+ *                          self_fills, runs (maximal runs of equal sign), steps_with_fills.  lagged_out_dev i64 [n][n_lags][4], lags in TRADE time,
+ *                          over the fills i and i + l: n, ss = sum s s', qq = sum (s q)(s' q'), same_step (pairs whose two fills carry the same env
+ *                          step: one sweep prints many same-sign fills in one step).  info_out_dev as cda_tape_flows fills it.
+ *   cda_tape_flow_returns  needs both.  Bar b covers the steps [b bar_steps, (b + 1) bar_steps); Q_b = sum of sign x quantity over its held fills (a
+ *                          bar without fills has Q_b = 0 and counts).  Where the tape ring has lost the episode's head every bar up to and including
+ *                          the bar of the first held fill is excluded (no fill held at all: every bar) and counted in bars_excluded.
+ *                          lagged_out_dev i64 [n][n_lags][6], per lag l >= 0 over the kept bars b whose r_(b + l) is defined: n, q = sum Q_b, r = sum
+ *                          r_(b + l), qr, qq, rr - lag 0: the contemporaneous impact regression (Kyle's lambda = cov / var, and its R^2); lags >= 1:
+ *                          does flow predict returns.  base_out_dev i64 [n][4]: the kept bars' fills, the kept bars that have fills, bars_excluded,
+ *                          the kept bars' quantity.  info_out_dev i32 [n][4] (may be NULL) as cda_tape_spreads fills it.
+ *   cda_stylised_check_host  the argument check the three make, on the host alone (no env, no device): kind = CDA_STYL_RETURNS / CDA_STYL_SIGNS /
+ *                          CDA_STYL_FLOW_RETURNS, max_step = the largest max_step of the range; CDA_OK or CDA_ERR_INVALID.  bar_steps, hist_half and
+ *                          max_step are read only by the kinds that take them.
+ * A NULL or misaligned output (8 B; info 4 B), a range outside the env, another `which`, n_lags outside 1 .. CDA_STYL_MAX_LAGS, a lag outside its
+ * bounds, bar_steps < 1, hist_half outside 1 .. CDA_STYL_MAX_HIST_HALF or too many bar points: CDA_ERR_INVALID, nothing is launched.
+ * CDA_ERR_UNSUPPORTED while a service the reduction needs is off. */
+#define CDA_STYL_MAX_BARS      4096
+#define CDA_STYL_MAX_LAGS      8
+#define CDA_STYL_MAX_LAG       (1 << 20)
+#define CDA_STYL_MAX_HIST_HALF 64
+#define CDA_STYL_RETURNS       0
+#define CDA_STYL_SIGNS         1
+#define CDA_STYL_FLOW_RETURNS  2
+int cda_quote_returns(cda_env* env, int32_t first_market, int32_t n_markets, int32_t which, const int32_t* lags_host, int32_t n_lags, int32_t bar_steps,
+                      int32_t hist_half, int64_t* base_out_dev, int64_t* lagged_out_dev, int64_t* hist_out_dev, int32_t* info_out_dev, void* stream);
+int cda_tape_signs(cda_env* env, int32_t first_market, int32_t n_markets, int32_t which, const int32_t* lags_host, int32_t n_lags, int64_t* base_out_dev,
+                   int64_t* lagged_out_dev, int32_t* info_out_dev, void* stream);
+int cda_tape_flow_returns(cda_env* env, int32_t first_market, int32_t n_markets, int32_t which, const int32_t* lags_host, int32_t n_lags, int32_t bar_steps,
+                          int64_t* lagged_out_dev, int64_t* base_out_dev, int32_t* info_out_dev, void* stream);
+int cda_stylised_check_host(int32_t kind, const int32_t* lags_host, int32_t n_lags, int32_t bar_steps, int32_t hist_half, int32_t max_step);
+
 /* ---- the book report: reductions over the STANDING book, on the device ------------------------------------------------------------------
  * The resting orders of markets [first_market, first_market + n_markets), read where they lie - the record's tile and, behind it, the HBM spill
  * ring - by one wave per (market, side), one launch each, on `stream`; no call synchronises the host and none writes the arena.  A side is walked
