@@ -159,7 +159,8 @@ TAPE_MAX_HORIZONS = 8            # CDA_TAPE_MAX_HORIZONS
 TAPE_EPISODES = {"current": 0, "previous": 1}      # CDA_TAPE_CURRENT, CDA_TAPE_PREVIOUS
 QUOTE_WORDS = 8                  # include/cda.h CDA_QUOTE_WORDS: int32 words of a cda_quote_record (quotes.QUOTE_DTYPE)
 QUOTE_STAT_WORDS = 16            # CDA_QUOTE_STAT_WORDS: int64 words of cda_quote_stats (quotes.STAT_FIELDS)
-SNAP_MAGIC = 0x53414443          # "CDAS"
+PNL_WORDS = 16                   # CDA_PNL_WORDS: int64 words per agent of cda_tape_pnl's stats (pnl.PNL_FIELDS)
+SNAP_MAGIC = 0x53414443         # "CDAS"
 SNAP_VERSION = 1
 
 

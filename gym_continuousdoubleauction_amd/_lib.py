@@ -35,6 +35,7 @@ SYMBOLS = [
     "cda_schedule_attach", "cda_schedule_detach", "cda_schedule_attached", "cda_schedule_epoch", "cda_schedule_counts", "cda_schedule_play", "cda_schedule_check_host",
     "cda_quotes_enable", "cda_quotes_disable", "cda_quotes_capacity", "cda_quote_meta", "cda_quote_series", "cda_quote_stats", "cda_tape_spreads",
     "cda_quote_returns", "cda_tape_signs", "cda_tape_flow_returns", "cda_stylised_check_host",
+    "cda_tape_pnl", "cda_tape_pnl_check_host",
 ]
 
 
@@ -256,6 +257,8 @@ def lib():
     L.cda_tape_signs.argtypes = [vp, i32, i32, i32, vp, i32, vp, vp, vp, vp]
     L.cda_tape_flow_returns.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp]
     L.cda_stylised_check_host.argtypes = [i32, vp, i32, i32, i32, i32]
+    L.cda_tape_pnl.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp]
+    L.cda_tape_pnl_check_host.argtypes = [i32, i32, i32, i32]
     L.cda_mlp_forward_backward.argtypes = [vp, vp, vp, vp, i64, i64, vp, vp, i64, i32, f32, f32, f32, C.POINTER(PpoExtra), vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]
     L.cda_mlp_rollout_chain.argtypes = [vp, vp, vp, i32, i32, i32, u64, vp, C.POINTER(RolloutBufs), i32, vp]
     L.cda_mlp_selftest_mfma.argtypes = [i32, vp, vp, vp]

@@ -1670,5 +1670,7 @@ int64_t cda_state_bytes_per_market(const cda_env* e) { return e ? (int64_t)e->P.
 #include "cda_quotes.inc"
 // the stylised-facts report (cda_quote_returns, cda_tape_signs, cda_tape_flow_returns): return and order-flow statistics of a remembered episode
 #include "cda_stylised.inc"
+// the P&L report (cda_tape_pnl): every agent's mark-to-mid equity curve of a remembered episode - drawdown, bar P&L moments, spread vs inventory
+#include "cda_tape_pnl.inc"
 // the label tap (cda_label_*): a law's answer for slots it does not play, beside a rollout's buffers - one walk of the book serves the attached table and the label table
 #include "cda_scripted_label.inc"

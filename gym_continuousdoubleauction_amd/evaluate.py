@@ -13,7 +13,7 @@ the greedy chains); mode="sample" runs the same loop on the sampling kernels.
 CLI: python -m gym_continuousdoubleauction_amd.evaluate --policy P [--opponent random|FILE ...] --markets --agents --max-step --episodes --trained-slots
      (a scripted opponent: pass | maker | taker | imbalance | NAME:key=value,...)
      [--sample] --seed --out JSON [--tape FILE.npz [--exec-report K[,K...]] [--spread-report K[,K...]]] [--quotes FILE.npz]
-     [--stylised-facts L[,L...] [--bar-steps K]]
+     [--stylised-facts L[,L...] [--bar-steps K]] [--pnl-report [--bar-steps K]]
 """
 import argparse
 import dataclasses
@@ -138,6 +138,28 @@ def _spread_report(env, horizons, module_of, names, episode0, keep):
     return out
 
 
+def _pnl_report(env, bar_steps, module_of, names, episode0, keep):
+    """evaluate(pnl_report=True): the P&L tables (CDAVecEnv.tape_pnl) of every market's previous episode, folded per module by pnl.pnl_by_module; a market counts
+    as in _execution_report."""
+    from .pnl import PNL_FIELDS, pnl_by_module, pnl_summary
+    stats, info = env.tape_pnl(bar_steps, episode="previous")
+    counted = env.tape_counts()["episode"].to(torch.int64) > torch.from_numpy(np.asarray(episode0)).to(env.device, torch.int64)
+    n_mod = len(names)
+    slot_module = torch.where(counted[:, None], module_of.to(torch.int64), torch.full_like(module_of, n_mod, dtype=torch.int64))      # row n_mod: not counted
+    st_h, info_h, sel = pnl_by_module(stats, slot_module, n_mod + 1).cpu().numpy(), info.cpu().numpy(), counted.cpu().numpy()
+    out = {"about": {"bar_steps": int(bar_steps), "episode": "previous", "markets": int(sel.sum()), "tape_records": int(info_h[sel, 0].sum()),
+                     "tape_records_lost": int(info_h[sel, 1].sum()), "quotes_lost": int(info_h[sel, 2].sum()), "partial_markets": int((info_h[sel, 3] != 0).sum()),
+                     "pnl_words": list(PNL_FIELDS)},
+           "modules": {}}
+    for i, name in enumerate(names):
+        block = pnl_summary(st_h[i], bar_steps=bar_steps)
+        block["row"] = [int(x) for x in st_h[i]]
+        out["modules"][name] = block
+    if keep is not None:
+        keep["pnl_tables"] = {"stats": stats.cpu().numpy(), "info": info_h, "counted": sel}
+    return out
+
+
 STYLISED_HIST_HALF = 16                                              # the return histogram of evaluate(stylised_facts=...): -16 .. 16 ticks, the ends clipped
 VARIANCE_RATIO_BARS = 5                                              # ... and, at one-step bars, the longer bar its variance ratio compares against
 
@@ -178,7 +200,7 @@ def _stylised_report(env, lags, bar_steps, episode0, keep):
 
 
 def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="greedy", seed=0, groups=None, keep=None, tape=None, tape_capacity=4096,
-             exec_horizons=None, quotes=None, spread_horizons=None, stylised_facts=None, bar_steps=1):
+             exec_horizons=None, quotes=None, spread_horizons=None, stylised_facts=None, bar_steps=1, pnl_report=False):
     """Play `policy` (a FusedPolicy or a policy file) on `env` (a CDAVecEnv with auto_reset) for episodes * max_step steps; return per-module results.
     opponents: None = self-play; else a list of "random", FusedPolicy objects, policy files or scripted opponents - "pass", "maker", "taker", "imbalance",
     "NAME:key=value,..." or a scripted.Profile (rule-based agents on the device: their slots carry LEAGUE_RANDOM in slot_net and their profile in the env's slot_script,
@@ -208,7 +230,11 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
     file - and add result["stylised_facts"]: the return, order-flow-sign and flow-return statistics of every market's last finished episode (CDAVecEnv.quote_returns,
     tape_signs, tape_flow_returns on the device), pooled over the markets (stylised.pool) and read through stylised.summary - autocorrelations of returns and of
     their magnitudes, the leverage correlation, variance ratio, excess kurtosis, sign autocorrelation, Kyle's lambda and R^2 per lag - with the pooled integer rows
-    beside the figures and what they cover ("about"), records lost to a ring reported, not hidden."""
+    beside the figures and what they cover ("about"), records lost to a ring reported, not hidden.
+    pnl_report (needs `tape`; the quotes are recorded whether or not `quotes` names a file; bar_steps: the bar size): add a "pnl" block to every module - what its
+    slots' mark-to-mid P&L did over every market's last finished episode: P&L and its split into inventory and trading, drawdown, bar P&L mean / std, Sharpe, hit
+    ratio, time under water (CDAVecEnv.tape_pnl on the device, folded by pnl.pnl_by_module, read through pnl.pnl_summary, the integer row beside the figures) -
+    and result["pnl"], which says what it covers, as the spread report does."""
     from .mlp import LEAGUE_RANDOM, FusedPolicy, PolicyBank, RolloutChains, read_policy
     if mode not in ("greedy", "sample"):
         raise ValueError(f"mode must be 'greedy' or 'sample' (got {mode!r})")
@@ -224,6 +250,14 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
         spread_horizons = _spread_hz(spread_horizons)
         if tape is None:
             raise ValueError("evaluate(spread_horizons=...) joins the trade tape of the evaluated episodes to their quotes: pass tape=FILE.npz as well")
+    if pnl_report:
+        from .stylised import MAX_BARS, _bar_steps, n_points
+        if tape is None:
+            raise ValueError("evaluate(pnl_report=True) joins the trade tape of the evaluated episodes to their quotes: pass tape=FILE.npz as well")
+        bar_steps = _bar_steps(bar_steps)
+        top = int(env.market_rows()["max_step"].max()) if env.per_market else int(env.max_step)
+        if n_points(top, bar_steps) > MAX_BARS:
+            raise ValueError(f"evaluate(pnl_report=True): an episode of {top} steps has more than {MAX_BARS} bars of {bar_steps} steps: raise bar_steps")
     if stylised_facts is not None:
         from .stylised import MAX_BARS, _bar_steps, _lags, n_points
         stylised_facts, bar_steps = _lags(stylised_facts, 1), _bar_steps(bar_steps)
@@ -231,7 +265,7 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
         if n_points(top, bar_steps) > MAX_BARS:
             raise ValueError(f"evaluate(stylised_facts=...): an episode of {top} steps has more than {MAX_BARS} bars of {bar_steps} steps: raise bar_steps")
     with_tape = tape is not None or stylised_facts is not None
-    with_quotes = quotes is not None or spread_horizons is not None or stylised_facts is not None
+    with_quotes = quotes is not None or spread_horizons is not None or stylised_facts is not None or bool(pnl_report)
     if with_quotes and env.quotes_enabled:
         raise ValueError("evaluate(quotes=... / spread_horizons=... / stylised_facts=...) needs an env whose quote tape is off: it enables one of its own for the evaluated episodes "
                          "(disable_quotes() first)")
@@ -338,6 +372,9 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
         stylised_rep = None
         if stylised_facts is not None:
             stylised_rep = _stylised_report(env, stylised_facts, bar_steps, tape_ep0, keep)
+        pnl_rep = None
+        if pnl_report:
+            pnl_rep = _pnl_report(env, bar_steps, module_of, names, tape_ep0, keep)
         if quotes is not None:
             from .quotes import save as save_quotes
             rec, cnt, qinfo = env.quote_series(int(env.max_step), episode="previous")
@@ -385,6 +422,10 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
             mods[name]["spreads"] = spread_rep["modules"][name]
     if stylised_rep is not None:
         result["stylised_facts"] = stylised_rep
+    if pnl_rep is not None:
+        result["pnl"] = pnl_rep["about"]
+        for name in names:
+            mods[name]["pnl"] = pnl_rep["modules"][name]
     if keep is not None:
         keep["chains"], keep["modules"], keep["tables"] = chains, modules, (table_h, env_h)
         keep["actions"] = {key: torch.cat([a[key] for a in acts]) for key in acts[0]}
@@ -412,7 +453,9 @@ def main(argv=None):
     p.add_argument("--stylised-facts", default=None, metavar="L[,L...]", help="add the stylised-facts block - return autocorrelations, volatility clustering, tails, order-flow "
                    "sign persistence, price impact of signed volume - at these lags, reduced on the device from every market's last finished episode (switches the trade "
                    "tape and the quote tape on)")
-    p.add_argument("--bar-steps", type=int, default=1, metavar="K", help="with --stylised-facts: the bar size in env steps (default 1)")
+    p.add_argument("--bar-steps", type=int, default=1, metavar="K", help="with --stylised-facts / --pnl-report: the bar size in env steps (default 1)")
+    p.add_argument("--pnl-report", action="store_true", help="with --tape: add per-module P&L, its inventory / trading split, drawdown, bar P&L moments, Sharpe and hit "
+                   "ratio - every agent's mark-to-mid equity curve, reduced on the device from every market's last finished episode (switches the quote tape on)")
     p.add_argument("--order-schedule", default=None, metavar="FILE.npz", help="attach this order schedule (orders.save_schedule) to the env: per-step order flow played ahead "
                    "of every step of the evaluated episodes")
     args = p.parse_args(argv)
@@ -432,6 +475,8 @@ def main(argv=None):
             spread_horizons = [int(k) for k in args.spread_report.split(",")]
         except ValueError:
             p.error(f"--spread-report takes step counts separated by commas, got {args.spread_report!r}")
+    if args.pnl_report and args.tape is None:
+        p.error("--pnl-report joins the trade tape to the quotes: give --tape FILE.npz as well")
     stylised_facts = None
     if args.stylised_facts is not None:
         try:
@@ -448,7 +493,7 @@ def main(argv=None):
             env.load_order_schedule(args.order_schedule)
         res = evaluate(env, args.policy, opponents=args.opponent, trained_slots=args.trained_slots, episodes=args.episodes,
                        mode="sample" if args.sample else "greedy", seed=args.seed, tape=args.tape, exec_horizons=exec_horizons,
-                       quotes=args.quotes, spread_horizons=spread_horizons, stylised_facts=stylised_facts, bar_steps=args.bar_steps)
+                       quotes=args.quotes, spread_horizons=spread_horizons, stylised_facts=stylised_facts, bar_steps=args.bar_steps, pnl_report=args.pnl_report)
     finally:
         env.close()
     res.pop("summary")

@@ -889,6 +889,37 @@ class CDAVecEnv:
                                               self._stream()), "cda_tape_flow_returns")
         return lagged, base, info
 
+    # ------------------------------------------------------------------ the P&L report: every agent's mark-to-mid equity curve of an episode (pnl.py)
+    def tape_pnl(self, bar_steps=1, episode="current", series=False, first_market=0, n_markets=None):
+        """What every agent's P&L did over one remembered episode: the trade tape joined to the quote tape on the bar points, reduced on the device in one launch
+        (include/cda.h cda_tape_pnl; pnl.pnl_from_records is its specification, word for word).  Needs the trade tape AND the quote tape.  -> (stats i64 [n, A, 16]
+        - pnl.PNL_FIELDS: marked / stale / unmarked points, bars, equity_first / _last, the inventory and trading parts of the P&L, sum_d2, up, down, under_water,
+        max_drawdown, equity_max / _min, open_fills; money in half price units -, info i32 [n, 4] as tape_spreads) or, with series=True, (stats, equity i64
+        [n, A, P], position i32 [n, A, P], marks i32 [n, P], info): E(p), pos(p) and the mark m(p) on the absolute grid of the P = ceil(largest max_step /
+        bar_steps) points, zeros where a point is not marked (position: not held).  Device tensors; every word is written by the kernel.  pnl.fold /
+        pnl.pnl_by_module fold rows, pnl.pnl_summary turns one into P&L, drawdown, Sharpe and hit ratio."""
+        from .pnl import PNL_WORDS, n_points
+        self._need_tape("tape_pnl()")
+        self._need_quotes("tape_pnl()")
+        first, n = self._market_range("tape_pnl", first_market, n_markets)
+        which = self._tape_which(episode)
+        bar = self._stylised_points("tape_pnl", first, n, bar_steps)
+        top = int(self.market_rows(first, n)["max_step"].max()) if self.per_market else int(self.max_step)
+        pts = n_points(top, bar)
+        self.join()
+        a = self.num_agents
+        with torch.cuda.device(self.device):
+            stats = torch.empty((n, a, PNL_WORDS), dtype=torch.int64, device=self.device)
+            info = torch.empty((n, 4), dtype=torch.int32, device=self.device)
+            equity = position = marks = None
+            if series:
+                equity = torch.empty((n, a, pts), dtype=torch.int64, device=self.device)
+                position = torch.empty((n, a, pts), dtype=torch.int32, device=self.device)
+                marks = torch.empty((n, pts), dtype=torch.int32, device=self.device)
+            check(lib().cda_tape_pnl(self._h, first, n, which, bar, stats.data_ptr(), equity.data_ptr() if series else None, position.data_ptr() if series else None,
+                                     marks.data_ptr() if series else None, pts, info.data_ptr(), self._stream()), "cda_tape_pnl")
+        return (stats, equity, position, marks, info) if series else (stats, info)
+
     def quote_episode(self, market=0, episode="current"):
         """One market's held quotes of an episode, oldest first, as a structured host array (quotes.QUOTE_DTYPE)."""
         from .quotes import as_quotes

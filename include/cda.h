@@ -789,6 +789,40 @@ int cda_tape_flow_returns(cda_env* env, int32_t first_market, int32_t n_markets,
                           int64_t* lagged_out_dev, int64_t* base_out_dev, int32_t* info_out_dev, void* stream);
 int cda_stylised_check_host(int32_t kind, const int32_t* lags_host, int32_t n_lags, int32_t bar_steps, int32_t hist_half, int32_t max_step);
 
+/* ---- the P&L report: every agent's mark-to-mid equity curve over one remembered episode, on the device -----------------------------------
+ * What did each agent's P&L do over the episode: the trade tape joined to the quote tape on the bar points, one launch on `stream`, a wave per
+ * market, no atomics on global memory; pnl.py states every word in numpy.  The conventions of the stylised-facts report hold: m2(s) = bid_price
+ * + ask_price of the held, two-sided quote record of step s; point p is step p x bar_steps on the episode's absolute grid and is HELD iff its
+ * quote record is.  The MARK m(p) is m2 of the latest held point p' <= p whose quote is two-sided - carried forward over points, not over the
+ * steps between them; a held point is MARKED if there is such a p' (the held points before the first two-sided one are unmarked) and STALE if it
+ * is marked and its own quote is not two-sided.  An agent's fills are the non-self fills (counter_id != init_id) it is a party of, signed sq =
+ * +quantity where it bought (its side bit is 0), -quantity where it sold; a fill of step s is INSIDE point p iff s < p x bar_steps (the quote of
+ * a step is taken ahead of the step's orders).  pos(p) = the sum of sq, C(p) = the sum of -sq x price over the held fills inside p, and the
+ * equity, in half price units, is E(p) = 2 C(p) + pos(p) m(p) at the marked points.  For adjacent marked points the increment d_p = E(p + 1) -
+ * E(p) = inv_p + trd_p exactly, inv_p = pos(p) (m(p + 1) - m(p)) the carried inventory times the mid's move, trd_p = the sum over the agent's
+ * fills of bar p of sq (m(p + 1) - 2 price).  Nothing is extrapolated: where the tape ring has lost the episode's head pos and C start from the
+ * first held fill, where the quote ring has, the points start at the first held quote; info says what was lost.  Fills at steps >= (the last
+ * marked point) x bar_steps - all fills, where no point is marked - are in no equity point: OPEN, counted, never marked.
+ *   stats_out_dev     i64 [n][A][CDA_PNL_WORDS]: points (marked), stale, unmarked, bars (increments), equity_first, equity_last, inventory (sum
+ *                     inv_p), trading (sum trd_p), sum_d2 (sum d_p^2), up, down (bars with d_p > 0 / < 0), under_water (marked points with E below
+ *                     its running maximum, which starts at equity_first), max_drawdown (max of running maximum - E, >= 0), equity_max, equity_min
+ *                     (over the marked points; 0 where there is none), open_fills.  Products are int64 and sums wrap in two's complement; a bar's
+ *                     signed quantity is kept as an int32 word, as cda_tape_flow_returns' Q_b.  All words are additive except max_drawdown and
+ *                     equity_max, which fold by max, and equity_min, which folds by min - over the rows with points > 0.
+ *   equity_out_dev    i64 [n][A][n_points] or NULL: E(p) on the absolute grid, 0 where p is not marked.
+ *   position_out_dev  i32 [n][A][n_points] or NULL: pos(p), 0 where p is not held.
+ *   marks_out_dev     i32 [n][n_points] or NULL: m(p), 0 where p is not marked.
+ *   info_out_dev      i32 [n][4] or NULL, as cda_tape_spreads fills it.
+ * Needs both tapes on, else CDA_ERR_UNSUPPORTED.  The bar points of the range's longest episode, ceil(largest max_step / bar_steps), must be <=
+ * CDA_STYL_MAX_BARS and, with any series output, <= n_points: checked on the host before the launch - cda_tape_pnl_check_host is that check alone
+ * (no env, no device; want_series != 0: a series output is asked for; max_step = the largest max_step of the range).  A NULL stats, a misaligned
+ * output (8 B; the int32 outputs 4 B), a range outside the env, another `which`, bar_steps < 1 or too many points: CDA_ERR_INVALID, nothing is
+ * launched.  Every word of every requested output is written exactly once - rows and columns of unheld points are zeros: no memset needed. */
+#define CDA_PNL_WORDS 16
+int cda_tape_pnl(cda_env* env, int32_t first_market, int32_t n_markets, int32_t which, int32_t bar_steps, int64_t* stats_out_dev, int64_t* equity_out_dev,
+                 int32_t* position_out_dev, int32_t* marks_out_dev, int32_t n_points, int32_t* info_out_dev, void* stream);
+int cda_tape_pnl_check_host(int32_t bar_steps, int32_t n_points, int32_t want_series, int32_t max_step);
+
 /* ---- the book report: reductions over the STANDING book, on the device ------------------------------------------------------------------
  * The resting orders of markets [first_market, first_market + n_markets), read where they lie - the record's tile and, behind it, the HBM spill
  * ring - by one wave per (market, side), one launch each, on `stream`; no call synchronises the host and none writes the arena.  A side is walked
