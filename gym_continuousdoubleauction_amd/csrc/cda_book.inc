@@ -607,6 +607,7 @@ __device__ __forceinline__ void settle_fill(Lds& L, int tr, int counter, int32_t
 // TAPE: the tape-writing instances (include/cda.h cda_tape_enable) append one record per fill to the market's ring, here, where price,
 // quantity, both parties, the resting order's id and what is left of it are at hand - self-trades included: the reference appends its
 // transaction_record before _process_trades looks at the parties (orderbook.py:108-140).  One lane, two 16-byte vector stores.
+// (The record's layout is stated once, for every reader, by the accessors beside TapeSpan in cda_tape.inc: tape_load, tape_price .. tape_step.)
 template <bool TAILS, bool LAZY_POSVAL, bool TAPE = false>
 __device__ __forceinline__ int32_t match(Lds& L, Mkt& m, int tr, int own_side, int32_t qty, int32_t limit, int lane) {
     int opp = own_side ^ 1;

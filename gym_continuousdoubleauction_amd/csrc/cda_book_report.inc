@@ -1,4 +1,5 @@
-// cda_book_report.inc - reductions over the STANDING book of a market range (include/cda.h cda_book_counts .. cda_book_pack), included at the end of cda_hip.hip.
+// cda_book_report.inc - reductions over the STANDING book of a market range (include/cda.h cda_book_counts .. cda_book_pack), included at the end of cda_hip.hip
+// (the wave toolkit - READER_WAVE, wave_scan_sum, lanes_le, lds_add - is cda_wave.hpp, included ahead of every .inc).
 //
 // All kernels are READERS of the arena: nothing here writes a market record or a spill ring, and nothing touches the step kernels.  One wave per (market,
 // side) - wave w of a launch serves side w & 1 of market first + (w >> 1), CDA_WPB waves per workgroup - walks the side in queue order (best price first, FIFO
@@ -36,19 +37,10 @@ __device__ __forceinline__ BookSide book_side(const uint8_t* arena, const Params
     b.n = b.tile_n + tail;
     return b;
 }
-// lanes 0 .. lane of a 64-bit lane mask
-__device__ __forceinline__ unsigned long long lanes_le(int lane) { return ~0ull >> (63 - lane); }
-// inclusive prefix sum over the lanes of a wave
-__device__ __forceinline__ long long wave_prefix_i64(long long v, int lane) {
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) { const long long o = __shfl_up(v, d); if (lane >= d) v += o; }
-    return v;
-}
-#define BOOK_WAVE_OF_LAUNCH() const int w = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = (int)(threadIdx.x & 63)
 
 // resting orders and distinct price levels of every side: out i32 [n][2][2] = (orders, levels)
 __global__ __launch_bounds__(64 * CDA_WPB) void k_book_counts(const uint8_t* arena, Params P, int cap, int first, int n, int32_t* out) {
-    BOOK_WAVE_OF_LAUNCH();
+    READER_WAVE();
     if (w >= 2 * n) return;
     const BookSide b = book_side(arena, P, cap, first + (w >> 1), w & 1);
     int levels = 0;
@@ -72,7 +64,7 @@ __device__ __forceinline__ void level_store(long long* rows, int level, int32_t 
     r[0] = (long long)price; r[1] = volume; r[2] = (long long)orders;
 }
 __global__ __launch_bounds__(64 * CDA_WPB) void k_book_levels(const uint8_t* arena, Params P, int cap, int first, int n, int L, long long* out) {
-    BOOK_WAVE_OF_LAUNCH();
+    READER_WAVE();
     if (w >= 2 * n) return;
     const BookSide b = book_side(arena, P, cap, first + (w >> 1), w & 1);
     long long* rows = out + 3 * (size_t)w * (size_t)L;
@@ -110,7 +102,7 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_book_levels(const uint8_t* are
 // cumulative quantity reaches it, by the first lane that does (its order is consumed partially).
 struct BookSizes { long long q[CDA_BOOK_MAX_SIZES]; };
 __global__ __launch_bounds__(64 * CDA_WPB) void k_book_impact(const uint8_t* arena, Params P, int cap, int first, int n, BookSizes S, int K, long long* out) {
-    BOOK_WAVE_OF_LAUNCH();
+    READER_WAVE();
     if (w >= 2 * n) return;
     const BookSide b = book_side(arena, P, cap, first + (w >> 1), w & 1);
     const uint32_t all = (1u << K) - 1u;
@@ -122,7 +114,7 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_book_impact(const uint8_t* are
         const bool valid = i < b.n;
         int32_t p = 0, q = 0;
         if (valid) { p = b.get(0, i); q = b.get(1, i); }
-        const long long vq = cq + wave_prefix_i64((long long)q, lane), vn = cn + wave_prefix_i64((long long)p * (long long)q, lane);
+        const long long vq = cq + wave_scan_sum((long long)q, lane), vn = cn + wave_scan_sum((long long)p * (long long)q, lane);
         cq = __shfl(vq, 63); cn = __shfl(vn, 63);                    // (a lane without an order adds nothing: lane 63 holds the pass's end)
         for (int k = 0; k < K; k++) {
             if ((done >> k) & 1u) continue;
@@ -148,7 +140,7 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_book_impact(const uint8_t* are
 // prices of its first and last own order in queue order and the quantity in front of the first; quantity and notional are summed in the wave's slice of LDS.
 __global__ __launch_bounds__(64 * CDA_WPB) void k_book_agents(const uint8_t* arena, Params P, int cap, int first, int n, int A, long long* out) {
     __shared__ unsigned long long table[CDA_WPB][CDA_MAX_AGENTS][2];
-    const int wib = (int)(threadIdx.x >> 6), w = (int)blockIdx.x * CDA_WPB + wib, lane = (int)(threadIdx.x & 63);
+    READER_WAVE_IN_GROUP(CDA_WPB);
     const bool live = w < 2 * n;
     unsigned long long (*t)[2] = table[wib];
     if (lane < 2 * CDA_MAX_AGENTS) t[lane >> 1][lane & 1] = 0ull;
@@ -164,11 +156,11 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_book_agents(const uint8_t* are
             const bool valid = i < b.n;
             int32_t p = 0, q = 0, owner = -1;
             if (valid) { p = b.get(0, i); q = b.get(1, i); owner = b.get(2, i) & 15; }
-            const long long vq = cq + wave_prefix_i64((long long)q, lane);
+            const long long vq = cq + wave_scan_sum((long long)q, lane);
             cq = __shfl(vq, 63);
             if (valid && owner < A) {
-                atomicAdd(&t[owner][0], (unsigned long long)(long long)q);
-                atomicAdd(&t[owner][1], (unsigned long long)((long long)p * (long long)q));
+                lds_add(&t[owner][0], (long long)q);
+                lds_add(&t[owner][1], (long long)p * (long long)q);
             }
             for (int a = 0; a < A; a++) {
                 const unsigned long long mk = __ballot(valid && owner == a);
@@ -213,7 +205,7 @@ __global__ __launch_bounds__(BOOK_SCAN_THREADS) void k_book_offsets(const uint8_
 // second half: the rows cda_get_book returns - (price, qty, owner, order_id, timestamp) - side after side, dense; a side whose run does not lie inside the
 // buffer as the offsets say (the book moved between the two launches, or another env's table) is left alone
 __global__ __launch_bounds__(64 * CDA_WPB) void k_book_pack(const uint8_t* arena, Params P, int cap, int first, int n, const long long* off, int32_t* out, long long out_rows) {
-    BOOK_WAVE_OF_LAUNCH();
+    READER_WAVE();
     if (w >= 2 * n) return;
     const BookSide b = book_side(arena, P, cap, first + (w >> 1), w & 1);
     const long long o = off[w];
@@ -227,29 +219,20 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_book_pack(const uint8_t* arena
 
 extern "C" {
 
-// the arguments that need no env are vetted first, then the range against the env; nothing is launched behind a refusal
-#define BOOK_RANGE_ARGS_OK(e, out, first, n) ((e) && (out) && (first) >= 0 && (n) >= 1)
-static dim3 book_grid(int32_t n_markets) { return dim3((unsigned)((2 * (int64_t)n_markets + CDA_WPB - 1) / CDA_WPB)); }
+// the arguments that need no env are vetted first, then the range against the env; nothing is launched behind a refusal.  One wave per (market, side): 2 n waves.
 
 int cda_book_counts(cda_env* e, int32_t first_market, int32_t n_markets, int32_t* counts_out_dev, void* stream) {
-    if (!BOOK_RANGE_ARGS_OK(e, counts_out_dev, first_market, n_markets)) return CDA_ERR_INVALID;
-    if (!range_ok(e, first_market, n_markets)) return CDA_ERR_INVALID;
-    HIPCHK(hipSetDevice(e->device));
-    hipLaunchKernelGGL(k_book_counts, book_grid(n_markets), dim3(64 * CDA_WPB), 0, (hipStream_t)stream, (const uint8_t*)e->arena, e->P, (int)e->cap, (int)first_market,
-                       (int)n_markets, counts_out_dev);
-    return launch_status();
+    if (!reader_args_ok(e, counts_out_dev, first_market, n_markets) || !range_ok(e, first_market, n_markets)) return CDA_ERR_INVALID;
+    return reader_launch(e, k_book_counts, 2 * n_markets, CDA_WPB, 0, stream, (const uint8_t*)e->arena, e->P, (int)e->cap, (int)first_market, (int)n_markets, counts_out_dev);
 }
 int cda_book_levels(cda_env* e, int32_t first_market, int32_t n_markets, int32_t max_levels, int64_t* levels_out_dev, void* stream) {
-    if (!BOOK_RANGE_ARGS_OK(e, levels_out_dev, first_market, n_markets) || max_levels < 1 || max_levels > CDA_BOOK_MAX_LEVELS || ((uintptr_t)levels_out_dev & 7) != 0)
-        return CDA_ERR_INVALID;
-    if (!range_ok(e, first_market, n_markets)) return CDA_ERR_INVALID;
-    HIPCHK(hipSetDevice(e->device));
-    hipLaunchKernelGGL(k_book_levels, book_grid(n_markets), dim3(64 * CDA_WPB), 0, (hipStream_t)stream, (const uint8_t*)e->arena, e->P, (int)e->cap, (int)first_market,
-                       (int)n_markets, (int)max_levels, (long long*)levels_out_dev);
-    return launch_status();
+    if (!reader_args_ok(e, levels_out_dev, first_market, n_markets) || max_levels < 1 || max_levels > CDA_BOOK_MAX_LEVELS || !aligned(levels_out_dev, 8) ||
+        !range_ok(e, first_market, n_markets)) return CDA_ERR_INVALID;
+    return reader_launch(e, k_book_levels, 2 * n_markets, CDA_WPB, 0, stream, (const uint8_t*)e->arena, e->P, (int)e->cap, (int)first_market, (int)n_markets, (int)max_levels,
+                         (long long*)levels_out_dev);
 }
 int cda_book_impact(cda_env* e, int32_t first_market, int32_t n_markets, const int64_t* sizes_host, int32_t n_sizes, int64_t* impact_out_dev, void* stream) {
-    if (!BOOK_RANGE_ARGS_OK(e, impact_out_dev, first_market, n_markets) || !sizes_host || n_sizes < 1 || n_sizes > CDA_BOOK_MAX_SIZES || ((uintptr_t)impact_out_dev & 7) != 0)
+    if (!reader_args_ok(e, impact_out_dev, first_market, n_markets) || !sizes_host || n_sizes < 1 || n_sizes > CDA_BOOK_MAX_SIZES || !aligned(impact_out_dev, 8))
         return CDA_ERR_INVALID;
     BookSizes S;
     memset(&S, 0, sizeof S);
@@ -258,36 +241,25 @@ int cda_book_impact(cda_env* e, int32_t first_market, int32_t n_markets, const i
         S.q[k] = (long long)sizes_host[k];
     }
     if (!range_ok(e, first_market, n_markets)) return CDA_ERR_INVALID;
-    HIPCHK(hipSetDevice(e->device));
-    hipLaunchKernelGGL(k_book_impact, book_grid(n_markets), dim3(64 * CDA_WPB), 0, (hipStream_t)stream, (const uint8_t*)e->arena, e->P, (int)e->cap, (int)first_market,
-                       (int)n_markets, S, (int)n_sizes, (long long*)impact_out_dev);
-    return launch_status();
+    return reader_launch(e, k_book_impact, 2 * n_markets, CDA_WPB, 0, stream, (const uint8_t*)e->arena, e->P, (int)e->cap, (int)first_market, (int)n_markets, S, (int)n_sizes,
+                         (long long*)impact_out_dev);
 }
 int cda_book_agents(cda_env* e, int32_t first_market, int32_t n_markets, int64_t* agents_out_dev, void* stream) {
-    if (!BOOK_RANGE_ARGS_OK(e, agents_out_dev, first_market, n_markets) || ((uintptr_t)agents_out_dev & 7) != 0) return CDA_ERR_INVALID;
-    if (!range_ok(e, first_market, n_markets) || e->P.cfg.num_agents < 1 || e->P.cfg.num_agents > CDA_MAX_AGENTS) return CDA_ERR_INVALID;
-    HIPCHK(hipSetDevice(e->device));
-    hipLaunchKernelGGL(k_book_agents, book_grid(n_markets), dim3(64 * CDA_WPB), 0, (hipStream_t)stream, (const uint8_t*)e->arena, e->P, (int)e->cap, (int)first_market,
-                       (int)n_markets, (int)e->P.cfg.num_agents, (long long*)agents_out_dev);
-    return launch_status();
+    if (!reader_args_ok(e, agents_out_dev, first_market, n_markets) || !aligned(agents_out_dev, 8) || !range_ok(e, first_market, n_markets) || !agents_ok(e)) return CDA_ERR_INVALID;
+    return reader_launch(e, k_book_agents, 2 * n_markets, CDA_WPB, 0, stream, (const uint8_t*)e->arena, e->P, (int)e->cap, (int)first_market, (int)n_markets,
+                         (int)e->P.cfg.num_agents, (long long*)agents_out_dev);
 }
 int cda_book_offsets(cda_env* e, int32_t first_market, int32_t n_markets, int64_t* offsets_dev, void* stream) {
-    if (!BOOK_RANGE_ARGS_OK(e, offsets_dev, first_market, n_markets) || ((uintptr_t)offsets_dev & 7) != 0) return CDA_ERR_INVALID;
-    if (!range_ok(e, first_market, n_markets)) return CDA_ERR_INVALID;
-    HIPCHK(hipSetDevice(e->device));
-    hipLaunchKernelGGL(k_book_offsets, dim3(1), dim3(BOOK_SCAN_THREADS), 0, (hipStream_t)stream, (const uint8_t*)e->arena, e->P, (int)e->cap, (int)first_market, (int)n_markets,
-                       (long long*)offsets_dev);
-    return launch_status();
+    if (!reader_args_ok(e, offsets_dev, first_market, n_markets) || !aligned(offsets_dev, 8) || !range_ok(e, first_market, n_markets)) return CDA_ERR_INVALID;
+    return reader_launch(e, k_book_offsets, 1, BOOK_SCAN_THREADS / 64, 0, stream, (const uint8_t*)e->arena, e->P, (int)e->cap, (int)first_market, (int)n_markets,
+                         (long long*)offsets_dev);                   // (the scan: ONE workgroup)
 }
 int cda_book_pack(cda_env* e, int32_t first_market, int32_t n_markets, const int64_t* offsets_dev, int64_t total_orders, void* orders_out_dev, int64_t capacity_orders,
                   void* stream) {
-    if (!BOOK_RANGE_ARGS_OK(e, offsets_dev, first_market, n_markets) || total_orders < 0 || capacity_orders < total_orders || (capacity_orders > 0 && !orders_out_dev) ||
-        ((uintptr_t)orders_out_dev & 3) != 0) return CDA_ERR_INVALID;
-    if (!range_ok(e, first_market, n_markets)) return CDA_ERR_INVALID;
-    HIPCHK(hipSetDevice(e->device));
-    hipLaunchKernelGGL(k_book_pack, book_grid(n_markets), dim3(64 * CDA_WPB), 0, (hipStream_t)stream, (const uint8_t*)e->arena, e->P, (int)e->cap, (int)first_market,
-                       (int)n_markets, (const long long*)offsets_dev, (int32_t*)orders_out_dev, (long long)capacity_orders);
-    return launch_status();
+    if (!reader_args_ok(e, offsets_dev, first_market, n_markets) || total_orders < 0 || capacity_orders < total_orders || (capacity_orders > 0 && !orders_out_dev) ||
+        !aligned(orders_out_dev, 4) || !range_ok(e, first_market, n_markets)) return CDA_ERR_INVALID;
+    return reader_launch(e, k_book_pack, 2 * n_markets, CDA_WPB, 0, stream, (const uint8_t*)e->arena, e->P, (int)e->cap, (int)first_market, (int)n_markets,
+                         (const long long*)offsets_dev, (int32_t*)orders_out_dev, (long long)capacity_orders);
 }
 
 }  // extern "C"

@@ -15,6 +15,8 @@
 //                      k_raw_snapshot  agg_LOB_raw            exchg/state_helper.py:159-160
 //   cda_hist_variants.inc  the loop over the compiled history depths of the policy network (4 and CDA_HIST_DEPTHS): includes a body file once per depth
 //   cda_cap_table.inc      cda::CapKernels, and per book capacity the table of that namespace's kernels (included behind the per-capacity includes below)
+//   cda_wave.hpp     the wave toolkit of every one-wave-per-market reader (and the scripted book walks): wave reductions and scans, lanes_le, lds_add, the
+//                    reader preamble READER_WAVE, reader_info - included below, ahead of every .inc
 //   cda_snapshot.inc k_snap_offsets, k_snap_pack, k_snap_check, k_snap_restore and the cda_snapshot_* entry points (included at the end)
 //   cda_book_report.inc  k_book_counts, k_book_levels, k_book_impact, k_book_agents, k_book_offsets, k_book_pack: read-only reductions over the
 //                    standing book (tile + spill ring), one wave per (market, side), and the cda_book_* entry points (included at the end)
@@ -24,6 +26,7 @@
 //    library of their own: nothing of them is in the product)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -63,6 +66,7 @@ using namespace cda;
 #ifndef CDA_VGPR_CAP_ATTR
 #define CDA_VGPR_CAP_ATTR
 #endif
+#include "cda_wave.hpp"      // the wave toolkit of the readers and the scripted book walks: reductions, scans, the reader preamble, the info row
 
 // ------------------------------------------------------------------------------------------
 // device helpers shared by the kernels
@@ -695,6 +699,15 @@ template <class K, class... A>
 static void launch_1d(K kern, int n, int block, size_t smem, hipStream_t stream, A... a) {
     launch(kern, Launch{dim3((unsigned)((n + block - 1) / block)), dim3(block), smem, stream}, a...);
 }
+// the grid of n waves (one per market, mostly), `waves` of them per workgroup
+static dim3 grid_for(int n, int waves = CDA_WPB) { return dim3((unsigned)((n + waves - 1) / waves)); }
+// a reader's launch (cda_tape_*, cda_book_*, cda_quote_*): `items` waves, `waves` per workgroup, `lds` bytes of dynamic LDS; the status is what the entry point returns
+template <class K, class... A>
+static int reader_launch(const cda_env* e, K kern, int items, int waves, size_t lds, void* stream, A... a) {
+    HIPCHK(hipSetDevice(e->device));
+    launch(kern, Launch{grid_for(items, waves), dim3(64 * waves), lds, (hipStream_t)stream}, a...);
+    return launch_status();
+}
 
 extern "C" {
 
@@ -795,7 +808,6 @@ int cda_check_market_params(const cda_config* env_cfg, int32_t n, const cda_mark
 }
 
 // launch the capacity variant of a market-wave kernel that matches the env
-static dim3 grid_for(int n) { return dim3((unsigned)((n + CDA_WPB - 1) / CDA_WPB)); }
 static size_t smem_for(const cda_env* e, int waves) {
     return (size_t)DEC_TABLE_BYTES + (size_t)waves * (size_t)e->k->lds_bytes_per_wave(e->P.cfg.num_agents, e->P.cfg.n_hist);
 }
@@ -804,6 +816,13 @@ static Launch waves_for(const cda_env* e, int n, size_t extra, hipStream_t strea
 static Launch one_wave(const cda_env* e) { return Launch{dim3(1), dim3(64), smem_for(e, 1), 0}; }
 
 static int range_ok(const cda_env* e, int32_t first, int32_t n) { return first >= 0 && n >= 1 && (int64_t)first + (int64_t)n <= (int64_t)e->P.n_markets; }
+// ---- what the readers' entry points (cda_tape_*, cda_book_*, cda_quote_*) share: their refusals (their launch: reader_launch above)
+static bool which_ok(int32_t which) { return which == CDA_TAPE_CURRENT || which == CDA_TAPE_PREVIOUS; }
+static bool agents_ok(const cda_env* e) { return e->P.cfg.num_agents >= 1 && e->P.cfg.num_agents <= CDA_MAX_AGENTS; }
+static bool aligned(const void* p, uintptr_t bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }      // (NULL is aligned: an optional output)
+// what every reader refuses without looking at the env: no env, no output, an empty or negative range.  An entry point vets these and its other env-free arguments
+// first and the range against the env (range_ok) last: a bad argument is CDA_ERR_INVALID before the env is touched.
+static bool reader_args_ok(const cda_env* e, const void* out, int32_t first, int32_t n) { return e && out && first >= 0 && n >= 1; }
 // everything an env can own, in cda_destroy's order; a half-built env (cda_create's failure paths) holds NULL where nothing was allocated yet
 static void env_free(cda_env* e) {
     if (e->arena) (void)hipFree(e->arena);

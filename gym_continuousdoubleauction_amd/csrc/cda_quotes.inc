@@ -1,5 +1,6 @@
 // cda_quotes.inc - the quote tape (include/cda.h cda_quotes_*, cda_quote_*, cda_tape_spreads): the top of the book per step of an episode, recorded on the device,
-// and the reductions over it.  Included at the end of cda_hip.hip, behind cda_book_report.inc (the walk of a side: BookSide) and cda_tape.inc (tape_span).
+// and the reductions over it.  Included at the end of cda_hip.hip, behind cda_book_report.inc (the walk of a side: BookSide) and cda_tape.inc (tape_span,
+// tape_load); the wave toolkit is cda_wave.hpp.  The record's layout as the readers see it - quote_two_sided, quote_m2 and their kin - stands beside QuoteSpan.
 //
 // Per market a ring of `capacity` records (cda_quote_record, eight int32 words = two 16-byte words) in a buffer of its own beside the arena, and one QuoteMeta
 // row: neither the market record, nor the state dump, nor the snapshot blob know of either.  The WRITER is k_quote_record, which launch_step issues behind the
@@ -84,21 +85,18 @@ __device__ __forceinline__ uint32_t quote_slot(const QuoteSpan& s, uint32_t cap,
     const uint32_t x = s.slot0 + (uint32_t)i;                        // < 2 x capacity <= 2^21
     return x >= cap ? x - cap : x;
 }
-__device__ __forceinline__ long long quote_wave_sum(long long v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-__device__ __forceinline__ long long quote_wave_min(long long v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { const long long o = __shfl_xor(v, d); v = o < v ? o : v; }
-    return v;
-}
-__device__ __forceinline__ long long quote_wave_max(long long v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { const long long o = __shfl_xor(v, d); v = o > v ? o : v; }
-    return v;
-}
+// THE LAYOUT OF A RECORD, as the readers see it: two 16-byte words r0, r1 of the ring = cda_quote_record (include/cda.h).  The writer is k_quote_record below (one
+// word per lane, in the struct's order); every reader decodes through these accessors and nowhere else.  m2 = bid + ask: the mid in half price units.
+static_assert(offsetof(cda_quote_record, flags) == 4 && offsetof(cda_quote_record, bid_price) == 8 && offsetof(cda_quote_record, ask_price) == 12,
+              "r0 = (step, flags, bid_price, ask_price)");
+static_assert(offsetof(cda_quote_record, bid_volume) == 16 && offsetof(cda_quote_record, ask_volume) == 20, "r1 = (bid_volume, ask_volume, bid_orders, ask_orders)");
+// (macros for the reason given beside the tape's accessors in cda_tape.inc; quote_m2_i32: the same sum in 32 bits, as styl_stage keeps it in LDS)
+#define quote_sides(r0) ((int)((r0).y & 3u))
+#define quote_two_sided(r0) (((r0).y & 3u) == 3u)
+#define quote_bid(r0) ((long long)(int)(r0).z)
+#define quote_ask(r0) ((long long)(int)(r0).w)
+#define quote_m2(r0) (quote_bid(r0) + quote_ask(r0))
+#define quote_m2_i32(r0) ((int32_t)(r0).z + (int32_t)(r0).w)
 
 // the best level of one side: its price, the summed quantity and the number of its orders.  The side is walked in queue order, 64 orders per pass: the level is the
 // run of orders from the first on that carry the first order's price - it ends inside a pass, or continues (a level deeper than the tile: into the HBM ring).
@@ -112,14 +110,15 @@ __device__ __forceinline__ void quote_head(const BookSide& b, int lane, int32_t&
         if (base == 0) price = __shfl(p, 0);
         const bool in = valid && p == price;
         const unsigned long long m = __ballot(in);
-        volume += quote_wave_sum(in ? (long long)q : 0ll);
+        volume += wave_sum(in ? (long long)q : 0ll);
         orders += (long long)__popcll(m);
         if (m != ~0ull) break;                                       // (uniform) the level ended inside this pass
     }
 }
 
+// (the record's layout is stated once, for every reader, by the accessors beside QuoteSpan above: quote_two_sided, quote_m2)
 __global__ __launch_bounds__(64 * CDA_WPB) void k_quote_record(const uint8_t* arena, Params P, QuoteArgs Q, int cap, int first, int n) {
-    BOOK_WAVE_OF_LAUNCH();
+    READER_WAVE();
     if (w >= n) return;
     const int mi = first + w;
     // the header's leading words, one per lane: what episode_over asks (the done mask, t_step) without the record
@@ -147,7 +146,7 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_quote_record(const uint8_t* ar
 
 // the rolled meta rows of a range, as the readers see them: out i32 [n][8]
 __global__ __launch_bounds__(64 * CDA_WPB) void k_quote_meta(const uint8_t* arena, Params P, QuoteArgs Q, int first, int n, int32_t* out) {
-    BOOK_WAVE_OF_LAUNCH();
+    READER_WAVE();
     if (w >= n) return;
     const QuoteMeta h = quote_meta_now(Q, arena, P, first + w, lane);
     if (lane < 8) out[8 * (size_t)w + lane] = quote_meta_word(h, lane);
@@ -157,7 +156,7 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_quote_meta(const uint8_t* aren
 // them because the ring overwrote them, step of the first copied record, partial}
 __global__ __launch_bounds__(64 * CDA_WPB) void k_quote_series(const uint8_t* arena, Params P, QuoteArgs Q, int first, int n, int which, int kmax, uint4* out,
                                                                int32_t* counts, int32_t* info) {
-    BOOK_WAVE_OF_LAUNCH();
+    READER_WAVE();
     if (w >= n) return;
     const int mi = first + w;
     const QuoteSpan sp = quote_span(quote_meta_now(Q, arena, P, mi, lane), Q.cap, which);
@@ -168,14 +167,14 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_quote_series(const uint8_t* ar
     for (long long x = 2ll * cnt + lane; x < 2ll * (long long)kmax; x += WAVE) dst[x] = make_uint4(0u, 0u, 0u, 0u);
     if (lane == 0) {
         if (counts) counts[w] = cnt;
-        if (info) { int32_t* o = info + 4 * (size_t)w; o[0] = cnt; o[1] = sp.lost; o[2] = sp.step0 + skip; o[3] = sp.partial; }
+        if (info) reader_info(info, w, cnt, sp.lost, sp.step0 + skip, sp.partial);
     }
 }
 
 // the statistics of an episode's held records: out i64 [n][CDA_QUOTE_STAT_WORDS].  64 steps per pass, lane l reads record base + l; the left neighbour comes by
 // __shfl_up, lane 0's from the carry of the pass before (uniform registers); wave reductions finish every sum.
 __global__ __launch_bounds__(64 * CDA_WPB) void k_quote_stats(const uint8_t* arena, Params P, QuoteArgs Q, int first, int n, int which, long long* out, int32_t* info) {
-    BOOK_WAVE_OF_LAUNCH();
+    READER_WAVE();
     if (w >= n) return;
     const int mi = first + w;
     const QuoteSpan sp = quote_span(quote_meta_now(Q, arena, P, mi, lane), Q.cap, which);
@@ -189,9 +188,9 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_quote_stats(const uint8_t* are
         const bool in = idx < sp.count;
         uint4 r0 = make_uint4(0u, 0u, 0u, 0u), r1 = r0;
         if (in) { const uint32_t slot = quote_slot(sp, Q.cap, idx); r0 = ring[2 * (size_t)slot]; r1 = ring[2 * (size_t)slot + 1]; }
-        const int side = (int)(r0.y & 3u);
+        const int side = quote_sides(r0);
         const int two = in && side == 3 ? 1 : 0;
-        const long long bid = (long long)(int)r0.z, ask = (long long)(int)r0.w, m2 = bid + ask, spread = ask - bid;
+        const long long bid = quote_bid(r0), ask = quote_ask(r0), m2 = bid + ask, spread = ask - bid;
         int p_two = __shfl_up(two, 1);
         long long p_m2 = __shfl_up(m2, 1);
         if (lane == 0) { p_two = c_two; p_m2 = c_m2; }
@@ -201,13 +200,13 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_quote_stats(const uint8_t* are
         s_bid += (long long)__popcll(__ballot(in && side == 1));
         s_ask += (long long)__popcll(__ballot(in && side == 2));
         s_empty += (long long)__popcll(__ballot(in && side == 0));
-        s_sp += quote_wave_sum(two ? spread : 0ll); s_sq += quote_wave_sum(two ? spread * spread : 0ll); s_m2 += quote_wave_sum(two ? m2 : 0ll);
-        s_bv += quote_wave_sum(two ? (long long)(int)r1.x : 0ll); s_av += quote_wave_sum(two ? (long long)(int)r1.y : 0ll);
-        const long long lo = quote_wave_min(two ? spread : 0x7fffffffffffffffll), hi = quote_wave_max(two ? spread : -0x7fffffffffffffffll - 1);
+        s_sp += wave_sum(two ? spread : 0ll); s_sq += wave_sum(two ? spread * spread : 0ll); s_m2 += wave_sum(two ? m2 : 0ll);
+        s_bv += wave_sum(two ? (long long)(int)r1.x : 0ll); s_av += wave_sum(two ? (long long)(int)r1.y : 0ll);
+        const long long lo = wave_min(two ? spread : 0x7fffffffffffffffll), hi = wave_max(two ? spread : -0x7fffffffffffffffll - 1);
         s_min = lo < s_min ? lo : s_min; s_max = hi > s_max ? hi : s_max;
         s_pairs += (long long)__popcll(__ballot(pair));
         s_chg += (long long)__popcll(__ballot(pair && d != 0));
-        s_abs += quote_wave_sum(d < 0 ? -d : d); s_d2 += quote_wave_sum(d * d);
+        s_abs += wave_sum(d < 0 ? -d : d); s_d2 += wave_sum(d * d);
         c_two = __shfl(two, 63); c_m2 = __shfl(m2, 63);
     }
     if (s_two == 0) { s_min = 0; s_max = 0; }
@@ -218,18 +217,17 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_quote_stats(const uint8_t* are
                             lane == QS_PAIRS ? s_pairs : lane == QS_M2_CHANGES ? s_chg : lane == QS_ABS_DM2 ? s_abs : s_d2;
         out[(size_t)w * CDA_QUOTE_STAT_WORDS + lane] = v;
     }
-    if (info && lane == 0) { int32_t* o = info + 4 * (size_t)w; o[0] = sp.count; o[1] = sp.lost; o[2] = sp.step0; o[3] = sp.partial; }
+    if (info && lane == 0) reader_info(info, w, sp.count, sp.lost, sp.step0, sp.partial);
 }
 
 // Spread reports: the trade tape joined to the quotes, by step.  One wave per market, lanes over the episode's tape records, 64 per pass (k_tape_exec's frame);
 // per fill and horizon the quotes of step s and of step s + k are read at their slots - indexed directly, no search - and the six words of (agent, horizon, role)
 // are integer adds on the wave's own slice of dynamic LDS, written out once, dense.
 struct SpreadHorizons { int32_t k[CDA_TAPE_MAX_HORIZONS]; };
-__device__ __forceinline__ void spread_add(unsigned long long* p, long long v) { atomicAdd(p, (unsigned long long)v); }
 __global__ __launch_bounds__(64 * CDA_WPB) void k_tape_spreads(const uint8_t* arena, Params P, TapeArgs T, QuoteArgs Q, int first, int n, int which, int agents, int nh,
                                                                SpreadHorizons hz, long long* out, int32_t* info) {
     extern __shared__ __align__(16) unsigned long long spread_lds[];  // per wave: agents x nh x 2 roles x SP_WORDS
-    const int wib = (int)(threadIdx.x >> 6), w = (int)blockIdx.x * CDA_WPB + wib, lane = (int)(threadIdx.x & 63);
+    READER_WAVE_IN_GROUP(CDA_WPB);
     const bool live = w < n;
     const int n_words = agents * nh * 2 * SP_WORDS;
     unsigned long long* tb = spread_lds + (size_t)wib * (size_t)n_words;
@@ -250,12 +248,12 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_tape_spreads(const uint8_t* ar
         for (int base = 0; base < count; base += WAVE) {
             const int idx = base + lane;
             const bool in = idx < count;
-            uint4 r0 = make_uint4(0u, 0u, 0u, 0u), r1 = r0;
-            if (in) { const uint32_t slot = (t0 + (uint32_t)idx) & tmask; r0 = tring[2 * (size_t)slot]; r1 = tring[2 * (size_t)slot + 1]; }
-            const uint32_t cid = r0.w, iid = r1.z;
-            const long long step = (long long)(r1.w >> 2);
-            const int cside = (int)(r1.w & 1u), iside = (int)((r1.w >> 1) & 1u);
-            const long long price = (long long)(int)r0.y, qty = (long long)(int)r0.z;
+            uint4 r0, r1;
+            tape_load(tring, tmask, t0, idx, in, r0, r1);
+            const uint32_t cid = tape_counter_id(r0), iid = tape_init_id(r1);
+            const long long step = (long long)tape_step(r1);
+            const int cside = tape_counter_side(r1), iside = tape_init_side(r1);
+            const long long price = (long long)tape_price(r0), qty = (long long)tape_qty(r0);
             const bool ok = in && cid < (uint32_t)agents && iid < (uint32_t)agents;      // (ids outside the env's agents cannot index the table)
             const bool ev = ok && cid != iid;
             used += __popcll(__ballot(ok));
@@ -263,27 +261,27 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_tape_spreads(const uint8_t* ar
             const bool now_held = ev && step >= q_first && step <= q_last;
             uint4 qa = make_uint4(0u, 0u, 0u, 0u);
             if (now_held) qa = qring[2 * (size_t)quote_slot(qs, Q.cap, (int)(step - q_first))];
-            const bool now_two = now_held && (qa.y & 3u) == 3u;
-            const long long now = 2 * price - ((long long)(int)qa.z + (long long)(int)qa.w);
+            const bool now_two = now_held && quote_two_sided(qa);
+            const long long now = 2 * price - quote_m2(qa);
             for (int h = 0; h < nh; h++) {
                 const long long due = step + (long long)hz.k[h];
                 const bool open = ev && due > q_last;
                 const bool later_held = ev && !open && due >= q_first;                   // (due >= step: held whenever the fill's own step is)
                 uint4 qb = make_uint4(0u, 0u, 0u, 0u);
                 if (later_held) qb = qring[2 * (size_t)quote_slot(qs, Q.cap, (int)(due - q_first))];
-                const bool scored = now_two && later_held && (qb.y & 3u) == 3u;
+                const bool scored = now_two && later_held && quote_two_sided(qb);
                 if (!ev) continue;
                 unsigned long long* cm = tb + (((int)cid * nh + h) * 2) * SP_WORDS;          // [agent][horizon][role 0 = maker][6]
                 unsigned long long* ct = tb + (((int)iid * nh + h) * 2 + 1) * SP_WORDS;      // ... [role 1 = taker]
                 if (scored) {
-                    const long long later = 2 * price - ((long long)(int)qb.z + (long long)(int)qb.w);
-                    spread_add(cm + SP_COST_NOW, (cside ? -now : now) * qty); spread_add(cm + SP_COST_LATER, (cside ? -later : later) * qty);
-                    spread_add(cm + SP_QTY, qty); spread_add(cm + SP_FILLS, 1ll);
-                    spread_add(ct + SP_COST_NOW, (iside ? -now : now) * qty); spread_add(ct + SP_COST_LATER, (iside ? -later : later) * qty);
-                    spread_add(ct + SP_QTY, qty); spread_add(ct + SP_FILLS, 1ll);
+                    const long long later = 2 * price - quote_m2(qb);
+                    lds_add(cm + SP_COST_NOW, (cside ? -now : now) * qty); lds_add(cm + SP_COST_LATER, (cside ? -later : later) * qty);
+                    lds_add(cm + SP_QTY, qty); lds_add(cm + SP_FILLS, 1ll);
+                    lds_add(ct + SP_COST_NOW, (iside ? -now : now) * qty); lds_add(ct + SP_COST_LATER, (iside ? -later : later) * qty);
+                    lds_add(ct + SP_QTY, qty); lds_add(ct + SP_FILLS, 1ll);
                 } else {
                     const int word = open ? SP_OPEN : SP_UNQUOTED;
-                    spread_add(cm + word, 1ll); spread_add(ct + word, 1ll);
+                    lds_add(cm + word, 1ll); lds_add(ct + word, 1ll);
                 }
             }
         }
@@ -292,10 +290,7 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_tape_spreads(const uint8_t* ar
     if (!live) return;
     long long* o = out + (size_t)w * (size_t)n_words;
     for (int i = lane; i < n_words; i += WAVE) o[i] = (long long)tb[i];
-    if (info && lane == 0) {
-        int32_t* x = info + 4 * (size_t)w;
-        x[0] = (int32_t)used; x[1] = (int32_t)ts.lost; x[2] = (int32_t)qs.lost; x[3] = (int32_t)(ts.partial | (qs.partial << 1));
-    }
+    if (info && lane == 0) reader_info(info, w, (int32_t)used, (int32_t)ts.lost, (int32_t)qs.lost, (int32_t)(ts.partial | (qs.partial << 1)));
 }
 
 // the launch every step entry point issues behind the order schedule's and ahead of the step (launch_step); arguments validated by the callers
@@ -336,53 +331,41 @@ int cda_quotes_disable(cda_env* e) {
 }
 int64_t cda_quotes_capacity(const cda_env* e) { return e && e->quotes.ring ? (int64_t)e->quotes.cap : 0; }
 
-#define QUOTE_WHICH_OK(which) ((which) == CDA_TAPE_CURRENT || (which) == CDA_TAPE_PREVIOUS)
-static dim3 quote_grid(int32_t n_markets) { return dim3((unsigned)((n_markets + CDA_WPB - 1) / CDA_WPB)); }
-
 int cda_quote_meta(cda_env* e, int32_t first_market, int32_t n_markets, int32_t* meta_out_dev, void* stream) {
-    if (!e || !meta_out_dev || !range_ok(e, first_market, n_markets) || ((uintptr_t)meta_out_dev & 3) != 0) return CDA_ERR_INVALID;
+    if (!reader_args_ok(e, meta_out_dev, first_market, n_markets) || !aligned(meta_out_dev, 4) || !range_ok(e, first_market, n_markets)) return CDA_ERR_INVALID;
     if (!e->quotes.ring) return CDA_ERR_UNSUPPORTED;
-    HIPCHK(hipSetDevice(e->device));
-    hipLaunchKernelGGL(k_quote_meta, quote_grid(n_markets), dim3(64 * CDA_WPB), 0, (hipStream_t)stream, (const uint8_t*)e->arena, e->P, e->quotes, (int)first_market,
-                       (int)n_markets, meta_out_dev);
-    return launch_status();
+    return reader_launch(e, k_quote_meta, n_markets, CDA_WPB, 0, stream, (const uint8_t*)e->arena, e->P, e->quotes, (int)first_market, (int)n_markets, meta_out_dev);
 }
 int cda_quote_series(cda_env* e, int32_t first_market, int32_t n_markets, int32_t which, int32_t k, void* records_out_dev, int32_t* counts_out_dev, int32_t* info_out_dev,
                      void* stream) {
-    if (!e || !records_out_dev || k < 1 || !QUOTE_WHICH_OK(which) || !range_ok(e, first_market, n_markets) || ((uintptr_t)records_out_dev & 15) != 0 ||
-        ((uintptr_t)counts_out_dev & 3) != 0 || ((uintptr_t)info_out_dev & 3) != 0) return CDA_ERR_INVALID;
+    if (!reader_args_ok(e, records_out_dev, first_market, n_markets) || k < 1 || !which_ok(which) || !aligned(records_out_dev, 16) || !aligned(counts_out_dev, 4) ||
+        !aligned(info_out_dev, 4) || !range_ok(e, first_market, n_markets)) return CDA_ERR_INVALID;
     if (!e->quotes.ring) return CDA_ERR_UNSUPPORTED;
-    HIPCHK(hipSetDevice(e->device));
-    hipLaunchKernelGGL(k_quote_series, quote_grid(n_markets), dim3(64 * CDA_WPB), 0, (hipStream_t)stream, (const uint8_t*)e->arena, e->P, e->quotes, (int)first_market,
-                       (int)n_markets, (int)which, (int)k, (uint4*)records_out_dev, counts_out_dev, info_out_dev);
-    return launch_status();
+    return reader_launch(e, k_quote_series, n_markets, CDA_WPB, 0, stream, (const uint8_t*)e->arena, e->P, e->quotes, (int)first_market, (int)n_markets, (int)which, (int)k,
+                         (uint4*)records_out_dev, counts_out_dev, info_out_dev);
 }
 int cda_quote_stats(cda_env* e, int32_t first_market, int32_t n_markets, int32_t which, int64_t* stats_out_dev, int32_t* info_out_dev, void* stream) {
-    if (!e || !stats_out_dev || !QUOTE_WHICH_OK(which) || !range_ok(e, first_market, n_markets) || ((uintptr_t)stats_out_dev & 7) != 0 ||
-        ((uintptr_t)info_out_dev & 3) != 0) return CDA_ERR_INVALID;
+    if (!reader_args_ok(e, stats_out_dev, first_market, n_markets) || !which_ok(which) || !aligned(stats_out_dev, 8) || !aligned(info_out_dev, 4) ||
+        !range_ok(e, first_market, n_markets)) return CDA_ERR_INVALID;
     if (!e->quotes.ring) return CDA_ERR_UNSUPPORTED;
-    HIPCHK(hipSetDevice(e->device));
-    hipLaunchKernelGGL(k_quote_stats, quote_grid(n_markets), dim3(64 * CDA_WPB), 0, (hipStream_t)stream, (const uint8_t*)e->arena, e->P, e->quotes, (int)first_market,
-                       (int)n_markets, (int)which, (long long*)stats_out_dev, info_out_dev);
-    return launch_status();
+    return reader_launch(e, k_quote_stats, n_markets, CDA_WPB, 0, stream, (const uint8_t*)e->arena, e->P, e->quotes, (int)first_market, (int)n_markets, (int)which,
+                         (long long*)stats_out_dev, info_out_dev);
 }
 int cda_tape_spreads(cda_env* e, int32_t first_market, int32_t n_markets, int32_t which, const int32_t* horizons_host, int32_t n_horizons, int64_t* spreads_out_dev,
                      int32_t* info_out_dev, void* stream) {
-    if (!e || !horizons_host || !spreads_out_dev || n_horizons < 1 || n_horizons > CDA_TAPE_MAX_HORIZONS || !QUOTE_WHICH_OK(which) ||
-        !range_ok(e, first_market, n_markets) || ((uintptr_t)spreads_out_dev & 7) != 0 || ((uintptr_t)info_out_dev & 3) != 0) return CDA_ERR_INVALID;
+    if (!reader_args_ok(e, spreads_out_dev, first_market, n_markets) || !horizons_host || n_horizons < 1 || n_horizons > CDA_TAPE_MAX_HORIZONS || !which_ok(which) ||
+        !aligned(spreads_out_dev, 8) || !aligned(info_out_dev, 4) || !range_ok(e, first_market, n_markets)) return CDA_ERR_INVALID;
     SpreadHorizons hz;
     memset(&hz, 0, sizeof hz);
     for (int h = 0; h < n_horizons; h++) {
         if (horizons_host[h] < 0) return CDA_ERR_INVALID;
         hz.k[h] = horizons_host[h];
     }
-    if (e->P.cfg.num_agents < 1 || e->P.cfg.num_agents > CDA_MAX_AGENTS) return CDA_ERR_INVALID;
+    if (!agents_ok(e)) return CDA_ERR_INVALID;
     if (!e->tape.ring || !e->quotes.ring) return CDA_ERR_UNSUPPORTED;
-    HIPCHK(hipSetDevice(e->device));
     const size_t lds = (size_t)CDA_WPB * (size_t)e->P.cfg.num_agents * (size_t)n_horizons * 2 * SP_WORDS * sizeof(unsigned long long);      // <= 4 x 16 x 8 x 12 x 8 = 48 KiB
-    hipLaunchKernelGGL(k_tape_spreads, quote_grid(n_markets), dim3(64 * CDA_WPB), lds, (hipStream_t)stream, (const uint8_t*)e->arena, e->P, e->tape, e->quotes,
-                       (int)first_market, (int)n_markets, (int)which, (int)e->P.cfg.num_agents, (int)n_horizons, hz, (long long*)spreads_out_dev, info_out_dev);
-    return launch_status();
+    return reader_launch(e, k_tape_spreads, n_markets, CDA_WPB, lds, stream, (const uint8_t*)e->arena, e->P, e->tape, e->quotes, (int)first_market, (int)n_markets, (int)which,
+                         (int)e->P.cfg.num_agents, (int)n_horizons, hz, (long long*)spreads_out_dev, info_out_dev);
 }
 
 }  // extern "C"

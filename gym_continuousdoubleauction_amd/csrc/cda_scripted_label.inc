@@ -42,7 +42,7 @@ __device__ __forceinline__ int label_depth(const cda_script_profile& pf, bool on
 __global__ __launch_bounds__(64 * CDA_WPB) void k_script_label(const uint8_t* arena, Params P, int cap, int first, int n, ScriptArgs S, LabelArgs Lb, const long long* counter,
                                                               long long draw, int32_t* env_cat, float* env_mean, float* env_sigma, int32_t* env_price, int32_t* env_off,
                                                               float* a_cont, float* logp, float* rec) {
-    BOOK_WAVE_OF_LAUNCH();
+    READER_WAVE();
     if (w >= n) return;
     const int mi = first + w, A = P.cfg.num_agents;
     const long long slot_ix = (long long)mi * A + lane;
@@ -77,7 +77,7 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_script_label(const uint8_t* ar
                 const int32_t up = __shfl_up(p, 1);
                 const unsigned long long heads = __ballot(valid && (lane == 0 ? (lv < 0 || p != cp) : p != up));
                 const int level = lv + __popcll(heads & lanes_le(lane));
-                const long long vq = wave_prefix_i64((long long)q, lane);
+                const long long vq = wave_scan_sum((long long)q, lane);
                 for (int d = 1; d <= dmax; d++) {                    // levels never decrease along the queue: the orders of levels < d are a prefix of the pass
                     const int k = __popcll(__ballot(valid && level < d));
                     if (k == 0) continue;                            // (uniform)

@@ -240,7 +240,7 @@ int cda_snapshot_pack(cda_env* e, int32_t first_market, int32_t n_markets, const
     h.spill_cap = e->P.lay.spill_cap; h.episode_metrics_on = e->P.lay.ep_on; h.nav_tolerance = e->P.ep_tol;
     h.first_market = first_market; h.em_agent_fields = CDA_EM_AGENT_FIELDS; h.em_env_fields = CDA_EM_ENV_FIELDS; h.section_meta_bytes = (int32_t)sizeof(SnapMeta);
     h.cfg = e->P.cfg;
-    const dim3 grid((unsigned)((n_markets + CDA_WPB - 1) / CDA_WPB)), block(64 * CDA_WPB);
+    const dim3 grid = grid_for(n_markets), block(64 * CDA_WPB);
     hipLaunchKernelGGL(k_snap_pack<CDA_SNAP_NT_STORES != 0>, grid, block, 0, (hipStream_t)stream, (const uint8_t*)e->arena, e->P, (int)first_market, (int)n_markets,
                        (const long long*)offsets_dev, (uint8_t*)blob_dev, (long long)blob_bytes, A);
     return launch_status();
@@ -280,7 +280,7 @@ int cda_snapshot_restore(cda_env* e, int32_t first_market, const void* blob_dev,
     HIPCHK(hipMemcpyAsync(&bad, e->snap_flag, sizeof bad, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     if (bad) return CDA_ERR_INVALID;                      // nothing of the env has been written
-    hipLaunchKernelGGL(k_snap_restore, dim3((unsigned)((n_markets + CDA_WPB - 1) / CDA_WPB)), dim3(64 * CDA_WPB), 0, st, e->arena, e->P, (int)first_market,
+    hipLaunchKernelGGL(k_snap_restore, grid_for(n_markets), dim3(64 * CDA_WPB), 0, st, e->arena, e->P, (int)first_market,
                        (const uint8_t*)blob_dev, (int)src_first, (int)n_markets, (int)(h.spill_cap == e->P.lay.spill_cap), obs_out);
     HIPCHK(hipGetLastError());
     return tape_after_restore(e, first_market, n_markets, st);      // (a blob carries no tape: the restored markets' records from here on are an episode's tail)

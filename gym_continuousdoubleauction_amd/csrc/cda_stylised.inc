@@ -1,8 +1,8 @@
 // cda_stylised.inc - the stylised-facts report (include/cda.h cda_quote_returns, cda_tape_signs, cda_tape_flow_returns): the time-series statistics of one
 // remembered episode - return autocovariances and a return histogram from the quote tape, order-flow sign autocovariances from the trade tape, and signed volume
-// joined to returns bar by bar from both.  Included behind cda_quotes.inc (quote_span, quote_slot, quote_wave_sum) and cda_tape.inc (tape_span); stylised.py states
-// every word in numpy.  All three kernels are READERS: one wave per market, exact integers, every output word additive, nothing atomic on global memory.
-//
+// joined to returns bar by bar from both.  Included behind cda_quotes.inc (quote_span, quote_slot, the quote accessors) and cda_tape.inc (tape_span, the tape
+// accessors; wave_sum: cda_wave.hpp); stylised.py states every word in numpy.  All three kernels are READERS: one wave per market, exact integers, every output
+// word additive, nothing atomic on global memory.
 // k_quote_returns, k_tape_flow_returns.  A wave first STAGES the episode's bar points in its own slice of dynamic LDS: m2[p] of point p (step p * bar_steps), 0 =
 // not two-sided (a two-sided m2 is at least 2) - one 16-byte load per point, the only pass over the quote ring, whatever the number of lags.  The joined kernel
 // also walks the tape once, 64 fills per pass, and adds every fill's signed quantity to its bar's word Q[b] beside the points (LDS integer adds: their order cannot
@@ -37,7 +37,7 @@ __device__ __forceinline__ StylPoints styl_points(const QuoteSpan& sp, int bar, 
 __device__ __forceinline__ void styl_stage(int32_t* m2, const uint4* qring, const QuoteSpan& sp, uint32_t cap, int bar, StylPoints pt, int lane) {
     for (int p = pt.lo + lane; p <= pt.hi; p += WAVE) {
         const uint4 r0 = qring[2 * (size_t)quote_slot(sp, cap, p * bar - sp.step0)];
-        m2[p] = (r0.y & 3u) == 3u ? (int32_t)r0.z + (int32_t)r0.w : 0;
+        m2[p] = quote_two_sided(r0) ? quote_m2_i32(r0) : 0;
     }
 }
 // r_p = m2[p + 1] - m2[p]; defined iff both points are held and two-sided
@@ -54,7 +54,7 @@ __device__ __forceinline__ long long styl_abs(long long v) { return v < 0 ? -v :
 __global__ __launch_bounds__(64 * CDA_WPB) void k_quote_returns(const uint8_t* arena, Params P, QuoteArgs Q, int first, int n, int which, int bar, int nl, StylLags lg,
                                                                 int hh, int cap_pts, long long* base_out, long long* lag_out, long long* hist_out, int32_t* info) {
     extern __shared__ __align__(16) int32_t styl_lds[];               // per wave: cap_pts points, 2 hh + 1 bins
-    const int wib = (int)(threadIdx.x >> 6), w = (int)blockIdx.x * (int)(blockDim.x >> 6) + wib, lane = (int)(threadIdx.x & 63);
+    READER_WAVE_IN_GROUP((int)(blockDim.x >> 6));
     const bool live = w < n;
     const int nb = 2 * hh + 1;
     int32_t* m2 = styl_lds + (size_t)wib * (size_t)(cap_pts + nb);
@@ -99,8 +99,8 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_quote_returns(const uint8_t* a
     __syncthreads();
     if (!live) return;
     const long long held = pt.hi >= pt.lo ? (long long)(pt.hi - pt.lo + 1) : 0ll;
-    const long long t_ret = quote_wave_sum((long long)c_ret), t_miss = quote_wave_sum((long long)c_miss), t_up = quote_wave_sum((long long)c_up),
-                    t_down = quote_wave_sum((long long)c_down), t_r = quote_wave_sum(s_r), t_abs = quote_wave_sum(s_abs), t_r2 = quote_wave_sum(s_r2);
+    const long long t_ret = wave_sum((long long)c_ret), t_miss = wave_sum((long long)c_miss), t_up = wave_sum((long long)c_up),
+                    t_down = wave_sum((long long)c_down), t_r = wave_sum(s_r), t_abs = wave_sum(s_abs), t_r2 = wave_sum(s_r2);
     if (lane < RT_WORDS) {
         const long long v = lane == RT_BARS ? held : lane == RT_RETURNS ? t_ret : lane == RT_MISSING ? t_miss : lane == RT_SUM_R ? t_r : lane == RT_SUM_ABS ? t_abs :
                             lane == RT_SUM_R2 ? t_r2 : lane == RT_UP ? t_up : t_down;
@@ -111,11 +111,11 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_quote_returns(const uint8_t* a
     for (int h = 0; h < CDA_STYL_MAX_LAGS; h++) {
         if (h >= nl) break;
 #pragma unroll
-        for (int j = 0; j < RT_LAG_WORDS; j++) { const long long s = quote_wave_sum(acc[h][j]); if (lane == h * RT_LAG_WORDS + j) v = s; }
+        for (int j = 0; j < RT_LAG_WORDS; j++) { const long long s = wave_sum(acc[h][j]); if (lane == h * RT_LAG_WORDS + j) v = s; }
     }
     if (lane < nl * RT_LAG_WORDS) lag_out[(size_t)w * (size_t)(nl * RT_LAG_WORDS) + lane] = v;
     for (int i = lane; i < nb; i += WAVE) hist_out[(size_t)w * (size_t)nb + i] = (long long)bins[i];
-    if (info && lane == 0) { int32_t* o = info + 4 * (size_t)w; o[0] = sp.count; o[1] = sp.lost; o[2] = sp.step0; o[3] = sp.partial; }
+    if (info && lane == 0) reader_info(info, w, sp.count, sp.lost, sp.step0, sp.partial);
 }
 
 // what a partner needs of a fill: its quantity and its sides_step word (bit 1: the initiator's side, bits 2..: the step); self = counter_id == init_id
@@ -125,13 +125,13 @@ __device__ __forceinline__ SignFill sign_fill(const uint4* ring, uint32_t mask, 
     if (idx < count) {
         const uint32_t slot = (s0 + (uint32_t)idx) & mask;
         const uint4 r0 = ring[2 * (size_t)slot], r1 = ring[2 * (size_t)slot + 1];
-        x.q = (int32_t)r0.z; x.w = r1.w; x.self = r0.w == r1.z ? 1 : 0;
+        x.q = tape_qty(r0); x.w = r1.w; x.self = tape_self(r0, r1) ? 1 : 0;
     }
     return x;
 }
 __global__ __launch_bounds__(64 * CDA_WPB) void k_tape_signs(TapeArgs T, int first, int n, int which, int nl, StylLags lg, long long* base_out, long long* lag_out,
                                                              int32_t* info) {
-    BOOK_WAVE_OF_LAUNCH();
+    READER_WAVE();
     if (w >= n) return;
     const int mi = first + w;
     const TapeSpan sp = tape_span(T.meta[mi], T.cap, which);
@@ -147,8 +147,8 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_tape_signs(TapeArgs T, int fir
         const SignFill nxt = sign_fill(ring, mask, s0, base + WAVE + lane, sp.count);
         const long long idx = base + lane;
         const bool in = idx < sp.count;
-        const int s = (cur.w & 2u) ? -1 : 1;
-        const uint32_t step = cur.w >> 2;
+        const int s = tape_init_sells(cur.w) ? -1 : 1;
+        const uint32_t step = tape_stepw(cur.w);
         const long long sq = (long long)s * (long long)cur.q;
         int p_sign = __shfl_up(s, 1);
         uint32_t p_step = __shfl_up(step, 1);
@@ -170,17 +170,17 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_tape_signs(TapeArgs T, int fir
                 pq = src < WAVE ? qa : qb; pw = src < WAVE ? wa : wb;
             } else if (pair) {
                 const uint32_t slot = (s0 + (uint32_t)(idx + (long long)l)) & mask;
-                pq = (int32_t)ring[2 * (size_t)slot].z; pw = ring[2 * (size_t)slot + 1].w;
+                pq = tape_qty(ring[2 * (size_t)slot]); pw = ring[2 * (size_t)slot + 1].w;
             }
             if (!pair) continue;
-            const int ps = (pw & 2u) ? -1 : 1;
-            acc[h][0] += 1; acc[h][1] += (long long)(s * ps); acc[h][2] += sq * ((long long)ps * (long long)pq); acc[h][3] += (pw >> 2) == step ? 1 : 0;
+            const int ps = tape_init_sells(pw) ? -1 : 1;
+            acc[h][0] += 1; acc[h][1] += (long long)(s * ps); acc[h][2] += sq * ((long long)ps * (long long)pq); acc[h][3] += tape_stepw(pw) == step ? 1 : 0;
         }
         k_sign = __shfl(s, 63); k_step = __shfl(step, 63);
         cur = nxt;
     }
-    const long long t_buys = quote_wave_sum((long long)c_buys), t_sells = quote_wave_sum((long long)c_sells), t_self = quote_wave_sum((long long)c_self),
-                    t_runs = quote_wave_sum((long long)c_runs), t_steps = quote_wave_sum((long long)c_steps), t_bq = quote_wave_sum(s_bq), t_sq = quote_wave_sum(s_sq);
+    const long long t_buys = wave_sum((long long)c_buys), t_sells = wave_sum((long long)c_sells), t_self = wave_sum((long long)c_self),
+                    t_runs = wave_sum((long long)c_runs), t_steps = wave_sum((long long)c_steps), t_bq = wave_sum(s_bq), t_sq = wave_sum(s_sq);
     if (lane < SG_WORDS) {
         const long long v = lane == SG_FILLS ? sp.count : lane == SG_BUYS ? t_buys : lane == SG_SELLS ? t_sells : lane == SG_BUY_QTY ? t_bq : lane == SG_SELL_QTY ? t_sq :
                             lane == SG_SELF ? t_self : lane == SG_RUNS ? t_runs : t_steps;
@@ -191,16 +191,16 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_tape_signs(TapeArgs T, int fir
     for (int h = 0; h < CDA_STYL_MAX_LAGS; h++) {
         if (h >= nl) break;
 #pragma unroll
-        for (int j = 0; j < SG_LAG_WORDS; j++) { const long long s = quote_wave_sum(acc[h][j]); if (lane == h * SG_LAG_WORDS + j) v = s; }
+        for (int j = 0; j < SG_LAG_WORDS; j++) { const long long s = wave_sum(acc[h][j]); if (lane == h * SG_LAG_WORDS + j) v = s; }
     }
     if (lane < nl * SG_LAG_WORDS) lag_out[(size_t)w * (size_t)(nl * SG_LAG_WORDS) + lane] = v;
-    if (info && lane == 0) { int32_t* o = info + 4 * (size_t)w; o[0] = (int32_t)sp.count; o[1] = (int32_t)sp.lost; o[2] = 0; o[3] = (int32_t)sp.partial; }
+    if (info && lane == 0) reader_info(info, w, (int32_t)sp.count, (int32_t)sp.lost, 0, (int32_t)sp.partial);
 }
 
 __global__ __launch_bounds__(64 * CDA_WPB) void k_tape_flow_returns(const uint8_t* arena, Params P, TapeArgs T, QuoteArgs Q, int first, int n, int which, int bar, int nl,
                                                                     StylLags lg, int cap_pts, long long* lag_out, long long* base_out, int32_t* info) {
     extern __shared__ __align__(16) int32_t styl_flow_lds[];          // per wave: cap_pts points, cap_pts bars
-    const int wib = (int)(threadIdx.x >> 6), w = (int)blockIdx.x * (int)(blockDim.x >> 6) + wib, lane = (int)(threadIdx.x & 63);
+    READER_WAVE_IN_GROUP((int)(blockDim.x >> 6));
     const bool live = w < n;
     int32_t* m2 = styl_flow_lds + (size_t)wib * (size_t)(2 * cap_pts);
     int32_t* qbar = m2 + cap_pts;
@@ -223,17 +223,17 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_tape_flow_returns(const uint8_
     long long s_qty = 0;
     if (live) {
         if (ts.lost > 0) {
-            if (ts.count > 0) b_first = (long long)((tring[2 * (size_t)t0 + 1].w >> 2) / (uint32_t)bar) + 1;
+            if (ts.count > 0) b_first = (long long)(tape_step(tring[2 * (size_t)t0 + 1]) / (uint32_t)bar) + 1;
             else b_first = qs.count > 0 ? (long long)((qs.step0 + qs.count - 1) / bar) + 1 : 0ll;
         }
         uint32_t k_bar = 0xffffffffu;                                 // the carry: the bar of the last fill of the pass before (no bar has this index)
         for (long long base = 0; base < ts.count; base += WAVE) {
             const bool in = base + lane < ts.count;
-            uint4 r0 = make_uint4(0u, 0u, 0u, 0u), r1 = r0;
-            if (in) { const uint32_t slot = (t0 + (uint32_t)(base + lane)) & tmask; r0 = tring[2 * (size_t)slot]; r1 = tring[2 * (size_t)slot + 1]; }
-            const uint32_t b = (r1.w >> 2) / (uint32_t)bar;
-            const int32_t qty = (int32_t)r0.z;
-            if (in && b < (uint32_t)cap_pts) atomicAdd(qbar + b, (r1.w & 2u) ? -qty : qty);
+            uint4 r0, r1;
+            tape_load(tring, tmask, t0, base + lane, in, r0, r1);
+            const uint32_t b = tape_step(r1) / (uint32_t)bar;
+            const int32_t qty = tape_qty(r0);
+            if (in && b < (uint32_t)cap_pts) atomicAdd(qbar + b, tape_init_sells(r1.w) ? -qty : qty);
             uint32_t p_bar = __shfl_up(b, 1);
             if (lane == 0) p_bar = k_bar;
             const bool kept = in && (long long)b >= b_first;
@@ -256,20 +256,17 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_tape_flow_returns(const uint8_
             acc[h][0] += 1; acc[h][1] += q; acc[h][2] += r; acc[h][3] += q * r; acc[h][4] += q * q; acc[h][5] += r * r;
         }
     }
-    const long long t_fills = quote_wave_sum((long long)c_fills), t_bars = quote_wave_sum((long long)c_bars), t_qty = quote_wave_sum(s_qty);
+    const long long t_fills = wave_sum((long long)c_fills), t_bars = wave_sum((long long)c_bars), t_qty = wave_sum(s_qty);
     if (lane < FR_WORDS) base_out[(size_t)w * FR_WORDS + lane] = lane == FR_FILLS ? t_fills : lane == FR_BARS_WITH_FILLS ? t_bars : lane == FR_BARS_EXCLUDED ? b_first : t_qty;
     long long v = 0;
 #pragma unroll
     for (int h = 0; h < CDA_STYL_MAX_LAGS; h++) {
         if (h >= nl) break;
 #pragma unroll
-        for (int j = 0; j < FR_LAG_WORDS; j++) { const long long s = quote_wave_sum(acc[h][j]); if (lane == h * FR_LAG_WORDS + j) v = s; }
+        for (int j = 0; j < FR_LAG_WORDS; j++) { const long long s = wave_sum(acc[h][j]); if (lane == h * FR_LAG_WORDS + j) v = s; }
     }
     if (lane < nl * FR_LAG_WORDS) lag_out[(size_t)w * (size_t)(nl * FR_LAG_WORDS) + lane] = v;
-    if (info && lane == 0) {
-        int32_t* o = info + 4 * (size_t)w;
-        o[0] = (int32_t)ts.count; o[1] = (int32_t)ts.lost; o[2] = (int32_t)qs.lost; o[3] = (int32_t)(ts.partial | (qs.partial << 1));
-    }
+    if (info && lane == 0) reader_info(info, w, (int32_t)ts.count, (int32_t)ts.lost, (int32_t)qs.lost, (int32_t)(ts.partial | (qs.partial << 1)));
 }
 
 // the longest episode of the range: its rows' largest max_step
@@ -305,51 +302,44 @@ int cda_stylised_check_host(int32_t kind, const int32_t* lags_host, int32_t n_la
 
 int cda_quote_returns(cda_env* e, int32_t first_market, int32_t n_markets, int32_t which, const int32_t* lags_host, int32_t n_lags, int32_t bar_steps, int32_t hist_half,
                       int64_t* base_out_dev, int64_t* lagged_out_dev, int64_t* hist_out_dev, int32_t* info_out_dev, void* stream) {
-    if (!e || !base_out_dev || !lagged_out_dev || !hist_out_dev || !QUOTE_WHICH_OK(which) || !range_ok(e, first_market, n_markets) ||
-        (((uintptr_t)base_out_dev | (uintptr_t)lagged_out_dev | (uintptr_t)hist_out_dev) & 7) != 0 || ((uintptr_t)info_out_dev & 3) != 0) return CDA_ERR_INVALID;
+    if (!reader_args_ok(e, base_out_dev, first_market, n_markets) || !lagged_out_dev || !hist_out_dev || !which_ok(which) || !aligned(base_out_dev, 8) ||
+        !aligned(lagged_out_dev, 8) || !aligned(hist_out_dev, 8) || !aligned(info_out_dev, 4) || !range_ok(e, first_market, n_markets)) return CDA_ERR_INVALID;
     const int32_t top = styl_range_top(e, first_market, n_markets);
     if (cda_stylised_check_host(CDA_STYL_RETURNS, lags_host, n_lags, bar_steps, hist_half, top) != CDA_OK) return CDA_ERR_INVALID;
     if (!e->quotes.ring) return CDA_ERR_UNSUPPORTED;
     const StylLags lg = styl_lags(lags_host, n_lags);
     const int64_t pts = ((int64_t)top + (int64_t)bar_steps - 1) / (int64_t)bar_steps;      // <= CDA_STYL_MAX_BARS
-    HIPCHK(hipSetDevice(e->device));
     const size_t per_wave = ((size_t)pts + 2 * (size_t)hist_half + 1) * sizeof(int32_t);
     const int waves = styl_waves(per_wave);
-    hipLaunchKernelGGL(k_quote_returns, dim3((unsigned)((n_markets + waves - 1) / waves)), dim3(64 * waves), per_wave * (size_t)waves, (hipStream_t)stream,
-                       (const uint8_t*)e->arena, e->P, e->quotes, (int)first_market, (int)n_markets, (int)which, (int)bar_steps, (int)n_lags, lg, (int)hist_half, (int)pts,
-                       (long long*)base_out_dev, (long long*)lagged_out_dev, (long long*)hist_out_dev, info_out_dev);
-    return launch_status();
+    return reader_launch(e, k_quote_returns, n_markets, waves, per_wave * (size_t)waves, stream, (const uint8_t*)e->arena, e->P, e->quotes, (int)first_market, (int)n_markets,
+                         (int)which, (int)bar_steps, (int)n_lags, lg, (int)hist_half, (int)pts, (long long*)base_out_dev, (long long*)lagged_out_dev, (long long*)hist_out_dev,
+                         info_out_dev);
 }
 
 int cda_tape_signs(cda_env* e, int32_t first_market, int32_t n_markets, int32_t which, const int32_t* lags_host, int32_t n_lags, int64_t* base_out_dev,
                    int64_t* lagged_out_dev, int32_t* info_out_dev, void* stream) {
-    if (!e || !base_out_dev || !lagged_out_dev || !QUOTE_WHICH_OK(which) || !range_ok(e, first_market, n_markets) ||
-        (((uintptr_t)base_out_dev | (uintptr_t)lagged_out_dev) & 7) != 0 || ((uintptr_t)info_out_dev & 3) != 0) return CDA_ERR_INVALID;
+    if (!reader_args_ok(e, base_out_dev, first_market, n_markets) || !lagged_out_dev || !which_ok(which) || !aligned(base_out_dev, 8) || !aligned(lagged_out_dev, 8) ||
+        !aligned(info_out_dev, 4) || !range_ok(e, first_market, n_markets)) return CDA_ERR_INVALID;
     if (cda_stylised_check_host(CDA_STYL_SIGNS, lags_host, n_lags, 1, 1, 1) != CDA_OK) return CDA_ERR_INVALID;
     if (!e->tape.ring) return CDA_ERR_UNSUPPORTED;
     const StylLags lg = styl_lags(lags_host, n_lags);
-    HIPCHK(hipSetDevice(e->device));
-    hipLaunchKernelGGL(k_tape_signs, quote_grid(n_markets), dim3(64 * CDA_WPB), 0, (hipStream_t)stream, e->tape, (int)first_market, (int)n_markets, (int)which, (int)n_lags, lg,
-                       (long long*)base_out_dev, (long long*)lagged_out_dev, info_out_dev);
-    return launch_status();
+    return reader_launch(e, k_tape_signs, n_markets, CDA_WPB, 0, stream, e->tape, (int)first_market, (int)n_markets, (int)which, (int)n_lags, lg, (long long*)base_out_dev,
+                         (long long*)lagged_out_dev, info_out_dev);
 }
 
 int cda_tape_flow_returns(cda_env* e, int32_t first_market, int32_t n_markets, int32_t which, const int32_t* lags_host, int32_t n_lags, int32_t bar_steps,
                           int64_t* lagged_out_dev, int64_t* base_out_dev, int32_t* info_out_dev, void* stream) {
-    if (!e || !base_out_dev || !lagged_out_dev || !QUOTE_WHICH_OK(which) || !range_ok(e, first_market, n_markets) ||
-        (((uintptr_t)base_out_dev | (uintptr_t)lagged_out_dev) & 7) != 0 || ((uintptr_t)info_out_dev & 3) != 0) return CDA_ERR_INVALID;
+    if (!reader_args_ok(e, base_out_dev, first_market, n_markets) || !lagged_out_dev || !which_ok(which) || !aligned(base_out_dev, 8) || !aligned(lagged_out_dev, 8) ||
+        !aligned(info_out_dev, 4) || !range_ok(e, first_market, n_markets)) return CDA_ERR_INVALID;
     const int32_t top = styl_range_top(e, first_market, n_markets);
     if (cda_stylised_check_host(CDA_STYL_FLOW_RETURNS, lags_host, n_lags, bar_steps, 1, top) != CDA_OK) return CDA_ERR_INVALID;
     if (!e->tape.ring || !e->quotes.ring) return CDA_ERR_UNSUPPORTED;
     const StylLags lg = styl_lags(lags_host, n_lags);
     const int64_t pts = ((int64_t)top + (int64_t)bar_steps - 1) / (int64_t)bar_steps;      // <= CDA_STYL_MAX_BARS
-    HIPCHK(hipSetDevice(e->device));
     const size_t per_wave = 2 * (size_t)pts * sizeof(int32_t);
     const int waves = styl_waves(per_wave);
-    hipLaunchKernelGGL(k_tape_flow_returns, dim3((unsigned)((n_markets + waves - 1) / waves)), dim3(64 * waves), per_wave * (size_t)waves, (hipStream_t)stream,
-                       (const uint8_t*)e->arena, e->P, e->tape, e->quotes, (int)first_market, (int)n_markets, (int)which, (int)bar_steps, (int)n_lags, lg, (int)pts,
-                       (long long*)lagged_out_dev, (long long*)base_out_dev, info_out_dev);
-    return launch_status();
+    return reader_launch(e, k_tape_flow_returns, n_markets, waves, per_wave * (size_t)waves, stream, (const uint8_t*)e->arena, e->P, e->tape, e->quotes, (int)first_market,
+                         (int)n_markets, (int)which, (int)bar_steps, (int)n_lags, lg, (int)pts, (long long*)lagged_out_dev, (long long*)base_out_dev, info_out_dev);
 }
 
 }  // extern "C"

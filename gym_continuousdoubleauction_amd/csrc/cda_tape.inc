@@ -1,4 +1,5 @@
-// cda_tape.inc - the trade tape's storage and read-out (include/cda.h cda_tape_*), included at the end of cda_hip.hip.
+// cda_tape.inc - the trade tape's storage and read-out (include/cda.h cda_tape_*), included at the end of cda_hip.hip (the wave toolkit: cda_wave.hpp, ahead of
+// every .inc).  The record's layout as the readers see it - tape_load and the tape_* accessors - stands beside TapeSpan below.
 //
 // The reference's order book keeps OrderBook.tape: one transaction_record per fill (orderbook.py:108-140).  Here a market's tape is a ring of
 // `capacity` records (CDA_TAPE_WORDS int32 each, cda_tape_record) in a buffer of its own, beside the arena: neither the market record, nor the state
@@ -85,14 +86,14 @@ __device__ __forceinline__ void tape_copy(uint4* dst, const uint4* ring, uint32_
 }
 // pack: wave k <- market first + k; a market whose run does not fit below out_records is left alone (its cursor too)
 __global__ __launch_bounds__(64 * CDA_WPB) void k_tape_pack(TapeArgs T, int first, int n, long long* cursor, const long long* off, uint4* out, long long out_records) {
-    const int k = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = (int)(threadIdx.x & 63);
-    if (k >= n) return;
-    const int mi = first + k;
-    const TapeRun r = tape_run(T.meta, T.cap, mi, cursor[k]);
-    const long long o = off[k];
-    if (o < 0 || o + r.count > out_records || off[k + 1] - o != r.count) return;
+    READER_WAVE();
+    if (w >= n) return;
+    const int mi = first + w;
+    const TapeRun r = tape_run(T.meta, T.cap, mi, cursor[w]);
+    const long long o = off[w];
+    if (o < 0 || o + r.count > out_records || off[w + 1] - o != r.count) return;
     tape_copy(out + 2 * o, T.ring + (size_t)mi * (size_t)T.cap * 2, T.cap, r.start, r.count, lane);
-    if (lane == 0) cursor[k] = r.start + r.count;
+    if (lane == 0) cursor[w] = r.start + r.count;
 }
 // One of the two episodes a market remembers, in record numbers: the current one is [n_total - n_episode, n_total), the previous one (the episode that ended at
 // the market's last reset) the n_prev records before it; `start` / `count`: what the ring still holds of it (the ring keeps [n_total - cap, n_total)), `lost`: the
@@ -110,9 +111,34 @@ __device__ __forceinline__ TapeSpan tape_span(const TapeMeta& h, uint32_t cap, i
     s.start = floor; s.count = hi - floor; s.lost = floor - lo; s.partial = which == CDA_TAPE_PREVIOUS ? h.prev_partial : h.partial;
     return s;
 }
+// THE LAYOUT OF A RECORD, as the readers see it: two 16-byte words r0, r1 of the ring = cda_tape_record (include/cda.h).  The writer is match<.., TAPE = true>
+// (cda_book.inc); every reader decodes through the accessors below and nowhere else.  They are MACROS on purpose: an inlined function hands the optimiser facts
+// about its result (value ranges, noundef) that the hand-written decoders never had, and six reader kernels then compiled to other code than their parent's;
+// as text substitution every reader is instruction for instruction what it was (profiles/readers/identity.txt).  Being macros, they may evaluate an argument
+// more than once, and tape_load ASSIGNS to its last two arguments: pass plain variables (r0, r1, a ring element), never an expression with side effects.
+static_assert(offsetof(cda_tape_record, price) == 4 && offsetof(cda_tape_record, quantity) == 8 && offsetof(cda_tape_record, counter_id) == 12,
+              "r0 = (time, price, quantity, counter_id)");
+static_assert(offsetof(cda_tape_record, init_id) == 24 && offsetof(cda_tape_record, sides_step) == 28, "r1 = (counter_order_id, counter_left, init_id, sides_step)");
+// Sides: 0 = bid (bought), 1 = ask (sold); counter_id: the resting order's trader (maker), init_id: the incoming order's (taker); a self-trade has both equal.
+#define tape_price(r0) ((int32_t)(r0).y)
+#define tape_qty(r0) ((int32_t)(r0).z)
+#define tape_counter_id(r0) ((r0).w)
+#define tape_init_id(r1) ((r1).z)
+#define tape_self(r0, r1) ((r0).w == (r1).z)
+#define tape_counter_side(r1) ((int)((r1).w & 1u))
+#define tape_init_side(r1) ((int)(((r1).w >> 1) & 1u))
+#define tape_step(r1) ((r1).w >> 2)
+// ... and of the raw sides_step word (r1.w), for a kernel that keeps the word itself (k_tape_signs)
+#define tape_stepw(w) ((w) >> 2)
+#define tape_init_sells(w) (((w) & 2u) != 0u)
+// r0, r1 <- record s0 + idx of the ring (slot masked: the run wraps where the ring does); a lane without a record (`in` false) gets zeros
+#define tape_load(ring, mask, s0, idx, in, r0, r1) do { \
+        r0 = make_uint4(0u, 0u, 0u, 0u); r1 = r0; \
+        if (in) { const uint32_t slot_ = ((s0) + (uint32_t)(idx)) & (mask); r0 = (ring)[2 * (size_t)slot_]; r1 = (ring)[2 * (size_t)slot_ + 1]; } \
+    } while (0)
 // the last k records of the current (or the previous) episode, oldest first; rows beyond the count are zero
 __global__ __launch_bounds__(64 * CDA_WPB) void k_tape_last(TapeArgs T, int first, int n, int which, int kmax, uint4* out, int32_t* counts) {
-    const int w = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = (int)(threadIdx.x & 63);
+    READER_WAVE();
     if (w >= n) return;
     const int mi = first + w;
     const TapeMeta h = T.meta[mi];
@@ -182,21 +208,17 @@ int cda_tape_offsets(cda_env* e, int32_t first_market, int32_t n_markets, const 
 }
 int cda_tape_pack(cda_env* e, int32_t first_market, int32_t n_markets, int64_t* cursor_dev, const int64_t* offsets_dev, void* records_out_dev, int64_t capacity_records,
                   void* stream) {
-    if (!e || !cursor_dev || !offsets_dev || capacity_records < 0 || (capacity_records > 0 && !records_out_dev) || !range_ok(e, first_market, n_markets)) return CDA_ERR_INVALID;
-    if (((uintptr_t)records_out_dev & 15) != 0) return CDA_ERR_INVALID;
+    if (!reader_args_ok(e, cursor_dev, first_market, n_markets) || !offsets_dev || capacity_records < 0 || (capacity_records > 0 && !records_out_dev) ||
+        !aligned(records_out_dev, 16) || !range_ok(e, first_market, n_markets)) return CDA_ERR_INVALID;
     if (!e->tape.ring) return CDA_ERR_UNSUPPORTED;
-    HIPCHK(hipSetDevice(e->device));
-    hipLaunchKernelGGL(k_tape_pack, dim3((unsigned)((n_markets + CDA_WPB - 1) / CDA_WPB)), dim3(64 * CDA_WPB), 0, (hipStream_t)stream, e->tape, (int)first_market, (int)n_markets,
-                       (long long*)cursor_dev, (const long long*)offsets_dev, (uint4*)records_out_dev, (long long)capacity_records);
-    return launch_status();
+    return reader_launch(e, k_tape_pack, n_markets, CDA_WPB, 0, stream, e->tape, (int)first_market, (int)n_markets, (long long*)cursor_dev, (const long long*)offsets_dev,
+                         (uint4*)records_out_dev, (long long)capacity_records);
 }
 int cda_tape_last_of(cda_env* e, int32_t first_market, int32_t n_markets, int32_t which, int32_t k, void* records_out_dev, int32_t* counts_out_dev, void* stream) {
-    if (!e || !records_out_dev || k < 1 || (which != CDA_TAPE_CURRENT && which != CDA_TAPE_PREVIOUS) || !range_ok(e, first_market, n_markets) || ((uintptr_t)records_out_dev & 15) != 0) return CDA_ERR_INVALID;
+    if (!reader_args_ok(e, records_out_dev, first_market, n_markets) || k < 1 || !which_ok(which) || !aligned(records_out_dev, 16) ||
+        !range_ok(e, first_market, n_markets)) return CDA_ERR_INVALID;
     if (!e->tape.ring) return CDA_ERR_UNSUPPORTED;
-    HIPCHK(hipSetDevice(e->device));
-    hipLaunchKernelGGL(k_tape_last, dim3((unsigned)((n_markets + CDA_WPB - 1) / CDA_WPB)), dim3(64 * CDA_WPB), 0, (hipStream_t)stream, e->tape, (int)first_market, (int)n_markets,
-                       (int)which, (int)k, (uint4*)records_out_dev, counts_out_dev);
-    return launch_status();
+    return reader_launch(e, k_tape_last, n_markets, CDA_WPB, 0, stream, e->tape, (int)first_market, (int)n_markets, (int)which, (int)k, (uint4*)records_out_dev, counts_out_dev);
 }
 int cda_tape_last(cda_env* e, int32_t first_market, int32_t n_markets, int32_t k, void* records_out_dev, int32_t* counts_out_dev, void* stream) {
     return cda_tape_last_of(e, first_market, n_markets, CDA_TAPE_CURRENT, k, records_out_dev, counts_out_dev, stream);

@@ -1,7 +1,7 @@
 // cda_tape_bars.inc - reductions over the records of one remembered episode of the trade tape (include/cda.h cda_tape_bars, cda_tape_flows), included behind
-// cda_tape.inc.  Both kernels are READERS: one wave per market (CDA_WPB markets per workgroup, as k_tape_pack), lanes over records, 64 records per pass, two
-// 16-byte loads per record along the ring (the slot is masked: the run wraps where the ring does).  Only the market's own wave writes the market's rows, each
-// row once: no atomics on global memory, nothing depends on scheduling.
+// cda_tape.inc (tape_span, tape_load; the wave toolkit: cda_wave.hpp).  Both kernels are READERS: one wave per market (CDA_WPB markets per workgroup, as
+// k_tape_pack), lanes over records, 64 records per pass, two 16-byte loads per record along the ring (the slot is masked: the run wraps where the ring does).
+// Only the market's own wave writes the market's rows, each row once: no atomics on global memory, nothing depends on scheduling.
 //
 // k_tape_bars.  Within an episode the step index never decreases, so the records of a bar are one run.  Per pass: the bar index of every lane's record, head
 // flags from the left neighbour's bar index (__ballot), a segmented inclusive scan over the lanes (__shfl_up, six steps: max / min / sums), after which the last
@@ -41,7 +41,7 @@ __device__ __forceinline__ BarAcc bar_from_lane(const BarAcc& a, int l) {
 }
 
 __global__ __launch_bounds__(64 * CDA_WPB) void k_tape_bars(TapeArgs T, int first, int n, int which, int bar_steps, int n_bars, uint4* out, int32_t* info) {
-    const int w = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = (int)(threadIdx.x & 63);
+    READER_WAVE();
     if (w >= n) return;
     const int mi = first + w;
     const TapeSpan sp = tape_span(T.meta[mi], T.cap, which);
@@ -55,12 +55,9 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_tape_bars(TapeArgs T, int firs
     int beyond = 0;
     for (long long base = 0; base < sp.count; base += WAVE) {
         const bool in = base + lane < sp.count;
-        uint4 r0 = zero, r1 = zero;
-        if (in) {
-            const uint32_t slot = (s0 + (uint32_t)(base + lane)) & mask;
-            r0 = ring[2 * (size_t)slot]; r1 = ring[2 * (size_t)slot + 1];
-        }
-        const uint32_t b = (r1.w >> 2) / (uint32_t)bar_steps;
+        uint4 r0, r1;
+        tape_load(ring, mask, s0, base + lane, in, r0, r1);
+        const uint32_t b = tape_step(r1) / (uint32_t)bar_steps;
         const bool valid = in && b < (uint32_t)n_bars;
         const int key = valid ? (int)b : NONE;
         const unsigned long long vmask = __ballot(valid);
@@ -69,12 +66,12 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_tape_bars(TapeArgs T, int firs
         const int lv = 63 - __clzll((long long)vmask);                // the pass's last aggregated record: its run is carried
         const int pk = __shfl_up(key, 1);
         const unsigned long long heads = __ballot(lane == 0 || key != pk);
-        const int seg = 63 - __clzll((long long)(heads & (~0ull >> (63 - lane))));      // first lane of this lane's run
+        const int seg = 63 - __clzll((long long)(heads & lanes_le(lane)));      // first lane of this lane's run
         const bool tail = lane == 63 || ((heads >> ((lane + 1) & 63)) & 1ull) != 0;
-        const int price = (int)r0.y, qty = (int)r0.z;
+        const int price = tape_price(r0), qty = tape_qty(r0);
         BarAcc a;
-        a.open = a.high = a.low = a.close = price; a.n_trades = 1; a.n_self = r0.w == r1.z ? 1 : 0;
-        a.volume = (long long)qty; a.buy_volume = (r1.w & 2u) == 0u ? (long long)qty : 0ll; a.notional = (long long)price * (long long)qty;
+        a.open = a.high = a.low = a.close = price; a.n_trades = 1; a.n_self = tape_self(r0, r1) ? 1 : 0;
+        a.volume = (long long)qty; a.buy_volume = !tape_init_sells(r1.w) ? (long long)qty : 0ll; a.notional = (long long)price * (long long)qty;
 #pragma unroll
         for (int d = 1; d < WAVE; d <<= 1) {                          // segmented inclusive scan: lane l ends with the sum over [seg, l]
             BarAcc o = bar_shfl_up(a, d);
@@ -98,16 +95,13 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_tape_bars(TapeArgs T, int firs
     }
     if (last >= 0 && lane == 0) bar_store(rows + 3 * (size_t)last, carry);
     for (long long i = 3ll * ((long long)last + 1) + lane; i < 3ll * (long long)n_bars; i += WAVE) rows[i] = zero;
-    if (info && lane == 0) {
-        int32_t* o = info + 4 * (size_t)w;
-        o[0] = (int32_t)(sp.count - (long long)beyond); o[1] = (int32_t)sp.lost; o[2] = (int32_t)beyond; o[3] = (int32_t)sp.partial;
-    }
+    if (info && lane == 0) reader_info(info, w, (int32_t)(sp.count - (long long)beyond), (int32_t)sp.lost, (int32_t)beyond, (int32_t)sp.partial);
 }
 
 constexpr int FLOW_CELLS_MAX = CDA_MAX_AGENTS * CDA_MAX_AGENTS * 3;
 __global__ __launch_bounds__(64 * CDA_WPB) void k_tape_flows(TapeArgs T, int first, int n, int which, int agents, long long* out, int32_t* info) {
     __shared__ unsigned long long table[CDA_WPB][FLOW_CELLS_MAX];     // 6 KB per wave
-    const int wib = (int)(threadIdx.x >> 6), w = (int)blockIdx.x * CDA_WPB + wib, lane = (int)(threadIdx.x & 63);
+    READER_WAVE_IN_GROUP(CDA_WPB);
     const bool live = w < n;
     unsigned long long* t = table[wib];
     const int cells = agents * agents * 3;
@@ -123,15 +117,15 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_tape_flows(TapeArgs T, int fir
         for (long long base = 0; base < sp.count; base += WAVE) {
             bool ok = false;
             if (base + lane < sp.count) {
-                const uint32_t slot = (s0 + (uint32_t)(base + lane)) & mask;
-                const uint4 r0 = ring[2 * (size_t)slot], r1 = ring[2 * (size_t)slot + 1];
-                ok = r1.z < (uint32_t)agents && r0.w < (uint32_t)agents;                 // (ids outside the env's agents cannot index the table)
+                uint4 r0, r1;
+                tape_load(ring, mask, s0, base + lane, true, r0, r1);
+                ok = tape_init_id(r1) < (uint32_t)agents && tape_counter_id(r0) < (uint32_t)agents;    // (ids outside the env's agents cannot index the table)
                 if (ok) {
-                    unsigned long long* c = t + ((int)r1.z * agents + (int)r0.w) * 3;    // [init_id][counter_id]
-                    const long long price = (long long)(int)r0.y, qty = (long long)(int)r0.z;
-                    atomicAdd(c, (unsigned long long)qty);
-                    atomicAdd(c + 1, (unsigned long long)(price * qty));
-                    atomicAdd(c + 2, 1ull);
+                    unsigned long long* c = t + ((int)tape_init_id(r1) * agents + (int)tape_counter_id(r0)) * 3;       // [init_id][counter_id]
+                    const long long price = (long long)tape_price(r0), qty = (long long)tape_qty(r0);
+                    lds_add(c, qty);
+                    lds_add(c + 1, price * qty);
+                    lds_add(c + 2, 1ll);
                 }
             }
             used += __popcll(__ballot(ok));
@@ -141,33 +135,25 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_tape_flows(TapeArgs T, int fir
     if (!live) return;
     long long* dst = out + (size_t)w * (size_t)cells;
     for (int i = lane; i < cells; i += WAVE) dst[i] = (long long)t[i];
-    if (info && lane == 0) {
-        int32_t* o = info + 4 * (size_t)w;
-        o[0] = (int32_t)used; o[1] = (int32_t)sp.lost; o[2] = 0; o[3] = (int32_t)sp.partial;
-    }
+    if (info && lane == 0) reader_info(info, w, (int32_t)used, (int32_t)sp.lost, 0, (int32_t)sp.partial);
 }
 
 extern "C" {
 
 int cda_tape_bars(cda_env* e, int32_t first_market, int32_t n_markets, int32_t which, int32_t bar_steps, int32_t n_bars, void* bars_out_dev, int32_t* info_out_dev,
                   void* stream) {
-    if (!e || !bars_out_dev || bar_steps < 1 || n_bars < 1 || (which != CDA_TAPE_CURRENT && which != CDA_TAPE_PREVIOUS) || !range_ok(e, first_market, n_markets) ||
-        ((uintptr_t)bars_out_dev & 15) != 0) return CDA_ERR_INVALID;
+    if (!reader_args_ok(e, bars_out_dev, first_market, n_markets) || bar_steps < 1 || n_bars < 1 || !which_ok(which) || !aligned(bars_out_dev, 16) ||
+        !range_ok(e, first_market, n_markets)) return CDA_ERR_INVALID;
     if (!e->tape.ring) return CDA_ERR_UNSUPPORTED;
-    HIPCHK(hipSetDevice(e->device));
-    hipLaunchKernelGGL(k_tape_bars, dim3((unsigned)((n_markets + CDA_WPB - 1) / CDA_WPB)), dim3(64 * CDA_WPB), 0, (hipStream_t)stream, e->tape, (int)first_market, (int)n_markets,
-                       (int)which, (int)bar_steps, (int)n_bars, (uint4*)bars_out_dev, info_out_dev);
-    return launch_status();
+    return reader_launch(e, k_tape_bars, n_markets, CDA_WPB, 0, stream, e->tape, (int)first_market, (int)n_markets, (int)which, (int)bar_steps, (int)n_bars,
+                         (uint4*)bars_out_dev, info_out_dev);
 }
 int cda_tape_flows(cda_env* e, int32_t first_market, int32_t n_markets, int32_t which, int64_t* flows_out_dev, int32_t* info_out_dev, void* stream) {
-    if (!e || !flows_out_dev || (which != CDA_TAPE_CURRENT && which != CDA_TAPE_PREVIOUS) || !range_ok(e, first_market, n_markets) ||
-        ((uintptr_t)flows_out_dev & 7) != 0) return CDA_ERR_INVALID;
+    if (!reader_args_ok(e, flows_out_dev, first_market, n_markets) || !which_ok(which) || !aligned(flows_out_dev, 8) || !range_ok(e, first_market, n_markets)) return CDA_ERR_INVALID;
     if (!e->tape.ring) return CDA_ERR_UNSUPPORTED;
-    if (e->P.cfg.num_agents < 1 || e->P.cfg.num_agents > CDA_MAX_AGENTS) return CDA_ERR_INVALID;
-    HIPCHK(hipSetDevice(e->device));
-    hipLaunchKernelGGL(k_tape_flows, dim3((unsigned)((n_markets + CDA_WPB - 1) / CDA_WPB)), dim3(64 * CDA_WPB), 0, (hipStream_t)stream, e->tape, (int)first_market, (int)n_markets,
-                       (int)which, (int)e->P.cfg.num_agents, (long long*)flows_out_dev, info_out_dev);
-    return launch_status();
+    if (!agents_ok(e)) return CDA_ERR_INVALID;
+    return reader_launch(e, k_tape_flows, n_markets, CDA_WPB, 0, stream, e->tape, (int)first_market, (int)n_markets, (int)which, (int)e->P.cfg.num_agents,
+                         (long long*)flows_out_dev, info_out_dev);
 }
 
 }  // extern "C"

@@ -1,7 +1,8 @@
 // cda_tape_exec.inc - the execution report over the records of one remembered episode of the trade tape (include/cda.h cda_tape_exec), included behind
-// cda_tape_bars.inc.  A READER like the two kernels there: one wave per market (CDA_WPB markets per workgroup), lanes over records, 64 records per pass, the
-// slot masked along the ring.  Per market and agent it fills two tables of 64-bit integers, both accumulated in the wave's own slice of (dynamic) LDS and
-// written out once, dense: only the market's own wave writes the market's rows, no atomics on global memory, nothing depends on scheduling.
+// cda_tape.inc (tape_span, tape_load, tape_step; the wave toolkit: cda_wave.hpp).  A READER like the two kernels there: one wave per market (CDA_WPB markets per
+// workgroup), lanes over records, 64 records per pass, the slot masked along the ring.  Per market and agent it fills two tables of 64-bit integers, both
+// accumulated in the wave's own slice of (dynamic) LDS and written out once, dense: only the market's own wave writes the market's rows, no atomics on global
+// memory, nothing depends on scheduling.
 //
 //   stats    [A][CDA_TAPE_STAT_WORDS]  the additive words (quantities, notionals, fills by side and by role, self-trades) are LDS adds of the lanes' records:
 //                                       integer sums, their order cannot matter.  The PATH words need the agent's running position at every one of its fills:
@@ -23,19 +24,18 @@ struct ExecHorizons { int32_t k[CDA_TAPE_MAX_HORIZONS]; };
 constexpr int EXEC_HCHUNK = 4;                                        // horizons searched side by side
 constexpr int EXEC_AHEAD = 64;                                        // the first probe of a mark search
 
-__device__ __forceinline__ void exec_add(unsigned long long* p, long long v) { atomicAdd(p, (unsigned long long)v); }
 // one party of a fill: side 0 = bid (bought), 1 = ask (sold); role 0 = maker (counter_id), 1 = taker (init_id)
 __device__ __forceinline__ void exec_party(unsigned long long* row, int side, int role, long long qty, long long notional) {
-    exec_add(row + (side ? XS_SELL_QTY : XS_BUY_QTY), qty);
-    exec_add(row + (side ? XS_SELL_NOTIONAL : XS_BUY_NOTIONAL), notional);
-    exec_add(row + (role ? XS_TAKER_QTY : XS_MAKER_QTY), qty);
-    exec_add(row + (role ? XS_TAKER_FILLS : XS_MAKER_FILLS), 1ll);
+    lds_add(row + (side ? XS_SELL_QTY : XS_BUY_QTY), qty);
+    lds_add(row + (side ? XS_SELL_NOTIONAL : XS_BUY_NOTIONAL), notional);
+    lds_add(row + (role ? XS_TAKER_QTY : XS_MAKER_QTY), qty);
+    lds_add(row + (role ? XS_TAKER_FILLS : XS_MAKER_FILLS), 1ll);
 }
 
 __global__ __launch_bounds__(64 * CDA_WPB) void k_tape_exec(TapeArgs T, int first, int n, int which, int agents, int nh, ExecHorizons hz, long long* stats_out,
                                                             long long* marks_out, int32_t* info) {
     extern __shared__ __align__(16) unsigned long long exec_lds[];    // per wave: agents x 16 stat words, then agents x nh x 2 x 4 mark-out words
-    const int wib = (int)(threadIdx.x >> 6), w = (int)blockIdx.x * CDA_WPB + wib, lane = (int)(threadIdx.x & 63);
+    READER_WAVE_IN_GROUP(CDA_WPB);
     const bool live = w < n;
     const int n_stat = agents * CDA_TAPE_STAT_WORDS, n_mark = agents * nh * 8;
     unsigned long long* st = exec_lds + (size_t)wib * (size_t)(n_stat + n_mark);
@@ -51,22 +51,19 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_tape_exec(TapeArgs T, int firs
         const uint4* ring = T.ring + (size_t)mi * (size_t)T.cap * 2;
         const uint32_t mask = T.cap - 1u, s0 = (uint32_t)sp.start & mask;
         const int count = (int)sp.count;                             // <= cap <= CDA_TAPE_CAP_MAX
-        const uint32_t s_last = count > 0 ? ring[2 * (size_t)((s0 + (uint32_t)(count - 1)) & mask) + 1].w >> 2 : 0u;
+        const uint32_t s_last = count > 0 ? tape_step(ring[2 * (size_t)((s0 + (uint32_t)(count - 1)) & mask) + 1]) : 0u;
         for (int base = 0; base < count; base += WAVE) {
             const int idx = base + lane;
             const bool in = idx < count;
-            uint4 r0 = make_uint4(0u, 0u, 0u, 0u), r1 = r0;
-            if (in) {
-                const uint32_t slot = (s0 + (uint32_t)idx) & mask;
-                r0 = ring[2 * (size_t)slot]; r1 = ring[2 * (size_t)slot + 1];
-            }
-            const uint32_t cid = r0.w, iid = r1.z, step = r1.w >> 2;
-            const int cside = (int)(r1.w & 1u), iside = (int)((r1.w >> 1) & 1u);
-            const long long price = (long long)(int)r0.y, qty = (long long)(int)r0.z;
+            uint4 r0, r1;
+            tape_load(ring, mask, s0, idx, in, r0, r1);
+            const uint32_t cid = tape_counter_id(r0), iid = tape_init_id(r1), step = tape_step(r1);
+            const int cside = tape_counter_side(r1), iside = tape_init_side(r1);
+            const long long price = (long long)tape_price(r0), qty = (long long)tape_qty(r0);
             const bool ok = in && cid < (uint32_t)agents && iid < (uint32_t)agents;      // (ids outside the env's agents cannot index the tables)
             const bool ev = ok && cid != iid;                        // a fill that moves two positions
             used += __popcll(__ballot(ok));
-            if (ok && !ev) { exec_add(st + iid * 16 + XS_SELF_QTY, qty); exec_add(st + iid * 16 + XS_SELF_FILLS, 1ll); }
+            if (ok && !ev) { lds_add(st + iid * 16 + XS_SELF_QTY, qty); lds_add(st + iid * 16 + XS_SELF_FILLS, 1ll); }
             if (ev) {
                 exec_party(st + cid * 16, cside, 0, qty, price * qty);
                 exec_party(st + iid * 16, iside, 1, qty, price * qty);
@@ -84,7 +81,7 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_tape_exec(TapeArgs T, int firs
                     scored[j] = ev && h0 + j < nh && tt[j] <= s_last;
                     // the last record with step <= tt lies in [idx, count): one probe EXEC_AHEAD records on, then the halving
                     const int e = idx + EXEC_AHEAD < count ? idx + EXEC_AHEAD : count - 1;
-                    const uint32_t se = ring[2 * (size_t)((s0 + (uint32_t)(scored[j] ? e : idx)) & mask) + 1].w >> 2;
+                    const uint32_t se = tape_step(ring[2 * (size_t)((s0 + (uint32_t)(scored[j] ? e : idx)) & mask) + 1]);
                     lo[j] = idx; hi[j] = idx;
                     if (scored[j]) { if (se <= tt[j]) { lo[j] = e; hi[j] = count - 1; } else hi[j] = e - 1; }
                 }
@@ -93,7 +90,7 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_tape_exec(TapeArgs T, int firs
 #pragma unroll
                     for (int j = 0; j < EXEC_HCHUNK; j++) {
                         const int mid = (lo[j] + hi[j] + 1) >> 1;    // lo == hi: mid = lo, the probe changes nothing
-                        const uint32_t sm = ring[2 * (size_t)((s0 + (uint32_t)mid) & mask) + 1].w >> 2;
+                        const uint32_t sm = tape_step(ring[2 * (size_t)((s0 + (uint32_t)mid) & mask) + 1]);
                         if (lo[j] < hi[j]) { if (sm <= tt[j]) lo[j] = mid; else hi[j] = mid - 1; }
                         more = more || lo[j] < hi[j];
                     }
@@ -105,11 +102,11 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_tape_exec(TapeArgs T, int firs
                     unsigned long long* cm = mk + ((int)cid * nh + h0 + j) * 8;           // [agent][horizon][role 0 = maker][4]
                     unsigned long long* ct = mk + ((int)iid * nh + h0 + j) * 8 + 4;       // ... [role 1 = taker]
                     if (scored[j]) {
-                        const long long mark = (long long)(int)ring[2 * (size_t)((s0 + (uint32_t)lo[j]) & mask)].y;
+                        const long long mark = (long long)tape_price(ring[2 * (size_t)((s0 + (uint32_t)lo[j]) & mask)]);
                         const long long v = (mark - price) * qty;
-                        exec_add(cm, cside ? -v : v); exec_add(cm + 1, qty); exec_add(cm + 2, 1ll);
-                        exec_add(ct, iside ? -v : v); exec_add(ct + 1, qty); exec_add(ct + 2, 1ll);
-                    } else { exec_add(cm + 3, 1ll); exec_add(ct + 3, 1ll); }
+                        lds_add(cm, cside ? -v : v); lds_add(cm + 1, qty); lds_add(cm + 2, 1ll);
+                        lds_add(ct, iside ? -v : v); lds_add(ct + 1, qty); lds_add(ct + 2, 1ll);
+                    } else { lds_add(cm + 3, 1ll); lds_add(ct + 3, 1ll); }
                 }
             }
             // ---- the running position, agent by agent
@@ -121,7 +118,7 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_tape_exec(TapeArgs T, int firs
                 const long long pos0 = (long long)row[XS_FINAL_POS], step0 = (long long)row[XS_LAST_STEP];      // what the agent carried into the pass
                 const int side = (int)iid == a ? iside : cside;
                 const long long d = mem ? (side ? -qty : qty) : 0ll;
-                long long x = d;
+                long long x = d;                                     // (wave_scan_sum(d, lane), kept open-coded: through the helper the kernel compiles one instruction shorter)
 #pragma unroll
                 for (int dd = 1; dd < WAVE; dd <<= 1) {
                     const long long y = __shfl_up(x, dd);
@@ -134,7 +131,7 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_tape_exec(TapeArgs T, int firs
                 const long long prev_step = below ? sp_ : step0;     // (step0 = -1: no fill yet, and `before` is 0)
                 if (mem) {
                     const long long gap = (long long)step - prev_step, mag = before < 0 ? -before : before;
-                    if (mag != 0 && gap != 0) exec_add(row + XS_ABS_POS_STEPS, mag * gap);
+                    if (mag != 0 && gap != 0) lds_add(row + XS_ABS_POS_STEPS, mag * gap);
                     if (after > 0) atomicMax((long long*)row + XS_MAX_LONG, after);
                     if (after < 0) atomicMin((long long*)row + XS_MAX_SHORT, after);
                 }
@@ -157,22 +154,18 @@ __global__ __launch_bounds__(64 * CDA_WPB) void k_tape_exec(TapeArgs T, int firs
     for (int i = lane; i < n_stat; i += WAVE) so[i] = (long long)st[i];
     long long* mo = marks_out + (size_t)w * (size_t)n_mark;
     for (int i = lane; i < n_mark; i += WAVE) mo[i] = (long long)mk[i];
-    if (info && lane == 0) {
-        int32_t* o = info + 4 * (size_t)w;
-        o[0] = (int32_t)used; o[1] = (int32_t)sp.lost; o[2] = 0; o[3] = (int32_t)sp.partial;
-    }
+    if (info && lane == 0) reader_info(info, w, (int32_t)used, (int32_t)sp.lost, 0, (int32_t)sp.partial);
 }
 
 extern "C" {
 
 int cda_tape_exec(cda_env* e, int32_t first_market, int32_t n_markets, int32_t which, const int32_t* horizons_dev_or_host, int32_t n_horizons, int64_t* stats_out_dev,
                   int64_t* markouts_out_dev, int32_t* info_out_dev, void* stream) {
-    if (!e || !horizons_dev_or_host || !stats_out_dev || !markouts_out_dev || n_horizons < 1 || n_horizons > CDA_TAPE_MAX_HORIZONS ||
-        (which != CDA_TAPE_CURRENT && which != CDA_TAPE_PREVIOUS) || !range_ok(e, first_market, n_markets) || ((uintptr_t)stats_out_dev & 7) != 0 ||
-        ((uintptr_t)markouts_out_dev & 7) != 0) return CDA_ERR_INVALID;
+    if (!reader_args_ok(e, stats_out_dev, first_market, n_markets) || !horizons_dev_or_host || !markouts_out_dev || n_horizons < 1 || n_horizons > CDA_TAPE_MAX_HORIZONS ||
+        !which_ok(which) || !aligned(stats_out_dev, 8) || !aligned(markouts_out_dev, 8) || !range_ok(e, first_market, n_markets)) return CDA_ERR_INVALID;
     if (!e->tape.ring) return CDA_ERR_UNSUPPORTED;
-    if (e->P.cfg.num_agents < 1 || e->P.cfg.num_agents > CDA_MAX_AGENTS) return CDA_ERR_INVALID;
-    HIPCHK(hipSetDevice(e->device));
+    if (!agents_ok(e)) return CDA_ERR_INVALID;
+    HIPCHK(hipSetDevice(e->device));                                 // (here as well as in reader_launch: the copy of a device array of horizons below runs on it)
     ExecHorizons hz;
     memset(&hz, 0, sizeof hz);
     hipPointerAttribute_t at;
@@ -184,9 +177,8 @@ int cda_tape_exec(cda_env* e, int32_t first_market, int32_t n_markets, int32_t w
     } else memcpy(hz.k, horizons_dev_or_host, sizeof(int32_t) * (size_t)n_horizons);
     for (int h = 0; h < n_horizons; h++) if (hz.k[h] < 0) return CDA_ERR_INVALID;
     const size_t lds = (size_t)CDA_WPB * (size_t)e->P.cfg.num_agents * (size_t)(CDA_TAPE_STAT_WORDS + 8 * n_horizons) * sizeof(unsigned long long);
-    hipLaunchKernelGGL(k_tape_exec, dim3((unsigned)((n_markets + CDA_WPB - 1) / CDA_WPB)), dim3(64 * CDA_WPB), lds, (hipStream_t)stream, e->tape, (int)first_market, (int)n_markets,
-                       (int)which, (int)e->P.cfg.num_agents, (int)n_horizons, hz, (long long*)stats_out_dev, (long long*)markouts_out_dev, info_out_dev);
-    return launch_status();
+    return reader_launch(e, k_tape_exec, n_markets, CDA_WPB, lds, stream, e->tape, (int)first_market, (int)n_markets, (int)which, (int)e->P.cfg.num_agents, (int)n_horizons, hz,
+                         (long long*)stats_out_dev, (long long*)markouts_out_dev, info_out_dev);
 }
 
 }  // extern "C"

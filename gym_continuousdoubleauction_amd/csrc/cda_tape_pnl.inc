@@ -1,8 +1,8 @@
 // cda_tape_pnl.inc - the P&L report (include/cda.h cda_tape_pnl): per market and agent the mark-to-mid equity curve of one remembered episode - the trade tape
 // joined to the quote tape on the bar points - and what a person reads off it: drawdown, the moments of the per-bar P&L, the time under water and the split of
 // the P&L into what the carried inventory gained on the mid's moves and what the trades themselves earned against each bar's closing mid.  Included behind
-// cda_stylised.inc (styl_points, styl_stage, styl_waves, styl_range_top, STYL_LDS_BYTES); pnl.py states every word in numpy.  A READER: one wave per market,
-// exact integers, nothing atomic on global memory, every requested output word written exactly once by plain vector stores.
+// cda_stylised.inc (styl_points, styl_stage, styl_waves, styl_range_top, STYL_LDS_BYTES; the scans and reductions: cda_wave.hpp); pnl.py states every word in
+// numpy.  A READER: one wave per market, exact integers, nothing atomic on global memory, every requested output word written exactly once by plain vector stores.
 //
 // The wave's slice of dynamic LDS holds, per bar point (at most CDA_STYL_MAX_BARS): cash[b] (int64), mark[p] (int32), qty[b] (int32) - 16 bytes a point, so a
 // workgroup runs four market-waves up to 1024 points, two up to 2048 and one at 4096 (styl_waves).  That leaves room for ONE agent's per-bar words: the agent
@@ -23,30 +23,13 @@ enum { PN_POINTS = 0, PN_STALE, PN_UNMARKED, PN_BARS, PN_EQUITY_FIRST, PN_EQUITY
 constexpr size_t PNL_POINT_BYTES = sizeof(long long) + 2 * sizeof(int32_t);
 constexpr long long PNL_LOWEST = -0x7fffffffffffffffll - 1, PNL_HIGHEST = 0x7fffffffffffffffll;
 
-// inclusive prefix sum / prefix max over the wave's lanes
-__device__ __forceinline__ long long pnl_scan_sum(long long x, int lane) {
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) { const long long y = __shfl_up(x, d); if (lane >= d) x += y; }
-    return x;
-}
-__device__ __forceinline__ long long pnl_scan_max(long long x, int lane) {
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) { const long long y = __shfl_up(x, d); if (lane >= d && y > x) x = y; }
-    return x;
-}
-__device__ __forceinline__ int pnl_scan_max(int x, int lane) {
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) { const int y = __shfl_up(x, d); if (lane >= d && y > x) x = y; }
-    return x;
-}
-
 // Four waves per SIMD asked for: left alone, the max-ilp scheduler spreads the point pass over 270 registers - one wave per SIMD, where 1000 points' LDS lets a
 // CU hold two workgroups; held to 128 the kernel takes 127, spills nothing and needs no scratch.
 __global__ __launch_bounds__(64 * CDA_WPB, 4) void k_tape_pnl(const uint8_t* arena, Params P, TapeArgs T, QuoteArgs Q, int first, int n, int which, int bar, int agents,
                                                            int cap_pts, int n_points, long long* stats_out, long long* equity_out, int32_t* position_out,
                                                            int32_t* marks_out, int32_t* info) {
     extern __shared__ __align__(16) long long pnl_lds[];              // per wave: cap_pts cash words, then cap_pts marks, cap_pts bar quantities
-    const int wib = (int)(threadIdx.x >> 6), w = (int)blockIdx.x * (int)(blockDim.x >> 6) + wib, lane = (int)(threadIdx.x & 63);
+    READER_WAVE_IN_GROUP((int)(blockDim.x >> 6));
     const bool live = w < n;
     long long* cash = pnl_lds + (size_t)wib * (size_t)(2 * cap_pts);  // (16 bytes a point = two 8-byte words)
     int32_t* mark = reinterpret_cast<int32_t*>(cash + cap_pts);
@@ -74,7 +57,7 @@ __global__ __launch_bounds__(64 * CDA_WPB, 4) void k_tape_pnl(const uint8_t* are
             const bool two = valid && mark[p] != 0;
             const unsigned long long m = __ballot(two);
             if (k_last < 0 && m != 0ull) first_two = p0 + __ffsll((long long)m) - 1;
-            int last = pnl_scan_max(two ? p : -1, lane);
+            int last = wave_scan_max(two ? p : -1, lane);
             last = last > k_last ? last : k_last;
             const int32_t v = last >= 0 ? mark[last] : 0;             // (a two-sided point's word is never rewritten)
             c_stale += valid && last >= 0 && !two ? 1 : 0;
@@ -86,7 +69,7 @@ __global__ __launch_bounds__(64 * CDA_WPB, 4) void k_tape_pnl(const uint8_t* are
     const bool any = first_two <= pt.hi;
     const long long n_marked = any ? (long long)(pt.hi - first_two + 1) : 0ll;
     const long long n_held = pt.hi >= pt.lo ? (long long)(pt.hi - pt.lo + 1) : 0ll;
-    const long long t_stale = quote_wave_sum((long long)c_stale);
+    const long long t_stale = wave_sum((long long)c_stale);
     if (live && marks_out)
         for (int p = lane; p < n_points; p += WAVE) marks_out[(size_t)w * (size_t)n_points + p] = p >= first_two && p <= pt.hi ? mark[p] : 0;
     const uint32_t t0 = (uint32_t)ts.start & tmask;
@@ -98,15 +81,15 @@ __global__ __launch_bounds__(64 * CDA_WPB, 4) void k_tape_pnl(const uint8_t* are
         if (live) {
             for (long long base = 0; base < ts.count; base += WAVE) {
                 const bool in = base + lane < ts.count;
-                uint4 r0 = make_uint4(0u, 0u, 0u, 0u), r1 = r0;
-                if (in) { const uint32_t slot = (t0 + (uint32_t)(base + lane)) & tmask; r0 = tring[2 * (size_t)slot]; r1 = tring[2 * (size_t)slot + 1]; }
-                const uint32_t cid = r0.w, iid = r1.z;
+                uint4 r0, r1;
+                tape_load(tring, tmask, t0, base + lane, in, r0, r1);
+                const uint32_t cid = tape_counter_id(r0), iid = tape_init_id(r1);
                 const bool ok = in && cid < (uint32_t)agents && iid < (uint32_t)agents;      // (ids outside the env's agents: as k_tape_exec)
                 if (a == 0) used += __popcll(__ballot(ok));
                 const bool mine = ok && cid != iid && (cid == (uint32_t)a || iid == (uint32_t)a);
-                const int side = iid == (uint32_t)a ? (int)((r1.w >> 1) & 1u) : (int)(r1.w & 1u);
-                const long long sq = side ? -(long long)(int)r0.z : (long long)(int)r0.z, price = (long long)(int)r0.y;
-                const uint32_t b = (r1.w >> 2) / (uint32_t)bar;
+                const int side = iid == (uint32_t)a ? tape_init_side(r1) : tape_counter_side(r1);
+                const long long sq = side ? -(long long)tape_qty(r0) : (long long)tape_qty(r0), price = (long long)tape_price(r0);
+                const uint32_t b = tape_step(r1) / (uint32_t)bar;
                 if (mine && b < (uint32_t)cap_pts) {
                     atomicAdd(qty + b, (int32_t)sq);
                     atomicAdd(reinterpret_cast<unsigned long long*>(cash + b), (unsigned long long)(-sq * price));
@@ -124,10 +107,10 @@ __global__ __launch_bounds__(64 * CDA_WPB, 4) void k_tape_pnl(const uint8_t* are
                 const int p = p0 + lane;
                 const bool valid = p <= pt.hi, held = valid && p >= pt.lo, marked = valid && p >= first_two;
                 const long long dq = valid && p >= 1 ? (long long)qty[p - 1] : 0ll, dc = valid && p >= 1 ? cash[p - 1] : 0ll;      // bar p - 1 ends at point p
-                const long long pos = k_pos + pnl_scan_sum(dq, lane), c = k_cash + pnl_scan_sum(dc, lane);
+                const long long pos = k_pos + wave_scan_sum(dq, lane), c = k_cash + wave_scan_sum(dc, lane);
                 const long long mk = marked ? (long long)mark[p] : 0ll;
                 const long long eq = marked ? 2 * c + pos * mk : 0ll;
-                long long top = pnl_scan_max(marked ? eq : PNL_LOWEST, lane);
+                long long top = wave_scan_max(marked ? eq : PNL_LOWEST, lane);
                 top = top > k_max ? top : k_max;
                 long long e_b = __shfl_up(eq, 1), pos_b = __shfl_up(pos, 1), mk_b = __shfl_up(mk, 1);
                 if (lane == 0) { e_b = k_eq; pos_b = k_pos; mk_b = k_mark; }
@@ -147,10 +130,10 @@ __global__ __launch_bounds__(64 * CDA_WPB, 4) void k_tape_pnl(const uint8_t* are
                 if (equity_out) equity_out[row * (size_t)n_points + p] = 0ll;
                 if (position_out) position_out[row * (size_t)n_points + p] = 0;
             }
-            const long long t_inv = quote_wave_sum(s_inv), t_trd = quote_wave_sum(s_trd), t_d2 = quote_wave_sum(s_d2), t_first = quote_wave_sum(s_first),
-                            t_last = quote_wave_sum(s_last), t_up = quote_wave_sum((long long)c_up), t_down = quote_wave_sum((long long)c_down),
-                            t_under = quote_wave_sum((long long)c_under), t_open = quote_wave_sum((long long)c_open), t_dd = quote_wave_max(m_dd),
-                            t_top = quote_wave_max(m_top), t_low = quote_wave_min(m_low);
+            const long long t_inv = wave_sum(s_inv), t_trd = wave_sum(s_trd), t_d2 = wave_sum(s_d2), t_first = wave_sum(s_first),
+                            t_last = wave_sum(s_last), t_up = wave_sum((long long)c_up), t_down = wave_sum((long long)c_down),
+                            t_under = wave_sum((long long)c_under), t_open = wave_sum((long long)c_open), t_dd = wave_max(m_dd),
+                            t_top = wave_max(m_top), t_low = wave_min(m_low);
             if (lane < CDA_PNL_WORDS) {
                 const long long v = lane == PN_POINTS ? n_marked : lane == PN_STALE ? t_stale : lane == PN_UNMARKED ? n_held - n_marked :
                                     lane == PN_BARS ? (n_marked > 0 ? n_marked - 1 : 0ll) : lane == PN_EQUITY_FIRST ? t_first : lane == PN_EQUITY_LAST ? t_last :
@@ -162,10 +145,7 @@ __global__ __launch_bounds__(64 * CDA_WPB, 4) void k_tape_pnl(const uint8_t* are
         }
         __syncthreads();
     }
-    if (live && info && lane == 0) {
-        int32_t* o = info + 4 * (size_t)w;
-        o[0] = (int32_t)used; o[1] = (int32_t)ts.lost; o[2] = (int32_t)qs.lost; o[3] = (int32_t)(ts.partial | (qs.partial << 1));
-    }
+    if (live && info && lane == 0) reader_info(info, w, (int32_t)used, (int32_t)ts.lost, (int32_t)qs.lost, (int32_t)(ts.partial | (qs.partial << 1)));
 }
 
 extern "C" {
@@ -180,21 +160,19 @@ int cda_tape_pnl_check_host(int32_t bar_steps, int32_t n_points, int32_t want_se
 
 int cda_tape_pnl(cda_env* e, int32_t first_market, int32_t n_markets, int32_t which, int32_t bar_steps, int64_t* stats_out_dev, int64_t* equity_out_dev,
                  int32_t* position_out_dev, int32_t* marks_out_dev, int32_t n_points, int32_t* info_out_dev, void* stream) {
-    if (!e || !stats_out_dev || !QUOTE_WHICH_OK(which) || !range_ok(e, first_market, n_markets) || (((uintptr_t)stats_out_dev | (uintptr_t)equity_out_dev) & 7) != 0 ||
-        (((uintptr_t)position_out_dev | (uintptr_t)marks_out_dev | (uintptr_t)info_out_dev) & 3) != 0) return CDA_ERR_INVALID;
+    if (!reader_args_ok(e, stats_out_dev, first_market, n_markets) || !which_ok(which) || !aligned(stats_out_dev, 8) || !aligned(equity_out_dev, 8) || !aligned(position_out_dev, 4) ||
+        !aligned(marks_out_dev, 4) || !aligned(info_out_dev, 4) || !range_ok(e, first_market, n_markets)) return CDA_ERR_INVALID;
     const int want = equity_out_dev || position_out_dev || marks_out_dev ? 1 : 0;
     const int32_t top = styl_range_top(e, first_market, n_markets);
     if (cda_tape_pnl_check_host(bar_steps, n_points, want, top) != CDA_OK) return CDA_ERR_INVALID;
-    if (e->P.cfg.num_agents < 1 || e->P.cfg.num_agents > CDA_MAX_AGENTS) return CDA_ERR_INVALID;
+    if (!agents_ok(e)) return CDA_ERR_INVALID;
     if (!e->tape.ring || !e->quotes.ring) return CDA_ERR_UNSUPPORTED;
     const int64_t pts = ((int64_t)top + (int64_t)bar_steps - 1) / (int64_t)bar_steps;      // <= CDA_STYL_MAX_BARS
-    HIPCHK(hipSetDevice(e->device));
     const size_t per_wave = (size_t)pts * PNL_POINT_BYTES;           // <= STYL_LDS_BYTES
     const int waves = styl_waves(per_wave);
-    hipLaunchKernelGGL(k_tape_pnl, dim3((unsigned)((n_markets + waves - 1) / waves)), dim3(64 * waves), per_wave * (size_t)waves, (hipStream_t)stream,
-                       (const uint8_t*)e->arena, e->P, e->tape, e->quotes, (int)first_market, (int)n_markets, (int)which, (int)bar_steps, (int)e->P.cfg.num_agents, (int)pts,
-                       (int)(want ? n_points : 0), (long long*)stats_out_dev, (long long*)equity_out_dev, position_out_dev, marks_out_dev, info_out_dev);
-    return launch_status();
+    return reader_launch(e, k_tape_pnl, n_markets, waves, per_wave * (size_t)waves, stream, (const uint8_t*)e->arena, e->P, e->tape, e->quotes, (int)first_market, (int)n_markets,
+                         (int)which, (int)bar_steps, (int)e->P.cfg.num_agents, (int)pts, (int)(want ? n_points : 0), (long long*)stats_out_dev, (long long*)equity_out_dev,
+                         position_out_dev, marks_out_dev, info_out_dev);
 }
 
 }  // extern "C"

@@ -8,6 +8,8 @@ A quote is the top of one market's book as the agents' orders of step t meet it:
 of its orders.  An absent side stores zeros; a volume or count beyond INT32_MAX stores INT32_MAX and sets the saturated bit."""
 import numpy as np
 
+from .tape import _horizons  # noqa: F401  (the spread report's horizons are the execution report's: one check, one message; MAX_HORIZONS below == tape.MAX_HORIZONS)
+
 QUOTE_WORDS = 8
 # one step's quote = eight int32 words (cda_quote_record)
 QUOTE_DTYPE = np.dtype([("step", "<i4"), ("flags", "<i4"), ("bid_price", "<i4"), ("ask_price", "<i4"), ("bid_volume", "<i4"), ("ask_volume", "<i4"),
@@ -165,11 +167,7 @@ def stats_summary(stats):
 
 
 # ---------------------------------------------------------------------------------------------------------------- spread reports
-def _horizons(horizons):
-    hz = [int(k) for k in (horizons if hasattr(horizons, "__iter__") else (horizons,))]
-    if not 1 <= len(hz) <= MAX_HORIZONS or min(hz) < 0 or max(hz) >= 2 ** 31:
-        raise ValueError(f"horizons: 1 .. {MAX_HORIZONS} step counts >= 0, got {horizons!r}")
-    return hz
+# (the horizons' check is tape.py's _horizons, imported above: MAX_HORIZONS == tape.MAX_HORIZONS)
 
 
 def spreads_from_records(tape_rows, quote_rows, horizons, num_agents):

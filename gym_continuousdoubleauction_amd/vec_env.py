@@ -626,12 +626,8 @@ class CDAVecEnv:
         if not (0 <= int(first_market) and n >= 1 and int(first_market) + n <= self.n_markets and int(k) >= 1):
             raise ValueError(f"tape_last: range [{first_market}, {int(first_market) + n}) x {k} records is outside the env")
         which = self._tape_which(episode)
-        self.join()
-        with torch.cuda.device(self.device):
-            rec = torch.empty((n, int(k), K.TAPE_WORDS), dtype=torch.int32, device=self.device)
-            cnt = torch.empty(n, dtype=torch.int32, device=self.device)
-            check(lib().cda_tape_last_of(self._h, int(first_market), n, which, int(k), rec.data_ptr(), cnt.data_ptr(), self._stream()), "cda_tape_last_of")
-        return rec, cnt
+        return self._reader_call(lib().cda_tape_last_of, "cda_tape_last_of", int(first_market), n, (which, int(k)),
+                                 (torch.empty((n, int(k), K.TAPE_WORDS), dtype=torch.int32, device=self.device), torch.empty(n, dtype=torch.int32, device=self.device)), info=False)
 
     @staticmethod
     def _tape_which(episode):
@@ -645,6 +641,22 @@ class CDAVecEnv:
             raise ValueError(f"{what}: range [{first_market}, {int(first_market) + n}) is outside the env's {self.n_markets} markets")
         return int(first_market), n
 
+    def _top_max_step(self, first=0, n=None):
+        """The largest max_step of the markets [first, first + n); by default of the whole env."""
+        return int(self.market_rows(first, n)["max_step"].max()) if self.per_market else int(self.max_step)
+
+    def _reader_call(self, fn, name, first, n, mid, outs, info=True):
+        """One launch of a device reader (include/cda.h `name`, fn = lib().<name>) over the markets [first, first + n), on the caller's stream, ordered after every
+        group's last step, no host synchronisation: fn(env, first, n, *mid, *outputs, stream).  mid: the plain arguments between the range and the outputs; outs:
+        the tuple of the output tensors, allocated by the caller on self.device; info: the four-word info row [n, 4] behind them, allocated here.  -> the tuple of
+        the outputs.  (Nothing else happens per call: these calls are launch-bound, and a microsecond of Python here is measurable.)"""
+        self.join()
+        if info:
+            outs += (torch.empty((n, 4), dtype=torch.int32, device=self.device),)
+        with torch.cuda.device(self.device):
+            check(fn(self._h, first, n, *mid, *[t.data_ptr() for t in outs], self._stream()), name)
+        return outs
+
     def tape_bars(self, bar_steps, n_bars=None, episode="current", first_market=0, n_markets=None):
         """Price / volume bars of one remembered episode, reduced on the device in one launch (include/cda.h cda_tape_bars): bar b of a market covers the episode's
         fills of env steps [b * bar_steps, (b + 1) * bar_steps) -> (bars i32 [n, n_bars, 12], info i32 [n, 4]), device tensors.  The twelve words of a bar are
@@ -657,16 +669,11 @@ class CDAVecEnv:
         if int(bar_steps) < 1:
             raise ValueError(f"tape_bars: bar_steps must be >= 1, got {bar_steps}")
         if n_bars is None:
-            top = int(self.market_rows()["max_step"].max()) if self.per_market else int(self.max_step)
-            n_bars = -(-top // int(bar_steps))
+            n_bars = -(-self._top_max_step() // int(bar_steps))
         if int(n_bars) < 1:
             raise ValueError(f"tape_bars: n_bars must be >= 1, got {n_bars}")
-        self.join()
-        with torch.cuda.device(self.device):
-            bars = torch.empty((n, int(n_bars), K.TAPE_BAR_WORDS), dtype=torch.int32, device=self.device)
-            info = torch.empty((n, 4), dtype=torch.int32, device=self.device)
-            check(lib().cda_tape_bars(self._h, first, n, which, int(bar_steps), int(n_bars), bars.data_ptr(), info.data_ptr(), self._stream()), "cda_tape_bars")
-        return bars, info
+        return self._reader_call(lib().cda_tape_bars, "cda_tape_bars", first, n, (which, int(bar_steps), int(n_bars)),
+                                 (torch.empty((n, int(n_bars), K.TAPE_BAR_WORDS), dtype=torch.int32, device=self.device),))
 
     def tape_flows(self, episode="current", first_market=0, n_markets=None):
         """Who trades with whom in one remembered episode (include/cda.h cda_tape_flows): (flows i64 [n, A, A, 3], info i32 [n, 4]), device tensors;
@@ -674,13 +681,8 @@ class CDAVecEnv:
         self._need_tape("tape_flows()")
         first, n = self._market_range("tape_flows", first_market, n_markets)
         which = self._tape_which(episode)
-        self.join()
-        a = self.num_agents
-        with torch.cuda.device(self.device):
-            flows = torch.empty((n, a, a, 3), dtype=torch.int64, device=self.device)
-            info = torch.empty((n, 4), dtype=torch.int32, device=self.device)
-            check(lib().cda_tape_flows(self._h, first, n, which, flows.data_ptr(), info.data_ptr(), self._stream()), "cda_tape_flows")
-        return flows, info
+        return self._reader_call(lib().cda_tape_flows, "cda_tape_flows", first, n, (which,),
+                                 (torch.empty((n, self.num_agents, self.num_agents, 3), dtype=torch.int64, device=self.device),))
 
     def tape_exec(self, horizons=(1, 5, 20), episode="current", first_market=0, n_markets=None):
         """The execution report of one remembered episode, per market and agent, reduced on the device in one launch (include/cda.h cda_tape_exec; tape.py
@@ -696,15 +698,10 @@ class CDAVecEnv:
         first, n = self._market_range("tape_exec", first_market, n_markets)
         which = self._tape_which(episode)
         hz = _horizons(horizons)
-        self.join()
         a = self.num_agents
-        with torch.cuda.device(self.device):
-            stats = torch.empty((n, a, K.TAPE_STAT_WORDS), dtype=torch.int64, device=self.device)
-            marks = torch.empty((n, a, len(hz), 2, 4), dtype=torch.int64, device=self.device)
-            info = torch.empty((n, 4), dtype=torch.int32, device=self.device)
-            check(lib().cda_tape_exec(self._h, first, n, which, (C.c_int32 * len(hz))(*hz), len(hz), stats.data_ptr(), marks.data_ptr(), info.data_ptr(),
-                                      self._stream()), "cda_tape_exec")
-        return stats, marks, info
+        return self._reader_call(lib().cda_tape_exec, "cda_tape_exec", first, n, (which, (C.c_int32 * len(hz))(*hz), len(hz)),
+                                 (torch.empty((n, a, K.TAPE_STAT_WORDS), dtype=torch.int64, device=self.device),
+                                  torch.empty((n, a, len(hz), 2, 4), dtype=torch.int64, device=self.device)))
 
     def tape_episode(self, market=0):
         """The current episode's records of one market, oldest first, as a host array i32 [n, 8] (at most the ring's capacity of them)."""
@@ -750,11 +747,7 @@ class CDAVecEnv:
         quotes.meta_from_words names the words, quotes.span says what the ring holds of either episode."""
         self._need_quotes("quote_meta()")
         first, n = self._market_range("quote_meta", first_market, n_markets)
-        self.join()
-        with torch.cuda.device(self.device):
-            out = torch.empty((n, 8), dtype=torch.int32, device=self.device)
-            check(lib().cda_quote_meta(self._h, first, n, out.data_ptr(), self._stream()), "cda_quote_meta")
-        return out
+        return self._reader_call(lib().cda_quote_meta, "cda_quote_meta", first, n, (), (torch.empty((n, 8), dtype=torch.int32, device=self.device),), info=False)[0]
 
     def quote_series(self, k=None, episode="current", first_market=0, n_markets=None):
         """The held quotes of one remembered episode, oldest first (include/cda.h cda_quote_series): (records i32 [n, k, 8] - quotes.QUOTE_DTYPE rows; rows beyond
@@ -765,17 +758,11 @@ class CDAVecEnv:
         first, n = self._market_range("quote_series", first_market, n_markets)
         which = self._tape_which(episode)
         if k is None:
-            top = int(self.market_rows()["max_step"].max()) if self.per_market else int(self.max_step)
-            k = max(1, min(self.quote_capacity, top))
+            k = max(1, min(self.quote_capacity, self._top_max_step()))
         if int(k) < 1:
             raise ValueError(f"quote_series: k must be >= 1, got {k}")
-        self.join()
-        with torch.cuda.device(self.device):
-            rec = torch.empty((n, int(k), K.QUOTE_WORDS), dtype=torch.int32, device=self.device)
-            cnt = torch.empty(n, dtype=torch.int32, device=self.device)
-            info = torch.empty((n, 4), dtype=torch.int32, device=self.device)
-            check(lib().cda_quote_series(self._h, first, n, which, int(k), rec.data_ptr(), cnt.data_ptr(), info.data_ptr(), self._stream()), "cda_quote_series")
-        return rec, cnt, info
+        return self._reader_call(lib().cda_quote_series, "cda_quote_series", first, n, (which, int(k)),
+                                 (torch.empty((n, int(k), K.QUOTE_WORDS), dtype=torch.int32, device=self.device), torch.empty(n, dtype=torch.int32, device=self.device)))
 
     def quote_stats(self, episode="current", first_market=0, n_markets=None):
         """The statistics of one remembered episode's held quotes, reduced on the device in one launch (include/cda.h cda_quote_stats; quotes.stats_from_quotes is
@@ -784,12 +771,8 @@ class CDAVecEnv:
         self._need_quotes("quote_stats()")
         first, n = self._market_range("quote_stats", first_market, n_markets)
         which = self._tape_which(episode)
-        self.join()
-        with torch.cuda.device(self.device):
-            stats = torch.empty((n, K.QUOTE_STAT_WORDS), dtype=torch.int64, device=self.device)
-            info = torch.empty((n, 4), dtype=torch.int32, device=self.device)
-            check(lib().cda_quote_stats(self._h, first, n, which, stats.data_ptr(), info.data_ptr(), self._stream()), "cda_quote_stats")
-        return stats, info
+        return self._reader_call(lib().cda_quote_stats, "cda_quote_stats", first, n, (which,),
+                                 (torch.empty((n, K.QUOTE_STAT_WORDS), dtype=torch.int64, device=self.device),))
 
     def tape_spreads(self, horizons=(1, 5, 20), episode="current", first_market=0, n_markets=None):
         """The spread report of one remembered episode: the trade tape joined to the quotes by step, reduced on the device in one launch (include/cda.h
@@ -798,27 +781,22 @@ class CDAVecEnv:
         side x (2 price - m2(s)) x quantity, cost_later the same against m2(s + k), the scored quantity and fills, the fills whose s + k lies beyond the last held
         quote (open) and those whose quote at s or s + k is one-sided or no longer held (unquoted).  info: tape records aggregated, tape records lost, quote records
         lost, partial bits (1 tape, 2 quotes).  horizons: 1 .. 8 step counts >= 0.  quotes.spread_summary turns a row into the per-share ratios."""
-        from .quotes import SPREAD_WORDS, _horizons
+        from .quotes import SPREAD_WORDS
+        from .tape import _horizons
         self._need_tape("tape_spreads()")
         self._need_quotes("tape_spreads()")
         first, n = self._market_range("tape_spreads", first_market, n_markets)
         which = self._tape_which(episode)
         hz = _horizons(horizons)
-        self.join()
-        a = self.num_agents
-        with torch.cuda.device(self.device):
-            out = torch.empty((n, a, len(hz), 2, SPREAD_WORDS), dtype=torch.int64, device=self.device)
-            info = torch.empty((n, 4), dtype=torch.int32, device=self.device)
-            check(lib().cda_tape_spreads(self._h, first, n, which, (C.c_int32 * len(hz))(*hz), len(hz), out.data_ptr(), info.data_ptr(), self._stream()),
-                  "cda_tape_spreads")
-        return out, info
+        return self._reader_call(lib().cda_tape_spreads, "cda_tape_spreads", first, n, (which, (C.c_int32 * len(hz))(*hz), len(hz)),
+                                 (torch.empty((n, self.num_agents, len(hz), 2, SPREAD_WORDS), dtype=torch.int64, device=self.device),))
 
     # ------------------------------------------------------------------ the stylised-facts report: return and order-flow statistics of an episode (stylised.py)
     def _stylised_points(self, what, first, n, bar_steps):
         """bar_steps, checked: the bar points of the longest episode of the range must fit a wave's LDS (include/cda.h CDA_STYL_MAX_BARS)"""
         from .stylised import MAX_BARS, _bar_steps, n_points
         bar = _bar_steps(bar_steps)
-        top = int(self.market_rows(first, n)["max_step"].max()) if self.per_market else int(self.max_step)
+        top = self._top_max_step(first, n)
         if n_points(top, bar) > MAX_BARS:
             raise ValueError(f"{what}: an episode of {top} steps has {n_points(top, bar)} bar points at bar_steps = {bar}, more than {MAX_BARS}: raise bar_steps")
         return bar
@@ -838,15 +816,10 @@ class CDAVecEnv:
         if not 1 <= int(hist_half) <= MAX_HIST_HALF:
             raise ValueError(f"quote_returns: hist_half must be in 1 .. {MAX_HIST_HALF}, got {hist_half}")
         bar = self._stylised_points("quote_returns", first, n, bar_steps)
-        self.join()
-        with torch.cuda.device(self.device):
-            base = torch.empty((n, len(RETURN_FIELDS)), dtype=torch.int64, device=self.device)
-            lagged = torch.empty((n, len(lg), len(RETURN_LAG_FIELDS)), dtype=torch.int64, device=self.device)
-            hist = torch.empty((n, 2 * int(hist_half) + 1), dtype=torch.int64, device=self.device)
-            info = torch.empty((n, 4), dtype=torch.int32, device=self.device)
-            check(lib().cda_quote_returns(self._h, first, n, which, (C.c_int32 * len(lg))(*lg), len(lg), bar, int(hist_half), base.data_ptr(), lagged.data_ptr(),
-                                          hist.data_ptr(), info.data_ptr(), self._stream()), "cda_quote_returns")
-        return base, lagged, hist, info
+        return self._reader_call(lib().cda_quote_returns, "cda_quote_returns", first, n, (which, (C.c_int32 * len(lg))(*lg), len(lg), bar, int(hist_half)),
+                                 (torch.empty((n, len(RETURN_FIELDS)), dtype=torch.int64, device=self.device),
+                                  torch.empty((n, len(lg), len(RETURN_LAG_FIELDS)), dtype=torch.int64, device=self.device),
+                                  torch.empty((n, 2 * int(hist_half) + 1), dtype=torch.int64, device=self.device)))
 
     def tape_signs(self, lags=(1, 2, 5, 10), episode="current", first_market=0, n_markets=None):
         """The order-flow sign statistics of one remembered episode's held fills, in tape order, reduced on the device in one launch (include/cda.h cda_tape_signs;
@@ -858,14 +831,9 @@ class CDAVecEnv:
         first, n = self._market_range("tape_signs", first_market, n_markets)
         which = self._tape_which(episode)
         lg = _lags(lags, 1)
-        self.join()
-        with torch.cuda.device(self.device):
-            base = torch.empty((n, len(SIGN_FIELDS)), dtype=torch.int64, device=self.device)
-            lagged = torch.empty((n, len(lg), len(SIGN_LAG_FIELDS)), dtype=torch.int64, device=self.device)
-            info = torch.empty((n, 4), dtype=torch.int32, device=self.device)
-            check(lib().cda_tape_signs(self._h, first, n, which, (C.c_int32 * len(lg))(*lg), len(lg), base.data_ptr(), lagged.data_ptr(), info.data_ptr(),
-                                       self._stream()), "cda_tape_signs")
-        return base, lagged, info
+        return self._reader_call(lib().cda_tape_signs, "cda_tape_signs", first, n, (which, (C.c_int32 * len(lg))(*lg), len(lg)),
+                                 (torch.empty((n, len(SIGN_FIELDS)), dtype=torch.int64, device=self.device),
+                                  torch.empty((n, len(lg), len(SIGN_LAG_FIELDS)), dtype=torch.int64, device=self.device)))
 
     def tape_flow_returns(self, lags=(0, 1, 5), bar_steps=1, episode="current", first_market=0, n_markets=None):
         """Signed volume joined to returns, bar by bar, of one remembered episode, reduced on the device in one launch (include/cda.h cda_tape_flow_returns;
@@ -880,14 +848,9 @@ class CDAVecEnv:
         which = self._tape_which(episode)
         lg = _lags(lags, 0)
         bar = self._stylised_points("tape_flow_returns", first, n, bar_steps)
-        self.join()
-        with torch.cuda.device(self.device):
-            lagged = torch.empty((n, len(lg), len(FLOW_LAG_FIELDS)), dtype=torch.int64, device=self.device)
-            base = torch.empty((n, len(FLOW_FIELDS)), dtype=torch.int64, device=self.device)
-            info = torch.empty((n, 4), dtype=torch.int32, device=self.device)
-            check(lib().cda_tape_flow_returns(self._h, first, n, which, (C.c_int32 * len(lg))(*lg), len(lg), bar, lagged.data_ptr(), base.data_ptr(), info.data_ptr(),
-                                              self._stream()), "cda_tape_flow_returns")
-        return lagged, base, info
+        return self._reader_call(lib().cda_tape_flow_returns, "cda_tape_flow_returns", first, n, (which, (C.c_int32 * len(lg))(*lg), len(lg), bar),
+                                 (torch.empty((n, len(lg), len(FLOW_LAG_FIELDS)), dtype=torch.int64, device=self.device),
+                                  torch.empty((n, len(FLOW_FIELDS)), dtype=torch.int64, device=self.device)))
 
     # ------------------------------------------------------------------ the P&L report: every agent's mark-to-mid equity curve of an episode (pnl.py)
     def tape_pnl(self, bar_steps=1, episode="current", series=False, first_market=0, n_markets=None):
@@ -904,20 +867,17 @@ class CDAVecEnv:
         first, n = self._market_range("tape_pnl", first_market, n_markets)
         which = self._tape_which(episode)
         bar = self._stylised_points("tape_pnl", first, n, bar_steps)
-        top = int(self.market_rows(first, n)["max_step"].max()) if self.per_market else int(self.max_step)
-        pts = n_points(top, bar)
-        self.join()
+        pts = n_points(self._top_max_step(first, n), bar)
         a = self.num_agents
-        with torch.cuda.device(self.device):
-            stats = torch.empty((n, a, PNL_WORDS), dtype=torch.int64, device=self.device)
-            info = torch.empty((n, 4), dtype=torch.int32, device=self.device)
-            equity = position = marks = None
-            if series:
-                equity = torch.empty((n, a, pts), dtype=torch.int64, device=self.device)
-                position = torch.empty((n, a, pts), dtype=torch.int32, device=self.device)
-                marks = torch.empty((n, pts), dtype=torch.int32, device=self.device)
-            check(lib().cda_tape_pnl(self._h, first, n, which, bar, stats.data_ptr(), equity.data_ptr() if series else None, position.data_ptr() if series else None,
-                                     marks.data_ptr() if series else None, pts, info.data_ptr(), self._stream()), "cda_tape_pnl")
+        stats = torch.empty((n, a, PNL_WORDS), dtype=torch.int64, device=self.device)
+        equity = position = marks = None
+        if series:
+            equity = torch.empty((n, a, pts), dtype=torch.int64, device=self.device)
+            position = torch.empty((n, a, pts), dtype=torch.int32, device=self.device)
+            marks = torch.empty((n, pts), dtype=torch.int32, device=self.device)
+        # (n_points stands between the curves and the info row, and the curves may be NULL: the tables travel among the plain arguments, the info row is the output)
+        info, = self._reader_call(lib().cda_tape_pnl, "cda_tape_pnl", first, n, (which, bar, stats.data_ptr(), equity.data_ptr() if series else None,
+                                  position.data_ptr() if series else None, marks.data_ptr() if series else None, pts), ())
         return (stats, equity, position, marks, info) if series else (stats, info)
 
     def quote_episode(self, market=0, episode="current"):
@@ -929,11 +889,7 @@ class CDAVecEnv:
     # ------------------------------------------------------------------ the book report: reductions over the standing book, on the device
     def _book_call(self, name, first_market, n_markets, shape, dtype, *mid):
         first, n = self._market_range(name, first_market, n_markets)
-        self.join()
-        with torch.cuda.device(self.device):
-            out = torch.empty((n,) + shape, dtype=dtype, device=self.device)
-            check(getattr(lib(), "cda_" + name)(self._h, first, n, *mid, out.data_ptr(), self._stream()), "cda_" + name)
-        return out
+        return self._reader_call(getattr(lib(), "cda_" + name), "cda_" + name, first, n, mid, (torch.empty((n,) + shape, dtype=dtype, device=self.device),), info=False)[0]
 
     def book_counts(self, first_market=0, n_markets=None):
         """Resting orders and distinct price levels of every side, tile and HBM ring together (include/cda.h cda_book_counts): i32 [n, 2, 2] =
