@@ -149,6 +149,7 @@ __device__ __forceinline__ void stage_tables_commit(const TablePrefetch& q) {
 // ------------------------------------------------------------------------------------------
 
 struct FinCapture { float* obs; int32_t* count; int32_t* index_out; int32_t cap; };      // episode-end capture: see capture_final_obs (cda_kernels.inc)
+constexpr int CDA_INFO_TENSORS = 20;    // members of cda_info_ptrs (include/cda.h)
 struct StepArgs {
     const int32_t* category; const float* size_mean; const float* size_sigma;
     const int32_t* price; const int32_t* price_offset; const uint8_t* present;
@@ -632,6 +633,7 @@ struct cda_env {
     uint8_t* arena;
     size_t arena_bytes;
     uint8_t* done_buf;       // auto_reset: u8[N] behind the market records - terminated | truncated of the last step
+    uint8_t* info_sink;      // where a step's kernel writes every info tensor its caller left NULL (fill_step_args): N x A x 40 bytes, the largest of them (reward_terms); never read
     uint8_t* handback;       // cda_set_handback: caller-owned [N, handback_stride(A)] bytes, or NULL
     int64_t hb_row_stride, hb_rows_total;   // cda_set_handback_geometry: rows between two ranks' first markets / global row count (0, 0 = equal shards of N)
     int32_t spill_wanted;    // orders per side the spill ring was asked to hold (automatic: num_agents * max_step rounded up); P.lay.spill_cap is what it got
@@ -826,6 +828,7 @@ static bool reader_args_ok(const cda_env* e, const void* out, int32_t first, int
 // everything an env can own, in cda_destroy's order; a half-built env (cda_create's failure paths) holds NULL where nothing was allocated yet
 static void env_free(cda_env* e) {
     if (e->arena) (void)hipFree(e->arena);
+    if (e->info_sink) (void)hipFree(e->info_sink);
     if (e->em_partials) (void)hipFree(e->em_partials);
     if (e->snap_flag) (void)hipFree(e->snap_flag);
     tape_free(e);
@@ -836,6 +839,10 @@ static void env_free(cda_env* e) {
     free(e);
 }
 
+// The info sink of an env: the step kernels test no info pointer (csrc/cda_kernels.inc step_loaded) - the launch carries the sink for every tensor the caller did not ask
+// for.  Sized for the largest tensor, so any member's index stays inside it: [N, A, 5] doubles (reward_terms); [N, A] cda_dec and [N, A, 4] int32 are 16 bytes per agent.
+static_assert(sizeof(cda_info_ptrs) == CDA_INFO_TENSORS * sizeof(void*), "cda_info_ptrs is CDA_INFO_TENSORS pointers and nothing else");
+static size_t info_sink_bytes(int32_t n_markets, int32_t num_agents) { return (size_t)n_markets * (size_t)num_agents * 5 * sizeof(double); }
 static int grant_policy_step_lds(const cda_env* e);
 int cda_create(const cda_config* cfg, int32_t n_markets, int32_t device, cda_env** out) {
     if (!cfg || !out || n_markets < 1) return CDA_ERR_INVALID;
@@ -906,6 +913,7 @@ int cda_create(const cda_config* cfg, int32_t n_markets, int32_t device, cda_env
     }
     launch_1d(k_init_arena, n_markets, 256, 0, 0, e->arena, P);
     he = hipMemsetAsync(e->arena + em_agent_off(P), 0, spill_arena_off(P) - em_agent_off(P), 0);          // the episode-metric accumulators
+    if (he == hipSuccess) he = hipMalloc((void**)&e->info_sink, info_sink_bytes(n_markets, cfg->num_agents));
     if (he == hipSuccess) he = hipMalloc((void**)&e->em_partials, (size_t)EM_BLOCKS * (CDA_EM_MAX_MODULES * CDA_EM_AGENT_FIELDS + CDA_EM_ENV_FIELDS) * sizeof(double));
     if (he == hipSuccess) he = hipDeviceSynchronize();
     if (he != hipSuccess) { env_free(e); return hip_fail(he, "k_init_arena"); }
@@ -989,7 +997,11 @@ static int fill_step_args(cda_env* e, StepArgs& S, const int32_t* category, cons
     if (!obs_out || !reward_out || !terminated_out || !truncated_out) return CDA_ERR_INVALID;
     S.category = category; S.size_mean = size_mean; S.size_sigma = size_sigma; S.price = price; S.price_offset = price_offset;
     S.present = present; S.obs_out = obs_out; S.reward_out = reward_out; S.terminated_out = terminated_out; S.truncated_out = truncated_out;
-    if (info_out) { S.info = *info_out; S.has_info = 1; } else { memset(&S.info, 0, sizeof S.info); S.has_info = 0; }
+    if (info_out) {                                        // the device sees CDA_INFO_TENSORS valid pointers: the caller's, and the env's sink for each one it left NULL
+        S.info = *info_out; S.has_info = 1;
+        void** member = reinterpret_cast<void**>(&S.info);
+        for (int k = 0; k < CDA_INFO_TENSORS; k++) if (!member[k]) member[k] = e->info_sink;
+    } else { memset(&S.info, 0, sizeof S.info); S.has_info = 0; }
     S.phase_cycles = g_phase_cycles;
     S.dbg_skip = g_dbg_skip;
     S.done_out = e->P.cfg.auto_reset ? e->done_buf : NULL;

@@ -354,6 +354,19 @@ __device__ __forceinline__ StepReward step_reward(Lds& L, const Params& P, int m
     return o;
 }
 
+// CDA_PHASE_TIMING, inside phase 7 (tools/phase_timing.py --info): the cycle counter's low word behind step_reward and behind the four conversions (tacc[9], low / high
+// half), behind the per-agent stores and behind the lane-0 block (tacc[13]) - the two accumulator slots the order phase leaves free
+#ifdef CDA_PHASE_TIMING
+#define TAIL_MARK(m, slot, shift) do { (m).tacc[slot] |= (__builtin_readcyclecounter() & 0xffffffffull) << (shift); } while (0)
+#else
+#define TAIL_MARK(m, slot, shift) do {} while (0)
+#endif
+
+// The info pointers of a launch.  A launch with info tensors carries CDA_INFO_TENSORS VALID pointers (cda_step puts the env's sink where its caller left NULL: csrc/cda_hip.hip
+// fill_step_args), so no store of the info block is tested - a test per tensor made every pointer's fetch wait behind the previous pointer's branch: one scalar-memory
+// round trip per tensor, back to back, at the end of every wave.  Untested, the compiler fetches them in a few wide scalar loads (profiles/info_tail/attribution.txt; a
+// per-lane vector fetch of the table ahead of phase 7 with readlane at the store sites measured SLOWER than the parent: profiles/info_tail/ab.txt).
+
 // The kernel's arguments as ONE struct: the out-of-line general step reads them back from the kernarg segment instead of having
 // them passed (which would keep them live - or copy them - in the hot kernel).
 struct StepKernArgs { uint8_t* arena; Params P; StepArgs S; };
@@ -386,18 +399,20 @@ __device__ __forceinline__ void step_loaded(const Params& P, const StepArgs& S, 
     uint32_t ferr = 0;
     StepReward rw; rw.r = rw.t0 = rw.t1 = rw.t2 = rw.t3 = rw.t4 = rw.drawdown = rw.max_nav = 0.0; rw.bankrupt = false;
     if (!CDA_DBG_HAS(S, 8)) rw = step_reward(L, P, mi, ferr, lane, has_info);
+    TAIL_MARK(m, 9, 0);
     if (has_info) {                                                          // Info_Helper.set_info (info_helper.py:30-116)
         // the four float(Decimal) fields of an account are converted by four lanes (a, a+16, a+32, a+48) through ONE call site
-        const cda_info_ptrs& I = S.info;
         const int al = lane_acc(lane), g = lane_grp(lane);
         if (al < A) {
             const Acc& a = L.acc[al];
             const cda_dec& src = g == 0 ? a.vwap : (g == 1 ? a.cash : (g == 2 ? a.hold : a.posval));
+            const cda_info_ptrs& I = S.info;
             double* dst = g == 0 ? I.vwap : (g == 1 ? I.cash : (g == 2 ? I.cash_on_hold : I.position_val));   // (per lane: fetched from the kernarg segment by a vector load - measured cheaper than four scalar pointers held live: 462.6 vs 443.5 M)
             const double v = d_to_double(ld_dec(src), &ferr);
-            if (dst) dst[(size_t)mi * (size_t)A + (size_t)al] = v;
+            dst[(size_t)mi * (size_t)A + (size_t)al] = v;
         }
     }
+    TAIL_MARK(m, 9, 32);
     if (!CDA_DBG_HAS(S, 4)) {                             // phase 6's stores (no decimal routine is called from here on)
         size_t ob = (size_t)mi * (size_t)(H * CDA_SNAPSHOT_DIM);
         if (lane < CDA_SNAPSHOT_DIM) {
@@ -418,18 +433,18 @@ __device__ __forceinline__ void step_loaded(const Params& P, const StepArgs& S, 
         __builtin_nontemporal_store(rw.r, &S.reward_out[ix]);
         if (has_info) {
             const cda_info_ptrs& I = S.info;
-            if (I.nav) I.nav[ix] = a.nav;
-            if (I.num_trades) I.num_trades[ix] = a.num_trades;
-            if (I.net_position) I.net_position[ix] = a.net_position;
-            if (I.drawdown) I.drawdown[ix] = rw.drawdown;
-            if (I.max_nav) I.max_nav[ix] = rw.max_nav;
-            if (I.num_trades_step) I.num_trades_step[ix] = a.num_trades_step;
-            if (I.num_passive_fills_step) I.num_passive_fills_step[ix] = a.num_passive_fills_step;
-            if (I.order_step_placed) I.order_step_placed[ix] = a.order_step_placed;
-            if (I.num_rejected_step) I.num_rejected_step[ix] = a.num_rejected_step;
-            if (I.is_pass_action) I.is_pass_action[ix] = (uint8_t)((pass_mask >> (lane & 31)) & 1u);
-            if (I.reward_terms) { double* rt = I.reward_terms + ix * 5; rt[0] = rw.t0; rt[1] = rw.t1; rt[2] = rw.t2; rt[3] = rw.t3; rt[4] = rw.t4; }
-            if (I.lob_actions) {                                               // decoded orders as the env keeps them (agent order, passes left out)
+            I.nav[ix] = a.nav;
+            I.num_trades[ix] = a.num_trades;
+            I.net_position[ix] = a.net_position;
+            I.drawdown[ix] = rw.drawdown;
+            I.max_nav[ix] = rw.max_nav;
+            I.num_trades_step[ix] = a.num_trades_step;
+            I.num_passive_fills_step[ix] = a.num_passive_fills_step;
+            I.order_step_placed[ix] = a.order_step_placed;
+            I.num_rejected_step[ix] = a.num_rejected_step;
+            I.is_pass_action[ix] = (uint8_t)((pass_mask >> (lane & 31)) & 1u);
+            { double* rt = I.reward_terms + ix * 5; rt[0] = rw.t0; rt[1] = rw.t1; rt[2] = rw.t2; rt[3] = rw.t3; rt[4] = rw.t4; }
+            {                                                                  // decoded orders as the env keeps them (agent order, passes left out)
                 int32_t* la = I.lob_actions + ix * 4;
                 const int32_t tsp = L.act_tsp[lane];
                 const bool has = in.pres && !((pass_mask >> (lane & 31)) & 1u);
@@ -442,6 +457,7 @@ __device__ __forceinline__ void step_loaded(const Params& P, const StepArgs& S, 
         }
         clear_step_counters(a);
     }
+    TAIL_MARK(m, 13, 0);
     if (__ballot(ferr != 0)) m.flags |= CDA_FLAG_DEC_DOMAIN;
     m.done_mask |= (uint32_t)__ballot(rw.bankrupt);
     if (lane == 0) {
@@ -449,10 +465,10 @@ __device__ __forceinline__ void step_loaded(const Params& P, const StepArgs& S, 
             const cda_info_ptrs& I = S.info;
             double bb = m.nb ? (double)L.book.price[0][0] : __longlong_as_double(0x7ff8000000000000LL);
             double ba = m.na ? (double)L.book.price[1][0] : __longlong_as_double(0x7ff8000000000000LL);
-            if (I.last_price) I.last_price[mi] = (double)m.last_price;
-            if (I.best_bid) I.best_bid[mi] = bb;
-            if (I.best_ask) I.best_ask[mi] = ba;
-            if (I.spread) I.spread[mi] = (m.nb && m.na) ? ba - bb : __longlong_as_double(0x7ff8000000000000LL);
+            I.last_price[mi] = (double)m.last_price;
+            I.best_bid[mi] = bb;
+            I.best_ask[mi] = ba;
+            I.spread[mi] = (m.nb && m.na) ? ba - bb : __longlong_as_double(0x7ff8000000000000LL);
         }
         // Done_Helper.set_all_done (done_helper.py:20-54)
         const bool term = __popc(m.done_mask) == A, trunc = m.t_step + 1 >= mrow(P, mi).max_step;
@@ -460,6 +476,7 @@ __device__ __forceinline__ void step_loaded(const Params& P, const StepArgs& S, 
         S.truncated_out[mi] = (uint8_t)trunc;
         if (S.done_out) S.done_out[mi] = (uint8_t)(term || trunc);
     }
+    TAIL_MARK(m, 13, 32);
     if (S.handback) {                                     // cda_set_handback: the compact record of what is new this step (ONE test per step)
         uint8_t* rec = S.handback + (size_t)mi * (size_t)S.handback_stride;
         if (lane < CDA_SNAPSHOT_DIM) reinterpret_cast<float*>(rec)[lane] = frame_v;

@@ -34,7 +34,9 @@ def bodies(co):
         elif cur is not None and line.strip():
             cur.append(re.sub(r"\s*//.*$", "", line).strip())
     for name, body in out.items():
-        while body and (body[-1].startswith("s_nop") or body[-1] == "..."):      # ("...": the zero fill objdump elides between a function and the next one's alignment)
+        # ("...": the zero fill objdump elides between a function and the next one's alignment; a single zero word it prints as the instruction 0x00000000 decodes to -
+        #  no function ends on a v_cndmask)
+        while body and (body[-1].startswith("s_nop") or body[-1] in ("...", "v_cndmask_b32_e32 v0, s0, v0, vcc")):
             body.pop()
         for i, ins in enumerate(body):                       # s15 set within a few instructions of a call: the kernel's ordinal
             if re.match(r"s_mov_b32 s15, \d+$", ins) and any("s_swappc_b64" in x for x in body[i + 1:i + 160]):

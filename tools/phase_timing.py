@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Debug: per-phase cycle breakdown of k_step (needs a -DCDA_PHASE_TIMING build of the library).
-Run on the GPU box: python tools/phase_timing.py"""
+Run on the GPU box: python tools/phase_timing.py
+    --info         step with every info tensor (k_step<true, false>) and print how phase 7 splits: reward, the four conversions, the stores, the lane-0 block
+    --lib PATH     a -DCDA_PHASE_TIMING library built beforehand (e.g. of another tree); --build-only [--out PATH]: build it and stop"""
 import ctypes as C
 import os
 import subprocess
@@ -13,16 +15,19 @@ import torch
 
 so = os.path.join(ROOT, "gpurun_out", "libcda_hip_timing.so")
 COUNTERS = "--counters" in sys.argv      # atomics in every out-of-line decimal routine: call counts, but the cycle stamps are then meaningless
+INFO = "--info" in sys.argv               # every info tensor: the headline kernel of bench.py
 PREBUILT = sys.argv[sys.argv.index("--lib") + 1] if "--lib" in sys.argv else None     # a -DCDA_PHASE_TIMING library built beforehand (e.g. of another tree)
 if PREBUILT:
     so = os.path.abspath(PREBUILT)
+elif "--out" in sys.argv:
+    so = os.path.abspath(sys.argv[sys.argv.index("--out") + 1])
 os.makedirs(os.path.dirname(so), exist_ok=True)
 import __graft_entry__ as G   # the product's own flags + the timing macro
 if "--build-only" in sys.argv or not PREBUILT:
     subprocess.check_call(["hipcc"] + G.HIPCC_FLAGS + ["-DCDA_PHASE_TIMING"] + (["-DCDA_DEC_COUNTERS"] if COUNTERS else []) + ["-o", so, os.path.join(ROOT, "gym_continuousdoubleauction_amd", "csrc", "cda_hip.hip"), os.path.join(ROOT, "gym_continuousdoubleauction_amd", "csrc", "cda_ppo.hip"),
-                           os.path.join(ROOT, "gym_continuousdoubleauction_amd", "csrc", "cda_mlp.hip")]
-                          + ["-Wl," + os.path.join(ROOT, "gym_continuousdoubleauction_amd", "build_tmp", f"cda_mlp_h{h}.o") for h in G.MLP_HIST_VARIANTS])
-    # (the whole library: _lib binds every symbol of both headers, the network's extra history depths too - their objects as build() left them)
+                           os.path.join(ROOT, "gym_continuousdoubleauction_amd", "csrc", "cda_learner.hip"), os.path.join(ROOT, "gym_continuousdoubleauction_amd", "csrc", "cda_mlp.hip")]
+                          + ["-Wl," + os.path.join(ROOT, "gym_continuousdoubleauction_amd", "build_tmp", name + ".o") for name, _defs in G.mlp_variant_objects()])
+    # (the whole library: _lib binds every symbol of the headers, the network's variants too - their objects as build() left them)
 if "--build-only" in sys.argv:
     sys.exit(0)
 from gym_continuousdoubleauction_amd import _lib
@@ -30,7 +35,7 @@ _lib.LIB_PATH = so
 from gym_continuousdoubleauction_amd import CDAVecEnv
 
 N, A = 4096, 4
-env = CDAVecEnv({"num_of_agents": A, "init_cash": 1000000, "max_step": 100000, "is_render": False}, n_markets=N, with_info=False)
+env = CDAVecEnv({"num_of_agents": A, "init_cash": 1000000, "max_step": 100000, "is_render": False}, n_markets=N, with_info=INFO)
 env.reset(seed=np.arange(1000, 1000 + N, dtype=np.uint64))
 buf = torch.zeros((N, 40), dtype=torch.int64, device="cuda:0")
 L = _lib.lib()
@@ -41,6 +46,14 @@ names = ["load", "snapshot_pre", "decode+rng", "shuffle", "orders", "mtm", "snap
 acc = np.zeros(9); span = 0.0
 tot_all = []; worst = None; sub = np.zeros(30); sub_worst = None; sub_slow = np.zeros(30); ph_slow = np.zeros(9)
 slow_fill_rows = []   # per step: the slowest wave's [fills, per-fill wave stamps 24..29]
+tail = np.zeros(5); tail_slow = np.zeros(5)      # phase 7 (--info): reward | four conversions | obs + per-agent stores | lane-0 block | hand-back, clock, to the phase's end
+def tail_split(raw, i=None):
+    """raw: the int64 stamp rows.  Phase 7 from its first stamp (ph[7]) to its last (ph[8]) cut at the four inner stamps (tacc[9], tacc[13]: two low words each)"""
+    r = raw if i is None else raw[i:i + 1]
+    lo = lambda x: x & 0xffffffff
+    t7, t8 = lo(r[:, 7]), lo(r[:, 8])
+    cuts = [t7, lo(r[:, 19]), lo(r[:, 19] >> 32), lo(r[:, 23]), lo(r[:, 23] >> 32), t8]
+    return np.array([float((lo(b - a)).mean()) for a, b in zip(cuts[:-1], cuts[1:])])
 T, W = 300, 200
 calls = (C.c_ulonglong * 8)()
 if COUNTERS:
@@ -55,7 +68,8 @@ for t in range(W + T):
     sigma = torch.rand((N, A), generator=g, device="cuda:0")
     env.step(cat, mean, sigma, price, off)
     if t >= W:
-        b = buf.cpu().numpy().astype(np.float64)
+        raw = buf.cpu().numpy()
+        b = raw.astype(np.float64)
         d = b[:, 1:10] - b[:, 0:9]
         acc += d.mean(axis=0)
         span += (b[:, 9].max() - b[:, 0].min())
@@ -64,6 +78,8 @@ for t in range(W + T):
         tot_all.append(tw)
         i = int(tw.argmax())
         sub_slow += b[i, 10:40]; ph_slow += d[i]
+        if INFO:
+            tail += tail_split(raw); tail_slow += tail_split(raw, i)
         slow_fill_rows.append(b[i, 10:40].copy())
         if worst is None or tw[i] > worst[0]:
             worst = (tw[i], d[i].copy(), t, i); sub_worst = b[i, 10:40].copy()
@@ -79,8 +95,13 @@ per_step_max = np.array([x.max() for x in tot_all])
 print("max over the 4096 waves of one step: mean %.0f  (min %.0f, max %.0f)" % (per_step_max.mean(), per_step_max.min(), per_step_max.max()))
 print("slowest wave seen: %.0f cycles at step %d market %d; phases:" % (worst[0], worst[2], worst[3]), dict(zip(names, worst[1].astype(int).tolist())))
 
+if INFO:
+    tn = ["step_reward", "four conversions", "obs + per-agent stores", "lane-0 block", "hand-back test, clock"]
+    print("phase 7 (reward/info) split, cycles - mean wave:", {n: round(float(v) / T, 1) for n, v in zip(tn, tail)}, "sum %.1f" % (tail.sum() / T))
+    print("phase 7 (reward/info) split, cycles - the slowest wave of each step:", {n: round(float(v) / T, 1) for n, v in zip(tn, tail_slow)}, "sum %.1f" % (tail_slow.sum() / T))
+
 subn = ["approval", "find_own", "match+settle", "insert/remove(after match)", "cancel/escrow/other", "fills",
-        "book_remove/in-place", "release transfer", "escrow transfer", "x9", "n_modify", "n_escrow", "lane-0 fills in mode 0", "x13",
+        "book_remove/in-place", "release transfer", "escrow transfer", "(phase-7 stamps, packed)", "n_modify", "n_escrow", "lane-0 fills in mode 0", "(phase-7 stamps, packed)",
         "fill:prep(mode,tv)", "fill:stage1 mul", "fill:stage2 select", "fill:stage2 add", "fill:stage3 (modes 1, 2)", "fill:tail(sync,ballots)", "fills with lane 0 involved", "lane-0 fills in mode 3/4", "fill:stage3 (covered)", "fill:stage3 (neutral)"]
 # the old printout (its fill:* stamps accumulate on lane 0 only, i.e. only in fills that lane 0's account takes part in)
 print("orders phase breakdown, mean per wave per step:", {n: round(v / T, 1) for n, v in zip(subn, sub[:24])})
