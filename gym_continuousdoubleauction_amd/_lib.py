@@ -36,6 +36,8 @@ SYMBOLS = [
     "cda_quotes_enable", "cda_quotes_disable", "cda_quotes_capacity", "cda_quote_meta", "cda_quote_series", "cda_quote_stats", "cda_tape_spreads",
     "cda_quote_returns", "cda_tape_signs", "cda_tape_flow_returns", "cda_stylised_check_host",
     "cda_tape_pnl", "cda_tape_pnl_check_host",
+    "cda_depth_enable", "cda_depth_disable", "cda_depth_capacity", "cda_depth_levels", "cda_depth_meta", "cda_depth_series", "cda_depth_profile",
+    "cda_depth_imbalance", "cda_depth_ofi", "cda_depth_check_host",
 ]
 
 
@@ -259,6 +261,18 @@ def lib():
     L.cda_stylised_check_host.argtypes = [i32, vp, i32, i32, i32, i32]
     L.cda_tape_pnl.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp]
     L.cda_tape_pnl_check_host.argtypes = [i32, i32, i32, i32]
+    L.cda_depth_enable.argtypes = [vp, i64, i32]
+    L.cda_depth_disable.argtypes = [vp]
+    L.cda_depth_capacity.argtypes = [vp]
+    L.cda_depth_capacity.restype = i64
+    L.cda_depth_levels.argtypes = [vp]
+    L.cda_depth_levels.restype = i32
+    L.cda_depth_meta.argtypes = [vp, i32, i32, vp, vp]
+    L.cda_depth_series.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp]
+    L.cda_depth_profile.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+    L.cda_depth_imbalance.argtypes = [vp, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp]
+    L.cda_depth_ofi.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp, i32, vp, vp, vp, vp]
+    L.cda_depth_check_host.argtypes = [i32, i32, vp, i32, i32, i32, vp, i32]
     L.cda_mlp_forward_backward.argtypes = [vp, vp, vp, vp, i64, i64, vp, vp, i64, i32, f32, f32, f32, C.POINTER(PpoExtra), vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]
     L.cda_mlp_rollout_chain.argtypes = [vp, vp, vp, i32, i32, i32, u64, vp, C.POINTER(RolloutBufs), i32, vp]
     L.cda_mlp_selftest_mfma.argtypes = [i32, vp, vp, vp]

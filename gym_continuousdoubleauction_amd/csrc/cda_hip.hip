@@ -625,6 +625,8 @@ struct QuoteMeta {               // 32 B per market
     int32_t flags;               // bit 0: the current episode's head was never recorded (partial); bit 1: the previous one's
 };
 struct QuoteArgs { uint4* ring; QuoteMeta* meta; uint32_t cap; uint32_t pad; };      // ring: uint4[n_markets][cap][2]
+// the depth tape (include/cda.h cda_depth_*, csrc/cda_depth.inc): the quote tape's meta rows and episode rule over rings of 1 + levels 16-byte words per record
+struct DepthArgs { uint4* ring; QuoteMeta* meta; uint32_t cap; uint32_t levels; };   // ring: uint4[n_markets][cap][1 + levels]
 struct cda_env {
     Params P;
     int device;
@@ -648,11 +650,15 @@ struct cda_env {
     cda::SchedArgs sched;    // cda_schedule_attach: the caller's resident order schedule and the env's own counters table (sched_of == NULL: nothing attached - no launch)
     int64_t sched_epoch;     // moved by every cda_schedule_attach / cda_schedule_detach
     QuoteArgs quotes;        // cda_quotes_enable: the quote tape's rings and meta rows (ring == NULL: off - no launch)
+    DepthArgs depth;         // cda_depth_enable: the depth tape's rings and meta rows (ring == NULL: off - no launch)
     int64_t one_launch_steps;   // cda_policy_step_launch_count: k_policy_step / k_net_step launches enqueued since cda_create (host side; a captured enqueue counts once)
 };
 // csrc/cda_quotes.inc (included at the end): the top of the book of [first, first + n), recorded on `stream` ahead of a step; a no-op while quotes are off
 static int quotes_record(cda_env* e, int32_t first, int32_t n, hipStream_t stream);
 static void quotes_free(cda_env* e);
+// csrc/cda_depth.inc (included at the end): the ladder of [first, first + n), recorded on `stream` behind the quotes and ahead of a step; a no-op while depth is off
+static int depth_record(cda_env* e, int32_t first, int32_t n, hipStream_t stream);
+static void depth_free(cda_env* e);
 // csrc/cda_schedule.inc (included at the end): the attached order schedule's windows of [first, first + n), queued on `stream` ahead of a step; a no-op while none is attached
 static int schedule_play(cda_env* e, int32_t first, int32_t n, hipStream_t stream);
 static void schedule_free(cda_env* e);
@@ -834,6 +840,7 @@ static void env_free(cda_env* e) {
     tape_free(e);
     schedule_free(e);
     quotes_free(e);
+    depth_free(e);
     if (e->rows) (void)hipFree(e->rows);
     free(e->rows_host);
     free(e);
@@ -974,6 +981,7 @@ int cda_reset(cda_env* e, const uint64_t* seeds, const uint8_t* mask, float* obs
 static int launch_step(cda_env* e, int32_t first, int32_t n, const StepArgs& S0, hipStream_t stream) {
     if (e->sched.sched_of) { const int rcs = schedule_play(e, first, n, stream); if (rcs) return rcs; }      // an attached order schedule: the markets' windows first
     if (e->quotes.ring) { const int rcq = quotes_record(e, first, n, stream); if (rcq) return rcq; }          // quotes on: the book as this step's orders meet it
+    if (e->depth.ring) { const int rcd = depth_record(e, first, n, stream); if (rcd) return rcd; }            // depth on: the same book, its ladder
     StepArgs S = S0;
     S.first_market = first; S.end_market = first + n;
     // the instance by (trade tape on, info tensors, episode-metric tallies: their code is not even in the instances without)
@@ -1089,7 +1097,7 @@ static int grant_policy_step_lds(const cda_env* e) {
 int cda_policy_step_supported(const cda_env* e) {
     if (!e) return 0;
     const int lds = e->cap == 256 ? policy_step_of(e).lds : 0;
-    return lds > 0 && lds <= 160 * 1024 && e->P.cfg.num_agents <= 8 && !e->handback && !e->tape.ring && !e->script.slot && !e->label.slot && !e->sched.sched_of && !e->quotes.ring;      // (no k_policy_step instance writes the trade tape, asks a scripted law, plays an order schedule or records quotes)
+    return lds > 0 && lds <= 160 * 1024 && e->P.cfg.num_agents <= 8 && !e->handback && !e->tape.ring && !e->script.slot && !e->label.slot && !e->sched.sched_of && !e->quotes.ring && !e->depth.ring;      // (no k_policy_step instance writes the trade tape, asks a scripted law, plays an order schedule or records quotes or depth)
 }
 // ... and whether it pays: every workgroup of k_policy_step streams the whole network for its sixteen rows, so the one launch wins while all of the env's
 // workgroups are resident at once (N <= 16 x CUs: 4096 markets on an MI355X - policy in the loop 278 -> 301-308 M at 4096 x 4) and loses to the batched policy
@@ -1262,7 +1270,7 @@ int cda_run_random(cda_env* e, int32_t n_steps, uint64_t action_seed, uint64_t m
                    int32_t* steps_taken_out, void* stream) {
     if (!e || n_steps < 0) return CDA_ERR_INVALID;
     if (e->sched.sched_of) return CDA_ERR_UNSUPPORTED;               // (k_run_random steps inside one launch: it cannot play an order schedule between its steps)
-    if (e->quotes.ring) return CDA_ERR_UNSUPPORTED;                  // (... nor record the quotes between them)
+    if (e->quotes.ring || e->depth.ring) return CDA_ERR_UNSUPPORTED; // (... nor record the quotes or the depth between them)
     HIPCHK(hipSetDevice(e->device));
     RunArgs R;
     R.n_steps = n_steps; R.seed = action_seed; R.market_base = market_index_base;
@@ -1705,3 +1713,5 @@ int64_t cda_state_bytes_per_market(const cda_env* e) { return e ? (int64_t)e->P.
 #include "cda_tape_pnl.inc"
 // the label tap (cda_label_*): a law's answer for slots it does not play, beside a rollout's buffers - one walk of the book serves the attached table and the label table
 #include "cda_scripted_label.inc"
+// the depth tape (cda_depth_*): the Level-2 ladder per step, recorded behind the quotes and ahead of every step, and the book-shape reductions over it
+#include "cda_depth.inc"

@@ -13,7 +13,7 @@ the greedy chains); mode="sample" runs the same loop on the sampling kernels.
 CLI: python -m gym_continuousdoubleauction_amd.evaluate --policy P [--opponent random|FILE ...] --markets --agents --max-step --episodes --trained-slots
      (a scripted opponent: pass | maker | taker | imbalance | NAME:key=value,...)
      [--sample] --seed --out JSON [--tape FILE.npz [--exec-report K[,K...]] [--spread-report K[,K...]]] [--quotes FILE.npz]
-     [--stylised-facts L[,L...] [--bar-steps K]] [--pnl-report [--bar-steps K]]
+     [--stylised-facts L[,L...] [--bar-steps K]] [--pnl-report [--bar-steps K]] [--depth FILE.npz --depth-levels L] [--book-shape-report [--bar-steps K]]
 """
 import argparse
 import dataclasses
@@ -199,8 +199,41 @@ def _stylised_report(env, lags, bar_steps, episode0, keep):
     return block
 
 
+BOOK_SHAPE_MAX_DIST, BOOK_SHAPE_HALF = 32, 8                         # evaluate(book_shape_report=True): the shape's distance bins (ticks, the last clipped) and 2 x 8 imbalance bins
+BOOK_SHAPE_LAGS, BOOK_SHAPE_OFI_LAGS = (1, 2, 5, 10), (0, 1, 2, 5)   # ... the response curve's lags (steps) and the OFI regression's (bars)
+
+
+def _book_shape_report(env, bar_steps, keep):
+    """evaluate(book_shape_report=True): the three depth reductions (CDAVecEnv.depth_profile / depth_imbalance / depth_ofi) of every market's previous episode,
+    pooled over the markets that have one (a book belongs to no module: ONE block) and read through depth.summary, the pooled integer rows beside the figures."""
+    from . import depth as D
+    L = env.depth_levels
+    depths = sorted({1, min(5, L), L})
+    prof = env.depth_profile(BOOK_SHAPE_MAX_DIST, episode="previous")
+    imb = env.depth_imbalance(BOOK_SHAPE_LAGS, L, BOOK_SHAPE_HALF, episode="previous")
+    ofi = env.depth_ofi(BOOK_SHAPE_OFI_LAGS, bar_steps, depths, episode="previous")
+    counted = prof[3][:, 0] > 0                                      # the markets whose ring holds something of a finished episode
+
+    def pooled(t):
+        return D.pool(t[counted]).cpu().numpy()
+    tick = int(env.market_rows()["tick_size"].max()) if env.per_market else int(env.config.get("tick_size", 1))
+    block = D.summary(profile=[pooled(t) for t in prof[:3]], imbalance=[pooled(t) for t in imb[:2]], ofi=[pooled(t) for t in ofi[:2]], lags=BOOK_SHAPE_LAGS,
+                      ofi_lags=BOOK_SHAPE_OFI_LAGS, depths=depths, tick=tick)
+    sel, info = counted.cpu().numpy(), prof[3].cpu().numpy()
+    block["about"] = {"levels": L, "max_dist": BOOK_SHAPE_MAX_DIST, "half": BOOK_SHAPE_HALF, "lags": list(BOOK_SHAPE_LAGS), "ofi_lags": list(BOOK_SHAPE_OFI_LAGS),
+                      "depths": depths, "bar_steps": int(bar_steps), "episode": "previous", "markets": int(sel.sum()), "records": int(info[sel, 0].sum()),
+                      "records_lost": int(info[sel, 1].sum()), "partial_markets": int((info[sel, 3] != 0).sum())}
+    block["rows"] = {"profile": pooled(prof[0]).tolist(), "levels": pooled(prof[1]).tolist(), "shape": pooled(prof[2]).tolist(), "response": pooled(imb[0]).tolist(),
+                     "imbalance": pooled(imb[1]).tolist(), "ofi_lagged": pooled(ofi[0]).tolist(), "ofi": pooled(ofi[1]).tolist()}
+    if keep is not None:
+        keep["depth_tables"] = {"profile": [t.cpu().numpy() for t in prof], "imbalance": [t.cpu().numpy() for t in imb], "ofi": [t.cpu().numpy() for t in ofi],
+                                "counted": sel, "depths": depths}
+    return block
+
+
 def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="greedy", seed=0, groups=None, keep=None, tape=None, tape_capacity=4096,
-             exec_horizons=None, quotes=None, spread_horizons=None, stylised_facts=None, bar_steps=1, pnl_report=False):
+             exec_horizons=None, quotes=None, spread_horizons=None, stylised_facts=None, bar_steps=1, pnl_report=False, depth=None, depth_levels=10,
+             book_shape_report=False):
     """Play `policy` (a FusedPolicy or a policy file) on `env` (a CDAVecEnv with auto_reset) for episodes * max_step steps; return per-module results.
     opponents: None = self-play; else a list of "random", FusedPolicy objects, policy files or scripted opponents - "pass", "maker", "taker", "imbalance",
     "NAME:key=value,..." or a scripted.Profile (rule-based agents on the device: their slots carry LEAGUE_RANDOM in slot_net and their profile in the env's slot_script,
@@ -234,7 +267,14 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
     pnl_report (needs `tape`; the quotes are recorded whether or not `quotes` names a file; bar_steps: the bar size): add a "pnl" block to every module - what its
     slots' mark-to-mid P&L did over every market's last finished episode: P&L and its split into inventory and trading, drawdown, bar P&L mean / std, Sharpe, hit
     ratio, time under water (CDAVecEnv.tape_pnl on the device, folded by pnl.pnl_by_module, read through pnl.pnl_summary, the integer row beside the figures) -
-    and result["pnl"], which says what it covers, as the spread report does."""
+    and result["pnl"], which says what it covers, as the spread report does.
+    depth (a path, optional; depth_levels: the levels per side, 1 .. 16): record the Level-2 ladder ahead of every step of the evaluated episodes on the device
+    (CDAVecEnv.enable_depth, two episodes of capacity; neither other tape is needed) and save every market's last finished episode as an .npz (depth.save): records
+    i32 [N, max_step, (1 + levels) * 4] with `levels`, `counts`, `info`, `modules` and `module_names`.  The env's depth tape must be OFF; it is off again afterwards.
+    book_shape_report (the ladders are recorded whether or not `depth` names a file; bar_steps: the OFI's bar size): add result["depth"] - the average shape of the
+    book, the future mid move given the depth imbalance and the multi-level order-flow-imbalance regression of every market's last finished episode
+    (CDAVecEnv.depth_profile, depth_imbalance, depth_ofi on the device), pooled over the markets (a book belongs to no module) and read through depth.summary,
+    with the pooled integer rows and what they cover ("about")."""
     from .mlp import LEAGUE_RANDOM, FusedPolicy, PolicyBank, RolloutChains, read_policy
     if mode not in ("greedy", "sample"):
         raise ValueError(f"mode must be 'greedy' or 'sample' (got {mode!r})")
@@ -264,6 +304,17 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
         top = int(env.market_rows()["max_step"].max()) if env.per_market else int(env.max_step)
         if n_points(top, bar_steps) > MAX_BARS:
             raise ValueError(f"evaluate(stylised_facts=...): an episode of {top} steps has more than {MAX_BARS} bars of {bar_steps} steps: raise bar_steps")
+    with_depth = depth is not None or bool(book_shape_report)
+    if with_depth:
+        from .depth import _levels as _depth_levels
+        from .stylised import MAX_BARS, _bar_steps, n_points
+        depth_levels, bar_steps = _depth_levels(depth_levels), _bar_steps(bar_steps)
+        top = int(env.market_rows()["max_step"].max()) if env.per_market else int(env.max_step)
+        if book_shape_report and n_points(top, bar_steps) > MAX_BARS:
+            raise ValueError(f"evaluate(book_shape_report=True): an episode of {top} steps has more than {MAX_BARS} bars of {bar_steps} steps: raise bar_steps")
+        if env.depth_enabled:
+            raise ValueError("evaluate(depth=... / book_shape_report=True) needs an env whose depth tape is off: it enables one of its own for the evaluated episodes "
+                             "(disable_depth() first)")
     with_tape = tape is not None or stylised_facts is not None
     with_quotes = quotes is not None or spread_horizons is not None or stylised_facts is not None or bool(pnl_report)
     if with_quotes and env.quotes_enabled:
@@ -309,6 +360,8 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
         env.enable_tape(tape_capacity)                                  # (likewise: the chains' graphs hold the tape-writing step instances)
     if with_quotes:
         env.enable_quotes(min(1 << 20, 2 * max(1, int(env.max_step))))  # (likewise: the recorder's launch; the finished episode and the running one both fit)
+    if with_depth:
+        env.enable_depth(min(1 << 20, 2 * max(1, int(env.max_step))), depth_levels)      # (likewise)
     tape_parts, tape_dropped = [], np.zeros(N, np.int64)
     try:
         if opp is None:
@@ -375,6 +428,13 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
         pnl_rep = None
         if pnl_report:
             pnl_rep = _pnl_report(env, bar_steps, module_of, names, tape_ep0, keep)
+        depth_rep = None
+        if book_shape_report:
+            depth_rep = _book_shape_report(env, bar_steps, keep)
+        if depth is not None:
+            from .depth import save as save_depth
+            rec, cnt, dinfo = env.depth_series(int(env.max_step), episode="previous")
+            save_depth(depth, rec, depth_levels, counts=cnt, info=dinfo, modules=modules.astype(np.int32), module_names=np.array(names))
         if quotes is not None:
             from .quotes import save as save_quotes
             rec, cnt, qinfo = env.quote_series(int(env.max_step), episode="previous")
@@ -392,6 +452,8 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
             env.disable_tape()
         if with_quotes and env.quotes_enabled:
             env.disable_quotes()
+        if with_depth and env.depth_enabled:
+            env.disable_depth()
         if scripts and env.scripted:
             env.clear_scripted()
     table_h, env_h = table.cpu().numpy(), env_row.cpu().numpy()
@@ -426,6 +488,8 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
         result["pnl"] = pnl_rep["about"]
         for name in names:
             mods[name]["pnl"] = pnl_rep["modules"][name]
+    if depth_rep is not None:
+        result["depth"] = depth_rep
     if keep is not None:
         keep["chains"], keep["modules"], keep["tables"] = chains, modules, (table_h, env_h)
         keep["actions"] = {key: torch.cat([a[key] for a in acts]) for key in acts[0]}
@@ -453,9 +517,14 @@ def main(argv=None):
     p.add_argument("--stylised-facts", default=None, metavar="L[,L...]", help="add the stylised-facts block - return autocorrelations, volatility clustering, tails, order-flow "
                    "sign persistence, price impact of signed volume - at these lags, reduced on the device from every market's last finished episode (switches the trade "
                    "tape and the quote tape on)")
-    p.add_argument("--bar-steps", type=int, default=1, metavar="K", help="with --stylised-facts / --pnl-report: the bar size in env steps (default 1)")
+    p.add_argument("--bar-steps", type=int, default=1, metavar="K", help="with --stylised-facts / --pnl-report / --book-shape-report: the bar size in env steps (default 1)")
     p.add_argument("--pnl-report", action="store_true", help="with --tape: add per-module P&L, its inventory / trading split, drawdown, bar P&L moments, Sharpe and hit "
                    "ratio - every agent's mark-to-mid equity curve, reduced on the device from every market's last finished episode (switches the quote tape on)")
+    p.add_argument("--depth", default=None, metavar="FILE.npz", help="record the Level-2 ladder ahead of every step (the depth tape) and save every market's last finished episode")
+    p.add_argument("--depth-levels", type=int, default=10, metavar="L", help="with --depth / --book-shape-report: price levels per side, 1 .. 16 (default 10)")
+    p.add_argument("--book-shape-report", action="store_true", help="add the pooled depth block - the average shape of the book, the mid's response to depth imbalance and "
+                   "the multi-level order-flow-imbalance regression (bars of --bar-steps), reduced on the device from every market's last finished episode (switches the "
+                   "depth tape on)")
     p.add_argument("--order-schedule", default=None, metavar="FILE.npz", help="attach this order schedule (orders.save_schedule) to the env: per-step order flow played ahead "
                    "of every step of the evaluated episodes")
     args = p.parse_args(argv)
@@ -493,7 +562,8 @@ def main(argv=None):
             env.load_order_schedule(args.order_schedule)
         res = evaluate(env, args.policy, opponents=args.opponent, trained_slots=args.trained_slots, episodes=args.episodes,
                        mode="sample" if args.sample else "greedy", seed=args.seed, tape=args.tape, exec_horizons=exec_horizons,
-                       quotes=args.quotes, spread_horizons=spread_horizons, stylised_facts=stylised_facts, bar_steps=args.bar_steps, pnl_report=args.pnl_report)
+                       quotes=args.quotes, spread_horizons=spread_horizons, stylised_facts=stylised_facts, bar_steps=args.bar_steps, pnl_report=args.pnl_report,
+                       depth=args.depth, depth_levels=args.depth_levels, book_shape_report=args.book_shape_report)
     finally:
         env.close()
     res.pop("summary")

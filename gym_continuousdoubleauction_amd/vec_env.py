@@ -47,6 +47,7 @@ class CDAVecEnv:
         self.tape_epoch = 0                 # bumped by enable_tape / disable_tape: graphs captured on this env's step launches hold the setting they were captured under
         self._tape_cursor = None            # drain_tape's default cursor (i64 [N], device) while the tape is on
         self.quote_epoch = 0                # bumped by enable_quotes / disable_quotes: captured graphs hold the recorder's launch (or none) of their capture
+        self.depth_epoch = 0                # bumped by enable_depth / disable_depth: likewise for the depth recorder's launch
         self.script_epoch = 0               # bumped by set_scripted / clear_scripted: graphs captured on this env's rollout chains hold the scripted launches (or none) of then
         self._script = None                 # set_scripted: an AttachedScripts (None while nothing is attached)
         self._schedule = None               # set_order_schedule: an AttachedSchedule (None while nothing is attached)
@@ -885,6 +886,122 @@ class CDAVecEnv:
         from .quotes import as_quotes
         rec, cnt, _ = self.quote_series(None, episode, int(market), 1)
         return as_quotes(rec[0, :int(cnt[0].item())].cpu().numpy()).copy()
+
+    # ------------------------------------------------------------------ the depth tape: the Level-2 ladder per step, recorded on the device (depth.py)
+    @property
+    def depth_enabled(self):
+        return int(lib().cda_depth_capacity(self._h)) > 0
+
+    @property
+    def depth_capacity(self):
+        return int(lib().cda_depth_capacity(self._h))
+
+    @property
+    def depth_levels(self):
+        return int(lib().cda_depth_levels(self._h))
+
+    def enable_depth(self, capacity=1024, levels=10):
+        """From now on every step entry point first records, per market whose episode is not over, the best `levels` price levels of both sides of the book the
+        step's orders will meet - price and summed volume per level (depth.record_dtype(levels)) - into the market's ring of `capacity` records on the device
+        (include/cda.h cda_depth_enable), behind an attached order schedule's window and the quote recorder and ahead of the step.  Off by default; rings start
+        empty; it needs neither the quote tape nor the trade tape.  While it is on the one-launch policy step is off (rollout chains take their two-launch path) and
+        run_random is refused.  Do not toggle it between the capture and the replay of a graph that holds this env's step launches (mlp.RolloutChains checks)."""
+        from .depth import MAX_LEVELS
+        capacity, levels = int(capacity), int(levels)
+        if not 1 <= capacity <= (1 << 20) or not 1 <= levels <= MAX_LEVELS:
+            raise ValueError(f"depth capacity must be in 1 .. {1 << 20} steps and levels in 1 .. {MAX_LEVELS}, got {capacity}, {levels}")
+        self.sync()
+        check(lib().cda_depth_enable(self._h, capacity, levels), "cda_depth_enable")
+        self.depth_epoch += 1                                     # (captured graphs of this env's step launches are stale from here on)
+
+    def disable_depth(self):
+        self.sync()
+        check(lib().cda_depth_disable(self._h), "cda_depth_disable")
+        self.depth_epoch += 1
+
+    def _need_depth(self, what):
+        if not self.depth_enabled:
+            raise RuntimeError(f"{what} needs the depth tape: call enable_depth() first (it is off by default)")
+
+    def depth_meta(self, first_market=0, n_markets=None):
+        """Every market's meta row of the depth tape as the readers see it - rolled to the market's clock by the episode rule (quotes.roll) - i32 [n, 8], a device
+        tensor; quotes.meta_from_words names the words, quotes.span says what the ring holds of either episode."""
+        self._need_depth("depth_meta()")
+        first, n = self._market_range("depth_meta", first_market, n_markets)
+        return self._reader_call(lib().cda_depth_meta, "cda_depth_meta", first, n, (), (torch.empty((n, 8), dtype=torch.int32, device=self.device),), info=False)[0]
+
+    def depth_series(self, k=None, episode="current", first_market=0, n_markets=None):
+        """The held ladders of one remembered episode, oldest first (include/cda.h cda_depth_series): (records i32 [n, k, (1 + levels) * 4] - depth.as_depth names
+        the words; rows beyond the count are zero -, counts i32 [n], info i32 [n, 4] = records returned, records of the episode's head the ring had overwritten,
+        step of the first returned record, partial flag), device tensors.  An episode longer than k returns its LAST k records.  k defaults to the smaller of the
+        ring's capacity and the largest max_step."""
+        self._need_depth("depth_series()")
+        first, n = self._market_range("depth_series", first_market, n_markets)
+        which = self._tape_which(episode)
+        if k is None:
+            k = max(1, min(self.depth_capacity, self._top_max_step()))
+        if int(k) < 1:
+            raise ValueError(f"depth_series: k must be >= 1, got {k}")
+        return self._reader_call(lib().cda_depth_series, "cda_depth_series", first, n, (which, int(k)),
+                                 (torch.empty((n, int(k), 4 * (1 + self.depth_levels)), dtype=torch.int32, device=self.device),
+                                  torch.empty(n, dtype=torch.int32, device=self.device)))
+
+    def depth_episode(self, market=0, episode="current"):
+        """One market's held ladders of an episode, oldest first, as a structured host array (depth.record_dtype(levels))."""
+        from .depth import as_depth
+        rec, cnt, _ = self.depth_series(None, episode, int(market), 1)
+        return as_depth(rec[0, :int(cnt[0].item())].cpu().numpy(), self.depth_levels).copy()
+
+    def depth_profile(self, max_dist=32, episode="current", first_market=0, n_markets=None):
+        """The average shape of the book over one remembered episode's held ladders, reduced on the device in one launch (include/cda.h cda_depth_profile;
+        depth.profile_from_records is its specification, word for word).  -> (base i64 [n, 8] - depth.PROFILE_FIELDS -, levels i64 [n, 2, L, 3] - per side and
+        level index steps, volume, distance in ticks from the side's best -, shape i64 [n, 2, max_dist + 1] - volume by distance, the last bin holds the clipped
+        mass -, info i32 [n, 4] as quote_stats), device tensors.  Every word is additive: depth.pool sums over markets, depth.summary reads the ratios."""
+        from .depth import MAX_DIST
+        self._need_depth("depth_profile()")
+        first, n = self._market_range("depth_profile", first_market, n_markets)
+        which = self._tape_which(episode)
+        if not 1 <= int(max_dist) <= MAX_DIST:
+            raise ValueError(f"depth_profile: max_dist must be in 1 .. {MAX_DIST}, got {max_dist}")
+        L = self.depth_levels
+        return self._reader_call(lib().cda_depth_profile, "cda_depth_profile", first, n, (which, int(max_dist)),
+                                 (torch.empty((n, 8), dtype=torch.int64, device=self.device), torch.empty((n, 2, L, 3), dtype=torch.int64, device=self.device),
+                                  torch.empty((n, 2, int(max_dist) + 1), dtype=torch.int64, device=self.device)))
+
+    def depth_imbalance(self, lags=(1, 2, 5, 10), k=None, half=8, episode="current", first_market=0, n_markets=None):
+        """The future mid move given today's depth imbalance, over one remembered episode's held ladders, reduced on the device in one launch (include/cda.h
+        cda_depth_imbalance; depth.imbalance_from_records is its specification, word for word).  -> (resp i64 [n, n_lags, 2 half, 5] - per lag and imbalance bin
+        depth.RESPONSE_FIELDS: n, sum r, sum r^2, up, down -, base i64 [n, 4] - depth.IMBALANCE_FIELDS -, info i32 [n, 4] as quote_stats), device tensors.  The
+        imbalance is taken over the first k levels (default: all recorded); lags: 1 .. 8 values >= 1, in steps."""
+        from .depth import MAX_HIST_HALF, _lags
+        self._need_depth("depth_imbalance()")
+        first, n = self._market_range("depth_imbalance", first_market, n_markets)
+        which = self._tape_which(episode)
+        lg = _lags(lags, 1)
+        k = self.depth_levels if k is None else int(k)
+        if not 1 <= k <= self.depth_levels or not 1 <= int(half) <= MAX_HIST_HALF:
+            raise ValueError(f"depth_imbalance: k must be in 1 .. {self.depth_levels} and half in 1 .. {MAX_HIST_HALF}, got {k}, {half}")
+        return self._reader_call(lib().cda_depth_imbalance, "cda_depth_imbalance", first, n, (which, (C.c_int32 * len(lg))(*lg), len(lg), k, int(half)),
+                                 (torch.empty((n, len(lg), 2 * int(half), 5), dtype=torch.int64, device=self.device),
+                                  torch.empty((n, 4), dtype=torch.int64, device=self.device)))
+
+    def depth_ofi(self, lags=(0, 1, 5), bar_steps=1, depths=(1,), episode="current", first_market=0, n_markets=None):
+        """Multi-level order-flow imbalance joined to returns, bar by bar, of one remembered episode's held ladders, reduced on the device in one launch
+        (include/cda.h cda_depth_ofi; depth.ofi_from_records is its specification, word for word).  -> (lagged i64 [n, n_depths, n_lags, 6] - depth.OFI_LAG_FIELDS
+        per depth K and lag l >= 0 over the kept bars b whose return r_(b + l) is defined: n, q = sum OFI_b, r, qr, qq, rr -, base i64 [n, 4] - depth.OFI_FIELDS:
+        pairs used, bars kept, bars excluded, saturated records -, info i32 [n, 4] as quote_stats), device tensors.  depths: 1 .. 4 values in 1 .. levels."""
+        from .depth import MAX_DEPTHS, _lags
+        self._need_depth("depth_ofi()")
+        first, n = self._market_range("depth_ofi", first_market, n_markets)
+        which = self._tape_which(episode)
+        lg = _lags(lags, 0)
+        dp = [int(x) for x in depths]
+        if not 1 <= len(dp) <= MAX_DEPTHS or min(dp) < 1 or max(dp) > self.depth_levels:
+            raise ValueError(f"depth_ofi: depths must be 1 .. {MAX_DEPTHS} values in 1 .. {self.depth_levels}, got {depths!r}")
+        bar = self._stylised_points("depth_ofi", first, n, bar_steps)
+        return self._reader_call(lib().cda_depth_ofi, "cda_depth_ofi", first, n, (which, (C.c_int32 * len(lg))(*lg), len(lg), bar, (C.c_int32 * len(dp))(*dp), len(dp)),
+                                 (torch.empty((n, len(dp), len(lg), 6), dtype=torch.int64, device=self.device),
+                                  torch.empty((n, 4), dtype=torch.int64, device=self.device)))
 
     # ------------------------------------------------------------------ the book report: reductions over the standing book, on the device
     def _book_call(self, name, first_market, n_markets, shape, dtype, *mid):

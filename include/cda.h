@@ -789,6 +789,87 @@ int cda_tape_flow_returns(cda_env* env, int32_t first_market, int32_t n_markets,
                           int64_t* lagged_out_dev, int64_t* base_out_dev, int32_t* info_out_dev, void* stream);
 int cda_stylised_check_host(int32_t kind, const int32_t* lags_host, int32_t n_lags, int32_t bar_steps, int32_t hist_half, int32_t max_step);
 
+/* ---- depth tape: the Level-2 ladder per step, recorded on the device, and the book-shape reports -----------------------------------------
+ * The quote tape keeps one level per side over time, cda_book_levels the whole ladder at one instant; this keeps the ladder over time.
+ * cda_depth_enable(env, capacity_steps, levels): from now on every step launch of this env first records, for every market of its range whose
+ * episode is not over, the best `levels` price levels of both sides (1 .. CDA_DEPTH_MAX_LEVELS) into the market's ring of `capacity_steps`
+ * records (1 .. CDA_QUOTE_CAP_MAX; n_markets x capacity x (1 + levels) x 16 bytes of its own beside the arena; CDA_ERR_NOMEM leaves the env as
+ * it was).  The recorder's launch runs behind the order schedule's and the quote recorder's and ahead of the step kernel.  OFF by default;
+ * enable / disable are synchronous, as cda_quotes_enable is, and everything said there of graphs, cda_policy_step_supported (0 while on),
+ * cda_run_random (CDA_ERR_UNSUPPORTED while on), snapshots and state dumps (unchanged) holds.  The service needs neither other tape.
+ * A record is 1 + levels 16-byte words.  Word 0 = (step, flags, bid_levels, ask_levels): the counts are the levels recorded of the side, at most
+ * `levels`; flags CDA_DEPTH_BID / CDA_DEPTH_ASK: the side has a level; CDA_DEPTH_SATURATED: a volume above INT32_MAX was stored as INT32_MAX;
+ * CDA_DEPTH_BID_MORE / CDA_DEPTH_ASK_MORE: the side has more than `levels` levels.  Word 1 + l = cda_depth_level l = (bid_price, bid_volume,
+ * ask_price, ask_volume), best first, prices as the book holds them; rows at or beyond a side's count are zero.
+ * Episodes: the quote tape's meta row and its ONE rule (above), over rows and rings of this service's own.
+ *   cda_depth_meta       the rolled meta rows -> meta_out_dev i32 [n][8].
+ *   cda_depth_series     the last k held records of the episode `which`, oldest first -> records_out_dev i32 [n][k][(1 + levels) x 4] (16-B aligned;
+ *                        rows beyond the count are zero), counts_out_dev i32 [n] and info_out_dev i32 [n][4] (either may be NULL) as cda_quote_series.
+ * Three reductions, one launch each, a wave per market, exact int64, every output word additive (two's-complement wrap): a fold over markets,
+ * episodes or ranks is a plain sum; depth.py states every word in numpy.  m2(s) = bid_price[0] + ask_price[0] of the held record of step s, defined
+ * iff that record is two-sided; tick = the tick_size of the market's own row (prices are multiples of it); a level at or beyond a side's count is
+ * absent.  info_out_dev i32 [n][4] (may be NULL): {records aggregated, records lost to the ring, step of the first held record, partial}.
+ *   cda_depth_profile    1 <= max_dist <= CDA_DEPTH_MAX_DIST.  base_out_dev i64 [n][8]: held steps, two-sided steps, bid-more steps, ask-more steps,
+ *                        saturated steps, sum of bid_levels, sum of ask_levels, 0.  levels_out_dev i64 [n][2][levels][3], per side and level index over
+ *                        the held records where that level exists: steps, sum of volume, sum of |price_l - price_0| / tick.  shape_out_dev i64
+ *                        [n][2][max_dist + 1]: volume by distance d = |price_l - price_0| / tick from the same side's best, in bin min(d, max_dist).
+ *   cda_depth_imbalance  1 <= k <= levels, 1 <= half <= CDA_STYL_MAX_HIST_HALF, lags in 1 .. CDA_STYL_MAX_LAG.  B, A = the bid / ask volume of the first k
+ *                        levels; bin = floor(2 B half / (B + A)) over the two-sided records (0 .. 2 half - 1).  resp_out_dev i64 [n][n_lags][2 half][5],
+ *                        per lag l over the steps s whose record is two-sided and whose r = m2(s + l) - m2(s) is defined: n, sum r, sum r^2, up, down.
+ *                        base_out_dev i64 [n][4]: held steps, two-sided steps, sum of B - A, sum of B + A over the two-sided steps.
+ *   cda_depth_ofi        multi-level order-flow imbalance against returns, bar by bar.  For consecutive held records s - 1 (primed) and s and level m:
+ *                        e_m(s) = [Pb >= Pb'] qb - [Pb <= Pb'] qb' - [Pa <= Pa'] qa + [Pa >= Pa'] qa'; an absent bid level reads as (0, 0), an absent
+ *                        ask level as (INT32_MAX, 0).  OFI_K(s) = sum of e_m(s) over m < K, K = depths_host[j] in 1 .. levels, 1 <= n_depths <=
+ *                        CDA_DEPTH_MAX_DEPTHS.  Bars, points and returns as cda_tape_flow_returns / cda_quote_returns define them, from this tape's m2;
+ *                        OFI_b = the sum over the pairs whose step s lies in bar b (an episode's first step has no pair).  Where the episode's head is
+ *                        not held (lost to the ring, or partial) every bar up to and including the bar of the first held step is excluded and counted
+ *                        (no record held: every word is zero).
+ *                        lagged_out_dev i64 [n][n_depths][n_lags][6], per lag l >= 0 over the kept bars b whose r_(b + l) is defined: n, q = sum OFI_b,
+ *                        r, qr, qq, rr.  base_out_dev i64 [n][4]: pairs used (in the kept bars that are complete: all their steps held), those bars,
+ *                        bars excluded, saturated records held.  Exact while bid + ask < 2^31, |OFI_b| < 2^31 (a bar's word is int32 and wraps, in
+ *                        the specification alike) and no sum leaves int64: at most 2^12 bars, so |r| < 2^25 and |OFI_b| < 2^25 always suffice.
+ *   cda_depth_check_host the argument check the three make, on the host alone: kind = CDA_DEPTH_PROFILE / _IMBALANCE / _OFI; levels = the service's;
+ *                        a = max_dist / k / bar_steps, b = unused / half / max_step (the largest of the range); CDA_OK or CDA_ERR_INVALID.
+ * A NULL pointer, a misaligned output (records 16 B, int64 8 B, int32 4 B), a range outside the env, another `which` or a parameter out of bounds:
+ * CDA_ERR_INVALID; depth off: CDA_ERR_UNSUPPORTED from the readers.  Nothing is launched behind a refusal. */
+#define CDA_DEPTH_MAX_LEVELS 16
+#define CDA_DEPTH_MAX_DIST   256
+#define CDA_DEPTH_MAX_DEPTHS 4
+#define CDA_DEPTH_BID        1
+#define CDA_DEPTH_ASK        2
+#define CDA_DEPTH_SATURATED  4
+#define CDA_DEPTH_BID_MORE   8
+#define CDA_DEPTH_ASK_MORE   16
+#define CDA_DEPTH_PROFILE    0
+#define CDA_DEPTH_IMBALANCE  1
+#define CDA_DEPTH_OFI        2
+typedef struct cda_depth_head {        /* word 0 of a record */
+    int32_t step;                      /* the env step index t of the episode: the book as step t's orders meet it */
+    int32_t flags;                     /* CDA_DEPTH_* */
+    int32_t bid_levels;                /* levels recorded of the side: min(the side's levels, `levels`) */
+    int32_t ask_levels;
+} cda_depth_head;
+typedef struct cda_depth_level {       /* word 1 + l of a record */
+    int32_t bid_price;
+    int32_t bid_volume;
+    int32_t ask_price;
+    int32_t ask_volume;
+} cda_depth_level;
+int cda_depth_enable(cda_env* env, int64_t capacity_steps, int32_t levels);
+int cda_depth_disable(cda_env* env);
+int64_t cda_depth_capacity(const cda_env* env);
+int32_t cda_depth_levels(const cda_env* env);
+int cda_depth_meta(cda_env* env, int32_t first_market, int32_t n_markets, int32_t* meta_out_dev, void* stream);
+int cda_depth_series(cda_env* env, int32_t first_market, int32_t n_markets, int32_t which, int32_t k, void* records_out_dev, int32_t* counts_out_dev,
+                     int32_t* info_out_dev, void* stream);
+int cda_depth_profile(cda_env* env, int32_t first_market, int32_t n_markets, int32_t which, int32_t max_dist, int64_t* base_out_dev, int64_t* levels_out_dev,
+                      int64_t* shape_out_dev, int32_t* info_out_dev, void* stream);
+int cda_depth_imbalance(cda_env* env, int32_t first_market, int32_t n_markets, int32_t which, const int32_t* lags_host, int32_t n_lags, int32_t k, int32_t half,
+                        int64_t* resp_out_dev, int64_t* base_out_dev, int32_t* info_out_dev, void* stream);
+int cda_depth_ofi(cda_env* env, int32_t first_market, int32_t n_markets, int32_t which, const int32_t* lags_host, int32_t n_lags, int32_t bar_steps,
+                  const int32_t* depths_host, int32_t n_depths, int64_t* lagged_out_dev, int64_t* base_out_dev, int32_t* info_out_dev, void* stream);
+int cda_depth_check_host(int32_t kind, int32_t levels, const int32_t* lags_host, int32_t n_lags, int32_t a, int32_t b, const int32_t* depths_host, int32_t n_depths);
+
 /* ---- the P&L report: every agent's mark-to-mid equity curve over one remembered episode, on the device -----------------------------------
  * What did each agent's P&L do over the episode: the trade tape joined to the quote tape on the bar points, one launch on `stream`, a wave per
  * market, no atomics on global memory; pnl.py states every word in numpy.  The conventions of the stylised-facts report hold: m2(s) = bid_price
