@@ -38,6 +38,8 @@ SYMBOLS = [
     "cda_tape_pnl", "cda_tape_pnl_check_host",
     "cda_depth_enable", "cda_depth_disable", "cda_depth_capacity", "cda_depth_levels", "cda_depth_meta", "cda_depth_series", "cda_depth_profile",
     "cda_depth_imbalance", "cda_depth_ofi", "cda_depth_check_host",
+    "cda_order_tape_enable", "cda_order_tape_disable", "cda_order_tape_capacity", "cda_order_tape_meta", "cda_order_tape_series", "cda_order_flow", "cda_order_fills",
+    "cda_order_tape_check_host",
 ]
 
 
@@ -273,6 +275,15 @@ def lib():
     L.cda_depth_imbalance.argtypes = [vp, i32, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp]
     L.cda_depth_ofi.argtypes = [vp, i32, i32, i32, vp, i32, i32, vp, i32, vp, vp, vp, vp]
     L.cda_depth_check_host.argtypes = [i32, i32, vp, i32, i32, i32, vp, i32]
+    L.cda_order_tape_enable.argtypes = [vp, i64]
+    L.cda_order_tape_disable.argtypes = [vp]
+    L.cda_order_tape_capacity.argtypes = [vp]
+    L.cda_order_tape_capacity.restype = i64
+    L.cda_order_tape_meta.argtypes = [vp, i32, i32, vp, vp]
+    L.cda_order_tape_series.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp]
+    L.cda_order_flow.argtypes = [vp, i32, i32, i32, vp, vp, vp]
+    L.cda_order_fills.argtypes = [vp, i32, i32, i32, vp, vp, vp]
+    L.cda_order_tape_check_host.argtypes = [i32, i32, i64, i32]
     L.cda_mlp_forward_backward.argtypes = [vp, vp, vp, vp, i64, i64, vp, vp, i64, i32, f32, f32, f32, C.POINTER(PpoExtra), vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp]
     L.cda_mlp_rollout_chain.argtypes = [vp, vp, vp, i32, i32, i32, u64, vp, C.POINTER(RolloutBufs), i32, vp]
     L.cda_mlp_selftest_mfma.argtypes = [i32, vp, vp, vp]

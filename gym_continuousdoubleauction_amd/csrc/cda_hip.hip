@@ -651,6 +651,7 @@ struct cda_env {
     int64_t sched_epoch;     // moved by every cda_schedule_attach / cda_schedule_detach
     QuoteArgs quotes;        // cda_quotes_enable: the quote tape's rings and meta rows (ring == NULL: off - no launch)
     DepthArgs depth;         // cda_depth_enable: the depth tape's rings and meta rows (ring == NULL: off - no launch)
+    DepthArgs otape;         // cda_order_tape_enable: the order tape's rings and meta rows, records of 1 + num_agents words (`levels` = num_agents; ring == NULL: off - no launch)
     int64_t one_launch_steps;   // cda_policy_step_launch_count: k_policy_step / k_net_step launches enqueued since cda_create (host side; a captured enqueue counts once)
 };
 // csrc/cda_quotes.inc (included at the end): the top of the book of [first, first + n), recorded on `stream` ahead of a step; a no-op while quotes are off
@@ -659,6 +660,10 @@ static void quotes_free(cda_env* e);
 // csrc/cda_depth.inc (included at the end): the ladder of [first, first + n), recorded on `stream` behind the quotes and ahead of a step; a no-op while depth is off
 static int depth_record(cda_env* e, int32_t first, int32_t n, hipStream_t stream);
 static void depth_free(cda_env* e);
+// csrc/cda_order_tape.inc (included at the end): the decoded orders and execution ranks of [first, first + n) for the step `S` is about to take, recorded on `stream`
+// behind the depth recorder and ahead of the step; a no-op while the order tape is off
+static int order_tape_record(cda_env* e, int32_t first, int32_t n, const StepArgs& S, hipStream_t stream);
+static void order_tape_free(cda_env* e);
 // csrc/cda_schedule.inc (included at the end): the attached order schedule's windows of [first, first + n), queued on `stream` ahead of a step; a no-op while none is attached
 static int schedule_play(cda_env* e, int32_t first, int32_t n, hipStream_t stream);
 static void schedule_free(cda_env* e);
@@ -841,6 +846,7 @@ static void env_free(cda_env* e) {
     schedule_free(e);
     quotes_free(e);
     depth_free(e);
+    order_tape_free(e);
     if (e->rows) (void)hipFree(e->rows);
     free(e->rows_host);
     free(e);
@@ -982,6 +988,7 @@ static int launch_step(cda_env* e, int32_t first, int32_t n, const StepArgs& S0,
     if (e->sched.sched_of) { const int rcs = schedule_play(e, first, n, stream); if (rcs) return rcs; }      // an attached order schedule: the markets' windows first
     if (e->quotes.ring) { const int rcq = quotes_record(e, first, n, stream); if (rcq) return rcq; }          // quotes on: the book as this step's orders meet it
     if (e->depth.ring) { const int rcd = depth_record(e, first, n, stream); if (rcd) return rcd; }            // depth on: the same book, its ladder
+    if (e->otape.ring) { const int rco = order_tape_record(e, first, n, S0, stream); if (rco) return rco; }  // order tape on: what this step's actions decode to, and their ranks
     StepArgs S = S0;
     S.first_market = first; S.end_market = first + n;
     // the instance by (trade tape on, info tensors, episode-metric tallies: their code is not even in the instances without)
@@ -1097,7 +1104,7 @@ static int grant_policy_step_lds(const cda_env* e) {
 int cda_policy_step_supported(const cda_env* e) {
     if (!e) return 0;
     const int lds = e->cap == 256 ? policy_step_of(e).lds : 0;
-    return lds > 0 && lds <= 160 * 1024 && e->P.cfg.num_agents <= 8 && !e->handback && !e->tape.ring && !e->script.slot && !e->label.slot && !e->sched.sched_of && !e->quotes.ring && !e->depth.ring;      // (no k_policy_step instance writes the trade tape, asks a scripted law, plays an order schedule or records quotes or depth)
+    return lds > 0 && lds <= 160 * 1024 && e->P.cfg.num_agents <= 8 && !e->handback && !e->tape.ring && !e->script.slot && !e->label.slot && !e->sched.sched_of && !e->quotes.ring && !e->depth.ring && !e->otape.ring;      // (no k_policy_step instance writes the trade tape, asks a scripted law, plays an order schedule or records quotes, depth or orders)
 }
 // ... and whether it pays: every workgroup of k_policy_step streams the whole network for its sixteen rows, so the one launch wins while all of the env's
 // workgroups are resident at once (N <= 16 x CUs: 4096 markets on an MI355X - policy in the loop 278 -> 301-308 M at 4096 x 4) and loses to the batched policy
@@ -1270,7 +1277,7 @@ int cda_run_random(cda_env* e, int32_t n_steps, uint64_t action_seed, uint64_t m
                    int32_t* steps_taken_out, void* stream) {
     if (!e || n_steps < 0) return CDA_ERR_INVALID;
     if (e->sched.sched_of) return CDA_ERR_UNSUPPORTED;               // (k_run_random steps inside one launch: it cannot play an order schedule between its steps)
-    if (e->quotes.ring || e->depth.ring) return CDA_ERR_UNSUPPORTED; // (... nor record the quotes or the depth between them)
+    if (e->quotes.ring || e->depth.ring || e->otape.ring) return CDA_ERR_UNSUPPORTED; // (... nor record the quotes, the depth or the orders between them)
     HIPCHK(hipSetDevice(e->device));
     RunArgs R;
     R.n_steps = n_steps; R.seed = action_seed; R.market_base = market_index_base;
@@ -1715,3 +1722,5 @@ int64_t cda_state_bytes_per_market(const cda_env* e) { return e ? (int64_t)e->P.
 #include "cda_scripted_label.inc"
 // the depth tape (cda_depth_*): the Level-2 ladder per step, recorded behind the quotes and ahead of every step, and the book-shape reductions over it
 #include "cda_depth.inc"
+// the order tape (cda_order_tape_*, cda_order_flow, cda_order_fills): every decoded order of a step and its execution rank, recorded ahead of every step
+#include "cda_order_tape.inc"

@@ -14,6 +14,7 @@ CLI: python -m gym_continuousdoubleauction_amd.evaluate --policy P [--opponent r
      (a scripted opponent: pass | maker | taker | imbalance | NAME:key=value,...)
      [--sample] --seed --out JSON [--tape FILE.npz [--exec-report K[,K...]] [--spread-report K[,K...]]] [--quotes FILE.npz]
      [--stylised-facts L[,L...] [--bar-steps K]] [--pnl-report [--bar-steps K]] [--depth FILE.npz --depth-levels L] [--book-shape-report [--bar-steps K]]
+     [--orders FILE.npz] [--order-flow-report]
 """
 import argparse
 import dataclasses
@@ -231,9 +232,38 @@ def _book_shape_report(env, bar_steps, keep):
     return block
 
 
+def _order_flow_report(env, module_of, names, with_fills, keep):
+    """evaluate(order_flow_report=True): the order-flow table (CDAVecEnv.order_flow) - and, with the trade tape, the fills-against-orders table
+    (CDAVecEnv.order_fills) - of every market's previous episode, folded per module through the slot map as tape.exec_by_module folds the execution report (every
+    word is additive: one index_add_) and read through order_tape.summary, the integer rows beside the ratios.  A market counts when its ring holds something of a
+    finished episode; the others' slots are mapped to no module."""
+    from . import order_tape as OT
+    flow, info = env.order_flow(episode="previous")
+    fills = env.order_fills(episode="previous")[0] if with_fills else None
+    counted = info[:, 0] > 0
+    n_mod = len(names)
+    slot_module = torch.where(counted[:, None], module_of.to(torch.int64), torch.full_like(module_of, n_mod, dtype=torch.int64)).reshape(-1)      # row n_mod: not counted
+
+    def fold(t):
+        return torch.zeros((n_mod + 1, t.shape[2]), dtype=torch.int64, device=t.device).index_add_(0, slot_module, t.reshape(-1, t.shape[2])).cpu().numpy()
+    fl_h, fi_h, info_h, sel = fold(flow), fold(fills) if with_fills else None, info.cpu().numpy(), counted.cpu().numpy()
+    out = {"about": {"episode": "previous", "markets": int(sel.sum()), "records": int(info_h[sel, 0].sum()), "records_lost": int(info_h[sel, 1].sum()),
+                     "partial_markets": int((info_h[sel, 3] != 0).sum()), "flow_words": list(OT.FLOW_FIELDS), "fill_words": list(OT.FILL_FIELDS) if with_fills else None},
+           "modules": {}}
+    for i, name in enumerate(names):
+        block = OT.summary(fl_h[i], fi_h[i] if with_fills else None)
+        block["flow"] = [int(x) for x in fl_h[i]]
+        if with_fills:
+            block["fills"] = [int(x) for x in fi_h[i]]
+        out["modules"][name] = block
+    if keep is not None:
+        keep["order_tables"] = {"flow": flow.cpu().numpy(), "fills": fills.cpu().numpy() if with_fills else None, "info": info_h, "counted": sel}
+    return out
+
+
 def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="greedy", seed=0, groups=None, keep=None, tape=None, tape_capacity=4096,
              exec_horizons=None, quotes=None, spread_horizons=None, stylised_facts=None, bar_steps=1, pnl_report=False, depth=None, depth_levels=10,
-             book_shape_report=False):
+             book_shape_report=False, orders=None, order_flow_report=False):
     """Play `policy` (a FusedPolicy or a policy file) on `env` (a CDAVecEnv with auto_reset) for episodes * max_step steps; return per-module results.
     opponents: None = self-play; else a list of "random", FusedPolicy objects, policy files or scripted opponents - "pass", "maker", "taker", "imbalance",
     "NAME:key=value,..." or a scripted.Profile (rule-based agents on the device: their slots carry LEAGUE_RANDOM in slot_net and their profile in the env's slot_script,
@@ -274,7 +304,13 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
     book_shape_report (the ladders are recorded whether or not `depth` names a file; bar_steps: the OFI's bar size): add result["depth"] - the average shape of the
     book, the future mid move given the depth imbalance and the multi-level order-flow-imbalance regression of every market's last finished episode
     (CDAVecEnv.depth_profile, depth_imbalance, depth_ofi on the device), pooled over the markets (a book belongs to no module) and read through depth.summary,
-    with the pooled integer rows and what they cover ("about")."""
+    with the pooled integer rows and what they cover ("about").
+    orders (a path, optional): record every decoded order and its execution rank ahead of every step of the evaluated episodes on the device
+    (CDAVecEnv.enable_order_tape, two episodes of capacity) and save every market's last finished episode as an .npz (order_tape.save): records i32 [N, max_step,
+    (1 + A) * 4] with `counts`, `info`, `modules` and `module_names`.  The env's order tape must be OFF; it is off again afterwards.
+    order_flow_report (the orders are recorded whether or not `orders` names a file): add result["orders"] and one "orders" block per module - what the module's slots
+    sent, how they priced it against the touch and, with tape=..., how much of it found liquidity at once (CDAVecEnv.order_flow / order_fills on the device, folded
+    through the slot map, read through order_tape.summary)."""
     from .mlp import LEAGUE_RANDOM, FusedPolicy, PolicyBank, RolloutChains, read_policy
     if mode not in ("greedy", "sample"):
         raise ValueError(f"mode must be 'greedy' or 'sample' (got {mode!r})")
@@ -315,6 +351,10 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
         if env.depth_enabled:
             raise ValueError("evaluate(depth=... / book_shape_report=True) needs an env whose depth tape is off: it enables one of its own for the evaluated episodes "
                              "(disable_depth() first)")
+    with_orders = orders is not None or bool(order_flow_report)
+    if with_orders and env.order_tape_enabled:
+        raise ValueError("evaluate(orders=... / order_flow_report=True) needs an env whose order tape is off: it enables one of its own for the evaluated episodes "
+                         "(disable_order_tape() first)")
     with_tape = tape is not None or stylised_facts is not None
     with_quotes = quotes is not None or spread_horizons is not None or stylised_facts is not None or bool(pnl_report)
     if with_quotes and env.quotes_enabled:
@@ -362,6 +402,8 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
         env.enable_quotes(min(1 << 20, 2 * max(1, int(env.max_step))))  # (likewise: the recorder's launch; the finished episode and the running one both fit)
     if with_depth:
         env.enable_depth(min(1 << 20, 2 * max(1, int(env.max_step))), depth_levels)      # (likewise)
+    if with_orders:
+        env.enable_order_tape(min(1 << 20, 1 << (2 * max(1, int(env.max_step)) - 1).bit_length()))      # (likewise; a power of two that holds two episodes)
     tape_parts, tape_dropped = [], np.zeros(N, np.int64)
     try:
         if opp is None:
@@ -431,6 +473,13 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
         depth_rep = None
         if book_shape_report:
             depth_rep = _book_shape_report(env, bar_steps, keep)
+        order_rep = None
+        if order_flow_report:
+            order_rep = _order_flow_report(env, module_of, names, tape is not None, keep)
+        if orders is not None:
+            from .order_tape import save as save_orders
+            rec, cnt, oinfo = env.order_tape_series(int(env.max_step), episode="previous")
+            save_orders(orders, rec, counts=cnt, info=oinfo, modules=modules.astype(np.int32), module_names=np.array(names))
         if depth is not None:
             from .depth import save as save_depth
             rec, cnt, dinfo = env.depth_series(int(env.max_step), episode="previous")
@@ -454,6 +503,8 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
             env.disable_quotes()
         if with_depth and env.depth_enabled:
             env.disable_depth()
+        if with_orders and env.order_tape_enabled:
+            env.disable_order_tape()
         if scripts and env.scripted:
             env.clear_scripted()
     table_h, env_h = table.cpu().numpy(), env_row.cpu().numpy()
@@ -490,6 +541,10 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
             mods[name]["pnl"] = pnl_rep["modules"][name]
     if depth_rep is not None:
         result["depth"] = depth_rep
+    if order_rep is not None:
+        result["orders"] = order_rep["about"]
+        for name in names:
+            mods[name]["orders"] = order_rep["modules"][name]
     if keep is not None:
         keep["chains"], keep["modules"], keep["tables"] = chains, modules, (table_h, env_h)
         keep["actions"] = {key: torch.cat([a[key] for a in acts]) for key in acts[0]}
@@ -525,6 +580,10 @@ def main(argv=None):
     p.add_argument("--book-shape-report", action="store_true", help="add the pooled depth block - the average shape of the book, the mid's response to depth imbalance and "
                    "the multi-level order-flow-imbalance regression (bars of --bar-steps), reduced on the device from every market's last finished episode (switches the "
                    "depth tape on)")
+    p.add_argument("--orders", default=None, metavar="FILE.npz", help="record every decoded order and its execution rank ahead of every step (the order tape) and save every "
+                   "market's last finished episode")
+    p.add_argument("--order-flow-report", action="store_true", help="add one orders block per module - what it sent, how it priced it against the touch and, with --tape, how "
+                   "much of it filled at once - reduced on the device from every market's last finished episode (switches the order tape on)")
     p.add_argument("--order-schedule", default=None, metavar="FILE.npz", help="attach this order schedule (orders.save_schedule) to the env: per-step order flow played ahead "
                    "of every step of the evaluated episodes")
     args = p.parse_args(argv)
@@ -563,7 +622,8 @@ def main(argv=None):
         res = evaluate(env, args.policy, opponents=args.opponent, trained_slots=args.trained_slots, episodes=args.episodes,
                        mode="sample" if args.sample else "greedy", seed=args.seed, tape=args.tape, exec_horizons=exec_horizons,
                        quotes=args.quotes, spread_horizons=spread_horizons, stylised_facts=stylised_facts, bar_steps=args.bar_steps, pnl_report=args.pnl_report,
-                       depth=args.depth, depth_levels=args.depth_levels, book_shape_report=args.book_shape_report)
+                       depth=args.depth, depth_levels=args.depth_levels, book_shape_report=args.book_shape_report,
+                       orders=args.orders, order_flow_report=args.order_flow_report)
     finally:
         env.close()
     res.pop("summary")

@@ -731,6 +731,8 @@ class RolloutChains:
         self._graph_quote_epoch = getattr(self.env, "quote_epoch", 0)
         # ... and the depth recorder's launch and ring (or none) as enabled now (CDAVecEnv.enable_depth / disable_depth)
         self._graph_depth_epoch = getattr(self.env, "depth_epoch", 0)
+        # ... and the order recorder's launch and ring (or none) as enabled now (CDAVecEnv.enable_order_tape / disable_order_tape)
+        self._graph_order_tape_epoch = getattr(self.env, "order_tape_epoch", 0)
         # ... and the label tap's launch and buffers (or none) as attached now (CDAVecEnv.set_label_tap / clear_label_tap; set_label_mix moves nothing)
         self._graph_label_epoch = getattr(self.env, "label_epoch", 0)
         # ... and the step instances (tallying or not) and the NAV tolerance of the env's episode-metrics setting as it is now (CDAVecEnv.enable_episode_metrics). The
@@ -759,6 +761,9 @@ class RolloutChains:
                                "and ring of the earlier setting - build a new RolloutChains")
         if self.graphs is not None and self._graph_depth_epoch != getattr(self.env, "depth_epoch", 0):
             raise RuntimeError("the env's depth tape was enabled or disabled after this RolloutChains captured its graphs: they would replay the recorder's launch "
+                               "and ring of the earlier setting - build a new RolloutChains")
+        if self.graphs is not None and self._graph_order_tape_epoch != getattr(self.env, "order_tape_epoch", 0):
+            raise RuntimeError("the env's order tape was enabled or disabled after this RolloutChains captured its graphs: they would replay the recorder's launch "
                                "and ring of the earlier setting - build a new RolloutChains")
         if self.graphs is not None and self._graph_label_epoch != getattr(self.env, "label_epoch", 0):
             raise RuntimeError("the env's label tap was attached or detached after this RolloutChains captured its graphs: they would replay the launches and "

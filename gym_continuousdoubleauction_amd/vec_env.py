@@ -48,6 +48,7 @@ class CDAVecEnv:
         self._tape_cursor = None            # drain_tape's default cursor (i64 [N], device) while the tape is on
         self.quote_epoch = 0                # bumped by enable_quotes / disable_quotes: captured graphs hold the recorder's launch (or none) of their capture
         self.depth_epoch = 0                # bumped by enable_depth / disable_depth: likewise for the depth recorder's launch
+        self.order_tape_epoch = 0           # bumped by enable_order_tape / disable_order_tape: likewise for the order recorder's launch
         self.script_epoch = 0               # bumped by set_scripted / clear_scripted: graphs captured on this env's rollout chains hold the scripted launches (or none) of then
         self._script = None                 # set_scripted: an AttachedScripts (None while nothing is attached)
         self._schedule = None               # set_order_schedule: an AttachedSchedule (None while nothing is attached)
@@ -1002,6 +1003,92 @@ class CDAVecEnv:
         return self._reader_call(lib().cda_depth_ofi, "cda_depth_ofi", first, n, (which, (C.c_int32 * len(lg))(*lg), len(lg), bar, (C.c_int32 * len(dp))(*dp), len(dp)),
                                  (torch.empty((n, len(dp), len(lg), 6), dtype=torch.int64, device=self.device),
                                   torch.empty((n, 4), dtype=torch.int64, device=self.device)))
+
+    # ------------------------------------------------------------------ the order tape: every decoded order of a step and its execution rank (order_tape.py)
+    @property
+    def order_tape_enabled(self):
+        return int(lib().cda_order_tape_capacity(self._h)) > 0
+
+    @property
+    def order_tape_capacity(self):
+        return int(lib().cda_order_tape_capacity(self._h))
+
+    def enable_order_tape(self, capacity=1024):
+        """From now on every step entry point first records, per market whose episode is not over, what the step's actions decode to - per agent type, side, size
+        and price as the step's own `lob_actions` info words, and the rank the step's shuffle gives the order in the execution order (order_tape.record_dtype(A)) -
+        into the market's ring of `capacity` records on the device (include/cda.h cda_order_tape_enable; a power of two), behind an attached order schedule's window
+        and the quote and depth recorders and ahead of the step.  The recorder works on a copy of the market's generator: the step that follows is bit for bit the
+        step an env without the tape takes.  Off by default; rings start empty; it needs no other tape (order_fills needs the trade tape too).  While it is on the
+        one-launch policy step is off (rollout chains take their two-launch path) and run_random is refused.  Do not toggle it between the capture and the replay
+        of a graph that holds this env's step launches (mlp.RolloutChains checks)."""
+        capacity = int(capacity)
+        if not 1 <= capacity <= (1 << 20) or capacity & (capacity - 1):
+            raise ValueError(f"order tape capacity must be a power of two in 1 .. {1 << 20} steps, got {capacity}")
+        self.sync()
+        check(lib().cda_order_tape_enable(self._h, capacity), "cda_order_tape_enable")
+        self.order_tape_epoch += 1                                # (captured graphs of this env's step launches are stale from here on)
+
+    def disable_order_tape(self):
+        self.sync()
+        check(lib().cda_order_tape_disable(self._h), "cda_order_tape_disable")
+        self.order_tape_epoch += 1
+
+    def _need_order_tape(self, what):
+        if not self.order_tape_enabled:
+            raise RuntimeError(f"{what} needs the order tape: call enable_order_tape() first (it is off by default)")
+
+    def order_tape_meta(self, first_market=0, n_markets=None):
+        """Every market's meta row of the order tape as the readers see it - rolled to the market's clock by the episode rule (quotes.roll) - i32 [n, 8], a device
+        tensor; quotes.meta_from_words names the words, quotes.span says what the ring holds of either episode."""
+        self._need_order_tape("order_tape_meta()")
+        first, n = self._market_range("order_tape_meta", first_market, n_markets)
+        return self._reader_call(lib().cda_order_tape_meta, "cda_order_tape_meta", first, n, (), (torch.empty((n, 8), dtype=torch.int32, device=self.device),), info=False)[0]
+
+    def order_tape_series(self, k=None, episode="current", first_market=0, n_markets=None):
+        """The held order records of one remembered episode, oldest first (include/cda.h cda_order_tape_series): (records i32 [n, k, (1 + A) * 4] -
+        order_tape.as_orders names the words; rows beyond the count are zero -, counts i32 [n], info i32 [n, 4] = records returned, records of the episode's head
+        the ring had overwritten, step of the first returned record, partial flag), device tensors.  An episode longer than k returns its LAST k records.  k
+        defaults to the smaller of the ring's capacity and the largest max_step."""
+        self._need_order_tape("order_tape_series()")
+        first, n = self._market_range("order_tape_series", first_market, n_markets)
+        which = self._tape_which(episode)
+        if k is None:
+            k = max(1, min(self.order_tape_capacity, self._top_max_step()))
+        if int(k) < 1:
+            raise ValueError(f"order_tape_series: k must be >= 1, got {k}")
+        return self._reader_call(lib().cda_order_tape_series, "cda_order_tape_series", first, n, (which, int(k)),
+                                 (torch.empty((n, int(k), 4 * (1 + self.num_agents)), dtype=torch.int32, device=self.device),
+                                  torch.empty(n, dtype=torch.int32, device=self.device)))
+
+    def order_tape_episode(self, market=0, episode="current"):
+        """One market's held order records of an episode, oldest first, as a structured host array (order_tape.record_dtype(A))."""
+        from .order_tape import as_orders
+        rec, cnt, _ = self.order_tape_series(None, episode, int(market), 1)
+        return as_orders(rec[0, :int(cnt[0].item())].cpu().numpy(), self.num_agents).copy()
+
+    def order_flow(self, episode="current", first_market=0, n_markets=None):
+        """What every agent sent over one remembered episode's held order records, reduced on the device in one launch (include/cda.h cda_order_flow;
+        order_tape.flow_from_records is its specification, word for word).  -> (flow i64 [n, A, 32] - order_tape.FLOW_FIELDS: steps present, passes, steps absent,
+        per type x side orders and quantity, the placement classes of the limit orders against the touch -, info i32 [n, 4] as quote_stats), device tensors.
+        Every word is additive: order_tape.pool sums over markets, order_tape.summary reads the ratios."""
+        self._need_order_tape("order_flow()")
+        first, n = self._market_range("order_flow", first_market, n_markets)
+        which = self._tape_which(episode)
+        return self._reader_call(lib().cda_order_flow, "cda_order_flow", first, n, (which,),
+                                 (torch.empty((n, self.num_agents, 32), dtype=torch.int64, device=self.device),))
+
+    def order_fills(self, episode="current", first_market=0, n_markets=None):
+        """The trade tape of one remembered episode joined to its order records on the fill's step, reduced on the device in one launch (include/cda.h
+        cda_order_fills; order_tape.fills_from_records is its specification, word for word).  Needs the trade tape as well.  -> (fills i64 [n, A, 24] -
+        order_tape.FILL_FIELDS: per order type orders, submitted quantity, orders filled at once, quantity so filled; maker, self and unmatched fills -, info i32
+        [n, 8] = order records held, lost, step of the first, partial, then fills held, lost, step of the first held fill (-1: none), partial), device tensors."""
+        self._need_order_tape("order_fills()")
+        self._need_tape("order_fills()")
+        first, n = self._market_range("order_fills", first_market, n_markets)
+        which = self._tape_which(episode)
+        return self._reader_call(lib().cda_order_fills, "cda_order_fills", first, n, (which,),
+                                 (torch.empty((n, self.num_agents, 24), dtype=torch.int64, device=self.device),
+                                  torch.empty((n, 8), dtype=torch.int32, device=self.device)), info=False)
 
     # ------------------------------------------------------------------ the book report: reductions over the standing book, on the device
     def _book_call(self, name, first_market, n_markets, shape, dtype, *mid):

@@ -870,6 +870,73 @@ int cda_depth_ofi(cda_env* env, int32_t first_market, int32_t n_markets, int32_t
                   const int32_t* depths_host, int32_t n_depths, int64_t* lagged_out_dev, int64_t* base_out_dev, int32_t* info_out_dev, void* stream);
 int cda_depth_check_host(int32_t kind, int32_t levels, const int32_t* lags_host, int32_t n_lags, int32_t a, int32_t b, const int32_t* depths_host, int32_t n_depths);
 
+/* ---- order tape: every decoded order of a step and its execution rank, recorded on the device, and two order-flow reports -----------------
+ * The trade tape holds what a step's orders did, the quote and depth tapes the book they met; this holds the orders themselves: what every agent
+ * sent - type, side, size, price as the step decodes them (the `lob_actions` info words) - and where the step's shuffle put it in the execution
+ * order.  cda_order_tape_enable(env, capacity_steps): from now on every step launch of this env first records, for every market of its range
+ * whose episode is not over, one record of 1 + num_agents 16-byte words into the market's ring of `capacity_steps` records (a power of two in
+ * 1 .. CDA_QUOTE_CAP_MAX; n_markets x capacity x (1 + num_agents) x 16 bytes of its own beside the arena; CDA_ERR_NOMEM leaves the env as it was).
+ * The recorder's launch runs behind the order schedule's, the quote recorder's and the depth recorder's and ahead of the step kernel; it decodes
+ * the step's actions and shuffles them on a COPY of the market's generator state: it consumes no draw and writes nothing into the market record.
+ * OFF by default; enable / disable are synchronous, as cda_quotes_enable is, and everything said there of graphs, cda_policy_step_supported and
+ * cda_net_step_supported (0 while on), cda_run_random (CDA_ERR_UNSUPPORTED while on), snapshots and state dumps (unchanged) holds.
+ * Word 0 = cda_order_head.  Word 1 + a = cda_order_slot of agent a:
+ *   code    -1: the agent was not present in this step (size, price = -1, action = 0).  Otherwise bits 0-1 = type (0 market, 1 limit, 2 modify,
+ *           3 cancel), bits 2-3 = side (0 bid, 1 ask, 2 passed), bits 4-7 = execution rank (0 = executed first; 0 for a pass), bit 8
+ *           (CDA_ORDER_CLAMPED) = the decode clamped size or price (the step flags CDA_FLAG_INT_OVERFLOW).
+ *   size, price   the `lob_actions` words: price in ticks, -1 for a market order; both -1 for a pass.
+ *   action  the clamped raw action: category | level << 4 | offset << 8 (category 0 .. 8, level 0 .. 9, offset 0 .. 2).
+ * Episodes: the quote tape's meta row and its ONE rule (above), over rows and rings of this service's own; a record is indexed by its step.
+ *   cda_order_tape_meta    the rolled meta rows -> meta_out_dev i32 [n][8].
+ *   cda_order_tape_series  the last k held records of the episode `which`, oldest first -> records_out_dev i32 [n][k][(1 + num_agents) x 4] (16-B
+ *                          aligned; rows beyond the count are zero), counts_out_dev i32 [n] and info_out_dev i32 [n][4] (either may be NULL) as
+ *                          cda_quote_series.
+ * Two reductions, one launch each, a wave per market, exact int64, every output word additive; order_tape.py states every word in numpy.
+ *   cda_order_flow   flow_out_dev i64 [n][num_agents][CDA_ORDER_FLOW_WORDS] over the held records of the episode: steps present, passes, steps
+ *                    absent; per type x side (index type x 2 + side) orders and submitted quantity; for LIMIT orders against the record's own touch:
+ *                    crossing (bid price >= best_ask with the ask side non-empty, ask price <= best_bid with the bid side non-empty), else with
+ *                    the own side empty no_reference, else inside (improves the own best), at_touch, behind and behind_ticks (the summed distance
+ *                    to the own best / the market's tick_size); zeros up to 32 words.  info_out_dev i32 [n][4] as cda_quote_stats.
+ *   cda_order_fills  fills_out_dev i64 [n][num_agents][CDA_ORDER_FILL_WORDS]: the trade tape of the episode joined to the order records on the
+ *                    fill's step.  Per order type (4): orders, submitted quantity (over the held order records), orders with at least one fill as
+ *                    initiator in their own step, quantity so filled - a held fill with init_id == a at step s belongs to agent a's order of step
+ *                    s.  Then maker_fills, maker_qty (counter_id == a), self_fills, self_qty (both ids == a), unmatched_fills, unmatched_qty
+ *                    (init_id == a and no order record of the step is held, or a sent no order in it: hook, stream or scheduled flow), zeros up to
+ *                    24 words.  A fill with an id outside the env's agents is skipped.  Needs both tapes: CDA_ERR_UNSUPPORTED while either is
+ *                    off.  info_out_dev i32 [n][8] (may be NULL): {order records held, lost, step of the first, partial, fills held, lost, step of
+ *                    the first held fill (-1: none), partial}.
+ *   cda_order_tape_check_host  the argument check of the entry points, on the host alone: kind = CDA_ORDER_CHECK_ENABLE (a = capacity_steps) /
+ *                    _SERIES (a = which, b = k) / _REPORT (a = which); num_agents = the env's; CDA_OK or CDA_ERR_INVALID.
+ * A NULL pointer, a misaligned output (records 16 B, int64 8 B, int32 4 B), a range outside the env, another `which`: CDA_ERR_INVALID; the tape
+ * off: CDA_ERR_UNSUPPORTED from the readers.  Nothing is launched behind a refusal. */
+#define CDA_ORDER_FLOW_WORDS   32
+#define CDA_ORDER_FILL_WORDS   24
+#define CDA_ORDER_CLAMPED      256
+#define CDA_ORDER_CHECK_ENABLE 0
+#define CDA_ORDER_CHECK_SERIES 1
+#define CDA_ORDER_CHECK_REPORT 2
+typedef struct cda_order_head {        /* word 0 of a record */
+    int32_t step;                      /* the env step index t of the episode */
+    int32_t flags;                     /* bits 0 / 1 = CDA_QUOTE_BID / CDA_QUOTE_ASK: the side is non-empty ahead of the step; bits 8..15: orders; bits 16..23: passes */
+    int32_t best_bid;                  /* ahead of the step, in ticks; 0 where the side is empty */
+    int32_t best_ask;
+} cda_order_head;
+typedef struct cda_order_slot {        /* word 1 + a of a record */
+    int32_t code;
+    int32_t size;
+    int32_t price;
+    int32_t action;
+} cda_order_slot;
+int cda_order_tape_enable(cda_env* env, int64_t capacity_steps);
+int cda_order_tape_disable(cda_env* env);
+int64_t cda_order_tape_capacity(const cda_env* env);
+int cda_order_tape_meta(cda_env* env, int32_t first_market, int32_t n_markets, int32_t* meta_out_dev, void* stream);
+int cda_order_tape_series(cda_env* env, int32_t first_market, int32_t n_markets, int32_t which, int32_t k, void* records_out_dev, int32_t* counts_out_dev,
+                          int32_t* info_out_dev, void* stream);
+int cda_order_flow(cda_env* env, int32_t first_market, int32_t n_markets, int32_t which, int64_t* flow_out_dev, int32_t* info_out_dev, void* stream);
+int cda_order_fills(cda_env* env, int32_t first_market, int32_t n_markets, int32_t which, int64_t* fills_out_dev, int32_t* info_out_dev, void* stream);
+int cda_order_tape_check_host(int32_t kind, int32_t num_agents, int64_t a, int32_t b);
+
 /* ---- the P&L report: every agent's mark-to-mid equity curve over one remembered episode, on the device -----------------------------------
  * What did each agent's P&L do over the episode: the trade tape joined to the quote tape on the bar points, one launch on `stream`, a wave per
  * market, no atomics on global memory; pnl.py states every word in numpy.  The conventions of the stylised-facts report hold: m2(s) = bid_price
