@@ -31,6 +31,8 @@ SYMBOLS = [
     "cda_scripted_attach", "cda_scripted_detach", "cda_scripted_epoch", "cda_scripted_attached", "cda_scripted_actions", "cda_scripted_decide_host",
     "cda_scripted_profile_check_host",
     "cda_label_tap_attach", "cda_label_tap_detach", "cda_label_tap_attached", "cda_label_tap_epoch", "cda_scripted_step_actions", "cda_label_actions", "cda_label_mix_host",
+    "cda_stateful_attach", "cda_stateful_detach", "cda_stateful_epoch", "cda_stateful_attached", "cda_stateful_actions", "cda_stateful_advance_host",
+    "cda_stateful_profile_check_host",
     "cda_submit_orders", "cda_submit_orders_window", "cda_order_msgs_check_host", "cda_order_msgs_check_agents_host",
     "cda_schedule_attach", "cda_schedule_detach", "cda_schedule_attached", "cda_schedule_epoch", "cda_schedule_counts", "cda_schedule_play", "cda_schedule_check_host",
     "cda_quotes_enable", "cda_quotes_disable", "cda_quotes_capacity", "cda_quote_meta", "cda_quote_series", "cda_quote_stats", "cda_tape_spreads",
@@ -237,6 +239,14 @@ def lib():
     L.cda_scripted_step_actions.argtypes = [vp, i32, i32, vp, i32] + [vp] * 5 + [vp] * 3 + [vp]
     L.cda_label_actions.argtypes = [vp, i32, i32, vp, vp, i32, u64, u64, vp, i64] + [vp] * 5 + [vp]
     L.cda_label_mix_host.argtypes = [u64, u64, vp, vp, vp, i64, u64, vp]
+    L.cda_stateful_attach.argtypes = [vp, vp, vp, i32, vp, u64, u64]
+    L.cda_stateful_detach.argtypes = [vp]
+    L.cda_stateful_epoch.argtypes = [vp]
+    L.cda_stateful_epoch.restype = i64
+    L.cda_stateful_attached.argtypes = [vp]
+    L.cda_stateful_actions.argtypes = [vp, i32, i32, vp, i64] + [vp] * 5 + [vp] * 3 + [vp]
+    L.cda_stateful_advance_host.argtypes = [vp, i32, vp, vp, i64, u64, u64, vp, vp, vp, vp] + [vp] * 5
+    L.cda_stateful_profile_check_host.argtypes = [vp, i32]
     L.cda_submit_orders.argtypes = [vp, i32, i32, vp, vp, vp, vp, C.c_uint32, vp]
     L.cda_submit_orders_window.argtypes = [vp, i32, i32, vp, vp, i64, i64, i64, vp, vp, C.c_uint32, vp]
     L.cda_order_msgs_check_host.argtypes = [vp, vp, i64, C.POINTER(i64)]

@@ -36,6 +36,7 @@
 #include "../../include/cda.h"
 #include "../../include/cda_random_agents.h"
 #include "../../include/cda_scripted_agents.h"
+#include "../../include/cda_stateful_agents.h"
 #include "cda_dec.hpp"
 #include "cda_market.hpp"
 #include <type_traits>
@@ -615,6 +616,9 @@ struct LabelArgs {
     const uint64_t* mix_q32;                                         // read by the kernel at every launch (NULL: never mixed)
     int32_t* cat; float* mean; float* sigma; int32_t* price; int32_t* off; int32_t* played;      // played == NULL: not written
 };
+// scripted opponents with memory (include/cda_stateful_agents.h, csrc/cda_stateful.inc): what cda_stateful_attach keeps - caller-owned device memory, as ScriptArgs' is,
+// the state tensor i64 [N][A][CDA_STATEFUL_WORDS] the kernel reads and writes among it
+struct StatefulArgs { const int32_t* slot; const cda_stateful_profile* profiles; int64_t* state; int32_t n_profiles; int32_t pad; uint64_t seed, market_base; };
 // the quote tape (include/cda.h cda_quotes_*, csrc/cda_quotes.inc): a market's meta row - eight int32 words - and what cda_quotes_enable keeps
 struct QuoteMeta {               // 32 B per market
     int64_t n_total;             // records since the quotes were enabled (the ring slot of record j is j % capacity)
@@ -653,6 +657,8 @@ struct cda_env {
     DepthArgs depth;         // cda_depth_enable: the depth tape's rings and meta rows (ring == NULL: off - no launch)
     DepthArgs otape;         // cda_order_tape_enable: the order tape's rings and meta rows, records of 1 + num_agents words (`levels` = num_agents; ring == NULL: off - no launch)
     int64_t one_launch_steps;   // cda_policy_step_launch_count: k_policy_step / k_net_step launches enqueued since cda_create (host side; a captured enqueue counts once)
+    StatefulArgs stateful;   // cda_stateful_attach: the caller's resident slot table, profiles and state tensor (slot == NULL: nothing attached - cda_stateful_actions launches nothing)
+    int64_t stateful_epoch;  // moved by every cda_stateful_attach / cda_stateful_detach
 };
 // csrc/cda_quotes.inc (included at the end): the top of the book of [first, first + n), recorded on `stream` ahead of a step; a no-op while quotes are off
 static int quotes_record(cda_env* e, int32_t first, int32_t n, hipStream_t stream);
@@ -1104,7 +1110,7 @@ static int grant_policy_step_lds(const cda_env* e) {
 int cda_policy_step_supported(const cda_env* e) {
     if (!e) return 0;
     const int lds = e->cap == 256 ? policy_step_of(e).lds : 0;
-    return lds > 0 && lds <= 160 * 1024 && e->P.cfg.num_agents <= 8 && !e->handback && !e->tape.ring && !e->script.slot && !e->label.slot && !e->sched.sched_of && !e->quotes.ring && !e->depth.ring && !e->otape.ring;      // (no k_policy_step instance writes the trade tape, asks a scripted law, plays an order schedule or records quotes, depth or orders)
+    return lds > 0 && lds <= 160 * 1024 && e->P.cfg.num_agents <= 8 && !e->handback && !e->tape.ring && !e->script.slot && !e->stateful.slot && !e->label.slot && !e->sched.sched_of && !e->quotes.ring && !e->depth.ring && !e->otape.ring;      // (no k_policy_step instance writes the trade tape, asks a scripted or stateful law, plays an order schedule or records quotes, depth or orders)
 }
 // ... and whether it pays: every workgroup of k_policy_step streams the whole network for its sixteen rows, so the one launch wins while all of the env's
 // workgroups are resident at once (N <= 16 x CUs: 4096 markets on an MI355X - policy in the loop 278 -> 301-308 M at 4096 x 4) and loses to the batched policy
@@ -1724,3 +1730,5 @@ int64_t cda_state_bytes_per_market(const cda_env* e) { return e ? (int64_t)e->P.
 #include "cda_depth.inc"
 // the order tape (cda_order_tape_*, cda_order_flow, cda_order_fills): every decoded order of a step and its execution rank, recorded ahead of every step
 #include "cda_order_tape.inc"
+// scripted opponents with memory (cda_stateful_*): a trend follower, a value trader and a parent order worked over time, on per-slot state resident on the device
+#include "cda_stateful.inc"

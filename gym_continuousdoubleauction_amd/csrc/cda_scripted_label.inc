@@ -175,9 +175,10 @@ int cda_label_tap_detach(cda_env* e) {
 int64_t cda_label_tap_epoch(const cda_env* e) { return e ? e->label_epoch : 0; }
 int cda_label_tap_attached(const cda_env* e) { return e && e->label.slot ? 1 : 0; }
 
-int cda_scripted_step_actions(cda_env* e, int32_t first_market, int32_t n_markets, const int64_t* counter_dev, int32_t t,
-                              int32_t* category, float* size_mean, float* size_sigma, int32_t* price, int32_t* price_offset,
-                              float* a_cont, float* logp, float* record, void* stream) {
+// what cda_scripted_step_actions issues for the stateless family: the scripted launch, the label tap's, or none
+static int scripted_step_launch(cda_env* e, int32_t first_market, int32_t n_markets, const int64_t* counter_dev, int32_t t,
+                                int32_t* category, float* size_mean, float* size_sigma, int32_t* price, int32_t* price_offset,
+                                float* a_cont, float* logp, float* record, void* stream) {
     if (!e || t < 0) return CDA_ERR_INVALID;
     if (!e->label.slot)                                              // no tap: this IS cda_scripted_actions - the same kernel and launch, or none
         return cda_scripted_actions(e, first_market, n_markets, counter_dev, t, category, size_mean, size_sigma, price, price_offset, a_cont, logp, record, stream);
@@ -191,6 +192,14 @@ int cda_scripted_step_actions(cda_env* e, int32_t first_market, int32_t n_market
     hipLaunchKernelGGL(k_script_label, grid_for(n_markets), dim3(64 * CDA_WPB), 0, (hipStream_t)stream, (const uint8_t*)e->arena, e->P, (int)e->cap, (int)first_market,
                        (int)n_markets, e->script, Lb, (const long long*)counter_dev, (long long)t, category, size_mean, size_sigma, price, price_offset, a_cont, logp, record);
     return launch_status();
+}
+int cda_scripted_step_actions(cda_env* e, int32_t first_market, int32_t n_markets, const int64_t* counter_dev, int32_t t,
+                              int32_t* category, float* size_mean, float* size_sigma, int32_t* price, int32_t* price_offset,
+                              float* a_cont, float* logp, float* record, void* stream) {
+    const int rc = scripted_step_launch(e, first_market, n_markets, counter_dev, t, category, size_mean, size_sigma, price, price_offset, a_cont, logp, record, stream);
+    if (rc != CDA_OK || !e->stateful.slot) return rc;
+    // ... and behind it the stateful family's launch (csrc/cda_stateful.inc), with draw = t: a slot both tables name plays its stateful law
+    return cda_stateful_actions(e, first_market, n_markets, counter_dev, t, category, size_mean, size_sigma, price, price_offset, a_cont, logp, record, stream);
 }
 
 int cda_label_actions(cda_env* e, int32_t first_market, int32_t n_markets, const int32_t* slot_label_dev, const void* profiles_dev, int32_t n_profiles, uint64_t seed,

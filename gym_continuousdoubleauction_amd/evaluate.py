@@ -11,7 +11,7 @@ the captured kernels), runs episodes * max_step steps, and reads the episodes th
 the greedy chains); mode="sample" runs the same loop on the sampling kernels.
 
 CLI: python -m gym_continuousdoubleauction_amd.evaluate --policy P [--opponent random|FILE ...] --markets --agents --max-step --episodes --trained-slots
-     (a scripted opponent: pass | maker | taker | imbalance | NAME:key=value,...)
+     (a scripted opponent: pass | maker | taker | imbalance | NAME:key=value,...; one with memory: trend | value | execution | NAME:key=value,...)
      [--sample] --seed --out JSON [--tape FILE.npz [--exec-report K[,K...]] [--spread-report K[,K...]]] [--quotes FILE.npz]
      [--stylised-facts L[,L...] [--bar-steps K]] [--pnl-report [--bar-steps K]] [--depth FILE.npz --depth-levels L] [--book-shape-report [--bar-steps K]]
      [--orders FILE.npz] [--order-flow-report]
@@ -267,7 +267,9 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
     """Play `policy` (a FusedPolicy or a policy file) on `env` (a CDAVecEnv with auto_reset) for episodes * max_step steps; return per-module results.
     opponents: None = self-play; else a list of "random", FusedPolicy objects, policy files or scripted opponents - "pass", "maker", "taker", "imbalance",
     "NAME:key=value,..." or a scripted.Profile (rule-based agents on the device: their slots carry LEAGUE_RANDOM in slot_net and their profile in the env's slot_script,
-    attached for the evaluation and detached afterwards) -, placed by slot_modules.  trained_slots: the policy's slots per
+    attached for the evaluation and detached afterwards) - or stateful ones - "trend", "value", "execution", "NAME:key=value,..." or a stateful.Profile (opponents
+    with memory: attached likewise through set_stateful, on a zeroed state tensor; the result names them in "stateful_modules" and in their module's "module") -,
+    placed by slot_modules.  trained_slots: the policy's slots per
     market when there are opponents (default 1).  groups: rollout chains (default 4).  keep (a dict, optional): receives the RolloutChains object, the
     placement, the collected metric tables (agent table, env row) and host copies of every step's env actions (`actions`: category, size_mean, size_sigma,
     price, price_offset as [steps, N, A]) - what a replay needs.
@@ -370,8 +372,13 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
     scripts = {p: parse_profile(o) for p, o in enumerate(opp or []) if is_scripted_spec(o)}      # opponent index -> Profile (a bad 'NAME:key=value' raises here)
     if scripts and env.scripted:
         raise ValueError("evaluate() with scripted opponents needs an env without scripts attached: it attaches its own for the evaluated episodes (clear_scripted() first)")
+    from . import stateful as SF
+    statefuls = {p: SF.parse_profile(o) for p, o in enumerate(opp or []) if SF.is_stateful_spec(o)}      # opponent index -> stateful.Profile
+    if statefuls and env.stateful:
+        raise ValueError("evaluate() with stateful opponents needs an env without stateful opponents attached: it attaches its own for the evaluated episodes "
+                         "(clear_stateful() first)")
     for p, o in enumerate(opp or []):
-        if (isinstance(o, str) and o == RANDOM) or p in scripts:
+        if (isinstance(o, str) and o == RANDOM) or p in scripts or p in statefuls:
             continue
         act, vfs = (o.activation, o.vf_share_layers) if isinstance(o, FusedPolicy) else read_policy(o, with_activation=True, with_vf_share_layers=True)[1:]
         if act != pol.activation:
@@ -432,6 +439,12 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
                 for j, p in enumerate(order):
                     slot_script[modules == 1 + p] = 1 + j
                 env.set_scripted(slot_script, [scripts[p] for p in order], seed=seed)      # before the chains are captured
+            if statefuls:                                                # likewise the stateful modules': the random module in slot_net, their profile in the stateful table
+                order = sorted(statefuls)
+                slot_stateful = np.zeros((N, A), dtype=np.int32)
+                for j, p in enumerate(order):
+                    slot_stateful[modules == 1 + p] = 1 + j
+                env.set_stateful(slot_stateful, [statefuls[p] for p in order], seed=seed)   # (a zeroed state tensor: every slot starts fresh)
         seeds = (np.uint64(int(seed) & (2 ** 63 - 1)) * np.uint64(N) + np.arange(N, dtype=np.uint64))
         env.reset(seed=seeds)
         env.collect_episode_metrics(clear=True)                          # nothing that ended before the reset counts
@@ -507,6 +520,8 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
             env.disable_order_tape()
         if scripts and env.scripted:
             env.clear_scripted()
+        if statefuls and env.stateful:
+            env.clear_stateful()
     table_h, env_h = table.cpu().numpy(), env_row.cpu().numpy()
     summary = summarise(table_h, env_h, module_names=names)
     check_nav_conservation(0, summary, strict=True)
@@ -525,6 +540,10 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
                          "activation": pol.activation},
               "agent_steps_per_s": N * A * total / wall if wall > 0 else None,
               "summary": summary}
+    if statefuls:                                                        # the stateful modules by name: stateful_<index among them>_<law>
+        result["stateful_modules"] = {}
+        for j, p in enumerate(sorted(statefuls)):
+            mods[f"opponent_{p}"]["module"] = result["stateful_modules"][f"opponent_{p}"] = SF.module_id(j, statefuls[p])
     if execution is not None:
         result["execution"] = execution["about"]
         for name in names:
@@ -554,7 +573,7 @@ def evaluate(env, policy, opponents=None, trained_slots=None, episodes=1, mode="
 def main(argv=None):
     p = argparse.ArgumentParser(description="evaluate a saved policy (greedy by default) against opponents on the HIP env")
     p.add_argument("--policy", required=True, help="a policy file (ppo --save, league_train --save-dir)")
-    p.add_argument("--opponent", action="append", default=None, help="'random', a scripted opponent ('pass', 'maker', 'taker', 'imbalance', 'NAME:key=value,...') or a policy file; repeat for several (market m plays opponent m mod P); none = self-play")
+    p.add_argument("--opponent", action="append", default=None, help="'random', a scripted opponent ('pass', 'maker', 'taker', 'imbalance', 'NAME:key=value,...'), one with memory ('trend', 'value', 'execution', 'NAME:key=value,...') or a policy file; repeat for several (market m plays opponent m mod P); none = self-play")
     p.add_argument("--markets", type=int, default=1024)
     p.add_argument("--agents", type=int, default=4)
     p.add_argument("--max-step", type=int, default=256)

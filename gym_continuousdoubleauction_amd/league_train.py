@@ -209,6 +209,8 @@ def train_league_fused(env, iters=4, horizon=None, num_trainable=2, lr=5e-5, epo
     if getattr(env, "scripted", False):                              # (a scripted slot's sample record is no policy sample: it must not reach a loss)
         raise ValueError("train_league_fused does not take an env with scripted opponents attached: pass them as scripted_opponents=[...] (the league attaches its pool's "
                          "profiles itself) after clear_scripted()")
+    from .ppo import _refuse_stateful
+    _refuse_stateful(env, scripted_opponents, "train_league_fused(scripted_opponents=...)")
     attach, profiles = contextlib.nullcontext(), []
     if scripted_opponents is not None:
         from . import scripted as SC

@@ -639,7 +639,7 @@ class RolloutChains:
         self._joins = [torch.cuda.Event() for _ in range(G)]
         self.graphs = None
         self._have_obs, self._env_epoch = False, 0
-        self._script_checked = None
+        self._script_checked = self._stateful_checked = None
         self.use_graphs = bool(use_graphs)
         self.join_mode = "events"
         self._check_scripted_slots()                               # (raise before anything is captured; run() looks again when the env's scripts changed)
@@ -652,16 +652,22 @@ class RolloutChains:
             raise ValueError(f"the env's label tap holds {tap['rows']} rows, this rollout has a horizon of {self.T} steps: attach the tap with rows >= the horizon")
 
     def _check_scripted_slots(self):
-        """a scripted opponent may sit in opponent slots only (once per script epoch of the env): league chains - none below n_trainable; shared-policy chains built
-        with trained_slots = k - slots < k unscripted and every slot >= k scripted (the update reads the leading k records of every row and nothing else)"""
-        if not getattr(self.env, "scripted", False) or self._script_checked == self.env.script_epoch:
+        """a scripted or stateful opponent may sit in opponent slots only (once per script / stateful epoch of the env): league chains - none below n_trainable;
+        shared-policy chains built with trained_slots = k - slots < k named by neither table and every slot >= k by one of them (the update reads the leading k
+        records of every row and nothing else)"""
+        scripted, stateful = bool(getattr(self.env, "scripted", False)), bool(getattr(self.env, "stateful", False))
+        epochs = (getattr(self.env, "script_epoch", 0), getattr(self.env, "stateful_epoch", 0))
+        if not (scripted or stateful) or (self._script_checked, self._stateful_checked) == epochs:
             return
+        slots = self.env.scripted_slots()
+        if stateful:                                                # (a stateful slot is an opponent slot like a scripted one)
+            slots = ((slots != 0) | (self.env.stateful_slots() != 0)).astype(slots.dtype)
         if self.bank is not None:
-            if bool((self.env.scripted_slots()[:, :self.bank.n_trainable] != 0).any()):
+            if bool((slots[:, :self.bank.n_trainable] != 0).any()):
                 raise ValueError(f"a scripted opponent sits in a trainable slot (< n_trainable = {self.bank.n_trainable}): scripted modules play opponent slots only")
         elif self.trained_slots is not None:
-            check_trained_slots(self.env.scripted_slots(), self.trained_slots)
-        self._script_checked = self.env.script_epoch
+            check_trained_slots(slots, self.trained_slots)
+        self._script_checked, self._stateful_checked = epochs
 
     @property
     def counter(self):
@@ -725,6 +731,8 @@ class RolloutChains:
         self._graph_tape_epoch = getattr(self.env, "tape_epoch", 0)
         # ... and the scripted launches (or none) of the env's scripted opponents as attached now (CDAVecEnv.set_scripted / clear_scripted)
         self._graph_script_epoch = getattr(self.env, "script_epoch", 0)
+        # ... and the stateful launch (or none) of the env's stateful opponents as attached now (CDAVecEnv.set_stateful / clear_stateful)
+        self._graph_stateful_epoch = getattr(self.env, "stateful_epoch", 0)
         # ... and the order schedule's launch and tables (or none) as attached now (CDAVecEnv.set_order_schedule / clear_order_schedule)
         self._graph_schedule_epoch = getattr(self.env, "schedule_epoch", 0)
         # ... and the quote recorder's launch and ring (or none) as enabled now (CDAVecEnv.enable_quotes / disable_quotes)
@@ -753,6 +761,9 @@ class RolloutChains:
         if self.graphs is not None and self._graph_script_epoch != getattr(self.env, "script_epoch", 0):
             raise RuntimeError("the env's scripted opponents were attached or detached after this RolloutChains captured its graphs: they would replay the "
                                "launches of the earlier setting - build a new RolloutChains")
+        if self.graphs is not None and self._graph_stateful_epoch != getattr(self.env, "stateful_epoch", 0):
+            raise RuntimeError("the env's stateful opponents were attached or detached after this RolloutChains captured its graphs: they would replay the "
+                               "launches and tables of the earlier setting - build a new RolloutChains")
         if self.graphs is not None and self._graph_schedule_epoch != getattr(self.env, "schedule_epoch", 0):
             raise RuntimeError("the env's order schedule was attached, replaced or detached after this RolloutChains captured its graphs: they would replay the "
                                "launches and tables of the earlier setting - build a new RolloutChains")

@@ -533,6 +533,19 @@ def merged_objective(objective=None, **overrides):
     return {**PPO_DEFAULTS, **(objective or {}), **{k: v for k, v in overrides.items() if v is not None}}
 
 
+def _refuse_stateful(env, specs, what):
+    """Stateful opponents (stateful.py) are out of scope for the training loops: a resumable run would have to carry the state tensor in its checkpoint, and a
+    stateful slot's sample record is no policy sample.  ValueError for a stateful spec among `specs`, or an env with stateful opponents attached."""
+    from .stateful import is_stateful_spec
+    named = [str(o) for o in (specs or []) if is_stateful_spec(o)]
+    if named:
+        raise ValueError(f"{what} does not take stateful opponents ({', '.join(named)}): training against opponents with memory is out of scope - a resumable run "
+                         "would have to carry their state tensor; evaluate() and run_scripted() play them")
+    if getattr(env, "stateful", False):
+        raise ValueError(f"{what.split('(')[0]} does not take an env with stateful opponents attached: their records are no policy samples and their state tensor is in "
+                         "no checkpoint (clear_stateful() first)")
+
+
 def train_fused(env, iters=4, horizon=64, lr=5e-5, epochs=4, reward_scale=None, seed=0, log=print, use_graph=True, chains=4, minibatch=262144,
                 gamma=None, lam=None, clip=None, vf_coef=None, ent_coef=None, policy=None, keep=None, sub_batches=None, objective=None, recorder=None, info_markets=0,
                 allreduce=None, world=1, first_market=0, episode_metrics=True, strict_nav_check=True, state_dependent_log_std=False, hidden=(256, 256),
@@ -580,6 +593,7 @@ def train_fused(env, iters=4, horizon=64, lr=5e-5, epochs=4, reward_scale=None, 
     opponents is refused."""
     if getattr(env, "label_tap", None) is not None:                         # (a mixed-in label is no policy sample either)
         raise ValueError("train_fused does not take an env with a label tap attached: an action the tap mixed in is not a sample of the policy (clear_label_tap() first)")
+    _refuse_stateful(env, opponents, "train_fused(opponents=...)")
     attach = contextlib.nullcontext()
     if opponents is not None:
         if getattr(env, "scripted", False):

@@ -21,6 +21,8 @@ ACTION_KEYS = ("category", "size_mean", "size_sigma", "price", "price_offset")
 
 # what set_scripted keeps: the two resident device tables (slot_script i32 [N, A], profiles u8 [n, 64]), the Profile objects, the draws' keys, and the slot table on the host
 AttachedScripts = collections.namedtuple("AttachedScripts", "slot_script profiles_dev profiles seed market_index_base slots_host")
+# what set_stateful keeps: the three resident device tensors (slots i32 [N, A], profiles u8 [n, 64], state i64 [N, A, 4]), the Profile objects, the keys, the host slot table
+AttachedStateful = collections.namedtuple("AttachedStateful", "slot_table profiles_dev state profiles seed market_index_base slots_host")
 # what set_order_schedule keeps: the three resident device tables (sched_of i32 [N], step_offsets i64 [n_sched, S + 1], msgs u8 [total, 16]), the host form and the digest
 AttachedSchedule = collections.namedtuple("AttachedSchedule", "sched_of step_offsets msgs packed sched_of_host loop clear_step_counters digest")
 
@@ -51,6 +53,8 @@ class CDAVecEnv:
         self.order_tape_epoch = 0           # bumped by enable_order_tape / disable_order_tape: likewise for the order recorder's launch
         self.script_epoch = 0               # bumped by set_scripted / clear_scripted: graphs captured on this env's rollout chains hold the scripted launches (or none) of then
         self._script = None                 # set_scripted: an AttachedScripts (None while nothing is attached)
+        self.stateful_epoch = 0             # bumped by set_stateful / clear_stateful: likewise for the stateful launch (or none)
+        self._stateful = None               # set_stateful: an AttachedStateful (None while nothing is attached)
         self._schedule = None               # set_order_schedule: an AttachedSchedule (None while nothing is attached)
         self.label_epoch = 0                # bumped by set_label_tap / clear_label_tap (not by set_label_mix): captured graphs hold the tap's launch and buffers of their capture
         self.label_tap = None               # set_label_tap: a dict of the tap's tensors and settings (None while no tap is attached)
@@ -1353,7 +1357,11 @@ class CDAVecEnv:
         launch on the caller's stream, ordered after every group's last step, no host synchronisation.  out: a dict of the five [N, A] action tensors (ACTION_KEYS;
         optionally 'a_cont' f32 [N, A, 2], 'logp' f32 [N, A], 'record' f32 [N, A, 8]) written in place where a slot is scripted and left alone elsewhere; None =
         fresh tensors holding a pass everywhere else.  counter: an int, or an i64 [1] device tensor read on the device.  Nothing attached: nothing is written."""
-        first, n = self._market_range("scripted_actions", first_market, n_markets)
+        return self._law_actions("cda_scripted_actions", "scripted_actions", draw, counter, out, first_market, n_markets)
+
+    def _law_actions(self, entry, what, draw, counter, out, first_market, n_markets):
+        """scripted_actions / stateful_actions: the shared argument checks and the one native call (`entry`: cda_scripted_actions or cda_stateful_actions)"""
+        first, n = self._market_range(what, first_market, n_markets)
         if out is None:
             out = self._action_buffers()
         dts = {"category": torch.int32, "size_mean": torch.float32, "size_sigma": torch.float32, "price": torch.int32, "price_offset": torch.int32,
@@ -1372,8 +1380,8 @@ class CDAVecEnv:
         self.join()
         opt = lambda k: out[k].data_ptr() if k in out else None     # noqa: E731
         with torch.cuda.device(self.device):
-            check(lib().cda_scripted_actions(self._h, first, n, ctr.data_ptr() if ctr is not None else None, int(draw), *(out[k].data_ptr() for k in ACTION_KEYS),
-                                             opt("a_cont"), opt("logp"), opt("record"), self._stream()), "cda_scripted_actions")
+            check(getattr(lib(), entry)(self._h, first, n, ctr.data_ptr() if ctr is not None else None, int(draw), *(out[k].data_ptr() for k in ACTION_KEYS),
+                                        opt("a_cont"), opt("logp"), opt("record"), self._stream()), entry)
         if ctr is not None:
             ctr.record_stream(torch.cuda.current_stream(self.device))
         return out
@@ -1383,19 +1391,23 @@ class CDAVecEnv:
         device, no host synchronisation inside the loop.  others: what the slots that are not scripted play - 'pass', or 'random' = the uniform random stream
         (random_actions_device keyed action_seed and the draw number).  The taker's draw number of step k is draw0 + k; draw0 = None continues where the last
         run_scripted stopped.  Returns step()'s tuple of the last step."""
-        if self._script is None:
-            raise RuntimeError("run_scripted() needs scripted opponents: call set_scripted() first")
+        if self._script is None and self._stateful is None:
+            raise RuntimeError("run_scripted() needs scripted opponents: call set_scripted() (or set_stateful()) first")
         if others not in ("pass", "random"):
             raise ValueError(f"others must be 'pass' or 'random', got {others!r}")
         d = int(getattr(self, "_script_draw", 0) if draw0 is None else draw0)
         acts = self._action_buffers()
+        base = (self._script if self._script is not None else self._stateful).market_index_base
         ret = None
         for k in range(int(n_steps)):
             if others == "random":
                 with torch.cuda.device(self.device):
-                    check(lib().cda_random_actions(int(action_seed) & (2 ** 64 - 1), self._script.market_index_base, d + k, 1, self.n_markets, self.num_agents,
+                    check(lib().cda_random_actions(int(action_seed) & (2 ** 64 - 1), base, d + k, 1, self.n_markets, self.num_agents,
                                                    *(acts[key].data_ptr() for key in ACTION_KEYS), self._stream()), "cda_random_actions")
-            self.scripted_actions(draw=d + k, out=acts)
+            if self._script is not None:
+                self.scripted_actions(draw=d + k, out=acts)
+            if self._stateful is not None:                            # (behind the stateless family, as the rollout chains order them)
+                self.stateful_actions(draw=d + k, out=acts)
             ret = self.step(acts)
         self._script_draw = d + int(n_steps)
         return ret
@@ -1480,6 +1492,64 @@ class CDAVecEnv:
         for t in (slot_t, prof_t) + ((ctr,) if ctr is not None else ()):
             t.record_stream(cur)
         return out
+
+    # ------------------------------------------------------------------ scripted opponents with memory: trend, value, execution (stateful.py states the laws)
+    @property
+    def stateful(self):
+        return self._stateful is not None
+
+    def set_stateful(self, slot_table, profiles, seed=0, market_index_base=0):
+        """Attach stateful opponents (include/cda.h cda_stateful_attach): slot_table int [N, A], 0 = the slot is not stateful, 1 + k = it plays profiles[k];
+        profiles: 1 .. 16 stateful.Profile objects (or names / 'NAME:key=value' strings).  The two tables and a ZEROED state tensor i64 [N, A, 4] (stateful_state())
+        become resident tensors the env keeps; rollout chains and run_scripted() then play the laws, behind the stateless family's launch.  `seed` keys the value law's
+        draws, market_index_base + market is the market's index in them.  A slot that set_scripted names at this moment is refused (ValueError).  While attached the
+        one-launch policy step is off.  A snapshot() does not carry the state: clone stateful_state() beside it and copy_ it back after restore()."""
+        from .stateful import MAX_PROFILES, STATE_WORDS, parse_profile, profiles_array
+        profs = [parse_profile(p) for p in profiles]
+        if not 1 <= len(profs) <= MAX_PROFILES:
+            raise ValueError(f"between 1 and {MAX_PROFILES} profiles, got {len(profs)}")
+        slots = np.ascontiguousarray(np.asarray(slot_table.detach().cpu().numpy() if hasattr(slot_table, "detach") else slot_table).astype(np.int64))
+        if slots.shape != (self.n_markets, self.num_agents):
+            raise ValueError(f"slot_table must have shape {(self.n_markets, self.num_agents)}, got {slots.shape}")
+        if slots.min() < 0 or slots.max() > len(profs):
+            raise ValueError(f"slot_table values must lie in 0 .. {len(profs)} (0 = not stateful, 1 + k = profile k)")
+        if self._script is not None and bool(((slots != 0) & (self._script.slots_host != 0)).any()):
+            raise ValueError("a slot is named by set_scripted and by set_stateful: a slot plays one family (clear_scripted() or re-attach the scripts without it)")
+        slot_t = torch.from_numpy(slots.astype(np.int32)).to(self.device)
+        prof_t = torch.from_numpy(profiles_array(profs).view(np.uint8).reshape(len(profs), 64).copy()).to(self.device)
+        state_t = torch.zeros((self.n_markets, self.num_agents, STATE_WORDS), dtype=torch.int64, device=self.device)
+        self.sync()
+        with torch.cuda.device(self.device):
+            check(lib().cda_stateful_attach(self._h, slot_t.data_ptr(), prof_t.data_ptr(), len(profs), state_t.data_ptr(), int(seed) & (2 ** 64 - 1),
+                                            int(market_index_base) & (2 ** 64 - 1)), "cda_stateful_attach")
+        self._stateful = AttachedStateful(slot_t, prof_t, state_t, profs, int(seed) & (2 ** 64 - 1), int(market_index_base) & (2 ** 64 - 1), slots.astype(np.int32))
+        self.stateful_epoch += 1
+
+    def clear_stateful(self):
+        self.sync()
+        check(lib().cda_stateful_detach(self._h), "cda_stateful_detach")
+        self._stateful = None
+        self.stateful_epoch += 1
+
+    def stateful_slots(self):
+        """the attached stateful slot table as a host array i32 [N, A] (zeros while nothing is attached)"""
+        return self._stateful.slots_host if self._stateful is not None else np.zeros((self.n_markets, self.num_agents), np.int32)
+
+    def stateful_profiles(self):
+        return list(self._stateful.profiles) if self._stateful is not None else []
+
+    def stateful_state(self):
+        """the RESIDENT state tensor i64 [N, A, 4] - the one k_stateful_actions reads and writes at every step (word 0: last t_step | tag << 32).  A caller clones it
+        and copy_s the clone back to carry the slots' memory across snapshot() / restore(); zeroing it makes every slot start fresh at its next step."""
+        if self._stateful is None:
+            raise RuntimeError("stateful_state() needs stateful opponents: call set_stateful() first")
+        return self._stateful.state
+
+    def stateful_actions(self, draw=0, counter=0, out=None, first_market=0, n_markets=None):
+        """Every stateful slot's state advanced on the markets' state NOW, and its action (include/cda.h cda_stateful_actions; stateful.play is its specification): one
+        launch, scripted_actions' arguments and conventions.  A second call before the next step changes nothing and answers the same.  Nothing attached: nothing is
+        written."""
+        return self._law_actions("cda_stateful_actions", "stateful_actions", draw, counter, out, first_market, n_markets)
 
     # ------------------------------------------------------------------ snapshots, forks and resumable runs
     def snapshot(self, first=0, n=None):

@@ -1076,6 +1076,41 @@ int cda_label_actions(cda_env* env, int32_t first_market, int32_t n_markets, con
 int cda_label_mix_host(uint64_t seed, uint64_t counter, const uint64_t* market_host, const uint32_t* draw_host, const uint32_t* agent_host, int64_t n, uint64_t mix_q32,
                        int32_t* played_out);
 
+/* ---- scripted opponents with memory: trend, value and execution laws on per-slot state -----------------------------------------------------
+ * A sibling family of the scripted opponents above: the laws, their 64-byte cda_stateful_profile, the per-slot state (CDA_STATEFUL_WORDS = 4 int64, word 0 the
+ * header: last t_step | tag) and the one update rule are stated once, in include/cda_stateful_agents.h (cda_stateful_advance, cda_stateful_decide).  The view is
+ * cda_script_view as it is.  The stateless family's entry points, kernels and profile are untouched; with nothing stateful attached an env launches what it launched.
+ *   cda_stateful_attach   slot_dev i32 [N][A] (device): 0 = the slot is not stateful, 1 + k = it plays profiles_dev[k]; profiles_dev: n_profiles (1 .. 16) profiles
+ *                         (device, 8-B aligned); state_dev i64 [N][A][4] (device, 32-B aligned: CDA_ERR_INVALID otherwise), zeroed by the caller for a fresh start.
+ *                         Both tables are read back and vetted first: an invalid profile or a slot value outside 0 .. n_profiles returns CDA_ERR_INVALID and changes
+ *                         nothing (synchronous).  The env KEEPS the three pointers - the caller's resident tensors - so a captured graph stays valid while their
+ *                         contents change; `seed` keys the value law's draws, market_index_base + market is the market's global index in them.
+ *   cda_stateful_detach   forgets them.  Every attach and detach moves cda_stateful_epoch; while a table is attached cda_policy_step_supported and
+ *                         cda_net_step_supported answer 0, as for scripts.
+ *   cda_stateful_actions  ONE launch on `stream` (csrc/cda_stateful.inc k_stateful_actions), a wave per market of the range: every stateful slot's state advanced on
+ *                         the market's state NOW and its action written, into the five FULL [N][A] action arrays and - where given - a_cont, logp and the sample
+ *                         record exactly as cda_scripted_actions writes them for a scripted slot.  Slots that are not stateful keep their bytes, actions and state;
+ *                         the arena is only read.  A second call at the same t_step changes no state and writes the same action.  The value law's draw is keyed
+ *                         (seed, *counter_dev or 0 when NULL, global market, draw, agent).  Nothing attached: CDA_OK, no launch.
+ *                         cda_scripted_step_actions - the one call every rollout chain makes between the policy launch and the step - issues this launch, with
+ *                         draw = t, BEHIND what it issues for the stateless family: a slot both tables name plays its stateful law.
+ *   cda_stateful_advance_host   the same two functions on host arrays, no device: item i plays profiles_host[profile_index_host[i]] (its tag: 1 + that index) on
+ *                         views_host[i] and the four words state_inout[4 i ..], advanced in place, with the key (seed, counter, market_host[i], draw_host[i],
+ *                         agent_host[i]).  cda_stateful_profile_check_host: CDA_OK iff every profile is valid.
+ * Not covered: training loops that attach stateful opponents themselves (a resumable run would have to carry the state tensor), the label tap with stateful experts,
+ * data-parallel runs, the dict facades, the state inside cda_snapshot_* blobs (the caller clones and restores its own tensor). */
+int cda_stateful_attach(cda_env* env, const int32_t* slot_dev, const void* profiles_dev, int32_t n_profiles, int64_t* state_dev, uint64_t seed, uint64_t market_index_base);
+int cda_stateful_detach(cda_env* env);
+int64_t cda_stateful_epoch(const cda_env* env);
+int cda_stateful_attached(const cda_env* env);
+int cda_stateful_actions(cda_env* env, int32_t first_market, int32_t n_markets, const int64_t* counter_dev, int64_t draw,
+                         int32_t* category, float* size_mean, float* size_sigma, int32_t* price, int32_t* price_offset,
+                         float* a_cont, float* logp, float* record, void* stream);
+int cda_stateful_advance_host(const void* profiles_host, int32_t n_profiles, const int32_t* profile_index_host, const void* views_host, int64_t n,
+                              uint64_t seed, uint64_t counter, const uint64_t* market_host, const uint32_t* draw_host, const uint32_t* agent_host, int64_t* state_inout,
+                              int32_t* category, float* size_mean, float* size_sigma, int32_t* price, int32_t* price_offset);
+int cda_stateful_profile_check_host(const void* profiles_host, int32_t n_profiles);
+
 /* ---- order streams: explicit orders into every market of a range, in one launch ------------------------------------------------------------
  * cda_submit_orders plays, for every market of [first_market, first_market + n_markets), the messages msgs_dev[offsets_dev[i] .. offsets_dev[i + 1])
  * (i counts from the range's first market) in order: ONE asynchronous launch on `stream`, a wave per market, the market's record loaded once and
